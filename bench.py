@@ -42,10 +42,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # a process setting, made by the entry point before the first device call (gdmix_amd/gdmix.py: process_defaults)
 
 SPREAD_DEFAULT = int(os.environ.get("GDMIX_RE_SPREAD", "4"))   # queues the large size classes are dealt over (gdmix_re_set_spread)
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak
 
 
 def parse():
@@ -103,7 +102,15 @@ def parse():
     ap.add_argument("--detail-file", default="", help="where the full result goes (default gpurun_out/bench_detail.json); the stdout line is the short form")
     ap.add_argument("--print-detail", action="store_true", help="also print the full result as one JSON line on stderr")
     ap.add_argument("--ml-entities", type=int, default=0, help="strong legs: keep this many MovieLens entities (tests at reduced size; 0 = all)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's batch) as DIR/<name>.npy, float32 / float64, "
+                         "a fixed seeded sample of each array larger than its cap, at most 64 MB in all (dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.scaling == "strong":
+        ap.error("--dump-outputs writes the weak-scaling step's outputs; it does not apply to --scaling strong")
+    return a
 
 
 WORKLOADS = {
@@ -727,6 +734,52 @@ RESULT_FD = None        # the process's original stdout once main() has pointed 
 COMPACT_LIMIT = 4096   # the driver keeps the tail of stdout: the result line has to be short (BENCH_r04: a 38.5 KB line was cut, parsed = null)
 
 
+DUMP_SEED = 20240601                      # the sample of a large output is drawn from this seed and the array's length only
+DUMP_CAPS = {"entity": 1 << 19, "coef": 1 << 20, "feature": 1 << 19}   # elements kept per index space: 50 MiB at the caps
+DUMP_LIMIT = 64 << 20
+
+
+def _dump_index(n, cap, device):
+    """The positions of an array of length n that are written: all of them, or `cap` of them drawn without replacement by a
+    generator seeded with DUMP_SEED and n (the same positions in every run over the same batch), ascending."""
+    import torch
+    if n <= cap:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng([DUMP_SEED, n]).choice(n, size=cap, replace=False))
+    return idx, torch.from_numpy(idx).to(device)
+
+
+def dump_outputs(path, packed, res):
+    """--dump-outputs: what the timed step (pack + solve) hands its caller, read back after its last step, as path/<name>.npy.
+    Per entity: status, nit, nfev (float32, exact) and fval, gnorm (float64); per coefficient: theta, theta_thr (float64); per
+    local feature: unique_global (float64, exact). Each index space is written whole up to its cap in DUMP_CAPS, beyond it at a
+    seeded sample of positions; <space>_index.npy holds the positions written. Returns {name: shape}."""
+    import torch
+    sizes = {"entity": packed.E, "coef": packed.P, "feature": packed.D}
+    arrays = {}
+    for space, n in sizes.items():
+        idx, idx_dev = _dump_index(n, DUMP_CAPS[space], res.theta.device)
+        arrays[f"{space}_index"] = idx.astype(np.float64)
+        if space == "entity":
+            for k in ("status", "nit", "nfev"):
+                arrays[k] = getattr(res, k).index_select(0, idx_dev).cpu().numpy().astype(np.float32)
+            for k in ("fval", "gnorm"):
+                arrays[k] = getattr(res, k).index_select(0, idx_dev).cpu().numpy()
+        elif space == "coef":
+            for k in ("theta", "theta_thr"):
+                arrays[k] = getattr(res, k)[:n].index_select(0, idx_dev).cpu().numpy()
+        else:
+            arrays["unique_global"] = packed.unique_global().index_select(0, idx_dev).to(torch.float64).cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+        np.save(os.path.join(path, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def _get(d, *path):
     for k in path:
         if not isinstance(d, dict) or d.get(k) is None:
@@ -1013,6 +1066,8 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0              # ... and until the slowest rank is done
+    if a.dump_outputs and rank == 0:           # (before the legs below solve into the same result buffers)
+        dump_outputs(a.dump_outputs, packed, res)
     status = res.status
     converged = int(((status >= 0) & (status <= 2)).sum().item())
     per_rank = None

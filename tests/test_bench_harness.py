@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -210,3 +211,71 @@ def test_projection_of_an_eight_rank_job_on_one_device(tmp_path):
     assert all(len(r["plain_ms"]) == 8 and len(r["rebalanced_ms"]) == 8 and r["imbalance"] >= 1.0 for r in pr["rounds"])
     short = line["_short"]["summary"]["c5_full_share"]
     assert short["entities"] == fs["entities"] and short["rounds"] == 3
+
+
+def _fake_step(E, D, seed):
+    """A packed batch and a solve result as dump_outputs reads them, on the host."""
+    import types
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    P = D + E
+    res = types.SimpleNamespace(theta=torch.randn(P, generator=g, dtype=torch.float64), theta_thr=torch.randn(P, generator=g, dtype=torch.float64),
+                                fval=torch.rand(E, generator=g, dtype=torch.float64), gnorm=torch.rand(E, generator=g, dtype=torch.float64),
+                                nit=torch.randint(0, 100, (E,), generator=g, dtype=torch.int32),
+                                nfev=torch.randint(0, 200, (E,), generator=g, dtype=torch.int32),
+                                status=torch.randint(0, 3, (E,), generator=g, dtype=torch.int32))
+    ug = torch.randint(0, 1 << 30, (D,), generator=g, dtype=torch.int32)
+    packed = types.SimpleNamespace(E=E, D=D, P=P, unique_global=lambda: ug)
+    return packed, res
+
+
+def test_dump_outputs_writes_float_arrays_a_fixed_sample_and_stays_under_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: every file float32 / float64; an index space larger than its cap is written at the same seeded positions in
+    every run (the sample depends on the array's length only), the values at those positions are the array's; at the real caps
+    the whole dump fits in 64 MB."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert sum(c * w for c, w in zip((bench.DUMP_CAPS["entity"], bench.DUMP_CAPS["coef"], bench.DUMP_CAPS["feature"]), (36, 24, 16))) \
+        <= bench.DUMP_LIMIT == 64 << 20
+    monkeypatch.setattr(bench, "DUMP_CAPS", {"entity": 50, "coef": 300, "feature": 1000})
+    packed, res = _fake_step(E=200, D=400, seed=1)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), packed, res)
+    names = {"entity_index", "status", "nit", "nfev", "fval", "gnorm", "coef_index", "theta", "theta_thr", "feature_index", "unique_global"}
+    assert set(shapes) == names and {f[:-4] for f in os.listdir(tmp_path / "a")} == names
+    ld = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in ld.values())
+    ei, ci, fi = (ld[k].astype(np.int64) for k in ("entity_index", "coef_index", "feature_index"))
+    assert len(ei) == 50 and len(np.unique(ei)) == 50 and np.all(np.diff(ei) > 0) and ei[-1] < 200
+    assert len(ci) == 300 and np.all(np.diff(ci) > 0) and ci[-1] < 600
+    assert np.array_equal(fi, np.arange(400))                        # under its cap: the whole array
+    assert np.array_equal(ld["nit"], res.nit.numpy()[ei].astype(np.float32)) and np.array_equal(ld["fval"], res.fval.numpy()[ei])
+    assert np.array_equal(ld["theta_thr"], res.theta_thr.numpy()[ci])
+    assert np.array_equal(ld["unique_global"], packed.unique_global().numpy().astype(np.float64))
+    packed2, res2 = _fake_step(E=200, D=400, seed=2)                  # another run: other values, the same positions
+    bench.dump_outputs(str(tmp_path / "b"), packed2, res2)
+    for k in ("entity_index", "coef_index", "feature_index"):
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), ld[k])
+
+
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"], timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_runs_agree(tmp_path):
+    """Two runs with the same arguments solve the same inputs: the dumped outputs agree, and they are the timed step's (every entity
+    of the batch converged, one file per output)."""
+    args = ["--entities", "20000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-fe", "--no-cli",
+            "--no-other-workloads", "--no-alone", "--project-ranks", "0", "--c5-full-entities", "0"]
+    dumps = []
+    for run in ("a", "b"):
+        line = _line(args + ["--dump-outputs", str(tmp_path / run)], tmp_path)
+        assert line["steps"] == 3 and line["config"]["entities_per_gpu"] == 20000
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)})
+    a, b = dumps
+    assert set(a) == set(b) and {"theta", "theta_thr", "status", "nit", "fval", "unique_global"} <= set(a)
+    assert len(a["status"]) == 20000 and np.all((a["status"] >= 0) & (a["status"] <= 2))
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].shape == b[k].shape, k
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-12, atol=0, err_msg=k)

@@ -10,7 +10,7 @@ minimum. `--tests` first runs the GPU parity tests matching the expression. `uns
 
 Recipes (what round 4's scripts were; DESIGN.md / docs/rounds cite the results):
     spread of the size classes     --env GDMIX_RE_SPREAD=0,2,3,4 --workloads c2,c5share
-    hardware queues per process    --env GPU_MAX_HW_QUEUES=4,8,16 --legs e2e --fields ms_per_step,detail.host_handover.entities_per_s
+    hardware queues per process    --env GPU_MAX_HW_QUEUES=1,2 --legs e2e --fields ms_per_step,detail.host_handover.entities_per_s
     same-XCD team barrier          --env GDMIX_RE_XCD_BARRIER=0,1 --workloads zipf,c5share --tests "team_tiers or device_wide"
     LDS vectors of the team kernel --env GDMIX_TEAM_ARENA_KB=0,200 --workloads zipf,c5share
     bitmap pack                    --env GDMIX_PACK_BITMAP=0,1 --workloads c2,ml20m_user --tests "pack"

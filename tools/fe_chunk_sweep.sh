@@ -1,7 +1,7 @@
 #!/bin/bash
 # fixed effect: column / row pass time against the unit length (GDMIX_FE_CHUNK), uniform and Zipf columns
 mkdir -p gpurun_out/r03h
-cd /root/repo
+cd "$(dirname "$0")/.."
 : > gpurun_out/r03h/fe_sweep.txt
 for c in 8192 16384 32768 62500 125000; do for m in uniform zipf; do
   echo "chunk $c $m" >> gpurun_out/r03h/fe_sweep.txt

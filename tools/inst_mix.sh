@@ -4,7 +4,7 @@
 # per kernel: SQ_INSTS_VALU split into fp64 add / mul / fma / transcendental, int32, int64, conversions and the rest (moves, DPP moves,
 # compares, selects: what the counters do not name), and the lanes an instruction had active (SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU / 4).
 export GDMIX_BENCH_LINE=full GDMIX_RE_SPREAD=0 PYTHONPATH=.:tests
-cd /tmp && export TMPDIR=/tmp && cd ${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd); cd /tmp && export TMPDIR=/tmp && cd "$R"
 O=gpurun_out/${1:?out}; W=${2:-c2}
 CMD="python bench.py --steps 5 --warmup 2 --workload $W --no-cpu-baseline --no-e2e --no-fe --no-cli --no-other-workloads --no-alone --project-ranks 0"
 rm -rf $O; mkdir -p $O

@@ -6,7 +6,7 @@
 #   2. for the builds listed in [pmc-lib names]: the LDS counters of the solve kernels (SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS ...)
 # then tools/ab.py over all builds for the step itself (three rounds, minimum and every run). Summary: gpurun_out/<out-name>/summary.txt
 export GDMIX_BENCH_LINE=full GDMIX_ALLOW_STALE_LIB=1 PYTHONPATH=.:tests
-cd /tmp && export TMPDIR=/tmp && cd ${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd); cd /tmp && export TMPDIR=/tmp && cd "$R"
 O=gpurun_out/${1:?out}; W=${2:-c2}; LIBS=${3:-cur}; PMC=${4:-}
 rm -rf $O; mkdir -p $O
 cp gdmix_amd/libgdmix_re.so $O/lib_cur_keep.so; cp gdmix_amd/libgdmix_re.so gdmix_amd/lib_cur.so

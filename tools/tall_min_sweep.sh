@@ -2,7 +2,7 @@
 # From how many samples on does a skinny entity (p <= 64) go to the tall kernels instead of a group class?  (gdmix_re_set_tall_min_n, default 32)
 #   bash tools/tall_min_sweep.sh <out-name> "32 64 96 129 257" [reps]
 # per value: MovieLens-20M per-user and per-movie as ONE batch (bench.py --workload ml20m_*), and the 8-share projection of both
-cd /tmp && export TMPDIR=/tmp && cd ${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd); cd /tmp && export TMPDIR=/tmp && cd "$R"
 export GDMIX_BENCH_LINE=full PYTHONPATH=.:tests
 O=gpurun_out/${1:?out}; VALS=${2:-"32 64 129"}; REPS=${3:-2}
 rm -rf $O; mkdir -p $O

@@ -1,7 +1,7 @@
 #!/bin/bash
 # per-phase times of the tall kernel (build with -DGDMIX_TALL_PROFILE into a side library)
 mkdir -p gpurun_out/r03d
-cd /root/repo
+cd "$(dirname "$0")/.."
 cp gdmix_amd/libgdmix_re.so /tmp/lib_keep.so
 GDMIX_EXTRA_FLAGS="-DGDMIX_TALL_PROFILE $TALL_EXTRA" python -m gdmix_amd.build --force > /dev/null 2>&1 || exit 1
 for w in ${TALL_WORKLOADS:-ml20m_user ml20m_movie}; do
