@@ -17,20 +17,25 @@ without WORLD_SIZE in the environment, `--gpus N` re-executes the script under t
 ranks, one device each (spawn_ranks), and a WORLD_SIZE that differs from --gpus is an error.
 
 `--workload` picks another BASELINE configuration for the step: ml20m_user / ml20m_movie (C3: MovieLens-20M
-entity sizes), c5share (C5: one GPU's share, 4M Zipf entities generated on the device), zipf, ...; the
-default C2 run also measures ml20m_user, ml20m_movie and c5share briefly and reports them under
-detail.workloads (--no-other-workloads skips that; it is never part of `value`).
+entity sizes), c5share (C5: one GPU's share, 4M Zipf entities generated on the device), zipf, ...
 
-ONE population over the ranks (BASELINE configs[2] and [4]; bench_strong.py): with --gpus N > 1 the default run also measures three
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the result line: nothing else.
+Everything else the benchmark measures runs only with --full, after the timed steps and never part of `value` (each leg
+keeps its own --no-... switch): the per-class roofline, the same step with the size classes one after another, the CPU baseline,
+the hand-over, scoring, fixed-effect, CLI and chain legs, and for the C2 run ml20m_user, ml20m_movie and c5share briefly
+(detail.workloads) and the strong-scaling legs below.
+
+ONE population over the ranks (BASELINE configs[2] and [4]; bench_strong.py): with --full and --gpus N > 1 the run also measures three
 populations split the reference's way — entity -> partition by the Java hash of its decimal id, partition -> rank by partitions[rank::N] —
 plain and through the re-balancer (top-level `strong_scaling`; `--scaling strong --workload c5|ml20m_user|ml20m_movie` makes one of them
-the headline); with --gpus 1 it solves the shares of an 8-rank job one after another on this device (detail.strong_projection: the data
-path has no collective, so max over shares is the job time apart from barriers — labelled a projection), including the first
-per-partition rounds of the C5 job, the granularity at which the product path re-balances.
+the headline, the re-balanced run and the C5 partition rounds with --full); with --full and --gpus 1 it solves the shares of an 8-rank job
+one after another on this device (detail.strong_projection: the data path has no collective, so max over shares is the job time apart
+from barriers — labelled a projection), including the first per-partition rounds of the C5 job, the granularity at which the product
+path re-balances.
 
-One JSON line is printed by rank 0. `roofline` is the HBM roofline of the dominant kernel
-(the size-class launch that takes the largest share of a step) by the algorithmic-bytes formula of SURVEY.md §8(d); `cpu_baseline` times the
-CPU oracle (oracle/re_oracle.c, a port) on a bounded sample on this box's host cores.
+One JSON line is printed by rank 0. With --full, `roofline` is the HBM roofline of the dominant kernel
+(the size-class launch that takes the largest share of a step) by the algorithmic-bytes formula of SURVEY.md §8(d) and `cpu_baseline` times the
+CPU oracle (oracle/re_oracle.c, a port) on a bounded sample on the host's cores; a plain run leaves both null.
 """
 import argparse
 import json
@@ -56,6 +61,9 @@ def parse():
     ap.add_argument("--mean-n", type=int, default=16)
     ap.add_argument("--k", type=int, default=4)
     ap.add_argument("--dim", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: roofline, cpu_baseline and the side legs (the --no-... switches "
+                         "below turn single legs off); without it a run times its steps and prints the result line only")
     ap.add_argument("--cpu-sample", type=int, default=0, help="entities per pass of the CPU baseline (0 = 200k)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive hand-over measurement")
@@ -80,23 +88,23 @@ def parse():
                     help="c2 (default, the configuration BASELINE.json's metric is quoted on for one GPU) or another of BASELINE's "
                          "configurations at its own entity sizes: " + "; ".join(f"{k} = {v}" for k, v in WORKLOADS.items()))
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip detail.workloads: C3 (MovieLens-20M per-user / per-movie) and C5's per-GPU share, two steps each, next to the C2 headline")
+                    help="--full: skip detail.workloads: C3 (MovieLens-20M per-user / per-movie) and C5's per-GPU share, two steps each, next to the C2 headline")
     ap.add_argument("--c5-entities", type=int, default=4_000_000, help="entities of the c5share workload per GPU (C5's share is 12.5 M)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): every rank owns its own batch, the headline of the bench contract. strong: ONE population split over "
                          "the ranks by the reference's partition hash and partitions[rank::ranks] (bench_strong.py); --workload picks "
                          "ml20m_user / ml20m_movie / c5 (default c5), `value` is that job's entities/s")
     ap.add_argument("--no-strong", action="store_true",
-                    help="with --gpus N > 1 the default run also measures the three strong-scaling populations (top-level `strong_scaling`); skip that")
+                    help="with --full and --gpus N > 1 the run also measures the three strong-scaling populations (top-level `strong_scaling`); skip that")
     ap.add_argument("--no-rebalance", action="store_true", help="strong-scaling legs: skip the run through the re-balancer")
     ap.add_argument("--rebalance-tolerance", type=float, default=0.02,
                     help="strong-scaling legs: ranks within (1 + tolerance) x the mean cost neither send nor receive (the product's default is 0.05)")
     ap.add_argument("--strong-steps", type=int, default=4, help="timed steps of each strong-scaling / projection leg (after two warm-up steps)")
     ap.add_argument("--project-ranks", type=int, default=8,
-                    help="--gpus 1, default workload: also solve the shares of an N-rank job one after another on this GPU "
+                    help="--full, --gpus 1, default workload: also solve the shares of an N-rank job one after another on this GPU "
                          "(detail.strong_projection; 0 = skip)")
     ap.add_argument("--c5-full-entities", type=int, default=100_000_000,
-                    help="--gpus 1, default workload: BASELINE configs[4] at its real per-GPU share — worker 0's 128 partitions of ONE population of this "
+                    help="--full, --gpus 1, default workload: BASELINE configs[4] at its real per-GPU share — worker 0's 128 partitions of ONE population of this "
                          "many Zipf-sized entities in 1 024 partitions, one partition per round (detail.c5_full_share; 0 = skip)")
     ap.add_argument("--c5-full-rounds", type=int, default=16, help="rounds of the whole 8-worker job projected on this device, plain and with the re-balancing plan applied")
     ap.add_argument("--detail-file", default="", help="where the full result goes (default gpurun_out/bench_detail.json); the stdout line is the short form")
@@ -711,11 +719,13 @@ def _fits(w, a, world, coll_dev):
 
 
 def strong_main(a, rank, world, solver, opts, coll_dev, backend):
-    """--scaling strong: the headline is ONE population split over the ranks (bench_strong.py)."""
+    """--scaling strong: the headline is ONE population split over the ranks (bench_strong.py); the re-balanced run of the same
+    share and C5's per-partition rounds come with --full."""
     import bench_strong
     name = a.workload if a.workload in bench_strong.STRONG_WORKLOADS else "c5"
+    extras = {"rebalance": not a.no_rebalance} if a.full else {"rebalance": False, "rounds": 0}
     r = bench_strong.strong_leg(name, rank, world, solver, opts, coll_dev, a.c5_entities, steps=a.steps, warmup=a.warmup,
-                                rebalance=not a.no_rebalance, ml_entities=a.ml_entities or None, tolerance=a.rebalance_tolerance)
+                                ml_entities=a.ml_entities or None, tolerance=a.rebalance_tolerance, **extras)
     if rank == 0:
         line = {"metric": "random-effect entities converged/sec", "value": round(r["entities_per_s"], 1), "unit": "entities/s",
                 "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": r["ms"], "higher_is_better": True,
@@ -1084,10 +1094,11 @@ def main():
     else:
         converged_all = converged
     value = converged_all * a.steps / dt
+    # ---- --full from here on: what a plain run does not need for its result line ----
     # clocks and power WHILE the device works (outside the timed region): rocm-smi is asked from a second thread while this one keeps
     # solving the same batch; the state at the end of the whole run (idle clocks) is recorded too
     gpu_load_state = None
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         import threading
         box = {}
         th = threading.Thread(target=lambda: box.update(state=gpu_state()))
@@ -1104,7 +1115,7 @@ def main():
     # would alone — a kernel's own roofline figure needs its duration alone
     saved = (kernel_ms.copy(), pack_ms, solve_ms, list(step_wall))
     alone_cls_ms, alone_solve_ms = kernel_ms / max(1, a.steps), solve_ms / max(1, a.steps)    # (--no-alone, or spread off: the timed steps themselves)
-    if not a.no_alone and SPREAD_DEFAULT > 1:
+    if a.full and not a.no_alone and SPREAD_DEFAULT > 1:
         kernel_ms = np.zeros(NUM_CLASSES)
         solve_ms = 0.0
         solver.set_spread(0)
@@ -1124,7 +1135,7 @@ def main():
     # (profiles/r04_host_path.txt: the same leg alone, with and without round 3's side stream)
     p_host = int(packed.P)
     th_host = out["theta_thr"]
-    c2_legs = a.workload == "c2" and world == 1
+    c2_legs = a.full and a.workload == "c2" and world == 1
     # SURVEY.md §8(d) metric (i) to the letter: "resident ragged-CSR batch -> theta resident on host". The headline step ends with
     # theta in HBM (config.step says so); this is the same step plus the copy of the thresholded coefficients (float64) and the
     # status words into page-locked host memory, serial on one stream (the hand-over leg below overlaps it with the next partition)
@@ -1154,7 +1165,7 @@ def main():
         e2e = host_handover(batch, opts, local_rank, p_host)
     # the scoring pass over the same resident batch (the path's HBM-bound stream; not part of `value`)
     score = None
-    if not a.no_e2e and world == 1:
+    if a.full and not a.no_e2e and world == 1:
         th = th_host
         for _ in range(2):
             solver.score(packed, th)
@@ -1181,7 +1192,7 @@ def main():
             cli_c5 = cli_shape_leg("c5", a.cli_c5_entities)
             cli_movie = cli_shape_leg("ml20m_movie", None)
     others = None
-    if a.workload == "c2" and not a.no_other_workloads:
+    if a.full and a.workload == "c2" and not a.no_other_workloads:
         del res
         res = None
         others = other_workloads_leg(a, rank, world, solver, opts, coll_dev)
@@ -1189,7 +1200,7 @@ def main():
 
     # ---- ONE population split over the ranks (BASELINE configs[2] and [4]): measured with ranks, projected on one GPU ----
     strong = projection = None
-    if a.workload == "c2" and not a.no_other_workloads:
+    if a.full and a.workload == "c2" and not a.no_other_workloads:
         import bench_strong
         res = None
         torch.cuda.empty_cache()
@@ -1204,7 +1215,7 @@ def main():
         solver.set_timing(True)
         res = solver.solve(packed, opts, out=out)
     c5_full = None
-    if a.workload == "c2" and world == 1 and not a.no_other_workloads and a.c5_full_entities > 0:
+    if a.full and a.workload == "c2" and world == 1 and not a.no_other_workloads and a.c5_full_entities > 0:
         import bench_strong
         res = None
         torch.cuda.empty_cache()
@@ -1218,113 +1229,115 @@ def main():
         res = solver.solve(packed, opts, out=out)
 
     if rank == 0:
-        # ---- roofline of the dominant kernel = the size-class launch with the largest share of a step ----
-        n, z = wl.n, wl.z
-        p = np.diff(packed.coef_ptr_host())
-        b_e = 8.0 * z + 16.0 * n + 8.0 * p + 32.0                    # B(e), SURVEY.md §8(d)
-        alg_bytes = float(b_e.sum())
-        # parity classes of SURVEY.md §8(d): W = both labels present (a finite optimum exists with the unregularised intercept),
-        # D = all labels equal (the solver runs until the gradient test passes; only invariants are comparable)
-        well_posed = int(((wl.ones > 0) & (wl.ones < n)).sum())
         classes = solver.class_counts(packed)
-        cls = packed._view(packed.c.cls_tmp, packed.E, torch.int32).cpu().numpy()
-        cls_ms = kernel_ms / a.steps
-        # a class that has entities and no launch of its own ran with the class behind it (a small lean tall class, re_api.hip)
-        pending = []
-        for c in range(len(classes)):
-            if cls_ms[c] > 0:
-                for q in pending:
-                    cls[cls == q] = c
-                pending = []
-            elif classes[c][1] > 0:
-                pending.append(c)
-        dom = int(np.argmax(cls_ms))
-        dom_bytes = float(b_e[cls == dom].sum())
-        dom_ms = float(cls_ms[dom])
-        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        dom_alone_ms = float(alone_cls_ms[dom])
-        achieved_alone = dom_bytes / (dom_alone_ms * 1e-3) / 1e9 if dom_alone_ms > 0 else 0.0
-        all_ms = solve_ms / a.steps      # the solve call's device time (the classes overlap: their launch durations do not add up)
         nfev = res.nfev.double().mean().item()
         nit = res.nit.double().mean().item()
-        nfev_e = res.nfev.cpu().numpy().astype(np.float64)
-        nit_e = res.nit.cpu().numpy().astype(np.float64)
-        # the re-streamed figure of SURVEY.md §8(d), B_stream(e) = nfev (8 nnz + 16 n) + 8 p + 32: what a design that does not keep
-        # the entity resident moves — and for the classes whose entities do not fit on chip (team kernels) the algorithmic figure
-        b_s = nfev_e * (8.0 * z + 16.0 * n) + 8.0 * p + 32.0
-        b_stream = float(b_s.sum())
-        per_class = []
-        for c in np.flatnonzero(cls_ms > 0):
-            sel = cls == c
-            per_class.append({"kernel": classes[c][0], "entities": int(sel.sum()), "ms": round(float(cls_ms[c]), 3),
-                              "alg_GBps": round(float(b_e[sel].sum()) / (cls_ms[c] * 1e-3) / 1e9, 2),
-                              "restreamed_GBps": round(float(b_s[sel].sum()) / (cls_ms[c] * 1e-3) / 1e9, 2),
-                              "lbfgs_state_GB": round(lbfgs_state_bytes(p[sel], nit_e[sel], nfev_e[sel], a.lbfgs_m, n=n[sel], one_workgroup=classes[c][0].endswith("workgroup")) / 1e9, 3)
-                              if "team" in classes[c][0] else None,
-                              "mean_n": round(float(n[sel].mean()), 1), "mean_p": round(float(p[sel].mean()), 1),
-                              "max_nnz": int(z[sel].max()), "mean_nfev": round(float(nfev_e[sel].mean()), 2)})
-        traffic = traffic_detail = valu = None
-        traffic_note = None
-        tpath = os.path.join(ROOT, "profiles", "latest_traffic.json")
-        workload_id = f"{a.workload} E={wl.E} n~{a.mean_n} k={a.k} D={a.dim} survey-generator" if a.workload == "c2" else f"{a.workload} E={wl.E}"
-        # PMC counters of the same kernel from separate rocprofv3 --pmc runs of this configuration (tools/profile_round.sh);
-        # they are per launch of a size class and only valid for the workload they were collected on
-        if not os.path.exists(tpath):
-            traffic_note = "profiles/latest_traffic.json is missing: run tools/profile_round.sh on the GPU box"
-        else:
-            with open(tpath) as fh:
-                tj = json.load(fh)
-            from gdmix_amd import build as _b
-            lib_abi = int(solver.lib.gdmix_re_abi_version())
-            if tj.get("_re_abi") != lib_abi or tj.get("_re_kernel_sources_sha16") != _b.kernel_source_hash():
-                traffic_note = (f"profiles/latest_traffic.json is stale: collected on ABI {tj.get('_re_abi')} / kernel sources {tj.get('_re_kernel_sources_sha16')}, "
-                                f"this library is ABI {lib_abi} / {_b.kernel_source_hash()} (tools/profile_round.sh collects it again)")
-            elif tj.get("_workload") != workload_id:
-                traffic_note = f"PMC passes were collected on workload {tj.get('_workload')!r}, this run is {workload_id!r}"
-            elif classes[dom][0] not in tj:
-                traffic_note = f"no PMC pass holds the dominant class {classes[dom][0]!r}"
+        roofline = cpu = per_class = parity = b_stream = None
+        if a.full:
+            # ---- roofline of the dominant kernel = the size-class launch with the largest share of a step ----
+            n, z = wl.n, wl.z
+            p = np.diff(packed.coef_ptr_host())
+            b_e = 8.0 * z + 16.0 * n + 8.0 * p + 32.0                    # B(e), SURVEY.md §8(d)
+            alg_bytes = float(b_e.sum())
+            # parity classes of SURVEY.md §8(d): W = both labels present (a finite optimum exists with the unregularised intercept),
+            # D = all labels equal (the solver runs until the gradient test passes; only invariants are comparable)
+            well_posed = int(((wl.ones > 0) & (wl.ones < n)).sum())
+            parity = {"W": well_posed, "D": int(wl.E - well_posed)}
+            cls = packed._view(packed.c.cls_tmp, packed.E, torch.int32).cpu().numpy()
+            cls_ms = kernel_ms / a.steps
+            # a class that has entities and no launch of its own ran with the class behind it (a small lean tall class, re_api.hip)
+            pending = []
+            for c in range(len(classes)):
+                if cls_ms[c] > 0:
+                    for q in pending:
+                        cls[cls == q] = c
+                    pending = []
+                elif classes[c][1] > 0:
+                    pending.append(c)
+            dom = int(np.argmax(cls_ms))
+            dom_bytes = float(b_e[cls == dom].sum())
+            dom_ms = float(cls_ms[dom])
+            achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            dom_alone_ms = float(alone_cls_ms[dom])
+            achieved_alone = dom_bytes / (dom_alone_ms * 1e-3) / 1e9 if dom_alone_ms > 0 else 0.0
+            all_ms = solve_ms / a.steps      # the solve call's device time (the classes overlap: their launch durations do not add up)
+            nfev_e = res.nfev.cpu().numpy().astype(np.float64)
+            nit_e = res.nit.cpu().numpy().astype(np.float64)
+            # the re-streamed figure of SURVEY.md §8(d), B_stream(e) = nfev (8 nnz + 16 n) + 8 p + 32: what a design that does not keep
+            # the entity resident moves — and for the classes whose entities do not fit on chip (team kernels) the algorithmic figure
+            b_s = nfev_e * (8.0 * z + 16.0 * n) + 8.0 * p + 32.0
+            b_stream = float(b_s.sum())
+            per_class = []
+            for c in np.flatnonzero(cls_ms > 0):
+                sel = cls == c
+                per_class.append({"kernel": classes[c][0], "entities": int(sel.sum()), "ms": round(float(cls_ms[c]), 3),
+                                  "alg_GBps": round(float(b_e[sel].sum()) / (cls_ms[c] * 1e-3) / 1e9, 2),
+                                  "restreamed_GBps": round(float(b_s[sel].sum()) / (cls_ms[c] * 1e-3) / 1e9, 2),
+                                  "lbfgs_state_GB": round(lbfgs_state_bytes(p[sel], nit_e[sel], nfev_e[sel], a.lbfgs_m, n=n[sel], one_workgroup=classes[c][0].endswith("workgroup")) / 1e9, 3)
+                                  if "team" in classes[c][0] else None,
+                                  "mean_n": round(float(n[sel].mean()), 1), "mean_p": round(float(p[sel].mean()), 1),
+                                  "max_nnz": int(z[sel].max()), "mean_nfev": round(float(nfev_e[sel].mean()), 2)})
+            traffic = traffic_detail = valu = None
+            traffic_note = None
+            tpath = os.path.join(ROOT, "profiles", "latest_traffic.json")
+            workload_id = f"{a.workload} E={wl.E} n~{a.mean_n} k={a.k} D={a.dim} survey-generator" if a.workload == "c2" else f"{a.workload} E={wl.E}"
+            # PMC counters of the same kernel from separate rocprofv3 --pmc runs of this configuration (tools/profile_round.sh);
+            # they are per launch of a size class and only valid for the workload they were collected on
+            if not os.path.exists(tpath):
+                traffic_note = "profiles/latest_traffic.json is missing: run tools/profile_round.sh on an MI355X"
             else:
-                traffic_detail = tj[classes[dom][0]]
-                traffic = traffic_detail["bytes"]
-                if traffic_detail.get("valu_insts"):
-                    # the binding resource: VALU issue. Peak = CUs x 4 SIMDs x clock / 4 cycles per wave64
-                    # fp64-path instruction.
-                    insts = float(traffic_detail["valu_insts"])
-                    peak = 256 * 4 * 2.4e9 / 4.0
-                    valu = {"insts_per_launch": insts, "insts_per_entity": insts / max(1, int(classes[dom][1])),
-                            "issue_rate_Ginst_s": insts / (dom_alone_ms * 1e-3) / 1e9 if dom_alone_ms else None,
-                            "issue_frac": insts / (dom_alone_ms * 1e-3) / peak if dom_alone_ms else None,
-                            "peak_Ginst_s": peak / 1e9,
-                            "source": "SQ_INSTS_VALU (rocprofv3 --pmc, separate pass) / live launch duration of the kernel alone (roofline.alone); peak = 256 CUs x 4 SIMDs x 2.4 GHz / 4 cycles"}
-        roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note, "traffic_detail": traffic_detail,
-                    "valu": valu,
-                    "kernel": classes[dom][0], "entities_in_launch": int(classes[dom][1]),
-                    "avg_launch_ms": dom_ms, "alg_bytes_per_launch": dom_bytes,
-                    "schedule": f"timed region: the large size classes run side by side on {SPREAD_DEFAULT} queues (gdmix_re_set_spread), so this launch shares the "
-                                "device with the other classes' and lasts longer than alone; `alone` = the same launch with the classes one after another",
-                    "alone": {"avg_launch_ms": dom_alone_ms, "achieved": round(achieved_alone, 3), "frac": achieved_alone / HBM_PEAK_GBS,
-                              "solve_ms_per_step": alone_solve_ms, "class_ms": [round(float(x), 3) for x in alone_cls_ms],
-                              "what": "the timed steps themselves (--no-alone, or GDMIX_RE_SPREAD <= 1)" if (a.no_alone or SPREAD_DEFAULT <= 1)
-                                      else "3 untimed steps after the timed region with gdmix_re_set_spread(ctx, 0)"},
-                    "alg_bytes_per_entity": alg_bytes / wl.E,
-                    "restreamed_bytes_per_launch": float(b_s[cls == dom].sum()),
-                    "all_solve_kernels": {"ms_per_step": all_ms, "alg_GBps": alg_bytes / (all_ms * 1e-3) / 1e9 if all_ms else 0.0},
-                    "note": "LDS/register-resident L-BFGS: bound by fp64 VALU issue and latency, not by HBM "
-                            "(SURVEY.md §8d honesty note); see DESIGN.md for the VALU-side accounting"}
-        cpu = None
-        if not a.no_cpu_baseline and world == 1:   # the CPU leg is timed at N = 1 only
-            # a bounded sample: about 13 M non-zeros per pass (200 k entities of C2)
-            per_ent = max(1.0, wl.Z / wl.E)
-            sample = a.cpu_sample if a.cpu_sample > 0 else int(min(wl.E, max(64, 12.8e6 / per_ent)))
-            sub = wl.host_sample(sample)
-            v, cores, es, d, passes = cpu_baseline(sub, opts_kw)
-            cpu = {"value": round(v, 1), "unit": "entities/s", "cores": cores, "kind": "port",
-                   # the reference itself (TF + scipy, one entity per fmin_l_bfgs_b call) cannot run on the GPU box; its rate measured in the build
-                   # container on these shapes is quoted, not timed here
-                   "reference_quoted": {"value": 639, "unit": "entities/s/core", "source": "BASELINE.md section 3"},
-                   "sample": f"first {es} entities of the same {a.workload} batch ({sub.Z} non-zeros) x {passes} passes, oracle/re_oracle.c fp64 "
-                             f"(restatement pinned to the reference by tests/golden), {cores} threads, {d:.1f} s"}
+                with open(tpath) as fh:
+                    tj = json.load(fh)
+                from gdmix_amd import build as _b
+                lib_abi = int(solver.lib.gdmix_re_abi_version())
+                if tj.get("_re_abi") != lib_abi or tj.get("_re_kernel_sources_sha16") != _b.kernel_source_hash():
+                    traffic_note = (f"profiles/latest_traffic.json is stale: collected on ABI {tj.get('_re_abi')} / kernel sources {tj.get('_re_kernel_sources_sha16')}, "
+                                    f"this library is ABI {lib_abi} / {_b.kernel_source_hash()} (tools/profile_round.sh collects it again)")
+                elif tj.get("_workload") != workload_id:
+                    traffic_note = f"PMC passes were collected on workload {tj.get('_workload')!r}, this run is {workload_id!r}"
+                elif classes[dom][0] not in tj:
+                    traffic_note = f"no PMC pass holds the dominant class {classes[dom][0]!r}"
+                else:
+                    traffic_detail = tj[classes[dom][0]]
+                    traffic = traffic_detail["bytes"]
+                    if traffic_detail.get("valu_insts"):
+                        # the binding resource: VALU issue. Peak = CUs x 4 SIMDs x clock / 4 cycles per wave64
+                        # fp64-path instruction.
+                        insts = float(traffic_detail["valu_insts"])
+                        peak = 256 * 4 * 2.4e9 / 4.0
+                        valu = {"insts_per_launch": insts, "insts_per_entity": insts / max(1, int(classes[dom][1])),
+                                "issue_rate_Ginst_s": insts / (dom_alone_ms * 1e-3) / 1e9 if dom_alone_ms else None,
+                                "issue_frac": insts / (dom_alone_ms * 1e-3) / peak if dom_alone_ms else None,
+                                "peak_Ginst_s": peak / 1e9,
+                                "source": "SQ_INSTS_VALU (rocprofv3 --pmc, separate pass) / live launch duration of the kernel alone (roofline.alone); peak = 256 CUs x 4 SIMDs x 2.4 GHz / 4 cycles"}
+            roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note, "traffic_detail": traffic_detail,
+                        "valu": valu,
+                        "kernel": classes[dom][0], "entities_in_launch": int(classes[dom][1]),
+                        "avg_launch_ms": dom_ms, "alg_bytes_per_launch": dom_bytes,
+                        "schedule": f"timed region: the large size classes run side by side on {SPREAD_DEFAULT} queues (gdmix_re_set_spread), so this launch shares the "
+                                    "device with the other classes' and lasts longer than alone; `alone` = the same launch with the classes one after another",
+                        "alone": {"avg_launch_ms": dom_alone_ms, "achieved": round(achieved_alone, 3), "frac": achieved_alone / HBM_PEAK_GBS,
+                                  "solve_ms_per_step": alone_solve_ms, "class_ms": [round(float(x), 3) for x in alone_cls_ms],
+                                  "what": "the timed steps themselves (--no-alone, or GDMIX_RE_SPREAD <= 1)" if (a.no_alone or SPREAD_DEFAULT <= 1)
+                                          else "3 untimed steps after the timed region with gdmix_re_set_spread(ctx, 0)"},
+                        "alg_bytes_per_entity": alg_bytes / wl.E,
+                        "restreamed_bytes_per_launch": float(b_s[cls == dom].sum()),
+                        "all_solve_kernels": {"ms_per_step": all_ms, "alg_GBps": alg_bytes / (all_ms * 1e-3) / 1e9 if all_ms else 0.0},
+                        "note": "LDS/register-resident L-BFGS: bound by fp64 VALU issue and latency, not by HBM "
+                                "(SURVEY.md §8d honesty note); see DESIGN.md for the VALU-side accounting"}
+            if not a.no_cpu_baseline and world == 1:   # the CPU leg is timed at N = 1 only
+                # a bounded sample: about 13 M non-zeros per pass (200 k entities of C2)
+                per_ent = max(1.0, wl.Z / wl.E)
+                sample = a.cpu_sample if a.cpu_sample > 0 else int(min(wl.E, max(64, 12.8e6 / per_ent)))
+                sub = wl.host_sample(sample)
+                v, cores, es, d, passes = cpu_baseline(sub, opts_kw)
+                cpu = {"value": round(v, 1), "unit": "entities/s", "cores": cores, "kind": "port",
+                       # the reference itself (TF + scipy, one entity per fmin_l_bfgs_b call) is not timed here: its rate measured on a CPU host
+                       # on these shapes is quoted
+                       "reference_quoted": {"value": 639, "unit": "entities/s/core", "source": "BASELINE.md section 3"},
+                       "sample": f"first {es} entities of the same {a.workload} batch ({sub.Z} non-zeros) x {passes} passes, oracle/re_oracle.c fp64 "
+                                 f"(restatement pinned to the reference by tests/golden), {cores} threads, {d:.1f} s"}
         line = {
             "metric": "random-effect entities converged/sec", "value": round(value, 1), "unit": "entities/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
@@ -1346,12 +1359,12 @@ def main():
                        "solve_kernel_ms_per_step": float(kernel_ms.sum()) / a.steps,
                        "classes": classes, "class_ms": [round(float(x) / a.steps, 3) for x in kernel_ms], "per_class": per_class,
                        "mean_nit": nit, "mean_nfev": nfev,
-                       "converged_per_step": converged_all, "parity_classes": {"W": well_posed, "D": int(wl.E - well_posed)}, "N": wl.N, "Z": wl.Z, "P": packed.P,
-                       "gpu_state_under_load": gpu_load_state, "gpu_state_at_end": gpu_state(),
+                       "converged_per_step": converged_all, "parity_classes": parity, "N": wl.N, "Z": wl.Z, "P": packed.P,
+                       "gpu_state_under_load": gpu_load_state, "gpu_state_at_end": gpu_state() if a.full else None,
                        "host_generate_s": t_gen, "solve_to_host": to_host, "host_handover": e2e, "score_pass": score, "fixed_effect_eval": fe_eval, "cli_end_to_end": cli_e2e,
                        "cli_subprocess": cli_sub, "cli_end_to_end_c5": cli_c5, "cli_end_to_end_ml20m_movie": cli_movie, "workloads": others, "c5_full_share": c5_full, "chain": chain_res,
                        "restreamed_bytes_per_step": b_stream,
-                       "restreamed_GBps": b_stream / (float(kernel_ms.sum()) / a.steps * 1e-3) / 1e9 if kernel_ms.sum() else None},
+                       "restreamed_GBps": b_stream / (float(kernel_ms.sum()) / a.steps * 1e-3) / 1e9 if b_stream is not None and kernel_ms.sum() else None},
         }
         emit(line, a)
     if world > 1:

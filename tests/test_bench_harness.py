@@ -104,6 +104,39 @@ def test_world_size_must_match_gpus_flag():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
 
 
+def test_full_is_off_by_default_and_a_plain_result_fits_the_short_line(monkeypatch):
+    """--full is asked for, never implied; the short line of a plain run carries the headline with roofline and cpu_baseline null."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.parse().full is True
+    plain = {"metric": "random-effect entities converged/sec", "value": 1.11e8, "unit": "entities/s", "n_gpus": 1, "steps": 3, "warmup": 1,
+             "ms_per_step": 9.0, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+             "config": {"workload": "C2", "workload_key": "c2"}, "roofline": None, "cpu_baseline": None, "strong_scaling": None,
+             "detail": {"pack_ms_per_step": 0.9, "solve_ms_per_step": 8.1, "converged_per_step": 1000000, "mean_nfev": 9.5, "workloads": None,
+                        "strong_projection": None, "c5_full_share": None, "chain": None}}
+    short = bench.compact_line(plain, "bench_detail.json")
+    assert short["value"] == 1.11e8 and short["ms_per_step"] == 9.0 and short["roofline"] is None and short["cpu_baseline"] is None
+    assert short["summary"] == {"pack_ms": 0.9, "solve_ms": 8.1, "converged_per_step": 1000000, "mean_nfev": 9.5}
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_timed_steps_only(tmp_path):
+    """Without --full a run times its steps and reports them: no roofline, CPU baseline or side leg in its result."""
+    line = _line(["--entities", "20000", "--steps", "2", "--warmup", "1"], tmp_path)
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["config"]["entities_per_gpu"] == 20000
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["strong_scaling"] is None
+    d = line["detail"]
+    assert d["converged_per_step"] == 20000 and len(d["step_wall_ms"]) == 2 and d["pack_ms_per_step"] > 0 and d["solve_ms_per_step"] > 0
+    assert abs(line["value"] - 20000 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    legs = ("per_class", "parity_classes", "gpu_state_under_load", "gpu_state_at_end", "solve_to_host", "host_handover", "score_pass",
+            "fixed_effect_eval", "cli_end_to_end", "cli_subprocess", "cli_end_to_end_c5", "cli_end_to_end_ml20m_movie", "workloads",
+            "c5_full_share", "chain", "strong_projection", "restreamed_bytes_per_step")
+    assert [k for k in legs if d[k] is not None] == []
+
+
 @pytest.mark.gpu
 def test_gpus_flag_starts_that_many_ranks(tmp_path):
     """--gpus 2 without a launcher: two ranks. On the 1-GPU box they share cuda:0 over gloo (harness test, numbers meaningless);
@@ -127,7 +160,7 @@ def test_gpus_flag_starts_that_many_ranks(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("workload", ["ml20m_movie"])
 def test_other_workloads_produce_a_line(workload, tmp_path):
-    line = _line(["--workload", workload, "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-e2e"], tmp_path)
+    line = _line(["--workload", workload, "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e"], tmp_path)
     assert line["n_gpus"] == 1 and line["config"]["workload_key"] == workload
     assert line["detail"]["converged_per_step"] == line["config"]["entities_per_gpu"] == 26744
     pc = line["detail"]["per_class"]
@@ -136,12 +169,12 @@ def test_other_workloads_produce_a_line(workload, tmp_path):
 
 @pytest.mark.gpu
 def test_default_legs_of_a_two_rank_run(tmp_path):
-    """The driver's scaling run is the default command with --gpus N: every rank also measures the MovieLens-20M workloads and
+    """The full run with --gpus N: every rank also measures the MovieLens-20M workloads and
     C5's per-GPU share after C2 (detail.workloads, collectives inside). Two ranks here; on the 1-GPU box they share the device and
     the C5 leg must be skipped by both ranks together (a rank that ran out of memory alone would leave the other in a barrier)."""
     import torch
     share = [] if torch.cuda.device_count() >= 2 else ["--ranks-share-device"]
-    line = _line(["--gpus", "2"] + share + ["--entities", "20000", "--steps", "2", "--warmup", "1"], tmp_path, timeout=1500)
+    line = _line(["--gpus", "2"] + share + ["--entities", "20000", "--steps", "2", "--warmup", "1", "--full"], tmp_path, timeout=1500)
     assert line["n_gpus"] == 2 and line["detail"]["converged_per_step"] == 40000
     w = line["detail"]["workloads"]
     assert set(w) == {"ml20m_user", "ml20m_movie", "c5share"}
@@ -168,7 +201,7 @@ def test_strong_scaling_splits_one_population_and_rebalancing_returns_the_same_m
     run's. Two ranks: on the 1-GPU box they share cuda:0 and the collectives are staged over gloo; with two devices it is RCCL."""
     import torch
     share = [] if torch.cuda.device_count() >= 2 else ["--ranks-share-device"]
-    line = _line(["--gpus", "2"] + share + ["--scaling", "strong", "--workload", workload, "--steps", "2", "--warmup", "1"] + extra, tmp_path)
+    line = _line(["--gpus", "2"] + share + ["--scaling", "strong", "--workload", workload, "--steps", "2", "--warmup", "1", "--full"] + extra, tmp_path)
     assert line["scaling"] == "strong" and line["n_gpus"] == 2 and line["config"]["workload_key"] == workload
     s = line["strong_scaling"][0]
     assert s["total_entities"] == total == sum(r["entities"] for r in s["per_rank"]) == s["converged_per_step"]
@@ -188,7 +221,7 @@ def test_strong_scaling_splits_one_population_and_rebalancing_returns_the_same_m
 @pytest.mark.gpu
 def test_projection_of_an_eight_rank_job_on_one_device(tmp_path):
     """--gpus 1: the shares of an 8-rank job solved one after another (detail.strong_projection), with the re-balancing plan."""
-    line = _line(["--entities", "20000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-fe", "--no-cli",
+    line = _line(["--entities", "20000", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e", "--no-fe", "--no-cli",
                   "--ml-entities", "8000", "--c5-entities", "20000", "--project-ranks", "8", "--c5-full-entities", "400000", "--c5-full-rounds", "3"],
                  tmp_path, timeout=1500)
     proj = {p["workload"]: p for p in line["detail"]["strong_projection"]}

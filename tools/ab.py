@@ -5,7 +5,7 @@
                        [--fields ms_per_step,detail.pack_ms_per_step,...] [--tests "-k expr"] [--out DIR] [-- bench args]
 
 Every combination of the --env values (and of --lib, copied over gdmix_amd/libgdmix_re.so) x every workload x `reps` rounds runs
-bench.py with the side legs off; the chosen fields of the full result (the detail file) are printed per run, then the per-variant
+bench.py --full with the side legs off (--legs keeps some on); the chosen fields of the full result (the detail file) are printed per run, then the per-variant
 minimum. `--tests` first runs the GPU parity tests matching the expression. `unset` as a value leaves the variable out.
 
 Recipes (what round 4's scripts were; DESIGN.md / docs/rounds cite the results):
@@ -101,7 +101,7 @@ def main():
                 tag = " ".join(f"{n}={v}" for n, v in combo) or "-"
                 for w in a.workloads.split(","):
                     detail = os.path.join(a.out, f"{w}_{tag.replace(' ', '_').replace('/', '+')}_{rep}.json")
-                    cmd = [sys.executable, "bench.py", "--workload", w, "--steps", str(a.steps), "--warmup", str(a.warmup), "--detail-file", detail] + off + extra
+                    cmd = [sys.executable, "bench.py", "--workload", w, "--steps", str(a.steps), "--warmup", str(a.warmup), "--full", "--detail-file", detail] + off + extra
                     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True)
                     if r.returncode != 0:
                         print(f"{w:12s} {tag}: FAILED rc {r.returncode}: {r.stderr[-400:]}")

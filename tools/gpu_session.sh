@@ -20,7 +20,7 @@ cp gdmix_amd/libgdmix_re.so $out/lib_at_start.so
 n=0
 bench_once() {   # $1 = label, rest = extra env assignments; prints the C2 step, the projection and the CLI legs that ran
   local label=$1; shift
-  env "$@" GDMIX_BENCH_LINE=full timeout 1200 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-fe --no-alone --c5-full-entities 0 $BENCH_EXTRA --detail-file $out/b.json > /dev/null 2> $out/b.err
+  env "$@" GDMIX_BENCH_LINE=full timeout 1200 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-e2e --no-fe --no-alone --c5-full-entities 0 $BENCH_EXTRA --detail-file $out/b.json > /dev/null 2> $out/b.err
   python - "$label" $out/b.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2])); dd = d["detail"]

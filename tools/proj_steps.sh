@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 out=$1; var=${2%%=*}; vals=$(echo ${2#*=} | tr , ' '); reps=${3:-2}
 mkdir -p $out
 for rep in $(seq 1 $reps); do for v in $vals; do
-  env $var=$v GDMIX_BENCH_LINE=full timeout 900 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-fe --no-alone --no-cli --c5-full-entities 0 --strong-steps 6 \
+  env $var=$v GDMIX_BENCH_LINE=full timeout 900 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-e2e --no-fe --no-alone --no-cli --c5-full-entities 0 --strong-steps 6 \
       --detail-file $out/${var}_${v}_$rep.json > /dev/null 2> $out/err.txt || tail -3 $out/err.txt
   python - $out/${var}_${v}_$rep.json "$var=$v rep=$rep" <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ for rep in $(seq 1 $REPS); do for v in $VALS; do
   for w in ml20m_user ml20m_movie; do
     timeout 600 python bench.py --steps 10 --warmup 3 --workload $w --tall-min-n $v --project-ranks 0 $COMMON --detail-file $O/${w}_${v}_$rep.json > /dev/null 2> $O/err.txt || tail -3 $O/err.txt
   done
-  timeout 900 python bench.py --steps 3 --warmup 2 --tall-min-n $v --strong-steps 6 $COMMON --detail-file $O/proj_${v}_$rep.json > /dev/null 2> $O/err.txt || tail -3 $O/err.txt
+  timeout 900 python bench.py --steps 3 --warmup 2 --full --tall-min-n $v --strong-steps 6 $COMMON --detail-file $O/proj_${v}_$rep.json > /dev/null 2> $O/err.txt || tail -3 $O/err.txt
   python - $O $v $rep <<'PY'
 import json, sys
 o, v, rep = sys.argv[1:4]
