@@ -23,15 +23,11 @@ constexpr int COMPACT_KD = TEAM_K + 2 * TEAM_MCAP;   // acc[] with the DIRECT pr
 // d = (x + d) - x): the small solve also yields g'd = -g'Hg algebraically, but the two differ once x dwarfs d (badly scaled
 // entities; tests/golden exit_hard_*, exit_extreme_*), and L-BFGS-B's line search runs on the former (lnsrlb: gd = ddot(g, d)).
 // It arrives with the first trial's products and replaces the algebraic value before the search takes its first decision.
-// The products are taken with y, not with g: S'g and Y'g at the new gradient are the stored ones plus these, and the new
-// column of S'Y / Y'Y is these — sums, where products with g would need differences of nearly equal numbers once the
-// gradient changes little between iterates.
-// ... and S'g and Y'g are ALSO taken directly (round 6; compact_advance's `sg`, 2 m more accumulators: COMPACT_KD in all): a stored s_i'g_k that is the sum of s_i'y over the iterations since the pair was made carries
-// the rounding of every term at the size the gradient had THEN — eps |s_i| |y_k| each — which is |g_then| / |g_now| times what the
-// direct product's is. A fit whose gradient falls by 10^3 - 10^4 inside the history window (tools/fuzz_fe.py case 6700230: squared
-// loss, |g| 3 000 -> 0.9 in twelve iterations) left the reference's trajectory by 1e-5 at the first iterate the problem amplifies,
-// where L-BFGS-B itself (direct products: cauchy's p = W'g) and the two-loop oracle stay together to 1e-9 (profiles/r06_fuzz.txt).
-// Without `sg` (GDMIX_TEAM_DIRECT_AB=0 builds of the team kernels) the sums are used, as in rounds 3 - 5.
+// The products are taken with y, not with g: the new column of S'Y / Y'Y is these — sums, where products with g would need
+// differences of nearly equal numbers once the gradient changes little between iterates.
+// S'g and Y'g themselves are taken directly (compact_advance's `sg`, 2 m more accumulators: COMPACT_KD in all), as L-BFGS-B does
+// (cauchy's p = W'g), because a running sum of products with y keeps the rounding each term had at the size the gradient had then,
+// which left scipy's trajectory once the gradient fell by 10^3 inside the history window (profiles/r06_fuzz.txt).
 
 // History layout of the compact-form kernels: tiles of 64 consecutive coefficients, and inside a tile slot-major:
 //     (s, y) of coefficient j, slot sl  =  ((double2*)W.ws)[((j >> 6) * m + sl) * 64 + (j & 63)]
@@ -69,7 +65,6 @@ struct CompactPlan {    // what the elementwise pass over the p-vectors has to d
 struct CompactMats {    // the m x m part (LDS; every workgroup keeps a replica)
   double SY[TEAM_MCAP * TEAM_MCAP];   // s_i'y_k, chronological, i <= k used
   double YY[TEAM_MCAP * TEAM_MCAP];   // y_i'y_k
-  double ap[TEAM_MCAP], bp[TEAM_MCAP];   // S'g_k, Y'g_k at the last accepted iterate
   double u[TEAM_MCAP], q[TEAM_MCAP];
   double sc[4];
 };
@@ -77,8 +72,8 @@ struct CompactMats {    // the m x m part (LDS; every workgroup keeps a replica)
 // Called by every thread of a workgroup with identical arguments. Contains one __syncthreads() on the
 // CA_DIRECTION path.
 __device__ __forceinline__ void compact_advance(CompactState& S, const double* acc /* [TEAM_K], registers or LDS */, double f_new,
-                                                const SolveParams& o, CompactMats& L, CompactPlan& plan, bool counted = true,
-                                                const double* sg = nullptr /* [2 MCAP]: S_i'g, Y_i'g taken directly (chronological), or none */) {
+                                                const SolveParams& o, CompactMats& L, CompactPlan& plan, bool counted,
+                                                const double* sg /* [2 MCAP]: S_i'g, Y_i'g (chronological) */) {
   const int m = o.m;
   counted = counted || S.first;
   S.nfev += counted ? 1 : 0;
@@ -161,7 +156,6 @@ __device__ __forceinline__ void compact_advance(CompactState& S, const double* a
         sy[h] = ok ? L.SY[(r + 1) * TEAM_MCAP + c + 1] : 0.0;
         yy[h] = ok ? L.YY[(r + 1) * TEAM_MCAP + c + 1] : 0.0;
       }
-      const double pa = (i + 1 < m) ? L.ap[i + 1] : 0.0, pb = (i + 1 < m) ? L.bp[i + 1] : 0.0;
       wave_lds_fence();
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -169,10 +163,9 @@ __device__ __forceinline__ void compact_advance(CompactState& S, const double* a
         const int r = idx / TEAM_MCAP, c = idx - r * TEAM_MCAP;
         if (idx < MM && r + 1 < m && c + 1 < m) { L.SY[idx] = sy[h]; L.YY[idx] = yy[h]; }
       }
-      if (i + 1 < m) { L.ap[i] = pa; L.bp[i] = pb; }
       wave_lds_fence();
     }
-    // s_i'y, y_i'y of row i in chronological order after the shift (y = g - g_k); s_i'g, y_i'g likewise where the caller has them
+    // s_i'y, y_i'y, s_i'g, y_i'g of row i in chronological order after the shift (y = g - g_k)
     double sy_i = 0.0, yy_i = 0.0, sg_i = 0.0, yg_i = 0.0;
 #pragma unroll
     for (int k = 0; k < TEAM_MCAP; ++k) {
@@ -180,18 +173,18 @@ __device__ __forceinline__ void compact_advance(CompactState& S, const double* a
         if (shift) {
           if (k + 1 < TEAM_MCAP) {
             sy_i = acc[5 + (k + 1 < TEAM_MCAP ? k + 1 : k)]; yy_i = acc[5 + TEAM_MCAP + (k + 1 < TEAM_MCAP ? k + 1 : k)];
-            if (sg) { sg_i = sg[k + 1 < TEAM_MCAP ? k + 1 : k]; yg_i = sg[TEAM_MCAP + (k + 1 < TEAM_MCAP ? k + 1 : k)]; }
+            sg_i = sg[k + 1 < TEAM_MCAP ? k + 1 : k]; yg_i = sg[TEAM_MCAP + (k + 1 < TEAM_MCAP ? k + 1 : k)];
           }
         } else {
           sy_i = acc[5 + k]; yy_i = acc[5 + TEAM_MCAP + k];
-          if (sg) { sg_i = sg[k]; yg_i = sg[TEAM_MCAP + k]; }
+          sg_i = sg[k]; yg_i = sg[TEAM_MCAP + k];
         }
       }
     }
-    // S'g, Y'g at the new gradient: taken directly, or the stored products at g_k plus the products with y; the new pair in closed form
+    // S'g, Y'g at the new gradient; the new pair's in closed form
     const int old_rows = store_pair ? cnew : col;
     double ai = 0.0, bi = 0.0;
-    if (i < old_rows && !restore) { ai = sg ? sg_i : L.ap[i] + sy_i; bi = sg ? yg_i : L.bp[i] + yy_i; }
+    if (i < old_rows && !restore) { ai = sg_i; bi = yg_i; }
     if (store_pair) {
       if (i < cnew) {
         L.SY[i * TEAM_MCAP + cnew] = sy_i;
@@ -253,7 +246,7 @@ __device__ __forceinline__ void compact_advance(CompactState& S, const double* a
     }
     const double term = row ? (gamma * bi * myq - ai * myu) : 0.0;
     const double gdn0 = wave_sum(term) - gg_cur * (col > 0 ? gamma : 1.0);
-    if (row) { L.ap[i] = ai; L.bp[i] = bi; L.q[i] = myq; L.u[i] = myu; }
+    if (row) { L.q[i] = myq; L.u[i] = myu; }
     if (i == 0) L.sc[0] = gdn0;
   }
   __syncthreads();

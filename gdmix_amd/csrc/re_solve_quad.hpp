@@ -37,33 +37,11 @@ __device__ __forceinline__ double dpp_row(double v) {
   return __hiloint2double(hi, lo);
 }
 
-// The same exchange through the LDS crossbar (ds_swizzle_b32, bit mode: lane' = lane ^ X inside 32 lanes; no memory is touched):
-// 0 vector instructions for the move instead of two v_mov_b32_dpp, at the latency of the LDS queue. quad_perm [1,0,3,2] = ^1,
-// [2,3,0,1] = ^2, row_half_mirror = ^7, row_mirror = ^15, the other row of a pair = ^16: the partner lanes of the DPP butterflies
-// below, so a sum built this way has the same bits. GDMIX_QUAD_SWZ: 1 = the reductions of several values at once (loss / residual
-// sum / |x|^2; g'd / y'y / max|g|; d'd / g'd: their moves overlap), 2 = the one-value reductions of the two-loop recursion as
-// well (a dependent chain). A/B: profiles/r06_c2_ab.txt.
-#ifndef GDMIX_QUAD_SWZ
-#define GDMIX_QUAD_SWZ 0
-#endif
-template <int X>
-__device__ __forceinline__ double swz_xor(double v) {
-  constexpr int pat = 0x1f | (X << 10);
-  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), pat);
-  const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), pat);
-  return __hiloint2double(hi, lo);
-}
+// (The butterfly moves through the LDS crossbar, ds_swizzle, instead of DPP: measured slower, rejected in round 6: profiles/r06_c2_ab.txt.)
 
 // dpp_ctrl: quad_perm:[1,0,3,2] = 0xB1, quad_perm:[2,3,0,1] = 0x4E, row_half_mirror = 0x141, row_mirror = 0x140
 // Butterfly: every lane of the row ends with the same bits (each stage adds the same two partial sums).
 __device__ __forceinline__ double row_sum(double v) {
-#if GDMIX_QUAD_SWZ & 2
-  v += swz_xor<1>(v);
-  v += swz_xor<2>(v);
-  v += swz_xor<7>(v);
-  v += swz_xor<15>(v);
-  return v;
-#endif
   v += dpp_row<0xB1>(v);
   v += dpp_row<0x4E>(v);
   v += dpp_row<0x141>(v);
@@ -72,18 +50,6 @@ __device__ __forceinline__ double row_sum(double v) {
 }
 
 __device__ __forceinline__ void row_sum2(double& a, double& b) {
-#if GDMIX_QUAD_SWZ & 1
-#define GDMIX_SSTEP2(X)                \
-  {                                    \
-    const double ta = swz_xor<X>(a);   \
-    const double tb = swz_xor<X>(b);   \
-    a += ta;                           \
-    b += tb;                           \
-  }
-  GDMIX_SSTEP2(1) GDMIX_SSTEP2(2) GDMIX_SSTEP2(7) GDMIX_SSTEP2(15)
-#undef GDMIX_SSTEP2
-  return;
-#endif
 #define GDMIX_RSTEP2(CTRL)              \
   {                                     \
     const double ta = dpp_row<CTRL>(a); \
@@ -142,8 +108,7 @@ __device__ __forceinline__ double xwave_combine(XWave& X, double v, int slot, bo
 template <int G>
 __device__ __forceinline__ double grp_sum(double v, XWave& X) {
   v = row_sum(v);
-  if (G >= 32 && (GDMIX_QUAD_SWZ & 2)) v += swz_xor<16>(v);
-  else if (G >= 32) { double a, b; rowpair_split(v, a, b); v = a + b; }
+  if (G >= 32) { double a, b; rowpair_split(v, a, b); v = a + b; }
   if (G >= 64) { double a, b; half_split(v, a, b); v = a + b; }
   if (G > 64) { v = xwave_combine<G>(X, v, 0, false); X.phase ^= 1; }
   return v;
@@ -152,11 +117,7 @@ __device__ __forceinline__ double grp_sum(double v, XWave& X) {
 template <int G>
 __device__ __forceinline__ void grp_sum2(double& a, double& b, XWave& X) {
   row_sum2(a, b);
-  if (G >= 32 && (GDMIX_QUAD_SWZ & 1)) {
-    const double ta = swz_xor<16>(a), tb = swz_xor<16>(b);
-    a += ta;
-    b += tb;
-  } else if (G >= 32) {
+  if (G >= 32) {
     double a0, a1, b0, b1;
     rowpair_split(a, a0, a1);
     rowpair_split(b, b0, b1);
@@ -184,20 +145,6 @@ __device__ __forceinline__ void grp_sum2(double& a, double& b, XWave& X) {
 }
 
 __device__ __forceinline__ void row_sum3(double& a, double& b, double& c) {
-#if GDMIX_QUAD_SWZ & 1
-#define GDMIX_SSTEP3(X)                \
-  {                                    \
-    const double ta = swz_xor<X>(a);   \
-    const double tb = swz_xor<X>(b);   \
-    const double tc = swz_xor<X>(c);   \
-    a += ta;                           \
-    b += tb;                           \
-    c += tc;                           \
-  }
-  GDMIX_SSTEP3(1) GDMIX_SSTEP3(2) GDMIX_SSTEP3(7) GDMIX_SSTEP3(15)
-#undef GDMIX_SSTEP3
-  return;
-#endif
 #define GDMIX_RSTEP3S(CTRL)             \
   {                                     \
     const double ta = dpp_row<CTRL>(a); \
@@ -215,12 +162,7 @@ __device__ __forceinline__ void row_sum3(double& a, double& b, double& c) {
 template <int G>
 __device__ __forceinline__ void grp_sum3(double& a, double& b, double& c, XWave& X) {
   row_sum3(a, b, c);
-  if (G >= 32 && (GDMIX_QUAD_SWZ & 1)) {
-    const double ta = swz_xor<16>(a), tb = swz_xor<16>(b), tc = swz_xor<16>(c);
-    a += ta;
-    b += tb;
-    c += tc;
-  } else if (G >= 32) {
+  if (G >= 32) {
     double a0, a1, b0, b1, c0, c1;
     rowpair_split(a, a0, a1);
     rowpair_split(b, b0, b1);
@@ -253,20 +195,6 @@ __device__ __forceinline__ void grp_sum3(double& a, double& b, double& c, XWave&
 }
 
 __device__ __forceinline__ void row_sum2_max(double& a, double& b, double& c) {
-#if GDMIX_QUAD_SWZ & 1
-#define GDMIX_SSTEP3M(X)               \
-  {                                    \
-    const double ta = swz_xor<X>(a);   \
-    const double tb = swz_xor<X>(b);   \
-    const double tc = swz_xor<X>(c);   \
-    a += ta;                           \
-    b += tb;                           \
-    c = max_nn(c, tc);                 \
-  }
-  GDMIX_SSTEP3M(1) GDMIX_SSTEP3M(2) GDMIX_SSTEP3M(7) GDMIX_SSTEP3M(15)
-#undef GDMIX_SSTEP3M
-  return;
-#endif
 #define GDMIX_RSTEP3(CTRL)              \
   {                                     \
     const double ta = dpp_row<CTRL>(a); \
@@ -283,12 +211,7 @@ __device__ __forceinline__ void row_sum2_max(double& a, double& b, double& c) {
 template <int G>
 __device__ __forceinline__ void grp_sum2_max(double& a, double& b, double& c, XWave& X) {
   row_sum2_max(a, b, c);
-  if (G >= 32 && (GDMIX_QUAD_SWZ & 1)) {
-    const double ta = swz_xor<16>(a), tb = swz_xor<16>(b), tc = swz_xor<16>(c);
-    a += ta;
-    b += tb;
-    c = max_nn(c, tc);
-  } else if (G >= 32) {
+  if (G >= 32) {
     double a0, a1, b0, b1, c0, c1;
     rowpair_split(a, a0, a1);
     rowpair_split(b, b0, b1);
@@ -337,16 +260,8 @@ struct QuadLayout {
 // <16,4> and was deleted in round 4: profiles/r03_c2_history_by_age.txt.)
 constexpr int QUAD_HDR_BYTES = 8 * (2 * M_REG + 16 + 8);   // rho, alpha, LineSearch slot, 8 scalars (one per wavefront of the group)
 
-// GDMIX_QUAD_ROW_DW: where the next row of a wavefront starts, in dwords modulo the 64 banks (rows = entities per wavefront > 1
-// only; < 0 = the packed size). A 32-lane ds_read_b64 group holds two rows of a G = 16 wavefront: lane-aligned reads (x_old, g_old,
-// the published point) of the two rows meet in the banks unless the rows start 32 banks apart — but the CSR pairs of rows of four
-// non-zeros (32 bytes a lane) then meet four deep. Sweep and counters: profiles/r06_c2_ab.txt.
-#ifndef GDMIX_QUAD_ROW_DW
-#define GDMIX_QUAD_ROW_DW (-1)
-#endif
-constexpr int LDS_BYTES_PER_CU = 160 * 1024;
-
-__host__ __device__ inline QuadLayout quad_layout(int pcap, int ncap, int zcap, int waves = 1, int rows = 1) {
+// (The rows of a wavefront padded to start 32 LDS banks apart: fewer bank conflicts, same time, rejected in round 6: profiles/r06_c2_ab.txt.)
+__host__ __device__ inline QuadLayout quad_layout(int pcap, int ncap, int zcap, int waves = 1) {
   QuadLayout q;
   // groups wider than a wavefront keep one private copy of the uniform solver state per wavefront (all
   // copies hold the same values; sharing one would race between a fast wave's write and a slow wave's read)
@@ -364,11 +279,6 @@ __host__ __device__ inline QuadLayout quad_layout(int pcap, int ncap, int zcap, 
   q.o = off; off += 4 * ncap;
   q.w = off; off += 4 * ncap;
   q.bytes = (off + 15) & ~15;
-  if (GDMIX_QUAD_ROW_DW >= 0 && rows > 1) {
-    const int padded = q.bytes + 4 * ((GDMIX_QUAD_ROW_DW - q.bytes / 4) & 63);
-    // never at the price of a resident wavefront
-    if (LDS_BYTES_PER_CU / (rows * padded) >= LDS_BYTES_PER_CU / (rows * q.bytes) || LDS_BYTES_PER_CU / (rows * padded) >= 8) q.bytes = padded;
-  }
   return q;
 }
 
@@ -398,34 +308,7 @@ static_assert(sizeof(LineSearch) <= 128, "LineSearch must fit its LDS slot");
 
 enum { SC_FOLD = 0, SC_GDOLD = 1, SC_THETA = 2, SC_MOVED = 3 };
 
-// ---- per-entity uniform state in the LANES of a register pair (GDMIX_QUAD_LANE_STATE, round 6) ----------------------------------
-// rho[a], alpha[a] and the three scalars an iteration carries (f_old, g'd_old, theta) are uniform per entity. Until round 6 they
-// lived in the row's LDS header: one ds_read per use inside the dependent chain of the two-loop recursion, 9 + 9 LDS accesses to
-// shift rho at a push. Here lane a of every 16-lane row keeps rho[a] (alpha[a]) of the row's entity in ONE register pair; a use is
-// a v_mov_b64_dpp row_newbcast:a (gfx90a+: the one DPP control 64-bit moves take), a store two v_cndmask under a constant lane
-// mask, the shift one row_shl:1. Groups wider than a row keep identical copies in every row (all their reductions are bit-equal
-// in all lanes). Lanes: 0..9 rho | alpha, 10 f_old, 11 g'd_old, 12 theta (of the first pair only).
-// Measured (profiles/r06_c2_ab.txt): LDS instructions of <32,3> - 36 %, vector instructions + 4.8 %, the kernel alone 4.50 -> 4.55 ms,
-// <16,4> (four more registers to spill) 2.41 -> 2.61 ms, the C2 step 9.04 -> 9.22 ms: these kernels are bound by vector issue, not by
-// LDS traffic. Off; kept for the record and for the next architecture.
-#ifndef GDMIX_QUAD_LANE_STATE
-#define GDMIX_QUAD_LANE_STATE 0
-#endif
-#ifndef GDMIX_QUAD_ZERO_STEPS
-#define GDMIX_QUAD_ZERO_STEPS 0      // (described where the steps are: quad_solve)
-#endif
-enum { LN_FOLD = 10, LN_GDOLD = 11, LN_THETA = 12 };
-static_assert(M_REG <= 10, "lane slots 10..12 hold the scalars");
-
-template <int LANE>
-__device__ __forceinline__ double row_get(double v) {
-  // mov_dpp, not update_dpp: no `old` operand the compiler would have to materialise in the destination first
-  return __longlong_as_double(__builtin_amdgcn_mov_dpp(__double_as_longlong(v), 0x150 + LANE, 0xf, 0xf, true));
-}
-template <int LANE>
-__device__ __forceinline__ double row_put(double reg, double v) {
-  return __builtin_amdgcn_inverse_ballot_w64(0x0001000100010001ull << LANE) ? v : reg;
-}
+// (The per-entity rho, alpha and scalars in the lanes of a register pair instead of LDS: slower, rejected in round 6: profiles/r06_c2_ab.txt.)
 
 // Is `v` true in any lane of the entity's group? G <= 64: from the wavefront's ballot (all lanes of a group are active
 // together). Wider groups: this wavefront's part only (quad_eval collects the wavefronts' parts behind its first fence).
@@ -437,12 +320,6 @@ __device__ __forceinline__ bool grp_any(bool v) {
   return ((m >> sh) & ((1ull << G) - 1ull)) != 0ull;
 }
 
-#ifndef QUAD_FUSED_COLS
-#define QUAD_FUSED_COLS 1
-#endif
-#ifndef QUAD_FUSED_COLS4
-#define QUAD_FUSED_COLS4 1
-#endif
 // sum_k val[k] * vec[idx[k]] over `len` packed {idx, float bits} pairs starting at `pairs`, added to acc
 // in index order. Gathers are issued four at a time; the FMA chain keeps the sequential order (masked
 // tail entries multiply by an exact 0).
@@ -458,19 +335,6 @@ __device__ __forceinline__ double gather_dot(const int2* pairs, int len, const d
     acc += (r > 1 ? (double)__int_as_float(p1.y) : 0.0) * v1;
     acc += (r > 2 ? (double)__int_as_float(p2.y) : 0.0) * v2;
     acc += (r > 3 ? (double)__int_as_float(p3.y) : 0.0) * v3;
-  }
-  return acc;
-}
-
-// The same for short runs (the columns of an entity mostly hold one or two entries): two at a time.
-__device__ __forceinline__ double gather_dot2(const int2* pairs, int len, const double* vec, double acc) {
-  for (int c = 0; c < len; c += 2) {
-    const int r = len - c;   // >= 1
-    const int2 p0 = pairs[c];
-    const int2 p1 = pairs[c + (r > 1 ? 1 : 0)];
-    const double v0 = vec[p0.x], v1 = vec[p1.x];
-    acc += (double)__int_as_float(p0.y) * v0;
-    acc += (r > 1 ? (double)__int_as_float(p1.y) : 0.0) * v1;
   }
   return acc;
 }
@@ -596,7 +460,7 @@ __device__ __forceinline__ double quad_eval(const QuadLds& L, const SolveParams&
   part += 0.5 * o.l2 * sq;
   grp_fence<G>();
   const double inv_n = 1.0 / (double)n;
-  if ((EPL <= 3 && QUAD_FUSED_COLS) || (EPL == 4 && QUAD_FUSED_COLS4 && LONG_COLS)) {
+  if (EPL <= 3 || LONG_COLS) {
     double acc[EPL];
     unsigned cc[EPL];
 #pragma unroll
@@ -621,39 +485,13 @@ __device__ __forceinline__ double quad_eval(const QuadLds& L, const SolveParams&
     double gj = 0.0;
     if (j < p) {
       double acc = (ic && j == 0) ? rpart : 0.0;
-      // two entries at a time where registers allow (A/B on C2: -3 % for EPL = 3; EPL = 4 spills more with it and loses 6 %)
-      acc = (EPL <= 3) ? gather_dot2(L.csc() + (colc[s] & 0xffffu), (int)(colc[s] >> 16), rs, acc)
-                       : gather_dot(L.csc() + (colc[s] & 0xffffu), (int)(colc[s] >> 16), rs, acc);
+      acc = gather_dot(L.csc() + (colc[s] & 0xffffu), (int)(colc[s] >> 16), rs, acc);
       const double reg = (j < first_reg) ? 0.0 : o.l2 * xt[s];
       gj = inv_n * (acc + reg);
     }
     g[s] = gj;
   }
   return inv_n * part;
-}
-
-// ---- the history without its shift (GDMIX_QUAD_APPEND, round 6) ------------------------------------------------------------------
-// A push shifts the whole register history down by one (54 v_mov_b64 at EPL = 3, + 9 + 9 LDS accesses for rho): the pair-push item of
-// VERDICT r5. Round 5 tried "pair a in slot a" with the slot chosen per ROW and lost to the ten compare / exec-save / branch skips
-// that needs. Here the slot is chosen per WAVEFRONT: while slots are free, every trip on which any row of the wavefront stores a pair
-// takes the next slot w for all rows (one scalar jump into ten static bodies); a row that stores nothing on that trip simply does not
-// use slot w (its mask `um` lacks the bit: a hole). Slot order is still time order for every row, so both loops of the recursion run
-// over the slots any row uses, in the same static order as before, with a row's `use` read from its mask. Once all ten slots are taken
-// a row frees, when it stores a pair, its oldest slot that holds nothing it uses (a hole, or a pair beyond its last m) — else its
-// oldest pair — by shifting the slots above it down (v_cndmask instead of v_mov: per-row start). Same pairs in the same order: same
-// bits. A/B: profiles/r06_c2_ab.txt.
-#ifndef GDMIX_QUAD_APPEND
-#define GDMIX_QUAD_APPEND 0
-#endif
-static_assert(!(GDMIX_QUAD_APPEND && (GDMIX_QUAD_LANE_STATE || GDMIX_QUAD_ZERO_STEPS)), "the append form of the history keeps rho in LDS and the masked steps");
-
-// OR of a per-entity value over the wavefront's entities (every lane of a group holds the group's value)
-template <int G>
-__device__ __forceinline__ unsigned wave_or_groups(unsigned v) {
-  unsigned r = (unsigned)__builtin_amdgcn_readlane((int)v, 0);
-  if (G < 64) r |= (unsigned)__builtin_amdgcn_readlane((int)v, 32);
-  if (G < 32) r |= (unsigned)__builtin_amdgcn_readlane((int)v, 16) | (unsigned)__builtin_amdgcn_readlane((int)v, 48);
-  return r;
 }
 
 template <int EPL>
@@ -684,22 +522,13 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
   double* const go = L.go();
   const int m = o.m;
   int cnt = 0;
-#if GDMIX_QUAD_APPEND
-  int w = 0;            // slots taken so far, the same for every row of the wavefront (M_REG: full)
-  unsigned um = 0u;     // this row's pairs in use: bit a = slot a
-#endif
   int nit = 0, nfev = 0, ifun = 0;
   int status = valid ? -1 : 0;
   bool iter0 = true, first = true;
   // nfev is scipy's funcalls: an evaluation at the point of the previous evaluation is not counted (quad_eval)
   double f = 0.0, gd = 0.0, rr = 0.0, stp = 0.0, sbgnrm = 0.0;
-#if GDMIX_QUAD_LANE_STATE
-  double rho_v = row_put<LN_THETA>(0.0, 1.0), alpha_v = 0.0;
-#endif
   if (valid) {
-#if !GDMIX_QUAD_LANE_STATE
     scal[SC_FOLD] = 0.0; scal[SC_GDOLD] = 0.0; scal[SC_THETA] = 1.0;
-#endif
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
       const int j = gl + G * s;
@@ -708,9 +537,6 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
   }
   while (__any(status < 0)) {
     bool need_dir = false, restart = false;
-#if GDMIX_QUAD_APPEND
-    bool do_push = false;
-#endif
     if (status < 0) {
       // ---- f, g at the trial point; g'd, y'y and max|g| in one reduction pass ------------------------
       bool counted;
@@ -741,14 +567,8 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
         // kernels waits for: the 15 stores alone were 2 % of the C2 step.
         int task = LS_CONV;
         {
-#if GDMIX_QUAD_LANE_STATE
-          // finit, ginit of the search are f_old, g'd_old of the iteration; gtest = ftol * ginit (dcsrch_start): same bits
-          const double ginit = row_get<LN_GDOLD>(rho_v);
-          const bool conv = dcsrch_converged(row_get<LN_FOLD>(rho_v), LS_FTOL * ginit, ginit, f, gd, stp);
-#else
           const LineSearch* const lsp = L.ls();
           const bool conv = dcsrch_converged(lsp->finit, lsp->gtest, lsp->ginit, f, gd, stp);
-#endif
           if (__any(!conv)) {
             if (!conv) {
               LineSearch LS = *L.ls();
@@ -773,11 +593,7 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
           // ---- NEW_X: scipy's python loop first (nit / maxiter / maxfun), then mainlb's own tests ---
           ++nit;
           iter0 = false;
-#if GDMIX_QUAD_LANE_STATE
-          const double fold = row_get<LN_FOLD>(rho_v);
-#else
           const double fold = scal[SC_FOLD];
-#endif
           const double dmx = fmax(fabs(fold), fmax(fabs(f), 1.0));
           if (nit >= o.max_iter) status = 2;
           else if (nfev > o.maxfun) status = 3;
@@ -785,28 +601,15 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
           else if (fold - f <= o.ftol * dmx) status = 1;
           else {
             need_dir = true;
-#if GDMIX_QUAD_LANE_STATE
-            const double gdold = row_get<LN_GDOLD>(rho_v);
-#else
             const double gdold = scal[SC_GDOLD];
-#endif
             double dr, ddum;
             if (stp == 1.0) { dr = gd - gdold; ddum = -gdold; }
             else { dr = (gd - gdold) * stp; ddum = -gdold * stp; }
-#if GDMIX_QUAD_APPEND
-            do_push = dr > EPSMCH * ddum;      // stored behind this region, where the slot is uniform (dr is formed again there: no register carries it)
-#else
             if (dr > EPSMCH * ddum) {
               // push (s, y): the history shifts down by one, newest at KR-1
-#if GDMIX_QUAD_LANE_STATE
-              {
-                const double sh = dpp_row<0x101>(rho_v);   // row_shl:1: lane a <- lane a + 1
-                rho_v = __builtin_amdgcn_inverse_ballot_w64(0x01ff01ff01ff01ffull) ? sh : rho_v;
-              }
-#else
+              // (Appending at the wavefront's next free slot instead: three times slower, rejected in round 6: profiles/r06_c2_ab.txt.)
 #pragma unroll
               for (int a = 0; a < M_REG - 1; ++a) rho[a] = rho[a + 1];
-#endif
 #pragma unroll
               for (int a = 0; a < KR - 1; ++a) {
 #pragma unroll
@@ -818,74 +621,14 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
                 S[KR - 1][s] = stp * V.d[s];   // exact for stp == 1
                 Y[KR - 1][s] = V.g[s] - ((j < p) ? go[j] : 0.0);
               }
-#if GDMIX_QUAD_LANE_STATE
-              rho_v = row_put<M_REG - 1>(rho_v, 1.0 / dr);
-              rho_v = row_put<LN_THETA>(rho_v, rr / dr);
-#else
               rho[M_REG - 1] = 1.0 / dr;
               scal[SC_THETA] = rr / dr;
-#endif
               if (cnt < m) ++cnt;
             }
-#endif
           }
         }
       }
     }
-#if GDMIX_QUAD_APPEND
-    // ---- the pairs of this trip: one slot for the whole wavefront while slots are free, then a shift per row ----------------------
-    if (__any(do_push)) {
-      double p_rho = 0.0;
-      if (do_push) {
-        const double gdold = scal[SC_GDOLD];
-        const double dr = (stp == 1.0) ? gd - gdold : (gd - gdold) * stp;      // as in the region above: same bits
-        p_rho = 1.0 / dr;
-        scal[SC_THETA] = rr / dr;
-      }
-      if (w < M_REG) {
-#define QUAD_APPEND_AT(a)                                                             \
-        case a:                                                                        \
-          if (do_push) {                                                               \
-            _Pragma("unroll") for (int s = 0; s < EPL; ++s) {                          \
-              const int j = gl + G * s;                                                \
-              S[a][s] = stp * V.d[s];                                                  \
-              Y[a][s] = V.g[s] - ((j < p) ? go[j] : 0.0);                              \
-            }                                                                          \
-          }                                                                            \
-          break;
-        switch (w) {
-          QUAD_APPEND_AT(0) QUAD_APPEND_AT(1) QUAD_APPEND_AT(2) QUAD_APPEND_AT(3) QUAD_APPEND_AT(4)
-          QUAD_APPEND_AT(5) QUAD_APPEND_AT(6) QUAD_APPEND_AT(7) QUAD_APPEND_AT(8) QUAD_APPEND_AT(9)
-          default: break;
-        }
-#undef QUAD_APPEND_AT
-        if (do_push) { rho[w] = p_rho; um |= 1u << w; }
-        ++w;
-      } else if (do_push) {
-        const unsigned freeb = ~um & ((1u << M_REG) - 1u);
-        const int k = freeb ? (__ffs((int)freeb) - 1) : 0;      // the slot this row gives up: everything above it moves down by one
-#pragma unroll
-        for (int a = 0; a < KR - 1; ++a) {
-          const bool mv = a >= k;
-#pragma unroll
-          for (int s = 0; s < EPL; ++s) { S[a][s] = mv ? S[a + 1][s] : S[a][s]; Y[a][s] = mv ? Y[a + 1][s] : Y[a][s]; }
-        }
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) {
-          const int j = gl + G * s;
-          S[KR - 1][s] = stp * V.d[s];
-          Y[KR - 1][s] = V.g[s] - ((j < p) ? go[j] : 0.0);
-        }
-        for (int a = k; a < M_REG - 1; ++a) rho[a] = rho[a + 1];
-        rho[M_REG - 1] = p_rho;
-        um = (um & ((1u << k) - 1u)) | ((um >> (k + 1)) << k) | (1u << (M_REG - 1));
-      }
-      if (do_push) {
-        if (__popc(um) > m) um &= um - 1u;      // more than the last m pairs: the oldest is not used any more
-        cnt = __popc(um);
-      }
-    }
-#endif
     // ---- new search direction for the rows that need one (again after a line-search restart) ---------
     while (__any(need_dir)) {
       if (need_dir && restart) {
@@ -894,23 +637,12 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
           const int j = gl + G * s;
           if (j < p) { V.x[s] = xo[j]; V.g[s] = go[j]; }
         }
-#if GDMIX_QUAD_LANE_STATE
-        f = row_get<LN_FOLD>(rho_v);
-#else
         f = scal[SC_FOLD];
-#endif
         restart = false;
         if (cnt == 0) { status = 4; need_dir = false; }
         else {
           cnt = 0;
-#if GDMIX_QUAD_APPEND
-          um = 0u;
-#endif
-#if GDMIX_QUAD_LANE_STATE
-          rho_v = row_put<LN_THETA>(rho_v, 1.0);
-#else
           scal[SC_THETA] = 1.0;
-#endif
         }
       }
       if (need_dir) {
@@ -921,118 +653,42 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
       // uses are M_REG-cmax .. M_REG-1 with cmax uniform: the first loop leaves at its lower end, the second enters at it (a switch
       // that falls through) — until round 5 every one of the 2 M_REG steps was skipped on its own (`if (__any(use))`: a compare, an
       // exec save and a taken branch each, ~11 of 20 skipped at C2's mean history of 4.5 pairs).
-#if GDMIX_QUAD_APPEND
-      // the slots any row of the wavefront uses in this direction: [lo, hi) (uniform); a row's own from its mask
-      const unsigned um_all = wave_or_groups<G>(need_dir ? um : 0u);
-      const int lo = um_all ? (__ffs((int)um_all) - 1) : M_REG, hi = um_all ? (32 - __clz((int)um_all)) : 0;
-#define QUAD_USE(a) (need_dir && ((um >> (a)) & 1u))
-#define QUAD_FIRST_EXIT(a) if ((a) < lo) goto first_loop_done;
-#define QUAD_SECOND_EXIT(a) if ((a) >= hi) goto second_loop_done;
-#else
+      // (Zero-multiplier steps for the rows that do not use a pair, instead of masked ones: slower, rejected in round 6: profiles/r06_c2_ab.txt.)
       const int cmax = wave_max_nonneg_i32(need_dir ? cnt : 0);
       const int a0 = M_REG - cmax;
-#define QUAD_USE(a) (need_dir && ((a) >= M_REG - cnt))
-#define QUAD_FIRST_EXIT(a) if ((a) < a0) goto first_loop_done;
-#define QUAD_SECOND_EXIT(a)
-#endif
-#if GDMIX_QUAD_LANE_STATE
-#define QUAD_RHO(a) row_get<a>(rho_v)
-#define QUAD_ALPHA(a) row_get<a>(alpha_v)
-#define QUAD_SET_ALPHA(a, v) alpha_v = row_put<a>(alpha_v, v)
-#else
-#define QUAD_RHO(a) rho[a]
-#define QUAD_ALPHA(a) alpha[a]
-#define QUAD_SET_ALPHA(a, v) alpha[a] = (v)
-#endif
-      // GDMIX_QUAD_ZERO_STEPS (round 6): a row that does not use pair a takes the step with a zero multiplier instead of sitting it
-      // out under an exec mask — d - 0 * y is d (the stored pairs are finite), and the wave saves the exec save / branch / restore
-      // and the copies of d the compiler placed behind every masked region (three v_mov_b64 a step at EPL = 3).
-      // Measured (profiles/r06_c2_ab.txt): <32,3> alone 4.50 -> 4.52 ms, <16,4> 2.41 -> 2.77 ms (the compiler keeps more of d live: 70 -> 84
-      // spilled registers), step 9.04 -> 9.43 ms. Off.
-#ifndef GDMIX_QUAD_ZERO_STEPS
-#define GDMIX_QUAD_ZERO_STEPS 0
-#endif
-#if GDMIX_QUAD_ZERO_STEPS
 #define QUAD_FIRST_LOOP_STEP(a)                                                   \
       {                                                                           \
         if ((a) < a0) goto first_loop_done;                                       \
         const bool use = need_dir && ((a) >= M_REG - cnt);                        \
-        double t = 0.0;                                                           \
-        _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += S[a][s] * V.d[s];    \
-        const double nal = use ? -(QUAD_RHO(a) * grp_sum<G>(t, X)) : 0.0;         \
-        QUAD_SET_ALPHA(a, -nal);                                                  \
-        _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] = fma(nal, Y[a][s], V.d[s]); \
+        if (use) {                                                                \
+          double t = 0.0;                                                         \
+          _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += S[a][s] * V.d[s];  \
+          const double al = rho[a] * grp_sum<G>(t, X);                            \
+          alpha[a] = al;                                                          \
+          _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] -= al * Y[a][s]; \
+        }                                                                         \
+      }
+      static_assert(M_REG == 10, "the steps below are written out for ten pairs");
+      QUAD_FIRST_LOOP_STEP(9) QUAD_FIRST_LOOP_STEP(8) QUAD_FIRST_LOOP_STEP(7) QUAD_FIRST_LOOP_STEP(6) QUAD_FIRST_LOOP_STEP(5)
+      QUAD_FIRST_LOOP_STEP(4) QUAD_FIRST_LOOP_STEP(3) QUAD_FIRST_LOOP_STEP(2) QUAD_FIRST_LOOP_STEP(1) QUAD_FIRST_LOOP_STEP(0)
+#undef QUAD_FIRST_LOOP_STEP
+    first_loop_done:;
+      if (need_dir && cnt > 0) {
+        const double h0 = 1.0 / scal[SC_THETA];
+#pragma unroll
+        for (int s = 0; s < EPL; ++s) V.d[s] *= h0;
       }
 #define QUAD_SECOND_LOOP_STEP(a)                                                  \
       {                                                                           \
         const bool use = need_dir && ((a) >= M_REG - cnt);                        \
-        double t = 0.0;                                                           \
-        _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += Y[a][s] * V.d[s];    \
-        const double c = use ? QUAD_ALPHA(a) - QUAD_RHO(a) * grp_sum<G>(t, X) : 0.0; \
-        _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] += c * S[a][s];    \
-      }
-#else
-#define QUAD_FIRST_LOOP_STEP(a)                                                   \
-      {                                                                           \
-        QUAD_FIRST_EXIT(a)                                                        \
-        const bool use = QUAD_USE(a);                                             \
-        if (use) {                                                                \
-          double t = 0.0;                                                         \
-          _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += S[a][s] * V.d[s];  \
-          const double al = QUAD_RHO(a) * grp_sum<G>(t, X);                       \
-          QUAD_SET_ALPHA(a, al);                                                  \
-          _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] -= al * Y[a][s]; \
-        }                                                                         \
-      }
-#endif
-      static_assert(M_REG == 10, "the steps below are written out for ten pairs");
-#if GDMIX_QUAD_APPEND
-      switch (hi) {      // newest slot in use first
-        case 10: QUAD_FIRST_LOOP_STEP(9) [[fallthrough]];
-        case 9: QUAD_FIRST_LOOP_STEP(8) [[fallthrough]];
-        case 8: QUAD_FIRST_LOOP_STEP(7) [[fallthrough]];
-        case 7: QUAD_FIRST_LOOP_STEP(6) [[fallthrough]];
-        case 6: QUAD_FIRST_LOOP_STEP(5) [[fallthrough]];
-        case 5: QUAD_FIRST_LOOP_STEP(4) [[fallthrough]];
-        case 4: QUAD_FIRST_LOOP_STEP(3) [[fallthrough]];
-        case 3: QUAD_FIRST_LOOP_STEP(2) [[fallthrough]];
-        case 2: QUAD_FIRST_LOOP_STEP(1) [[fallthrough]];
-        case 1: QUAD_FIRST_LOOP_STEP(0) [[fallthrough]];
-        default: break;
-      }
-#else
-      QUAD_FIRST_LOOP_STEP(9) QUAD_FIRST_LOOP_STEP(8) QUAD_FIRST_LOOP_STEP(7) QUAD_FIRST_LOOP_STEP(6) QUAD_FIRST_LOOP_STEP(5)
-      QUAD_FIRST_LOOP_STEP(4) QUAD_FIRST_LOOP_STEP(3) QUAD_FIRST_LOOP_STEP(2) QUAD_FIRST_LOOP_STEP(1) QUAD_FIRST_LOOP_STEP(0)
-#endif
-#undef QUAD_FIRST_LOOP_STEP
-    first_loop_done:;
-      if (need_dir && cnt > 0) {
-#if GDMIX_QUAD_LANE_STATE
-        const double h0 = 1.0 / row_get<LN_THETA>(rho_v);
-#else
-        const double h0 = 1.0 / scal[SC_THETA];
-#endif
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) V.d[s] *= h0;
-      }
-#if !GDMIX_QUAD_ZERO_STEPS
-#define QUAD_SECOND_LOOP_STEP(a)                                                  \
-      {                                                                           \
-        QUAD_SECOND_EXIT(a)                                                       \
-        const bool use = QUAD_USE(a);                                             \
         if (use) {                                                                \
           double t = 0.0;                                                         \
           _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += Y[a][s] * V.d[s];  \
-          const double c = QUAD_ALPHA(a) - QUAD_RHO(a) * grp_sum<G>(t, X);        \
+          const double c = alpha[a] - rho[a] * grp_sum<G>(t, X);                  \
           _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] += c * S[a][s];  \
         }                                                                         \
       }
-#endif
-#if GDMIX_QUAD_APPEND
-      switch (lo) {
-#else
       switch (a0) {
-#endif
         case 0: QUAD_SECOND_LOOP_STEP(0) [[fallthrough]];
         case 1: QUAD_SECOND_LOOP_STEP(1) [[fallthrough]];
         case 2: QUAD_SECOND_LOOP_STEP(2) [[fallthrough]];
@@ -1045,16 +701,7 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
         case 9: QUAD_SECOND_LOOP_STEP(9) [[fallthrough]];
         default: break;
       }
-#if GDMIX_QUAD_APPEND
-    second_loop_done:;
-#endif
-#undef QUAD_USE
-#undef QUAD_FIRST_EXIT
-#undef QUAD_SECOND_EXIT
 #undef QUAD_SECOND_LOOP_STEP
-#undef QUAD_RHO
-#undef QUAD_ALPHA
-#undef QUAD_SET_ALPHA
       if (need_dir) {
         // z = x + d ; d = z - x (mainlb re-derives d from the subspace point); save x, g
         double dd = 0.0, gdp = 0.0;
@@ -1071,13 +718,8 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
         }
         grp_sum2<G>(dd, gdp, X);
         gd = gdp;
-#if GDMIX_QUAD_LANE_STATE
-        rho_v = row_put<LN_GDOLD>(rho_v, gd);
-        rho_v = row_put<LN_FOLD>(rho_v, f);
-#else
         scal[SC_GDOLD] = gd;
         scal[SC_FOLD] = f;
-#endif
         if (gd >= 0.0) {
           restart = true;   // lnsrlb info = -4: stay in this loop
         } else {

@@ -22,28 +22,14 @@
 
 namespace gdmix {
 
-// -DGDMIX_TEAM_PROFILE: thread 0 of a team's first workgroup accumulates wall-clock ticks (100 MHz) per phase
-// and prints them per entity. Exploration only.
-#ifdef GDMIX_TEAM_PROFILE
-#define TEAM_PROF_DECL unsigned long long prof_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long prof_last = wall_clock64();
-#define TEAM_PROF(i) do { const unsigned long long _n = wall_clock64(); prof_t[i] += _n - prof_last; prof_last = _n; } while (0)
-#else
-#define TEAM_PROF_DECL
-#define TEAM_PROF(i) do { } while (0)
-#endif
-
-// GDMIX_TEAM_DIRECT_AB=1 (round 6, the default): the team kernels take S'g and Y'g directly too (re_lbfgs_compact.hpp: why) — 20 more
-// accumulators in registers and a reduction of 47 values instead of 27. With two tiles per trip at every history length that
-// spilled 152 registers and cost 5 % on a Zipf partition; with one tile per trip from GDMIX_TEAM_DIRECT_ONE_TILE_FROM + 1 pairs on
-// it spills fewer than before (17) and costs 1.7 - 1.9 % (C5 share 700 -> 714 ms, profiles/r06_fuzz.txt). =0: the sums of round 3.
-#ifndef GDMIX_TEAM_DIRECT_AB
-#define GDMIX_TEAM_DIRECT_AB 1
-#endif
+// The team kernels take S'g and Y'g directly (round 6; re_lbfgs_compact.hpp: why) — 20 more accumulators in registers and a
+// reduction of 47 values instead of 27. With two tiles per trip at every history length that spilled 152 registers and cost 5 % on a
+// Zipf partition; with one tile per trip from GDMIX_TEAM_DIRECT_ONE_TILE_FROM + 1 pairs on it spills 17 and costs 1.7 - 1.9 % (C5
+// share 700 -> 714 ms, profiles/r06_fuzz.txt).
 #ifndef GDMIX_TEAM_DIRECT_ONE_TILE_FROM
 #define GDMIX_TEAM_DIRECT_ONE_TILE_FROM 5
 #endif
-constexpr int TEAM_KX = GDMIX_TEAM_DIRECT_AB ? COMPACT_KD : TEAM_K;   // the team's accumulators: [0, TEAM_K - 1) as acc[], then S'g, Y'g (direct only), max|g| LAST
-constexpr int TEAM_VEC = GDMIX_TEAM_DIRECT_AB ? 48 : 32;   // doubles per workgroup slot of the device-wide exchange buffer
+constexpr int TEAM_VEC = 48;   // doubles per workgroup slot of the device-wide exchange buffer
 constexpr int TEAM_MAX_BLOCKS = 256;           // workgroups per team
 constexpr int TEAM_MAX_TEAMS = 256;
 constexpr int TEAM_SHORT_COL = 16;            // tiles whose columns are all this short: one lane per column
@@ -268,11 +254,7 @@ __device__ __forceinline__ double gather_dot8(const float* __restrict__ val, con
 // wavefront index + k * wavefronts of the team, lane = coefficient inside the tile) — and returns the loss sum.
 // SC1: x, the residuals and the partial sums of split columns are exchanged through sc1 accesses (ld_x / st_x above).
 template <int NW, bool SC1>
-__device__ __forceinline__ double team_fg(Team<NW>& tm, const EntityView& P, const SolveParams& o, const Work& W
-#ifdef GDMIX_TEAM_PROFILE
-                                          , unsigned long long (&prof_t)[8], unsigned long long& prof_last
-#endif
-                                          ) {
+__device__ __forceinline__ double team_fg(Team<NW>& tm, const EntityView& P, const SolveParams& o, const Work& W) {
   const int n = P.n, p = P.p, ic = P.ic;
   const double* __restrict__ x = W.x;
   // ---- rows: logits, per-sample loss and residual
@@ -294,9 +276,7 @@ __device__ __forceinline__ double team_fg(Team<NW>& tm, const EntityView& P, con
     st_x<SC1>(W.rs + i, ri);
     pr[1] += ri;
   }
-  TEAM_PROF(0);
   tm.reduce(pr);   // also makes rs[] visible to the whole team
-  TEAM_PROF(1);
   const double loss = pr[0], rsum = pr[1];
   // ---- columns: X'r by tiles of 64 coefficients per wavefront, lane c of the tile ends up owning column c
   const int first_reg = (ic && !o.regularize_bias) ? 1 : 0;
@@ -429,7 +409,6 @@ __device__ __forceinline__ double team_fg(Team<NW>& tm, const EntityView& P, con
       W.g[j] = inv_n * (a + ((j < first_reg) ? 0.0 : o.l2 * ld_x<SC1>(x + j)));
     }
   }
-  TEAM_PROF(2);
   return loss;
 }
 
@@ -439,10 +418,10 @@ __device__ __forceinline__ double team_fg(Team<NW>& tm, const EntityView& P, con
 // same order either way: the sums do not depend on the tiles per trip.
 template <int NW, int HC>
 __device__ __forceinline__ void team_products(const Team<NW>& tm, const Work& W, int p, int m, int col, int head, int first_reg,
-                                              double (&acc)[TEAM_KX]) {
+                                              double (&acc)[COMPACT_KD]) {
   const double* __restrict__ x = W.x;
-  // (with the direct products the long histories go one tile per trip: their 2 x HC pairs and 4 HC + 7 accumulators do not fit the registers)
-  constexpr int T = (GDMIX_TEAM_DIRECT_AB && HC > GDMIX_TEAM_DIRECT_ONE_TILE_FROM) ? 1 : 2;
+  // (the long histories go one tile per trip: their 2 x HC pairs and 4 HC + 7 accumulators do not fit the registers)
+  constexpr int T = (HC > GDMIX_TEAM_DIRECT_ONE_TILE_FROM) ? 1 : 2;
   for (int tile = tm.wid; tile * WAVE < p; tile += T * tm.nwaves) {
     int jv[T];
     bool ok[T];
@@ -472,16 +451,14 @@ __device__ __forceinline__ void team_products(const Team<NW>& tm, const Work& W,
         acc[3] += yj * yj;
         acc[4] += yj * gj[u];
         acc[TEAM_RD] += rj[u] * dj[u];
-        acc[TEAM_KX - 1] = fmax(acc[TEAM_KX - 1], fabs(gj[u]));
+        acc[COMPACT_KD - 1] = fmax(acc[COMPACT_KD - 1], fabs(gj[u]));
 #pragma unroll
         for (int i = 0; i < HC; ++i) {
           const double hx = i < col ? h[u][i].x : 0.0, hy = i < col ? h[u][i].y : 0.0;
           acc[5 + i] += hx * yj;
           acc[5 + TEAM_MCAP + i] += hy * yj;
-          if (GDMIX_TEAM_DIRECT_AB) {
-            acc[TEAM_K - 1 + i] += hx * gj[u];
-            acc[TEAM_K - 1 + TEAM_MCAP + i] += hy * gj[u];
-          }
+          acc[TEAM_K - 1 + i] += hx * gj[u];
+          acc[TEAM_K - 1 + TEAM_MCAP + i] += hy * gj[u];
         }
       }
     }
@@ -489,31 +466,21 @@ __device__ __forceinline__ void team_products(const Team<NW>& tm, const Work& W,
 }
 
 // f, g and every dot product the driver needs, at W.x, all vectors in HBM. acc[] layout: 0 sum x_j^2 over regularised j,
-// 1 g'd, 2 g'g, 3 y'y, 4 y'g, 5.. S_i'y, 5+MCAP.. Y_i'y (y = g - r; chronological i < col), TEAM_RD r'd, then (direct products)
+// 1 g'd, 2 g'g, 3 y'y, 4 y'g, 5.. S_i'y, 5+MCAP.. Y_i'y (y = g - r; chronological i < col), TEAM_RD r'd, then
 // S_i'g, Y_i'g, and max|g_j| last (Team::reduce takes the maximum of its last value).
 template <int NW>
 __device__ __forceinline__ double team_eval(Team<NW>& tm, const EntityView& P, const SolveParams& o, const Work& W,
-                                            int col, int head, double (&acc)[TEAM_KX]
-#ifdef GDMIX_TEAM_PROFILE
-                                            , unsigned long long (&prof_t)[8], unsigned long long& prof_last
-#endif
-                                            ) {
+                                            int col, int head, double (&acc)[COMPACT_KD]) {
   const int n = P.n, p = P.p, ic = P.ic, m = o.m;
   const int first_reg = (ic && !o.regularize_bias) ? 1 : 0;
   const double inv_n = o.sum_loss ? 1.0 : 1.0 / (double)n;
-#ifdef GDMIX_TEAM_PROFILE
-  const double loss = team_fg<NW, false>(tm, P, o, W, prof_t, prof_last);
-#else
   const double loss = team_fg<NW, false>(tm, P, o, W);
-#endif
   // Products with the gradient in a second sweep over the same coefficients (the thread that stored g[j] reads it
   // back: no synchronisation), so that the accumulators and the tile staging above are not live at the same time.
 #pragma unroll
-  for (int k = 0; k < TEAM_KX; ++k) acc[k] = 0.0;
+  for (int k = 0; k < COMPACT_KD; ++k) acc[k] = 0.0;
   GDMIX_HIST_DISPATCH(col, (team_products<NW, HC>(tm, W, p, m, col, head, first_reg, acc)))
-  TEAM_PROF(2);
   tm.reduce(acc);
-  TEAM_PROF(3);
   return inv_n * (loss + 0.5 * o.l2 * acc[0]);
 }
 
@@ -554,8 +521,7 @@ __device__ __forceinline__ void team_solve(Team<NW>& tm, const EntityView& P, co
   CompactState S;
   compact_init(S);
   CompactPlan plan;
-  double acc[TEAM_KX];
-  TEAM_PROF_DECL
+  double acc[COMPACT_KD];
   for (int j = tm.tid; j < p; j += tm.NT) { W.d[j] = 0.0; W.r[j] = 0.0; }
   tm.sync();
   unsigned upd = 0;   // updates so far = trials formed
@@ -563,24 +529,15 @@ __device__ __forceinline__ void team_solve(Team<NW>& tm, const EntityView& P, co
   tm.sync();
   for (;;) {
     tm.moved_clear(upd + 1u);   // the slot the next update uses
-#ifdef GDMIX_TEAM_PROFILE
-    const double f_new = team_eval(tm, P, o, W, S.col, S.head, acc, prof_t, prof_last);
-#else
     const double f_new = team_eval(tm, P, o, W, S.col, S.head, acc);
-#endif
     if (tm.aborted()) { ++S.nfev; S.status = GDMIX_RE_ST_ABORTED; break; }
-#if GDMIX_TEAM_DIRECT_AB
     {
       double a[TEAM_K];
 #pragma unroll
       for (int k = 0; k < TEAM_K - 1; ++k) a[k] = acc[k];
-      a[TEAM_K - 1] = acc[TEAM_KX - 1];
+      a[TEAM_K - 1] = acc[COMPACT_KD - 1];
       compact_advance(S, a, f_new, o, L.mats, plan, tm.moved_get(upd), acc + (TEAM_K - 1));
     }
-#else
-    compact_advance(S, acc, f_new, o, L.mats, plan, tm.moved_get(upd));
-#endif
-    TEAM_PROF(4);
     if (plan.action == CA_STOP) break;
     if (plan.action == CA_STOP_RESTORE) {
       for (int j = tm.tid; j < p; j += tm.NT) W.x[j] = W.t[j];
@@ -593,16 +550,8 @@ __device__ __forceinline__ void team_solve(Team<NW>& tm, const EntityView& P, co
       GDMIX_HIST_DISPATCH((plan.action == CA_DIRECTION ? plan.col : 0),
                           for (int j = tm.tid; j < p; j += tm.NT) compact_update_n<HC>(plan, L.mats, W, p, m, j, mv))
     }
-    TEAM_PROF(5);
     tm.sync();
-    TEAM_PROF(6);
   }
-#ifdef GDMIX_TEAM_PROFILE
-  if (tm.tid == 0 && blockIdx.x % 64 == 0)   // a few lines only: device printf perturbs the other workgroups
-    printf("team n=%d p=%d nfev=%d us/eval: rows %.1f red1 %.1f cols %.1f red2 %.1f solve %.1f upd %.1f sync %.1f\n", P.n, p, S.nfev,
-           prof_t[0] * 0.01 / S.nfev, prof_t[1] * 0.01 / S.nfev, prof_t[2] * 0.01 / S.nfev, prof_t[3] * 0.01 / S.nfev,
-           prof_t[4] * 0.01 / S.nfev, prof_t[5] * 0.01 / S.nfev, prof_t[6] * 0.01 / S.nfev);
-#endif
   out.f = S.f;
   out.gnorm = S.sbgnrm;
   out.nit = S.nit;
