@@ -22,7 +22,7 @@ class RawBatch:
     uid: Optional[np.ndarray] = None     # int64 [N] sample ids (scoring output only)
     entity_ids: Optional[List[str]] = None  # [E] str(entity id) as job_consumers.py:235-239 renders it
     has_label: bool = True
-    binary_labels: bool = True              # False: real-valued labels (fixed-effect linear regression)
+    binary_labels: bool = True              # False: real-valued labels (linear regression, fixed or random effect)
     trusted: bool = False                   # built by the native reader, which checked all of validate() while decoding
 
     def __post_init__(self):
@@ -115,7 +115,7 @@ class RawBatch:
             weight=None if self.weight is None else self.weight[rows],
             uid=None if self.uid is None else self.uid[rows],
             entity_ids=None if self.entity_ids is None else [self.entity_ids[i] for i in ents],
-            has_label=self.has_label)
+            has_label=self.has_label, binary_labels=self.binary_labels)
 
 
 class WireRawBatch(RawBatch):
@@ -125,10 +125,11 @@ class WireRawBatch(RawBatch):
     col_global) exist only if somebody asks for them (host-side consumers: select(), the CPU stand-ins of the tests), rebuilt then by a
     cumsum and a widening copy."""
 
-    def __init__(self, ent_row_ptr, ent_n, row_nnz, col, val, y, y8, offset, weight=None, uid=None, entity_ids=None, has_label=True):
+    def __init__(self, ent_row_ptr, ent_n, row_nnz, col, val, y, y8, offset, weight=None, uid=None, entity_ids=None, has_label=True,
+                 binary_labels=True):
         d = self.__dict__
         d.update(ent_row_ptr=ent_row_ptr, val=val, y=y, offset=offset, weight=weight, uid=uid, entity_ids=entity_ids, has_label=has_label,
-                 binary_labels=True, trusted=True, _ent_n=ent_n, _row_nnz=row_nnz, _col=col, _y8=y8, _row_nnz_ptr=None, _col_global=None)
+                 binary_labels=binary_labels, trusted=True, _ent_n=ent_n, _row_nnz=row_nnz, _col=col, _y8=y8, _row_nnz_ptr=None, _col_global=None)
 
     @property
     def row_nnz_ptr(self):
@@ -210,4 +211,4 @@ def concat(batches):
                                for b in batches]) if any_w else None,
         uid=np.concatenate([b.uid for b in batches]) if any_u else None,
         entity_ids=sum([list(b.entity_ids) for b in batches], []) if any_id else None,
-        has_label=all(b.has_label for b in batches))
+        has_label=all(b.has_label for b in batches), binary_labels=all(b.binary_labels for b in batches))

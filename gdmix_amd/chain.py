@@ -12,7 +12,8 @@ What gdmix-workflow schedules for gdmix-workflow/test/resources/lr-movieLens.yam
     per-movie partition, train    -> the same with the per-user stage's scores as offsets
 
 Every stage's predictionScore is the accumulated logit so far (X theta + offset), stored as Avro `float`; the next stage's offset is
-that float. Only the first iteration is run, as the reference's workflow does: no per-coordinate score is subtracted
+that float. With model_type="linear_regression" the three stages train the squared loss on the ratings themselves (data["rating"], real-valued labels)
+and report the mean squared error of the accumulated score instead of the AUC (the `mse` branch of gdmix-data's Evaluator.scala). Only the first iteration is run, as the reference's workflow does: no per-coordinate score is subtracted
 (OffsetUpdater's dFPerCoordinateScoreOpt = None), though update_offsets takes one.
 
 The stages run through `gdmix_amd.gdmix` exactly as gdmix-workflow would start them (in this process, or as child processes);
@@ -28,6 +29,7 @@ import time
 import numpy as np
 
 from . import partitioner
+from .constants import LINEAR_REGRESSION as LINEAR, LOGISTIC_REGRESSION as LOGISTIC
 from .io import avro, tfrecord
 
 USERS, MOVIES, RATINGS = 943, 1682, 100_000        # MovieLens-100K (scripts/download_process_movieLens_data.py:378-462)
@@ -104,7 +106,10 @@ def make_dataset(users=USERS, movies=MOVIES, ratings=RATINGS, seed=20240603, tra
          + np.bincount(rows_u, uvals * v[movie[rows_u], ucols], ratings) + c[movie])
     y = (rng.random(ratings) < 1.0 / (1.0 + np.exp(-z))).astype(np.int64)
     train = rng.random(ratings) < train_fraction
-    return dict(n=ratings, uid=np.arange(ratings, dtype=np.int64) + 1000, user=user.astype(np.int64) + 1, movie=movie.astype(np.int64) + 1,
+    # the rating behind the thresholded response, 1 .. 5 stars: the regression target of model_type="linear_regression" (drawn last, so
+    # that every other array is what it was before the key existed)
+    rating = np.clip(np.rint(3.0 + 0.9 * z + 0.6 * rng.standard_normal(ratings)), 1.0, 5.0).astype(np.float32)
+    return dict(n=ratings, rating=rating, uid=np.arange(ratings, dtype=np.int64) + 1000, user=user.astype(np.int64) + 1, movie=movie.astype(np.int64) + 1,
                 response=y, train=train, true_logit=z,
                 bags={"global": (gptr, gcols, gvals, D_GLOBAL), "per_user": (mptr, mcols, mvals, D_MOVIE_FEATS),
                       "per_movie": (uptr, ucols, uvals, D_USER_FEATS)},
@@ -125,21 +130,29 @@ def _feature_file(path, dim, prefix):
         f.write("".join(f"{prefix}{i},\n" for i in range(dim)))
 
 
-def write_global_inputs(root, data, files=4):
+def labels_of(data, model_type):
+    """The label column of the chain: the 0/1 response, or the rating itself for linear_regression."""
+    return data["rating"] if model_type == LINEAR else data["response"]
+
+
+def write_global_inputs(root, data, files=4, model_type=LOGISTIC):
     """The fixed-effect stage's inputs: per-record tf.train.Example files (train / validation), metadata, feature list."""
+    linear = model_type == LINEAR
+    label = labels_of(data, model_type)
     d = os.path.join(root, "global")
     for name, rows in (("trainingData", np.flatnonzero(data["train"])), ("validationData", np.flatnonzero(~data["train"]))):
         os.makedirs(os.path.join(d, name), exist_ok=True)
         ptr, cols, vals, dim = bag_rows(data, "global", rows)
         cuts = np.linspace(0, rows.size, files + 1).astype(int)
         for f in range(files):
-            recs = [tfrecord.encode_example({"uid": ("int64", [int(data["uid"][rows[i]])]), "response": ("int64", [int(data["response"][rows[i]])]),
+            recs = [tfrecord.encode_example({"uid": ("int64", [int(data["uid"][rows[i]])]),
+                                             "response": ("float", [float(label[rows[i]])]) if linear else ("int64", [int(label[rows[i]])]),
                                              "global_indices": ("int64", cols[ptr[i]:ptr[i + 1]]), "global_values": ("float", vals[ptr[i]:ptr[i + 1]])})
                     for i in range(cuts[f], cuts[f + 1])]
             tfrecord.write_records(os.path.join(d, name, f"part-{f:05d}.tfrecord"), recs)
     md = {"features": [{"name": "uid", "dtype": "long", "shape": [], "isSparse": False},
                        {"name": "global", "dtype": "float", "shape": [D_GLOBAL], "isSparse": True}],
-          "labels": [{"name": "response", "dtype": "int", "shape": [], "isSparse": False}]}
+          "labels": [{"name": "response", "dtype": "float" if linear else "int", "shape": [], "isSparse": False}]}
     os.makedirs(os.path.join(d, "metadata"), exist_ok=True)
     with open(os.path.join(d, "metadata", "tensor_metadata.json"), "w") as f:
         json.dump(md, f)
@@ -162,12 +175,14 @@ def read_scores(score_dir):
             np.array([np.nan if x is None else x for x in lab], np.float32))
 
 
-def partition_stage(root, data, stage, prev_train_scores, prev_valid_scores, num_partitions=4, upper_bound=None):
+def partition_stage(root, data, stage, prev_train_scores, prev_valid_scores, num_partitions=4, upper_bound=None, model_type=LOGISTIC):
     """The Spark partition job ahead of a random-effect stage (DataPartitioner.scala:203-380), host side: offsets from the previous
     stage's score files (update_offsets: inner join on uid, FLOAT), grouping by entity, Java-hash partition ids, active/ layout."""
     ent_col = data["entity"][stage]
     ent = data["user"] if stage == "per_user" else data["movie"]
     out = os.path.join(root, stage, "partition")
+    linear = model_type == LINEAR
+    label = labels_of(data, model_type)
     parts = set()
     for name, mask, scores, split in (("trainingData", data["train"], prev_train_scores, True), ("validationData", ~data["train"], prev_valid_scores, False)):
         rows_all = np.flatnonzero(mask)
@@ -177,8 +192,8 @@ def partition_stage(root, data, stage, prev_train_scores, prev_valid_scores, num
         ptr, cols, vals, dim = bag_rows(data, stage, rows)
         # training data: an entity with more than upper_bound samples keeps group 0 (uid mod (count / upper_bound + 1)) as ACTIVE data,
         # trained on; its other groups are PASSIVE data, only scored (DataPartitioner.scala:322-380)
-        batches = partitioner.build_batches(ent[rows], data["uid"][rows], data["response"][rows].astype(np.float32), off, None, ptr, cols, vals,
-                                            num_partitions, upper_bound=upper_bound if split else None, split=split)
+        batches = partitioner.build_batches(ent[rows], data["uid"][rows], label[rows].astype(np.float32), off, None, ptr, cols, vals,
+                                            num_partitions, upper_bound=upper_bound if split else None, split=split, binary_labels=not linear)
         partitioner.write_partitions(os.path.join(out, name), batches, ent_col, stage, int_entity_ids=True, weight_column_name=None)
         if split:
             parts |= {p for (_, p) in batches}
@@ -187,7 +202,7 @@ def partition_stage(root, data, stage, prev_train_scores, prev_valid_scores, num
                        {"name": "offset", "dtype": "float", "shape": [], "isSparse": False},
                        {"name": "uid", "dtype": "long", "shape": [], "isSparse": False},
                        {"name": ent_col, "dtype": "long", "shape": [], "isSparse": False}],
-          "labels": [{"name": "response", "dtype": "int", "shape": [], "isSparse": False}]}
+          "labels": [{"name": "response", "dtype": "float" if linear else "int", "shape": [], "isSparse": False}]}
     os.makedirs(os.path.join(out, "metadata"), exist_ok=True)
     with open(os.path.join(out, "metadata", "tensor_metadata.json"), "w") as f:
         json.dump(md, f)
@@ -197,25 +212,36 @@ def partition_stage(root, data, stage, prev_train_scores, prev_valid_scores, num
     return out
 
 
-COMMON = ["--model_type=logistic_regression", "--uid_column_name=uid", "--label_column_name=response",
+COMMON = ["--uid_column_name=uid", "--label_column_name=response",
           "--prediction_score_column_name=predictionScore", "--l2_reg_weight=1.0", "--regularize_bias=False",
           "--lbfgs_tolerance=1.0e-12", "--num_of_lbfgs_iterations=100", "--num_of_lbfgs_curvature_pairs=10"]
 
 
-def stage_argv(root, stage):
+def stage_argv(root, stage, model_type=LOGISTIC):
     """The flat argv gdmix-workflow would hand the trainer for this stage of lr-movieLens.yaml (output under <root>/<stage>/)."""
     out = os.path.join(root, stage)
+    common = [f"--model_type={model_type}"] + COMMON
     if stage == "global":
         d = os.path.join(root, "global")
         return ["gdmix", "--stage=fixed_effect", "--action=train", f"--training_data_dir={d}/trainingData", f"--validation_data_dir={d}/validationData",
                 f"--metadata_file={d}/metadata/tensor_metadata.json", f"--feature_file={d}/featureList", "--feature_bag=global",
-                f"--output_model_dir={out}/models", f"--training_score_dir={out}/trainingScores", f"--validation_score_dir={out}/validationScores"] + COMMON
+                f"--output_model_dir={out}/models", f"--training_score_dir={out}/trainingScores", f"--validation_score_dir={out}/validationScores"] + common
     p = os.path.join(out, "partition")
     return ["gdmix", "--stage=random_effect", "--action=train", f"--partition_list_file={p}/partitionList.txt", f"--training_data_dir={p}/trainingData",
             f"--validation_data_dir={p}/validationData", f"--metadata_file={p}/metadata/tensor_metadata.json", f"--feature_file={p}/featureList",
             f"--feature_bag={stage}", f"--partition_entity={'user_id' if stage == 'per_user' else 'movie_id'}",
             f"--output_model_dir={out}/models", f"--training_score_dir={out}/trainingScores", f"--validation_score_dir={out}/validationScores",
-            "--enable_local_indexing=False", "--num_of_consumers=1", "--max_training_queue_size=10"] + COMMON
+            "--enable_local_indexing=False", "--num_of_consumers=1", "--max_training_queue_size=10"] + common
+
+
+def global_training_scores_argv(root):
+    """linear_regression: the fixed effect writes no training scores after training (fe_model.py, as the reference:
+    fixed_effect_lr_lbfgs_model.py:106-110), and the per-user partition job needs them as offsets. They come from an inference run of the
+    trained model over the training data — the fixed-effect driver scores --validation_data_dir into --validation_score_dir."""
+    d, out = os.path.join(root, "global"), os.path.join(root, "global")
+    return ["gdmix", "--stage=fixed_effect", "--action=inference", f"--validation_data_dir={d}/trainingData", f"--metadata_file={d}/metadata/tensor_metadata.json",
+            f"--feature_file={d}/featureList", "--feature_bag=global", f"--output_model_dir={out}/models", f"--validation_score_dir={out}/trainingScores",
+            f"--model_type={LINEAR}"] + COMMON
 
 
 def run_stage(argv, child_process=False):
@@ -251,11 +277,22 @@ def auc(label, score):
     return float((ranks[pos].sum() - n1 * (n1 + 1) / 2.0) / (n1 * n0)) if n1 and n0 else float("nan")
 
 
-def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper_bounds=None):
+def mse(label, score):
+    """Mean of (label - score)^2: what gdmix-data's Evaluator reports per stage for a regression (`mse`)."""
+    d = np.asarray(label, np.float64) - np.asarray(score, np.float64)
+    return float(np.mean(d * d)) if d.size else float("nan")
+
+
+def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper_bounds=None, model_type=LOGISTIC):
     """global -> per_user -> per_movie under `root`; -> {stage: {"s", "partition_s", "train_auc", "validation_auc"}, "total_s"}.
-    upper_bounds: {stage: active-data bound per entity} (the rest of a larger entity's samples is passive data)."""
+    upper_bounds: {stage: active-data bound per entity} (the rest of a larger entity's samples is passive data).
+    model_type="linear_regression": every stage gets that model type, the labels are the ratings (real-valued), and a stage reports
+    "train_mse" / "validation_mse" instead of the AUC."""
+    if model_type not in (LOGISTIC, LINEAR):
+        raise ValueError(f"model type {model_type!r}: the chain runs logistic_regression and linear_regression")
+    metric = "mse" if model_type == LINEAR else "auc"
     os.makedirs(root, exist_ok=True)
-    write_global_inputs(root, data)
+    write_global_inputs(root, data, model_type=model_type)
     out = {}
     prev = None
     t_all = time.perf_counter()
@@ -264,19 +301,21 @@ def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper
         if stage != "global":
             t = time.perf_counter()
             partition_stage(root, data, stage, os.path.join(root, prev, "trainingScores"), os.path.join(root, prev, "validationScores"), num_partitions,
-                            upper_bound=(upper_bounds or {}).get(stage))
+                            upper_bound=(upper_bounds or {}).get(stage), model_type=model_type)
             t_part = time.perf_counter() - t
         t = time.perf_counter()
-        run_stage(stage_argv(root, stage), child_process)
+        run_stage(stage_argv(root, stage, model_type), child_process)
+        if stage == "global" and model_type == LINEAR:
+            run_stage(global_training_scores_argv(root), child_process)
         dt = time.perf_counter() - t
         r = {"s": dt, "partition_s": t_part}
         for which, d in (("train", "trainingScores"), ("validation", "validationScores")):
             uid, sc, _, lab = read_scores(os.path.join(root, stage, d))
-            r[which + "_auc"] = auc(lab, sc)
+            r[f"{which}_{metric}"] = mse(lab, sc) if metric == "mse" else auc(lab, sc)
             r[which + "_samples"] = int(uid.size)
         out[stage] = r
         if log:
-            log(f"{stage}: {dt:.2f} s (+ {t_part:.2f} s partition), AUC train {r['train_auc']:.4f} validation {r['validation_auc']:.4f}")
+            log(f"{stage}: {dt:.2f} s (+ {t_part:.2f} s partition), {metric.upper()} train {r['train_' + metric]:.4f} validation {r['validation_' + metric]:.4f}")
         prev = stage
     out["total_s"] = time.perf_counter() - t_all
     return out

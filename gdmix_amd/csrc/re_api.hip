@@ -826,12 +826,13 @@ GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
   }
   // the mid class adapts with the split: a caller who pinned the split (gdmix_re_set_tall_split_n) pinned the routing — no per-batch class
   tab.tall_mid_n = (ctx->impl.tall_mid_n < 0 && ctx->impl.tall_split_set) ? 0 : ctx->impl.tall_mid_n;
-  if (opts->sum_loss || opts->linear) {
+  if (opts->sum_loss) {
     // the fixed-effect objective lives in the team kernels only: every entity goes device-wide, one after another
-    if (opts->m > TEAM_MCAP) { set_error("sum_loss / linear need m <= %d", TEAM_MCAP); return GDMIX_RE_EINVAL; }
-    if (opts->variance_mode != GDMIX_RE_VAR_NONE) { set_error("variance is not available with sum_loss / linear"); return GDMIX_RE_EINVAL; }
+    if (opts->m > TEAM_MCAP) { set_error("sum_loss needs m <= %d", TEAM_MCAP); return GDMIX_RE_EINVAL; }
+    if (opts->variance_mode != GDMIX_RE_VAR_NONE) { set_error("variance is not available with sum_loss"); return GDMIX_RE_EINVAL; }
     tab.giant_nnz = 1;
   }
+  // linear without sum_loss is the random effect's squared loss: the normal class table, every launcher picks its <LIN> kernels by P.linear
 
   int32_t* cc = b->class_count;
   HIP_TRY(hipMemsetAsync(cc, 0, 6 * GDMIX_RE_NUM_CLASSES * sizeof(int32_t), s));
@@ -979,6 +980,13 @@ GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
   side_join.join();   // before the team kernels (they use the whole device and the scratch slots)
   if (hc[BLOCK_CLASS] > 0 || hc[TEAM128_CLASS] > 0 || hc[TEAM32_CLASS] > 0 || hc[TEAM8_CLASS] > 0 || hc[GIANT_CLASS] > 0) {
     double* const scratch = slot_scratch;
+    // squared loss, SIMPLE variance: the compact-form team kernels hold both losses and their epilogue is the logistic one. They get no
+    // variance pointer; re_variance_simple_lin_kernel fills these classes' entities in behind them (re_solve.hip)
+    const bool lin_var = P.linear && P.variance_mode == GDMIX_RE_VAR_SIMPLE && opts->m <= TEAM_MCAP;
+    const int lin_var_begin = begin;
+    OutDev O_team = O;
+    if (lin_var) O_team.variance = nullptr;
+    const OutDev& O = O_team;   // (every launch of this block)
     if (hc[BLOCK_CLASS] > 0) {
       if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev0[BLOCK_CLASS], s)); }
       HIP_TRY(launch_solve_block(B, O, P, theta0, begin, hc[BLOCK_CLASS], scratch, slot_doubles, slots, b->max_p, s));
@@ -1025,6 +1033,7 @@ GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
                                 ctx->impl.grid_sync, ctx->impl.num_cus, 1, s));
       if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev1[GIANT_CLASS], s)); ctx->impl.ev_used[GIANT_CLASS] = true; }
     }
+    if (lin_var) HIP_TRY(launch_variance_simple_lin(B, P, out->variance, lin_var_begin, n_slot_users, ctx->impl.num_cus, s));
   }
   if (opts->variance_mode == GDMIX_RE_VAR_FULL) {
     const int rc = run_variance_full(ctx, b, B, P, out->theta, out->variance, s);
@@ -1049,7 +1058,7 @@ GDMIX_API int gdmix_re_variance_full(gdmix_re_ctx* ctx, const gdmix_re_packed* b
   P.l2 = opts->l2; P.ftol = opts->ftol; P.pgtol = opts->pgtol; P.threshold = opts->threshold;
   P.regularize_bias = opts->regularize_bias; P.has_intercept = opts->has_intercept ? 1 : 0; P.m = opts->m; P.max_iter = opts->max_iter;
   P.maxfun = opts->maxfun; P.maxls = opts->maxls; P.variance_mode = GDMIX_RE_VAR_FULL;
-  P.sum_loss = 0; P.linear = 0;
+  P.sum_loss = 0; P.linear = opts->linear ? 1 : 0;
   return run_variance_full(ctx, b, make_batch_dev(b), P, theta, variance, static_cast<hipStream_t>(stream));
 }
 

@@ -215,6 +215,20 @@ __device__ __forceinline__ double logistic_terms(double z, double yi, double wi,
 // logistic variance weight rho (1 - rho) of _compute_variance (binary_logistic_regression.py:167-168)
 __device__ __forceinline__ double sigmoid_full(double z) { return 1.0 / (1.0 + exp(-z)); }
 
+// The per-sample loss of a solver instantiation, chosen at compile time (a run-time branch in the evaluation would move the register
+// allocation of the logistic kernels). LIN: the squared loss of --model_type=linear_regression (include/gdmix_re.h, `linear`):
+// returns w (y - z)^2, writes r = 2 w (z - y). No exp, log or reciprocal.
+template <bool LIN>
+__device__ __forceinline__ double loss_terms(double z, double yi, double wi, double& ri) {
+  if constexpr (LIN) {
+    const double we = wi * (z - yi);
+    ri = 2.0 * we;
+    return we * (z - yi);
+  } else {
+    return logistic_terms(z, yi, wi, ri);
+  }
+}
+
 // ---- More'-Thuente line search (MINPACK-2 dcsrch/dcstep as L-BFGS-B 3.0's lnsrlb calls it) --------
 // All state is uniform across the cooperating threads.
 struct LineSearch {

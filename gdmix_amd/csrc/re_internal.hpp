@@ -269,6 +269,7 @@ hipError_t launch_solve_tall(int variant, const BatchDev& B, const OutDev& O, co
 hipError_t launch_solve_tall_team(const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0, int begin, int count,
                                   int num_cus, int64_t Z, void* tail_buf, void* team_buf, int xcd_fast, hipStream_t s);
 void launch_sort_class(int32_t* list, int count, const int64_t* ent_nnz_ptr, hipStream_t s);
+hipError_t launch_variance_simple_lin(const BatchDev& B, const SolveParams& o, double* variance, int begin, int count, int num_cus, hipStream_t s);
 hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams& o, const double* theta, double* variance,
                                 double* scratch, size_t slot_doubles, int slots, int64_t max_p, hipStream_t s);
 constexpr int64_t VAR_FULL_MAX_P = 2048;   // FULL variance densifies p x p (as the reference does): one wavefront per entity up to here,

@@ -180,7 +180,9 @@ __device__ __forceinline__ void write_results(G& grp, const OutDev& O, const Sol
 // offset is an instruction immediate off one base register (runtime offsets cost ~12 VGPRs of addresses).
 // G < 64: 64/G entities per wavefront; G = 64: one; G > 64: one entity per workgroup of G/64 wavefronts
 // (cross-wave stage of every reduction through LDS + one barrier).
-template <int G, int EPL, int NCAP, int ZCAP>
+// LIN: the loss of the instantiation (re_device.hpp, loss_terms), a template parameter of every solve kernel: the <false> instantiations
+// hold the code they held before the squared loss existed; the launchers choose by SolveParams::linear.
+template <int G, int EPL, int NCAP, int ZCAP, bool LIN>
 __global__ __launch_bounds__(G > WAVE ? G : WAVE)
 __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 ? GDMIX_QUAD_WAVES_EPL4 : 1)))) void re_solve_grp_kernel(
     BatchDev B, OutDev O, SolveParams o, const double* __restrict__ theta0, int begin, int count) {
@@ -243,7 +245,7 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
   }
   grp_fence<G>();
   SolveStats st;
-  quad_solve<G, EPL, (NCAP > G)>(L, o, gl, n, p, ic, valid, rowc, colc, V, X, st);
+  quad_solve<G, EPL, (NCAP > G), LIN>(L, o, gl, n, p, ic, valid, rowc, colc, V, X, st);
   if (!valid) return;
 
 #pragma unroll
@@ -276,10 +278,15 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
     const double x0 = ic ? xs[0] : 0.0;
     double dpart = 0.0;
     for (int i = gl; i < n; i += G) {
-      const int k0 = L.row_ptr()[i], k1 = L.row_ptr()[i + 1];
-      const double z = gather_dot(L.csr() + k0, k1 - k0, xs + ic, x0) + (double)L.o()[i];
-      const double rho = sigmoid_full(z);
-      const double di = rho * (1.0 - rho) * (L.has_w ? (double)L.w()[i] : 1.0);
+      double di;
+      if constexpr (LIN) {   // D_i = 2 w_i: the squared loss has the same curvature at every theta
+        di = 2.0 * (L.has_w ? (double)L.w()[i] : 1.0);
+      } else {
+        const int k0 = L.row_ptr()[i], k1 = L.row_ptr()[i + 1];
+        const double z = gather_dot(L.csr() + k0, k1 - k0, xs + ic, x0) + (double)L.o()[i];
+        const double rho = sigmoid_full(z);
+        di = rho * (1.0 - rho) * (L.has_w ? (double)L.w()[i] : 1.0);
+      }
       rs[i] = di;
       dpart += di;
     }
@@ -313,15 +320,15 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
   }
 }
 
-template <int G, int EPL, int NCAP, int ZCAP>
+template <int G, int EPL, int NCAP, int ZCAP, bool LIN>
 static hipError_t launch_quad_t(const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0,
                                 int begin, int count, hipStream_t s) {
   constexpr int NG = G >= WAVE ? 1 : WAVE / G;
   constexpr int NWG = G > WAVE ? G / WAVE : 1;
   const int row_lds_bytes = quad_layout(G * EPL, NCAP, ZCAP, NWG).bytes;
   static DynLdsOnce lds_attr;
-  if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_grp_kernel<G, EPL, NCAP, ZCAP>)); rc != hipSuccess) return rc;
-  hipLaunchKernelGGL((re_solve_grp_kernel<G, EPL, NCAP, ZCAP>), dim3((count + NG - 1) / NG), dim3(G > WAVE ? G : WAVE),
+  if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_grp_kernel<G, EPL, NCAP, ZCAP, LIN>)); rc != hipSuccess) return rc;
+  hipLaunchKernelGGL((re_solve_grp_kernel<G, EPL, NCAP, ZCAP, LIN>), dim3((count + NG - 1) / NG), dim3(G > WAVE ? G : WAVE),
                      (size_t)row_lds_bytes * NG, s, B, O, o, theta0, begin, count);
   return hipGetLastError();
 }
@@ -330,7 +337,8 @@ hipError_t launch_solve_quad(int g, int epl, const BatchDev& B, const OutDev& O,
                              int begin, int count, int ncap, int zcap, hipStream_t s) {
   if (count <= 0) return hipSuccess;
 #define GDMIX_GRP_CASE(GG, EE, NN, ZZ) \
-  if (g == GG && epl == EE && ncap == NN && zcap == ZZ) return launch_quad_t<GG, EE, NN, ZZ>(B, O, o, theta0, begin, count, s);
+  if (g == GG && epl == EE && ncap == NN && zcap == ZZ)                                                            \
+    return o.linear ? launch_quad_t<GG, EE, NN, ZZ, true>(B, O, o, theta0, begin, count, s) : launch_quad_t<GG, EE, NN, ZZ, false>(B, O, o, theta0, begin, count, s);
   GDMIX_GRP_CASE(16, 2, 16, 64) GDMIX_GRP_CASE(16, 2, 32, 128) GDMIX_GRP_CASE(16, 2, 128, 512)
   GDMIX_GRP_CASE(16, 3, 16, 64) GDMIX_GRP_CASE(16, 3, 32, 128) GDMIX_GRP_CASE(16, 3, 128, 512)
   GDMIX_GRP_CASE(16, 4, 16, 64) GDMIX_GRP_CASE(16, 4, 32, 128) GDMIX_GRP_CASE(16, 4, 128, 512)
@@ -347,6 +355,7 @@ hipError_t launch_solve_quad(int g, int epl, const BatchDev& B, const OutDev& O,
 // ---------------------------------------------------------------------------------------------------
 // one wavefront per entity, everything LDS-resident
 // ---------------------------------------------------------------------------------------------------
+template <bool LIN>
 __global__ __launch_bounds__(WAVE) void re_solve_wave_kernel(BatchDev B, OutDev O, SolveParams o,
                                                              const double* __restrict__ theta0, int begin) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -407,23 +416,29 @@ __global__ __launch_bounds__(WAVE) void re_solve_wave_kernel(BatchDev B, OutDev 
   grp.sync();
   EntityView P{n, d, p, ic, s_row_ptr, s_csr_col, s_csr_val, s_col_ptr, s_csc_row, s_csc_val, s_y, s_o, s_w};
   SolveStats st;
-  lbfgs_solve(grp, P, o, W, st);
+  lbfgs_solve<LIN>(grp, P, o, W, st);
   write_results(grp, O, o, e, c0, p, W.x, st);
-  if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) variance_simple(grp, P, o, W, O.variance + c0);
+  if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) variance_simple<false, LIN>(grp, P, o, W, O.variance + c0);
 }
 
 hipError_t launch_solve_wave(const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0,
                              int begin, int count, int lds_bytes, hipStream_t s) {
   if (count <= 0) return hipSuccess;
-  static DynLdsOnce lds_attr;
-  if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel)); rc != hipSuccess) return rc;
-  hipLaunchKernelGGL(re_solve_wave_kernel, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
+  static DynLdsOnce lds_attr, lin_attr;
+  if (o.linear) {
+    if (hipError_t rc = lin_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<true>)); rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(re_solve_wave_kernel<true>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
+    return hipGetLastError();
+  }
+  if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<false>)); rc != hipSuccess) return rc;
+  hipLaunchKernelGGL(re_solve_wave_kernel<false>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
   return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------
 // one workgroup per entity, state in a global scratch slot, X streamed from HBM/L2
 // ---------------------------------------------------------------------------------------------------
+template <bool LIN>
 __global__ __launch_bounds__(WAVE* BLOCK_NW) void re_solve_block_kernel(BatchDev B, OutDev O, SolveParams o,
                                                                         const double* __restrict__ theta0,
                                                                         int begin, int count, double* scratch,
@@ -457,9 +472,9 @@ __global__ __launch_bounds__(WAVE* BLOCK_NW) void re_solve_block_kernel(BatchDev
     EntityView P{n, d, p, ic, B.row_ptr + r0 + e, B.csr_col + z0, B.csr_val + z0, B.col_ptr + z0 + e,
                  B.csc_row + z0, B.csc_val + z0, B.y + r0, B.offset + r0, B.weight ? B.weight + r0 : nullptr};
     SolveStats st;
-    lbfgs_solve(grp, P, o, W, st);
+    lbfgs_solve<LIN>(grp, P, o, W, st);
     write_results(grp, O, o, e, c0, p, W.x, st);
-    if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) variance_simple(grp, P, o, W, O.variance + c0);
+    if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) variance_simple<false, LIN>(grp, P, o, W, O.variance + c0);
     grp.sync();   // the slot is reused by the next entity
   }
 }
@@ -686,8 +701,12 @@ hipError_t launch_solve_block(const BatchDev& B, const OutDev& O, const SolvePar
   if (count <= 0) return hipSuccess;
   if (o.m > TEAM_MCAP) {   // two-loop form, any m
     int grid = count < slots ? count : slots;
-    hipLaunchKernelGGL(re_solve_block_kernel, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
-                       scratch, slot_doubles, max_p);
+    if (o.linear)
+      hipLaunchKernelGGL(re_solve_block_kernel<true>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
+                         scratch, slot_doubles, max_p);
+    else
+      hipLaunchKernelGGL(re_solve_block_kernel<false>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
+                         scratch, slot_doubles, max_p);
     return hipGetLastError();
   }
   return launch_team_block<TEAM_BLOCK_NW>(B, O, o, theta0, begin, count, scratch, slot_doubles, slots, max_p, s);
@@ -724,11 +743,70 @@ hipError_t launch_solve_grid(const BatchDev& B, const OutDev& O, const SolvePara
 }
 
 // ---------------------------------------------------------------------------------------------------
+// SIMPLE variance of the squared loss for the classes of the team kernels (workgroup, team tiers, device-wide). Those kernels hold both
+// losses in one instantiation (SolveParams::linear at run time, the fixed-effect path) and their epilogue is the logistic variance_simple:
+// rather than a run-time branch in them, the launcher withholds O.variance from them and this kernel follows. D_i = 2 w_i does not
+// depend on theta: 1 / (sum_i 2 w_i X~_ij^2 + l2 [j regularised] + 1e-12), duplicates of a cell summed before squaring as in variance_simple.
+// One workgroup per entity of order[begin, begin + count), grid-stride.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WAVE* BLOCK_NW) void re_variance_simple_lin_kernel(BatchDev B, SolveParams o, double* __restrict__ variance, int begin, int count) {
+  __shared__ double red[2 * BLOCK_NW];
+  const int ic = o.has_intercept ? 1 : 0;
+  const int first_reg = (ic && !o.regularize_bias) ? 1 : 0;
+  BlockGroup<BLOCK_NW> grp{(int)threadIdx.x, red, 0};
+  for (int idx = blockIdx.x; idx < count; idx += gridDim.x) {
+    const int64_t e = B.order[begin + idx];
+    const int64_t r0 = B.ent_row_ptr[e], z0 = B.ent_nnz_ptr[e], f0 = B.ent_feat_ptr[e];
+    const int n = (int)(B.ent_row_ptr[e + 1] - r0);
+    const int p = (int)(B.ent_feat_ptr[e + 1] - f0) + ic;
+    const int64_t c0 = f0 + e * ic;
+    const float* const w = B.weight ? B.weight + r0 : nullptr;
+    const int32_t* const col_ptr = B.col_ptr + z0 + e;
+    const int32_t* const csc_row = B.csc_row + z0;
+    const float* const csc_val = B.csc_val + z0;
+    double dpart = 0.0;
+    if (ic)
+      for (int i = grp.tid; i < n; i += grp.NT) dpart += 2.0 * (w ? (double)w[i] : 1.0);
+    const double dsum = grp.sum(dpart);   // (uniform trip: every thread of the workgroup reduces, whatever ic is)
+    for (int j = grp.tid; j < p; j += grp.NT) {
+      double h;
+      if (ic && j == 0) {
+        h = dsum;
+      } else {
+        h = 0.0;
+        const int c = j - ic;
+        const int k1 = col_ptr[c + 1];
+        int k = col_ptr[c];
+        while (k < k1) {   // runs of equal row = duplicates of one matrix cell
+          const int row = csc_row[k];
+          double v = (double)csc_val[k];
+          ++k;
+          while (k < k1 && csc_row[k] == row) { v += (double)csc_val[k]; ++k; }
+          h += v * v * (2.0 * (w ? (double)w[row] : 1.0));
+        }
+      }
+      h += (j < first_reg) ? 0.0 : o.l2;
+      variance[c0 + j] = 1.0 / (h + 1.0e-12);
+    }
+  }
+}
+
+hipError_t launch_variance_simple_lin(const BatchDev& B, const SolveParams& o, double* variance, int begin, int count, int num_cus, hipStream_t s) {
+  if (count <= 0) return hipSuccess;
+  int grid = 8 * num_cus;
+  if (grid > count) grid = count;
+  hipLaunchKernelGGL(re_variance_simple_lin_kernel, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, o, variance, begin, count);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
 // FULL variance: diag((X~' D X~ + (l2 + 1e-12) I - l2 e0 e0')^-1)   (binary_logistic_regression.py:181-187)
 // One wavefront per entity, H and L^-1 in a global scratch slot (2 p^2 + p + n doubles). H is SPD, so the
 // inverse comes from a Cholesky factor: diag(H^-1)_j = sum_i (L^-1)_ij^2 (the reference uses LU,
 // np.linalg.inv; both agree to rounding on these well-conditioned matrices).
 // ---------------------------------------------------------------------------------------------------
+// LIN: D_i = 2 w_i (the squared loss; include/gdmix_re.h, `linear`)
+template <bool LIN>
 __global__ __launch_bounds__(256) void re_variance_full_kernel(BatchDev B, int64_t E, SolveParams o,
                                                                const double* __restrict__ theta,
                                                                double* __restrict__ variance, double* scratch,
@@ -756,11 +834,16 @@ __global__ __launch_bounds__(256) void re_variance_full_kernel(BatchDev B, int64
     for (int i = 0; i < n; ++i) {
       const int k0 = rp[i], k1 = rp[i + 1];
       // logit and D_i (every lane computes the same scalar)
-      double acc = ic ? th[0] : 0.0;
-      for (int k = k0; k < k1; ++k) acc += (double)B.csr_val[z0 + k] * th[ic + B.csr_col[z0 + k]];
-      const double z = acc + (double)B.offset[r0 + i];
-      const double rho = 1.0 / (1.0 + exp(-z));
-      const double di = rho * (1.0 - rho) * (B.weight ? (double)B.weight[r0 + i] : 1.0);
+      double di;
+      if constexpr (LIN) {
+        di = 2.0 * (B.weight ? (double)B.weight[r0 + i] : 1.0);
+      } else {
+        double acc = ic ? th[0] : 0.0;
+        for (int k = k0; k < k1; ++k) acc += (double)B.csr_val[z0 + k] * th[ic + B.csr_col[z0 + k]];
+        const double z = acc + (double)B.offset[r0 + i];
+        const double rho = 1.0 / (1.0 + exp(-z));
+        di = rho * (1.0 - rho) * (B.weight ? (double)B.weight[r0 + i] : 1.0);
+      }
       // dense row (duplicates summed, as toarray() does)
       if (lane == 0) {
         if (ic) xi[0] = 1.0;
@@ -826,8 +909,12 @@ hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams&
   if ((int64_t)waves > E) waves = (int)E;
   const int blocks = (waves + 3) / 4;
   // every wave of the grid owns one slot: grid = blocks * 4 waves <= slots is ensured by the caller
-  hipLaunchKernelGGL(re_variance_full_kernel, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
-                     slot_doubles, max_p);
+  if (o.linear)
+    hipLaunchKernelGGL(re_variance_full_kernel<true>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
+                       slot_doubles, max_p);
+  else
+    hipLaunchKernelGGL(re_variance_full_kernel<false>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
+                       slot_doubles, max_p);
   return hipGetLastError();
 }
 

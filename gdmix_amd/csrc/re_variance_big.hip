@@ -1,7 +1,7 @@
 // re_variance_big.hip — FULL coefficient variances of entities too large for one wavefront (p > VAR_FULL_MAX_P):
 // diag((X~' D X~ + (l2 + 1e-12) I - l2 e0 e0')^-1), binary_logistic_regression.py:181-187 (the reference densifies the Hessian
 // and calls np.linalg.inv whatever p is). One entity at a time, the whole device on it:
-//   vf_rows_kernel      d_i = w_i rho_i (1 - rho_i)
+//   vf_rows_kernel      d_i = w_i rho_i (1 - rho_i)      (vf_rows_lin_kernel: d_i = 2 w_i, the squared loss)
 //   vf_build_kernel     H = X~' D X~ column by column: workgroup a spreads d .* column a over the samples and takes its
 //                       products with the columns b >= a (ordered sums: deterministic), H symmetric, leading dimension padded to tiles
 //   vf_potrf / vf_trsm / vf_syrk   right-looking Cholesky H = L L' on 64 x 64 tiles
@@ -47,6 +47,12 @@ __global__ void vf_rows_kernel(BatchDev B, VfEntity V, int ic, const double* __r
     const double rho = sigmoid_full(acc + (double)B.offset[V.r0 + i]);
     dvec[i] = rho * (1.0 - rho) * (B.weight ? (double)B.weight[V.r0 + i] : 1.0);
   }
+}
+
+// squared loss: the curvature weight does not depend on theta
+__global__ void vf_rows_lin_kernel(BatchDev B, VfEntity V, double* __restrict__ dvec) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V.n; i += gridDim.x * blockDim.x)
+    dvec[i] = 2.0 * (B.weight ? (double)B.weight[V.r0 + i] : 1.0);
 }
 
 // H = identity on the padding, zero elsewhere
@@ -313,7 +319,8 @@ hipError_t launch_variance_full_big(gdmix_ctx_impl* ci, const BatchDev& B, int64
   double* wslots = dvec + max_n;
   for (int q = 0; q < n_big; ++q) {
     const VfEntity& V = host[(size_t)q];
-    hipLaunchKernelGGL(vf_rows_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
+    if (o.linear) hipLaunchKernelGGL(vf_rows_lin_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, dvec);
+    else hipLaunchKernelGGL(vf_rows_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
     hipLaunchKernelGGL(vf_clear_kernel, dim3(ci->num_cus * 8), dim3(256), 0, s, H, V.p, V.ld);
     rc = hipMemsetAsync(wslots, 0, (size_t)V.n * VAR_BIG_BUILD_GROUPS * 8, s);
     if (rc != hipSuccess) return rc;

@@ -5,7 +5,8 @@ shared by Params, SchemaParams and REParams, unknown flags are ignored, any fail
     python -m gdmix_amd.gdmix --stage=random_effect --action=train --model_type=logistic_regression \\
         --partition_list_file=... --training_data_dir=... --metadata_file=... --output_model_dir=... ...
 
---stage=fixed_effect runs the linear / logistic fixed-effect model (fe_model.py); the DeText stage is out of scope.
+--model_type=linear_regression trains the per-entity squared loss on real-valued labels (model.py). --stage=fixed_effect runs the linear /
+logistic fixed-effect model (fe_model.py); the DeText stage is out of scope.
 """
 import logging
 import sys
@@ -29,9 +30,10 @@ def run(args):
         from .fe_model import FixedEffectLRModelLBFGS
         driver = FixedEffectDriver(base_training_params=params, model=FixedEffectLRModelLBFGS(raw_model_params=args, base_training_params=params))
     elif params.stage == constants.RANDOM_EFFECT:
-        if params.model_type != constants.LOGISTIC_REGRESSION:
-            raise ValueError("Random effect supports logistic_regression only")
-        driver = RandomEffectDriver(base_training_params=params, model=RandomEffectLRLBFGSModel(raw_model_params=args))
+        if params.model_type not in (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION):
+            raise ValueError(f"model type {params.model_type!r}: the random effect runs logistic_regression and linear_regression")
+        driver = RandomEffectDriver(base_training_params=params,
+                                    model=RandomEffectLRLBFGSModel(raw_model_params=args, base_training_params=params))
     else:
         raise NotImplementedError(f"stage {params.stage!r} does not run on this library")
     if params.action == constants.ACTION_TRAIN:

@@ -46,13 +46,14 @@ def _column(ctx, name, kinds, entity_label):
 
 def read_grouped_partition(input_path, metadata, entity_name, feature_bag, offset_column_name,
                            uid_column_name, label_column_name=None, weight_column_name=None,
-                           num_features=None, check_crc=False, native=None, threads=0, wire=False):
+                           num_features=None, check_crc=False, native=None, threads=0, wire=False, binary_labels=True):
     """Read every record under input_path into one RawBatch (entity order = file order, then record order).
 
     feature_bag None => intercept-only model: one dummy zero feature per sample (job_consumers.py:213-218).
     label_column_name None (or absent from the records) => batch.has_label False (inference data).
     native: True = libgdmix_io.so (multi-threaded C++), False = the Python decoder below, None = native when the
     library has been built. Both follow the same rules (tests/test_native_io.py).
+    binary_labels: True (logistic regression) refuses a label other than 0 or 1, as fit() does; False keeps real-valued labels.
     wire: with the native reader, hand the partition over in the 32-bit form (batch.WireRawBatch); ignored by the Python decoder.
     """
     md = metadata if isinstance(metadata, DatasetMetadata) else DatasetMetadata(metadata)
@@ -66,7 +67,7 @@ def read_grouped_partition(input_path, metadata, entity_name, feature_bag, offse
     if native:
         return native_reader.read_grouped_files(files, entity_name, feature_bag, offset_column_name, uid_column_name,
                                                 label_column_name, weight_column_name if has_weight_col else None,
-                                                num_features, check_crc, threads, wire=wire)
+                                                num_features, check_crc, threads, wire=wire, binary_labels=binary_labels)
     ent_n, row_k = [], []
     cols, vals, ys, offs, ws, uids, ids = [], [], [], [], [], [], []
     has_label = label_column_name is not None
@@ -139,7 +140,7 @@ def read_grouped_partition(input_path, metadata, entity_name, feature_bag, offse
                     row_nnz_ptr=np.concatenate([[0], np.cumsum(rk)]).astype(np.int64),
                     col_global=cat(cols, np.int64), val=cat(vals, np.float32), y=cat(ys, np.float32),
                     offset=cat(offs, np.float32), weight=cat(ws, np.float32) if has_weight_col else None,
-                    uid=cat(uids, np.int64), entity_ids=ids, has_label=has_label)
+                    uid=cat(uids, np.int64), entity_ids=ids, has_label=has_label, binary_labels=binary_labels)
 
 
 def write_grouped_partition(path, batch: RawBatch, entity_name, feature_bag, offset_column_name="offset",
@@ -147,11 +148,13 @@ def write_grouped_partition(path, batch: RawBatch, entity_name, feature_bag, off
                             int_entity_ids=False, native=None):
     """Write a RawBatch as one SequenceExample per entity (layout of DataPartitioner's output,
     SURVEY.md Appendix A). Used by tests, the partitioner tool and to materialise synthetic partitions.
-    native None => libgdmix_io.so when built (same bytes for uncompressed files)."""
+    native None => libgdmix_io.so when built (same bytes for uncompressed files). Real-valued labels (batch.binary_labels False) are
+    written as a float list by the Python encoder; the library's writer knows the int64 label list only."""
     from . import native_reader
+    real_labels = batch.has_label and not batch.binary_labels
     if native is None:
         native = native_reader.available()
-    if native:
+    if native and not real_labels:
         native_reader.write_grouped_file(path, batch, entity_name, feature_bag, offset_column_name, uid_column_name,
                                          label_column_name, weight_column_name, int_entity_ids)
         return
@@ -165,7 +168,7 @@ def write_grouped_partition(path, batch: RawBatch, entity_name, feature_bag, off
                uid_column_name: ("int64", batch.uid[sl]),
                offset_column_name: ("float", batch.offset[sl])}
         if batch.has_label and label_column_name:
-            ctx[label_column_name] = ("int64", batch.y[sl].astype(np.int64))
+            ctx[label_column_name] = ("float", batch.y[sl]) if real_labels else ("int64", batch.y[sl].astype(np.int64))
         if batch.weight is not None and weight_column_name:
             ctx[weight_column_name] = ("float", batch.weight[sl])
         fls = {}

@@ -265,10 +265,13 @@ def _split_ids(raw, ptr, E):
 
 
 def read_grouped_files(files, entity_name, feature_bag, offset_column_name, uid_column_name, label_column_name=None,
-                       weight_column_name=None, num_features=None, check_crc=False, threads=0, stats=None, wire=False) -> RawBatch:
+                       weight_column_name=None, num_features=None, check_crc=False, threads=0, stats=None, wire=False,
+                       binary_labels=True) -> RawBatch:
     """files -> RawBatch; same arguments as grouped_reader.read_grouped_partition after file resolution and the
     metadata checks. weight_column_name None => no weight array. wire=True: the library narrows the partition to the 32-bit hand-over
-    form (gdmix_io_narrow) and the result is a batch.WireRawBatch around its arrays — what a device solver uploads as it is."""
+    form (gdmix_io_narrow) and the result is a batch.WireRawBatch around its arrays — what a device solver uploads as it is.
+    binary_labels=False (linear regression): a label other than 0 or 1 is data, not an error; such a batch carries binary_labels=False and
+    its wire form float labels (y_width 4)."""
     lib = load_library()
     sc = _Schema(_enc(entity_name), _enc(feature_bag), _enc(offset_column_name), _enc(uid_column_name),
                  _enc(label_column_name), _enc(weight_column_name),
@@ -289,7 +292,7 @@ def read_grouped_files(files, entity_name, feature_bag, offset_column_name, uid_
     if stats is not None:
         stats["bytes_read"] = int(b.bytes_read)
     v = lambda ptr, n, dt: _view(owner, ptr, n, dt)
-    if bool(b.has_label) and not int(b.labels_binary):
+    if binary_labels and bool(b.has_label) and not int(b.labels_binary):
         raise AssertionError("labels must be 0 or 1")   # fit() asserts it (binary_logistic_regression.py:208)
     if wire:
         rc = lib.gdmix_io_narrow(out, _threads(threads))
@@ -301,14 +304,14 @@ def read_grouped_files(files, entity_name, feature_bag, offset_column_name, uid_
                             row_nnz=v(b.row_nnz or 0, N, kdt), col=v(b.col or 0, Z, cdt), val=v(b.val, Z, np.float32),
                             y=v(b.y, N, np.float32), y8=v(b.y8, N, np.uint8) if b.y8 else None, offset=v(b.offset, N, np.float32),
                             weight=v(b.weight, N, np.float32) if weight_column_name is not None else None,
-                            uid=v(b.uid, N, np.int64), entity_ids=ids, has_label=bool(b.has_label))
+                            uid=v(b.uid, N, np.int64), entity_ids=ids, has_label=bool(b.has_label), binary_labels=bool(binary_labels))
     # the library built these arrays itself (monotone pointers, matching lengths, labels checked while decoding): the
     # passes RawBatch.validate would make over them are skipped
     return RawBatch(ent_row_ptr=v(b.ent_row_ptr, E + 1, np.int64), row_nnz_ptr=v(b.row_nnz_ptr, N + 1, np.int64),
                     col_global=v(b.col_global, Z, np.int64), val=v(b.val, Z, np.float32),
                     y=v(b.y, N, np.float32), offset=v(b.offset, N, np.float32),
                     weight=v(b.weight, N, np.float32) if weight_column_name is not None else None,
-                    uid=v(b.uid, N, np.int64), entity_ids=ids, has_label=bool(b.has_label), trusted=True)
+                    uid=v(b.uid, N, np.int64), entity_ids=ids, has_label=bool(b.has_label), binary_labels=bool(binary_labels), trusted=True)
 
 
 # ---- Avro writers ------------------------------------------------------------------------------------------

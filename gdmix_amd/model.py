@@ -374,10 +374,17 @@ def _model_coefficients_for_batch(table, entity_ids, unique_global, ent_feat_ptr
 
 
 class RandomEffectLRLBFGSModel:
-    """Per-entity L2-regularised logistic regression, all entities of a partition solved on one MI355X."""
+    """Per-entity L2-regularised logistic regression, all entities of a partition solved on one MI355X.
+    base_training_params.model_type == linear_regression: the per-entity squared loss on real-valued labels instead (include/gdmix_re.h,
+    `linear`); everything else — grouping, warm start, variance modes, scoring, inference, re-balancing — is the same path. Unlike the
+    fixed effect, scoring after training stays on: a random effect's scores are the next coordinate's offsets."""
 
-    def __init__(self, raw_model_params, device=None):
+    def __init__(self, raw_model_params, device=None, base_training_params=None):
         self.model_params: REParams = self._parse_parameters(raw_model_params)
+        self.model_type = constants.LOGISTIC_REGRESSION if base_training_params is None else base_training_params.model_type
+        if self.model_type not in (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION):
+            raise ValueError(f"model type {self.model_type!r}: the random effect runs logistic_regression and linear_regression")
+        self.linear = self.model_type == constants.LINEAR_REGRESSION
         self.checkpoint_path = os.path.join(self.model_params.output_model_dir)
         self.metadata_file = self.model_params.metadata_file
         self.feature_bag_name = self.model_params.feature_bag
@@ -446,7 +453,7 @@ class RandomEffectLRLBFGSModel:
                              has_intercept=self.has_intercept,
                              m=mp.num_of_lbfgs_curvature_pairs, max_iter=mp.num_of_lbfgs_iterations,
                              ftol=mp.lbfgs_tolerance, variance_mode=VARIANCE_MODES[mp.random_effect_variance_mode],
-                             threshold=mp.sparsity_threshold)
+                             threshold=mp.sparsity_threshold, linear=self.linear)
 
     def _action(self, action, action_context, metadata_file, checkpoint_path, execution_context, schema_params):
         partition_index = execution_context[constants.PARTITION_INDEX]
@@ -584,7 +591,7 @@ class RandomEffectLRLBFGSModel:
             feature_bag=self.feature_bag_name, offset_column_name=self.model_params.offset_column_name,
             uid_column_name=schema_params.uid_column_name,
             label_column_name=schema_params.label_column_name, weight_column_name=schema_params.weight_column_name,
-            num_features=num_features, wire=self._wants_wire())
+            num_features=num_features, wire=self._wants_wire(), binary_labels=not self.linear)
 
     def _wants_wire(self):
         """The reader narrows the partition to the 32-bit hand-over form when a device solver will take it (it uploads that form as it

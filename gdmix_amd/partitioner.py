@@ -134,9 +134,10 @@ def group_samples(entity, gid):
 
 
 def build_batches(entity, uid, label, offset, weight, row_nnz_ptr, col_global, val, num_partitions,
-                  lower_bound=None, upper_bound=None, split=True):
+                  lower_bound=None, upper_bound=None, split=True, binary_labels=True):
     """Flat per-sample arrays (sparse bag as CSR over samples) -> {(subdir, partition id): RawBatch}.
-    subdir is 'active' / 'passive' when split (training data), '' otherwise (validation data: all groups)."""
+    subdir is 'active' / 'passive' when split (training data), '' otherwise (validation data: all groups).
+    binary_labels=False: real-valued labels (linear regression)."""
     entity = np.asarray(entity)
     uid = np.asarray(uid, np.int64)
     gid = group_ids(entity, uid, lower_bound, upper_bound)
@@ -165,7 +166,7 @@ def build_batches(entity, uid, label, offset, weight, row_nnz_ptr, col_global, v
                 col_global=np.asarray(col_global, np.int64)[nz], val=np.asarray(val, np.float32)[nz],
                 y=np.asarray(label, np.float32)[rows], offset=np.asarray(offset, np.float32)[rows],
                 weight=None if weight is None else np.asarray(weight, np.float32)[rows], uid=uid[rows],
-                entity_ids=[str(x) for x in rec_entity[recs]], has_label=True)
+                entity_ids=[str(x) for x in rec_entity[recs]], has_label=True, binary_labels=binary_labels)
     return out
 
 

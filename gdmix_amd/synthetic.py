@@ -70,6 +70,16 @@ def make_batch(E, mean_n=16, k=4, D=1024, seed=C2_SEED, size_dist="poisson", l_o
         entity_ids=[str(i) for i in range(entity_id_base, entity_id_base + E)])
 
 
+def with_real_labels(batch, seed=0, scale=2.0, noise=1.0):
+    """The same batch with real-valued labels for --model_type=linear_regression: scale * y + N(0, noise) over the 0/1 labels the
+    generator planted, fp32 — a regression target that still carries the planted effects. Every other array is shared with `batch`;
+    the result has binary_labels=False (wire form: float labels, y_width 4)."""
+    import dataclasses
+    rng = np.random.default_rng([int(seed), 0x11EA])
+    y = (scale * np.asarray(batch.y, np.float64) + noise * rng.standard_normal(batch.N)).astype(np.float32)
+    return dataclasses.replace(batch, y=y, binary_labels=False)
+
+
 def make_survey_batch(E, mean_n=16, k=4, D=1024, seed=C2_SEED, size_dist="poisson", entity_id_base=0, with_uid=False):
     """The generator SURVEY.md §8(d) states for the measured configurations, to the letter: n_e = max(1, Poisson(mean_n)); per
     sample k DISTINCT columns drawn uniformly from [0, D) (in draw order, not sorted); values ~ N(0,1) fp32; offset ~ N(0,1)

@@ -160,11 +160,24 @@ typedef struct {
   double  pgtol;            /* scipy default                          1e-5          */
   int32_t variance_mode;    /* GDMIX_RE_VAR_*                         default NONE  */
   double  threshold;        /* sparsity_threshold applied to theta_thr, default 1e-4 (model_utils.py:4-12) */
-  /* The two switches below turn the per-entity objective into the fixed-effect one
+  /* The two switches below together turn the per-entity objective into the fixed-effect one
    * (fixed_effect_lr_lbfgs_model.py:309-392): a batch with one "entity" = one worker's shard. Defaults 0.
-   * Non-default values route every entity to the team kernels. */
+   * sum_loss != 0 routes every entity to the device-wide team kernel, needs m <= 10 and refuses a variance mode. */
   int32_t sum_loss;         /* 1: f = sum_i w_i l_i + (l2/2)|theta_reg|^2, not divided by n (:363-381)            */
   int32_t linear;           /* 1: l_i = (y_i - z_i)^2 (linear regression, :356-358) instead of the logistic loss */
+  /* linear != 0 with sum_loss == 0 is the random effect's linear regression (--model_type=linear_regression; the reference has none: this
+   * is its per-entity objective with its fixed-effect loss put in). For one entity of n samples, theta in local index space, intercept
+   * first, labels y real-valued:
+   *     z_i = x_i . theta + offset_i
+   *     f(theta) = (1/n) ( sum_i w_i (y_i - z_i)^2 + (l2/2) |theta_reg|^2 )
+   *     g        = (1/n) ( X~' (2 w (z - y)) + l2 theta_reg )
+   * Everything else is as for the logistic loss: the same L-BFGS-B loop, theta0, m, max_iter, ftol, pgtol, maxls, every stop and status
+   * code, thresholding into theta_thr, and the same size classes (classification goes by LDS footprint): every solve kernel has an
+   * instantiation of its own for this loss. Variance is _compute_variance (binary_logistic_regression.py:144-189) with the curvature
+   * weight D_i = 2 w_i in place of rho_i (1 - rho_i) w_i — it does not depend on theta:
+   *     SIMPLE  1 / (sum_i D_i X~_ij^2 + l2 [- l2 for an unregularised intercept] + 1e-12)
+   *     FULL    diag((X~' D X~ + (l2 + 1e-12) I [- l2 e0 e0'])^-1)      (gdmix_re_variance_full takes the loss from opts->linear too)
+   * neither divided by n, as in the reference. gdmix_re_score is the same for both losses: x . theta + offset. */
 } gdmix_re_opts;
 
 /* fills *o with the defaults above */

@@ -1,0 +1,106 @@
+"""Is the device code of every kernel the same as another commit's? Without a GPU: both trees' .hip units are compiled to gfx950
+assembly with the build's flags (`hipcc -S --cuda-device-only`) and compared kernel by kernel after stripping comments, section
+directives and per-compile labels. Kernels are matched by demangled name; --gained-false names kernels whose template list gained a
+trailing `false` argument since the other commit (a new compile-time parameter whose `false` instantiation must be the old kernel).
+
+    python tools/asm_compare.py --parent HEAD~1 \\
+        --gained-false re_solve_grp_kernel,re_solve_wave_kernel,re_solve_block_kernel,re_variance_full_kernel,re_solve_tall_kernel,re_solve_tall_team_kernel
+
+Prints per unit: kernels identical / different / only in this tree; exit status 1 if a kernel of the other commit differs or is missing.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from gdmix_amd import build      # noqa: E402
+
+
+def compile_units(csrc, out):
+    os.makedirs(out, exist_ok=True)
+    flags = [f for f in build.FLAGS if f != "-shared"] + os.environ.get("GDMIX_EXTRA_FLAGS", "").split()
+
+    def one(f):
+        dst = os.path.join(out, f + ".s")
+        subprocess.run([build.HIPCC] + flags + ["--cuda-device-only", "-S", os.path.join(csrc, f), "-o", dst], check=True, stderr=subprocess.DEVNULL)
+        return dst
+    with ThreadPoolExecutor(len(build.SOURCES)) as ex:
+        return dict(zip(build.SOURCES, ex.map(one, build.SOURCES)))
+
+
+def functions(path):
+    """-> {mangled name: [normalised lines]}, {mangled name: kernel descriptor text}"""
+    txt = open(path).read()
+    out, cur, buf = {}, None, []
+    for line in txt.splitlines():
+        m = re.match(r"^(\w+):\s*(;.*)?$", line)
+        if m and cur is None and not line.startswith(".L"):
+            cur, buf = m.group(1), []
+            continue
+        if cur is not None:
+            if re.match(r"^\.Lfunc_end\d+:", line):
+                out[cur], cur = buf, None
+                continue
+            line = re.sub(r";.*$", "", line).rstrip()
+            if not line or re.match(r"\s*\.(text|section)\b", line):
+                continue
+            line = re.sub(r"\.LBB\d+_", ".LBB_", line)
+            line = re.sub(r"\.Ltmp\d+|\.L__unnamed_\d+|\.Lfunc_begin\d+|\.Lfunc_end\d+", ".L", line)
+            buf.append(line.replace(cur, "SELF"))
+    meta = {m.group(1): m.group(2).replace(m.group(1), "SELF") for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", txt, re.S)}
+    return out, meta
+
+
+def demangle(names):
+    res = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    return {n: re.sub(r"^void ", "", d).split("(")[0] for n, d in zip(names, res)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", default="HEAD", help="the commit to compare the working tree with")
+    ap.add_argument("--gained-false", default="", help="comma list of kernel names whose template arguments gained a trailing `false`")
+    a = ap.parse_args()
+    gained = [g for g in a.gained_false.split(",") if g]
+
+    def key(d):
+        if any(re.match(rf"(\w+::)*{re.escape(g)}\b", d) for g in gained):
+            d = re.sub(r"<false>$", "", re.sub(r", false>$", ">", d))
+        return d
+    bad = 0
+    with tempfile.TemporaryDirectory() as tmp:
+        old = os.path.join(tmp, "old")
+        os.makedirs(old)
+        tar = subprocess.run(["git", "archive", a.parent, "gdmix_amd/csrc", "include"], cwd=ROOT, capture_output=True, check=True).stdout
+        subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
+        s_old = compile_units(os.path.join(old, "gdmix_amd", "csrc"), os.path.join(tmp, "s_old"))
+        s_new = compile_units(build.CSRC, os.path.join(tmp, "s_new"))
+        for unit in build.SOURCES:
+            fo, mo = functions(s_old[unit])
+            fn, mn = functions(s_new[unit])
+            do, dn = demangle(list(fo)), demangle(list(fn))
+            new_by_key = {key(dn[k]): k for k in fn if k not in fo}
+            same = diff = 0
+            for k in fo:
+                k2 = k if k in fn else new_by_key.get(do[k])      # same symbol, or the symbol that gained its `false`
+                if k2 is None:
+                    print(f"{unit}: MISSING {do[k]}")
+                    bad += 1
+                elif fo[k] == fn[k2] and mo.get(k) == mn.get(k2):
+                    same += 1
+                else:
+                    print(f"{unit}: DIFFERENT {do[k]} ({len(fo[k])} -> {len(fn[k2])} lines)")
+                    diff += 1
+                    bad += 1
+            print(f"{unit}: {same} identical, {diff} different, {len(fn) - same - diff} only in this tree")
+    print("every kernel of the other commit is unchanged" if not bad else f"{bad} kernels differ or are missing")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -24,7 +24,7 @@ def per_dispatch(db, counter):
 
 
 def class_name(kernel):
-    m = re.search(r"re_solve_grp_kernel<(\d+), (\d+), (\d+), (\d+)>", kernel)
+    m = re.search(r"re_solve_grp_kernel<(\d+), (\d+), (\d+), (\d+)(?:, false)?>", kernel)      # (the loss is the fifth parameter; the logistic instantiations)
     if m:
         g, epl, ncap, zcap = m.groups()
         return f"re_solve_grp_kernel<{g},{epl}> n<={ncap} nnz<={zcap}"
