@@ -526,6 +526,8 @@ GDMIX_API int gdmix_re_create(int hip_device, gdmix_re_ctx** out) {
   c->impl.grid_sync = nullptr;
   c->impl.big_tmp = nullptr;
   c->impl.big_tmp_bytes = 0;
+  c->impl.eval_small_set = 0; c->impl.eval_small_max = 64;
+  c->impl.eval_tmp = nullptr; c->impl.eval_tmp_bytes = 0;
   c->impl.n_side = 0; c->impl.side_fork = nullptr;
   c->impl.aux_ev[0] = c->impl.aux_ev[1] = nullptr;
   c->impl.defer_unique = 0; c->impl.unique_pending = false; c->impl.unique_ev = nullptr;
@@ -576,6 +578,7 @@ GDMIX_API void gdmix_re_destroy(gdmix_re_ctx* ctx) {
   if (ctx->impl.unique_ev) (void)hipEventDestroy(ctx->impl.unique_ev);
   if (ctx->impl.grid_sync) (void)hipFree(ctx->impl.grid_sync);
   if (ctx->impl.big_tmp) (void)hipFree(ctx->impl.big_tmp);
+  if (ctx->impl.eval_tmp) (void)hipFree(ctx->impl.eval_tmp);
   if (ctx->impl.host_pinned) (void)hipHostFree(ctx->impl.host_pinned);
   if (ctx->impl.side_fork) (void)hipEventDestroy(ctx->impl.side_fork);
   for (int k = 0; k < 2; ++k) if (ctx->impl.aux_ev[k]) (void)hipEventDestroy(ctx->impl.aux_ev[k]);

@@ -183,6 +183,10 @@ struct gdmix_ctx_impl {
   hipEvent_t unique_ev;
   hipEvent_t ev0[GDMIX_RE_NUM_CLASSES], ev1[GDMIX_RE_NUM_CLASSES];
   bool ev_used[GDMIX_RE_NUM_CLASSES];
+  // evaluation (re_evaluate.hip)
+  int eval_small_set, eval_small_max;   // gdmix_re_set_eval_small_max was called / its value (otherwise 64)
+  void* eval_tmp;                       // device: grow-only temporary storage of the sort and the prefix sum
+  size_t eval_tmp_bytes;
 };
 
 // A few bytes from the device to the host WITHOUT a stream synchronise (round 5). The counts a pack or a solve decides its next

@@ -200,6 +200,8 @@ class RandomEffectDriver:
                     self.model.predict(output_dir=output_dir, input_data_path=data_path,
                                        metadata_file=self.model.metadata_file, checkpoint_path=self.model.checkpoint_path,
                                        execution_context=self.execution_context, schema_params=schema_params)
+        if hasattr(self.model, "finish_metrics"):      # REParams.metric_output_dir: the summary of everything scored
+            self.model.finish_metrics()
         logger.info("Inference complete")
 
     def _prepare_training_context(self, partition_index):

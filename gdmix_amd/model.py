@@ -410,6 +410,31 @@ class RandomEffectLRLBFGSModel:
         self._group = None          # plan_group(): partitions that are solved in one device batch
         self._decoded = {}          # read key -> RawBatch decoded for a group, until _read hands it out
         self.last_training_stats = None
+        self._stage_metrics = None  # metrics.StageMetrics when model_params.metric_output_dir is set (created with the first scores)
+
+    # ---- the stage's metric, on the device while it scores (REParams.metric_output_dir) -------------------------------------------
+    def _metrics(self):
+        out_dir = getattr(self.model_params, "metric_output_dir", None)
+        if not out_dir:
+            return None
+        if self._stage_metrics is None:
+            from . import metrics
+            self._stage_metrics = metrics.StageMetrics(self._get_solver(), out_dir, metrics.MSE if self.linear else metrics.AUC)
+        return self._stage_metrics
+
+    def _metric_data(self, input_path):
+        """Which of the stage's two metrics a scored directory belongs to: its training data (active or passive) or anything else."""
+        p = os.path.abspath(input_path)
+        for d in (self.training_data_dir, self.passive_training_data_dir):
+            if d and (p + os.sep).startswith(os.path.abspath(d) + os.sep):
+                return "training"
+        return "validation"
+
+    def finish_metrics(self):
+        """End of the stage: evalSummary.json from the accumulators (nothing without metric_output_dir, or when nothing was scored)."""
+        if self._stage_metrics is not None:
+            self._stage_metrics.write_summary()
+            self._stage_metrics = None
 
     # ---- Model API (models/api.py) ---------------------------------------------------------------------
     def train(self, training_data_dir, validation_data_dir, metadata_file, checkpoint_path, execution_context, schema_params):
@@ -552,6 +577,7 @@ class RandomEffectLRLBFGSModel:
     def end_pipeline(self):
         try:
             self.flush()
+            self.finish_metrics()
         finally:
             for f in list(self._prefetched.values()) + list(self._prefetched_models.values()):
                 f.cancel()
@@ -790,6 +816,9 @@ class RandomEffectLRLBFGSModel:
         if g["scores"] is None:
             packed, theta = g["resident"]
             logit, per_coord = self._get_solver().score(packed, theta, None)
+            sm = self._metrics()
+            if sm is not None:      # (a group is made of labelled training partitions only)
+                g["entity_metrics"] = (sm.feed("training", packed, logit), host_array(packed._raw_dev["ent_row_ptr"]))
             g["scores"] = (host_array(logit), host_array(per_coord))
             g["resident"] = None        # the packed batch and the coefficients leave HBM
         logit, per_coord = g["scores"]
@@ -1018,8 +1047,17 @@ class RandomEffectLRLBFGSModel:
             avro.write_file(output_file, schema, [])
             return
         solver = self._get_solver()
+        sm = self._metrics()
+        if sm is not None and not batch.has_label:
+            sm.no_labels(input_path)
+            sm = None
         if group is not None:
             logit, per_coord = self._group_scores(*group)
+            if sm is not None and group[0].get("entity_metrics") is not None:
+                host, rp = group[0]["entity_metrics"]
+                e0, e1 = int(np.searchsorted(rp, group[1][0])), int(np.searchsorted(rp, group[1][1]))
+                assert e1 - e0 == batch.E
+                sm.write_entities("training", output_file, batch.entity_ids, host, e0, e1)
         else:
             if packed is None:
                 packed = self._pack(solver, batch)
@@ -1028,6 +1066,9 @@ class RandomEffectLRLBFGSModel:
                 theta, has_model = _model_coefficients_for_batch(model_weights, batch.entity_ids, uniq, feat_ptr,
                                                                  self.has_intercept, num_features)
             logit, per_coord = solver.score(packed, theta, has_model)
+            if sm is not None:
+                which = self._metric_data(input_path)
+                sm.write_entities(which, output_file, batch.entity_ids, sm.feed(which, packed, logit))
             logit, per_coord = host_array(logit), host_array(per_coord)
         weights = batch.weight if batch.weight is not None else np.ones(batch.N, np.float32)
         self._write_behind(output_file, _write_scores, output_file, schema, schema_params, batch.uid, logit, batch.y if batch.has_label else None,

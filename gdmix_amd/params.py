@@ -96,6 +96,9 @@ class REParams(LRParams):
     disable_random_effect_scoring_after_training: bool = False
     # not in the reference: move entities between the workers of a node when partitions are skewed (rebalance.py)
     rebalance_entities: bool = False
+    # not in the reference: the stage writes its metric (evalSummary.json: auc, or mse for linear_regression) and the per-entity
+    # metrics of everything it scores under this directory, computed on the device while the scores are there (metrics.py)
+    metric_output_dir: Optional[str] = None
 
     def __post_init__(self):
         # the reference's REParams.__post_init__ does NOT chain to LRParams.__post_init__ (random_effect_lr_lbfgs_model.py:

@@ -67,6 +67,21 @@ class _Result(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class _EvalOut(C.Structure):
+    _fields_ = [("two_u", C.c_void_p), ("n_pos", C.c_void_p), ("n_neg", C.c_void_p), ("n_nan", C.c_void_p), ("sse", C.c_void_p), ("auc", C.c_void_p)]
+
+
+class _EvalAcc(C.Structure):
+    _fields_ = [("keys", C.c_void_p), ("capacity", C.c_int64), ("count", C.c_int64), ("state", C.c_void_p)]
+
+
+EVAL_ACC_STATE_BYTES = 33024
+
+
+class _EvalTotals(C.Structure):
+    _fields_ = [("two_u", C.c_uint64), ("n", C.c_int64), ("n_pos", C.c_int64), ("n_neg", C.c_int64), ("n_nan", C.c_int64), ("sse", C.c_double)]
+
+
 EXPORTED_SYMBOLS = (
     "gdmix_re_abi_version", "gdmix_re_build_id", "gdmix_re_device_shared", "gdmix_re_grid_lock_acquire", "gdmix_re_grid_lock_release", "gdmix_re_grid_lock_stats", "gdmix_re_last_error", "gdmix_re_default_opts", "gdmix_re_create",
     "gdmix_re_destroy", "gdmix_re_pack_workspace_bytes", "gdmix_re_pack", "gdmix_re_set_defer_unique", "gdmix_re_pack_join", "gdmix_re_solve",
@@ -75,6 +90,8 @@ EXPORTED_SYMBOLS = (
     "gdmix_fe_create", "gdmix_fe_destroy", "gdmix_fe_eval", "gdmix_fe_reduce_buffer", "gdmix_fe_step", "gdmix_fe_step_async", "gdmix_fe_step_status", "gdmix_fe_solve", "gdmix_fe_result",
     "gdmix_fe_last_eval_ms", "gdmix_fe_stream_bytes", "gdmix_fe_score", "gdmix_fe_hessian_diag", "gdmix_fe_hessian_dense_scratch_bytes", "gdmix_fe_hessian_dense",
     "gdmix_fe_variance_of_hessian",
+    "gdmix_re_eval_workspace_bytes", "gdmix_re_eval_entities", "gdmix_re_set_eval_small_max", "gdmix_re_eval_acc_reset", "gdmix_re_eval_acc_add",
+    "gdmix_re_eval_acc_workspace_bytes", "gdmix_re_eval_acc_finish",
     "gdmix_re_class_kernel_name", "gdmix_java_string_hash", "gdmix_java_partition_id",
     "gdmix_java_partition_ids_i64")
 
@@ -168,7 +185,17 @@ def load_library():
     lib.gdmix_java_partition_id.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
     lib.gdmix_java_partition_id.restype = C.c_int32
     lib.gdmix_java_partition_ids_i64.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
-    if lib.gdmix_re_abi_version() != 12:
+    lib.gdmix_re_eval_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.gdmix_re_eval_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_eval_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(_EvalOut), C.c_void_p,
+                                           C.c_size_t, C.c_void_p]
+    lib.gdmix_re_set_eval_small_max.argtypes = [C.c_void_p, C.c_int]
+    lib.gdmix_re_eval_acc_reset.argtypes = [C.c_void_p, C.POINTER(_EvalAcc), C.c_void_p]
+    lib.gdmix_re_eval_acc_add.argtypes = [C.c_void_p, C.POINTER(_EvalAcc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.gdmix_re_eval_acc_workspace_bytes.argtypes = [C.c_int64]
+    lib.gdmix_re_eval_acc_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_eval_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalAcc), C.c_void_p, C.c_size_t, C.POINTER(_EvalTotals), C.c_void_p]
+    if lib.gdmix_re_abi_version() != 13:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 12
+#define GDMIX_RE_ABI_VERSION 13
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -51,7 +51,7 @@ extern "C" {
 #define GDMIX_RE_EINVAL    (-1)   /* bad argument */
 #define GDMIX_RE_EHIP      (-2)   /* a HIP runtime call failed (no device, launch failure, ...) */
 #define GDMIX_RE_ENOMEM    (-3)   /* workspace too small */
-#define GDMIX_RE_ERANGE    (-4)   /* an entity exceeds an int32 per-entity limit */
+#define GDMIX_RE_ERANGE    (-4)   /* an entity exceeds an int32 per-entity limit; an evaluation of 2^31 samples or entities or more */
 
 /* per-entity solver status, mirrors scipy fmin_l_bfgs_b's task/warnflag */
 #define GDMIX_RE_ST_PGTOL     0   /* CONVERGENCE: NORM OF PROJECTED GRADIENT <= PGTOL      */
@@ -357,6 +357,77 @@ GDMIX_API int gdmix_re_last_solve_ms(gdmix_re_ctx* ctx, float* ms_out);
 
 /* Name of the kernel variant that solved size class c (for profiling reports), or NULL. */
 GDMIX_API const char* gdmix_re_class_kernel_name(int c);
+
+/* ---- (ABI 13) evaluation: the stage metric on the device — exact AUC and MSE, per entity and over a whole stage ------------------
+ * What gdmix-data's Evaluator.scala computes in a Spark job of its own (Spark's BinaryClassificationMetrics / RegressionMetrics on
+ * (score, label), unweighted), and the AUC per entity, which the reference cannot report. csrc/re_evaluate.hip.
+ *
+ * Definitions
+ *   score       the fp32 predictionScore (what gdmix_re_score writes to `logit`). -0.0f equals +0.0f. Label positive <=> label > 0.5f.
+ *   key         fp32 score -> uint32 that orders as the floats do (-0 canonicalised to +0; sign bit set for non-negative scores, all bits
+ *               complemented for negative ones), the label in the low bit below it: a 33-bit key in which the negatives of a tie group
+ *               sort in front of its positives. gdmix_amd/metrics.py: sortable_key is the host statement of the 32-bit part.
+ *   twoU        sum over positives i of (2 #{negatives j: s_j < s_i} + #{negatives j: s_j == s_i}), an unsigned 64-bit integer.
+ *               AUC = twoU / (2 n_pos n_neg), undefined (NaN) when n_pos == 0 or n_neg == 0: ties at half weight, what Spark's
+ *               trapezoid over the distinct thresholds gives.
+ *   SSE         sum of (label - score)^2 in fp64, both widened from fp32 first; MSE = SSE / n, n = n_pos + n_neg. Added in trees of a
+ *               fixed shape (at most 2 048 terms in a row per lane; csrc/re_evaluate.hip states the shape): relative error below
+ *               2.5e-13, the same bits from run to run.
+ *   NaN         a NaN score is counted (n_nan) and left out of every sum and count; gdmix_amd/metrics.py reports AUC and MSE as NaN
+ *               when n_nan > 0. Infinities order as usual.
+ *   limits      fewer than 2^31 samples per evaluation and fewer than 2^31 entities: more is refused with GDMIX_RE_ERANGE and a
+ *               message, never approximated.
+ * The device returns the INTEGERS and the fp64 SSE; the global division is the caller's, from exact integers. Per entity the device also
+ * writes auc[e] = (double)twoU / (2.0 * (double)n_pos * (double)n_neg), one division of exactly converted integers: exact (correctly
+ * rounded) for entities below 2^26 samples — a caller redoes the division for larger ones.
+ * Out of scope: sample weights in the metric; metrics other than AUC and MSE; combining the accumulators of several workers (each worker
+ * finishes its own; from the counts a caller can combine MSE exactly and AUC not at all). */
+typedef struct {          /* device pointers, [E] each; any may be NULL */
+  uint64_t* two_u;
+  int32_t*  n_pos;
+  int32_t*  n_neg;
+  int32_t*  n_nan;
+  double*   sse;
+  double*   auc;
+} gdmix_re_eval_out;
+
+typedef struct {          /* host */
+  uint64_t two_u;
+  int64_t  n;             /* samples added, NaN scores included */
+  int64_t  n_pos, n_neg, n_nan;
+  double   sse;
+} gdmix_re_eval_totals;
+
+/* Per entity, for a scored batch: ent_row_ptr [E+1] (gdmix_re_packed.ent_row_ptr), score / label [N], all on the device. Entities of
+ * at most 64 samples are evaluated in registers, without a sort (1, 2 or 4 per wavefront pass); larger ones by a radix sort of
+ * (entity, key) and a rank-sum pass over the sorted keys. Results do not depend on which of the two an entity takes. Synchronises
+ * `stream` once (to learn how many entities take the sort path). Workspace: gdmix_re_eval_workspace_bytes (host only; 0 beyond the
+ * limits); too small a workspace is GDMIX_RE_ENOMEM. rocPRIM's temporary storage is the context's own (grow-only). */
+GDMIX_API size_t gdmix_re_eval_workspace_bytes(int64_t E, int64_t N);
+GDMIX_API int gdmix_re_eval_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                     const gdmix_re_eval_out* out, void* workspace, size_t workspace_bytes, void* stream);
+/* Testing knob: entities of more than `small_max` samples take the sort path (0 => every entity that has a sample). 0 .. 64, default 64. */
+GDMIX_API int gdmix_re_set_eval_small_max(gdmix_re_ctx* ctx, int small_max);
+
+/* The metric of a whole stage, which scores partition after partition (and training next to validation data): an accumulator, a host
+ * struct of the caller's. `keys` ([capacity] uint64 on the device: a sample's 33-bit key takes 8 bytes) and `state`
+ * (GDMIX_RE_EVAL_ACC_STATE_BYTES on the device) are the caller's buffers; `count` is kept by the library. `reset` empties it; `add`
+ * appends a batch's keys and adds up its SSE in one read of the samples; `finish` sorts once, runs the rank-sum pass with a single
+ * segment, synchronises `stream` and fills *host_out — the accumulator stays as it is, more batches may follow. A key buffer too small
+ * for count + N is GDMIX_RE_ENOMEM and nothing is added (the caller may move the keys to a larger buffer and set keys / capacity). The
+ * integers do not depend on how the samples were split into batches or on the order of the batches. */
+#define GDMIX_RE_EVAL_ACC_STATE_BYTES 33024
+typedef struct {
+  uint64_t* keys;
+  int64_t   capacity;
+  int64_t   count;
+  void*     state;
+} gdmix_re_eval_acc;
+GDMIX_API int gdmix_re_eval_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_acc* acc, void* stream);
+GDMIX_API int gdmix_re_eval_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_acc* acc, const float* score, const float* label, int64_t N, void* stream);
+GDMIX_API size_t gdmix_re_eval_acc_workspace_bytes(int64_t N);      /* N = acc->count */
+GDMIX_API int gdmix_re_eval_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_acc* acc, void* workspace, size_t workspace_bytes,
+                                       gdmix_re_eval_totals* host_out, void* stream);
 
 /* ---- B4: the upstream Spark partitioner's hash, bit-exact (host functions) ------------------------
  * hashCode over UTF-16 code units in wrapping int32; Math.abs(Int.MinValue) stays negative; Scala %
