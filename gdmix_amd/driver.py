@@ -97,6 +97,12 @@ class RandomEffectDriver:
     def run_training(self, schema_params, export_model=False, output_model_dir=None):
         logger.info(f"Commencing {self.effect_name} training")
         logger.info(f"Execution context : {self.execution_context}")
+        grid = getattr(getattr(self.model, "model_params", None), "l2_grid", None)
+        if grid is not None and grid() is not None:
+            # --l2_reg_weights: pass 1 solves every partition once per weight and compares the validation metric (sweep.py); it leaves
+            # the winner in model_params.l2_reg_weight, and what follows is the stage as it always runs
+            from . import sweep
+            sweep.run(self, schema_params)
         partition_index_list = self._get_partition_list()
         logger.info(f"This worker on work on the following list of partitions : {partition_index_list}")
         # With entity re-balancing the workers train in lockstep, one partition each per round; a worker that has no

@@ -2,6 +2,7 @@
 GDMixParams / SchemaParams / Params (gdmix-trainer/src/gdmix/params.py:12-50), LRParams
 (models/custom/base_lr_params.py:5-42) and REParams (models/custom/random_effect_lr_lbfgs_model.py:34-53).
 """
+import math
 from dataclasses import dataclass
 from typing import ClassVar, Optional
 
@@ -12,6 +13,25 @@ _ACTIONS = (constants.ACTION_INFERENCE, constants.ACTION_TRAIN)
 _STAGES = (constants.FIXED_EFFECT, constants.RANDOM_EFFECT)
 _MODEL_TYPES = (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION, constants.DETEXT)
 _VARIANCE_MODE = (constants.FULL, constants.SIMPLE)
+
+
+def parse_l2_grid(text):
+    """'100,10,3,1,0.1' -> (100.0, 10.0, 3.0, 1.0, 0.1): comma-separated finite floats >= 0, at least one, no duplicates."""
+    out = []
+    for item in str(text).split(","):
+        item = item.strip()
+        if not item:
+            raise ValueError(f"--l2_reg_weights={text!r}: an empty item")
+        try:
+            w = float(item)
+        except ValueError:
+            raise ValueError(f"--l2_reg_weights={text!r}: {item!r} is not a number") from None
+        if not math.isfinite(w) or w < 0.0:
+            raise ValueError(f"--l2_reg_weights={text!r}: {item!r} is not a finite weight >= 0")
+        if w in out:
+            raise ValueError(f"--l2_reg_weights={text!r}: {item!r} is listed twice")
+        out.append(w)
+    return tuple(out)
 
 
 class _ArgvMixin:
@@ -99,8 +119,17 @@ class REParams(LRParams):
     # not in the reference: the stage writes its metric (evalSummary.json: auc, or mse for linear_regression) and the per-entity
     # metrics of everything it scores under this directory, computed on the device while the scores are there (metrics.py)
     metric_output_dir: Optional[str] = None
+    # not in the reference: --action=train sweeps these weights inside the stage (sweep.py: every partition solved once per weight, the
+    # validation data scored under all of them, the stage metric of each on the device), then trains the stage as usual with the best one.
+    # Comma-separated; l2_reg_weight is ignored when it is given. Needs validation_data_dir and metric_output_dir.
+    l2_reg_weights: Optional[str] = None
+
+    def l2_grid(self):
+        """The weights of --l2_reg_weights in the order given, or None without the flag."""
+        return None if self.l2_reg_weights is None else parse_l2_grid(self.l2_reg_weights)
 
     def __post_init__(self):
+        self.l2_grid()      # a bad list is an error at parse time
         # the reference's REParams.__post_init__ does NOT chain to LRParams.__post_init__ (random_effect_lr_lbfgs_model.py:
         # 48-53): `--has_intercept False` with regularize_bias left at its default True is a valid random-effect
         # configuration upstream (test_random_effect_lr_lbfgs_model.py: warm start without intercept)

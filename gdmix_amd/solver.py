@@ -92,6 +92,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_fe_variance_of_hessian",
     "gdmix_re_eval_workspace_bytes", "gdmix_re_eval_entities", "gdmix_re_set_eval_small_max", "gdmix_re_eval_acc_reset", "gdmix_re_eval_acc_add",
     "gdmix_re_eval_acc_workspace_bytes", "gdmix_re_eval_acc_finish",
+    "gdmix_re_join_features", "gdmix_re_score_models_workspace_bytes", "gdmix_re_score_models",
     "gdmix_re_class_kernel_name", "gdmix_java_string_hash", "gdmix_java_partition_id",
     "gdmix_java_partition_ids_i64")
 
@@ -195,7 +196,12 @@ def load_library():
     lib.gdmix_re_eval_acc_workspace_bytes.argtypes = [C.c_int64]
     lib.gdmix_re_eval_acc_workspace_bytes.restype = C.c_size_t
     lib.gdmix_re_eval_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalAcc), C.c_void_p, C.c_size_t, C.POINTER(_EvalTotals), C.c_void_p]
-    if lib.gdmix_re_abi_version() != 13:
+    lib.gdmix_re_join_features.argtypes = [C.c_void_p, C.POINTER(_Packed), C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gdmix_re_score_models_workspace_bytes.argtypes = [C.c_int64, C.c_int]
+    lib.gdmix_re_score_models_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_score_models.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    if lib.gdmix_re_abi_version() != 14:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib
@@ -714,6 +720,56 @@ class REDeviceSolver:
         _check(self.lib.gdmix_re_score(self._h, C.byref(packed.c), int(packed.has_intercept), theta.data_ptr(),
                                        None if has_model is None else has_model.data_ptr(), logit.data_ptr(),
                                        per.data_ptr(), self._stream()), "gdmix_re_score")
+        return logit, per
+
+    # ---- sweep: K models of one training batch score another batch (include/gdmix_re.h, "sweep") ------------------------------
+    SWEEP_MODELS_PER_PASS = 8       # GDMIX_RE_SWEEP_MODELS_PER_PASS
+
+    @_serialised
+    def join_features(self, eval_packed: PackedBatch, train_packed: PackedBatch, train_entity):
+        """gdmix_re_join_features: train_entity [E_eval] int32 (numpy or device tensor; -1: the entity has no model) ->
+        (coef_pos [P_eval] int64, has_model [E_eval] uint8), device tensors."""
+        t = self.torch
+        if eval_packed.has_intercept != train_packed.has_intercept:
+            raise GdmixReError("join_features: the two batches differ in has_intercept")
+        if isinstance(train_entity, np.ndarray):
+            train_entity = t.from_numpy(np.ascontiguousarray(train_entity, np.int32)).to(self.device)
+        if train_entity.dtype != t.int32 or train_entity.numel() != eval_packed.E or not train_entity.is_cuda:
+            raise GdmixReError("train_entity must be int32 on the solver's device, one entry per entity of the evaluation batch")
+        coef_pos = t.empty(eval_packed.P, dtype=t.int64, device=self.device)
+        has_model = t.empty(eval_packed.E, dtype=t.uint8, device=self.device)
+        _check(self.lib.gdmix_re_join_features(self._h, C.byref(eval_packed.c), C.byref(train_packed.c), int(eval_packed.has_intercept),
+                                               train_entity.data_ptr() if eval_packed.E else None, coef_pos.data_ptr() if eval_packed.P else None,
+                                               has_model.data_ptr() if eval_packed.E else None, self._stream()), "gdmix_re_join_features")
+        return coef_pos, has_model
+
+    @_serialised
+    def score_models(self, eval_packed: PackedBatch, thetas, coef_pos, has_model=None, per_coord=True, slot_major=False):
+        """gdmix_re_score_models: thetas = K float64 device tensors in the TRAINING batch's index space, coef_pos / has_model from
+        join_features -> (logit [K, N], per_coord [K, N] | None) float32 device tensors. slot_major: each pass first copies its models
+        into one [P_train][models] array (a device temporary) so that a slot's coefficients are one contiguous read."""
+        t = self.torch
+        K = len(thetas)
+        if K < 1:
+            raise GdmixReError("score_models: no model")
+        P_train = int(thetas[0].numel())
+        for th in thetas:
+            if not th.is_cuda or th.dtype != t.float64 or th.numel() != P_train or not th.is_contiguous():
+                raise GdmixReError("score_models: every model is a contiguous float64 device array of the training batch's length")
+        if coef_pos.dtype != t.int64 or coef_pos.numel() != eval_packed.P:
+            raise GdmixReError("score_models: coef_pos must be int64 with one entry per coefficient slot of the evaluation batch")
+        N = eval_packed.N
+        logit = t.empty((K, N), dtype=t.float32, device=self.device)
+        per = t.empty((K, N), dtype=t.float32, device=self.device) if per_coord else None
+        ptrs = (C.c_void_p * K)(*[th.data_ptr() for th in thetas])
+        ws, nbytes = None, 0
+        if slot_major and P_train > 0:
+            nbytes = int(self.lib.gdmix_re_score_models_workspace_bytes(P_train, K))
+            ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=self.device)
+        _check(self.lib.gdmix_re_score_models(self._h, C.byref(eval_packed.c), int(eval_packed.has_intercept), ptrs, K, P_train,
+                                              coef_pos.data_ptr() if eval_packed.P else None, None if has_model is None else has_model.data_ptr(),
+                                              logit.data_ptr() if N else None, None if per is None or not N else per.data_ptr(),
+                                              None if ws is None else ws.data_ptr(), nbytes, self._stream()), "gdmix_re_score_models")
         return logit, per
 
     def partition_ids(self, ids, num_partitions: int):

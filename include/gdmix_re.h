@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 13
+#define GDMIX_RE_ABI_VERSION 14
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -237,7 +237,8 @@ GDMIX_API int gdmix_re_pack(gdmix_re_ctx* ctx, const gdmix_re_raw_batch* raw_dev
  * NEXT to the gdmix_re_solve the caller queues behind the pack: a copy-shaped kernel beside kernels bound by their arithmetic.
  * Every other member of gdmix_re_packed is ordered on `stream` as before. `unique_global` is ordered on the stream of the next of
  * these calls on the same context: gdmix_re_solve (on return the stream is behind the compaction as it is behind the solve),
- * gdmix_re_score, gdmix_re_variance_full, gdmix_fe_create, gdmix_re_pack (the next batch), gdmix_re_pack_join. A caller that reads
+ * gdmix_re_score, gdmix_re_variance_full, gdmix_fe_create, gdmix_re_pack (the next batch), gdmix_re_pack_join, gdmix_re_join_features,
+ * gdmix_re_score_models. A caller that reads
  * unique_global itself, or frees / reuses the workspace, without one of them in between calls gdmix_re_pack_join(ctx, stream)
  * first. Default off (everything stream-ordered when gdmix_re_pack returns); gdmix_amd/solver.py switches it on. Results are the
  * same bits either way. A context without side streams ignores the request. */
@@ -428,6 +429,45 @@ GDMIX_API int gdmix_re_eval_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_acc* acc, c
 GDMIX_API size_t gdmix_re_eval_acc_workspace_bytes(int64_t N);      /* N = acc->count */
 GDMIX_API int gdmix_re_eval_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_acc* acc, void* workspace, size_t workspace_bytes,
                                        gdmix_re_eval_totals* host_out, void* stream);
+
+/* ---- (ABI 14) sweep: K models trained on one batch score another batch in one pass over its non-zeros ----------------------------
+ * A stage that sweeps l2_reg_weight (gdmix_amd/sweep.py) solves a training partition K times and scores the validation partition under
+ * all K models. The models live in the TRAINING batch's coefficient index space (gdmix_re_result.theta_thr of K solves of one packed
+ * batch); the validation partition is a packed batch of its own, with other entities and other features per entity. csrc/re_sweep.hip.
+ *
+ * gdmix_re_join_features: where in the training batch's coefficient array every coefficient slot of the evaluation batch finds its value.
+ *   train_entity  [eval->E] int32, device: the training batch's row of the same entity, -1 if it has none (a value outside
+ *                 [0, train->E) counts as none). The caller builds it from the two id lists; an id listed twice in the training batch
+ *                 maps to its LAST row (the model a table built by dict.update keeps).
+ *   coef_pos      [P_eval] int64, device, P_eval = eval->D + eval->E * has_intercept: for slot s of the evaluation batch (entity e, the
+ *                 intercept or a global feature index g) the index in the training batch's [P_train] arrays of entity train_entity[e]'s
+ *                 coefficient for the same thing: intercept -> intercept, g -> the slot whose unique_global is g; -1 where that entity
+ *                 never saw g, or where e has no model.
+ *   has_model     [eval->E] uint8, device: train_entity[e] names a row.
+ *   Both unique_global lists are ascending inside an entity: a thread per evaluation feature bisects its entity's training list. Both
+ *   batches need a valid D (the host struct after gdmix_re_pack). Reads unique_global of both batches: it orders a deferred compaction
+ *   (gdmix_re_set_defer_unique) on `stream` first.
+ *
+ * gdmix_re_score_models: thetas = HOST array of K device pointers, each a [P_train] fp64 array in the training batch's index space.
+ *   logit [K][N] (row k at logit + k * N), logit_per_coord [K][N] or NULL, fp32, N = eval->N. Defined by equivalence: with
+ *       theta_mapped_k[s] = coef_pos[s] < 0 ? 0.0 : thetas[k][coef_pos[s]]
+ *   row k is BIT FOR BIT what gdmix_re_score(eval, has_intercept, theta_mapped_k, has_model, ...) writes: the same products in the same
+ *   order, every step one fused multiply-add acc = fma((double)v, t, acc) starting from the intercept (or +0.0 without one), a missing
+ *   coefficient entering as +0.0 — so a zero logit has the sign it has there. has_model NULL: every entity has a model (every slot is
+ *   then looked up; an intercept slot of -1 reads as +0.0). Every coef_pos entry must be -1 or below P_train (what
+ *   gdmix_re_join_features writes); nothing else is checked on the device.
+ *   One thread per sample, the entity search of gdmix_re_score; (value, column, coef_pos) of a non-zero are loaded once and feed the
+ *   accumulators of up to GDMIX_RE_SWEEP_MODELS_PER_PASS models; a longer list takes several passes over the batch.
+ *   workspace NULL: the K coefficients of a slot are gathered from the K arrays. workspace of at least
+ *   gdmix_re_score_models_workspace_bytes(P_train, K) device bytes: each pass first copies its models into one slot-major array
+ *   [P_train][models of the pass] there, and a slot's coefficients are one contiguous read. The same bits either way. */
+#define GDMIX_RE_SWEEP_MODELS_PER_PASS 8
+GDMIX_API int gdmix_re_join_features(gdmix_re_ctx* ctx, const gdmix_re_packed* eval, const gdmix_re_packed* train, int has_intercept,
+                                     const int32_t* train_entity, int64_t* coef_pos, uint8_t* has_model, void* stream);
+GDMIX_API size_t gdmix_re_score_models_workspace_bytes(int64_t P_train, int K);
+GDMIX_API int gdmix_re_score_models(gdmix_re_ctx* ctx, const gdmix_re_packed* eval, int has_intercept, const double* const* thetas, int K,
+                                    int64_t P_train, const int64_t* coef_pos, const uint8_t* has_model, float* logit, float* logit_per_coord,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- B4: the upstream Spark partitioner's hash, bit-exact (host functions) ------------------------
  * hashCode over UTF-16 code units in wrapping int32; Math.abs(Int.MinValue) stays negative; Scala %

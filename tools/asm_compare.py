@@ -22,6 +22,7 @@ from gdmix_amd import build      # noqa: E402
 
 
 def compile_units(csrc, out):
+    """-> {unit: assembly file} for the units of build.SOURCES that exist under csrc (a unit added since the other commit is not there)."""
     os.makedirs(out, exist_ok=True)
     flags = [f for f in build.FLAGS if f != "-shared"] + os.environ.get("GDMIX_EXTRA_FLAGS", "").split()
 
@@ -29,8 +30,9 @@ def compile_units(csrc, out):
         dst = os.path.join(out, f + ".s")
         subprocess.run([build.HIPCC] + flags + ["--cuda-device-only", "-S", os.path.join(csrc, f), "-o", dst], check=True, stderr=subprocess.DEVNULL)
         return dst
-    with ThreadPoolExecutor(len(build.SOURCES)) as ex:
-        return dict(zip(build.SOURCES, ex.map(one, build.SOURCES)))
+    units = [f for f in build.SOURCES if os.path.exists(os.path.join(csrc, f))]
+    with ThreadPoolExecutor(len(units)) as ex:
+        return dict(zip(units, ex.map(one, units)))
 
 
 def functions(path):
@@ -81,6 +83,9 @@ def main():
         s_old = compile_units(os.path.join(old, "gdmix_amd", "csrc"), os.path.join(tmp, "s_old"))
         s_new = compile_units(build.CSRC, os.path.join(tmp, "s_new"))
         for unit in build.SOURCES:
+            if unit not in s_old:
+                print(f"{unit}: a new unit, {len(functions(s_new[unit])[0])} functions only in this tree")
+                continue
             fo, mo = functions(s_old[unit])
             fn, mn = functions(s_new[unit])
             do, dn = demangle(list(fo)), demangle(list(fn))
