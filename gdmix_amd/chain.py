@@ -218,17 +218,22 @@ COMMON = ["--uid_column_name=uid", "--label_column_name=response",
 
 
 def metric_dir(root, stage):
-    """Where a random-effect stage of the chain writes its device metric (REParams.metric_output_dir)."""
+    """Where a stage of the chain writes its device metric (--metric_output_dir)."""
     return os.path.join(root, stage, "metrics")
 
 
-def stage_argv(root, stage, model_type=LOGISTIC, device_metrics=False):
+def stage_argv(root, stage, model_type=LOGISTIC, device_metrics=False, l2_grids=None):
     """The flat argv gdmix-workflow would hand the trainer for this stage of lr-movieLens.yaml (output under <root>/<stage>/).
-    device_metrics: a random-effect stage also reports its metric (--metric_output_dir, not a flag of the reference)."""
+    device_metrics: a random-effect stage also reports its metric (--metric_output_dir, not a flag of the reference).
+    l2_grids: {stage: "w0,w1,..."} — a stage listed there, the global one included, sweeps l2_reg_weight itself (--l2_reg_weights) and
+    reports its metric (a sweep needs the directory). None: the argv of every stage is what it was before the argument existed."""
     out = os.path.join(root, stage)
     common = [f"--model_type={model_type}"] + COMMON
-    if device_metrics and stage != "global":
+    grid = (l2_grids or {}).get(stage)
+    if (device_metrics and stage != "global") or grid is not None:
         common = common + [f"--metric_output_dir={metric_dir(root, stage)}"]
+    if grid is not None:
+        common = common + [f"--l2_reg_weights={grid}"]
     if stage == "global":
         d = os.path.join(root, "global")
         return ["gdmix", "--stage=fixed_effect", "--action=train", f"--training_data_dir={d}/trainingData", f"--validation_data_dir={d}/validationData",
@@ -291,13 +296,15 @@ def mse(label, score):
     return float(np.mean(d * d)) if d.size else float("nan")
 
 
-def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper_bounds=None, model_type=LOGISTIC, device_metrics=True):
+def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper_bounds=None, model_type=LOGISTIC, device_metrics=True, l2_grids=None):
     """global -> per_user -> per_movie under `root`; -> {stage: {"s", "partition_s", "train_auc", "validation_auc"}, "total_s"}.
     device_metrics: the two random-effect stages also report the metric they computed on the device while scoring
     ("train_<metric>_device", "validation_<metric>_device", from <root>/<stage>/metrics/evalSummary.json).
     upper_bounds: {stage: active-data bound per entity} (the rest of a larger entity's samples is passive data).
     model_type="linear_regression": every stage gets that model type, the labels are the ratings (real-valued), and a stage reports
-    "train_mse" / "validation_mse" instead of the AUC."""
+    "train_mse" / "validation_mse" instead of the AUC.
+    l2_grids: {stage: "w0,w1,..."} — a stage listed there sweeps l2_reg_weight inside the stage (stage_argv); its result gains
+    "l2_reg_weight" (the winner, from <root>/<stage>/metrics/sweep/evals.json) and the device metrics, the global stage's too."""
     if model_type not in (LOGISTIC, LINEAR):
         raise ValueError(f"model type {model_type!r}: the chain runs logistic_regression and linear_regression")
     metric = "mse" if model_type == LINEAR else "auc"
@@ -314,7 +321,8 @@ def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper
                             upper_bound=(upper_bounds or {}).get(stage), model_type=model_type)
             t_part = time.perf_counter() - t
         t = time.perf_counter()
-        run_stage(stage_argv(root, stage, model_type, device_metrics), child_process)
+        swept = (l2_grids or {}).get(stage) is not None
+        run_stage(stage_argv(root, stage, model_type, device_metrics, l2_grids), child_process)
         if stage == "global" and model_type == LINEAR:
             run_stage(global_training_scores_argv(root), child_process)
         dt = time.perf_counter() - t
@@ -324,13 +332,16 @@ def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper
             r[f"{which}_{metric}"] = mse(lab, sc) if metric == "mse" else auc(lab, sc)
             r[which + "_samples"] = int(uid.size)
         summary = os.path.join(metric_dir(root, stage), "evalSummary.json")
-        if device_metrics and stage != "global" and os.path.exists(summary):
+        if ((device_metrics and stage != "global") or swept) and os.path.exists(summary):
             with open(summary) as f:
                 dev = json.load(f)
             for which, block in (("train", "training"), ("validation", "validation")):
                 if block in dev:
                     v = dev[block][metric]
                     r[f"{which}_{metric}_device"] = float("nan") if v is None else v
+        if swept:
+            with open(os.path.join(metric_dir(root, stage), "sweep", "evals.json")) as f:
+                r["l2_reg_weight"] = json.load(f)["model params"]["l2_reg_weight"]
         out[stage] = r
         if log:
             log(f"{stage}: {dt:.2f} s (+ {t_part:.2f} s partition), {metric.upper()} train {r['train_' + metric]:.4f} validation {r['validation_' + metric]:.4f}")

@@ -1008,6 +1008,7 @@ struct gdmix_fe_problem {
   FeDev F;
   SolveParams o;
   void* pool;            // one device allocation carved into the vectors and partial sums
+  size_t pool_bytes, pool_multi, pool_multi_end, pool_inv;   // its size; the part gdmix_fe_restart keeps (F.multi); where F.inv lies
   void* copies[2];       // the row pass's and the column pass's copy of the non-zeros, with their unit tables
   void* ccopies[2];      // ... and their units in the 6-byte form
   int compress;          // bit 0: row pass, bit 1: column pass may use the 6-byte form (GDMIX_FE_COMPRESS; default: FE_COMPRESS_DEFAULT)
@@ -1408,6 +1409,7 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   const size_t o_inv = take(P * 4), o_sync = take(sizeof(FeSync));
   hipError_t rc = hipMalloc(&p->pool, off);
   if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", off, hipGetErrorString(rc)); fe_free(p); return GDMIX_RE_ENOMEM; }
+  p->pool_bytes = off; p->pool_multi = o_multi; p->pool_multi_end = o_red; p->pool_inv = o_inv;
   char* base = static_cast<char*>(p->pool);
   rc = hipMemsetAsync(base, 0, off, s);
   if (rc == hipSuccess) rc = hipMemsetAsync(base + o_inv, 0xff, P * 4, s);   // -1: the coefficient is not a column of this shard
@@ -1443,6 +1445,39 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   rc = hipGetLastError();
   if (rc != hipSuccess) { set_error("launch failed: %s", hipGetErrorString(rc)); fe_free(p); return GDMIX_RE_EHIP; }
   *out = p;
+  return GDMIX_RE_OK;
+}
+
+// The problem as gdmix_fe_create leaves it, for other options and another start point (include/gdmix_fe.h): the pool is zeroed again
+// but for the list of row blocks with several units, F.inv refilled, the start point and a fresh L-BFGS state written by the same
+// fe_init_kernel, the host's counters put back. Everything is enqueued behind whatever the stream still holds of the last solve.
+GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, const double* theta0, void* stream) {
+  if (!p || !opts) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
+  const FeDev& F = p->F;
+  if ((opts->has_intercept ? 1 : 0) != F.ic || opts->m != F.m || (opts->linear ? 1 : 0) != p->o.linear) {
+    set_error("gdmix_fe_restart: has_intercept, linear and m must be the creation's (%d, %d, %d), not (%d, %d, %d): the pool is sized by them",
+              F.ic, p->o.linear, F.m, opts->has_intercept ? 1 : 0, opts->linear ? 1 : 0, opts->m);
+    return GDMIX_RE_EINVAL;
+  }
+  if (opts->regularize_bias && !opts->has_intercept) { set_error("regularize_bias requires has_intercept"); return GDMIX_RE_EINVAL; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(p->ctx->impl.device));
+  SolveParams& o = p->o;
+  o.l2 = opts->l2; o.ftol = opts->ftol; o.pgtol = opts->pgtol; o.regularize_bias = opts->regularize_bias;
+  o.max_iter = opts->max_iter; o.maxfun = opts->maxfun; o.maxls = opts->maxls;
+  char* base = static_cast<char*>(p->pool);
+  HIP_TRY(hipMemsetAsync(base, 0, p->pool_multi, s));
+  HIP_TRY(hipMemsetAsync(base + p->pool_multi_end, 0, p->pool_bytes - p->pool_multi_end, s));
+  HIP_TRY(hipMemsetAsync(base + p->pool_inv, 0xff, (size_t)F.P * 4, s));
+  int gp = (F.P + 255) / 256;
+  if (gp > 1024) gp = 1024;
+  hipLaunchKernelGGL(fe_init_kernel, dim3(gp), dim3(256), 0, s, F, theta0);
+  HIP_TRY(hipGetLastError());
+  p->timed = false;
+  p->dirty = false;
+  p->gen = 0u;
+  p->seq = 0;
+  p->evals = 0;
   return GDMIX_RE_OK;
 }
 

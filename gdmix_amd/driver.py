@@ -271,6 +271,8 @@ class FixedEffectDriver:
 
     def run_training(self, schema_params, export_model=False, output_model_dir=None):
         logger.info(f"Commencing {self.effect_name} training")
+        if hasattr(self.model, "check_request"):      # --metric_output_dir / --l2_reg_weights: refusals come before a process group or a file
+            self.model.check_request(self.execution_context, constants.ACTION_TRAIN)
         self._init_collectives()
         ctx = dict(self.execution_context)
         ctx[constants.PARTITION_INDEX] = ctx[constants.TASK_INDEX]
@@ -282,6 +284,8 @@ class FixedEffectDriver:
 
     def run_inference(self, schema_params):
         logger.info(f"Commencing {self.effect_name} inference")
+        if hasattr(self.model, "check_request"):
+            self.model.check_request(self.execution_context, constants.ACTION_INFERENCE)
         ctx = dict(self.execution_context)
         ctx[constants.PARTITION_INDEX] = ctx[constants.TASK_INDEX]
         self.model.predict(output_dir=self.base_training_params.validation_score_dir,

@@ -13,6 +13,15 @@ gdmix_amd/fixed_effect.py. Same constructor, attributes, train / predict / expor
 Training with W > 1 workers: every worker runs this with torch.distributed initialised; gradient and value are
 all-reduced once per L-BFGS evaluation (fixed_effect.py: run_stepping_loop), the step is replicated.
 Not carried over: fixed_effect_variance_mode (rejected), copy_to_local and the TF server knobs (accepted, unused).
+
+Not in the reference, one worker only (both refused with several, before anything is read):
+  --metric_output_dir=DIR   everything the stage scores is also fed, from HBM, into an exact AUC (logistic_regression) or MSE
+       (linear_regression) on the device (metrics.DeviceEvaluator): DIR/evalSummary.json in the random-effect stage's layout
+       (metrics.StageMetrics.write_summary; no perEntity/: a fixed effect has no entities). --action=inference reports what it scores.
+  --l2_reg_weights=w0,w1,.. the stage sweeps l2_reg_weight itself: shards read, uploaded and packed once, gdmix_fe_create once, per
+       weight a cold gdmix_fe_restart + solve, the validation shard scored under all the models in one pass over its non-zeros
+       (gdmix_fe_score_models), one exact metric per weight, the files of sweep.py under DIR/sweep/. The winner's coefficients then go
+       through the rest of train() as if fit_stepping had returned them: the stage's files are those of a plain run at that weight.
 """
 import glob
 import logging
@@ -28,7 +37,7 @@ from .io import avro, native_reader, tfrecord
 from .io.features import read_feature_list
 from .io.grouped_reader import resolve_input_files
 from .io.metadata import DatasetMetadata
-from .params import LRParams
+from .params import LRParams, parse_l2_grid
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.INFO)
@@ -47,9 +56,18 @@ class FixedLRParams(LRParams):
     delayed_exit_in_seconds: int = 60
     disable_fixed_effect_scoring_after_training: bool = False
     fixed_effect_variance_mode: Optional[str] = None
+    # not in the reference (the random-effect stage's flags of the same names, params.REParams): the stage metric on the device, and
+    # a sweep over l2_reg_weight inside the stage; l2_reg_weight is ignored when the list is given
+    metric_output_dir: Optional[str] = None
+    l2_reg_weights: Optional[str] = None
+
+    def l2_grid(self):
+        """The weights of --l2_reg_weights in the order given, or None without the flag."""
+        return None if self.l2_reg_weights is None else parse_l2_grid(self.l2_reg_weights)
 
     def __post_init__(self):
         super().__post_init__()
+        self.l2_grid()      # a bad list is an error at parse time
         assert self.fixed_effect_variance_mode is None or self.fixed_effect_variance_mode in (constants.FULL, constants.SIMPLE), \
             f"Action: {self.fixed_effect_variance_mode} must be in {(constants.FULL, constants.SIMPLE)}"
 
@@ -157,6 +175,8 @@ class FixedEffectLRModelLBFGS:
         self.last_training_info = None
         self._device = device
         self._fe = None
+        self.metric_output_dir = p.metric_output_dir
+        self._metrics = None      # metrics.StageMetrics while a stage with --metric_output_dir runs
 
     # ---- helpers ------------------------------------------------------------------------------------------------
     def _parse_parameters(self, raw_model_parameters):
@@ -179,29 +199,140 @@ class FixedEffectLRModelLBFGS:
                                      schema_params.uid_column_name, schema_params.label_column_name, self.offset_column_name,
                                      schema_params.weight_column_name)
 
+    # ---- what the two flags refuse ---------------------------------------------------------------------------------
+    def check_request(self, execution_context, action=constants.ACTION_TRAIN):
+        """--metric_output_dir / --l2_reg_weights: everything they do not do is refused here, before a file is read, a process group
+        is formed or a solver created (as sweep.validate does for the random effect). Inference ignores --l2_reg_weights."""
+        from .sweep import SweepError
+        mp = self.model_params
+        grid = mp.l2_grid() if action == constants.ACTION_TRAIN else None
+        if grid is None and not mp.metric_output_dir:
+            return
+        if int(execution_context.get(constants.NUM_WORKERS) or 1) > 1:
+            flag = "--l2_reg_weights" if grid is not None else "--metric_output_dir"
+            raise SweepError(f"{flag} runs on one worker: the AUC of several workers cannot be combined from their counts")
+        if grid is None:
+            return
+        if not mp.validation_data_dir:
+            raise SweepError("--l2_reg_weights needs --validation_data_dir: only validation data can choose a weight")
+        if not mp.metric_output_dir:
+            raise SweepError("--l2_reg_weights needs --metric_output_dir: the sweep writes its metrics there")
+        prior = sorted(glob.glob(os.path.join(mp.output_model_dir, "*.avro"))) if mp.output_model_dir else []
+        if prior:
+            raise SweepError(f"--l2_reg_weights is a cold start, and {prior[0]} is a prior model the stage would warm-start from: "
+                             "warm-started sweeps are not implemented")
+
+    # ---- the stage metric (--metric_output_dir) ---------------------------------------------------------------------
+    def _metric_name(self):
+        from . import metrics
+        return metrics.MSE if self.model_type == constants.LINEAR_REGRESSION else metrics.AUC
+
+    def _begin_metrics(self):
+        self._metrics = None
+        if self.metric_output_dir:
+            from . import metrics
+            fe = self._solver()
+            if not hasattr(fe, "score_device"):
+                raise NotImplementedError("--metric_output_dir needs the device scoring path (FixedEffectDeviceSolver.score_device)")
+            self._metrics = metrics.StageMetrics(getattr(fe, "solver", None), self.metric_output_dir, self._metric_name())
+
+    def _finish_metrics(self):
+        m, self._metrics = self._metrics, None
+        return None if m is None else m.write_summary()
+
+    def _device_shard(self, data):
+        """The shard's sample-major arrays (and labels) in HBM, uploaded once per shard read."""
+        if "_dev" not in data:
+            bag = self.feature_bag_name is not None
+            data["_dev"] = self._solver().upload(data["row_nnz_ptr"] if bag else None, data["col"] if bag else None, data["val"] if bag else None,
+                                                 data["offset"], self.num_features if bag else 0, label=data["y"] if data["has_label"] else None)
+        return data["_dev"]
+
+    # ---- the sweep (--l2_reg_weights) ----------------------------------------------------------------------------------
+    def _stage_coefficients(self, theta):
+        """fit_stepping's coefficients as the stage keeps them: the dummy weight of an intercept-only model in front
+        (add_dummy_weight), then threshold_coefficients (:648-649)."""
+        if self.feature_bag_name is None:
+            theta = np.concatenate([[0.0], theta])
+        return np.where(np.abs(theta) <= self.sparsity_threshold, 0.0, theta)
+
+    def _sweep(self, data, vdata, grid):
+        """-> (theta, info) of the weight with the best validation metric, as fit_stepping returns them; model_params.l2_reg_weight is
+        the winner's from here on."""
+        from . import sweep
+        if not vdata["has_label"]:
+            raise sweep.SweepError("the validation data carries no labels: the sweep has nothing to compare")
+        fe = self._solver()
+        bag = self.feature_bag_name is not None
+        metric = self._metric_name()
+        out_dir = self.metric_output_dir
+        K = len(grid)
+        logger.info(f"sweeping l2_reg_weight over {list(grid)} by validation {metric}; --l2_reg_weight={self.l2_reg_weight} is ignored")
+
+        def select(thetas):
+            blocks = []
+            if vdata["n"] > 0:
+                shard = self._device_shard(vdata)
+                stage = [self._stage_coefficients(th) for th in thetas]
+                chunk = fe.models_per_chunk(K, stage[0].size, vdata["n"])
+                for first in range(0, K, chunk):
+                    _, per = fe.score_models(shard, [th if bag else th[1:] for th in stage[first:first + chunk]], self.has_intercept, per_coord=True)
+                    for j in range(per.shape[0]):
+                        ev = fe.new_evaluator()
+                        ev.add(fe.file_scores(shard, per[j]), shard.y)
+                        blocks.append(ev.finish())
+                    del per
+            else:
+                blocks = [fe.new_evaluator().finish() for _ in grid]
+            values = [b[metric] for b in blocks]
+            for k, (w, b) in enumerate(zip(grid, blocks)):
+                sweep.write_model_summary(out_dir, k, w, metric, b)
+            best = sweep.select_best(metric, values)      # (every metric undefined: the stage fails here, the per-model summaries say why)
+            sweep.write_evals(out_dir, metric, grid, values, best)
+            logger.info(f"sweep: validation {metric} {dict(zip(grid, values))}; best l2_reg_weight = {grid[best]} (index {best})")
+            return best
+
+        theta, info, best = fe.fit_sweep(
+            data["row_nnz_ptr"] if bag else np.zeros(data["n"] + 1, np.int64), data["col"] if bag else [], data["val"] if bag else [],
+            data["y"], self.num_features, l2_grid=grid, select=select, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
+            has_intercept=self.has_intercept, regularize_bias=self.is_regularize_bias, model_type=self.model_type, max_iter=self.max_iteration,
+            m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
+            variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold)
+        self.l2_reg_weight = self.model_params.l2_reg_weight = float(grid[best])
+        return theta, info
+
     # ---- train ----------------------------------------------------------------------------------------------------
     def train(self, training_data_dir, validation_data_dir, metadata_file, checkpoint_path, execution_context, schema_params):
         task_index = execution_context[constants.TASK_INDEX]
         num_workers = execution_context[constants.NUM_WORKERS]
         is_chief = execution_context[constants.IS_CHIEF]
+        self.check_request(execution_context, constants.ACTION_TRAIN)
+        grid = self.model_params.l2_grid()
+        self._begin_metrics()
         data = self._read(training_data_dir, num_workers, task_index, schema_params)
-        prev_model = self._load_model(catch_exception=True)
-        expected = self.num_features + 1 if self.has_intercept else self.num_features
-        x0 = None
-        if prev_model is not None and len(prev_model) == expected:
-            logger.info("Found a previous model, loaded as the initial point for training")
-            x0 = np.asarray(prev_model, np.float64)
-        elif prev_model is not None:
-            logger.info(f"Initial model size is {len(prev_model)}, expected {expected}, use all zeros instead.")
         D = self.num_features
         bag = self.feature_bag_name is not None
-        theta, info = self._solver().fit_stepping(
-            data["row_nnz_ptr"] if bag else np.zeros(data["n"] + 1, np.int64), data["col"] if bag else [], data["val"] if bag else [],
-            data["y"], D, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
-            has_intercept=self.has_intercept, l2=self.l2_reg_weight, regularize_bias=self.is_regularize_bias,
-            model_type=self.model_type, theta0=self._strip_dummy(x0) if not bag else x0, max_iter=self.max_iteration,
-            m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
-            variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold)
+        vdata = None
+        if grid is not None:
+            # --l2_reg_weights: the validation shard is read here, once, and chooses the weight; no prior model (check_request)
+            vdata = self._read(validation_data_dir, num_workers, task_index, schema_params)
+            theta, info = self._sweep(data, vdata, grid)
+        else:
+            prev_model = self._load_model(catch_exception=True)
+            expected = self.num_features + 1 if self.has_intercept else self.num_features
+            x0 = None
+            if prev_model is not None and len(prev_model) == expected:
+                logger.info("Found a previous model, loaded as the initial point for training")
+                x0 = np.asarray(prev_model, np.float64)
+            elif prev_model is not None:
+                logger.info(f"Initial model size is {len(prev_model)}, expected {expected}, use all zeros instead.")
+            theta, info = self._solver().fit_stepping(
+                data["row_nnz_ptr"] if bag else np.zeros(data["n"] + 1, np.int64), data["col"] if bag else [], data["val"] if bag else [],
+                data["y"], D, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
+                has_intercept=self.has_intercept, l2=self.l2_reg_weight, regularize_bias=self.is_regularize_bias,
+                model_type=self.model_type, theta0=self._strip_dummy(x0) if not bag else x0, max_iter=self.max_iteration,
+                m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
+                variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold)
         self.variances = info.pop("variances", None)
         if not bag:
             theta = np.concatenate([[0.0], theta])   # the dummy weight of an intercept-only model (add_dummy_weight)
@@ -214,25 +345,39 @@ class FixedEffectLRModelLBFGS:
         # the reference's variance computation rides on the scoring pass over the training data, which therefore runs (and writes
         # its scores) whenever a variance mode is set (:650-661)
         if not self.disable_fixed_effect_scoring_after_training or self.fixed_effect_variance_mode is not None:
-            self._score_and_write(theta, data, task_index, schema_params, self.training_output_dir)
+            self._score_and_write(theta, data, task_index, schema_params, self.training_output_dir, which="training")
         if validation_data_dir:
-            vdata = self._read(validation_data_dir, num_workers, task_index, schema_params)
-            self._score_and_write(theta, vdata, task_index, schema_params, self.validation_output_dir)
+            if vdata is None:
+                vdata = self._read(validation_data_dir, num_workers, task_index, schema_params)
+            self._score_and_write(theta, vdata, task_index, schema_params, self.validation_output_dir, which="validation")
         if is_chief:
             self._save_model()
+        self._finish_metrics()
 
     @staticmethod
     def _strip_dummy(x0):
         return None if x0 is None else x0[1:]
 
     # ---- scoring ---------------------------------------------------------------------------------------------------
-    def _score_and_write(self, theta, data, task_index, schema_params, output_dir):
-        """logits = X w + b (per-coordinate score), + offset (score); :214-306,406-440."""
+    def _score_and_write(self, theta, data, task_index, schema_params, output_dir, which="validation"):
+        """logits = X w + b (per-coordinate score), + offset (score); :214-306,406-440. With --metric_output_dir the scores stay in HBM
+        long enough to enter `which`'s accumulator of the stage metric: the very floats the score file holds."""
         from .fixed_effect import shard_as_batch, to_local
         n = data["n"]
         bag = self.feature_bag_name is not None
+        if self._metrics is not None and not data["has_label"]:
+            self._metrics.no_labels(f"the {which} data")
         if n == 0:
             per_coord = np.zeros(0, np.float32)
+        elif self._metrics is not None:
+            fe = self._solver()
+            shard = self._device_shard(data)
+            _, per_dev = fe.score_device(shard, theta if bag else theta[1:], self.has_intercept)
+            if data["has_label"]:
+                if which not in self._metrics.ev:
+                    self._metrics.ev[which] = fe.new_evaluator()
+                self._metrics.ev[which].add(fe.file_scores(shard, per_dev), shard.y)
+            per_coord = fe.to_host(per_dev)
         else:
             fe = self._solver()
             if hasattr(fe, "score"):      # the device path: one pass over the sample-major arrays, no pack
@@ -366,6 +511,9 @@ class FixedEffectLRModelLBFGS:
     def predict(self, output_dir, input_data_path, metadata_file, checkpoint_path, execution_context, schema_params):
         task_index = execution_context[constants.TASK_INDEX]
         num_workers = execution_context[constants.NUM_WORKERS]
+        self.check_request(execution_context, constants.ACTION_INFERENCE)      # (--l2_reg_weights is ignored here)
+        self._begin_metrics()
         data = self._read(input_data_path, num_workers, task_index, schema_params)
         theta = self._load_model()
-        self._score_and_write(theta, data, task_index, schema_params, output_dir)
+        self._score_and_write(theta, data, task_index, schema_params, output_dir, which="validation")
+        self._finish_metrics()

@@ -108,6 +108,44 @@ class FixedEffectDeviceSolver:
         """-> (score, per-coordinate score) of every sample under theta (intercept last); see device_score."""
         return device_score(self.solver, row_nnz_ptr, col_global, val, offset, theta, num_features, has_intercept)
 
+    def upload(self, row_nnz_ptr, col_global, val, offset, num_features, label=None):
+        """The sample-major arrays of a raw shard on the device, once, for any number of score_device / score_models calls."""
+        return DeviceShard(self.solver, row_nnz_ptr, col_global, val, offset, num_features, label)
+
+    def score_device(self, shard, theta, has_intercept=True):
+        """-> (score, per-coordinate score) of an uploaded shard as float32 DEVICE tensors (gdmix_fe_score); theta: numpy or device."""
+        return device_score_shard(self.solver, shard, theta, has_intercept)
+
+    def score_models(self, shard, thetas, has_intercept=True, per_coord=True, slot_major=True):
+        """gdmix_fe_score_models: K coefficient vectors (numpy or float64 device tensors, intercept last) over an uploaded shard in one
+        pass over its non-zeros -> (score [K, n], per_coord [K, n] | None) float32 device tensors; row k is bit for bit score_device's
+        for thetas[k]. slot_major: each pass first copies its models into one [coefficient][model] array (a device temporary)."""
+        return device_score_models(self.solver, shard, thetas, has_intercept, per_coord, slot_major)
+
+    def file_scores(self, shard, per_coord):
+        """The predictionScore the stage's score file holds for these per-coordinate scores — float32(float64(per_coord) + float64(offset)),
+        as fe_model._score_and_write forms it on the host — without leaving the device (what the stage metric is computed on)."""
+        t = self.solver.torch
+        return (per_coord.to(t.float64) + shard.of.to(t.float64)).to(t.float32)
+
+    @staticmethod
+    def to_host(x):
+        return x.cpu().numpy()
+
+    def new_evaluator(self):
+        """An accumulator of the exact stage metric for scores that stay on the device (metrics.DeviceEvaluator)."""
+        from . import metrics
+        return metrics.DeviceEvaluator(self.solver)
+
+    def models_per_chunk(self, K, P, n_eval):
+        """How many of K models are scored at once: all of them if K x (coefficients + score and per-coordinate rows) fits into half
+        of the free device memory (GDMIX_SWEEP_CHUNK sets it: tests) — sweep._models_per_chunk with the fixed effect's two rows."""
+        forced = int(os.environ.get("GDMIX_SWEEP_CHUNK", "0"))
+        if forced > 0:
+            return min(K, forced)
+        free, _ = self.solver.torch.cuda.mem_get_info(self.solver.device)
+        return int(max(1, min(K, (free // 2) // (8 * P + 8 * n_eval + 1))))
+
     def fit(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
             regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12, dummy=None):
         """-> (theta [num_features + has_intercept], intercept last; info dict with f, nit, nfev, status, gnorm)."""
@@ -133,27 +171,84 @@ class FixedEffectDeviceSolver:
         return theta, info
 
 
-def device_score(solver, row_nnz_ptr, col_global, val, offset, theta, num_features, has_intercept):
-    """(score, per-coordinate score) float32 numpy arrays of every sample: x . w + b (+ offset). theta: [num_features +
-    has_intercept], intercept last. The shard is read once off its sample-major arrays (gdmix_fe_score): no pack."""
+class DeviceShard:
+    """A raw shard's sample-major arrays in HBM: row_nnz_ptr [n + 1] / col_global / val (None, None, None for a model without a
+    feature bag), offset [n], and the labels when given. Feature indices are checked against [0, num_features) once, here."""
+
+    def __init__(self, solver, row_nnz_ptr, col_global, val, offset, num_features, label=None):
+        t = solver.torch
+        dev = solver.device
+        up = lambda a, dt: None if a is None else t.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
+        self.n = (len(row_nnz_ptr) - 1) if row_nnz_ptr is not None else len(offset)
+        self.rp, self.cg, self.vl = up(row_nnz_ptr, np.int64), up(col_global, np.int64), up(val, np.float32)
+        if self.cg is not None and self.cg.numel() and (int(self.cg.min()) < 0 or int(self.cg.max()) >= num_features):
+            raise ValueError(f"feature index outside [0, {num_features})")
+        self.of = up(offset, np.float32)
+        self.y = up(label, np.float32)
+        self.num_features = int(num_features)
+
+    def pointers(self):
+        """(row_nnz_ptr, col_global, val, offset) as the library takes them: NULL for what is absent or empty."""
+        ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()
+        return (None if self.cg is None or self.cg.numel() == 0 else self.rp.data_ptr()), ptr(self.cg), ptr(self.vl), ptr(self.of)
+
+
+def _theta_on_device(solver, theta, P):
     t = solver.torch
-    n = (len(row_nnz_ptr) - 1) if row_nnz_ptr is not None else len(offset)
-    dev = solver.device
-    up = lambda a, dt: None if a is None else t.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
-    rp, cg, vl = up(row_nnz_ptr, np.int64), up(col_global, np.int64), up(val, np.float32)
-    if cg is not None and cg.numel() and (int(cg.min()) < 0 or int(cg.max()) >= num_features):
-        raise ValueError(f"feature index outside [0, {num_features})")
-    of = up(offset, np.float32)
-    th = up(theta, np.float64)
-    assert th.numel() == num_features + (1 if has_intercept else 0)
-    score = t.empty(n, dtype=t.float32, device=dev)
-    per = t.empty(n, dtype=t.float32, device=dev)
-    ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()
-    rc = solver.lib.gdmix_fe_score(solver._h, n, None if cg is None or cg.numel() == 0 else rp.data_ptr(), ptr(cg), ptr(vl), ptr(of),
-                                   th.data_ptr(), int(num_features), int(bool(has_intercept)), ptr(score), ptr(per), solver._stream())
+    th = theta if t.is_tensor(theta) else t.from_numpy(np.ascontiguousarray(theta, np.float64)).to(solver.device)
+    if not th.is_cuda or th.dtype != t.float64 or not th.is_contiguous() or th.numel() != P:
+        from .solver import GdmixReError
+        raise GdmixReError(f"a coefficient vector is a contiguous float64 array of {P} entries (intercept last)")
+    return th
+
+
+def device_score_shard(solver, shard, theta, has_intercept):
+    """(score, per-coordinate score) float32 DEVICE tensors of every sample of an uploaded shard (gdmix_fe_score)."""
+    t = solver.torch
+    th = _theta_on_device(solver, theta, shard.num_features + (1 if has_intercept else 0))
+    score = t.empty(shard.n, dtype=t.float32, device=solver.device)
+    per = t.empty(shard.n, dtype=t.float32, device=solver.device)
+    if shard.n == 0:
+        return score, per
+    rc = solver.lib.gdmix_fe_score(solver._h, shard.n, *shard.pointers(), th.data_ptr(), shard.num_features, int(bool(has_intercept)),
+                                   score.data_ptr(), per.data_ptr(), solver._stream())
     if rc != 0:
         from .solver import GdmixReError
         raise GdmixReError("gdmix_fe_score: " + solver.lib.gdmix_re_last_error().decode())
+    return score, per
+
+
+def device_score_models(solver, shard, thetas, has_intercept, per_coord=True, slot_major=True):
+    """gdmix_fe_score_models over an uploaded shard -> (score [K, n], per_coord [K, n] | None) float32 device tensors."""
+    from .solver import GdmixReError
+    t = solver.torch
+    K = len(thetas)
+    if K < 1:
+        raise GdmixReError("score_models: no model")
+    P = shard.num_features + (1 if has_intercept else 0)
+    ths = [_theta_on_device(solver, th, P) for th in thetas]
+    n = shard.n
+    score = t.empty((K, n), dtype=t.float32, device=solver.device)
+    per = t.empty((K, n), dtype=t.float32, device=solver.device) if per_coord else None
+    ptrs = (C.c_void_p * K)(*[th.data_ptr() for th in ths])
+    ws, nbytes = None, 0
+    if slot_major:
+        nbytes = int(solver.lib.gdmix_fe_score_models_workspace_bytes(shard.num_features, K))
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=solver.device)
+    rc = solver.lib.gdmix_fe_score_models(solver._h, n, *shard.pointers(), ptrs, K, shard.num_features, int(bool(has_intercept)),
+                                          score.data_ptr() if n else None, None if per is None or not n else per.data_ptr(),
+                                          None if ws is None else ws.data_ptr(), nbytes, solver._stream())
+    if rc != 0:
+        raise GdmixReError("gdmix_fe_score_models: " + solver.lib.gdmix_re_last_error().decode())
+    return score, per
+
+
+def device_score(solver, row_nnz_ptr, col_global, val, offset, theta, num_features, has_intercept):
+    """(score, per-coordinate score) float32 numpy arrays of every sample: x . w + b (+ offset). theta: [num_features +
+    has_intercept], intercept last. The shard is read once off its sample-major arrays (gdmix_fe_score): no pack. Uploads the shard
+    and downloads the scores on every call; DeviceShard + device_score_shard keep both in HBM."""
+    shard = DeviceShard(solver, row_nnz_ptr, col_global, val, offset, num_features)
+    score, per = device_score_shard(solver, shard, theta, has_intercept)
     return score.cpu().numpy(), per.cpu().numpy()
 
 
@@ -185,6 +280,14 @@ class _SteppingProblem:
         from .solver import GdmixReError
         if rc != 0:
             raise GdmixReError(f"{what}: " + self.lib.gdmix_re_last_error().decode())
+
+    def restart(self, opts, theta0_dev=None):
+        """gdmix_fe_restart: the problem as creation left it, for other options (l2, regularize_bias, the limits and tolerances) and
+        another start point (None: zeros); the copies of the non-zeros and their tables stay. Stream-ordered."""
+        c_opts = opts.to_c()
+        self._check(self.lib.gdmix_fe_restart(self._h, C.byref(c_opts), None if theta0_dev is None else theta0_dev.data_ptr(),
+                                              self.solver._stream()), "gdmix_fe_restart")
+        self.theta0 = theta0_dev      # kept alive: a kernel on the stream reads it
 
     def reduce_tensor(self):
         """The [gradient, value] buffer as a torch tensor view (no copy), for torch.distributed.all_reduce."""
@@ -304,13 +407,10 @@ def run_stepping_loop(problem, all_reduce=None, max_evals=100000, lookahead=None
     raise RuntimeError(f"the fixed-effect L-BFGS loop did not stop within {max_evals} evaluations")
 
 
-def _fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
-                  regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
-                  group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0):
-    """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
-    worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
-    model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
-    hold no non-zero, so that its all-reduce buffer has the same num_features + 2 entries as everyone else's."""
+def _stepping_setup(self, row_nnz_ptr, col_global, val, y, num_features, offset, weight, has_intercept, l2, regularize_bias, model_type, theta0,
+                    max_iter, m, tolerance, group, dummy, variance_mode):
+    """What a fit through include/gdmix_fe.h needs before its loop: the shard as a packed one-entity batch, the options, the problem
+    (gdmix_fe_create) and the all-reduce of this process group. -> (solver, batch, dummy, D, packed, opts, problem, all_reduce)."""
     if model_type not in (LOGISTIC_REGRESSION, LINEAR_REGRESSION):
         raise ValueError(f"unknown model type {model_type!r}")
     batch, dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, has_intercept,
@@ -352,6 +452,18 @@ def _fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=No
                     t.copy_(h)
     except ImportError:
         pass
+    return s, batch, dummy, D, packed, opts, prob, all_reduce
+
+
+def _fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
+                  regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
+                  group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0):
+    """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
+    worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
+    model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
+    hold no non-zero, so that its all-reduce buffer has the same num_features + 2 entries as everyone else's."""
+    s, batch, dummy, D, packed, opts, prob, all_reduce = _stepping_setup(self, row_nnz_ptr, col_global, val, y, num_features, offset, weight, has_intercept, l2,
+                                                                         regularize_bias, model_type, theta0, max_iter, m, tolerance, group, dummy, variance_mode)
     status = run_stepping_loop(prob, all_reduce)
     theta, info = prob.result()
     info["status"] = status
@@ -369,6 +481,40 @@ def _fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=No
         return theta, info, prob
     prob.close()
     return theta, info
+
+
+def _fit_sweep(self, row_nnz_ptr, col_global, val, y, num_features, l2_grid, select, offset=None, weight=None, has_intercept=True,
+               regularize_bias=True, model_type=LOGISTIC_REGRESSION, max_iter=100, m=10, tolerance=1e-12, dummy=None, variance_mode=None,
+               threshold=0.0):
+    """One worker's fit for every weight of l2_grid on ONE problem: the shard is packed and gdmix_fe_create runs once; per weight, in the
+    order given, gdmix_fe_restart (cold: zeros) + the same loop and status check as fit_stepping — by the restart's contract the bits
+    of a fresh fit_stepping at that weight. select(thetas) — the K coefficient vectors as fit_stepping would have returned them — names
+    the winner; -> (theta, info, best) of the winner as fit_stepping returns them, its variances (at its weight, for it alone) included."""
+    import dataclasses
+    if _world_size(None) > 1:
+        raise ValueError("a sweep over l2_reg_weight runs on one worker")
+    s, batch, dummy, D, packed, opts, prob, all_reduce = _stepping_setup(self, row_nnz_ptr, col_global, val, y, num_features, offset, weight, has_intercept,
+                                                                         float(l2_grid[0]), regularize_bias, model_type, None, max_iter, m, tolerance, None,
+                                                                         dummy, variance_mode)
+    try:
+        fits = []
+        for w in l2_grid:
+            prob.restart(dataclasses.replace(opts, l2=float(w)), None)
+            status = run_stepping_loop(prob, None)
+            theta, info = prob.result()
+            info["status"] = status
+            fits.append((theta, info))
+        best = int(select([th[D:] if dummy else th for th, _ in fits]))
+        theta, info = fits[best]
+        if variance_mode is not None:
+            th = np.where(np.abs(theta) <= threshold, 0.0, theta)
+            info["variances"] = _variances(s, prob, batch, th, D, has_intercept, float(l2_grid[best]), bool(regularize_bias) and bool(has_intercept),
+                                           str(variance_mode).upper(), None, None, packed=packed, dummy=dummy)
+            if dummy:
+                info["variances"] = info["variances"][D:]
+        return (theta[D:] if dummy else theta), info, best
+    finally:
+        prob.close()
 
 
 # FULL densifies a (D + 1) x (D + 1) Hessian, as the reference does (fixed_effect_lr_lbfgs_model.py:291, 457: no limit there but
@@ -508,3 +654,4 @@ def _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2,
 
 
 FixedEffectDeviceSolver.fit_stepping = _fit_stepping
+FixedEffectDeviceSolver.fit_sweep = _fit_sweep

@@ -107,6 +107,35 @@ GDMIX_API int gdmix_fe_score(gdmix_re_ctx* ctx, int64_t n, const int64_t* row_nn
                              const float* offset, const double* theta, int64_t num_features, int has_intercept, float* score,
                              float* per_coord, void* stream);
 
+/* ---- a sweep over l2 inside one stage (ABI 15; gdmix_amd/fe_model.py: --l2_reg_weights) ----
+ *
+ * gdmix_fe_restart puts an existing problem back into exactly the state gdmix_fe_create leaves it in, for new l2, regularize_bias,
+ * max_iter, maxfun, maxls, ftol, pgtol and a new start point (theta0: device pointer [D + has_intercept] or NULL = zeros; read by a
+ * kernel on the stream, so it must stay alive until the stream has passed this call). Cleared and re-armed: the L-BFGS state, history,
+ * plan and vectors, the shard-local copy of x, the reduce buffer (and the library's note that it is dirty), every partial sum, the
+ * finishing counters, the sync words of the one-launch step, the status ring and the counts of steps / evaluations / launches, and with
+ * the state the stop flag — which made every kernel of the stopped problem a no-op: a restart may come right behind a gdmix_fe_solve
+ * that left `lookahead` no-op evaluations queued after the stop. Kept as they are: both copies of the non-zeros, their unit tables, the
+ * frequent-column tables and the list of row blocks with several units — everything gdmix_fe_create sorted, split and synchronised for.
+ * opts->has_intercept, opts->linear and opts->m must equal the creation's (the pool is sized and the copies are read by them):
+ * GDMIX_RE_EINVAL otherwise. Stream-ordered, no synchronisation. The definition of the call: a solve after a restart gives the same
+ * bits as gdmix_fe_create with those options and that start point followed by the same solve. */
+GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, const double* theta0, void* stream);
+
+/* gdmix_fe_score under K coefficient vectors in ONE pass over the shard's non-zeros (csrc/fe_sweep.hip). thetas: HOST array of K device
+ * pointers, each [num_features + has_intercept] with the intercept last; score / per_coord: [K][n] float, row k for thetas[k]
+ * (per_coord may be NULL). Defined by equivalence: row k is bit for bit what gdmix_fe_score writes for thetas[k] — a row's products
+ * are added in the row's order, each step one fused multiply-add into one fp64 accumulator that starts at the intercept. (col, val) of a
+ * non-zero are loaded once and feed up to GDMIX_RE_SWEEP_MODELS_PER_PASS accumulators: 12 B per non-zero per pass instead of per model; a
+ * longer list takes several passes. workspace (device, gdmix_fe_score_models_workspace_bytes(num_features, K) bytes; may be NULL): each
+ * pass first copies its coefficient vectors into one slot-major array [num_features + 1][models of the pass], so that a non-zero's
+ * coefficients are one contiguous read; without it they are read from the K arrays. Same arguments otherwise as gdmix_fe_score; n = 0 is
+ * legal and does nothing. */
+GDMIX_API size_t gdmix_fe_score_models_workspace_bytes(int64_t num_features, int K);
+GDMIX_API int gdmix_fe_score_models(gdmix_re_ctx* ctx, int64_t n, const int64_t* row_nnz_ptr, const int64_t* col_global, const float* val,
+                                    const float* offset, const double* const* thetas, int K, int64_t num_features, int has_intercept,
+                                    float* score, float* per_coord, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Bytes of non-zero entries one row pass / one column pass of this problem reads (its own copies of the shard: 8 B per entry, 10 in the
  * three-array form; units in the 6-byte form of round 5 — values + 16-bit {key delta, accumulator} words — with their fillers and
  * padding). What the passes stream, next to the algorithmic 8 B per entry and pass the bench's roofline figure is quoted on. */
