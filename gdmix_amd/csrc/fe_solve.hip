@@ -1027,15 +1027,6 @@ struct gdmix_fe_problem {
 };
 constexpr int FE_RING = 8;
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _rc = (expr);                                                            \
-    if (_rc != hipSuccess) {                                                            \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_rc), __FILE__, __LINE__); \
-      return GDMIX_RE_EHIP;                                                             \
-    }                                                                                   \
-  } while (0)
-
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Entries per unit. Blocks stay whole (a row block then finishes its rows itself) when that still gives the device enough
@@ -1523,10 +1514,7 @@ GDMIX_API int gdmix_fe_hessian_dense(gdmix_re_ctx* ctx, const gdmix_re_packed* b
   if (ld < b->D + ic || ld % 64) { set_error("ld must be d + has_intercept rounded up to a multiple of 64"); return GDMIX_RE_EINVAL; }
   if (scratch_bytes < hessian_dense_scratch_doubles(b->N) * 8) { set_error("scratch too small"); return GDMIX_RE_ENOMEM; }
   HIP_TRY(hipSetDevice(ctx->impl.device));
-  BatchDev B;
-  B.ent_row_ptr = b->ent_row_ptr; B.ent_nnz_ptr = b->ent_nnz_ptr; B.ent_feat_ptr = b->ent_feat_ptr; B.row_ptr = b->row_ptr; B.csr_col = b->csr_col;
-  B.csr_val = b->csr_val; B.col_ptr = b->col_ptr; B.csc_row = b->csc_row; B.csc_val = b->csc_val; B.y = b->y; B.offset = b->offset; B.weight = b->weight;
-  B.order = b->order;
+  const BatchDev B = batch_dev(b);
   HIP_TRY(launch_hessian_dense(&ctx->impl, B, b->N, b->D, ic, theta_local, H, ld, static_cast<double*>(scratch), static_cast<hipStream_t>(stream)));
   return GDMIX_RE_OK;
 }

@@ -3,8 +3,8 @@
 // in include/gdmix_fe.h (gdmix_fe_score_models); this unit is its only implementation and adds symbols only: no kernel of another
 // unit changes.
 //
-//   fe_sweep_transpose_kernel   the KP coefficient vectors of a pass -> one slot-major array [num_features + 1][KP] (only when the
-//                               caller gave a workspace): the KP coefficients of a feature are one contiguous KP * 8-byte read — for
+//   sweep_transpose_kernel      (sweep_common.hpp, shared with re_sweep.hip) the KP coefficient vectors of a pass -> one slot-major
+//                               array [num_features + 1][KP] (only when the caller gave a workspace): the KP coefficients of a feature are one contiguous KP * 8-byte read — for
 //                               KP = 8 half a 128-byte line — instead of KP lines KP arrays apart. The vectors are tiny next to X.
 //   fe_sweep_score_kernel       one thread per sample straight off the reader's sample-major arrays, as fe_score_kernel (fe_solve.hip);
 //                               (column, value) of a non-zero are loaded once and feed KP accumulators, KP in {1, 2, 4, 8} models per
@@ -18,39 +18,13 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "re_internal.hpp"
+#include "sweep_common.hpp"
 #include "../../include/gdmix_fe.h"
 
 namespace gdmix {
 
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t _rc = (expr);                                                                 \
-    if (_rc != hipSuccess) {                                                                 \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_rc), __FILE__, __LINE__); \
-      return GDMIX_RE_EHIP;                                                                  \
-    }                                                                                        \
-  } while (0)
-
-constexpr int FE_SWEEP_MAX_KP = GDMIX_RE_SWEEP_MODELS_PER_PASS;
-
-template <int KP>
-struct FeSweepThetas { const double* p[KP]; };
-
-// tm[j * KP + k] = theta_k[j]: coalesced reads of KP arrays, KP * 8 contiguous bytes written per coefficient
-template <int KP>
-__global__ __launch_bounds__(256) void fe_sweep_transpose_kernel(FeSweepThetas<KP> T, int64_t P, double* __restrict__ tm) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= P) return;
-  double v[KP];
-#pragma unroll
-  for (int k = 0; k < KP; ++k) v[k] = T.p[k][j];
-#pragma unroll
-  for (int k = 0; k < KP; ++k) tm[j * KP + k] = v[k];
-}
-
 template <int KP, bool SLOT_MAJOR>
-__device__ __forceinline__ void fe_sweep_fetch(const FeSweepThetas<KP>& T, const double* __restrict__ tm, int64_t j, double (&t)[KP]) {
+__device__ __forceinline__ void fe_sweep_fetch(const SweepThetas<KP>& T, const double* __restrict__ tm, int64_t j, double (&t)[KP]) {
   if (SLOT_MAJOR) {
 #pragma unroll
     for (int k = 0; k < KP; ++k) t[k] = tm[j * KP + k];
@@ -62,7 +36,7 @@ __device__ __forceinline__ void fe_sweep_fetch(const FeSweepThetas<KP>& T, const
 
 template <int KP, bool SLOT_MAJOR>
 __global__ __launch_bounds__(256) void fe_sweep_score_kernel(int64_t n, const int64_t* __restrict__ row_nnz_ptr, const int64_t* __restrict__ col_global,
-                                                             const float* __restrict__ val, const float* __restrict__ offset, FeSweepThetas<KP> T,
+                                                             const float* __restrict__ val, const float* __restrict__ offset, SweepThetas<KP> T,
                                                              const double* __restrict__ tm, int64_t D, int ic, int kn, float* __restrict__ score,
                                                              float* __restrict__ per_coord) {
   constexpr int U = KP <= 2 ? 4 : 2;      // non-zeros in flight
@@ -115,12 +89,12 @@ __global__ __launch_bounds__(256) void fe_sweep_score_kernel(int64_t n, const in
 template <int KP>
 static hipError_t fe_sweep_pass(int64_t n, const int64_t* rp, const int64_t* col, const float* val, const float* offset, const double* const* thetas,
                                 int kn, int64_t D, int ic, double* tm, float* score, float* per_coord, hipStream_t s) {
-  FeSweepThetas<KP> T;
+  SweepThetas<KP> T;
   for (int k = 0; k < KP; ++k) T.p[k] = thetas[k < kn ? k : 0];
   const unsigned blocks = (unsigned)((n + 255) / 256);
   if (tm) {
     const int64_t P = D + ic;
-    hipLaunchKernelGGL((fe_sweep_transpose_kernel<KP>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, T, P, tm);
+    hipLaunchKernelGGL((sweep_transpose_kernel<KP>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, T, P, tm);
     hipLaunchKernelGGL((fe_sweep_score_kernel<KP, true>), dim3(blocks), dim3(256), 0, s, n, rp, col, val, offset, T, (const double*)tm, D, ic, kn, score,
                        per_coord);
   } else {
@@ -130,8 +104,6 @@ static hipError_t fe_sweep_pass(int64_t n, const int64_t* rp, const int64_t* col
   return hipGetLastError();
 }
 
-static int fe_sweep_width(int k) { return k <= 1 ? 1 : (k <= 2 ? 2 : (k <= 4 ? 4 : 8)); }
-
 }  // namespace gdmix
 
 using namespace gdmix;
@@ -140,7 +112,7 @@ extern "C" {
 
 GDMIX_API size_t gdmix_fe_score_models_workspace_bytes(int64_t num_features, int K) {
   if (num_features < 0 || K < 1) return 0;
-  return (size_t)(num_features + 1) * (size_t)fe_sweep_width(K < FE_SWEEP_MAX_KP ? K : FE_SWEEP_MAX_KP) * 8;
+  return sweep_workspace_bytes(num_features + 1, K);
 }
 
 GDMIX_API int gdmix_fe_score_models(gdmix_re_ctx* ctx, int64_t n, const int64_t* row_nnz_ptr, const int64_t* col_global, const float* val,
@@ -163,12 +135,12 @@ GDMIX_API int gdmix_fe_score_models(gdmix_re_ctx* ctx, int64_t n, const int64_t*
   HIP_TRY(hipSetDevice(ctx->impl.device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* tm = static_cast<double*>(workspace);
-  for (int first = 0; first < K; first += FE_SWEEP_MAX_KP) {
-    const int kn = K - first < FE_SWEEP_MAX_KP ? K - first : FE_SWEEP_MAX_KP;
+  for (int first = 0; first < K; first += SWEEP_MAX_KP) {
+    const int kn = K - first < SWEEP_MAX_KP ? K - first : SWEEP_MAX_KP;
     float* sc = score + (int64_t)first * n;
     float* pc = per_coord ? per_coord + (int64_t)first * n : nullptr;
     hipError_t rc;
-    switch (fe_sweep_width(kn)) {
+    switch (sweep_width(kn)) {
       case 1: rc = fe_sweep_pass<1>(n, row_nnz_ptr, col_global, val, offset, thetas + first, kn, num_features, ic, tm, sc, pc, s); break;
       case 2: rc = fe_sweep_pass<2>(n, row_nnz_ptr, col_global, val, offset, thetas + first, kn, num_features, ic, tm, sc, pc, s); break;
       case 4: rc = fe_sweep_pass<4>(n, row_nnz_ptr, col_global, val, offset, thetas + first, kn, num_features, ic, tm, sc, pc, s); break;

@@ -32,15 +32,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t _rc = (expr);                                                                 \
-    if (_rc != hipSuccess) {                                                                 \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_rc), __FILE__, __LINE__); \
-      return GDMIX_RE_EHIP;                                                                  \
-    }                                                                                        \
-  } while (0)
-
 // Size classes in routing order (see re_internal.hpp). A 64-thread workgroup may use up to 64 KiB of LDS
 // here; larger blocks go to the workgroup-per-entity kernel.
 struct ClassDesc { int kind; int lds; const char* name; int ncap, zcap; };   // quad: lds = LDS of a whole wave (4 rows)
@@ -132,15 +123,6 @@ __global__ void class_base_kernel(int32_t* cc, int tall_adapt_limit, int tall_ad
     int run = 0;
     for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c) { cc[GDMIX_RE_NUM_CLASSES + c] = run; run += cc[c]; cc[2 * GDMIX_RE_NUM_CLASSES + c] = 0; }
   }
-}
-
-static BatchDev make_batch_dev(const gdmix_re_packed* b) {
-  BatchDev B;
-  B.ent_row_ptr = b->ent_row_ptr; B.ent_nnz_ptr = b->ent_nnz_ptr; B.ent_feat_ptr = b->ent_feat_ptr;
-  B.row_ptr = b->row_ptr; B.csr_col = b->csr_col; B.csr_val = b->csr_val;
-  B.col_ptr = b->col_ptr; B.csc_row = b->csc_row; B.csc_val = b->csc_val;
-  B.y = b->y; B.offset = b->offset; B.weight = b->weight; B.order = b->order;
-  return B;
 }
 
 __global__ __launch_bounds__(WAVE) void publish_kernel(const uint32_t* __restrict__ src, int words, uint32_t* box_data, uint32_t* box_flag, uint32_t seq) {
@@ -851,7 +833,7 @@ GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
   P.regularize_bias = opts->regularize_bias; P.has_intercept = ic; P.m = opts->m; P.max_iter = opts->max_iter;
   P.maxfun = opts->maxfun; P.maxls = opts->maxls; P.variance_mode = opts->variance_mode;
   P.sum_loss = opts->sum_loss ? 1 : 0; P.linear = opts->linear ? 1 : 0;
-  BatchDev B = make_batch_dev(b);
+  BatchDev B = batch_dev(b);
   OutDev O{out->theta, out->theta_thr, out->variance, out->fval, out->gnorm, out->nit, out->nfev, out->status};
 
   const bool timing = ctx->impl.timing != 0;
@@ -1062,7 +1044,7 @@ GDMIX_API int gdmix_re_variance_full(gdmix_re_ctx* ctx, const gdmix_re_packed* b
   P.regularize_bias = opts->regularize_bias; P.has_intercept = opts->has_intercept ? 1 : 0; P.m = opts->m; P.max_iter = opts->max_iter;
   P.maxfun = opts->maxfun; P.maxls = opts->maxls; P.variance_mode = GDMIX_RE_VAR_FULL;
   P.sum_loss = 0; P.linear = opts->linear ? 1 : 0;
-  return run_variance_full(ctx, b, make_batch_dev(b), P, theta, variance, static_cast<hipStream_t>(stream));
+  return run_variance_full(ctx, b, batch_dev(b), P, theta, variance, static_cast<hipStream_t>(stream));
 }
 
 GDMIX_API int gdmix_re_score(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int has_intercept, const double* theta,
@@ -1071,7 +1053,7 @@ GDMIX_API int gdmix_re_score(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int ha
   if (!theta && !has_model) { set_error("theta is NULL"); return GDMIX_RE_EINVAL; }
   HIP_TRY(hipSetDevice(ctx->impl.device));
   HIP_TRY(join_unique(&ctx->impl, static_cast<hipStream_t>(stream)));
-  BatchDev B = make_batch_dev(b);
+  BatchDev B = batch_dev(b);
   HIP_TRY(launch_score(B, b->E, b->N, has_intercept ? 1 : 0, theta, has_model, logit, logit_per_coord,
                        static_cast<hipStream_t>(stream)));
   return GDMIX_RE_OK;

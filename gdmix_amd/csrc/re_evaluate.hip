@@ -31,15 +31,6 @@
 
 namespace gdmix {
 
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t _rc = (expr);                                                                 \
-    if (_rc != hipSuccess) {                                                                 \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_rc), __FILE__, __LINE__); \
-      return GDMIX_RE_EHIP;                                                                  \
-    }                                                                                        \
-  } while (0)
-
 constexpr uint32_t KEY_NAN = 0xFFFFFFFFu;   // the key of no score (it is the image of a NaN): sorts behind +inf, counted apart
 constexpr int RANK_THREADS = 256, RANK_ITEMS = 16, RANK_TILE = RANK_THREADS * RANK_ITEMS;
 constexpr int SSE_RUN = 2048;               // terms a lane adds in a row,

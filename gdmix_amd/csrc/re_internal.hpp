@@ -133,6 +133,14 @@ struct BatchDev {
   const float* weight;
   const int32_t* order;
 };
+inline BatchDev batch_dev(const gdmix_re_packed* b) {
+  BatchDev B;
+  B.ent_row_ptr = b->ent_row_ptr; B.ent_nnz_ptr = b->ent_nnz_ptr; B.ent_feat_ptr = b->ent_feat_ptr;
+  B.row_ptr = b->row_ptr; B.csr_col = b->csr_col; B.csr_val = b->csr_val;
+  B.col_ptr = b->col_ptr; B.csc_row = b->csc_row; B.csc_val = b->csc_val;
+  B.y = b->y; B.offset = b->offset; B.weight = b->weight; B.order = b->order;
+  return B;
+}
 
 struct OutDev {
   double* theta;
@@ -336,6 +344,16 @@ hipError_t launch_partition_ids(const int64_t* ids, int64_t count, int32_t num_p
                                 hipStream_t s);
 
 void set_error(const char* fmt, ...);
+
+// a HIP call inside a function of the C ABI: on failure the error text is set and the function returns GDMIX_RE_EHIP
+#define HIP_TRY(expr)                                                                        \
+  do {                                                                                       \
+    hipError_t _rc = (expr);                                                                 \
+    if (_rc != hipSuccess) {                                                                 \
+      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_rc), __FILE__, __LINE__); \
+      return GDMIX_RE_EHIP;                                                                  \
+    }                                                                                        \
+  } while (0)
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE property of a kernel: one flag per call site would leave the
 // second device of a process at the 64 KB default. One of these per call site (static), a bit per device.

@@ -761,15 +761,6 @@ static PackLayout pack_layout(int64_t E, int64_t N, int64_t Z) {
 
 size_t pack_workspace_bytes(int64_t E, int64_t N, int64_t Z) { return pack_layout(E, N, Z).total; }
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _rc = (expr);                                                            \
-    if (_rc != hipSuccess) {                                                            \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_rc), __FILE__, __LINE__); \
-      return GDMIX_RE_EHIP;                                                             \
-    }                                                                                   \
-  } while (0)
-
 static bool debug_sync() {
   static int v = -1;
   if (v < 0) { const char* e = getenv("GDMIX_RE_DEBUG_SYNC"); v = (e && e[0] == '1') ? 1 : 0; }

@@ -24,15 +24,6 @@
 
 namespace gdmix {
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _rc = (expr);                                                            \
-    if (_rc != hipSuccess) {                                                            \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_rc), __FILE__, __LINE__); \
-      return GDMIX_RE_EHIP;                                                             \
-    }                                                                                   \
-  } while (0)
-
 constexpr int BIG_CH = 1024;               // entries per chunk: the unit of work of every per-entry pass here (4 096 until the end of round 4: a share of a
                                            // strongly scaled job has ~1 200 chunks of that size, one wavefront each for 120 us of big_scatter_kernel; 1 024: per-user share
                                            // pack 0.58 -> 0.51 ms, whole populations unchanged; 512 is worse again: tools/r04_bigch.sh)

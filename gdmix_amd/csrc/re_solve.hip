@@ -8,6 +8,7 @@
 //                                          L-BFGS state lives in a per-workgroup global scratch slot
 //   re_score_kernel                        logits X~theta + offset, one thread per sample
 #include "re_internal.hpp"
+#include "re_search.hpp"
 #include "re_solve_team.hpp"
 
 namespace gdmix {
@@ -922,36 +923,9 @@ hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams&
 // scoring: logits of every sample of the batch  (job_consumers.py:138-152, binary_logistic_regression.py:241-262)
 // ---------------------------------------------------------------------------------------------------
 // One thread per sample over the whole batch, whatever the entity sizes are (a Zipf partition has entities of one
-// sample and of a million): a pure streaming pass, bound by HBM. The entity of a sample is found by bisection of
-// ent_row_ptr — the wavefront's first and last sample by a 64-way search of the whole wavefront, each lane then within
-// that range, which is a handful of entities or a single one. Adjacent lanes read adjacent rows, so the (value, column)
-// loads of a wavefront fall on consecutive cache lines; the coefficient gathers of an entity stay in L1/L2.
-
-// largest e in [lo, hi] with ptr[e] <= g (ptr[lo] <= g)
-__device__ __forceinline__ int64_t entity_of_sample(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t g) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (ptr[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// The same by a whole wavefront (uniform arguments, all lanes active): 64 probes per step instead of one, so a
-// million entities take four dependent loads instead of twenty.
-__device__ __forceinline__ int64_t wave_entity_of_sample(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t g, int lane) {
-  while (lo < hi) {
-    const int64_t step = (hi - lo + WAVE - 1) / WAVE;
-    const int64_t probe = lo + (int64_t)(lane + 1) * step;
-    const bool le = ptr[probe < hi ? probe : hi] <= g;     // non-decreasing in the lane index
-    const int c = __popcll(__ballot(le));
-    const int64_t below = lo + (int64_t)c * step;           // last probe that is <= g (lo itself when c == 0)
-    const int64_t above = lo + (int64_t)(c + 1) * step;     // first probe that is > g
-    const int64_t nhi = (c < WAVE && above <= hi) ? above - 1 : hi;
-    lo = below < hi ? below : hi;
-    hi = (c == WAVE) ? lo : nhi;
-  }
-  return lo;
-}
+// sample and of a million): a pure streaming pass, bound by HBM. The entity of a sample is found by the searches of
+// re_search.hpp. Adjacent lanes read adjacent rows, so the (value, column) loads of a wavefront fall on consecutive
+// cache lines; the coefficient gathers of an entity stay in L1/L2.
 
 __global__ __launch_bounds__(256) void re_score_kernel(BatchDev B, int64_t E, int64_t N, int ic, const double* __restrict__ theta,
                                                        const uint8_t* __restrict__ has_model,

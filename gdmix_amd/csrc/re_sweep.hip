@@ -5,12 +5,12 @@
 //   join_entity_kernel    one thread per entity of the evaluation batch: has_model, and the intercept's place in the training batch's
 //                         coefficient array.
 //   join_feature_kernel   one thread per coefficient slot (feature) of the evaluation batch: its entity by the wavefront-wide bisection of
-//                         ent_feat_ptr re_score_kernel uses for samples (entities have 1 .. 65 k features: dealt by feature, not by
-//                         entity), then a bisection of the same entity's ascending feature list in the training batch. Reads 4 B and
+//                         ent_feat_ptr (re_search.hpp) re_score_kernel uses for samples (entities have 1 .. 65 k features: dealt by
+//                         feature, not by entity), then a bisection of the same entity's ascending feature list in the training batch. Reads 4 B and
 //                         writes 8 B per slot, plus log2(d_train) dependent 4 B probes into one entity's list (cached: neighbouring lanes
 //                         probe the same list).
-//   sweep_transpose_kernel the KP coefficient arrays of a pass -> one slot-major array [P_train][KP] (only when the caller gave a
-//                         workspace: the K coefficients of a slot then are one contiguous KP * 8-byte read instead of KP distant lines).
+//   sweep_transpose_kernel (sweep_common.hpp, shared with fe_sweep.hip) the KP coefficient arrays of a pass -> one slot-major array
+//                         [P_train][KP] (only when the caller gave a workspace: the K coefficients of a slot then are one contiguous KP * 8-byte read instead of KP distant lines).
 //   sweep_score_kernel    one thread per sample, the entity search of re_score_kernel; (value, column, coefficient place) of a non-zero are
 //                         loaded once and feed KP accumulators, KP in {1, 2, 4, 8} models per pass (more models: more passes). Row k of
 //                         the output is bit for bit what re_score_kernel writes for the mapped coefficients of model k: the same
@@ -19,54 +19,10 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "re_internal.hpp"
+#include "re_search.hpp"
+#include "sweep_common.hpp"
 
 namespace gdmix {
-
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t _rc = (expr);                                                                 \
-    if (_rc != hipSuccess) {                                                                 \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_rc), __FILE__, __LINE__); \
-      return GDMIX_RE_EHIP;                                                                  \
-    }                                                                                        \
-  } while (0)
-
-constexpr int SWEEP_WAVE = 64;
-constexpr int SWEEP_MAX_KP = GDMIX_RE_SWEEP_MODELS_PER_PASS;   // models one pass carries (accumulators and gathers in flight: registers)
-
-// largest e in [lo, hi] with ptr[e] <= g (ptr[lo] <= g) — the two searches of re_score_kernel (re_solve.hip), restated: that unit
-// keeps them to itself
-__device__ __forceinline__ int64_t sweep_owner(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t g) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (ptr[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// the same by a whole wavefront (uniform arguments, all lanes active): 64 probes per step
-__device__ __forceinline__ int64_t sweep_wave_owner(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t g, int lane) {
-  while (lo < hi) {
-    const int64_t step = (hi - lo + SWEEP_WAVE - 1) / SWEEP_WAVE;
-    const int64_t probe = lo + (int64_t)(lane + 1) * step;
-    const bool le = ptr[probe < hi ? probe : hi] <= g;     // non-decreasing in the lane index
-    const int c = __popcll(__ballot(le));
-    const int64_t below = lo + (int64_t)c * step;
-    const int64_t above = lo + (int64_t)(c + 1) * step;
-    const int64_t nhi = (c < SWEEP_WAVE && above <= hi) ? above - 1 : hi;
-    lo = below < hi ? below : hi;
-    hi = (c == SWEEP_WAVE) ? lo : nhi;
-  }
-  return lo;
-}
-// the entity of item g of a wavefront's 64 consecutive items [gf, gf + 64) under the offsets `ptr` ([E + 1], items in all: M)
-__device__ __forceinline__ int64_t sweep_entity_of(const int64_t* __restrict__ ptr, int64_t E, int64_t M, int64_t gf, int64_t g, int lane) {
-  const int64_t gl = (gf + SWEEP_WAVE - 1 < M) ? gf + SWEEP_WAVE - 1 : M - 1;
-  const int64_t e_lo = sweep_wave_owner(ptr, 0, E - 1, gf, lane);
-  const int64_t w_hi = (e_lo + SWEEP_WAVE < E) ? e_lo + SWEEP_WAVE : E - 1;   // 64 items span at most 64 non-empty entities
-  const int64_t e_hi = sweep_wave_owner(ptr, e_lo, (ptr[w_hi] > gl) ? w_hi : E - 1, gl, lane);
-  return sweep_owner(ptr, e_lo, e_hi, g < M ? g : gl);
-}
 
 // ---- join -----------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void join_entity_kernel(const int64_t* __restrict__ eval_feat_ptr, int64_t E_eval, const int64_t* __restrict__ train_feat_ptr,
@@ -84,11 +40,11 @@ __global__ __launch_bounds__(256) void join_feature_kernel(const int64_t* __rest
                                                            int64_t D_eval, const int64_t* __restrict__ train_feat_ptr,
                                                            const int32_t* __restrict__ train_unique, int64_t E_train, int ic,
                                                            const int32_t* __restrict__ train_entity, int64_t* __restrict__ coef_pos) {
-  const int lane = threadIdx.x & (SWEEP_WAVE - 1);
+  const int lane = threadIdx.x & (WAVE - 1);
   const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t ff = f - lane;
   if (ff >= D_eval) return;
-  const int64_t e = sweep_entity_of(eval_feat_ptr, E_eval, D_eval, ff, f, lane);
+  const int64_t e = wave_entity_of(eval_feat_ptr, E_eval, D_eval, ff, f, lane);
   if (f >= D_eval) return;
   const int64_t te = train_entity[e];
   int64_t pos = -1;
@@ -106,21 +62,6 @@ __global__ __launch_bounds__(256) void join_feature_kernel(const int64_t* __rest
 }
 
 // ---- score ----------------------------------------------------------------------------------------------------------------------------
-template <int KP>
-struct SweepThetas { const double* p[KP]; };
-
-// tm[s * KP + k] = theta_k[s]: coalesced reads of KP arrays, KP * 8 contiguous bytes written per slot
-template <int KP>
-__global__ __launch_bounds__(256) void sweep_transpose_kernel(SweepThetas<KP> T, int64_t P, double* __restrict__ tm) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= P) return;
-  double v[KP];
-#pragma unroll
-  for (int k = 0; k < KP; ++k) v[k] = T.p[k][s];
-#pragma unroll
-  for (int k = 0; k < KP; ++k) tm[s * KP + k] = v[k];
-}
-
 // the KP coefficients at place `pos` of the training batch's array (pos < 0: the entity has no coefficient there: +0.0, as the mapped array has)
 template <int KP, bool SLOT_MAJOR>
 __device__ __forceinline__ void sweep_fetch(const SweepThetas<KP>& T, const double* __restrict__ tm, int64_t pos, double (&t)[KP]) {
@@ -140,11 +81,11 @@ template <int KP, bool SLOT_MAJOR>
 __global__ __launch_bounds__(256) void sweep_score_kernel(BatchDev B, int64_t E, int64_t N, int ic, SweepThetas<KP> T, const double* __restrict__ tm,
                                                           const int64_t* __restrict__ coef_pos, const uint8_t* __restrict__ has_model, int kn,
                                                           float* __restrict__ logit, float* __restrict__ per_coord) {
-  const int lane = threadIdx.x & (SWEEP_WAVE - 1);
+  const int lane = threadIdx.x & (WAVE - 1);
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t gf = g - lane;
   if (gf >= N) return;
-  const int64_t e = sweep_entity_of(B.ent_row_ptr, E, N, gf, g, lane);
+  const int64_t e = wave_entity_of(B.ent_row_ptr, E, N, gf, g, lane);
   if (g >= N) return;
   const int64_t r0 = B.ent_row_ptr[e], z0 = B.ent_nnz_ptr[e];
   const double off = (double)B.offset[g];
@@ -196,14 +137,6 @@ __global__ __launch_bounds__(256) void sweep_score_kernel(BatchDev B, int64_t E,
       if (per_coord) per_coord[(int64_t)k * N + g] = (float)(z[k] - off);
     }
   }
-}
-
-static BatchDev sweep_batch_dev(const gdmix_re_packed* b) {
-  BatchDev B;
-  B.ent_row_ptr = b->ent_row_ptr; B.ent_nnz_ptr = b->ent_nnz_ptr; B.ent_feat_ptr = b->ent_feat_ptr; B.row_ptr = b->row_ptr;
-  B.csr_col = b->csr_col; B.csr_val = b->csr_val; B.col_ptr = b->col_ptr; B.csc_row = b->csc_row; B.csc_val = b->csc_val;
-  B.y = b->y; B.offset = b->offset; B.weight = b->weight; B.order = b->order;
-  return B;
 }
 
 // one pass: models [first, first + kn) of `thetas`, kn <= KP (the unused places of a pass read model `first` again and store nothing)
@@ -258,8 +191,7 @@ GDMIX_API int gdmix_re_join_features(gdmix_re_ctx* ctx, const gdmix_re_packed* e
 
 GDMIX_API size_t gdmix_re_score_models_workspace_bytes(int64_t P_train, int K) {
   if (P_train < 0 || K < 1) return 0;
-  const int kp = K < SWEEP_MAX_KP ? K : SWEEP_MAX_KP;
-  return (size_t)P_train * (size_t)(kp <= 1 ? 1 : (kp <= 2 ? 2 : (kp <= 4 ? 4 : 8))) * 8;
+  return sweep_workspace_bytes(P_train, K);
 }
 
 GDMIX_API int gdmix_re_score_models(gdmix_re_ctx* ctx, const gdmix_re_packed* eval, int has_intercept, const double* const* thetas, int K,
@@ -279,7 +211,7 @@ GDMIX_API int gdmix_re_score_models(gdmix_re_ctx* ctx, const gdmix_re_packed* ev
   HIP_TRY(hipSetDevice(ctx->impl.device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(join_unique(&ctx->impl, s));
-  const BatchDev B = sweep_batch_dev(eval);
+  const BatchDev B = batch_dev(eval);
   const int ic = has_intercept ? 1 : 0;
   double* tm = (workspace && P_train > 0) ? static_cast<double*>(workspace) : nullptr;
   const int64_t N = eval->N;
@@ -288,10 +220,12 @@ GDMIX_API int gdmix_re_score_models(gdmix_re_ctx* ctx, const gdmix_re_packed* ev
     float* lo = logit + (int64_t)first * N;
     float* pc = logit_per_coord ? logit_per_coord + (int64_t)first * N : nullptr;
     hipError_t rc;
-    if (kn == 1) rc = sweep_pass<1>(B, eval->E, N, ic, thetas + first, kn, P_train, tm, coef_pos, has_model, lo, pc, s);
-    else if (kn == 2) rc = sweep_pass<2>(B, eval->E, N, ic, thetas + first, kn, P_train, tm, coef_pos, has_model, lo, pc, s);
-    else if (kn <= 4) rc = sweep_pass<4>(B, eval->E, N, ic, thetas + first, kn, P_train, tm, coef_pos, has_model, lo, pc, s);
-    else rc = sweep_pass<8>(B, eval->E, N, ic, thetas + first, kn, P_train, tm, coef_pos, has_model, lo, pc, s);
+    switch (sweep_width(kn)) {
+      case 1: rc = sweep_pass<1>(B, eval->E, N, ic, thetas + first, kn, P_train, tm, coef_pos, has_model, lo, pc, s); break;
+      case 2: rc = sweep_pass<2>(B, eval->E, N, ic, thetas + first, kn, P_train, tm, coef_pos, has_model, lo, pc, s); break;
+      case 4: rc = sweep_pass<4>(B, eval->E, N, ic, thetas + first, kn, P_train, tm, coef_pos, has_model, lo, pc, s); break;
+      default: rc = sweep_pass<8>(B, eval->E, N, ic, thetas + first, kn, P_train, tm, coef_pos, has_model, lo, pc, s); break;
+    }
     HIP_TRY(rc);
   }
   return GDMIX_RE_OK;

@@ -9,15 +9,6 @@
 
 namespace gdmix {
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _rc = (expr);                                                            \
-    if (_rc != hipSuccess) {                                                            \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_rc), __FILE__, __LINE__); \
-      return GDMIX_RE_EHIP;                                                             \
-    }                                                                                   \
-  } while (0)
-
 constexpr int WIRE_CHUNK = 4096;   // counts per workgroup (256 threads x 16)
 
 template <typename T>

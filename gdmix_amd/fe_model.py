@@ -203,24 +203,15 @@ class FixedEffectLRModelLBFGS:
     def check_request(self, execution_context, action=constants.ACTION_TRAIN):
         """--metric_output_dir / --l2_reg_weights: everything they do not do is refused here, before a file is read, a process group
         is formed or a solver created (as sweep.validate does for the random effect). Inference ignores --l2_reg_weights."""
-        from .sweep import SweepError
+        from . import sweep
         mp = self.model_params
         grid = mp.l2_grid() if action == constants.ACTION_TRAIN else None
         if grid is None and not mp.metric_output_dir:
             return
-        if int(execution_context.get(constants.NUM_WORKERS) or 1) > 1:
-            flag = "--l2_reg_weights" if grid is not None else "--metric_output_dir"
-            raise SweepError(f"{flag} runs on one worker: the AUC of several workers cannot be combined from their counts")
-        if grid is None:
-            return
-        if not mp.validation_data_dir:
-            raise SweepError("--l2_reg_weights needs --validation_data_dir: only validation data can choose a weight")
-        if not mp.metric_output_dir:
-            raise SweepError("--l2_reg_weights needs --metric_output_dir: the sweep writes its metrics there")
-        prior = sorted(glob.glob(os.path.join(mp.output_model_dir, "*.avro"))) if mp.output_model_dir else []
-        if prior:
-            raise SweepError(f"--l2_reg_weights is a cold start, and {prior[0]} is a prior model the stage would warm-start from: "
-                             "warm-started sweeps are not implemented")
+        sweep.refuse_several_workers(execution_context, "--l2_reg_weights" if grid is not None else "--metric_output_dir")
+        if grid is not None:
+            sweep.refuse_blind_or_warm(mp, sorted(glob.glob(os.path.join(mp.output_model_dir, "*.avro"))) if mp.output_model_dir else [],
+                                       " the stage would warm-start from")
 
     # ---- the stage metric (--metric_output_dir) ---------------------------------------------------------------------
     def _metric_name(self):
@@ -240,12 +231,19 @@ class FixedEffectLRModelLBFGS:
         m, self._metrics = self._metrics, None
         return None if m is None else m.write_summary()
 
+    def _shard_arrays(self, data, fit=False):
+        """(row_nnz_ptr, col, val) of the shard. A model without a feature bag has none: Nones as upload / score take them, or with
+        `fit` the empty rows fit_* and shard_as_batch take."""
+        if self.feature_bag_name is not None:
+            return data["row_nnz_ptr"], data["col"], data["val"]
+        return (np.zeros(data["n"] + 1, np.int64), [], []) if fit else (None, None, None)
+
     def _device_shard(self, data):
         """The shard's sample-major arrays (and labels) in HBM, uploaded once per shard read."""
         if "_dev" not in data:
             bag = self.feature_bag_name is not None
-            data["_dev"] = self._solver().upload(data["row_nnz_ptr"] if bag else None, data["col"] if bag else None, data["val"] if bag else None,
-                                                 data["offset"], self.num_features if bag else 0, label=data["y"] if data["has_label"] else None)
+            data["_dev"] = self._solver().upload(*self._shard_arrays(data), data["offset"], self.num_features if bag else 0,
+                                                 label=data["y"] if data["has_label"] else None)
         return data["_dev"]
 
     # ---- the sweep (--l2_reg_weights) ----------------------------------------------------------------------------------
@@ -265,7 +263,6 @@ class FixedEffectLRModelLBFGS:
         fe = self._solver()
         bag = self.feature_bag_name is not None
         metric = self._metric_name()
-        out_dir = self.metric_output_dir
         K = len(grid)
         logger.info(f"sweeping l2_reg_weight over {list(grid)} by validation {metric}; --l2_reg_weight={self.l2_reg_weight} is ignored")
 
@@ -284,18 +281,11 @@ class FixedEffectLRModelLBFGS:
                     del per
             else:
                 blocks = [fe.new_evaluator().finish() for _ in grid]
-            values = [b[metric] for b in blocks]
-            for k, (w, b) in enumerate(zip(grid, blocks)):
-                sweep.write_model_summary(out_dir, k, w, metric, b)
-            best = sweep.select_best(metric, values)      # (every metric undefined: the stage fails here, the per-model summaries say why)
-            sweep.write_evals(out_dir, metric, grid, values, best)
-            logger.info(f"sweep: validation {metric} {dict(zip(grid, values))}; best l2_reg_weight = {grid[best]} (index {best})")
-            return best
+            return sweep.conclude(self.metric_output_dir, metric, grid, blocks)
 
         theta, info, best = fe.fit_sweep(
-            data["row_nnz_ptr"] if bag else np.zeros(data["n"] + 1, np.int64), data["col"] if bag else [], data["val"] if bag else [],
-            data["y"], self.num_features, l2_grid=grid, select=select, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
-            has_intercept=self.has_intercept, regularize_bias=self.is_regularize_bias, model_type=self.model_type, max_iter=self.max_iteration,
+            *self._shard_arrays(data, fit=True), data["y"], self.num_features, l2_grid=grid, select=select, offset=data["offset"],
+            weight=data["weight"] if data["has_weight"] else None, has_intercept=self.has_intercept, regularize_bias=self.is_regularize_bias, model_type=self.model_type, max_iter=self.max_iteration,
             m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
             variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold)
         self.l2_reg_weight = self.model_params.l2_reg_weight = float(grid[best])
@@ -327,21 +317,17 @@ class FixedEffectLRModelLBFGS:
             elif prev_model is not None:
                 logger.info(f"Initial model size is {len(prev_model)}, expected {expected}, use all zeros instead.")
             theta, info = self._solver().fit_stepping(
-                data["row_nnz_ptr"] if bag else np.zeros(data["n"] + 1, np.int64), data["col"] if bag else [], data["val"] if bag else [],
-                data["y"], D, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
+                *self._shard_arrays(data, fit=True), data["y"], D, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
                 has_intercept=self.has_intercept, l2=self.l2_reg_weight, regularize_bias=self.is_regularize_bias,
                 model_type=self.model_type, theta0=self._strip_dummy(x0) if not bag else x0, max_iter=self.max_iteration,
                 m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
                 variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold)
         self.variances = info.pop("variances", None)
-        if not bag:
-            theta = np.concatenate([[0.0], theta])   # the dummy weight of an intercept-only model (add_dummy_weight)
-            if self.variances is not None:
-                self.variances = np.concatenate([[0.0], self.variances])
+        if not bag and self.variances is not None:
+            self.variances = np.concatenate([[0.0], self.variances])   # next to the dummy weight of an intercept-only model
         self.last_training_info = info
         logger.info(f"f_min: {info['fval']} num of funcalls: {info['nfev']} status: {info['status']}")
-        theta = np.where(np.abs(theta) <= self.sparsity_threshold, 0.0, theta)   # threshold_coefficients (:648-649)
-        self.model_coefficients = theta
+        self.model_coefficients = theta = self._stage_coefficients(theta)
         # the reference's variance computation rides on the scoring pass over the training data, which therefore runs (and writes
         # its scores) whenever a variance mode is set (:650-661)
         if not self.disable_fixed_effect_scoring_after_training or self.fixed_effect_variance_mode is not None:
@@ -381,11 +367,10 @@ class FixedEffectLRModelLBFGS:
         else:
             fe = self._solver()
             if hasattr(fe, "score"):      # the device path: one pass over the sample-major arrays, no pack
-                _, per_coord = fe.score(data["row_nnz_ptr"] if bag else None, data["col"] if bag else None, data["val"] if bag else None,
-                                        data["offset"], theta if bag else theta[1:], self.num_features if bag else 0, self.has_intercept)
+                _, per_coord = fe.score(*self._shard_arrays(data), data["offset"], theta if bag else theta[1:], self.num_features if bag else 0,
+                                        self.has_intercept)
             else:
-                batch, dummy = shard_as_batch(data["row_nnz_ptr"] if bag else np.zeros(n + 1, np.int64), data["col"] if bag else [],
-                                              data["val"] if bag else [], np.zeros(n, np.float32), data["offset"], None, self.has_intercept,
+                batch, dummy = shard_as_batch(*self._shard_arrays(data, fit=True), np.zeros(n, np.float32), data["offset"], None, self.has_intercept,
                                               dummy=not bag)
                 packed = fe.solver.pack(batch, has_intercept=self.has_intercept)
                 uniq = packed.unique_global().cpu().numpy()

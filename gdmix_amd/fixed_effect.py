@@ -138,30 +138,20 @@ class FixedEffectDeviceSolver:
         return metrics.DeviceEvaluator(self.solver)
 
     def models_per_chunk(self, K, P, n_eval):
-        """How many of K models are scored at once: all of them if K x (coefficients + score and per-coordinate rows) fits into half
-        of the free device memory (GDMIX_SWEEP_CHUNK sets it: tests) — sweep._models_per_chunk with the fixed effect's two rows."""
-        forced = int(os.environ.get("GDMIX_SWEEP_CHUNK", "0"))
-        if forced > 0:
-            return min(K, forced)
-        free, _ = self.solver.torch.cuda.mem_get_info(self.solver.device)
-        return int(max(1, min(K, (free // 2) // (8 * P + 8 * n_eval + 1))))
+        """How many of K models are scored at once (sweep.models_per_chunk): a model is its coefficients and two rows of the output,
+        score and per-coordinate score."""
+        from .sweep import models_per_chunk
+        return models_per_chunk(self.solver.torch, self.solver.device, K, 8 * P + 8 * n_eval + 1)
 
     def fit(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
             regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12, dummy=None):
         """-> (theta [num_features + has_intercept], intercept last; info dict with f, nit, nfev, status, gnorm)."""
-        if model_type not in (LOGISTIC_REGRESSION, LINEAR_REGRESSION):
-            raise ValueError(f"unknown model type {model_type!r}")
-        batch, dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, has_intercept,
-                                      binary_labels=(model_type == LOGISTIC_REGRESSION), dummy=dummy)
+        opts = fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance)
+        batch, dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, has_intercept, binary_labels=not opts.linear, dummy=dummy)
         if not dummy and batch.col_global.size and (batch.col_global.min() < 0 or batch.col_global.max() >= num_features):
             raise ValueError(f"feature index outside [0, {num_features})")
         packed = self.solver.pack(batch, has_intercept=has_intercept)
         uniq = packed.unique_global().cpu().numpy()
-        opts = SolverOptions(l2=l2, regularize_bias=bool(regularize_bias) and bool(has_intercept), has_intercept=has_intercept, m=m,
-                             max_iter=max_iter, ftol=tolerance, threshold=0.0, sum_loss=True,
-                             linear=(model_type == LINEAR_REGRESSION))
-        if not has_intercept:
-            opts.regularize_bias = False
         t0 = None if theta0 is None else to_local(theta0, uniq, num_features, has_intercept, dummy)
         res = self.solver.solve(packed, opts, theta0=t0).to_host()
         theta = to_global(res["theta"], uniq, num_features, has_intercept, dummy)
@@ -169,6 +159,51 @@ class FixedEffectDeviceSolver:
         if not 0 <= int(info["status"]) <= 4:
             raise RuntimeError(f"the fixed-effect solve did not finish (device status {int(info['status'])}: 9 = a device barrier timed out)")
         return theta, info
+
+    def fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
+                     regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
+                     group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0):
+        """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
+        worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
+        model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
+        hold no non-zero, so that its all-reduce buffer has the same num_features + 2 entries as everyone else's."""
+        opts = fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance)
+        fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode)
+        theta, info = fit.stage_result(*fit.run(), l2, threshold)
+        if return_problem:
+            return theta, info, fit.prob
+        fit.prob.close()
+        return theta, info
+
+    def fit_sweep(self, row_nnz_ptr, col_global, val, y, num_features, l2_grid, select, offset=None, weight=None, has_intercept=True,
+                  regularize_bias=True, model_type=LOGISTIC_REGRESSION, max_iter=100, m=10, tolerance=1e-12, dummy=None, variance_mode=None,
+                  threshold=0.0):
+        """One worker's fit for every weight of l2_grid on ONE problem: the shard is packed and gdmix_fe_create runs once; per weight, in the
+        order given, gdmix_fe_restart (cold: zeros) + the same loop and status check as fit_stepping — by the restart's contract the bits
+        of a fresh fit_stepping at that weight. select(thetas) — the K coefficient vectors as fit_stepping would have returned them — names
+        the winner; -> (theta, info, best) of the winner as fit_stepping returns them, its variances (at its weight, for it alone) included."""
+        import dataclasses
+        if _world_size(None) > 1:
+            raise ValueError("a sweep over l2_reg_weight runs on one worker")
+        opts = fit_options(has_intercept, float(l2_grid[0]), regularize_bias, model_type, max_iter, m, tolerance)
+        fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, None, None, dummy, variance_mode)
+        try:
+            fits = []
+            for w in l2_grid:
+                fit.prob.restart(dataclasses.replace(opts, l2=float(w)), None)
+                fits.append(fit.run())
+            best = int(select([fit.strip_dummy(th) for th, _ in fits]))
+            return fit.stage_result(*fits[best], l2_grid[best], threshold) + (best,)
+        finally:
+            fit.prob.close()
+
+
+def fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance):
+    """The solver's options of a fixed-effect fit: the objective is not divided by n, the model is stored unthresholded."""
+    if model_type not in (LOGISTIC_REGRESSION, LINEAR_REGRESSION):
+        raise ValueError(f"unknown model type {model_type!r}")
+    return SolverOptions(l2=l2, regularize_bias=bool(regularize_bias) and bool(has_intercept), has_intercept=has_intercept, m=m,
+                         max_iter=max_iter, ftol=tolerance, threshold=0.0, sum_loss=True, linear=(model_type == LINEAR_REGRESSION))
 
 
 class DeviceShard:
@@ -407,114 +442,71 @@ def run_stepping_loop(problem, all_reduce=None, max_evals=100000, lookahead=None
     raise RuntimeError(f"the fixed-effect L-BFGS loop did not stop within {max_evals} evaluations")
 
 
-def _stepping_setup(self, row_nnz_ptr, col_global, val, y, num_features, offset, weight, has_intercept, l2, regularize_bias, model_type, theta0,
-                    max_iter, m, tolerance, group, dummy, variance_mode):
-    """What a fit through include/gdmix_fe.h needs before its loop: the shard as a packed one-entity batch, the options, the problem
-    (gdmix_fe_create) and the all-reduce of this process group. -> (solver, batch, dummy, D, packed, opts, problem, all_reduce)."""
-    if model_type not in (LOGISTIC_REGRESSION, LINEAR_REGRESSION):
-        raise ValueError(f"unknown model type {model_type!r}")
-    batch, dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, has_intercept,
-                                  binary_labels=(model_type == LOGISTIC_REGRESSION), dummy=dummy)
-    D = 1 if dummy else int(num_features)   # the dummy zero feature of an intercept-only model occupies global index 0
-    if not dummy and batch.col_global.size and (batch.col_global.min() < 0 or batch.col_global.max() >= D):
-        raise ValueError(f"feature index outside [0, {D})")
-    # whether the variances can be computed is decided before any training (a job that trains for its whole budget and
-    # then dies on the variances loses the model)
-    if variance_mode is not None:
-        check_variance_request(str(variance_mode).upper(), D + (1 if has_intercept else 0), _world_size(group))
-    s = self.solver
-    packed = s.pack(batch, has_intercept=has_intercept)
-    opts = SolverOptions(l2=l2, regularize_bias=bool(regularize_bias) and bool(has_intercept), has_intercept=has_intercept, m=m,
-                         max_iter=max_iter, ftol=tolerance, threshold=0.0, sum_loss=True, linear=(model_type == LINEAR_REGRESSION))
-    ic = 1 if has_intercept else 0
-    t0 = None
-    if theta0 is not None:
-        full = np.zeros(D + ic)
-        th = np.asarray(theta0, np.float64)
-        if dummy:
-            full[D:] = th[-ic:] if ic else []
-        else:
-            full[:] = th
-        t0 = s.torch.from_numpy(full).to(s.device)
-    prob = _SteppingProblem(s, packed, D, opts, t0)
-    all_reduce = None
-    try:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-            if dist.get_backend(group) == "nccl":          # RCCL, in place on the device buffer, ordered on the stream
-                def all_reduce(t):
-                    dist.all_reduce(t, group=group)
-                all_reduce.device_ordered = True
-            else:                                          # e.g. gloo: staged through the host
-                def all_reduce(t):
-                    h = t.cpu()
-                    dist.all_reduce(h, group=group)
-                    t.copy_(h)
-    except ImportError:
-        pass
-    return s, batch, dummy, D, packed, opts, prob, all_reduce
+class _SteppingFit:
+    """What a fit through include/gdmix_fe.h needs around its loop: the shard as a packed one-entity batch, the problem (gdmix_fe_create)
+    and the all-reduce of this process group; then the loop, and the result as the stage takes it."""
 
-
-def _fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
-                  regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
-                  group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0):
-    """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
-    worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
-    model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
-    hold no non-zero, so that its all-reduce buffer has the same num_features + 2 entries as everyone else's."""
-    s, batch, dummy, D, packed, opts, prob, all_reduce = _stepping_setup(self, row_nnz_ptr, col_global, val, y, num_features, offset, weight, has_intercept, l2,
-                                                                         regularize_bias, model_type, theta0, max_iter, m, tolerance, group, dummy, variance_mode)
-    status = run_stepping_loop(prob, all_reduce)
-    theta, info = prob.result()
-    info["status"] = status
-    if variance_mode is not None:
-        # the variances of the thresholded model on the training data, as the reference's scoring pass after training computes
-        # them (fixed_effect_lr_lbfgs_model.py:648-661, 271-305, 451-463)
-        th = np.where(np.abs(theta) <= threshold, 0.0, theta)
-        info["variances"] = _variances(s, prob, batch, th, D, has_intercept, float(l2), bool(regularize_bias) and bool(has_intercept),
-                                       str(variance_mode).upper(), all_reduce, group, packed=packed, dummy=dummy)
-        if dummy:
-            info["variances"] = info["variances"][D:]
-    if dummy:
-        theta = theta[D:]
-    if return_problem:
-        return theta, info, prob
-    prob.close()
-    return theta, info
-
-
-def _fit_sweep(self, row_nnz_ptr, col_global, val, y, num_features, l2_grid, select, offset=None, weight=None, has_intercept=True,
-               regularize_bias=True, model_type=LOGISTIC_REGRESSION, max_iter=100, m=10, tolerance=1e-12, dummy=None, variance_mode=None,
-               threshold=0.0):
-    """One worker's fit for every weight of l2_grid on ONE problem: the shard is packed and gdmix_fe_create runs once; per weight, in the
-    order given, gdmix_fe_restart (cold: zeros) + the same loop and status check as fit_stepping — by the restart's contract the bits
-    of a fresh fit_stepping at that weight. select(thetas) — the K coefficient vectors as fit_stepping would have returned them — names
-    the winner; -> (theta, info, best) of the winner as fit_stepping returns them, its variances (at its weight, for it alone) included."""
-    import dataclasses
-    if _world_size(None) > 1:
-        raise ValueError("a sweep over l2_reg_weight runs on one worker")
-    s, batch, dummy, D, packed, opts, prob, all_reduce = _stepping_setup(self, row_nnz_ptr, col_global, val, y, num_features, offset, weight, has_intercept,
-                                                                         float(l2_grid[0]), regularize_bias, model_type, None, max_iter, m, tolerance, None,
-                                                                         dummy, variance_mode)
-    try:
-        fits = []
-        for w in l2_grid:
-            prob.restart(dataclasses.replace(opts, l2=float(w)), None)
-            status = run_stepping_loop(prob, None)
-            theta, info = prob.result()
-            info["status"] = status
-            fits.append((theta, info))
-        best = int(select([th[D:] if dummy else th for th, _ in fits]))
-        theta, info = fits[best]
+    def __init__(self, solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode):
+        ic = 1 if opts.has_intercept else 0
+        self.batch, self.dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, opts.has_intercept,
+                                                binary_labels=not opts.linear, dummy=dummy)
+        D = 1 if self.dummy else int(num_features)   # the dummy zero feature of an intercept-only model occupies global index 0
+        if not self.dummy and self.batch.col_global.size and (self.batch.col_global.min() < 0 or self.batch.col_global.max() >= D):
+            raise ValueError(f"feature index outside [0, {D})")
+        # whether the variances can be computed is decided before any training (a job that trains for its whole budget and
+        # then dies on the variances loses the model)
         if variance_mode is not None:
+            check_variance_request(str(variance_mode).upper(), D + ic, _world_size(group))
+        self.solver, self.opts, self.D, self.group, self.variance_mode = solver, opts, D, group, variance_mode
+        self.packed = solver.pack(self.batch, has_intercept=opts.has_intercept)
+        t0 = None
+        if theta0 is not None:
+            full = np.zeros(D + ic)
+            th = np.asarray(theta0, np.float64)
+            if self.dummy:
+                full[D:] = th[-ic:] if ic else []
+            else:
+                full[:] = th
+            t0 = solver.torch.from_numpy(full).to(solver.device)
+        self.prob = _SteppingProblem(solver, self.packed, D, opts, t0)
+        self.all_reduce = None
+        try:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+                if dist.get_backend(group) == "nccl":          # RCCL, in place on the device buffer, ordered on the stream
+                    def all_reduce(t):
+                        dist.all_reduce(t, group=group)
+                    all_reduce.device_ordered = True
+                else:                                          # e.g. gloo: staged through the host
+                    def all_reduce(t):
+                        h = t.cpu()
+                        dist.all_reduce(h, group=group)
+                        t.copy_(h)
+                self.all_reduce = all_reduce
+        except ImportError:
+            pass
+
+    def run(self):
+        """The loop on the problem as it stands -> (theta, info) in the problem's layout (the dummy feature still in front)."""
+        status = run_stepping_loop(self.prob, self.all_reduce)
+        theta, info = self.prob.result()
+        info["status"] = status
+        return theta, info
+
+    def strip_dummy(self, x):
+        return x[self.D:] if self.dummy else x
+
+    def stage_result(self, theta, info, l2, threshold):
+        """(theta, info) of run() as fit_stepping returns them: with a variance mode, the variances of the thresholded model on the
+        training data, as the reference's scoring pass after training computes them (fixed_effect_lr_lbfgs_model.py:648-661, 271-305,
+        451-463); the dummy entry stripped from both."""
+        if self.variance_mode is not None:
             th = np.where(np.abs(theta) <= threshold, 0.0, theta)
-            info["variances"] = _variances(s, prob, batch, th, D, has_intercept, float(l2_grid[best]), bool(regularize_bias) and bool(has_intercept),
-                                           str(variance_mode).upper(), None, None, packed=packed, dummy=dummy)
-            if dummy:
-                info["variances"] = info["variances"][D:]
-        return (theta[D:] if dummy else theta), info, best
-    finally:
-        prob.close()
+            o = self.opts
+            info["variances"] = self.strip_dummy(_variances(self.solver, self.prob, self.batch, th, self.D, o.has_intercept, float(l2), o.regularize_bias,
+                                                            str(self.variance_mode).upper(), self.all_reduce, self.group, packed=self.packed,
+                                                            dummy=self.dummy))
+        return self.strip_dummy(theta), info
 
 
 # FULL densifies a (D + 1) x (D + 1) Hessian, as the reference does (fixed_effect_lr_lbfgs_model.py:291, 457: no limit there but
@@ -525,7 +517,6 @@ def _fit_sweep(self, row_nnz_ptr, col_global, val, y, num_features, l2_grid, sel
 # P x P matrix (RCCL), and every worker factors the sum (gdmix_fe_variance_of_hessian) — replicated, as scipy is in the reference.
 FULL_VARIANCE_HOST_MAX = 4096
 FULL_VARIANCE_DEVICE_MAX = 16384
-FULL_VARIANCE_MAX_FEATURES = FULL_VARIANCE_HOST_MAX   # (the name round 2 used)
 
 
 def _world_size(group=None):
@@ -652,6 +643,3 @@ def _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2,
     unreg = D if (ic and not regularize_bias) else -1
     return solver.variance_of_hessian(Hg, P, l2, unreg).cpu().numpy()
 
-
-FixedEffectDeviceSolver.fit_stepping = _fit_stepping
-FixedEffectDeviceSolver.fit_sweep = _fit_sweep

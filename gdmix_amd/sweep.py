@@ -88,6 +88,18 @@ def write_evals(out_dir, metric, weights, values, best):
     return out
 
 
+def conclude(out_dir, metric, weights, blocks):
+    """What both sweeps do with the K finished accumulators (DeviceEvaluator.finish()'s dicts): the per-model summaries, the selection,
+    evals.json and the log line. -> the best index. (Every metric undefined: select_best raises, the summaries written before say why.)"""
+    values = [b[metric] for b in blocks]
+    for k, (w, b) in enumerate(zip(weights, blocks)):
+        write_model_summary(out_dir, k, w, metric, b)
+    best = select_best(metric, values)
+    write_evals(out_dir, metric, weights, values, best)
+    logger.info(f"sweep: validation {metric} {dict(zip(weights, values))}; best l2_reg_weight = {weights[best]} (index {best})")
+    return best
+
+
 # ---- the join, stated in numpy --------------------------------------------------------------------------------------------------------
 def train_entity_map(eval_ids, train_ids):
     """[E_eval] int32: the training batch's row of the same entity id, -1 if it has none; an id listed twice in the training batch
@@ -124,32 +136,39 @@ def join_features_host(eval_feat_ptr, eval_unique, train_feat_ptr, train_unique,
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------------
-def validate(model, execution_context):
-    """Everything a sweep does not do is refused here, before a partition is read or a solver created."""
-    mp = model.model_params
+def refuse_several_workers(execution_context, flag="--l2_reg_weights"):
+    if int(execution_context.get(constants.NUM_WORKERS) or 1) > 1:
+        raise SweepError(f"{flag} runs on one worker: the AUC of several workers cannot be combined from their counts")
+
+
+def refuse_blind_or_warm(mp, prior, prior_is=""):
+    """No validation data, no metric directory, or a prior model (`prior`: the model files found where the stage would look for one)."""
     if not mp.validation_data_dir:
         raise SweepError("--l2_reg_weights needs --validation_data_dir: only validation data can choose a weight")
     if not mp.metric_output_dir:
         raise SweepError("--l2_reg_weights needs --metric_output_dir: the sweep writes its metrics there")
-    prior = sorted(glob.glob(os.path.join(mp.output_model_dir, "part-*.avro")))
     if prior:
-        raise SweepError(f"--l2_reg_weights is a cold start, and {prior[0]} is a prior model: warm-started sweeps are not implemented")
+        raise SweepError(f"--l2_reg_weights is a cold start, and {prior[0]} is a prior model{prior_is}: warm-started sweeps are not implemented")
+
+
+def validate(model, execution_context):
+    """Everything a sweep does not do is refused here, before a partition is read or a solver created."""
+    mp = model.model_params
+    refuse_blind_or_warm(mp, sorted(glob.glob(os.path.join(mp.output_model_dir, "part-*.avro"))))
     if mp.rebalance_entities:
         raise SweepError("--l2_reg_weights does not run with --rebalance_entities=True")
-    if int(execution_context.get(constants.NUM_WORKERS) or 1) > 1:
-        raise SweepError("--l2_reg_weights runs on one worker: the AUC of several workers cannot be combined from their counts")
+    refuse_several_workers(execution_context)
 
 
 # ---- pass 1 --------------------------------------------------------------------------------------------------------------------------
-def _models_per_chunk(solver, K, P_train, N_eval):
-    """How many of the K models are solved before they are scored: all of them if K x (coefficients + scores) fits into half of the
-    free device memory next to the batch (GDMIX_SWEEP_CHUNK sets it: tests)."""
+def models_per_chunk(torch, device, K, bytes_per_model):
+    """How many of K models are held at once: all of them if they fit into half of the free device memory (GDMIX_SWEEP_CHUNK sets
+    it: tests)."""
     forced = int(os.environ.get("GDMIX_SWEEP_CHUNK", "0"))
     if forced > 0:
         return min(K, forced)
-    free, _ = solver.torch.cuda.mem_get_info(solver.device)
-    per_model = 8 * P_train + 4 * N_eval + 1
-    return int(max(1, min(K, (free // 2) // per_model)))
+    free, _ = torch.cuda.mem_get_info(device)
+    return int(max(1, min(K, (free // 2) // bytes_per_model)))
 
 
 def _solve(model, solver, packed, opts, out):
@@ -187,7 +206,7 @@ def sweep_partition(model, solver, train_batch, eval_batch, weights, evaluators,
         coef_pos, has_model = solver.join_features(vp, tp, train_entity_map(eval_batch.entity_ids, train_batch.entity_ids))
         labels = vp._raw_dev["y"]
     K = len(weights)
-    chunk = _models_per_chunk(solver, K, tp.P, 0 if vp is None else vp.N)
+    chunk = models_per_chunk(t, solver.device, K, 8 * tp.P + 4 * (0 if vp is None else vp.N) + 1)      # coefficients, and scores next to the batch
     base = solver.alloc_result(tp, variance=False)
     opts0 = model._solver_options()
     for first in range(0, K, chunk):
@@ -233,12 +252,6 @@ def run(driver, schema_params):
             if train_batch.E > 0:
                 sweep_partition(model, solver, train_batch, eval_batch, weights, evaluators)
             del train_batch, eval_batch
-    blocks = [ev.finish() for ev in evaluators]
-    values = [b[metric] for b in blocks]
-    for k, (w, b) in enumerate(zip(weights, blocks)):
-        write_model_summary(mp.metric_output_dir, k, w, metric, b)
-    best = select_best(metric, values)          # (every metric undefined: the stage fails here, the per-model summaries say why)
-    write_evals(mp.metric_output_dir, metric, weights, values, best)
-    logger.info(f"sweep: validation {metric} {dict(zip(weights, values))}; best l2_reg_weight = {weights[best]} (index {best})")
+    best = conclude(mp.metric_output_dir, metric, weights, [ev.finish() for ev in evaluators])
     mp.l2_reg_weight = float(weights[best])
     return best, weights[best]

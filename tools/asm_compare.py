@@ -1,7 +1,8 @@
 """Is the device code of every kernel the same as another commit's? Without a GPU: both trees' .hip units are compiled to gfx950
 assembly with the build's flags (`hipcc -S --cuda-device-only`) and compared kernel by kernel after stripping comments, section
 directives and per-compile labels. Kernels are matched by demangled name; --gained-false names kernels whose template list gained a
-trailing `false` argument since the other commit (a new compile-time parameter whose `false` instantiation must be the old kernel).
+trailing `false` argument since the other commit (a new compile-time parameter whose `false` instantiation must be the old kernel);
+--renamed old=new,... names kernels and types that were renamed since: the other commit's names and lines are read under the new names.
 
     python tools/asm_compare.py --parent HEAD~1 \\
         --gained-false re_solve_grp_kernel,re_solve_wave_kernel,re_solve_block_kernel,re_variance_full_kernel,re_solve_tall_kernel,re_solve_tall_team_kernel
@@ -35,9 +36,12 @@ def compile_units(csrc, out):
         return dict(zip(units, ex.map(one, units)))
 
 
-def functions(path):
-    """-> {mangled name: [normalised lines]}, {mangled name: kernel descriptor text}"""
+def functions(path, renamed=()):
+    """-> {mangled name: [normalised lines]}, {mangled name: kernel descriptor text}; `renamed`: (old, new) identifiers, applied to the
+    text in their mangled (length-prefixed) spelling"""
     txt = open(path).read()
+    for o, n in renamed:
+        txt = txt.replace(f"{len(o)}{o}", f"{len(n)}{n}")
     out, cur, buf = {}, None, []
     for line in txt.splitlines():
         m = re.match(r"^(\w+):\s*(;.*)?$", line)
@@ -67,7 +71,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", default="HEAD", help="the commit to compare the working tree with")
     ap.add_argument("--gained-false", default="", help="comma list of kernel names whose template arguments gained a trailing `false`")
+    ap.add_argument("--renamed", default="", help="comma list of old=new: kernel or type names of the other commit that were renamed since")
     a = ap.parse_args()
+    renamed = [tuple(r.split("=")) for r in a.renamed.split(",") if r]
     gained = [g for g in a.gained_false.split(",") if g]
 
     def key(d):
@@ -86,7 +92,7 @@ def main():
             if unit not in s_old:
                 print(f"{unit}: a new unit, {len(functions(s_new[unit])[0])} functions only in this tree")
                 continue
-            fo, mo = functions(s_old[unit])
+            fo, mo = functions(s_old[unit], renamed)
             fn, mn = functions(s_new[unit])
             do, dn = demangle(list(fo)), demangle(list(fn))
             new_by_key = {key(dn[k]): k for k in fn if k not in fo}
