@@ -311,8 +311,10 @@ class ModelTable:
         return found, chunk, row
 
 
-def _model_coefficients_for_batch(table, entity_ids, unique_global, ent_feat_ptr, has_intercept, num_features, native=None, out=None):
-    """Coefficients of the prior / trained models in the packed batch's local index space.
+def _model_coefficients_for_batch(table, entity_ids, unique_global, ent_feat_ptr, has_intercept, num_features, native=None, out=None,
+                                  field="theta"):
+    """Coefficients of the prior / trained models in the packed batch's local index space (field="variance": their variances by the
+    same join; a chunk without variances leaves zeros).
 
     For every entity that has a model: intercept from the model (always), and for every feature present in
     the current data the model's coefficient if it has one, else 0 (prepare_jobs:262-288 for training warm
@@ -339,10 +341,14 @@ def _model_coefficients_for_batch(table, entity_ids, unique_global, ent_feat_ptr
     if native:
         for c in np.unique(chunk[found]):
             ch = table._chunks[int(c)]
+            if ch[field] is None:
+                continue
             src_row = np.where(found & (chunk == c), row, -1)
-            native_reader.map_coefficients(theta, ent_feat_ptr, unique_global, src_row, ch["coef_ptr"], ch["feat_ptr"], ch["theta"],
+            native_reader.map_coefficients(theta, ent_feat_ptr, unique_global, src_row, ch["coef_ptr"], ch["feat_ptr"], ch[field],
                                            ch["idx"], has_intercept, zero_first=not cleared)
             cleared = True
+        if not cleared:
+            theta[:] = 0.0
         return theta, has_model
     F = int(num_features) + 1
     ent_of_feat = np.repeat(np.arange(E, dtype=np.int64), d)
@@ -350,10 +356,12 @@ def _model_coefficients_for_batch(table, entity_ids, unique_global, ent_feat_ptr
     feat_coef_pos = coef_ptr[:-1][ent_of_feat] + ic + (np.arange(unique_global.size, dtype=np.int64) - ent_feat_ptr[:-1][ent_of_feat])
     for c in np.unique(chunk[found]):
         ch = table._chunks[int(c)]
+        if ch[field] is None:
+            continue
         sel = np.flatnonzero(found & (chunk == c))
         rows = row[sel]
         if ic:
-            theta[coef_ptr[sel]] = ch["theta"][ch["coef_ptr"][rows]]
+            theta[coef_ptr[sel]] = ch[field][ch["coef_ptr"][rows]]
         fa, fb = ch["feat_ptr"][rows], ch["feat_ptr"][rows + 1]
         cnt = fb - fa
         if cnt.sum() == 0:
@@ -362,7 +370,7 @@ def _model_coefficients_for_batch(table, entity_ids, unique_global, ent_feat_ptr
         src_feat = _ranges(fa, cnt)                              # positions in the chunk's idx array
         src_ent = np.repeat(sel, cnt)                            # batch entity of each prior feature
         within = src_feat - np.repeat(fa, cnt)
-        src_val = ch["theta"][np.repeat(ch["coef_ptr"][rows], cnt) + ic + within]
+        src_val = ch[field][np.repeat(ch["coef_ptr"][rows], cnt) + ic + within]
         prior_key = src_ent * F + ch["idx"][src_feat]
         order = np.argsort(prior_key, kind="stable")
         pk, pv = prior_key[order], src_val[order]
@@ -371,6 +379,91 @@ def _model_coefficients_for_batch(table, entity_ids, unique_global, ent_feat_ptr
         hit = (pos < pk.size) & (pk[pos_c] == cur_key)
         theta[feat_coef_pos[hit]] = pv[pos_c[hit]]
     return theta, has_model
+
+
+# ---- incremental training (REParams.incremental_training; include/gdmix_re.h, "incremental training") ------------------------------
+def usable_variance(v):
+    """Prior variances with the default put in: 1 where the variance is missing (0 after the join), not finite or <= 0."""
+    v = np.asarray(v, np.float64)
+    return np.where(np.isfinite(v) & (v > 0.0), v, 1.0)
+
+
+def prior_for_batch(table, entity_ids, unique_global, ent_feat_ptr, has_intercept, num_features, native=None):
+    """(mean [P], variance [P]) of the prior model in the packed batch's local index space, defaults put in: a coefficient without a
+    prior (a new entity, a feature new for the entity, a coefficient thresholded out of the model file, a record without variances, a
+    variance that is not finite or <= 0) has mean 0 where the mean is missing and variance 1 where the variance is missing."""
+    mean, _ = _model_coefficients_for_batch(table, entity_ids, unique_global, ent_feat_ptr, has_intercept, num_features, native=native)
+    var, _ = _model_coefficients_for_batch(table, entity_ids, unique_global, ent_feat_ptr, has_intercept, num_features, native=native,
+                                           field="variance")
+    return mean, usable_variance(var)
+
+
+def prior_scale(variance, ent_feat_ptr, has_intercept):
+    """s = sqrt(v) in the batch's coefficient order; 1 for every intercept: the solve kernels' intercept column is the constant 1 and
+    cannot be scaled (include/gdmix_re.h, "The intercept": unregularised it has no penalty, regularised it is penalised with v_0 = 1)."""
+    scale = np.sqrt(np.asarray(variance, np.float64))
+    if has_intercept:
+        E = len(ent_feat_ptr) - 1
+        scale[np.asarray(ent_feat_ptr[:-1], np.int64) + np.arange(E, dtype=np.int64)] = 1.0
+    return scale
+
+
+def carry_over_prior_features(table, entity_ids, theta, variance, unique_global, ent_feat_ptr, has_intercept):
+    """A partition's trained models with the prior features their entities' new data lacks put back: such a feature keeps its prior mean
+    and its prior variance (the one the regulariser would have used: 1 where the prior has none) — its posterior is its prior.
+    -> (theta, variance | None, unique_global, ent_feat_ptr) in the same layout, features ascending inside an entity. Host arrays."""
+    from .batch import _ranges
+    E = len(entity_ids)
+    ic = 1 if has_intercept else 0
+    ent_feat_ptr = np.asarray(ent_feat_ptr, np.int64)
+    unique_global = np.asarray(unique_global, np.int64)
+    found, chunk, row = table.lookup(entity_ids)
+    p_ent, p_idx, p_mean, p_var = [], [], [], []
+    for c in np.unique(chunk[found]):
+        ch = table._chunks[int(c)]
+        sel = np.flatnonzero(found & (chunk == c))
+        rows = row[sel]
+        fa = ch["feat_ptr"][rows]
+        cnt = ch["feat_ptr"][rows + 1] - fa
+        if cnt.sum() == 0:
+            continue
+        src = _ranges(fa, cnt)
+        pos = np.repeat(ch["coef_ptr"][rows] + ic - fa, cnt) + src
+        p_ent.append(np.repeat(sel, cnt)); p_idx.append(ch["idx"][src]); p_mean.append(ch["theta"][pos])
+        p_var.append(np.zeros(pos.size) if ch["variance"] is None else ch["variance"][pos])
+    if not p_ent:
+        return theta, variance, unique_global, ent_feat_ptr
+    p_ent, p_idx, p_mean, p_var = (np.concatenate(a) for a in (p_ent, p_idx, p_mean, p_var))
+    F = int(max(unique_global.max(initial=0), p_idx.max(initial=0))) + 1
+    d = np.diff(ent_feat_ptr)
+    cur_ent = np.repeat(np.arange(E, dtype=np.int64), d)
+    cur_key = cur_ent * F + unique_global                    # ascending: entity-major, features ascending inside an entity
+    p_key = p_ent * F + p_idx
+    at = np.minimum(np.searchsorted(cur_key, p_key), max(cur_key.size - 1, 0))
+    absent = np.ones(p_key.size, bool) if cur_key.size == 0 else cur_key[at] != p_key
+    absent &= p_mean != 0.0                                  # (a zero mean is no coefficient: the model file would not hold it)
+    if not absent.any():
+        return theta, variance, unique_global, ent_feat_ptr
+    a_key, first = np.unique(p_key[absent], return_index=True)
+    a_ent = p_ent[absent][first]
+    a_mean, a_var = p_mean[absent][first], usable_variance(p_var[absent][first])
+    all_key = np.concatenate([cur_key, a_key])
+    order = np.argsort(all_key, kind="stable")
+    cur_coef = ent_feat_ptr[:-1][cur_ent] + cur_ent * ic + ic + (np.arange(unique_global.size, dtype=np.int64) - ent_feat_ptr[:-1][cur_ent])
+    all_ent = np.concatenate([cur_ent, a_ent])[order]
+    new_feat_ptr = np.concatenate([[0], np.cumsum(np.bincount(all_ent, minlength=E))]).astype(np.int64)
+    new_uniq = (all_key[order] - all_ent * F).astype(np.int64)
+    new_pos = np.arange(all_key.size, dtype=np.int64) + all_ent * ic + ic        # features ascending inside an entity
+    P = int(new_feat_ptr[-1]) + E * ic
+
+    def merged(cur, carried):
+        out = np.zeros(P, np.float64)
+        if ic:
+            out[new_feat_ptr[:-1] + np.arange(E, dtype=np.int64)] = cur[ent_feat_ptr[:-1] + np.arange(E, dtype=np.int64)]
+        out[new_pos] = np.concatenate([cur[cur_coef], carried])[order]
+        return out
+    return merged(np.asarray(theta, np.float64), a_mean), None if variance is None else merged(np.asarray(variance, np.float64), a_var), \
+        new_uniq, new_feat_ptr
 
 
 class RandomEffectLRLBFGSModel:
@@ -443,6 +536,9 @@ class RandomEffectLRLBFGSModel:
                      execution_context, schema_params)
 
     def predict(self, output_dir, input_data_path, metadata_file, checkpoint_path, execution_context, schema_params):
+        if getattr(self.model_params, "incremental_training", False):
+            raise ValueError("--incremental_training does not run with --action inference: it defines how a model is trained, scoring reads "
+                             "the model as it is")
         logger.info(f"Running inference on dataset : {input_data_path}, results to be written to path : {output_dir}")
         self._action(constants.ACTION_INFERENCE, (output_dir, input_data_path), metadata_file, checkpoint_path,
                      execution_context, schema_params)
@@ -683,7 +779,13 @@ class RandomEffectLRLBFGSModel:
         coef_ptr = feat_ptr + np.arange(batch.E + 1, dtype=np.int64) * ic
         self.last_training_stats = dict(entities=batch.E, samples=batch.N, nnz=batch.Z, **stats)
         results = ModelTable()
-        results.add_chunk(batch.entity_ids, theta_thr, coef_ptr, uniq, feat_ptr, variance)
+        if self._incremental(model_weights):
+            # dict.update replaces an entity's whole model: a prior feature its new data lacks would be dropped. Its posterior is its prior.
+            m_theta, m_var, m_uniq, m_fp = carry_over_prior_features(model_weights, batch.entity_ids, theta_thr, variance, uniq, feat_ptr,
+                                                                     self.has_intercept)
+            results.add_chunk(batch.entity_ids, m_theta, m_fp + np.arange(batch.E + 1, dtype=np.int64) * ic, m_uniq, m_fp, m_var)
+        else:
+            results.add_chunk(batch.entity_ids, theta_thr, coef_ptr, uniq, feat_ptr, variance)
         if self._read_cache is not None and self._read_cache[1] is batch and len(results) == batch.E:   # (an entity id listed twice is scored with its later model: no shortcut)
             if resident is not None:
                 self._read_cache[2:4] = list(resident)
@@ -824,10 +926,30 @@ class RandomEffectLRLBFGSModel:
         logit, per_coord = g["scores"]
         return logit[rows[0]:rows[1]], per_coord[rows[0]:rows[1]]
 
-    def _pack_and_solve(self, solver, pack, opts, theta0):
-        """pack() -> solve -> results on the host; once more without the tall team class if a team barrier timed out."""
+    def _incremental(self, model_weights):
+        """Is this partition trained against its prior model (REParams.incremental_training, and there is one)?"""
+        return bool(getattr(self.model_params, "incremental_training", False)) and bool(model_weights)
+
+    @staticmethod
+    def _solve_with_prior(solver, packed, opts, prior):
+        """The solve of include/gdmix_re.h, "incremental training": the transformed batch is solved from phi = 0 with the variance mode of
+        `opts`, theta, its thresholded form and the variances come back through gdmix_re_prior_restore. `packed` stays as it is."""
+        from .solver import SolveResult
+        mean, scale = prior
+        work = solver.prior_apply(packed, mean, scale)
+        solved = solver.solve(work, opts, theta0=None)
+        back = solver.prior_restore(packed, mean, scale, solved.theta, solved._t.get("variance"), threshold=opts.threshold)
+        return SolveResult({**solved._t, **back}, packed.E, packed.P)
+
+    def _pack_and_solve(self, solver, pack, opts, theta0, prior=None):
+        """pack() -> solve -> results on the host; once more without the tall team class if a team barrier timed out.
+        prior: (mean, scale) device arrays of an incremental solve (theta0 is then None), else None."""
+        if prior is not None:
+            solve = lambda packed, opts, theta0=None: self._solve_with_prior(solver, packed, opts, prior)
+        else:
+            solve = solver.solve
         packed = pack()
-        solved = solver.solve(packed, opts, theta0=theta0)
+        solved = solve(packed, opts, theta0=theta0)
         res = solved.to_host(("theta_thr", "variance") + self._STAT_KEYS)
         if (res["status"] == self.ST_ABORTED).any() and getattr(solver, "tall_team_n", 0) != 0:
             # a team of workgroups gave up waiting for a member (a device too busy, or too small, to keep four whole CUs per
@@ -840,7 +962,7 @@ class RandomEffectLRLBFGSModel:
             try:
                 solved = packed = None
                 packed = pack()
-                solved = solver.solve(packed, opts, theta0=theta0)
+                solved = solve(packed, opts, theta0=theta0)
                 res = solved.to_host(("theta_thr", "variance") + self._STAT_KEYS)
             finally:
                 solver.set_tall_team_n(keep)
@@ -894,10 +1016,21 @@ class RandomEffectLRLBFGSModel:
             packed = self._pack(solver, batch)
             feat_ptr = host_array(packed.ent_feat_ptr())
             uniq = host_array(packed.unique_global().to(torch_int64()))
-            theta0 = self._start_point(model_weights, batch.entity_ids, uniq, feat_ptr, batch.E, num_features)
+            prior = None
+            if self._incremental(model_weights):
+                # the prior model is the regulariser, not only the starting point: means and variances in the batch's index space go up,
+                # the solve runs on the transformed batch from phi = 0, i.e. from theta = mean
+                mean, var = prior_for_batch(model_weights, batch.entity_ids, uniq, feat_ptr, self.has_intercept, num_features)
+                scale = prior_scale(var, feat_ptr, self.has_intercept)
+                import torch
+                prior = (torch.from_numpy(mean).to(solver.device), torch.from_numpy(scale).to(solver.device))
+                theta0 = None
+            else:
+                theta0 = self._start_point(model_weights, batch.entity_ids, uniq, feat_ptr, batch.E, num_features)
             first = [packed]
             packed = None
-            packed, solved, res = self._pack_and_solve(solver, lambda: first.pop() if first else self._pack(solver, batch), opts, theta0)
+            packed, solved, res = self._pack_and_solve(solver, lambda: first.pop() if first else self._pack(solver, batch), opts, theta0,
+                                                       prior=prior)
             theta_thr, variance = res["theta_thr"], res.get("variance")
             self._check_statuses(res["status"], batch.E)
             theta_dev = getattr(solved, "theta_thr", None)    # still in HBM: what the scoring pass of this partition reads

@@ -123,6 +123,12 @@ class REParams(LRParams):
     # validation data scored under all of them, the stage metric of each on the device), then trains the stage as usual with the best one.
     # Comma-separated; l2_reg_weight is ignored when it is given. Needs validation_data_dir and metric_output_dir.
     l2_reg_weights: Optional[str] = None
+    # not in the reference (which leaves it open, random_effect_lr_lbfgs_model.py:155-160: "revisit it when we implement incremental
+    # learning"): with a prior model in output_model_dir the L2 term is centred on the prior means and weighted by the prior precisions
+    # (the variances --random_effect_variance_mode wrote), so that training on a new day's data alone is the Bayesian update of
+    # yesterday's model, as Photon-ML defines incremental training (include/gdmix_re.h, "incremental training"). A prior feature an
+    # entity's new data lacks keeps its prior mean and variance. Without a prior model the stage trains as without the flag.
+    incremental_training: bool = False
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -130,6 +136,10 @@ class REParams(LRParams):
 
     def __post_init__(self):
         self.l2_grid()      # a bad list is an error at parse time
+        if self.incremental_training and self.l2_reg_weights is not None:
+            raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
+        if self.incremental_training and self.rebalance_entities:
+            raise ValueError("--incremental_training does not run with --rebalance_entities: prior variances do not travel with the exchange")
         # the reference's REParams.__post_init__ does NOT chain to LRParams.__post_init__ (random_effect_lr_lbfgs_model.py:
         # 48-53): `--has_intercept False` with regularize_bias left at its default True is a valid random-effect
         # configuration upstream (test_random_effect_lr_lbfgs_model.py: warm start without intercept)

@@ -93,6 +93,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_eval_workspace_bytes", "gdmix_re_eval_entities", "gdmix_re_set_eval_small_max", "gdmix_re_eval_acc_reset", "gdmix_re_eval_acc_add",
     "gdmix_re_eval_acc_workspace_bytes", "gdmix_re_eval_acc_finish",
     "gdmix_re_join_features", "gdmix_re_score_models_workspace_bytes", "gdmix_re_score_models",
+    "gdmix_re_prior_workspace_bytes", "gdmix_re_prior_apply", "gdmix_re_prior_restore",
     "gdmix_re_class_kernel_name", "gdmix_java_string_hash", "gdmix_java_partition_id",
     "gdmix_java_partition_ids_i64")
 
@@ -206,7 +207,12 @@ def load_library():
     lib.gdmix_re_score_models_workspace_bytes.restype = C.c_size_t
     lib.gdmix_re_score_models.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    if lib.gdmix_re_abi_version() != 15:
+    lib.gdmix_re_prior_workspace_bytes.argtypes = [C.POINTER(_Packed)]
+    lib.gdmix_re_prior_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_prior_apply.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(_Packed), C.c_void_p]
+    lib.gdmix_re_prior_restore.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+    if lib.gdmix_re_abi_version() != 16:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib
@@ -258,9 +264,13 @@ def java_partition_id(s: str, num_partitions: int) -> int:
 class PackedBatch:
     """A packed ragged CSR/CSC batch resident in HBM. Keeps the torch tensors that back it alive."""
 
-    def __init__(self, c_struct, tensors, raw_dev, has_intercept, join=None):
+    def __init__(self, c_struct, tensors, raw_dev, has_intercept, join=None, parent=None):
         self.c = c_struct
         self._join = join       # REDeviceSolver.pack_join of the context that packed it (gdmix_re_set_defer_unique), or None
+        # REDeviceSolver.prior_apply: the batch this one shares its index arrays, labels, weights and scratch with. Kept alive here; the
+        # join of a deferred compaction and the workspace stay the parent's (this batch has no join of its own: nothing to wait for
+        # when it is dropped)
+        self._parent = parent
         self._tensors = tensors
         self._raw_dev = raw_dev
         self.has_intercept = bool(has_intercept)
@@ -271,6 +281,9 @@ class PackedBatch:
     def _view(self, ptr, count, dtype):
         import torch
         ws = self._tensors["workspace"]
+        own = self._tensors.get("prior_workspace")      # the arrays gdmix_re_prior_apply wrote (csr_val, csc_val, offset)
+        if own is not None and own.data_ptr() <= ptr < own.data_ptr() + own.numel():
+            ws = own
         off = ptr - ws.data_ptr()
         nbytes = count * torch.empty(0, dtype=dtype).element_size()
         return ws[off:off + nbytes].view(dtype)
@@ -286,6 +299,8 @@ class PackedBatch:
 
     def unique_global(self):
         import torch
+        if self._parent is not None:
+            return self._parent.unique_global()
         if self._join is not None:
             self._join()        # the compaction that writes it may still be running next to the solve (a no-op once waited for)
         return self._view(self.c.unique_global, self.D, torch.int32)      # int32 since ABI 12: half the bytes to compact, to copy and to keep
@@ -318,6 +333,17 @@ class PackedBatch:
     def csc_val(self):
         import torch
         return self._view(self.c.csc_val, self.Z, torch.float32)
+
+    def csr_val(self):
+        import torch
+        return self._view(self.c.csr_val, self.Z, torch.float32)
+
+    def offset(self):
+        """[N] float32: the raw batch's offsets, or the shifted ones of a batch made by REDeviceSolver.prior_apply."""
+        import torch
+        if self._parent is not None:
+            return self._view(self.c.offset, self.N, torch.float32)
+        return self._raw_dev["offset"]
 
     def coef_ptr_host(self):
         """[E+1] int64 numpy: offsets of each entity's coefficient slice in theta."""
@@ -726,6 +752,53 @@ class REDeviceSolver:
                                        None if has_model is None else has_model.data_ptr(), logit.data_ptr(),
                                        per.data_ptr(), self._stream()), "gdmix_re_score")
         return logit, per
+
+    # ---- incremental training: L2 centred on a prior model (include/gdmix_re.h, "incremental training") ----------------------------
+    def _coef_array(self, a, P, what):
+        t = self.torch
+        if isinstance(a, np.ndarray):
+            a = t.from_numpy(np.ascontiguousarray(a, np.float64)).to(self.device)
+        elif not a.is_cuda:
+            a = a.to(self.device, non_blocking=a.is_pinned())
+        if a.numel() != P or a.dtype != t.float64 or not a.is_contiguous():
+            raise GdmixReError(f"{what} must be a contiguous float64 array with one entry per coefficient")
+        return a
+
+    @_serialised
+    def prior_apply(self, packed: PackedBatch, mean, scale) -> PackedBatch:
+        """gdmix_re_prior_apply: mean / scale [P] float64 (numpy or tensors; scale = sqrt of the prior variances, 1 where there is none) ->
+        the transformed batch x' = x s, offset' = offset + x~ mean. It shares every other array with `packed`, which stays as it is."""
+        t = self.torch
+        mean = self._coef_array(mean, packed.P, "mean")
+        scale = self._coef_array(scale, packed.P, "scale")
+        nbytes = int(self.lib.gdmix_re_prior_workspace_bytes(C.byref(packed.c)))
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=self.device)
+        c_out = _Packed()
+        _check(self.lib.gdmix_re_prior_apply(self._h, C.byref(packed.c), int(packed.has_intercept), mean.data_ptr() if packed.P else None,
+                                             scale.data_ptr() if packed.P else None, ws.data_ptr(), nbytes, C.byref(c_out), self._stream()),
+               "gdmix_re_prior_apply")
+        tensors = dict(packed._tensors)
+        tensors["prior_workspace"] = ws
+        tensors["prior"] = (mean, scale)
+        return PackedBatch(c_out, tensors, packed._raw_dev, packed.has_intercept, join=None, parent=packed)
+
+    @_serialised
+    def prior_restore(self, packed: PackedBatch, mean, scale, phi, var_phi=None, threshold=1e-4):
+        """gdmix_re_prior_restore: phi (and the variances of the transformed solve) -> dict(theta, theta_thr, variance | None), device tensors:
+        theta = mean + scale * phi, thresholded on theta, variance = scale^2 var_phi."""
+        t = self.torch
+        P = packed.P
+        mean = self._coef_array(mean, P, "mean")
+        scale = self._coef_array(scale, P, "scale")
+        phi = self._coef_array(phi, P, "phi")
+        var_phi = None if var_phi is None else self._coef_array(var_phi, P, "var_phi")
+        theta = t.empty(P, dtype=t.float64, device=self.device)
+        theta_thr = t.empty(P, dtype=t.float64, device=self.device)
+        variance = None if var_phi is None else t.empty(P, dtype=t.float64, device=self.device)
+        p = lambda x: None if x is None or not P else x.data_ptr()
+        _check(self.lib.gdmix_re_prior_restore(self._h, C.byref(packed.c), int(packed.has_intercept), p(mean), p(scale), float(threshold), p(phi), p(var_phi),
+                                               p(theta), p(theta_thr), p(variance), self._stream()), "gdmix_re_prior_restore")
+        return dict(theta=theta, theta_thr=theta_thr, variance=variance)
 
     # ---- sweep: K models of one training batch score another batch (include/gdmix_re.h, "sweep") ------------------------------
     SWEEP_MODELS_PER_PASS = 8       # GDMIX_RE_SWEEP_MODELS_PER_PASS

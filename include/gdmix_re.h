@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 15
+#define GDMIX_RE_ABI_VERSION 16
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -468,6 +468,63 @@ GDMIX_API size_t gdmix_re_score_models_workspace_bytes(int64_t P_train, int K);
 GDMIX_API int gdmix_re_score_models(gdmix_re_ctx* ctx, const gdmix_re_packed* eval, int has_intercept, const double* const* thetas, int K,
                                     int64_t P_train, const int64_t* coef_pos, const uint8_t* has_model, float* logit, float* logit_per_coord,
                                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- (ABI 16) incremental training: the L2 term centred on a prior model and weighted by its precisions ---------------------------
+ * A warm start alone forgets the prior model once it converges: with l2 > 0 the optimum does not depend on the starting point. With
+ * --incremental_training True (gdmix_amd/params.py; not in the reference, which leaves it open: random_effect_lr_lbfgs_model.py:155-160,
+ * fixed_effect_lr_lbfgs_model.py:363-366) the prior model's means and variances (what --random_effect_variance_mode writes) define the
+ * regulariser, as Photon-ML defines incremental training: a model trained on a new day's data alone is the Bayesian update of
+ * yesterday's. csrc/re_prior.hip.
+ *
+ * Definition. One entity, theta in local index space, intercept first; coefficient j has a prior mean mu_j and a prior variance v_j,
+ * s_j = sqrt(v_j):
+ *     F(theta) = (1/n) ( sum_i w_i l(z_i, y_i) + (l2/2) sum_{j regularised} (theta_j - mu_j)^2 / v_j ),   z = X~ theta + offset
+ * l the logistic or the squared loss (opts->linear) as without a prior.
+ * Defaults. A coefficient has no prior when the entity is new, when the feature is new for the entity, when the coefficient was
+ * thresholded out of the model file, when the record has no variances, or when its variance is missing, not finite or <= 0. Such a
+ * coefficient gets mu_j = 0 where the mean is missing and v_j = 1 where the variance is missing: an entity without a prior has exactly
+ * the objective of gdmix_re_opts.
+ * The intercept. Every solve kernel's intercept column is the constant 1: it cannot be scaled, so s_0 = 1 for every intercept. An
+ * unregularised intercept (regularize_bias 0) has no penalty anyway. A regularised one is penalised with v_0 = 1, (l2/2)(theta_0 -
+ * mu_0)^2: its prior mean is honoured, its prior variance is not (F above with v_0 := 1), and its written variance is Var'(phi_0). mu_0
+ * applies as the shift below either way.
+ * Substitution. phi_j = (theta_j - mu_j) / s_j turns F into the objective of gdmix_re_opts in phi on a transformed batch:
+ *     x'_ij     = x_ij s_j
+ *     offset'_i = offset_i + sum_j x~_ij mu_j          (intercept included)
+ *     penalty   = (l2/2) |phi_reg|^2,   phi0 = 0       (theta0 NULL: the solve starts at theta = mu)
+ * and afterwards theta_j = mu_j + s_j phi_j, Var(theta_j) = v_j Var'(phi_j), Var' the variance mode (SIMPLE or FULL) of the transformed
+ * batch, since H_theta^-1 = S H_phi^-1 S. No solve, pack, score or variance kernel knows about priors: gdmix_re_prior_apply makes the
+ * transformed batch, gdmix_re_solve solves it, gdmix_re_prior_restore maps the result back.
+ * Consequences.
+ *   rounding    the transformed batch is held in the precision of every batch on this path: x' = (float)((double)x * s_j), one rounding
+ *               per non-zero; offset' is the fp64 sum mu_0 + sum_j x_ij mu_j + offset_i rounded once to fp32 — what gdmix_re_score
+ *               writes to `logit` for theta = mu (to the order of the sum). The problem solved is the one with these fp32 values; it
+ *               differs from the exact-arithmetic F by a relative perturbation of the data of 2^-24.
+ *   stop tests  pgtol, ftol and every other stop test of L-BFGS-B apply in phi-space: |s (.) grad_theta F|_inf <= pgtol. fval is F;
+ *               nit, nfev and status are those of the transformed solve.
+ *   threshold   the sparsity threshold applies to theta, not to phi.
+ *
+ * gdmix_re_prior_apply: mean / scale [P] fp64 on the device, P = packed->D + packed->E * has_intercept, in the batch's coefficient order;
+ *   `scale` arrives computed (the host takes the square root: the caller and the device use the same bits). Writes new csr_val, csc_val and
+ *   offset arrays into `workspace` (at least gdmix_re_prior_workspace_bytes(packed) device bytes; less is GDMIX_RE_ENOMEM) and fills *out
+ *   as a copy of *packed that points at them. Index arrays, y, weight, order and the scratch are SHARED with *packed, not copied; *packed
+ *   itself is left as it is (a stage scores it afterwards with theta). Work is dealt by sample rows and by non-zeros, never by entity (one
+ *   batch holds entities of one non-zero next to a head of 2^20): the CSR pass gives a row to a lane, a row of more than 32 non-zeros to
+ *   its whole wavefront, reads each non-zero once, gathers mu and s at (coefficient base + csr_col), writes x' and the row's offset';
+ *   the CSC pass gives four consecutive non-zeros to a lane, which finds their column by bisection of the entity's col_ptr.
+ * gdmix_re_prior_restore: phi [P] (gdmix_re_result.theta of the transformed solve), var_phi [P] or NULL ->
+ *     theta[j]     = mean[j] + scale[j] * phi[j]                      (fp64, product and sum rounded separately)
+ *     theta_thr[j] = |theta[j]| <= threshold ? 0.0 : theta[j]         (threshold_coefficients, as gdmix_re_solve applies it)
+ *     variance[j]  = (scale[j] * scale[j]) * var_phi[j]               (when both variance and var_phi are given)
+ *   theta, theta_thr, variance: any may be NULL; each may alias its input (phi, var_phi).
+ * Both calls are stream-ordered, without a host synchronisation, and read nothing a deferred compaction writes (unique_global): they
+ * need no gdmix_re_pack_join. */
+GDMIX_API size_t gdmix_re_prior_workspace_bytes(const gdmix_re_packed* packed);
+GDMIX_API int gdmix_re_prior_apply(gdmix_re_ctx* ctx, const gdmix_re_packed* packed, int has_intercept, const double* mean, const double* scale,
+                                   void* workspace, size_t workspace_bytes, gdmix_re_packed* out, void* stream);
+GDMIX_API int gdmix_re_prior_restore(gdmix_re_ctx* ctx, const gdmix_re_packed* packed, int has_intercept, const double* mean, const double* scale,
+                                     double threshold, const double* phi, const double* var_phi, double* theta, double* theta_thr,
+                                     double* variance, void* stream);
 
 /* ---- B4: the upstream Spark partitioner's hash, bit-exact (host functions) ------------------------
  * hashCode over UTF-16 code units in wrapping int32; Math.abs(Int.MinValue) stays negative; Scala %
