@@ -111,10 +111,21 @@ struct FeDev {
   CompactPlan* plan;
   CompactMats* mats;
   Work W;                   // global coefficient space, P each; ws / wy m*P
+  const double *mu, *sc;    // [P] prior mean and scale (include/gdmix_fe.h, "incremental training"), NULL without one; read by the PRIOR variants only
 };
 
+// theta_j of the coefficient whose solver variable is xj: phi_j with a prior installed (W.x holds phi then), itself otherwise
+template <bool PRIOR>
+__device__ __forceinline__ double fe_theta_of(const FeDev& F, int64_t j, double xj) {
+  return PRIOR ? __builtin_fma(F.sc[j], xj, F.mu[j]) : xj;      // one rounding, the same at every site
+}
+
+template <bool PRIOR = false>
 __global__ void fe_prepare_kernel(FeDev F) {
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < F.d; j += gridDim.x * blockDim.x) F.xl[j] = F.W.x[F.umap[j]];
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < F.d; j += gridDim.x * blockDim.x) {
+    const int64_t g = F.umap[j];
+    F.xl[j] = fe_theta_of<PRIOR>(F, g, F.W.x[g]);
+  }
 }
 
 // ---- the data term's VALUE, added up error-free (round 6) ----------------------------------------------------------------------------
@@ -232,8 +243,9 @@ __device__ __forceinline__ void fe_scatter_compressed(double* acc, const unsigne
   }
 }
 
-template <bool ROWS, bool HESS, bool PACKED>
+template <bool ROWS, bool HESS, bool PACKED, bool PRIOR = false>
 __global__ __launch_bounds__(WAVE) void fe_scatter_kernel(FeDev F, SolveParams o) {
+  static_assert(ROWS || !PRIOR, "the column pass gathers residuals: it has no prior variant");
   // exactly 16 KiB: ten wavefronts per CU (160 KiB of LDS). Round 5: a spare accumulator for the lanes beyond the end of the last
   // trip made it 16 400 B = nine; those lanes now add 0.0 to accumulator 0 (x + 0.0 == x bit for bit; an accumulator that is still
   // -0.0 cannot occur: they start at +0.0). Measured: nine or ten makes no difference (0.556 ms either way, three runs each):
@@ -247,7 +259,7 @@ __global__ __launch_bounds__(WAVE) void fe_scatter_kernel(FeDev F, SolveParams o
   const int k0 = C.ustart[u], k1 = C.ustart[u + 1], b = C.ublock[u];
   const int kb = PACKED ? C.kbase[u] : 0;
   const bool whole = ROWS && (C.ufirst[b + 1] - C.ufirst[b] == 1);
-  const double xb = (ROWS && F.ic) ? F.W.x[F.D] : 0.0;
+  const double xb = (ROWS && F.ic) ? fe_theta_of<PRIOR>(F, F.D, F.W.x[F.D]) : 0.0;
   const uint2* __restrict__ ent = C.ent;
   const int32_t* __restrict__ key = C.key;
   const float* __restrict__ val = C.val;
@@ -376,7 +388,7 @@ __device__ __forceinline__ double fe_strand_sum(const double* __restrict__ part,
 
 // rows of the blocks that were cut into several units
 constexpr int FE_FIX_PER_BLOCK = FE_B / FE_RED_OUT;   // workgroups of fe_rows_fix_kernel per block
-template <bool HESS = false>
+template <bool HESS = false, bool PRIOR = false>
 __global__ __launch_bounds__(FE_THREADS) void fe_rows_fix_kernel(FeDev F, SolveParams o) {
   __shared__ double lds[FE_STRANDS][FE_RED_OUT];
   if (!HESS && F.state->status >= 0) return;
@@ -384,7 +396,7 @@ __global__ __launch_bounds__(FE_THREADS) void fe_rows_fix_kernel(FeDev F, SolveP
   const int b = F.multi[blockIdx.x / FE_FIX_PER_BLOCK];
   const int i = (blockIdx.x % FE_FIX_PER_BLOCK) * FE_RED_OUT + out;
   const int row = b * FE_B + i;
-  const double xb = F.ic ? F.W.x[F.D] : 0.0;
+  const double xb = F.ic ? fe_theta_of<PRIOR>(F, F.D, F.W.x[F.D]) : 0.0;
   const double t = fe_strand_sum(F.rc.part, F.rc.ufirst[b], F.rc.ufirst[b + 1], i, strand, lds, out);
   double loss = 0.0, loss_lo = 0.0, rsum = 0.0;
   if (strand == 0 && row < F.n) fe_emit_row<HESS>(F, o, row, t, xb, loss, loss_lo, rsum);
@@ -523,7 +535,14 @@ __global__ void fe_hot_remap_kernel(const int32_t* __restrict__ ptr, int n, cons
 // "virtual block" vb of nvb — coefficients (vb * 256 + tid) + k * nvb * 256 — into acc_part[vb]. The partition is a function of P
 // alone (nvb = min(ceil(P / 256), FE_DOT_BLOCKS)), not of the launch: fe_dots_kernel runs one workgroup per virtual block,
 // fe_tail_kernel deals them over fewer resident workgroups, and both give the same bits.
-template <bool SC1 = false>
+// the reduced data gradient of coefficient j in the solver's variable: with a prior, grad_phi = s (.) grad_theta. The product is rounded on
+// its own — not fused into the sum with the regulariser behind it — so that a neutral prior (s = 1) leaves the bits of the plain path.
+__device__ __forceinline__ double fe_mul_rounded(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+template <bool SC1 = false, bool PRIOR = false>
 __device__ __forceinline__ void fe_dots_block(const FeDev& F, const SolveParams& o, int vb, int nvb, double (*red)[COMPACT_KD]) {
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid >> 6;
   const int col = F.state->col, head = F.state->head, m = o.m, P = F.P;
@@ -533,7 +552,8 @@ __device__ __forceinline__ void fe_dots_block(const FeDev& F, const SolveParams&
   for (int j = vb * FE_THREADS + tid; j < P; j += nvb * FE_THREADS) {
     const bool reg = (j < F.D) || o.regularize_bias;   // the intercept is coefficient D
     const double xj = F.W.x[j];
-    const double gj = F.fg[j] + (reg ? o.l2 * xj : 0.0);
+    const double fj = PRIOR ? fe_mul_rounded(F.fg[j], F.sc[j]) : F.fg[j];
+    const double gj = fj + (reg ? o.l2 * xj : 0.0);
     F.fg[j] = 0.0;   // consumed: the next evaluation starts from a clear buffer (gdmix_fe_eval)
     F.W.g[j] = gj;
     const double dj = F.W.d[j], rj = F.W.r[j];
@@ -579,10 +599,11 @@ __device__ __forceinline__ void fe_dots_block(const FeDev& F, const SolveParams&
   }
 }
 
+template <bool PRIOR = false>
 __global__ __launch_bounds__(FE_THREADS) void fe_dots_kernel(FeDev F, SolveParams o) {
   __shared__ double red[FE_WAVES][COMPACT_KD];
   if (F.state->status >= 0) return;     // a step enqueued behind the stop (gdmix_fe_step_async) is a no-op
-  fe_dots_block(F, o, blockIdx.x, gridDim.x, red);
+  fe_dots_block<false, PRIOR>(F, o, blockIdx.x, gridDim.x, red);
 }
 
 // one workgroup: totals of the products (the virtual blocks' shares, in a fixed order), then the driver's decision
@@ -672,11 +693,12 @@ __global__ __launch_bounds__(FE_THREADS) void fe_step_kernel(FeDev F, SolveParam
 }
 
 // the elementwise part of a step for coefficient j; the shard's copy of x in local order follows it (the row pass gathers from xl)
+template <bool PRIOR = false>
 __device__ __forceinline__ void fe_update_one(const FeDev& F, const CompactPlan& plan, const CompactMats& mats, int m, int j) {
   if (plan.action == CA_STOP_RESTORE) F.W.x[j] = F.W.t[j];
   else compact_update(plan, mats, F.W, F.P, m, j);
   const int jl = F.inv[j];
-  if (jl >= 0) F.xl[jl] = F.W.x[j];
+  if (jl >= 0) F.xl[jl] = fe_theta_of<PRIOR>(F, j, F.W.x[j]);
 }
 
 // ---- the whole step in ONE launch (round 5) ----------------------------------------------------------------------------------------
@@ -691,6 +713,7 @@ __device__ __forceinline__ void fe_update_one(const FeDev& F, const CompactPlan&
 // evaluations ahead of the status it has read (gdmix_fe_step_async).
 struct FeSync { unsigned arrive, gen, aborted; };      // aborted: sticky, set by a waiter whose watchdog fired (never cleared: the problem is dead)
 
+template <bool PRIOR = false>
 __global__ __launch_bounds__(FE_THREADS) void fe_tail_kernel(FeDev F, SolveParams o, int dot_blocks, int32_t* status_out, unsigned seq) {
   __shared__ double red[FE_WAVES][COMPACT_KD];
   __shared__ double tot[COMPACT_KD];
@@ -702,7 +725,7 @@ __global__ __launch_bounds__(FE_THREADS) void fe_tail_kernel(FeDev F, SolveParam
   if (threadIdx.x == 0) timed_out = 0;
   const int tid = threadIdx.x;
   for (int vb = blockIdx.x; vb < dot_blocks; vb += gridDim.x) {
-    fe_dots_block<true>(F, o, vb, dot_blocks, red);
+    fe_dots_block<true, PRIOR>(F, o, vb, dot_blocks, red);
     __syncthreads();                     // red is reused
   }
   // What crosses workgroups inside this launch — the shares, then plan and matrices — is written with write-through (sc1) stores
@@ -767,18 +790,27 @@ __global__ __launch_bounds__(FE_THREADS) void fe_tail_kernel(FeDev F, SolveParam
   const CompactPlan plan = plan_s;
   if (plan.action == CA_STOP) return;
   for (int vb = blockIdx.x; vb < dot_blocks; vb += gridDim.x)
-    for (int j = vb * FE_THREADS + tid; j < F.P; j += dot_blocks * FE_THREADS) fe_update_one(F, plan, mats, o.m, j);
+    for (int j = vb * FE_THREADS + tid; j < F.P; j += dot_blocks * FE_THREADS) fe_update_one<PRIOR>(F, plan, mats, o.m, j);
 }
 
+template <bool PRIOR = false>
 __global__ void fe_update_kernel(FeDev F, int m) {
   const CompactPlan plan = *F.plan;
   if (plan.action == CA_STOP) return;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < F.P; j += gridDim.x * blockDim.x) fe_update_one(F, plan, *F.mats, m, j);
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < F.P; j += gridDim.x * blockDim.x) fe_update_one<PRIOR>(F, plan, *F.mats, m, j);
 }
 
+// the start point in the solver's variable: theta0 itself, or with a prior phi0 = (theta0 - mu) / s (theta0 NULL: phi0 = 0, theta = mu)
+template <bool PRIOR>
+__device__ __forceinline__ double fe_start_of(const FeDev& F, const double* __restrict__ theta0, int64_t j) {
+  if (!theta0) return 0.0;
+  return PRIOR ? (theta0[j] - F.mu[j]) / F.sc[j] : theta0[j];
+}
+
+template <bool PRIOR = false>
 __global__ void fe_init_kernel(FeDev F, const double* __restrict__ theta0) {
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < F.P; j += gridDim.x * blockDim.x) {
-    F.W.x[j] = theta0 ? theta0[j] : 0.0;
+    F.W.x[j] = fe_start_of<PRIOR>(F, theta0, j);
     F.W.d[j] = 0.0;
     F.W.r[j] = 0.0;
     F.W.g[j] = 0.0;
@@ -787,7 +819,7 @@ __global__ void fe_init_kernel(FeDev F, const double* __restrict__ theta0) {
   // the shard's local copy of the start point (afterwards the update keeps it current: fe_update_one)
   for (int jl = blockIdx.x * blockDim.x + threadIdx.x; jl < F.d; jl += gridDim.x * blockDim.x) {
     const int64_t j = F.umap[jl];      // (widened: an index into the global coefficient space)
-    F.xl[jl] = theta0 ? theta0[j] : 0.0;
+    F.xl[jl] = fe_theta_of<PRIOR>(F, j, fe_start_of<PRIOR>(F, theta0, j));
     F.inv[j] = jl;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -801,6 +833,20 @@ __global__ void fe_init_kernel(FeDev F, const double* __restrict__ theta0) {
 // From the packed shard's CSR (for the column pass) and CSC (for the row pass) arrays: segment of every entry (flag + scan),
 // stable sort by block of the entry's index (rocPRIM radix sort on the block number alone, so the source order — the order of
 // the gathered vector — survives inside a block), units = the blocks' runs cut every `chunk` entries.
+// ---- incremental training: what only a problem with a prior launches ------------------------------------------------------------------
+// *bad = 1 if a scale is not finite or not > 0 (gdmix_fe_set_prior reads it back before anything of the problem is touched)
+__global__ void fe_prior_check_kernel(const double* __restrict__ scale, int P, int32_t* __restrict__ bad) {
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < P; j += gridDim.x * blockDim.x) {
+    const double s = scale[j];
+    if (!(s > 0.0) || s == __builtin_inf()) *bad = 1;      // (every writer stores the same value)
+  }
+}
+
+// gdmix_fe_result with a prior: theta = mu + s (.) phi, the expression the passes gathered from
+__global__ void fe_prior_theta_kernel(FeDev F, double* __restrict__ theta) {
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < F.P; j += gridDim.x * blockDim.x) theta[j] = fe_theta_of<true>(F, j, F.W.x[j]);
+}
+
 __global__ void fe_flag_kernel(const int32_t* __restrict__ ptr, int nseg, int64_t z, int32_t* __restrict__ flag) {
   for (int s = blockIdx.x * blockDim.x + threadIdx.x + 1; s < nseg; s += gridDim.x * blockDim.x) {
     const int p = ptr[s];
@@ -1013,6 +1059,7 @@ struct gdmix_fe_problem {
   void* ccopies[2];      // ... and their units in the 6-byte form
   int compress;          // bit 0: row pass, bit 1: column pass may use the 6-byte form (GDMIX_FE_COMPRESS; default: FE_COMPRESS_DEFAULT)
   void* hot_mem;         // the frequent columns' tables
+  double* prior_mem;     // [2 P] the problem's copy of the prior mean and scale, then the check's flag (gdmix_fe_set_prior); NULL until the first prior
   int32_t* status_dev;
   hipEvent_t ev[3];
   bool timed;
@@ -1241,6 +1288,7 @@ static void fe_free(gdmix_fe_problem* p) {
   for (auto& c : p->copies) if (c) (void)hipFree(c);
   for (auto& c : p->ccopies) if (c) (void)hipFree(c);
   if (p->hot_mem) (void)hipFree(p->hot_mem);
+  if (p->prior_mem) (void)hipFree(p->prior_mem);
   delete p;
 }
 
@@ -1303,8 +1351,9 @@ static int fe_split_hot(gdmix_fe_problem* p, const gdmix_re_packed* b, hipStream
   return GDMIX_RE_OK;
 }
 
+// prior: x of F is phi (a prior is installed and the pass runs at the solver's point): the row pass reads theta = mu + s (.) phi
 template <bool HESS>
-static int fe_passes(gdmix_fe_problem* p, const FeDev& F, hipStream_t s, bool timed) {
+static int fe_passes(gdmix_fe_problem* p, const FeDev& F, hipStream_t s, bool timed, bool prior) {
   // features absent from this shard must read 0 in the reduce buffer; fe_dots_kernel leaves it cleared behind a step
   if (p->dirty) HIP_TRY(hipMemsetAsync(F.fg, 0, ((size_t)F.P + 1) * 8, s));
   p->dirty = true;
@@ -1313,19 +1362,49 @@ static int fe_passes(gdmix_fe_problem* p, const FeDev& F, hipStream_t s, bool ti
   if (gd < 1) gd = 1;
   // xl (x in the shard's local order) is kept current by the step's update (fe_update_one); the Hessian passes may run at
   // another point: they gather it themselves and put the solver's back afterwards
-  if (HESS) hipLaunchKernelGGL(fe_prepare_kernel, dim3(gd), dim3(256), 0, s, F);
+  if (HESS && prior) hipLaunchKernelGGL(fe_prepare_kernel<true>, dim3(gd), dim3(256), 0, s, F);
+  else if (HESS) hipLaunchKernelGGL(fe_prepare_kernel<false>, dim3(gd), dim3(256), 0, s, F);
   if (timed) HIP_TRY(hipEventRecord(p->ev[0], s));
-  if (F.rc.ent) hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, true>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
-  else hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, false>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
-  if (F.nmulti) hipLaunchKernelGGL((fe_rows_fix_kernel<HESS>), dim3(F.nmulti * FE_FIX_PER_BLOCK), dim3(FE_THREADS), 0, s, F, p->o);
+  if (prior) {
+    if (F.rc.ent) hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, true, true>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
+    else hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, false, true>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
+    if (F.nmulti) hipLaunchKernelGGL((fe_rows_fix_kernel<HESS, true>), dim3(F.nmulti * FE_FIX_PER_BLOCK), dim3(FE_THREADS), 0, s, F, p->o);
+  } else {
+    if (F.rc.ent) hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, true>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
+    else hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, false>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
+    if (F.nmulti) hipLaunchKernelGGL((fe_rows_fix_kernel<HESS>), dim3(F.nmulti * FE_FIX_PER_BLOCK), dim3(FE_THREADS), 0, s, F, p->o);
+  }
   if (timed) HIP_TRY(hipEventRecord(p->ev[1], s));
   if (F.cc.ent) hipLaunchKernelGGL((fe_scatter_kernel<false, HESS, true>), dim3(F.cc.nlaunch), dim3(WAVE), 0, s, F, p->o);
   else hipLaunchKernelGGL((fe_scatter_kernel<false, HESS, false>), dim3(F.cc.nlaunch), dim3(WAVE), 0, s, F, p->o);
   if (timed) HIP_TRY(hipEventRecord(p->ev[2], s));
   int gf = (F.d + FE_RED_OUT - 1) / FE_RED_OUT;
   hipLaunchKernelGGL(fe_finish_kernel<HESS>, dim3((gf < FE_FIN_BLOCKS ? FE_FIN_BLOCKS : gf) + F.hot.n), dim3(FE_THREADS), 0, s, F);
-  if (HESS) hipLaunchKernelGGL(fe_prepare_kernel, dim3(gd), dim3(256), 0, s, p->F);
+  if (HESS && p->F.mu) hipLaunchKernelGGL(fe_prepare_kernel<true>, dim3(gd), dim3(256), 0, s, p->F);      // the solver's point back into xl
+  else if (HESS) hipLaunchKernelGGL(fe_prepare_kernel<false>, dim3(gd), dim3(256), 0, s, p->F);
   HIP_TRY(hipGetLastError());
+  return GDMIX_RE_OK;
+}
+
+// The problem as gdmix_fe_create leaves it, at its current options and prior, from start point theta0 (gdmix_fe_restart, gdmix_fe_set_prior):
+// the pool is zeroed again but for the list of row blocks with several units, F.inv refilled, the start point and a fresh L-BFGS state
+// written by the same fe_init_kernel, the host's counters put back. Everything is enqueued behind whatever the stream still holds.
+static int fe_reset(gdmix_fe_problem* p, const double* theta0, hipStream_t s) {
+  const FeDev& F = p->F;
+  char* base = static_cast<char*>(p->pool);
+  HIP_TRY(hipMemsetAsync(base, 0, p->pool_multi, s));
+  HIP_TRY(hipMemsetAsync(base + p->pool_multi_end, 0, p->pool_bytes - p->pool_multi_end, s));
+  HIP_TRY(hipMemsetAsync(base + p->pool_inv, 0xff, (size_t)F.P * 4, s));
+  int gp = (F.P + 255) / 256;
+  if (gp > 1024) gp = 1024;
+  if (F.mu) hipLaunchKernelGGL(fe_init_kernel<true>, dim3(gp), dim3(256), 0, s, F, theta0);
+  else hipLaunchKernelGGL(fe_init_kernel<false>, dim3(gp), dim3(256), 0, s, F, theta0);
+  HIP_TRY(hipGetLastError());
+  p->timed = false;
+  p->dirty = false;
+  p->gen = 0u;
+  p->seq = 0;
+  p->evals = 0;
   return GDMIX_RE_OK;
 }
 
@@ -1354,6 +1433,7 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   p->compress = FE_COMPRESS_DEFAULT;
   if (const char* e = getenv("GDMIX_FE_COMPRESS")) p->compress = atoi(e) & 3;
   p->hot_mem = nullptr;
+  p->prior_mem = nullptr;
   p->timed = false;
   p->dirty = false;      // the pool is zeroed at creation
   for (auto& e : p->ev) e = nullptr;
@@ -1373,6 +1453,7 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   const int ic = opts->has_intercept ? 1 : 0;
   F.n = (int)b->N; F.z = b->Z; F.d = (int)b->D; F.ic = ic; F.D = num_features; F.P = (int)num_features + ic; F.m = opts->m;
   F.y = b->y; F.o = b->offset; F.w = b->weight; F.umap = b->unique_global;
+  F.mu = nullptr; F.sc = nullptr;
   SolveParams& o = p->o;
   o.l2 = opts->l2; o.ftol = opts->ftol; o.pgtol = opts->pgtol; o.threshold = 0.0; o.regularize_bias = opts->regularize_bias;
   o.has_intercept = ic; o.m = opts->m; o.max_iter = opts->max_iter; o.maxfun = opts->maxfun; o.maxls = opts->maxls;
@@ -1432,16 +1513,14 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   F.sync = reinterpret_cast<FeSync*>(base + o_sync);
   int gp = (int)((P + 255) / 256);
   if (gp > 1024) gp = 1024;
-  hipLaunchKernelGGL(fe_init_kernel, dim3(gp), dim3(256), 0, s, F, theta0);
+  hipLaunchKernelGGL(fe_init_kernel<false>, dim3(gp), dim3(256), 0, s, F, theta0);
   rc = hipGetLastError();
   if (rc != hipSuccess) { set_error("launch failed: %s", hipGetErrorString(rc)); fe_free(p); return GDMIX_RE_EHIP; }
   *out = p;
   return GDMIX_RE_OK;
 }
 
-// The problem as gdmix_fe_create leaves it, for other options and another start point (include/gdmix_fe.h): the pool is zeroed again
-// but for the list of row blocks with several units, F.inv refilled, the start point and a fresh L-BFGS state written by the same
-// fe_init_kernel, the host's counters put back. Everything is enqueued behind whatever the stream still holds of the last solve.
+// The problem as gdmix_fe_create leaves it, for other options and another start point (include/gdmix_fe.h): fe_reset above.
 GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, const double* theta0, void* stream) {
   if (!p || !opts) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
   const FeDev& F = p->F;
@@ -1456,20 +1535,41 @@ GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, c
   SolveParams& o = p->o;
   o.l2 = opts->l2; o.ftol = opts->ftol; o.pgtol = opts->pgtol; o.regularize_bias = opts->regularize_bias;
   o.max_iter = opts->max_iter; o.maxfun = opts->maxfun; o.maxls = opts->maxls;
-  char* base = static_cast<char*>(p->pool);
-  HIP_TRY(hipMemsetAsync(base, 0, p->pool_multi, s));
-  HIP_TRY(hipMemsetAsync(base + p->pool_multi_end, 0, p->pool_bytes - p->pool_multi_end, s));
-  HIP_TRY(hipMemsetAsync(base + p->pool_inv, 0xff, (size_t)F.P * 4, s));
+  return fe_reset(p, theta0, s);
+}
+
+GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const double* scale, void* stream) {
+  if (!p) { set_error("problem is NULL"); return GDMIX_RE_EINVAL; }
+  if ((mean == nullptr) != (scale == nullptr)) { set_error("gdmix_fe_set_prior: mean and scale are given together, or both NULL"); return GDMIX_RE_EINVAL; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(p->ctx->impl.device));
+  FeDev& F = p->F;
+  if (!mean) {
+    F.mu = nullptr; F.sc = nullptr;      // (the copy stays allocated: kernels of an earlier solve may still be queued on it)
+    return fe_reset(p, nullptr, s);
+  }
+  const size_t P = (size_t)F.P;
+  if (!p->prior_mem) {
+    void* mem = nullptr;
+    const hipError_t rc = hipMalloc(&mem, 2 * P * 8 + 64);
+    if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", 2 * P * 8 + 64, hipGetErrorString(rc)); return GDMIX_RE_ENOMEM; }
+    p->prior_mem = static_cast<double*>(mem);
+  }
+  // the caller's scale is checked before the problem's copy — a prior an earlier call installed — is overwritten
+  int32_t* bad_dev = reinterpret_cast<int32_t*>(p->prior_mem + 2 * P);
   int gp = (F.P + 255) / 256;
   if (gp > 1024) gp = 1024;
-  hipLaunchKernelGGL(fe_init_kernel, dim3(gp), dim3(256), 0, s, F, theta0);
+  HIP_TRY(hipMemsetAsync(bad_dev, 0, sizeof(int32_t), s));
+  hipLaunchKernelGGL(fe_prior_check_kernel, dim3(gp), dim3(256), 0, s, scale, F.P, bad_dev);
   HIP_TRY(hipGetLastError());
-  p->timed = false;
-  p->dirty = false;
-  p->gen = 0u;
-  p->seq = 0;
-  p->evals = 0;
-  return GDMIX_RE_OK;
+  int32_t bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, bad_dev, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));      // the one wait of this call
+  if (bad) { set_error("gdmix_fe_set_prior: every scale must be finite and > 0"); return GDMIX_RE_EINVAL; }
+  HIP_TRY(hipMemcpyAsync(p->prior_mem, mean, P * 8, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(p->prior_mem + P, scale, P * 8, hipMemcpyDeviceToDevice, s));
+  F.mu = p->prior_mem; F.sc = p->prior_mem + P;
+  return fe_reset(p, nullptr, s);
 }
 
 GDMIX_API void gdmix_fe_destroy(gdmix_fe_problem* p) {
@@ -1488,7 +1588,7 @@ GDMIX_API int gdmix_fe_eval(gdmix_fe_problem* p, void* stream) {
   // the first two evaluations of a problem are timed (gdmix_fe_last_eval_ms reports the second): with the status read a few steps
   // late the LAST evaluations of a solve are no-ops
   const bool timed = p->evals < 2;
-  const int rc = fe_passes<false>(p, p->F, static_cast<hipStream_t>(stream), timed);
+  const int rc = fe_passes<false>(p, p->F, static_cast<hipStream_t>(stream), timed, p->F.mu != nullptr);
   if (rc == GDMIX_RE_OK) { if (timed) p->timed = true; ++p->evals; }
   return rc;
 }
@@ -1498,7 +1598,8 @@ GDMIX_API int gdmix_fe_hessian_diag(gdmix_fe_problem* p, const double* theta, vo
   FeDev F = p->F;
   if (theta) F.W.x = const_cast<double*>(theta);   // the passes only read x
   p->dirty = true;   // (a step enqueued behind the stop leaves the buffer as it was)
-  return fe_passes<true>(p, F, static_cast<hipStream_t>(stream), false);
+  // theta is in theta units whatever the problem holds: only the current point of a problem with a prior is phi
+  return fe_passes<true>(p, F, static_cast<hipStream_t>(stream), false, !theta && F.mu != nullptr);
 }
 
 GDMIX_API size_t gdmix_fe_hessian_dense_scratch_bytes(const gdmix_re_packed* shard) {
@@ -1538,12 +1639,15 @@ static int fe_enqueue_step(gdmix_fe_problem* p, hipStream_t s) {
     if (g < 1) g = 1;
     ++p->gen;
     if (p->gen == 0u) ++p->gen;
-    hipLaunchKernelGGL(fe_tail_kernel, dim3(g), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev, p->gen);
+    if (F.mu) hipLaunchKernelGGL(fe_tail_kernel<true>, dim3(g), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev, p->gen);
+    else hipLaunchKernelGGL(fe_tail_kernel<false>, dim3(g), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev, p->gen);
   } else {
-    hipLaunchKernelGGL(fe_dots_kernel, dim3(dot_blocks), dim3(FE_THREADS), 0, s, F, p->o);
+    if (F.mu) hipLaunchKernelGGL(fe_dots_kernel<true>, dim3(dot_blocks), dim3(FE_THREADS), 0, s, F, p->o);
+    else hipLaunchKernelGGL(fe_dots_kernel<false>, dim3(dot_blocks), dim3(FE_THREADS), 0, s, F, p->o);
     hipLaunchKernelGGL(fe_step_kernel, dim3(1), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev);
     if (gp > 1024) gp = 1024;
-    hipLaunchKernelGGL(fe_update_kernel, dim3(gp), dim3(256), 0, s, F, p->o.m);
+    if (F.mu) hipLaunchKernelGGL(fe_update_kernel<true>, dim3(gp), dim3(256), 0, s, F, p->o.m);
+    else hipLaunchKernelGGL(fe_update_kernel<false>, dim3(gp), dim3(256), 0, s, F, p->o.m);
   }
   p->dirty = false;
   HIP_TRY(hipGetLastError());
@@ -1610,7 +1714,14 @@ GDMIX_API int gdmix_fe_result(gdmix_fe_problem* p, double* theta, double* fval, 
                               void* stream) {
   if (!p) { set_error("problem is NULL"); return GDMIX_RE_EINVAL; }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (theta) HIP_TRY(hipMemcpyAsync(theta, p->F.W.x, (size_t)p->F.P * 8, hipMemcpyDeviceToDevice, s));
+  if (theta && p->F.mu) {
+    int gp = (p->F.P + 255) / 256;
+    if (gp > 1024) gp = 1024;
+    hipLaunchKernelGGL(fe_prior_theta_kernel, dim3(gp), dim3(256), 0, s, p->F, theta);
+    HIP_TRY(hipGetLastError());
+  } else if (theta) {
+    HIP_TRY(hipMemcpyAsync(theta, p->F.W.x, (size_t)p->F.P * 8, hipMemcpyDeviceToDevice, s));
+  }
   CompactState S;
   HIP_TRY(hipMemcpyAsync(&S, p->F.state, sizeof(S), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

@@ -12,7 +12,8 @@ gdmix_amd/fixed_effect.py. Same constructor, attributes, train / predict / expor
 
 Training with W > 1 workers: every worker runs this with torch.distributed initialised; gradient and value are
 all-reduced once per L-BFGS evaluation (fixed_effect.py: run_stepping_loop), the step is replicated.
-Not carried over: fixed_effect_variance_mode (rejected), copy_to_local and the TF server knobs (accepted, unused).
+Not carried over: copy_to_local and the TF server knobs (accepted, unused). fixed_effect_variance_mode is carried over: SIMPLE and FULL
+are computed on the training data after the fit and written next to the means (fixed_effect._variances).
 
 Not in the reference, one worker only (both refused with several, before anything is read):
   --metric_output_dir=DIR   everything the stage scores is also fed, from HBM, into an exact AUC (logistic_regression) or MSE
@@ -22,6 +23,12 @@ Not in the reference, one worker only (both refused with several, before anythin
        weight a cold gdmix_fe_restart + solve, the validation shard scored under all the models in one pass over its non-zeros
        (gdmix_fe_score_models), one exact metric per weight, the files of sweep.py under DIR/sweep/. The winner's coefficients then go
        through the rest of train() as if fit_stepping had returned them: the stage's files are those of a plain run at that weight.
+Not in the reference either, any number of workers:
+  --incremental_training=True   with a prior model in output_model_dir the L2 term is centred on its means and weighted by its precisions
+       (the variances --fixed_effect_variance_mode wrote into the same file; 1 where there is none), the fit starts at the prior means, and
+       the variances written are the posterior's: training on a new day's data alone is the Bayesian update of yesterday's model
+       (include/gdmix_fe.h, "incremental training"; the reference leaves it open, :361-367). Every worker reads the same model file.
+       Without a prior model the stage is a plain cold run. Refused with --l2_reg_weights and with --action=inference.
 """
 import glob
 import logging
@@ -60,6 +67,9 @@ class FixedLRParams(LRParams):
     # a sweep over l2_reg_weight inside the stage; l2_reg_weight is ignored when the list is given
     metric_output_dir: Optional[str] = None
     l2_reg_weights: Optional[str] = None
+    # not in the reference (which leaves it open, fixed_effect_lr_lbfgs_model.py:361-367); the random-effect stage's flag of the same
+    # name (params.REParams): the L2 term centred on the prior model in output_model_dir and weighted by its precisions
+    incremental_training: bool = False
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -68,6 +78,8 @@ class FixedLRParams(LRParams):
     def __post_init__(self):
         super().__post_init__()
         self.l2_grid()      # a bad list is an error at parse time
+        if self.incremental_training and self.l2_reg_weights is not None:
+            raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         assert self.fixed_effect_variance_mode is None or self.fixed_effect_variance_mode in (constants.FULL, constants.SIMPLE), \
             f"Action: {self.fixed_effect_variance_mode} must be in {(constants.FULL, constants.SIMPLE)}"
 
@@ -308,12 +320,24 @@ class FixedEffectLRModelLBFGS:
             vdata = self._read(validation_data_dir, num_workers, task_index, schema_params)
             theta, info = self._sweep(data, vdata, grid)
         else:
-            prev_model = self._load_model(catch_exception=True)
+            incremental = bool(self.model_params.incremental_training)
+            prev_model = self._load_model(catch_exception=True, with_variance=incremental)
+            prev_var = None
+            if incremental and prev_model is not None:
+                prev_model, prev_var = prev_model
             expected = self.num_features + 1 if self.has_intercept else self.num_features
-            x0 = None
+            x0 = prior = None
             if prev_model is not None and len(prev_model) == expected:
-                logger.info("Found a previous model, loaded as the initial point for training")
                 x0 = np.asarray(prev_model, np.float64)
+                if incremental:
+                    # the L2 term is centred on the prior model (include/gdmix_fe.h, "incremental training"); the fit starts at its means
+                    logger.info("Found a previous model, loaded as the prior of incremental training")
+                    if prev_var is None:
+                        logger.info("The previous model carries no variances: every prior variance defaults to 1")
+                    prior = (x0 if bag else x0[1:], prev_var if (bag or prev_var is None) else prev_var[1:])
+                    x0 = None
+                else:
+                    logger.info("Found a previous model, loaded as the initial point for training")
             elif prev_model is not None:
                 logger.info(f"Initial model size is {len(prev_model)}, expected {expected}, use all zeros instead.")
             theta, info = self._solver().fit_stepping(
@@ -321,7 +345,7 @@ class FixedEffectLRModelLBFGS:
                 has_intercept=self.has_intercept, l2=self.l2_reg_weight, regularize_bias=self.is_regularize_bias,
                 model_type=self.model_type, theta0=self._strip_dummy(x0) if not bag else x0, max_iter=self.max_iteration,
                 m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
-                variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold)
+                variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold, **({} if prior is None else {"prior": prior}))
         self.variances = info.pop("variances", None)
         if not bag and self.variances is not None:
             self.variances = np.concatenate([[0.0], self.variances])   # next to the dummy weight of an intercept-only model
@@ -433,8 +457,10 @@ class FixedEffectLRModelLBFGS:
         enc = [avro.enc_string(n) + avro.enc_string(t) for (n, t) in fl]
         return (fl, native_reader.EncodedFeatures(enc) if native_reader.available() else enc)
 
-    def _load_model(self, catch_exception=False):
-        """-> coefficients [num_features (+1, intercept last)] or None (:730-747, load_linear_models_from_avro)."""
+    def _load_model(self, catch_exception=False, with_variance=False):
+        """-> coefficients [num_features (+1, intercept last)] or None (:730-747, load_linear_models_from_avro). with_variance: ->
+        (coefficients, variances | None) — the record's variances mapped by the same join, 0 where the record has none for a coefficient
+        (fixed_effect.usable_variance puts the default in), None for a record without variances."""
         if not (self.checkpoint_path and os.path.exists(self.checkpoint_path)):
             if catch_exception:
                 return None
@@ -446,24 +472,34 @@ class FixedEffectLRModelLBFGS:
             raise ValueError(f"Load model failed, no model file or multiple model files found in the model directory {self.checkpoint_path}")
         D = self.num_features
         ic = 1 if self.has_intercept else 0
-        theta = self._load_model_native(files[0], D, ic)
+        theta = self._load_model_native(files[0], D, ic, with_variance=with_variance)
         if theta is not None:
             return theta
+        return self._load_model_python(files[0], D, ic, with_variance=with_variance)
+
+    def _load_model_python(self, path, D, ic, with_variance=False):
+        """The record-by-record decoder with the reference's lenient rules: every file the native reader declines."""
         from .io.features import get_feature_map
         fmap = get_feature_map(self.feature_file) if self.feature_file else {}
-        rec = next(iter(avro.read_file(files[0])))
-        theta = np.zeros(D + ic)
-        for m in rec["means"]:
-            if m["name"] == constants.INTERCEPT and m["term"] == "":
-                if ic:
-                    theta[D] = m["value"]
-            else:
-                j = fmap.get((m["name"], m["term"]))
-                if j is not None and j < D:
-                    theta[j] = m["value"]
-        return theta
+        rec = next(iter(avro.read_file(path)))
 
-    def _load_model_native(self, path, D, ic):
+        def joined(triples):
+            out = np.zeros(D + ic)
+            for m in triples:
+                if m["name"] == constants.INTERCEPT and m["term"] == "":
+                    if ic:
+                        out[D] = m["value"]
+                else:
+                    j = fmap.get((m["name"], m["term"]))
+                    if j is not None and j < D:
+                        out[j] = m["value"]
+            return out
+        theta = joined(rec["means"])
+        if not with_variance:
+            return theta
+        return theta, None if rec.get("variances") is None else joined(rec["variances"])
+
+    def _load_model_native(self, path, D, ic, with_variance=False):
         """The same coefficients through libgdmix_io.so (a million (name, term, value) triples decode in milliseconds instead
         of seconds); None when the file is not of the plain layout this trainer and photon-ml write — intercept first, every
         feature in the feature file — and the record-by-record Python decoder has to apply the reference's lenient rules."""
@@ -487,7 +523,14 @@ class FixedEffectLRModelLBFGS:
         theta = np.zeros(D + ic)
         theta[D] = m["mean"][c0]
         theta[idx] = m["mean"][c0 + 1:c1]      # of a feature listed twice the later value, as the Python loop leaves it
-        return theta
+        if not with_variance:
+            return theta
+        if m["variance"] is None or not m["has_variance"][0]:
+            return theta, None
+        var = np.zeros(D + ic)
+        var[D] = m["variance"][c0]
+        var[idx] = m["variance"][c0 + 1:c1]
+        return theta, var
 
     def export(self, output_model_dir):
         logger.info("No need model export for LR model.")
@@ -496,6 +539,9 @@ class FixedEffectLRModelLBFGS:
     def predict(self, output_dir, input_data_path, metadata_file, checkpoint_path, execution_context, schema_params):
         task_index = execution_context[constants.TASK_INDEX]
         num_workers = execution_context[constants.NUM_WORKERS]
+        if self.model_params.incremental_training:
+            raise ValueError("--incremental_training does not run with --action inference: it defines how a model is trained, scoring reads "
+                             "the model as it is")
         self.check_request(execution_context, constants.ACTION_INFERENCE)      # (--l2_reg_weights is ignored here)
         self._begin_metrics()
         data = self._read(input_data_path, num_workers, task_index, schema_params)

@@ -162,13 +162,17 @@ class FixedEffectDeviceSolver:
 
     def fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
                      regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
-                     group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0):
+                     group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0, prior=None):
         """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
         worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
         model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
-        hold no non-zero, so that its all-reduce buffer has the same num_features + 2 entries as everyone else's."""
+        hold no non-zero, so that its all-reduce buffer has the same num_features + 2 entries as everyone else's.
+        prior = (mean, variance), each in theta0's layout: incremental training (include/gdmix_fe.h, "incremental training") — the L2
+        term is centred on `mean` and weighted by 1 / variance (1 where a variance is not finite or <= 0), the fit starts at `mean`
+        (theta0 must be None), and the variances returned are the posterior's. Every worker passes the same prior."""
         opts = fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance)
-        fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode)
+        fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode,
+                           prior=prior)
         theta, info = fit.stage_result(*fit.run(), l2, threshold)
         if return_problem:
             return theta, info, fit.prob
@@ -324,6 +328,17 @@ class _SteppingProblem:
                                               self.solver._stream()), "gdmix_fe_restart")
         self.theta0 = theta0_dev      # kept alive: a kernel on the stream reads it
 
+    def set_prior(self, mean_dev=None, scale_dev=None):
+        """gdmix_fe_set_prior: float64 device tensors [D + has_intercept], intercept last (copied by the library); None, None removes the
+        prior. Leaves the problem as a restart with its current options at phi = 0 does."""
+        for x in (mean_dev, scale_dev):
+            if x is not None and (not x.is_cuda or x.dtype != self.solver.torch.float64 or not x.is_contiguous() or x.numel() != self.count - 1):
+                from .solver import GdmixReError
+                raise GdmixReError(f"a prior vector is a contiguous float64 device array of {self.count - 1} entries (intercept last)")
+        self._check(self.lib.gdmix_fe_set_prior(self._h, None if mean_dev is None else mean_dev.data_ptr(),
+                                                None if scale_dev is None else scale_dev.data_ptr(), self.solver._stream()), "gdmix_fe_set_prior")
+        self.theta0 = None
+
     def reduce_tensor(self):
         """The [gradient, value] buffer as a torch tensor view (no copy), for torch.distributed.all_reduce."""
         t = self.solver.torch
@@ -446,8 +461,11 @@ class _SteppingFit:
     """What a fit through include/gdmix_fe.h needs around its loop: the shard as a packed one-entity batch, the problem (gdmix_fe_create)
     and the all-reduce of this process group; then the loop, and the result as the stage takes it."""
 
-    def __init__(self, solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode):
+    def __init__(self, solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode,
+                 prior=None):
         ic = 1 if opts.has_intercept else 0
+        if prior is not None and theta0 is not None:
+            raise ValueError("a fit with a prior starts at the prior mean: theta0 must be None")
         self.batch, self.dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, opts.has_intercept,
                                                 binary_labels=not opts.linear, dummy=dummy)
         D = 1 if self.dummy else int(num_features)   # the dummy zero feature of an intercept-only model occupies global index 0
@@ -469,6 +487,11 @@ class _SteppingFit:
                 full[:] = th
             t0 = solver.torch.from_numpy(full).to(solver.device)
         self.prob = _SteppingProblem(solver, self.packed, D, opts, t0)
+        self.prior_scale = None
+        if prior is not None:
+            mean, self.prior_scale = prior_vectors(prior[0], prior[1], D, ic, self.dummy, opts.regularize_bias)
+            up = lambda a: solver.torch.from_numpy(a).to(solver.device)
+            self.prob.set_prior(up(mean), up(self.prior_scale))
         self.all_reduce = None
         try:
             import torch.distributed as dist
@@ -505,7 +528,7 @@ class _SteppingFit:
             o = self.opts
             info["variances"] = self.strip_dummy(_variances(self.solver, self.prob, self.batch, th, self.D, o.has_intercept, float(l2), o.regularize_bias,
                                                             str(self.variance_mode).upper(), self.all_reduce, self.group, packed=self.packed,
-                                                            dummy=self.dummy))
+                                                            dummy=self.dummy, scale=self.prior_scale))
         return self.strip_dummy(theta), info
 
 
@@ -540,11 +563,66 @@ def check_variance_request(mode, P, num_workers):
                          "coefficients (use SIMPLE for larger models)")
 
 
-def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias, mode, all_reduce, group, packed=None, dummy=False):
+def usable_variance(v):
+    """Prior variances with the default put in: 1 where the variance is missing (0 after the join), not finite or <= 0 (model.usable_variance)."""
+    v = np.asarray(v, np.float64)
+    return np.where(np.isfinite(v) & (v > 0.0), v, 1.0)
+
+
+def prior_vectors(mean, variance, D, ic, dummy, regularize_bias):
+    """(mean, scale = sqrt(variance)) [D + ic] as gdmix_fe_set_prior takes them, from a prior in theta0's layout (a dummy model's: the
+    intercept alone; the dummy feature gets mean 0, scale 1). variance None: every variance 1. An unregularised intercept has no penalty:
+    its scale is 1 and its mean is only where the fit starts (include/gdmix_fe.h, "The intercept")."""
+    P = D + ic
+    mu, v = np.zeros(P), np.ones(P)
+    m_in = np.asarray(mean, np.float64)
+    v_in = np.ones(m_in.size) if variance is None else usable_variance(variance)
+    if m_in.size != (ic if dummy else P) or v_in.size != m_in.size:
+        raise ValueError(f"a prior has {ic if dummy else P} means and as many variances (intercept last), not {m_in.size} and {v_in.size}")
+    if dummy:
+        mu[D:], v[D:] = m_in, v_in
+    else:
+        mu[:], v[:] = m_in, v_in
+    if not np.all(np.isfinite(mu)):
+        raise ValueError("a prior mean is not finite")
+    if ic and not regularize_bias:
+        v[D] = 1.0
+    return mu, np.sqrt(v)
+
+
+def simple_variances(H, l2, ic, regularize_bias, scale=None):
+    """SIMPLE variances from the diagonal H of X~' D X~ (intercept last): 1 / (H_j + l2 [j regularised] + 1e-12); with a prior of scale s
+    the same in phi-space mapped back, s_j^2 / (s_j^2 H_j + l2 [j regularised] + 1e-12)."""
+    eps = 1.0e-12
+    reg = np.full(H.size, float(l2))
+    if ic and not regularize_bias:
+        reg[-1] = 0.0
+    if scale is None:
+        return 1.0 / (H + reg + eps)
+    s2 = np.asarray(scale, np.float64) ** 2
+    return s2 / (s2 * H + reg + eps)
+
+
+def full_variances_of(H, l2, ic, regularize_bias, scale=None):
+    """FULL variances from the dense X~' D X~ (intercept last): diag((H + (l2 + 1e-12) I - l2 e_u e_u')^-1), u an unregularised intercept;
+    with a prior of scale s, s_j^2 diag((S H S + (l2 + 1e-12) I - l2 e_u e_u')^-1)_j = diag((H + diag((l2 [regularised] + 1e-12) / v))^-1)."""
+    eps = 1.0e-12
+    P = H.shape[0]
+    reg = np.full(P, float(l2) + eps)
+    if ic and not regularize_bias:
+        reg[-1] -= l2
+    if scale is not None:
+        reg = reg / (np.asarray(scale, np.float64) ** 2)
+    return np.diagonal(np.linalg.inv(H + np.diag(reg))).copy()
+
+
+def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias, mode, all_reduce, group, packed=None, dummy=False, scale=None):
     """variance of every coefficient (intercept last). SIMPLE: 1 / (diag(X~' D X~) + l2 [regularised] + 1e-12), the diagonal by two
     more streaming passes on the device and the same all-reduce as an evaluation. FULL: diag((X~' D X~ + (l2 + 1e-12) I - l2
     [intercept unregularised])^-1): the dense matrix is built on the host from the shard (scipy), summed over the workers and
-    inverted with numpy, exactly as the reference does (:296-305, 457-463) — only sensible for small feature spaces."""
+    inverted with numpy, exactly as the reference does (:296-305, 457-463) — only sensible for small feature spaces.
+    scale: the prior scale [D + ic] of an incremental fit (include/gdmix_fe.h, "incremental training"): the same mode applied in phi-space
+    to S H S and mapped back, Var(theta_j) = s_j^2 Var'(phi_j); theta is theta, and the curvature the device returns is theta-space's."""
     eps = 1.0e-12
     ic = 1 if has_intercept else 0
     P = D + ic
@@ -555,6 +633,8 @@ def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias
         if all_reduce is not None:
             all_reduce(buf)
         H = buf[:P].cpu().numpy().copy()
+        if scale is not None:
+            return simple_variances(H, l2, ic, regularize_bias, scale)
         H += l2
         if ic and not regularize_bias:
             H[-1] -= l2
@@ -562,8 +642,9 @@ def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias
     if mode != "FULL":
         raise ValueError(f"unknown variance mode {mode!r}")
     check_variance_request(mode, P, _world_size(group))
-    if P > FULL_VARIANCE_HOST_MAX and _world_size(group) > 1:
-        return _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2, regularize_bias, group, dummy)
+    if P > FULL_VARIANCE_HOST_MAX and (_world_size(group) > 1 or scale is not None):
+        # (with a prior any number of workers: the one-worker shortcut below, solver.variance_full, knows no prior)
+        return _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2, regularize_bias, group, dummy, scale=scale)
     if P > FULL_VARIANCE_HOST_MAX:
         # on the device, in the shard's local index space (intercept first): the random-effect FULL variance of a one-entity
         # batch is this very matrix (binary_logistic_regression.py:181-187 = fixed_effect_lr_lbfgs_model.py:296-305, 457-463).
@@ -600,15 +681,18 @@ def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias
                 H = ht.numpy()
     except ImportError:
         pass
+    if scale is not None:
+        return full_variances_of(H, l2, ic, regularize_bias, scale)
     H = H + np.diag([l2 + eps] * P)
     if ic and not regularize_bias:
         H[-1, -1] -= l2
     return np.diagonal(np.linalg.inv(H)).copy()
 
 
-def _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2, regularize_bias, group, dummy=False):
+def _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2, regularize_bias, group, dummy=False, scale=None):
     """FULL variances on the device with the Hessian summed over the workers (fixed_effect_lr_lbfgs_model.py:291-305, 384-389,
-    457-463). Coefficient order: features 0 .. D-1, intercept last."""
+    457-463). Coefficient order: features 0 .. D-1, intercept last. scale: the prior scale of an incremental fit — rows and columns of
+    the summed matrix are scaled by it (S H S), the variances of that by s^2; with it also the route of a single worker."""
     import torch
     import torch.distributed as dist
     ic = 1 if has_intercept else 0
@@ -634,12 +718,19 @@ def _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2,
         idx = torch.cat([torch.full((ic,), D, dtype=torch.int64, device=solver.device), uniq_dev.to(torch.int64)])   # local -> global coefficient
         Hg.index_put_((idx[:, None], idx[None, :]), Hl[:p_l, :p_l])       # one 2-D scatter into the common index space
         del Hl
-    if dist.get_backend(group) == "nccl":
+    if _world_size(group) == 1:
+        pass
+    elif dist.get_backend(group) == "nccl":
         dist.all_reduce(Hg, group=group)
     else:      # (gloo: the two-worker tests on one device)
         h = Hg.cpu()
         dist.all_reduce(h, group=group)
         Hg = h.to(solver.device)
     unreg = D if (ic and not regularize_bias) else -1
-    return solver.variance_of_hessian(Hg, P, l2, unreg).cpu().numpy()
+    if scale is None:
+        return solver.variance_of_hessian(Hg, P, l2, unreg).cpu().numpy()
+    s = torch.from_numpy(np.ascontiguousarray(scale, np.float64)).to(solver.device)
+    Hg[:P, :P] *= s[:, None]
+    Hg[:P, :P] *= s[None, :]
+    return (solver.variance_of_hessian(Hg, P, l2, unreg) * s * s).cpu().numpy()
 

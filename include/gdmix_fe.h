@@ -122,6 +122,54 @@ GDMIX_API int gdmix_fe_score(gdmix_re_ctx* ctx, int64_t n, const int64_t* row_nn
  * bits as gdmix_fe_create with those options and that start point followed by the same solve. */
 GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, const double* theta0, void* stream);
 
+/* ---- (ABI 17) incremental training: the L2 term centred on a prior model and weighted by its precisions ---------------------------
+ * The fixed-effect half of gdmix_re.h's section of the same name (--incremental_training True, gdmix_amd/fe_model.py; the reference
+ * leaves it open: fixed_effect_lr_lbfgs_model.py:361-367). A warm start alone forgets the prior model once it converges: with l2 > 0 the
+ * optimum does not depend on the start point.
+ *
+ * Definition. theta = [w (D), b], intercept last; coefficient j has a prior mean mu_j and a prior variance v_j, s_j = sqrt(v_j); R = the
+ * regularised coefficients: every j < D, and the intercept iff regularize_bias:
+ *     F(theta) = sum_i w_i l(y_i, x_i . w + b + offset_i) + (l2/2) sum_{j in R} (theta_j - mu_j)^2 / v_j
+ * not divided by n (the fixed effect's convention), l the logistic or the squared loss (opts->linear) as without a prior.
+ * The prior is global. It applies to every coefficient of the model, whether or not this worker's shard holds a non-zero in that
+ * column: a coefficient no worker has data for stays at its prior mean, exactly.
+ * Defaults (the caller's, gdmix_amd/fe_model.py; those of the random effect). mu_j = 0 where the prior file has no mean for j — a
+ * coefficient thresholded out of the file counts as missing —, v_j = 1 where the variance is missing, not finite or <= 0. A prior file
+ * without variances gives (l2/2) |theta_R - mu_R|^2.
+ * The intercept. Unlike the random effect's kernels, nothing here pins the intercept column: a regularised intercept's prior variance is
+ * honoured like any other. An unregularised intercept has no penalty: the caller passes s_D = 1, and mu_D is only where it starts.
+ * Substitution. The optimiser works in phi_j = (theta_j - mu_j) / s_j, from phi = 0:
+ *     penalty (l2/2) |phi_R|^2,   grad_phi = s (.) grad_theta,   theta_j = mu_j + s_j phi_j
+ * The shard is NOT transformed (as csrc/re_prior.hip does for the random effect: a rounding per non-zero and a second copy of the
+ * values). The problem already keeps the trial point in two places — the global x and the shard-local copy the row pass gathers from
+ * — and consumes the reduced data gradient coefficient by coefficient, so the change of variables costs work per coefficient, none per
+ * non-zero, and rounds no data:
+ *     x holds phi; wherever the shard-local copy of coefficient j is written it gets mu_j + s_j phi_j (one fma);
+ *     the row pass's intercept is mu_D + s_D phi_D;
+ *     the step scales the reduced data gradient, fg[j] * s_j (rounded on its own), before it adds the regulariser l2 phi_j. The
+ *       all-reduce between evaluation and step is untouched and carries the theta-space data gradient: every worker scales after the
+ *       reduce and computes the same step;
+ *     gdmix_fe_result returns theta = mu + s (.) phi.
+ * Each is a compile-time variant of its kernel; a problem without a prior runs the instantiations without, instruction for instruction
+ * what it ran before. mu = 0, s = 1 makes every added operation exact: the bits of a problem without a prior.
+ * Consequences.
+ *   stop tests  pgtol, ftol and every other stop test of L-BFGS-B apply in phi-space: |s (.) grad_theta F|_inf <= pgtol; gdmix_fe_result's
+ *               gnorm is |grad_phi|_inf. fval is F; nit, nfev and status are those of the solve in phi.
+ *   threshold   the sparsity threshold (the caller's) applies to theta, not to phi.
+ *   variances   gdmix_fe_hessian_diag takes theta (NULL: the current point, mapped) and returns theta-space curvature, as before. The
+ *               caller maps: Var(theta_j) = s_j^2 Var'(phi_j), Var' the stage's variance mode applied to H' = S H S —
+ *               SIMPLE  s_j^2 / (s_j^2 H_jj + l2 [j in R] + 1e-12),
+ *               FULL    s_j^2 diag((S H S + (l2 + 1e-12) I - l2 e_u e_u')^-1)_j, u an unregularised intercept.
+ *
+ * gdmix_fe_set_prior: mean / scale device pointers [D + has_intercept], intercept last; `scale` arrives computed (the host takes the
+ *   square root: caller and device use the same bits). Both are copied into the problem: the caller may free them once the stream has
+ *   passed the call. NULL, NULL removes the prior. Either way the call leaves the problem in the state of a gdmix_fe_restart with its
+ *   current options at phi = 0 (theta = mu; without a prior: zeros). Stream-ordered. Every scale must be finite and > 0: a kernel checks
+ *   the caller's array and the host reads its verdict back — the one place the call waits — before anything of the problem is touched;
+ *   GDMIX_RE_EINVAL otherwise, the problem as it was.
+ *   While a prior is installed gdmix_fe_restart's theta0 is in theta units: NULL means mu, otherwise phi0 = (theta0 - mu) / s. */
+GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const double* scale, void* stream);
+
 /* gdmix_fe_score under K coefficient vectors in ONE pass over the shard's non-zeros (csrc/fe_sweep.hip). thetas: HOST array of K device
  * pointers, each [num_features + has_intercept] with the intercept last; score / per_coord: [K][n] float, row k for thetas[k]
  * (per_coord may be NULL). Defined by equivalence: row k is bit for bit what gdmix_fe_score writes for thetas[k] — a row's products
