@@ -32,99 +32,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-// Size classes in routing order (see re_internal.hpp). A 64-thread workgroup may use up to 64 KiB of LDS
-// here; larger blocks go to the workgroup-per-entity kernel.
-struct ClassDesc { int kind; int lds; const char* name; int ncap, zcap; };   // quad: lds = LDS of a whole wave (4 rows)
-static const ClassDesc kClasses[GDMIX_RE_NUM_CLASSES] = {
-    {KIND_QUAD2, 1, "re_solve_grp_kernel<16,2> n<=16 nnz<=64", 16, 64},     {KIND_QUAD2, 1, "re_solve_grp_kernel<16,2> n<=32 nnz<=128", 32, 128},
-    {KIND_QUAD2, 1, "re_solve_grp_kernel<16,2> n<=128 nnz<=512", 128, 512},
-    {KIND_QUAD3, 1, "re_solve_grp_kernel<16,3> n<=16 nnz<=64", 16, 64},     {KIND_QUAD3, 1, "re_solve_grp_kernel<16,3> n<=32 nnz<=128", 32, 128},
-    {KIND_QUAD3, 1, "re_solve_grp_kernel<16,3> n<=128 nnz<=512", 128, 512},
-    {KIND_QUAD4, 1, "re_solve_grp_kernel<16,4> n<=16 nnz<=64", 16, 64},     {KIND_QUAD4, 1, "re_solve_grp_kernel<16,4> n<=32 nnz<=128", 32, 128},
-    {KIND_QUAD4, 1, "re_solve_grp_kernel<16,4> n<=128 nnz<=512", 128, 512},
-    {KIND_PAIR3, 1, "re_solve_grp_kernel<32,3> n<=32 nnz<=128", 32, 128},   {KIND_PAIR3, 1, "re_solve_grp_kernel<32,3> n<=64 nnz<=256", 64, 256},
-    {KIND_PAIR3, 1, "re_solve_grp_kernel<32,3> n<=256 nnz<=1024", 256, 1024},
-    {KIND_PAIR4, 1, "re_solve_grp_kernel<32,4> n<=32 nnz<=128", 32, 128},   {KIND_PAIR4, 1, "re_solve_grp_kernel<32,4> n<=64 nnz<=256", 64, 256},
-    {KIND_PAIR4, 1, "re_solve_grp_kernel<32,4> n<=256 nnz<=1024", 256, 1024},
-    {KIND_G64_3, 1, "re_solve_grp_kernel<64,3> n<=64 nnz<=512", 64, 512},    {KIND_G64_3, 1, "re_solve_grp_kernel<64,3> n<=512 nnz<=2048", 512, 2048},
-    {KIND_G64_4, 1, "re_solve_grp_kernel<64,4> n<=64 nnz<=512", 64, 512},    {KIND_G64_4, 1, "re_solve_grp_kernel<64,4> n<=512 nnz<=2048", 512, 2048},
-    {KIND_G128_3, 1, "re_solve_grp_kernel<128,3> n<=128 nnz<=1024", 128, 1024}, {KIND_G128_3, 1, "re_solve_grp_kernel<128,3> n<=1024 nnz<=3072", 1024, 3072},
-    {KIND_G128_4, 1, "re_solve_grp_kernel<128,4> n<=128 nnz<=1024", 128, 1024}, {KIND_G128_4, 1, "re_solve_grp_kernel<128,4> n<=1024 nnz<=3072", 1024, 3072},
-    {KIND_G256_3, 1, "re_solve_grp_kernel<256,3> n<=256 nnz<=2048", 256, 2048}, {KIND_G256_3, 1, "re_solve_grp_kernel<256,3> n<=2048 nnz<=4096", 2048, 4096},
-    {KIND_G256_4, 1, "re_solve_grp_kernel<256,4> n<=256 nnz<=2048", 256, 2048}, {KIND_G256_4, 1, "re_solve_grp_kernel<256,4> n<=2048 nnz<=4096", 2048, 4096},
-    {KIND_G512_4, 1, "re_solve_grp_kernel<512,4> n<=512 nnz<=4096", 512, 4096},
-    {KIND_WLDS, 24576, "re_solve_wave_kernel lds<=24K"},     {KIND_WLDS, 65536, "re_solve_wave_kernel lds<=64K"},
-    {KIND_TALL_T, 0, "re_solve_tall_team_kernel<8> x4 p<=64"},
-    {KIND_TALL_L, 0, "re_solve_tall_kernel<1> lean p<=64"},
-    {KIND_TALL_S, 0, "re_solve_tall_kernel<1> p<=64"},
-    {KIND_TALL_M, 0, "re_solve_tall_kernel<4> p<=64"},
-    {KIND_TALL, 0, "re_solve_tall_kernel<8> p<=64"},
-    {KIND_BLOCK, 0, "re_solve_team_kernel workgroup"},
-    {KIND_GRID, 0, "re_solve_team_kernel 128 teams"},
-    {KIND_GRID, 0, "re_solve_team_kernel 32 teams"},
-    {KIND_GRID, 0, "re_solve_team_kernel 8 teams"},
-    {KIND_GRID, 0, "re_solve_team_kernel device-wide"}};
-
-__global__ void class_base_kernel(int32_t* cc, int tall_adapt_limit, int tall_adapt_small, int tall_team_n, int tall_team_limit, int tall_mid_n) {
-  // cc[0..NC) counts -> cc[NC..2NC) exclusive bases, cc[2NC..3NC) cursors = 0
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    // The split between the one-wavefront and the eight-wavefront tall kernels (4 096 samples by default: right for a batch with
-    // thousands of tall entities, where a CU is better spent on eight entities than on one) is lowered for a batch whose
-    // eight-wavefront class stays small anyway — a share of a strongly scaled job: 17 k users, 5 - 11 of them above 4 096 samples, and
-    // the step lasts as long as ONE wavefront needs for a 4 000-sample entity (tools/share_timeline.py). The lowest of 512 / 1 024 /
-    // 2 048 that keeps the class within `tall_adapt_limit` workgroups (one per CU) wins; re_order_kernel moves the entities.
-    int32_t* const ge = cc + 3 * GDMIX_RE_NUM_CLASSES;
-    // The team class (four workgroups per entity) takes the tallest entities of the batch: those above the lowest of
-    // tall_team_n x {1, 2, 4} samples that keeps it within one round of teams — a batch with more than that above the highest
-    // threshold has no team class (throughput binds it, not one entity's chain). No limit: everything from tall_team_n on.
-    int team_from = 0;
-    if (tall_team_n > 0) {
-      if (tall_team_limit <= 0) { if (ge[TALL_TEAM_GE] > 0) team_from = tall_team_n; }
-      else
-        for (int k = 0; k < TALL_TEAM_STEPS && team_from == 0; ++k)
-          if (ge[TALL_TEAM_GE + k] > 0 && ge[TALL_TEAM_GE + k] <= tall_team_limit) team_from = tall_team_n << k;
-      if (team_from > 0) {
-        const int moved = ge[TALL_TEAM_GE + (team_from == tall_team_n ? 0 : (team_from == 2 * tall_team_n ? 1 : 2))];
-        cc[TALL_T_CLASS] += moved;
-        cc[TALL_CLASS] -= moved;
-      }
-    }
-    ge[TALL_TEAM_SLOT] = team_from;
-    // ... and only for a batch whose one-wavefront class is small itself (at most `tall_adapt_small` entities: two rounds of its launch):
-    // a whole population is bound by throughput, where the one-wavefront kernel is the better use of a CU (MovieLens-20M per user on one
-    // GPU, 14 k such entities: 8.9 ms with the split at 4 096, 9.4 ms when 224 more entities took a CU each)
-    int split = 0;
-    if (tall_adapt_limit > 0 && cc[TALL_S_CLASS] <= tall_adapt_small) {
-      for (int k = 0; k < TALL_ADAPT_STEPS && split == 0; ++k)
-        if (ge[k] > 0 && cc[TALL_CLASS] + ge[k] <= tall_adapt_limit) {
-          split = tall_adapt_n(k);
-          cc[TALL_CLASS] += ge[k];
-          cc[TALL_S_CLASS] -= ge[k];
-        }
-    }
-    ge[TALL_ADAPT_SLOT] = split;
-    // The mid class (four wavefronts per entity, two workgroups per CU) takes the largest one-wavefront entities BELOW the split: the
-    // lowest threshold of tall_mid_step() that keeps it within one round of its launch (-tall_mid_n workgroups), in a small batch only
-    // (same test as the split: a whole population is bound by throughput). tall_mid_n > 0: everything from that many samples on.
-    int mid_from = 0;
-    // entities of at least `split` samples have left the one-wavefront class (counted with the same rule: ge[k] of the chosen split)
-    const int gone = split > 0 ? ge[split == tall_adapt_n(0) ? 0 : (split == tall_adapt_n(1) ? 1 : 2)] : 0;
-    if (tall_mid_n > 0) {
-      const int cnt = (split > 0 && split <= tall_mid_n) ? 0 : ge[TALL_MID_GE] - gone;
-      if (cnt > 0) { mid_from = tall_mid_n; cc[TALL_M_CLASS] += cnt; cc[TALL_S_CLASS] -= cnt; }
-    } else if (tall_mid_n < 0 && cc[TALL_S_CLASS] <= tall_adapt_small) {
-      for (int k = 0; k < TALL_MID_STEPS && mid_from == 0; ++k) {
-        if (split > 0 && tall_mid_step(k) >= split) break;
-        const int cnt = ge[TALL_MID_GE + k] - gone;
-        if (cnt > 0 && cnt <= -tall_mid_n) { mid_from = tall_mid_step(k); cc[TALL_M_CLASS] += cnt; cc[TALL_S_CLASS] -= cnt; }
-      }
-    }
-    ge[TALL_MID_SLOT] = mid_from;
-    int run = 0;
-    for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c) { cc[GDMIX_RE_NUM_CLASSES + c] = run; run += cc[c]; cc[2 * GDMIX_RE_NUM_CLASSES + c] = 0; }
-  }
-}
-
 __global__ __launch_bounds__(WAVE) void publish_kernel(const uint32_t* __restrict__ src, int words, uint32_t* box_data, uint32_t* box_flag, uint32_t seq) {
   // Write-through stores (system scope, relaxed) to the page-locked box, a wait until they are acknowledged, then the flag the same
   // way. NOT a system-scope release: that writes back this XCD's whole L2 first, behind whatever kernels are filling it at the
@@ -392,30 +299,12 @@ ScopedGridGate::~ScopedGridGate() {
 
 extern "C" {
 
-// A class whose launch cannot fill the device: fewer wavefronts than three quarters of what the CUs hold at two per SIMD (the eight-wavefront
-// tall workgroups: fewer entities than CUs). Such a class runs on one of the context's side streams, next to the large ones and to
-// the other small ones.
-// Large classes are dealt over the caller's stream and the side streams, in launch order (round 4): side by side their tails overlap
-// — a class launch ends with the workgroups whose entities need the most iterations while the rest of the device idles — and
-// wavefronts of different classes share a SIMD. C2: 9.35 -> 8.93 ms of solve, step 10.70 -> 10.30 ms; MovieLens-20M per-movie 6.04 -> 5.70 ms
-// (tools/r04_spread.sh: 2 / 3 / 4 queues 10.44 / 10.31 / 10.30 ms; most-entities-first changes nothing). gdmix_re_set_spread(ctx, 0)
-// (GDMIX_RE_SPREAD=0 for a whole process): one after another on the caller's stream, as before (A/B, and the per-kernel durations of a
-// profile: overlapped kernels stretch each other).
+// how many queues the large classes of a solve are dealt over (plan_launches, re_route.hip; GDMIX_RE_SPREAD=0 for a whole process: one)
 static int spread_default() {
   const char* e = getenv("GDMIX_RE_SPREAD");
   const int n = e ? atoi(e) : 4;
   return n > 1 ? n : 0;
 }
-static bool class_is_small(int kind, int count, int num_cus) {
-  const int gl = group_lanes(kind);
-  long waves = count;                                   // wavefront kernels, one-wavefront tall variants
-  if (kind == KIND_TALL_T) return true;                // at most one round of teams
-  if (kind == KIND_TALL) waves = (long)count * 4 * TALL_NW / 8;   // one workgroup per CU: count < num_cus
-  if (kind == KIND_TALL_M) waves = (long)count * 8 / TALL_MID_WGS;   // two workgroups per CU
-  else if (gl > 0) waves = gl >= WAVE ? (long)count * (gl / WAVE) : ((long)count * gl + WAVE - 1) / WAVE;
-  return waves < (long)num_cus * 6;
-}
-
 GDMIX_API int gdmix_re_abi_version(void) { return GDMIX_RE_ABI_VERSION; }
 
 // Test hooks of the inter-process chain of persistent grids (host only, no device): the lock a device named `key` would use.
@@ -543,7 +432,7 @@ GDMIX_API int gdmix_re_create(int hip_device, gdmix_re_ctx** out) {
       }
     }
   }
-  rc = hipMalloc(&c->impl.grid_sync, TEAM_MAX_TEAMS * sizeof(TeamSync) + TALL_VARIANTS * TALL_TAIL_BYTES + TALL_TEAM_BYTES);
+  rc = hipMalloc(&c->impl.grid_sync, GridSyncLayout::BYTES);
   if (rc != hipSuccess) {
     set_error("hipMalloc failed: %s", hipGetErrorString(rc));
     (void)hipHostFree(c->impl.host_pinned);
@@ -763,6 +652,121 @@ static int run_variance_full(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
   return GDMIX_RE_OK;
 }
 
+}  // extern "C"
+
+// ---- the steps of gdmix_re_solve, in the order it takes them (after make_class_table, route: re_route.hip) ----------------------
+namespace {
+
+// scratch slots of the workgroup-per-entity and team kernels
+struct Slots { double* scratch = nullptr; size_t doubles = 0; int n = 0; };
+
+int size_slots(const gdmix_ctx_impl* ci, const gdmix_re_packed* b, const gdmix_re_opts* opts, int n_slot_users, Slots* out) {
+  if (n_slot_users <= 0) return GDMIX_RE_OK;
+  out->n = slots_for(b, opts, &out->doubles);
+  const size_t need = (size_t)out->n * out->doubles * 8;
+  if (ci->scratch && ci->scratch_bytes >= need) out->scratch = static_cast<double*>(ci->scratch);
+  else if (b->scratch && b->scratch_bytes >= need) out->scratch = static_cast<double*>(b->scratch);
+  else {
+    // shrink the slot count to what is available rather than failing, but never below one slot
+    size_t avail = ci->scratch ? ci->scratch_bytes : 0;
+    void* base = ci->scratch;
+    if (b->scratch_bytes > avail) { avail = b->scratch_bytes; base = b->scratch; }
+    out->n = (int)(avail / (out->doubles * 8));
+    if (out->n < 1) {
+      set_error("%d entities need a scratch slot: provide >= %zu bytes via gdmix_re_set_scratch", n_slot_users, out->doubles * 8);
+      return GDMIX_RE_ENOMEM;
+    }
+    out->scratch = static_cast<double*>(base);
+  }
+  return GDMIX_RE_OK;
+}
+
+// One class's launch on stream s, between the events gdmix_re_last_solve_ms reads when timing is on.
+template <class F>
+int timed(gdmix_ctx_impl* ci, int c, hipStream_t s, F&& launch) {
+  if (ci->timing) HIP_TRY(hipEventRecord(ci->ev0[c], s));
+  const hipError_t rc = launch();
+  if (rc != hipSuccess) { set_error("launch of class %d (%s) failed: %s", c, kClasses[c].name, hipGetErrorString(rc)); return GDMIX_RE_EHIP; }
+  if (ci->timing) { HIP_TRY(hipEventRecord(ci->ev1[c], s)); ci->ev_used[c] = true; }
+  return GDMIX_RE_OK;
+}
+
+// a class below the block class: the kernel of its kind
+hipError_t launch_class(const gdmix_ctx_impl* ci, const gdmix_re_packed* b, const BatchDev& B, const OutDev& O, const SolveParams& P,
+                        const double* theta0, const Launch& L, int lean_merged, hipStream_t s) {
+  const ClassDesc& d = kClasses[L.c];
+  switch (d.kind) {
+    case KIND_WLDS:
+      return launch_solve_wave(B, O, P, theta0, L.begin, L.count, d.lds, s);
+    case KIND_TALL_T: {
+      const char* xe = getenv("GDMIX_RE_XCD_BARRIER");   // 0: every signal with the full release (A/B and tests)
+      return launch_solve_tall_team(B, O, P, theta0, L.begin, L.count, ci->num_cus, b->Z, GridSyncLayout::tall_tail(ci, d.tall_variant),
+                                    GridSyncLayout::tall_team_buf(ci), (xe && atoi(xe) == 0) ? 0 : 1, s);
+    }
+    case KIND_TALL_L: case KIND_TALL_S: case KIND_TALL_M: case KIND_TALL:
+      return launch_solve_tall(d.tall_variant, B, O, P, theta0, L.begin, L.count, ci->num_cus, b->Z, GridSyncLayout::tall_tail(ci, d.tall_variant),
+                               GridSyncLayout::tall_ticket(ci, d.tall_variant), d.kind == KIND_TALL_S ? lean_merged : 0, s);
+    default:   // the group kinds
+      return d.lanes > 0 ? launch_solve_quad(d.lanes, d.epl, B, O, P, theta0, L.begin, L.count, d.ncap, d.zcap, s) : hipErrorInvalidValue;
+  }
+}
+
+// Team count of a tier: the longest solve on its team should take about as long as the whole tier on the device, i.e.
+// teams ~ total work / largest entity's work (non-zeros as the measure), within what the tier allows: few large
+// entities get large teams (the critical path matters), many small ones small teams (the barriers do).
+int team_count(int tier_max, unsigned long long total_nnz, unsigned long long largest_nnz, int entities, int slots, int num_cus) {
+  // teams ~ total work / largest entity's work, as a power of two: rounded down when the tier has many entities (the
+  // barriers of many small teams are the cost); a tier of a handful of entities gets about one team per entity (5
+  // entities of 0.2 .. 0.9 M non-zeros: 9.4 ms on one team of 256 CUs, 6.5 ms on four of 64; a makespan model with
+  // fixed per-CU constants did worse than these two rules on the larger tiers)
+  const unsigned long long ratio = largest_nnz ? total_nnz / largest_nnz : 1;
+  int teams = 1;
+  while (teams * 2 <= tier_max && (unsigned long long)(teams * 2) <= ratio) teams *= 2;
+  if (entities <= 16) {   // a handful: one team per entity, as far as a power of two, the tier and 4x the rule above allow
+    // (powers of two keep a team on few XCDs: 6 entities on 6 teams of 42 CUs, each spread over all eight XCDs, took 39 ms
+    // against 28 ms on 4 teams of 64)
+    int want = 1;
+    while (want * 2 <= entities && want * 2 <= tier_max && want * 2 <= teams * 4) want *= 2;
+    if (want > teams) teams = want;
+  }
+  if (const char* ev = getenv("GDMIX_RE_TEAMS")) teams = atoi(ev);   // exploration knob
+  if (teams > TEAM_MAX_TEAMS) teams = TEAM_MAX_TEAMS;
+  while (teams > 1 && (slots < teams || num_cus % teams)) teams >>= 1;
+  return teams < 1 ? 1 : teams;
+}
+
+// The classes that work out of scratch slots, one after another on the caller's stream: the workgroup class, the team tiers (after
+// the workgroup kernel on the same stream, so its slots are free again), the device-wide class.
+int launch_slot_classes(gdmix_ctx_impl* ci, const gdmix_re_packed* b, const ClassCounts& hc, const BatchDev& B, OutDev O, const SolveParams& P,
+                        const double* theta0, const Slots& slots, int n_slot_users, hipStream_t s) {
+  // squared loss, SIMPLE variance: the compact-form team kernels hold both losses and their epilogue is the logistic one. They get no
+  // variance pointer; re_variance_simple_lin_kernel fills these classes' entities in behind them (re_solve.hip)
+  const bool lin_var = P.linear && P.variance_mode == GDMIX_RE_VAR_SIMPLE && P.m <= TEAM_MCAP;
+  double* const variance = O.variance;
+  if (lin_var) O.variance = nullptr;
+  if (hc.count[BLOCK_CLASS] > 0) {
+    const int rc = timed(ci, BLOCK_CLASS, s, [&] {
+      return launch_solve_block(B, O, P, theta0, hc.base[BLOCK_CLASS], hc.count[BLOCK_CLASS], slots.scratch, slots.doubles, slots.n, b->max_p, s);
+    });
+    if (rc != GDMIX_RE_OK) return rc;
+  }
+  for (int c = TEAM128_CLASS; c <= GIANT_CLASS; ++c) {
+    if (hc.count[c] <= 0) continue;
+    const int tier_max = c == TEAM128_CLASS ? 128 : (c == TEAM32_CLASS ? 32 : 8);
+    const int teams = c == GIANT_CLASS ? 1 : team_count(tier_max, hc.team_nnz_total[c], (unsigned long long)hc.largest_nnz(c), hc.count[c], slots.n, ci->num_cus);
+    const int rc = timed(ci, c, s, [&] {
+      return launch_solve_grid(B, O, P, theta0, hc.base[c], hc.count[c], slots.scratch, slots.doubles, b->max_p, GridSyncLayout::team_sync(ci), ci->num_cus, teams, s);
+    });
+    if (rc != GDMIX_RE_OK) return rc;
+  }
+  if (lin_var) HIP_TRY(launch_variance_simple_lin(B, P, variance, hc.base[BLOCK_CLASS], n_slot_users, ci->num_cus, s));
+  return GDMIX_RE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const gdmix_re_opts* opts, const double* theta0,
                    const gdmix_re_result* out, void* stream) {
   if (!ctx || !b || !opts || !out) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
@@ -779,253 +783,59 @@ GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
   }
   if (opts->variance_mode != GDMIX_RE_VAR_NONE && !out->variance) { set_error("variance requested but out->variance is NULL"); return GDMIX_RE_EINVAL; }
   if (b->E == 0) return GDMIX_RE_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(hipSetDevice(ctx->impl.device));
-  const int ic = opts->has_intercept ? 1 : 0;
+  gdmix_ctx_impl* const ci = &ctx->impl;
+  hipStream_t const s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(ci->device));
 
   ClassTable tab;
-  for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c) {
-    tab.kind[c] = kClasses[c].kind;
-    tab.ncap[c] = kClasses[c].ncap;
-    tab.zcap[c] = kClasses[c].zcap;
-    int lds = kClasses[c].lds;
-    const int gl = group_lanes(kClasses[c].kind);
-    if (lds > 0 && gl > 0)
-      lds = (gl >= WAVE ? 1 : WAVE / gl) * quad_layout(gl * group_epl(kClasses[c].kind), kClasses[c].ncap, kClasses[c].zcap, gl > WAVE ? gl / WAVE : 1).bytes;
-    bool on = lds > 0 && (lds <= ctx->impl.wave_lds_limit || (gl > WAVE && ctx->impl.wave_lds_limit >= 65536 && lds <= 160 * 1024));
-    if (gl > 0 && !(ctx->impl.kernel_mask & 4)) on = false;
-    if (kClasses[c].kind == KIND_WLDS && !(ctx->impl.kernel_mask & 2)) on = false;
-    tab.lds_bytes[c] = on ? lds : 0;
-  }
-  // the compact-form team kernels keep TEAM_MCAP history pairs
-  tab.giant_nnz = opts->m <= TEAM_MCAP ? ctx->impl.giant_nnz : 0;
-  tab.team_nnz = opts->m <= TEAM_MCAP ? ctx->impl.team_nnz : 0;
-  tab.tall_min_n = ctx->impl.tall_min_n;
-  tab.tall_split_n = ctx->impl.tall_split_n;
-  tab.tall_adapt_limit = ctx->impl.tall_split_set ? 0 : ctx->impl.tall_adapt_limit;   // an explicit split is kept, whatever its value
-  {   // > 0: adaptive from team_n on; < 0: everything from -team_n on (tests); never below TALL_TEAM_MIN_N samples
-    const int tn = ctx->impl.tall_team_n;
-    tab.tall_team_n = tn > 0 ? tn : -tn;
-    if (tab.tall_team_n > 0 && tab.tall_team_n < TALL_TEAM_MIN_N) tab.tall_team_n = TALL_TEAM_MIN_N;
-    tab.tall_team_limit = tn > 0 ? ctx->impl.tall_team_limit : 0;
-  }
-  // the mid class adapts with the split: a caller who pinned the split (gdmix_re_set_tall_split_n) pinned the routing — no per-batch class
-  tab.tall_mid_n = (ctx->impl.tall_mid_n < 0 && ctx->impl.tall_split_set) ? 0 : ctx->impl.tall_mid_n;
-  if (opts->sum_loss) {
-    // the fixed-effect objective lives in the team kernels only: every entity goes device-wide, one after another
-    if (opts->m > TEAM_MCAP) { set_error("sum_loss needs m <= %d", TEAM_MCAP); return GDMIX_RE_EINVAL; }
-    if (opts->variance_mode != GDMIX_RE_VAR_NONE) { set_error("variance is not available with sum_loss"); return GDMIX_RE_EINVAL; }
-    tab.giant_nnz = 1;
-  }
-  // linear without sum_loss is the random effect's squared loss: the normal class table, every launcher picks its <LIN> kernels by P.linear
-
-  int32_t* cc = b->class_count;
-  HIP_TRY(hipMemsetAsync(cc, 0, 6 * GDMIX_RE_NUM_CLASSES * sizeof(int32_t), s));
-  HIP_TRY(launch_classify(b, ic, opts->m, tab, b->cls_tmp, cc, s));
-  hipLaunchKernelGGL(class_base_kernel, dim3(1), dim3(1), 0, s, cc, tab.tall_adapt_limit, 16 * ctx->impl.num_cus, tab.tall_team_n, tab.tall_team_limit, tab.tall_mid_n);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(launch_order(b, b->cls_tmp, cc + GDMIX_RE_NUM_CLASSES, cc + 2 * GDMIX_RE_NUM_CLASSES, s));
-  int32_t* hc = ctx->impl.host_pinned + 256;
-  HIP_TRY(fetch_small(&ctx->impl, 0, cc, 6 * GDMIX_RE_NUM_CLASSES * sizeof(int32_t), hc, s));
+  int rc = make_class_table(ci, opts, &tab);
+  if (rc != GDMIX_RE_OK) return rc;
+  const ClassCounts* hc = nullptr;
+  rc = route(ci, b, tab, opts, s, &hc);
+  if (rc != GDMIX_RE_OK) return rc;
 
   SolveParams P;
   P.l2 = opts->l2; P.ftol = opts->ftol; P.pgtol = opts->pgtol; P.threshold = opts->threshold;
-  P.regularize_bias = opts->regularize_bias; P.has_intercept = ic; P.m = opts->m; P.max_iter = opts->max_iter;
+  P.regularize_bias = opts->regularize_bias; P.has_intercept = opts->has_intercept ? 1 : 0; P.m = opts->m; P.max_iter = opts->max_iter;
   P.maxfun = opts->maxfun; P.maxls = opts->maxls; P.variance_mode = opts->variance_mode;
   P.sum_loss = opts->sum_loss ? 1 : 0; P.linear = opts->linear ? 1 : 0;
-  BatchDev B = batch_dev(b);
-  OutDev O{out->theta, out->theta_thr, out->variance, out->fval, out->gnorm, out->nit, out->nfev, out->status};
+  const BatchDev B = batch_dev(b);
+  const OutDev O{out->theta, out->theta_thr, out->variance, out->fval, out->gnorm, out->nit, out->nfev, out->status};
+  for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c) ci->ev_used[c] = false;
 
-  const bool timing = ctx->impl.timing != 0;
-  for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c) ctx->impl.ev_used[c] = false;
-  // scratch slots of the workgroup-per-entity and team kernels
-  size_t slot_doubles = 0;
-  int slots = 0;
-  double* slot_scratch = nullptr;
-  const int n_slot_users = hc[BLOCK_CLASS] + hc[TEAM128_CLASS] + hc[TEAM32_CLASS] + hc[TEAM8_CLASS] + hc[GIANT_CLASS];
-  if (n_slot_users > 0) {
-    slots = slots_for(b, opts, &slot_doubles);
-    size_t need = (size_t)slots * slot_doubles * 8;
-    if (ctx->impl.scratch && ctx->impl.scratch_bytes >= need) slot_scratch = static_cast<double*>(ctx->impl.scratch);
-    else if (b->scratch && b->scratch_bytes >= need) slot_scratch = static_cast<double*>(b->scratch);
-    else {
-      // shrink the slot count to what is available rather than failing, but never below one slot
-      size_t avail = ctx->impl.scratch ? ctx->impl.scratch_bytes : 0;
-      void* base = ctx->impl.scratch;
-      if (b->scratch_bytes > avail) { avail = b->scratch_bytes; base = b->scratch; }
-      slots = (int)(avail / (slot_doubles * 8));
-      if (slots < 1) {
-        set_error("%d entities need a scratch slot: provide >= %zu bytes via gdmix_re_set_scratch", n_slot_users, slot_doubles * 8);
-        return GDMIX_RE_ENOMEM;
-      }
-      slot_scratch = static_cast<double*>(base);
-    }
-  }
-  // A lean tall class of a few thousand entities is not worth a launch of its own (a launch lasts at least one entity's solve and
-  // ends in a thin tail): it then runs with the class behind it — its entities sit right in front of that class's in `order`, and
-  // the general one-wavefront kernel takes any of them. An entity's result does not depend on which of the two ran it: same
-  // accumulator sets, same order of the adds (the variants differ in where loads are issued and in occupancy only).
+  int n_slot_users = 0;
+  for (int c = BLOCK_CLASS; c <= GIANT_CLASS; ++c) n_slot_users += hc->count[c];
+  Slots slots;
+  rc = size_slots(ci, b, opts, n_slot_users, &slots);
+  if (rc != GDMIX_RE_OK) return rc;
+
   int lean_rounds = 4;   // (GDMIX_RE_LEAN_MERGE_ROUNDS: exploration knob)
   if (const char* ev = getenv("GDMIX_RE_LEAN_MERGE_ROUNDS")) lean_rounds = atoi(ev);
-  const int lean_merged = (hc[TALL_L_CLASS] > 0 && hc[TALL_L_CLASS] < lean_rounds * ctx->impl.num_cus * TALL_LEAN_WGS) ? hc[TALL_L_CLASS] : 0;
-  int n_launch_classes = 0;
-  for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c) n_launch_classes += (hc[c] > 0 && !(c == TALL_L_CLASS && lean_merged)) ? 1 : 0;
-  hipStream_t const s_main = s;
-  // the side stream starts where the caller's stream stands now (the class lists are ready), not where it stands when the first
-  // small class comes up in the loop: that one may be the last
-  // Once the side stream has forked, EVERY way out of this function joins it back into the caller's stream (an error
+  const LaunchPlan plan = plan_launches(*hc, ci->num_cus, ci->n_side, ci->spread, lean_rounds);
+  // the side streams start where the caller's stream stands now (the class lists are ready), not where it stands when the first
+  // class of theirs comes up in the loop: that one may be the last
+  // Once they have forked, EVERY way out of this function joins them back into the caller's stream (an error
   // between fork and join used to return with side-stream kernels still running on buffers the caller may then free or reuse).
-  SideJoin side_join{&ctx->impl, s_main};
-  bool forked = false;
-  if (ctx->impl.n_side > 0 && n_launch_classes > 1) {
-    for (int c = 0; c < BLOCK_CLASS && !forked; ++c) {
-      int cnt = hc[c];
-      if (c == TALL_L_CLASS && lean_merged) continue;
-      if (c == TALL_S_CLASS) cnt += lean_merged;
-      forked = cnt > 0 && class_is_small(kClasses[c].kind, cnt, ctx->impl.num_cus);
-    }
-    if (ctx->impl.spread > 1) forked = true;
-    if (forked) HIP_TRY(hipEventRecord(ctx->impl.side_fork, s_main));
-  }
-  // Launch plan. The tall classes go first: their kernels are the longest chains of a small batch (one workgroup, or one wavefront,
-  // per entity, for as long as that entity's solve lasts) and each is preceded by three small launches (fill, sort, tail) that must
-  // not queue behind the group kernels' workgroups. Stream of a class:
-  //   large class                      -> dealt over the caller's stream and the side streams in launch order (gdmix_re_set_spread);
-  //   small tall class (<8>, <1>, lean) -> a side stream of its own (side 1, 2, 0: the device has four hardware queues by default,
-  //                                        a fourth side stream would share one — measured: both tall classes of a MovieLens share on
-  //                                        one queue, 1.1 + 2.1 ms one after the other);
-  //   other small classes              -> the caller's stream when no large class uses it, else side 0 (behind the lean tall class,
-  //                                        the shortest of the three).
-  // Only the streams that get work are woken (SideJoin::use): a C2 partition touches the caller's stream and side 0.
-  // Disjoint entities and outputs; the tall variants have a tail slot each: a schedule changes the time, never a bit of the result.
-  struct Launch { int c, b0, cnt; bool small; int spread; };
-  Launch plan[GDMIX_RE_NUM_CLASSES];
-  int n_plan = 0;
-  bool any_large = false;
-  {
-    int begin = 0;
-    int b0s[GDMIX_RE_NUM_CLASSES], cnts[GDMIX_RE_NUM_CLASSES];
-    for (int c = 0; c < BLOCK_CLASS; ++c) {
-      b0s[c] = begin; cnts[c] = hc[c];
-      begin += hc[c];
-      if (c == TALL_L_CLASS && lean_merged) cnts[c] = 0;
-      if (c == TALL_S_CLASS && lean_merged) { b0s[c] -= lean_merged; cnts[c] += lean_merged; }
-    }
-    const int first[5] = {TALL_T_CLASS, TALL_CLASS, TALL_M_CLASS, TALL_S_CLASS, TALL_L_CLASS};
-    for (int k = 0; k < 5 + BLOCK_CLASS; ++k) {
-      const int c = k < 5 ? first[k] : k - 5;
-      if (k >= 5 && (c == TALL_T_CLASS || c == TALL_CLASS || c == TALL_M_CLASS || c == TALL_S_CLASS || c == TALL_L_CLASS)) continue;
-      if (cnts[c] <= 0) continue;
-      const bool small = forked && class_is_small(kClasses[c].kind, cnts[c], ctx->impl.num_cus);
-      any_large = any_large || !small;
-      plan[n_plan++] = Launch{c, b0s[c], cnts[c], small, -1};
-    }
-  }
-  int begin = 0;
-  int spread_rr = 0;
-  for (int c = 0; c < BLOCK_CLASS; ++c) begin += hc[c];
-  for (int k = 0; k < n_plan; ++k) {
-    const int c = plan[k].c, b0 = plan[k].b0, cnt = plan[k].cnt;
-    hipStream_t s = s_main;
-    if (!plan[k].small && forked && ctx->impl.spread > 1) {   // large classes side by side
-      const int nq = ctx->impl.spread < ctx->impl.n_side + 1 ? ctx->impl.spread : ctx->impl.n_side + 1;
-      const int q = spread_rr++ % nq;
-      if (q > 0) { HIP_TRY(side_join.use(q - 1)); s = ctx->impl.side[q - 1]; }
-    }
-    if (plan[k].small) {
-      const int ns = ctx->impl.n_side;
-      int k_side = -1;
-      if (c == TALL_CLASS) k_side = 1 % ns;
-      else if (c == TALL_S_CLASS) k_side = 2 % ns;
-      else if (c == TALL_M_CLASS && !any_large) k_side = -1;      // the caller's stream, ahead of the group classes (three side streams: a fourth would share a hardware queue)
-      else if (c == TALL_T_CLASS || c == TALL_L_CLASS || any_large) k_side = 0;
-      if (k_side >= 0) { HIP_TRY(side_join.use(k_side)); s = ctx->impl.side[k_side]; }
-    }
-    if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev0[c], s)); }
-    switch (kClasses[c].kind) {
-      case KIND_QUAD2: case KIND_QUAD3: case KIND_QUAD4: case KIND_PAIR3: case KIND_PAIR4:
-      case KIND_G64_3: case KIND_G64_4: case KIND_G128_3: case KIND_G128_4: case KIND_G256_3: case KIND_G256_4: case KIND_G512_4:
-        HIP_TRY(launch_solve_quad(group_lanes(kClasses[c].kind), group_epl(kClasses[c].kind), B, O, P, theta0, b0, cnt,
-                                  kClasses[c].ncap, kClasses[c].zcap, s));
-        break;
-      case KIND_TALL_T: {
-        const char* xe = getenv("GDMIX_RE_XCD_BARRIER");   // 0: every signal with the full release (A/B and tests)
-        HIP_TRY(launch_solve_tall_team(B, O, P, theta0, b0, cnt, ctx->impl.num_cus, b->Z, static_cast<char*>(ctx->impl.grid_sync) + TEAM_MAX_TEAMS * sizeof(TeamSync) + TALL_VARIANT_TEAM * TALL_TAIL_BYTES,
-                                       static_cast<char*>(ctx->impl.grid_sync) + TEAM_MAX_TEAMS * sizeof(TeamSync) + TALL_VARIANTS * TALL_TAIL_BYTES, (xe && atoi(xe) == 0) ? 0 : 1, s));
-        break;
-      }
-      case KIND_TALL_L: HIP_TRY(launch_solve_tall(TALL_VARIANT_LEAN, B, O, P, theta0, b0, cnt, ctx->impl.num_cus, b->Z, static_cast<char*>(ctx->impl.grid_sync) + TEAM_MAX_TEAMS * sizeof(TeamSync) + TALL_VARIANT_LEAN * TALL_TAIL_BYTES, static_cast<TeamSync*>(ctx->impl.grid_sync) + TALL_VARIANT_LEAN, 0, s)); break;
-      case KIND_TALL_S: HIP_TRY(launch_solve_tall(TALL_VARIANT_SMALL, B, O, P, theta0, b0, cnt, ctx->impl.num_cus, b->Z, static_cast<char*>(ctx->impl.grid_sync) + TEAM_MAX_TEAMS * sizeof(TeamSync) + TALL_VARIANT_SMALL * TALL_TAIL_BYTES, static_cast<TeamSync*>(ctx->impl.grid_sync) + TALL_VARIANT_SMALL, lean_merged, s)); break;
-      case KIND_TALL_M: HIP_TRY(launch_solve_tall(TALL_VARIANT_MID, B, O, P, theta0, b0, cnt, ctx->impl.num_cus, b->Z, static_cast<char*>(ctx->impl.grid_sync) + TEAM_MAX_TEAMS * sizeof(TeamSync) + TALL_VARIANT_MID * TALL_TAIL_BYTES, static_cast<TeamSync*>(ctx->impl.grid_sync) + TALL_VARIANT_MID, 0, s)); break;
-      case KIND_TALL: HIP_TRY(launch_solve_tall(TALL_VARIANT_LARGE, B, O, P, theta0, b0, cnt, ctx->impl.num_cus, b->Z, static_cast<char*>(ctx->impl.grid_sync) + TEAM_MAX_TEAMS * sizeof(TeamSync) + TALL_VARIANT_LARGE * TALL_TAIL_BYTES, static_cast<TeamSync*>(ctx->impl.grid_sync) + TALL_VARIANT_LARGE, 0, s)); break;
-      default: HIP_TRY(launch_solve_wave(B, O, P, theta0, b0, cnt, kClasses[c].lds, s)); break;
-    }
-    if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev1[c], s)); ctx->impl.ev_used[c] = true; }
+  SideJoin side_join{ci, s};
+  if (plan.fork) HIP_TRY(hipEventRecord(ci->side_fork, s));
+  for (int k = 0; k < plan.n; ++k) {
+    const Launch& L = plan.launch[k];
+    hipStream_t q = s;
+    if (L.stream >= 0) { HIP_TRY(side_join.use(L.stream)); q = ci->side[L.stream]; }
+    rc = timed(ci, L.c, q, [&] { return launch_class(ci, b, B, O, P, theta0, L, plan.lean_merged, q); });
+    if (rc != GDMIX_RE_OK) return rc;
   }
   side_join.join();   // before the team kernels (they use the whole device and the scratch slots)
-  if (hc[BLOCK_CLASS] > 0 || hc[TEAM128_CLASS] > 0 || hc[TEAM32_CLASS] > 0 || hc[TEAM8_CLASS] > 0 || hc[GIANT_CLASS] > 0) {
-    double* const scratch = slot_scratch;
-    // squared loss, SIMPLE variance: the compact-form team kernels hold both losses and their epilogue is the logistic one. They get no
-    // variance pointer; re_variance_simple_lin_kernel fills these classes' entities in behind them (re_solve.hip)
-    const bool lin_var = P.linear && P.variance_mode == GDMIX_RE_VAR_SIMPLE && opts->m <= TEAM_MCAP;
-    const int lin_var_begin = begin;
-    OutDev O_team = O;
-    if (lin_var) O_team.variance = nullptr;
-    const OutDev& O = O_team;   // (every launch of this block)
-    if (hc[BLOCK_CLASS] > 0) {
-      if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev0[BLOCK_CLASS], s)); }
-      HIP_TRY(launch_solve_block(B, O, P, theta0, begin, hc[BLOCK_CLASS], scratch, slot_doubles, slots, b->max_p, s));
-      if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev1[BLOCK_CLASS], s)); ctx->impl.ev_used[BLOCK_CLASS] = true; }
-      begin += hc[BLOCK_CLASS];
-    }
-    // the team kernels run after the workgroup kernel on the same stream, so its slots are free again
-    for (int tier = 0; tier < 3; ++tier) {
-      const int cls = tier == 0 ? TEAM128_CLASS : (tier == 1 ? TEAM32_CLASS : TEAM8_CLASS);
-      if (hc[cls] <= 0) continue;
-      // Team count: the longest solve on its team should take about as long as the whole tier on the device, i.e.
-      // teams ~ total work / largest entity's work (non-zeros as the measure), within what the tier allows: few large
-      // entities get large teams (the critical path matters), many small ones small teams (the barriers do).
-      const int tier_max = tier == 0 ? 128 : (tier == 1 ? 32 : 8);
-      const unsigned long long tot = reinterpret_cast<const unsigned long long*>(hc + 4 * GDMIX_RE_NUM_CLASSES)[cls];
-      const unsigned long long big = (unsigned long long)hc[3 * GDMIX_RE_NUM_CLASSES + cls];
-      // teams ~ total work / largest entity's work, as a power of two: rounded down when the tier has many entities (the
-      // barriers of many small teams are the cost); a tier of a handful of entities gets about one team per entity (5
-      // entities of 0.2 .. 0.9 M non-zeros: 9.4 ms on one team of 256 CUs, 6.5 ms on four of 64; a makespan model with
-      // fixed per-CU constants did worse than these two rules on the larger tiers)
-      const unsigned long long ratio = big ? tot / big : 1;
-      int teams = 1;
-      while (teams * 2 <= tier_max && (unsigned long long)(teams * 2) <= ratio) teams *= 2;
-      if (hc[cls] <= 16) {   // a handful: one team per entity, as far as a power of two, the tier and 4x the rule above allow
-        // (powers of two keep a team on few XCDs: 6 entities on 6 teams of 42 CUs, each spread over all eight XCDs, took 39 ms
-        // against 28 ms on 4 teams of 64)
-        int want = 1;
-        while (want * 2 <= hc[cls] && want * 2 <= tier_max && want * 2 <= teams * 4) want *= 2;
-        if (want > teams) teams = want;
-      }
-      if (const char* ev = getenv("GDMIX_RE_TEAMS")) teams = atoi(ev);   // exploration knob
-      if (teams > TEAM_MAX_TEAMS) teams = TEAM_MAX_TEAMS;
-      while (teams > 1 && (slots < teams || ctx->impl.num_cus % teams)) teams >>= 1;
-      if (teams < 1) teams = 1;
-      if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev0[cls], s)); }
-      HIP_TRY(launch_solve_grid(B, O, P, theta0, begin, hc[cls], scratch, slot_doubles, b->max_p, ctx->impl.grid_sync,
-                                ctx->impl.num_cus, teams, s));
-      if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev1[cls], s)); ctx->impl.ev_used[cls] = true; }
-      begin += hc[cls];
-    }
-    if (hc[GIANT_CLASS] > 0) {
-      if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev0[GIANT_CLASS], s)); }
-      HIP_TRY(launch_solve_grid(B, O, P, theta0, begin, hc[GIANT_CLASS], scratch, slot_doubles, b->max_p,
-                                ctx->impl.grid_sync, ctx->impl.num_cus, 1, s));
-      if (timing) { HIP_TRY(hipEventRecord(ctx->impl.ev1[GIANT_CLASS], s)); ctx->impl.ev_used[GIANT_CLASS] = true; }
-    }
-    if (lin_var) HIP_TRY(launch_variance_simple_lin(B, P, out->variance, lin_var_begin, n_slot_users, ctx->impl.num_cus, s));
+  if (n_slot_users > 0) {
+    rc = launch_slot_classes(ci, b, *hc, B, O, P, theta0, slots, n_slot_users, s);
+    if (rc != GDMIX_RE_OK) return rc;
   }
   if (opts->variance_mode == GDMIX_RE_VAR_FULL) {
-    const int rc = run_variance_full(ctx, b, B, P, out->theta, out->variance, s);
+    rc = run_variance_full(ctx, b, B, P, out->theta, out->variance, s);
     if (rc != GDMIX_RE_OK) return rc;
   }
   // a pack's deferred compaction ran next to this solve: from here on the caller's stream is behind it, as it is behind the solve
-  HIP_TRY(join_unique(&ctx->impl, s_main));
+  HIP_TRY(join_unique(ci, s));
   return GDMIX_RE_OK;
 }
 

@@ -27,25 +27,17 @@ enum { KIND_WREG1 = 0, KIND_WREG2 = 1, KIND_WREG4 = 2, KIND_WLDS = 3, KIND_BLOCK
        KIND_G64_3 = 11, KIND_G64_4 = 12, KIND_G128_4 = 13, KIND_G256_4 = 14, KIND_G512_4 = 15, KIND_GRID = 16, KIND_G128_3 = 17, KIND_G256_3 = 18,
        KIND_TALL = 20, KIND_TALL_S = 21, KIND_TALL_L = 22, KIND_TALL_T = 23, KIND_TALL_M = 24 };   // (19: the register team kernels of round 2, removed in round 3)
 
-// group kernels (several entities per wavefront): lanes per entity, coefficient slots per lane; 0 if not a group kind
-__host__ __device__ inline int group_lanes(int kind) {
+// group kernels (several entities per wavefront): lanes per entity, coefficient slots per lane; 0 if not a group kind. These two are
+// kClasses' `lanes` and `epl` columns as a function of the kind, for re_classify_kernel (which gets the kinds in its ClassTable argument):
+// compare chains, so that the kernel stays as it is; class_table_consistent() holds them to the table. Host code reads the table.
+__host__ __device__ constexpr int group_lanes(int kind) {
   return (kind == KIND_QUAD2 || kind == KIND_QUAD3 || kind == KIND_QUAD4) ? 16 : ((kind == KIND_PAIR3 || kind == KIND_PAIR4) ? 32 :
          ((kind == KIND_G64_3 || kind == KIND_G64_4) ? 64 : ((kind == KIND_G128_4 || kind == KIND_G128_3) ? 128 : ((kind == KIND_G256_4 || kind == KIND_G256_3) ? 256 : (kind == KIND_G512_4 ? 512 : 0)))));
 }
-__host__ __device__ inline int group_epl(int kind) {
+__host__ __device__ constexpr int group_epl(int kind) {
   return kind == KIND_QUAD2 ? 2 : ((kind == KIND_QUAD3 || kind == KIND_PAIR3 || kind == KIND_G64_3 || kind == KIND_G128_3 || kind == KIND_G256_3) ? 3 : (group_lanes(kind) > 0 ? 4 : 0));
 }
-constexpr int GIANT_CLASS = GDMIX_RE_NUM_CLASSES - 1;   // device-wide kernel, one entity at a time
-constexpr int TEAM8_CLASS = GDMIX_RE_NUM_CLASSES - 2;    // 8 teams of 32 CUs
-constexpr int TEAM32_CLASS = GDMIX_RE_NUM_CLASSES - 3;   // 32 teams of 8 CUs
-constexpr int TEAM128_CLASS = GDMIX_RE_NUM_CLASSES - 4;  // 128 teams of 2 CUs
-constexpr int BLOCK_CLASS = GDMIX_RE_NUM_CLASSES - 5;
-constexpr int TALL_CLASS = BLOCK_CLASS - 1;      // tall entities of at least tall_split_n samples: one workgroup of TALL_NW wavefronts per CU
-constexpr int TALL_M_CLASS = BLOCK_CLASS - 2;    // (round 6) the largest of the smaller ones in a SMALL batch: workgroups of TALL_NW_MID wavefronts, two per CU
-constexpr int TALL_S_CLASS = BLOCK_CLASS - 3;    // smaller ones: workgroups of TALL_NW_SMALL wavefronts, several per CU
-constexpr int TALL_L_CLASS = BLOCK_CLASS - 4;    // ... and those that fit a twelfth of a CU's LDS: the lean variant, three wavefronts per SIMD
-constexpr int TALL_T_CLASS = BLOCK_CLASS - 5;    // the tallest of a batch: TALL_TEAM_C workgroups (CUs of one XCD) share one entity's samples
-constexpr int TALL_TEAM_C = 4;                   // workgroups per entity of that class (fixed: an entity's sums depend on the split)
+constexpr int TALL_TEAM_C = 4;                   // workgroups per entity of the tall team class (fixed: an entity's sums depend on the split)
 constexpr int TALL_TEAM_MAX = 64;                // teams per launch
 constexpr int TALL_TEAM_BYTES = 192 * 1024;      // device buffer of the context: the teams' exchange structures (re_solve_tall.hip)
 constexpr int TALL_TEAM_MIN_N = 64;              // no team for fewer samples than this, whatever the caller asks for (every member gets samples)
@@ -69,7 +61,107 @@ constexpr int TALL_LEAN_ARENA = (tall_lds_bytes(TALL_LEAN_WGS) - 1408) & ~15;   
 __host__ __device__ inline size_t tall_resident_bytes(int nw, int S, int d, int n, int nnz, bool has_w) {
   return (size_t)nw * (d + 1) * (S + 1) * 8 + (size_t)8 * (nnz + 8) + (size_t)4 * (n + 2) + (size_t)(has_w ? 12 : 8) * n + 16;
 }
+
+// ---- the size classes ---------------------------------------------------------------------------------------------------------------
+// One row per class, in routing order (re_classify_kernel takes the first class that holds the entity): the only description of a
+// class. A 64-thread workgroup may use up to 64 KiB of LDS here; larger blocks go to the workgroup-per-entity kernel.
+struct ClassDesc {
+  int kind;
+  int lanes, epl;     // group kernels: lanes per entity, coefficient slots per lane (0: not a group kind)
+  int ncap, zcap;     // group kernels: sample / non-zero capacity of an entity's LDS block
+  int lds;            // LDS bucket of the class: bytes (wavefront kernel); 1 = from the layout of ncap and zcap (group kernels); 0 = none
+  int occ_lanes;      // lanes of the device one entity keeps busy, for class_is_small (0: the class is small whatever it holds)
+  int tall_variant;   // TALL_VARIANT_* of a tall class, -1 for the others
+  int tall_rank;      // the tall classes are launched first, in this order (plan_launches); -1 for the others
+  int small_side;     // side stream of the class when it is small; -1: the caller's stream when no large class uses it, else side 0
+  const char* name;   // gdmix_re_class_kernel_name
+};
 enum { TALL_VARIANT_LARGE = 0, TALL_VARIANT_SMALL = 1, TALL_VARIANT_LEAN = 2, TALL_VARIANT_TEAM = 3, TALL_VARIANT_MID = 4, TALL_VARIANTS = 5 };
+constexpr ClassDesc grp_class(int kind, int lanes, int epl, int ncap, int zcap, const char* name) { return {kind, lanes, epl, ncap, zcap, 1, lanes, -1, -1, -1, name}; }
+constexpr ClassDesc wave_class(int lds, const char* name) { return {KIND_WLDS, 0, 0, 0, 0, lds, WAVE, -1, -1, -1, name}; }
+constexpr ClassDesc tall_class(int kind, int variant, int rank, int occ_lanes, int side, const char* name) { return {kind, 0, 0, 0, 0, 0, occ_lanes, variant, rank, side, name}; }
+constexpr ClassDesc team_class(int kind, const char* name) { return {kind, 0, 0, 0, 0, 0, WAVE, -1, -1, -1, name}; }
+inline constexpr ClassDesc kClasses[GDMIX_RE_NUM_CLASSES] = {
+    grp_class(KIND_QUAD2, 16, 2, 16, 64, "re_solve_grp_kernel<16,2> n<=16 nnz<=64"),
+    grp_class(KIND_QUAD2, 16, 2, 32, 128, "re_solve_grp_kernel<16,2> n<=32 nnz<=128"),
+    grp_class(KIND_QUAD2, 16, 2, 128, 512, "re_solve_grp_kernel<16,2> n<=128 nnz<=512"),
+    grp_class(KIND_QUAD3, 16, 3, 16, 64, "re_solve_grp_kernel<16,3> n<=16 nnz<=64"),
+    grp_class(KIND_QUAD3, 16, 3, 32, 128, "re_solve_grp_kernel<16,3> n<=32 nnz<=128"),
+    grp_class(KIND_QUAD3, 16, 3, 128, 512, "re_solve_grp_kernel<16,3> n<=128 nnz<=512"),
+    grp_class(KIND_QUAD4, 16, 4, 16, 64, "re_solve_grp_kernel<16,4> n<=16 nnz<=64"),
+    grp_class(KIND_QUAD4, 16, 4, 32, 128, "re_solve_grp_kernel<16,4> n<=32 nnz<=128"),
+    grp_class(KIND_QUAD4, 16, 4, 128, 512, "re_solve_grp_kernel<16,4> n<=128 nnz<=512"),
+    grp_class(KIND_PAIR3, 32, 3, 32, 128, "re_solve_grp_kernel<32,3> n<=32 nnz<=128"),
+    grp_class(KIND_PAIR3, 32, 3, 64, 256, "re_solve_grp_kernel<32,3> n<=64 nnz<=256"),
+    grp_class(KIND_PAIR3, 32, 3, 256, 1024, "re_solve_grp_kernel<32,3> n<=256 nnz<=1024"),
+    grp_class(KIND_PAIR4, 32, 4, 32, 128, "re_solve_grp_kernel<32,4> n<=32 nnz<=128"),
+    grp_class(KIND_PAIR4, 32, 4, 64, 256, "re_solve_grp_kernel<32,4> n<=64 nnz<=256"),
+    grp_class(KIND_PAIR4, 32, 4, 256, 1024, "re_solve_grp_kernel<32,4> n<=256 nnz<=1024"),
+    grp_class(KIND_G64_3, 64, 3, 64, 512, "re_solve_grp_kernel<64,3> n<=64 nnz<=512"),
+    grp_class(KIND_G64_3, 64, 3, 512, 2048, "re_solve_grp_kernel<64,3> n<=512 nnz<=2048"),
+    grp_class(KIND_G64_4, 64, 4, 64, 512, "re_solve_grp_kernel<64,4> n<=64 nnz<=512"),
+    grp_class(KIND_G64_4, 64, 4, 512, 2048, "re_solve_grp_kernel<64,4> n<=512 nnz<=2048"),
+    grp_class(KIND_G128_3, 128, 3, 128, 1024, "re_solve_grp_kernel<128,3> n<=128 nnz<=1024"),
+    grp_class(KIND_G128_3, 128, 3, 1024, 3072, "re_solve_grp_kernel<128,3> n<=1024 nnz<=3072"),
+    grp_class(KIND_G128_4, 128, 4, 128, 1024, "re_solve_grp_kernel<128,4> n<=128 nnz<=1024"),
+    grp_class(KIND_G128_4, 128, 4, 1024, 3072, "re_solve_grp_kernel<128,4> n<=1024 nnz<=3072"),
+    grp_class(KIND_G256_3, 256, 3, 256, 2048, "re_solve_grp_kernel<256,3> n<=256 nnz<=2048"),
+    grp_class(KIND_G256_3, 256, 3, 2048, 4096, "re_solve_grp_kernel<256,3> n<=2048 nnz<=4096"),
+    grp_class(KIND_G256_4, 256, 4, 256, 2048, "re_solve_grp_kernel<256,4> n<=256 nnz<=2048"),
+    grp_class(KIND_G256_4, 256, 4, 2048, 4096, "re_solve_grp_kernel<256,4> n<=2048 nnz<=4096"),
+    grp_class(KIND_G512_4, 512, 4, 512, 4096, "re_solve_grp_kernel<512,4> n<=512 nnz<=4096"),
+    wave_class(24576, "re_solve_wave_kernel lds<=24K"),
+    wave_class(65536, "re_solve_wave_kernel lds<=64K"),
+    // the tall classes, launched T, <8>, <4>, <1>, lean. Small ones get a side stream each — side 1, 2, 0: the device has four
+    // hardware queues by default, so the mid class shares the other small classes' rule and the team class the lean one's stream.
+    // occ_lanes: one eight-wavefront workgroup per CU counts as four wavefronts (small = fewer entities than 1.5 x the CUs), a mid
+    // workgroup as half of a CU's eight; the team class holds at most one round of teams
+    tall_class(KIND_TALL_T, TALL_VARIANT_TEAM, 0, 0, 0, "re_solve_tall_team_kernel<8> x4 p<=64"),
+    tall_class(KIND_TALL_L, TALL_VARIANT_LEAN, 4, WAVE, 0, "re_solve_tall_kernel<1> lean p<=64"),
+    tall_class(KIND_TALL_S, TALL_VARIANT_SMALL, 3, WAVE, 2, "re_solve_tall_kernel<1> p<=64"),
+    tall_class(KIND_TALL_M, TALL_VARIANT_MID, 2, 8 / TALL_MID_WGS * WAVE, -1, "re_solve_tall_kernel<4> p<=64"),
+    tall_class(KIND_TALL, TALL_VARIANT_LARGE, 1, 4 * TALL_NW / 8 * WAVE, 1, "re_solve_tall_kernel<8> p<=64"),
+    team_class(KIND_BLOCK, "re_solve_team_kernel workgroup"),
+    team_class(KIND_GRID, "re_solve_team_kernel 128 teams"),
+    team_class(KIND_GRID, "re_solve_team_kernel 32 teams"),
+    team_class(KIND_GRID, "re_solve_team_kernel 8 teams"),
+    team_class(KIND_GRID, "re_solve_team_kernel device-wide")};
+constexpr int class_of_kind(int kind) {   // the first class of a kind
+  for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c)
+    if (kClasses[c].kind == kind) return c;
+  return -1;
+}
+constexpr int TALL_T_CLASS = class_of_kind(KIND_TALL_T);   // the tallest of a batch: TALL_TEAM_C workgroups (CUs of one XCD) share one entity's samples
+constexpr int TALL_L_CLASS = class_of_kind(KIND_TALL_L);   // tall entities that fit a twelfth of a CU's LDS: the lean variant, three wavefronts per SIMD
+constexpr int TALL_S_CLASS = class_of_kind(KIND_TALL_S);   // the other smaller ones: workgroups of TALL_NW_SMALL wavefronts, several per CU
+constexpr int TALL_M_CLASS = class_of_kind(KIND_TALL_M);   // (round 6) the largest of the smaller ones in a SMALL batch: workgroups of TALL_NW_MID wavefronts, two per CU
+constexpr int TALL_CLASS = class_of_kind(KIND_TALL);       // tall entities of at least tall_split_n samples: one workgroup of TALL_NW wavefronts per CU
+constexpr int BLOCK_CLASS = class_of_kind(KIND_BLOCK);
+constexpr int TEAM128_CLASS = BLOCK_CLASS + 1;   // 128 teams of 2 CUs
+constexpr int TEAM32_CLASS = BLOCK_CLASS + 2;    // 32 teams of 8 CUs
+constexpr int TEAM8_CLASS = BLOCK_CLASS + 3;     // 8 teams of 32 CUs
+constexpr int GIANT_CLASS = BLOCK_CLASS + 4;     // device-wide kernel, one entity at a time
+constexpr int tall_class_of_rank(int rank) {
+  for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c)
+    if (kClasses[c].tall_rank == rank) return c;
+  return -1;
+}
+constexpr bool class_table_consistent() {
+  for (int k = 0; k < TALL_VARIANTS; ++k)
+    if (tall_class_of_rank(k) < 0) return false;
+
+  for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c) {
+    const ClassDesc& d = kClasses[c];
+    if (d.lanes != group_lanes(d.kind) || d.epl != group_epl(d.kind)) return false;
+    if ((d.tall_variant >= 0) != (c >= TALL_T_CLASS && c < BLOCK_CLASS) || (d.tall_variant >= 0) != (d.tall_rank >= 0)) return false;
+    if (c > BLOCK_CLASS && d.kind != KIND_GRID) return false;
+    if (c < TALL_T_CLASS && d.lds <= 0) return false;   // the classes re_classify_kernel picks by LDS bucket come first
+  }
+  return true;
+}
+static_assert(class_table_consistent(), "group_lanes / group_epl and the class constants describe kClasses");
+static_assert(GIANT_CLASS == GDMIX_RE_NUM_CLASSES - 1 && BLOCK_CLASS - TALL_T_CLASS == TALL_VARIANTS, "the tall classes, the block class, three tiers and the giant class end the table");
+static_assert(TALL_L_CLASS + 1 == TALL_S_CLASS, "a merged lean class sits right in front of the one-wavefront class in `order`");
 constexpr int BLOCK_NW = 4;   // wavefronts per workgroup of the block kernel
 #ifndef GDMIX_TEAM_BLOCK_NW
 #define GDMIX_TEAM_BLOCK_NW 8
@@ -95,18 +187,10 @@ struct ClassTable {
                           // holds (tests); 0: no mid class; < 0: chosen per batch, -tall_mid_n = the class's size limit (one round of its
                           // launch): the lowest of tall_mid_step(k) samples that keeps the class within it, in a small batch only
 };
-// counts[3 * NUM_CLASSES + k], k = 0..2: one-wavefront tall entities (TALL_S_CLASS) with at least TALL_ADAPT_N[k] samples;
-// counts[3 * NUM_CLASSES + TALL_ADAPT_SLOT]: the split class_base_kernel chose (0: none). (The row's team-tier columns hold the tiers' largest entity.)
+// What class_base_kernel decides a batch's tall classes on: re_classify_kernel's counts of candidates and the thresholds chosen from them.
 constexpr int TALL_ADAPT_STEPS = 3;
 __host__ __device__ constexpr int tall_adapt_n(int k) { return k == 0 ? 512 : (k == 1 ? 1024 : 2048); }
-constexpr int TALL_ADAPT_SLOT = 3;
-// counts[3 * NUM_CLASSES + TALL_TEAM_GE + k], k = 0..2: eight-wavefront tall entities with at least tall_team_n << k samples;
-// counts[3 * NUM_CLASSES + TALL_TEAM_SLOT]: the threshold class_base_kernel chose (0: no team class in this batch)
 constexpr int TALL_TEAM_STEPS = 3;
-constexpr int TALL_TEAM_GE = 4;
-constexpr int TALL_TEAM_SLOT = 7;
-// counts[3 * NUM_CLASSES + TALL_MID_GE + k], k = 0..5: one-wavefront tall entities (TALL_S_CLASS) with at least tall_mid_step(k) samples;
-// counts[3 * NUM_CLASSES + TALL_MID_SLOT]: the threshold class_base_kernel chose (0: no mid class in this batch).
 // Why a mid class (round 6): a share of a strongly scaled MovieLens job is as long as ONE wavefront needs for the
 // largest entity below the per-batch split — a 970-sample user x 49 evaluations, 25 - 40 us each, streamed (it does not fit the eighth
 // of a CU's LDS a one-wavefront workgroup has). On four wavefronts with half a CU's LDS the same entity is resident and an
@@ -114,8 +198,34 @@ constexpr int TALL_TEAM_SLOT = 7;
 // one wavefront per entity is the better use of a CU: the class exists only in a batch small enough for the split to adapt too.
 constexpr int TALL_MID_STEPS = 6;
 __host__ __device__ constexpr int tall_mid_step(int k) { return k == 0 ? 256 : (k == 1 ? 384 : (k == 2 ? 512 : (k == 3 ? 768 : (k == 4 ? 1024 : 1536)))); }
-constexpr int TALL_MID_GE = 8;
-constexpr int TALL_MID_SLOT = 14;
+struct TallRouting {
+  int32_t tall_ge[TALL_ADAPT_STEPS];   // one-wavefront tall entities (TALL_S_CLASS) with at least tall_adapt_n(k) samples
+  int32_t split;                       // the split class_base_kernel chose (0: none)
+  int32_t team_ge[TALL_TEAM_STEPS];    // eight-wavefront tall entities with at least tall_team_n << k samples
+  int32_t team_from;                   // the threshold class_base_kernel chose (0: no team class in this batch)
+  int32_t mid_ge[TALL_MID_STEPS];      // one-wavefront tall entities (TALL_S_CLASS) with at least tall_mid_step(k) samples
+  int32_t mid_from;                    // the threshold class_base_kernel chose (0: no mid class in this batch)
+};
+// The per-batch count record, gdmix_re_packed::class_count: six rows of NUM_CLASSES words. A solve zeroes it, re_classify_kernel,
+// class_base_kernel and re_order_kernel fill it, and the host reads it back through a mailbox (route, re_route.hip).
+struct ClassCounts {
+  int32_t count[GDMIX_RE_NUM_CLASSES];    // row 0: entities per class
+  int32_t base[GDMIX_RE_NUM_CLASSES];     // row 1: where the class begins in `order`
+  int32_t cursor[GDMIX_RE_NUM_CLASSES];   // row 2: tickets handed out by re_order_kernel
+  // row 3 has two tenants: the tall routing in its first words, the team tiers' largest entity (non-zeros) at the tiers' columns
+  TallRouting tall;
+  int32_t row3_free[TEAM128_CLASS - (int)(sizeof(TallRouting) / sizeof(int32_t))];
+  int32_t team_largest_nnz[GDMIX_RE_NUM_CLASSES - TEAM128_CLASS];   // of class TEAM128_CLASS + k (largest_nnz)
+  unsigned long long team_nnz_total[GDMIX_RE_NUM_CLASSES];          // rows 4-5: non-zeros of the class, team tiers only
+  __host__ __device__ int32_t& largest_nnz(int c) { return team_largest_nnz[c - TEAM128_CLASS]; }
+  __host__ __device__ const int32_t& largest_nnz(int c) const { return team_largest_nnz[c - TEAM128_CLASS]; }
+};
+static_assert(sizeof(ClassCounts) == 6 * GDMIX_RE_NUM_CLASSES * sizeof(int32_t), "gdmix_re_packed::class_count is documented as [6*NUM_CLASSES]");
+static_assert(offsetof(ClassCounts, count) == 0 && offsetof(ClassCounts, base) == 1 * GDMIX_RE_NUM_CLASSES * sizeof(int32_t) &&
+              offsetof(ClassCounts, cursor) == 2 * GDMIX_RE_NUM_CLASSES * sizeof(int32_t) && offsetof(ClassCounts, tall) == 3 * GDMIX_RE_NUM_CLASSES * sizeof(int32_t) &&
+              offsetof(ClassCounts, team_largest_nnz) == (3 * GDMIX_RE_NUM_CLASSES + TEAM128_CLASS) * sizeof(int32_t) &&
+              offsetof(ClassCounts, team_nnz_total) == 4 * GDMIX_RE_NUM_CLASSES * sizeof(int32_t), "the rows of the count record");
+static_assert(offsetof(TallRouting, mid_from) / sizeof(int32_t) < (size_t)TEAM128_CLASS, "row 3: the last threshold slot stays below the team tiers' columns");
 
 // Device pointers of a packed batch, passed by value to kernels.
 struct BatchDev {
@@ -173,8 +283,7 @@ struct gdmix_ctx_impl {
   int tall_team_limit;    // ClassTable::tall_team_limit: one round of teams on this device
   int tall_mid_n;         // ClassTable::tall_mid_n (gdmix_re_set_tall_mid_n; GDMIX_RE_TALL_MID=0 switches the class off)
   int spread;             // > 1: large classes are dealt over this many queues (the caller's stream + side streams); 0: one after another
-  void* grid_sync;        // device: TeamSync of the team kernels (the first three also: ticket counters of the tall variants), followed
-                          // by TALL_TAIL_BYTES for each tall variant (four: the team variant last) and TALL_TEAM_BYTES
+  void* grid_sync;        // device: the sync and exchange buffers of the team and tall kernels, laid out by GridSyncLayout (re_solve_team.hpp)
   void* big_tmp;          // device: grow-only temporary of the big-entity pack path
   size_t big_tmp_bytes;
   // classes too small to fill the device run on side streams, next to the large ones on the caller's stream and next to each other
@@ -208,6 +317,9 @@ struct gdmix_ctx_impl {
 constexpr size_t HOST_PINNED_BYTES = 8192;
 constexpr size_t MAILBOX_OFFSET = 4096, MAILBOX_BYTES = 1024, MAILBOX_DATA = 64;   // per box: flag word at 0, data from byte 64
 constexpr int FETCH_SPIN_US = 400;
+constexpr size_t COUNTS_READBACK_WORDS = 256;   // where a solve's ClassCounts land in host_pinned (int32 words from its start)
+static_assert(sizeof(ClassCounts) <= MAILBOX_BYTES - MAILBOX_DATA, "a larger count record falls back to copy + synchronise in post_small");
+static_assert(COUNTS_READBACK_WORDS * sizeof(int32_t) + sizeof(ClassCounts) <= MAILBOX_OFFSET, "the read-back areas end where the mailboxes begin");
 struct SmallFetch { int box; uint32_t seq; size_t bytes; void* host_dst; hipStream_t s; };
 hipError_t post_small(gdmix_ctx_impl* ctx, int box, const void* dev_src, size_t bytes, void* host_dst, hipStream_t s, SmallFetch* f);   // queue the hand-over
 hipError_t wait_small(gdmix_ctx_impl* ctx, const SmallFetch& f);                                                                    // ... and take it
@@ -261,10 +373,18 @@ struct SideJoin {
   ~SideJoin() { join(); }
 };
 
-hipError_t launch_classify(const gdmix_re_packed* b, int ic, int m, const ClassTable& tab, int32_t* cls_tmp,
-                           int32_t* counts_dev, hipStream_t s);
-hipError_t launch_order(const gdmix_re_packed* b, int32_t* cls_tmp, const int32_t* class_base_dev,
-                        int32_t* cursor_dev, hipStream_t s);
+// routing (re_route.hip): the rules of this solve; the batch's entities classified and ordered, the counts read back (*host points
+// into the context's pinned buffer, good until the next solve); the launches of the classes below the block class
+int make_class_table(const gdmix_ctx_impl* ci, const gdmix_re_opts* opts, ClassTable* out);
+int route(gdmix_ctx_impl* ci, const gdmix_re_packed* b, const ClassTable& tab, const gdmix_re_opts* opts, hipStream_t s, const ClassCounts** host);
+struct Launch { int c, begin, count, stream; };   // entities order[begin, begin + count) of class c; stream -1: the caller's, k >= 0: side stream k
+struct LaunchPlan {
+  Launch launch[GDMIX_RE_NUM_CLASSES];
+  int n;
+  int lean_merged;   // > 0: that many entities of the lean tall class run at the front of the one-wavefront class's launch
+  bool fork;         // the side streams start from the caller's stream
+};
+LaunchPlan plan_launches(const ClassCounts& counts, int num_cus, int n_side, int spread, int lean_rounds);
 hipError_t launch_solve_quad(int g, int epl, const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0,
                              int begin, int count, int ncap, int zcap, hipStream_t s);
 hipError_t launch_solve_wave(const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0,
@@ -277,7 +397,7 @@ hipError_t launch_solve_grid(const BatchDev& B, const OutDev& O, const SolvePara
                              void* sync_buf, int blocks, int teams, hipStream_t s);
 constexpr int TALL_TAIL_BYTES = 256;   // device buffer of the context: padded copy of the end of the batch's row-major arrays
 hipError_t launch_solve_tall(int variant, const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0, int begin, int count,
-                             int num_cus, int64_t Z, void* tail_buf, void* sync_buf, int front_small, hipStream_t s);
+                             int num_cus, int64_t Z, void* tail_buf, unsigned* ticket, int front_small, hipStream_t s);
 hipError_t launch_solve_tall_team(const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0, int begin, int count,
                                   int num_cus, int64_t Z, void* tail_buf, void* team_buf, int xcd_fast, hipStream_t s);
 void launch_sort_class(int32_t* list, int count, const int64_t* ent_nnz_ptr, hipStream_t s);

@@ -1,6 +1,6 @@
 // re_solve.hip — gfx950 kernels of the random-effect solve and score.
 //
-//   re_classify_kernel / re_order_kernel   bucket entities by the LDS footprint of their solve
+//   (re_route.hip: the kernels that bucket entities by the LDS footprint of their solve)
 //   re_solve_wave_kernel                   ONE WAVEFRONT PER ENTITY: the entity's (X, y, offset, weight)
 //                                          block and all L-BFGS state live in LDS for the whole solve
 //   re_solve_block_kernel                  one 256-thread workgroup per entity for blocks that do not
@@ -12,139 +12,6 @@
 #include "re_solve_team.hpp"
 
 namespace gdmix {
-
-// ---------------------------------------------------------------------------------------------------
-// classification
-// ---------------------------------------------------------------------------------------------------
-__global__ void re_classify_kernel(const int64_t* __restrict__ ent_row_ptr, const int64_t* __restrict__ ent_nnz_ptr,
-                                   const int64_t* __restrict__ ent_feat_ptr, int64_t E, int ic, int m, bool has_w,
-                                   ClassTable tab, int32_t* __restrict__ cls_out, int32_t* __restrict__ counts) {
-  __shared__ int32_t local[GDMIX_RE_NUM_CLASSES];
-  __shared__ int32_t tall_ge[TALL_ADAPT_STEPS], team_ge[TALL_TEAM_STEPS], mid_ge[TALL_MID_STEPS];
-  if (threadIdx.x < GDMIX_RE_NUM_CLASSES) local[threadIdx.x] = 0;
-  if (threadIdx.x < TALL_ADAPT_STEPS) tall_ge[threadIdx.x] = 0;
-  if (threadIdx.x < TALL_TEAM_STEPS) team_ge[threadIdx.x] = 0;
-  if (threadIdx.x < TALL_MID_STEPS) mid_ge[threadIdx.x] = 0;
-  __syncthreads();
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
-    const int n = (int)(ent_row_ptr[e + 1] - ent_row_ptr[e]);
-    const int z = (int)(ent_nnz_ptr[e + 1] - ent_nnz_ptr[e]);
-    const int d = (int)(ent_feat_ptr[e + 1] - ent_feat_ptr[e]);
-    const int p = d + ic;
-    int c = BLOCK_CLASS;
-    // cheapest first: the group kernel with the fewest lanes and coefficient slots that holds the entity, smallest LDS bucket;
-    // then the LDS-resident wavefront kernel (any m); the one-workgroup team kernel takes what is left
-    const size_t wlds_bytes = wave_lds_bytes(p, n, z, d, m, has_w);
-    for (int k = 0; k < BLOCK_CLASS; ++k) {
-      if (tab.lds_bytes[k] <= 0) continue;
-      const int kind = tab.kind[k];
-      if (group_lanes(kind) > 0) {
-        const int cap = group_lanes(kind) * group_epl(kind);
-        if (m <= M_REG && p <= cap && n <= tab.ncap[k] && z <= tab.zcap[k]) { c = k; break; }
-      } else if (kind == KIND_WLDS) {
-        if (wlds_bytes <= (size_t)tab.lds_bytes[k]) { c = k; break; }
-      }
-    }
-    if (tab.tall_min_n > 0 && m <= M_REG && p <= TALL_MAX_P && n >= tab.tall_min_n && !(tab.giant_nnz > 0 && z >= tab.giant_nnz)) c = (n >= tab.tall_split_n) ? TALL_CLASS
-        : (tall_resident_bytes(1, tall_sets(1, p), d, n, z, has_w) <= (size_t)TALL_LEAN_ARENA ? TALL_L_CLASS : TALL_S_CLASS);
-    else if (tab.giant_nnz > 0 && z >= tab.giant_nnz) c = GIANT_CLASS;
-    else if (c == BLOCK_CLASS || (tab.team_nnz > 0 && z >= tab.team_nnz)) {
-      // too large for a wavefront group: a team of CUs, sized by the non-zeros (streaming bandwidth)
-      if (tab.team_nnz > 0 && z >= tab.team_nnz)
-        c = (z >= 128 * tab.team_nnz) ? TEAM8_CLASS : ((z >= 8 * tab.team_nnz) ? TEAM32_CLASS : TEAM128_CLASS);
-    }
-    cls_out[e] = c;
-    atomicAdd(&local[c], 1);
-    if (c == TALL_S_CLASS && tab.tall_adapt_limit > 0 && n >= tall_adapt_n(0)) {
-#pragma unroll
-      for (int k = 0; k < TALL_ADAPT_STEPS; ++k)
-        if (n >= tall_adapt_n(k)) atomicAdd(&tall_ge[k], 1);
-    }
-    if (c == TALL_S_CLASS && tab.tall_mid_n < 0 && n >= tall_mid_step(0)) {      // candidates of the mid class (class_base_kernel decides)
-#pragma unroll
-      for (int k = 0; k < TALL_MID_STEPS; ++k)
-        if (n >= tall_mid_step(k)) atomicAdd(&mid_ge[k], 1);
-    }
-    if (c == TALL_S_CLASS && tab.tall_mid_n > 0 && n >= tab.tall_mid_n) atomicAdd(&mid_ge[0], 1);      // a fixed threshold: slot 0 counts them
-    if (c == TALL_CLASS && tab.tall_team_n > 0 && n >= tab.tall_team_n) {   // candidates of the team class (class_base_kernel decides)
-#pragma unroll
-      for (int k = 0; k < TALL_TEAM_STEPS; ++k)
-        if ((int64_t)n >= ((int64_t)tab.tall_team_n << k)) atomicAdd(&team_ge[k], 1);
-    }
-    if (c >= TEAM128_CLASS && c <= TEAM8_CLASS) {
-      // work of the team tiers (non-zeros: total and largest entity), for the choice of the team size; rare entities
-      atomicAdd(reinterpret_cast<unsigned long long*>(counts + 4 * GDMIX_RE_NUM_CLASSES) + c, (unsigned long long)z);
-      atomicMax(counts + 3 * GDMIX_RE_NUM_CLASSES + c, z);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < GDMIX_RE_NUM_CLASSES && local[threadIdx.x]) atomicAdd(&counts[threadIdx.x], local[threadIdx.x]);
-  if (threadIdx.x < TALL_ADAPT_STEPS && tall_ge[threadIdx.x]) atomicAdd(&counts[3 * GDMIX_RE_NUM_CLASSES + threadIdx.x], tall_ge[threadIdx.x]);
-  if (threadIdx.x < TALL_TEAM_STEPS && team_ge[threadIdx.x]) atomicAdd(&counts[3 * GDMIX_RE_NUM_CLASSES + TALL_TEAM_GE + threadIdx.x], team_ge[threadIdx.x]);
-  if (threadIdx.x < TALL_MID_STEPS && mid_ge[threadIdx.x]) atomicAdd(&counts[3 * GDMIX_RE_NUM_CLASSES + TALL_MID_GE + threadIdx.x], mid_ge[threadIdx.x]);
-}
-
-// order[class_base[c] + k] = e. Position inside a class is by ticket: the launch order inside a class
-// does not influence any entity's result (every entity is solved independently and deterministically),
-// only which workgroup picks it up. Tickets are taken per workgroup (LDS histogram, then one global
-// atomic per class per workgroup): per-entity global atomics on 8 addresses serialise in L2.
-// split > 0 (class_base_kernel lowered the split of the tall classes for this batch): one-wavefront tall entities of at least
-// `split` samples move to the eight-wavefront class here, in cls as well (the per-class times are attributed through it).
-__global__ __launch_bounds__(256) void re_order_kernel(int32_t* __restrict__ cls, int64_t E,
-                                                       const int32_t* __restrict__ class_base,
-                                                       int32_t* __restrict__ cursor, int32_t* __restrict__ order,
-                                                       const int64_t* __restrict__ ent_row_ptr, const int32_t* __restrict__ split_dev) {
-  __shared__ int32_t cnt[GDMIX_RE_NUM_CLASSES], base[GDMIX_RE_NUM_CLASSES];
-  const int split = *split_dev;
-  const int team_from = split_dev[TALL_TEAM_SLOT - TALL_ADAPT_SLOT];   // > 0: eight-wavefront tall entities of at least this many samples get a team
-  const int mid_from = split_dev[TALL_MID_SLOT - TALL_ADAPT_SLOT];     // > 0: one-wavefront tall entities of at least this many samples (below the split) go to the mid class
-  const int64_t chunk = (int64_t)blockDim.x * 8;
-  for (int64_t start = (int64_t)blockIdx.x * chunk; start < E; start += (int64_t)gridDim.x * chunk) {
-    if (threadIdx.x < GDMIX_RE_NUM_CLASSES) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    int c[8], pos[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t e = start + (int64_t)k * blockDim.x + threadIdx.x;
-      c[k] = (e < E) ? cls[e] : -1;
-      if (split > 0 && c[k] == TALL_S_CLASS && ent_row_ptr[e + 1] - ent_row_ptr[e] >= split) { c[k] = TALL_CLASS; cls[e] = TALL_CLASS; }
-      else if (team_from > 0 && c[k] == TALL_CLASS && ent_row_ptr[e + 1] - ent_row_ptr[e] >= team_from) { c[k] = TALL_T_CLASS; cls[e] = TALL_T_CLASS; }
-      else if (mid_from > 0 && c[k] == TALL_S_CLASS && ent_row_ptr[e + 1] - ent_row_ptr[e] >= mid_from) { c[k] = TALL_M_CLASS; cls[e] = TALL_M_CLASS; }
-      pos[k] = (c[k] >= 0) ? atomicAdd(&cnt[c[k]], 1) : 0;
-    }
-    __syncthreads();
-    if (threadIdx.x < GDMIX_RE_NUM_CLASSES)
-      base[threadIdx.x] = cnt[threadIdx.x] ? atomicAdd(&cursor[threadIdx.x], cnt[threadIdx.x]) : 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t e = start + (int64_t)k * blockDim.x + threadIdx.x;
-      if (c[k] >= 0) order[class_base[c[k]] + base[c[k]] + pos[k]] = (int32_t)e;
-    }
-    __syncthreads();
-  }
-}
-
-hipError_t launch_classify(const gdmix_re_packed* b, int ic, int m, const ClassTable& tab, int32_t* cls_tmp,
-                           int32_t* counts_dev, hipStream_t s) {
-  if (b->E == 0) return hipSuccess;
-  int grid = (int)((b->E + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL(re_classify_kernel, dim3(grid), dim3(256), 0, s, b->ent_row_ptr, b->ent_nnz_ptr,
-                     b->ent_feat_ptr, b->E, ic, m, b->weight != nullptr, tab, cls_tmp, counts_dev);
-  return hipGetLastError();
-}
-
-hipError_t launch_order(const gdmix_re_packed* b, int32_t* cls_tmp, const int32_t* class_base_dev,
-                        int32_t* cursor_dev, hipStream_t s) {
-  if (b->E == 0) return hipSuccess;
-  int grid = (int)((b->E + 2047) / 2048);
-  if (grid > 2048) grid = 2048;
-  // (class_base_dev = counts + NUM_CLASSES: the chosen split sits two rows further)
-  hipLaunchKernelGGL(re_order_kernel, dim3(grid), dim3(256), 0, s, cls_tmp, b->E, class_base_dev, cursor_dev,
-                     b->order, b->ent_row_ptr, class_base_dev + 2 * GDMIX_RE_NUM_CLASSES + TALL_ADAPT_SLOT);
-  return hipGetLastError();
-}
 
 // ---------------------------------------------------------------------------------------------------
 // shared epilogue: theta, thresholded theta, stats

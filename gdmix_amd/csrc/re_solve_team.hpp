@@ -18,6 +18,7 @@
 // agree with them to rounding (different summation order), which tests/test_gpu_parity.py pins against
 // the reference fixtures through the workgroup class.
 #pragma once
+#include "re_internal.hpp"
 #include "re_lbfgs_compact.hpp"
 
 namespace gdmix {
@@ -47,6 +48,27 @@ struct TeamSync {
   unsigned pad[10];
   double vec[2][TEAM_VEC][TEAM_MAX_BLOCKS];   // [phase][value][workgroup]
   unsigned xcc[TEAM_MAX_BLOCKS];              // HW_REG_XCC_ID of every workgroup of the team, published once per launch (1 + id)
+};
+
+// The layout of gdmix_ctx_impl::grid_sync (device memory of the context), in this order:
+//   TeamSync[TEAM_MAX_TEAMS]            the exchange buffers of the team tiers and the device-wide kernel
+//   TALL_VARIANTS x TALL_TAIL_BYTES     each tall variant's padded copy of the end of the batch's row-major arrays: the variants run
+//                                       side by side on their own streams (five: large, small, lean, team, mid)
+//   TALL_TEAM_BYTES                     the tall teams' exchange structures
+//   TALL_VARIANTS x TICKET_BYTES        each tall variant's ticket counter (a cache line of its own: it decides which workgroup
+//                                       takes which entity, never a result bit)
+struct GridSyncLayout {
+  static constexpr size_t TICKET_BYTES = 64;
+  static constexpr size_t TAILS = TEAM_MAX_TEAMS * sizeof(TeamSync);
+  static constexpr size_t TEAM_BUF = TAILS + TALL_VARIANTS * TALL_TAIL_BYTES;
+  static constexpr size_t TICKETS = TEAM_BUF + TALL_TEAM_BYTES;
+  static constexpr size_t BYTES = TICKETS + TALL_VARIANTS * TICKET_BYTES;
+  static TeamSync* team_sync(const gdmix_ctx_impl* ci) { return static_cast<TeamSync*>(ci->grid_sync); }
+  static void* tall_tail(const gdmix_ctx_impl* ci, int variant) { return static_cast<char*>(ci->grid_sync) + TAILS + variant * TALL_TAIL_BYTES; }
+  static void* tall_team_buf(const gdmix_ctx_impl* ci) { return static_cast<char*>(ci->grid_sync) + TEAM_BUF; }
+  static unsigned* tall_ticket(const gdmix_ctx_impl* ci, int variant) {
+    return reinterpret_cast<unsigned*>(static_cast<char*>(ci->grid_sync) + TICKETS + variant * TICKET_BYTES);
+  }
 };
 
 // LDS of one workgroup of a team.

@@ -3,6 +3,7 @@ assembly with the build's flags (`hipcc -S --cuda-device-only`) and compared ker
 directives and per-compile labels. Kernels are matched by demangled name; --gained-false names kernels whose template list gained a
 trailing `false` argument since the other commit (a new compile-time parameter whose `false` instantiation must be the old kernel);
 --renamed old=new,... names kernels and types that were renamed since: the other commit's names and lines are read under the new names.
+A kernel that moved to another unit is found there by its name.
 
     python tools/asm_compare.py --parent HEAD~1 \\
         --gained-false re_solve_grp_kernel,re_solve_wave_kernel,re_solve_block_kernel,re_variance_full_kernel,re_solve_tall_kernel,re_solve_tall_team_kernel
@@ -10,6 +11,7 @@ trailing `false` argument since the other commit (a new compile-time parameter w
 Prints per unit: kernels identical / different / only in this tree; exit status 1 if a kernel of the other commit differs or is missing.
 """
 import argparse
+import difflib
 import os
 import re
 import subprocess
@@ -72,6 +74,7 @@ def main():
     ap.add_argument("--parent", default="HEAD", help="the commit to compare the working tree with")
     ap.add_argument("--gained-false", default="", help="comma list of kernel names whose template arguments gained a trailing `false`")
     ap.add_argument("--renamed", default="", help="comma list of old=new: kernel or type names of the other commit that were renamed since")
+    ap.add_argument("--diff", action="store_true", help="print the lines of a kernel that differs")
     a = ap.parse_args()
     renamed = [tuple(r.split("=")) for r in a.renamed.split(",") if r]
     gained = [g for g in a.gained_false.split(",") if g]
@@ -88,17 +91,27 @@ def main():
         subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
         s_old = compile_units(os.path.join(old, "gdmix_amd", "csrc"), os.path.join(tmp, "s_old"))
         s_new = compile_units(build.CSRC, os.path.join(tmp, "s_new"))
+        new = {unit: functions(s_new[unit]) for unit in build.SOURCES}
+        # a kernel that left its unit is looked for, by name, in the other units of this tree
+        fn_all = {k: v for f, _ in new.values() for k, v in f.items()}
+        mn_all = {k: v for _, m in new.values() for k, v in m.items()}
+        moved_by_key = {key(d): k for k, d in demangle(list(fn_all)).items()}
         for unit in build.SOURCES:
             if unit not in s_old:
-                print(f"{unit}: a new unit, {len(functions(s_new[unit])[0])} functions only in this tree")
+                print(f"{unit}: a new unit, {len(new[unit][0])} functions")
                 continue
             fo, mo = functions(s_old[unit], renamed)
-            fn, mn = functions(s_new[unit])
+            fn, mn = new[unit]
             do, dn = demangle(list(fo)), demangle(list(fn))
             new_by_key = {key(dn[k]): k for k in fn if k not in fo}
-            same = diff = 0
+            same = diff = moved = 0
             for k in fo:
                 k2 = k if k in fn else new_by_key.get(do[k])      # same symbol, or the symbol that gained its `false`
+                if k2 is None and (k in fn_all or do[k] in moved_by_key):
+                    k2 = k if k in fn_all else moved_by_key[do[k]]
+                    print(f"{unit}: {do[k]} is in another unit now")
+                    moved += 1
+                    fn, mn = {**fn_all, **fn}, {**mn_all, **mn}
                 if k2 is None:
                     print(f"{unit}: MISSING {do[k]}")
                     bad += 1
@@ -106,9 +119,11 @@ def main():
                     same += 1
                 else:
                     print(f"{unit}: DIFFERENT {do[k]} ({len(fo[k])} -> {len(fn[k2])} lines)")
+                    if a.diff:
+                        print("\n".join(difflib.unified_diff(fo[k] + mo.get(k, "").splitlines(), fn[k2] + mn.get(k2, "").splitlines(), "other", "this tree", lineterm="", n=1)))
                     diff += 1
                     bad += 1
-            print(f"{unit}: {same} identical, {diff} different, {len(fn) - same - diff} only in this tree")
+            print(f"{unit}: {same} identical, {diff} different, {len(new[unit][0]) - same - diff + moved} only in this tree")
     print("every kernel of the other commit is unchanged" if not bad else f"{bad} kernels differ or are missing")
     return 1 if bad else 0
 
