@@ -103,6 +103,12 @@ class RandomEffectDriver:
             # the winner in model_params.l2_reg_weight, and what follows is the stage as it always runs
             from . import sweep
             sweep.run(self, schema_params)
+        kind = getattr(getattr(self.model, "model_params", None), "normalization", None)
+        if kind is not None and kind() != "none":
+            # --feature_normalization: the statistics of the stage's training data (or the file that holds them) come first and leave
+            # the factors on the model; what follows is the stage as it always runs, penalising in normalised units
+            from . import feature_stats
+            feature_stats.run(self, schema_params)
         partition_index_list = self._get_partition_list()
         logger.info(f"This worker on work on the following list of partitions : {partition_index_list}")
         # With entity re-balancing the workers train in lockstep, one partition each per round; a worker that has no

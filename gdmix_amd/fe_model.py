@@ -44,7 +44,7 @@ from .io import avro, native_reader, tfrecord
 from .io.features import read_feature_list
 from .io.grouped_reader import resolve_input_files
 from .io.metadata import DatasetMetadata
-from .params import LRParams, parse_l2_grid
+from .params import LRParams, check_feature_normalization, parse_l2_grid
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.INFO)
@@ -70,14 +70,25 @@ class FixedLRParams(LRParams):
     # not in the reference (which leaves it open, fixed_effect_lr_lbfgs_model.py:361-367); the random-effect stage's flag of the same
     # name (params.REParams): the L2 term centred on the prior model in output_model_dir and weighted by its precisions
     incremental_training: bool = False
+    # not in the reference; the random-effect stage's flags of the same names (params.REParams): the L2 term penalises coefficients in
+    # normalised units, the factors from exact column statistics of all workers' training data (all-reduced integers)
+    feature_normalization: Optional[str] = None
+    feature_statistics_file: Optional[str] = None
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
         return None if self.l2_reg_weights is None else parse_l2_grid(self.l2_reg_weights)
 
+    def normalization(self):
+        """The value of --feature_normalization ("none" without the flag)."""
+        return "none" if self.feature_normalization is None else self.feature_normalization
+
     def __post_init__(self):
         super().__post_init__()
         self.l2_grid()      # a bad list is an error at parse time
+        check_feature_normalization(self, (
+            (self.incremental_training, "--incremental_training", "prior variances are in the original feature units, and composing the two is not implemented"),
+            (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep in normalised units is not implemented")))
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         assert self.fixed_effect_variance_mode is None or self.fixed_effect_variance_mode in (constants.FULL, constants.SIMPLE), \
@@ -258,6 +269,19 @@ class FixedEffectLRModelLBFGS:
                                                  label=data["y"] if data["has_label"] else None)
         return data["_dev"]
 
+    # ---- feature normalisation (--feature_normalization) ------------------------------------------------------------------
+    def _feature_factors(self, kind, data, is_chief):
+        """The factors [num_features] of this stage, the same bits on every worker: the statistics of all workers' training samples, from
+        --feature_statistics_file or from two passes over this worker's device shard with the integers all-reduced (feature_stats.py).
+        A worker whose shard is empty still takes part."""
+        from . import feature_stats
+        fe = self._solver()
+        shard = self._device_shard(data) if data["n"] > 0 else None
+        factor, self.feature_statistics = feature_stats.fixed_effect_factors(
+            kind, self.model_params.feature_statistics_file, fe.solver, self.num_features, None if shard is None else shard.cg,
+            None if shard is None else shard.vl, data["n"], is_chief=is_chief)
+        return factor
+
     # ---- the sweep (--l2_reg_weights) ----------------------------------------------------------------------------------
     def _stage_coefficients(self, theta):
         """fit_stepping's coefficients as the stage keeps them: the dummy weight of an intercept-only model in front
@@ -340,12 +364,16 @@ class FixedEffectLRModelLBFGS:
                     logger.info("Found a previous model, loaded as the initial point for training")
             elif prev_model is not None:
                 logger.info(f"Initial model size is {len(prev_model)}, expected {expected}, use all zeros instead.")
+            extra = {} if prior is None else {"prior": prior}
+            kind = self.model_params.normalization()
+            if kind != "none" and bag:
+                extra["feature_scale"] = self._feature_factors(kind, data, is_chief)
             theta, info = self._solver().fit_stepping(
                 *self._shard_arrays(data, fit=True), data["y"], D, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
                 has_intercept=self.has_intercept, l2=self.l2_reg_weight, regularize_bias=self.is_regularize_bias,
                 model_type=self.model_type, theta0=self._strip_dummy(x0) if not bag else x0, max_iter=self.max_iteration,
                 m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
-                variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold, **({} if prior is None else {"prior": prior}))
+                variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold, **extra)
         self.variances = info.pop("variances", None)
         if not bag and self.variances is not None:
             self.variances = np.concatenate([[0.0], self.variances])   # next to the dummy weight of an intercept-only model

@@ -162,17 +162,20 @@ class FixedEffectDeviceSolver:
 
     def fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
                      regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
-                     group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0, prior=None):
+                     group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0, prior=None, feature_scale=None):
         """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
         worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
         model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
         hold no non-zero, so that its all-reduce buffer has the same num_features + 2 entries as everyone else's.
         prior = (mean, variance), each in theta0's layout: incremental training (include/gdmix_fe.h, "incremental training") — the L2
         term is centred on `mean` and weighted by 1 / variance (1 where a variance is not finite or <= 0), the fit starts at `mean`
-        (theta0 must be None), and the variances returned are the posterior's. Every worker passes the same prior."""
+        (theta0 must be None), and the variances returned are the posterior's. Every worker passes the same prior.
+        feature_scale = s [num_features]: feature normalisation (include/gdmix_re.h, "feature normalisation") — the penalty is
+        (l2/2) sum (theta_j / s_j)^2, i.e. a prior of mean 0 and variance s^2 with s = 1 for the intercept; theta0, in theta units, is
+        honoured; not together with `prior`. Every worker passes the same factors."""
         opts = fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance)
         fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode,
-                           prior=prior)
+                           prior=prior, feature_scale=feature_scale)
         theta, info = fit.stage_result(*fit.run(), l2, threshold)
         if return_problem:
             return theta, info, fit.prob
@@ -462,10 +465,12 @@ class _SteppingFit:
     and the all-reduce of this process group; then the loop, and the result as the stage takes it."""
 
     def __init__(self, solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode,
-                 prior=None):
+                 prior=None, feature_scale=None):
         ic = 1 if opts.has_intercept else 0
         if prior is not None and theta0 is not None:
             raise ValueError("a fit with a prior starts at the prior mean: theta0 must be None")
+        if prior is not None and feature_scale is not None:
+            raise ValueError("feature normalisation does not compose with a prior model")
         self.batch, self.dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, opts.has_intercept,
                                                 binary_labels=not opts.linear, dummy=dummy)
         D = 1 if self.dummy else int(num_features)   # the dummy zero feature of an intercept-only model occupies global index 0
@@ -486,12 +491,24 @@ class _SteppingFit:
             else:
                 full[:] = th
             t0 = solver.torch.from_numpy(full).to(solver.device)
-        self.prob = _SteppingProblem(solver, self.packed, D, opts, t0)
+        self.prob = _SteppingProblem(solver, self.packed, D, opts, None if (feature_scale is not None and not self.dummy) else t0)
         self.prior_scale = None
         if prior is not None:
             mean, self.prior_scale = prior_vectors(prior[0], prior[1], D, ic, self.dummy, opts.regularize_bias)
             up = lambda a: solver.torch.from_numpy(a).to(solver.device)
             self.prob.set_prior(up(mean), up(self.prior_scale))
+        elif feature_scale is not None and not self.dummy:
+            # mean 0, scale s, 1 for the intercept: created cold, the prior installed, then the start point in theta units
+            # (gdmix_fe_set_prior leaves the problem at phi = 0; gdmix_fe_restart takes theta0 as theta while a prior is installed)
+            sc = np.ones(D + ic)
+            sc[:D] = np.asarray(feature_scale, np.float64)
+            if sc.shape != (D + ic,) or not np.all(np.isfinite(sc) & (sc > 0)):
+                raise ValueError(f"feature_scale holds {D} finite factors > 0")
+            self.prior_scale = sc
+            up = lambda a: solver.torch.from_numpy(a).to(solver.device)
+            self.prob.set_prior(up(np.zeros(D + ic)), up(sc))
+            if t0 is not None:
+                self.prob.restart(opts, t0)
         self.all_reduce = None
         try:
             import torch.distributed as dist

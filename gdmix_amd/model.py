@@ -504,6 +504,7 @@ class RandomEffectLRLBFGSModel:
         self._decoded = {}          # read key -> RawBatch decoded for a group, until _read hands it out
         self.last_training_stats = None
         self._stage_metrics = None  # metrics.StageMetrics when model_params.metric_output_dir is set (created with the first scores)
+        self._feature_factor = None # --feature_normalization: the stage's factors [num_features] on the device (set_feature_factors)
 
     # ---- the stage's metric, on the device while it scores (REParams.metric_output_dir) -------------------------------------------
     def _metrics(self):
@@ -931,21 +932,46 @@ class RandomEffectLRLBFGSModel:
         return bool(getattr(self.model_params, "incremental_training", False)) and bool(model_weights)
 
     @staticmethod
-    def _solve_with_prior(solver, packed, opts, prior):
-        """The solve of include/gdmix_re.h, "incremental training": the transformed batch is solved from phi = 0 with the variance mode of
-        `opts`, theta, its thresholded form and the variances come back through gdmix_re_prior_restore. `packed` stays as it is."""
+    def _solve_with_prior(solver, packed, opts, prior, phi0=None):
+        """The solve of include/gdmix_re.h, "incremental training": the transformed batch is solved from phi = 0 (or from phi0) with the
+        variance mode of `opts`, theta, its thresholded form and the variances come back through gdmix_re_prior_restore. `packed` stays
+        as it is."""
         from .solver import SolveResult
         mean, scale = prior
         work = solver.prior_apply(packed, mean, scale)
-        solved = solver.solve(work, opts, theta0=None)
+        solved = solver.solve(work, opts, theta0=phi0)
         back = solver.prior_restore(packed, mean, scale, solved.theta, solved._t.get("variance"), threshold=opts.threshold)
         return SolveResult({**solved._t, **back}, packed.E, packed.P)
+
+    def set_feature_factors(self, factor):
+        """--feature_normalization: the stage's factors [num_features of the bag] (feature_stats.run), kept on the device; None: none.
+        From here on every solve of the stage penalises theta_j / s_j (include/gdmix_re.h, "feature normalisation")."""
+        if factor is None:
+            self._feature_factor = None
+            return
+        solver = self._get_solver()
+        self._feature_factor = solver.torch.from_numpy(np.ascontiguousarray(factor, np.float64)).to(solver.device)
+
+    def _solve_normalised(self, solver, packed, opts, theta0):
+        """The solve in normalised units: scale [P] = the factors in the batch's coefficient order (1 at every intercept), built on the
+        device; the transformed batch solved from phi0 = theta0 / scale; theta, its thresholded form and the variances restored."""
+        t = solver.torch
+        scale = solver.feature_scale_expand(packed, self._feature_factor)
+        mean = t.zeros(packed.P, dtype=t.float64, device=solver.device)
+        phi0 = None
+        if theta0 is not None:
+            if isinstance(theta0, np.ndarray):
+                theta0 = t.from_numpy(np.ascontiguousarray(theta0, np.float64))
+            phi0 = theta0.to(solver.device, non_blocking=getattr(theta0, "is_pinned", lambda: False)()) / scale
+        return self._solve_with_prior(solver, packed, opts, (mean, scale), phi0)
 
     def _pack_and_solve(self, solver, pack, opts, theta0, prior=None):
         """pack() -> solve -> results on the host; once more without the tall team class if a team barrier timed out.
         prior: (mean, scale) device arrays of an incremental solve (theta0 is then None), else None."""
         if prior is not None:
             solve = lambda packed, opts, theta0=None: self._solve_with_prior(solver, packed, opts, prior)
+        elif getattr(self, "_feature_factor", None) is not None:
+            solve = lambda packed, opts, theta0=None: self._solve_normalised(solver, packed, opts, theta0)
         else:
             solve = solver.solve
         packed = pack()

@@ -15,6 +15,19 @@ _MODEL_TYPES = (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION, cons
 _VARIANCE_MODE = (constants.FULL, constants.SIMPLE)
 
 
+def check_feature_normalization(p, stage_flags):
+    """--feature_normalization / --feature_statistics_file of a stage's parameters: what needs no context is refused at parse time.
+    stage_flags: the other flags of this stage the feature does not run with, as (set?, flag, why)."""
+    from . import feature_stats
+    kind = feature_stats.check_kind(feature_stats.NONE if p.feature_normalization is None else p.feature_normalization)
+    if kind == feature_stats.NONE:
+        return kind
+    for is_set, flag, why in stage_flags:
+        if is_set:
+            raise ValueError(f"--feature_normalization={kind} does not run with {flag}: {why}")
+    return kind
+
+
 def parse_l2_grid(text):
     """'100,10,3,1,0.1' -> (100.0, 10.0, 3.0, 1.0, 0.1): comma-separated finite floats >= 0, at least one, no duplicates."""
     out = []
@@ -129,13 +142,28 @@ class REParams(LRParams):
     # yesterday's model, as Photon-ML defines incremental training (include/gdmix_re.h, "incremental training"). A prior feature an
     # entity's new data lacks keeps its prior mean and variance. Without a prior model the stage trains as without the flag.
     incremental_training: bool = False
+    # not in the reference (Photon-ML's NormalizationType): none (the default, also when the flag is absent), scale_with_standard_deviation
+    # or scale_with_max_magnitude — the L2 term penalises coefficients in normalised units, (l2/2) sum (theta_j / s_j)^2 with s_j from
+    # exact column statistics of the stage's training data (include/gdmix_re.h, "feature normalisation"; feature_stats.py). Models, scores
+    # and metrics stay in the original feature units. --action=inference accepts and ignores both flags.
+    feature_normalization: Optional[str] = None
+    # the statistics as an .npz: read and used when the file exists (no statistics pass runs), computed and written there otherwise
+    feature_statistics_file: Optional[str] = None
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
         return None if self.l2_reg_weights is None else parse_l2_grid(self.l2_reg_weights)
 
+    def normalization(self):
+        """The value of --feature_normalization ("none" without the flag)."""
+        return "none" if self.feature_normalization is None else self.feature_normalization
+
     def __post_init__(self):
         self.l2_grid()      # a bad list is an error at parse time
+        check_feature_normalization(self, (
+            (self.incremental_training, "--incremental_training", "prior variances are in the original feature units, and composing the two is not implemented"),
+            (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep in normalised units is not implemented"),
+            (self.rebalance_entities, "--rebalance_entities", "the factors do not travel with the exchange")))
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         if self.incremental_training and self.rebalance_entities:

@@ -94,6 +94,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_eval_acc_workspace_bytes", "gdmix_re_eval_acc_finish",
     "gdmix_re_join_features", "gdmix_re_score_models_workspace_bytes", "gdmix_re_score_models",
     "gdmix_re_prior_workspace_bytes", "gdmix_re_prior_apply", "gdmix_re_prior_restore",
+    "gdmix_re_feature_extent", "gdmix_re_feature_moments", "gdmix_re_feature_scale_expand",
     "gdmix_re_class_kernel_name", "gdmix_java_string_hash", "gdmix_java_partition_id",
     "gdmix_java_partition_ids_i64")
 
@@ -213,7 +214,11 @@ def load_library():
     lib.gdmix_re_prior_apply.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(_Packed), C.c_void_p]
     lib.gdmix_re_prior_restore.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
-    if lib.gdmix_re_abi_version() != 17:
+    lib.gdmix_re_feature_extent.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gdmix_re_feature_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]
+    lib.gdmix_re_feature_scale_expand.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    if lib.gdmix_re_abi_version() != 18:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib
@@ -801,8 +806,36 @@ class REDeviceSolver:
                                                p(theta), p(theta_thr), p(variance), self._stream()), "gdmix_re_prior_restore")
         return dict(theta=theta, theta_thr=theta_thr, variance=variance)
 
+    # ---- feature normalisation: exact column statistics (include/gdmix_re.h, "feature normalisation"; gdmix_amd/feature_stats.py) ----
+    @_serialised
+    def feature_extent(self, col_ptr, col_width, val_ptr, Z, num_features, count, max_abs_bits, bad):
+        """gdmix_re_feature_extent: pass 1 over Z entries (device pointers), accumulated into count [D] int64 / max_abs_bits [D] int32 (the
+        bit patterns of non-negative floats) / bad [2] int64 = {0, -1} device tensors."""
+        _check(self.lib.gdmix_re_feature_extent(self._h, col_ptr, int(col_width), val_ptr, int(Z), int(num_features), count.data_ptr(),
+                                                max_abs_bits.data_ptr(), bad.data_ptr(), self._stream()), "gdmix_re_feature_extent")
+
+    @_serialised
+    def feature_moments(self, col_ptr, col_width, val_ptr, Z, num_features, limb_bits, shift1, shift2, limbs, bad):
+        """gdmix_re_feature_moments: pass 2, accumulated into limbs [D, 4] int64."""
+        _check(self.lib.gdmix_re_feature_moments(self._h, col_ptr, int(col_width), val_ptr, int(Z), int(num_features), limb_bits.data_ptr(),
+                                                 shift1.data_ptr(), shift2.data_ptr(), limbs.data_ptr(), bad.data_ptr(), self._stream()),
+               "gdmix_re_feature_moments")
+
+    @_serialised
+    def feature_scale_expand(self, packed: PackedBatch, factor):
+        """gdmix_re_feature_scale_expand: factor [num_features] float64 device tensor -> scale [P] float64 in the batch's coefficient order
+        (factor[unique_global] at the feature slots, 1 at the intercept slots), built on the device."""
+        t = self.torch
+        if not factor.is_cuda or factor.dtype != t.float64 or not factor.is_contiguous():
+            raise GdmixReError("feature_scale_expand: factor must be a contiguous float64 device array")
+        scale = t.empty(packed.P, dtype=t.float64, device=self.device)
+        _check(self.lib.gdmix_re_feature_scale_expand(self._h, C.byref(packed.c), int(packed.has_intercept), factor.data_ptr() if factor.numel() else None,
+                                                      int(factor.numel()), scale.data_ptr() if packed.P else None, self._stream()),
+               "gdmix_re_feature_scale_expand")
+        return scale
+
     # ---- sweep: K models of one training batch score another batch (include/gdmix_re.h, "sweep") ------------------------------
-    SWEEP_MODELS_PER_PASS = 8       # GDMIX_RE_SWEEP_MODELS_PER_PASS
+    SWEEP_MODELS_PER_PASS = 8      # GDMIX_RE_SWEEP_MODELS_PER_PASS
 
     @_serialised
     def join_features(self, eval_packed: PackedBatch, train_packed: PackedBatch, train_entity):

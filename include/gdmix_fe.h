@@ -170,6 +170,19 @@ GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, c
  *   While a prior is installed gdmix_fe_restart's theta0 is in theta units: NULL means mu, otherwise phi0 = (theta0 - mu) / s. */
 GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const double* scale, void* stream);
 
+/* ---- (ABI 18) feature normalisation ---------------------------------------------------------------------------------------------------
+ * The fixed-effect half of gdmix_re.h's section of the same name (--feature_normalization, gdmix_amd/fe_model.py): the statistics, their
+ * definitions, bounds and kernels are stated there (gdmix_re_feature_extent / gdmix_re_feature_moments take the reader arrays gdmix_fe_score
+ * takes). Here the data are the training samples of ALL workers: count_j and N are all-reduced with SUM and the bit patterns of max |x| with
+ * MAX after pass 1, every worker derives the same shifts, and the four limb sums per feature are all-reduced with SUM after pass 2 — int64
+ * tensors, exact on any backend — so every worker derives the same factors s_j from the same integers. A worker whose shard is empty still
+ * takes part in the collectives.
+ * Objective. F of the incremental section with mu = 0 and v_j = s_j^2: the penalty is (l2/2) sum_{j in R} (theta_j / s_j)^2. s_D = 1 for the
+ * intercept, regularised or not: this feature's own choice. The caller installs it with gdmix_fe_set_prior(mean = 0, scale = [s, 1]) after
+ * gdmix_fe_create; a warm start follows as gdmix_fe_restart(theta0), which takes theta units while a prior is installed. Everything the
+ * incremental section states for a prior holds: the stop tests apply in phi = theta / s, the threshold to theta, Var(theta_j) = s_j^2 Var'(phi_j).
+ * No entry point is added to this header. */
+
 /* gdmix_fe_score under K coefficient vectors in ONE pass over the shard's non-zeros (csrc/fe_sweep.hip). thetas: HOST array of K device
  * pointers, each [num_features + has_intercept] with the intercept last; score / per_coord: [K][n] float, row k for thetas[k]
  * (per_coord may be NULL). Defined by equivalence: row k is bit for bit what gdmix_fe_score writes for thetas[k] — a row's products

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 17
+#define GDMIX_RE_ABI_VERSION 18
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -525,6 +525,59 @@ GDMIX_API int gdmix_re_prior_apply(gdmix_re_ctx* ctx, const gdmix_re_packed* pac
 GDMIX_API int gdmix_re_prior_restore(gdmix_re_ctx* ctx, const gdmix_re_packed* packed, int has_intercept, const double* mean, const double* scale,
                                      double threshold, const double* phi, const double* var_phi, double* theta, double* theta_thr,
                                      double* variance, void* stream);
+
+/* ---- (ABI 18) feature normalisation: exact column statistics on the device, factors, the expansion to coefficient order ---------------
+ * --feature_normalization (gdmix_amd/params.py; Photon-ML's NormalizationType, not in the reference) penalises coefficients in normalised
+ * units: the objective of gdmix_re_opts with the penalty (l2/2) sum_{j regularised} (theta_j / s_j)^2, which is the incremental section's F
+ * with mu = 0 and v_j = s_j^2. gdmix_re_prior_apply / gdmix_re_solve / gdmix_re_prior_restore solve it as they stand (mean = 0, phi0 =
+ * theta0 / s for a warm start); the stop tests apply in phi, the threshold to theta, Var(theta_j) = s_j^2 Var'(phi_j). What this section adds
+ * is the column statistics the factors come from, csrc/feature_stats.hip.
+ *
+ * Data. The stage's training data: for the random effect the ACTIVE training samples of every partition in the partition list, for the
+ * fixed effect the training samples of all workers. N is their number. Zeros are implicit; sample weights are not used (as in Photon's
+ * summary). Statistics are taken over STORED ENTRIES: a (sample, feature) pair stored twice counts as two entries.
+ * Per feature j of the bag, exact:
+ *     count_j = the number of stored entries (int64),   a_j = max |x| (a float32, carried as its bit pattern)
+ * and from these two alone
+ *     E_j = floor(log2 a_j),  L_j = min(31, 62 - bit_length(count_j)),  shift1_j = 2 L_j - (E_j + 1),  shift2_j = 2 L_j - 2 (E_j + 1).
+ * A feature with count_j = 0 or a_j = 0 is dead (limb_bits 0: it has no accumulator). L_j < 25 (more than 2^37 entries of one feature) is
+ * an error naming the feature: below 25 the square of the column's largest value is no longer exact.
+ * Moments, as exact integers:  I1_j = sum rint(x 2^shift1_j),  I2_j = sum rint(x^2 2^shift2_j): the float32 is widened to fp64, x x is exact,
+ * the scaling is ldexp, the rounding ties-to-even. |x| <= a_j < 2^(E_j + 1), so each term is below 2^(2 L_j) in magnitude; it is split into
+ * a high limb (arithmetic shift by L_j) and a low limb (mask), summed in separate int64 accumulators, which by the choice of L_j cannot
+ * overflow. The host recombines I = hi 2^L + lo. Integer addition commutes: the four accumulators per feature do not depend on the order of
+ * the entries, on how the data are cut into calls, on the launch geometry, on the path (LDS or global) or on the number of workers.
+ * Bound per moment: |I1_j 2^-shift1_j - sum x| <= count_j 2^(E_j + 1 - 2 L_j) / 2, and |I2_j 2^-shift2_j - sum x^2| <= count_j 2^(2 (E_j + 1)
+ * - 2 L_j) / 2 (half a unit of the last place of the scaled integer per entry).
+ * Mean and variance (host, gdmix_amd/feature_stats.py), rounded to fp64 within 1 ulp of the exact rational value of
+ *     mean_j = I1 2^-shift1 / N,     var_j = (I2 2^-shift2 - (I1 2^-shift1)^2 / N) / (N - 1)          (0 for N = 1)
+ * Spark's unbiased variance with the zeros counted. var_j is exactly 0 when N I2 2^(2 L) = I1^2 (a constant dense column), and 0 where the
+ * roundings of the terms leave that integer difference negative.
+ * Factors. scale_with_standard_deviation: s_j = 1 / sqrt(var_j); scale_with_max_magnitude: s_j = 1 / a_j; s_j = 1 where the feature is
+ * dead, where var_j = 0 or where the result is not finite; s = 1 for every intercept ("The intercept" above; for the fixed effect by this
+ * feature's own choice, for regularised and unregularised intercepts alike).
+ *
+ * gdmix_re_feature_extent (pass 1) and gdmix_re_feature_moments (pass 2) are stream-ordered and ACCUMULATE into the caller's arrays (zeroed
+ * before the first call; one call per partition or per chunk of a shard). col: Z column ids of col_width bytes (8: int64, 4: int32, 2:
+ * uint16 — the raw batch's col_global, the wire form's narrower ids, the reader arrays gdmix_fe_score takes), val: Z floats.
+ *   count [D] uint64, max_abs_bits [D] uint32 (the bit pattern of a non-negative float orders as the float does: an unsigned max)
+ *   limb_bits / shift1 / shift2 [D] int32: L_j, shift1_j, shift2_j as derived from the (all-reduced) pass 1; limb_bits 0 for a dead feature
+ *   limbs [D][4] int64: hi and lo of I1, hi and lo of I2
+ *   bad [2]: the caller sets {0, -1}. bad[0] counts the entries of this call that are not finite, whose column is outside [0, D), or (pass 2)
+ *            with |x| >= 2^(E_j + 1), the bound the shifts were made for (on a dead feature: any non-zero value); bad[1] is the smallest index
+ *            of a bad entry within its call (an unsigned atomic min). A bad entry is left out of every accumulator: nothing wraps silently.
+ * Paths. Up to 4 096 features (GDMIX_STATS_LDS_MAX_FEATURES in the environment: a test hook, at most 5 000) the table is private to a
+ * workgroup in LDS, flushed with one global atomic per touched slot; above, global 64-bit integer atomics per entry. A wavefront whose
+ * entries share one column adds them with shuffles first. The two paths give the same bits.
+ * gdmix_re_feature_scale_expand: scale [P] fp64 in the batch's coefficient order from factor [num_features]: factor[unique_global] at the
+ * feature slots, 1 at every intercept slot. Built on the device (P is tens of millions); waits for a deferred compaction itself. */
+GDMIX_API int gdmix_re_feature_extent(gdmix_re_ctx* ctx, const void* col, int col_width, const float* val, int64_t Z, int64_t num_features,
+                                      uint64_t* count, uint32_t* max_abs_bits, int64_t* bad, void* stream);
+GDMIX_API int gdmix_re_feature_moments(gdmix_re_ctx* ctx, const void* col, int col_width, const float* val, int64_t Z, int64_t num_features,
+                                       const int32_t* limb_bits, const int32_t* shift1, const int32_t* shift2, int64_t* limbs, int64_t* bad,
+                                       void* stream);
+GDMIX_API int gdmix_re_feature_scale_expand(gdmix_re_ctx* ctx, const gdmix_re_packed* packed, int has_intercept, const double* factor,
+                                            int64_t num_features, double* scale, void* stream);
 
 /* ---- B4: the upstream Spark partitioner's hash, bit-exact (host functions) ------------------------
  * hashCode over UTF-16 code units in wrapping int32; Math.abs(Int.MinValue) stays negative; Scala %
