@@ -118,6 +118,16 @@ class RawBatch:
             has_label=self.has_label, binary_labels=self.binary_labels)
 
 
+def check_count_labels(y, what="poisson_regression"):
+    """The label check of a count target: every label finite and >= 0 (0 and non-integers are counts too; a negative label has no
+    Poisson likelihood and a non-finite one no loss). ValueError with the first offender otherwise."""
+    y = np.asarray(y)
+    bad = ~(y >= 0) | ~np.isfinite(y)      # (NaN fails y >= 0)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"{what}: labels must be finite and >= 0; label {i} is {float(y[i])!r} ({int(bad.sum())} of {y.size} are not)")
+
+
 class WireRawBatch(RawBatch):
     """A partition as libgdmix_io's gdmix_io_narrow leaves it: the 32-bit hand-over form (per-sample counts, uint16 / int32 feature
     indices, byte labels) next to the arrays both forms share (ent_row_ptr, val, y, offset, weight, uid, ids). to_wire() hands the

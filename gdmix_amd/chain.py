@@ -29,7 +29,7 @@ import time
 import numpy as np
 
 from . import partitioner
-from .constants import LINEAR_REGRESSION as LINEAR, LOGISTIC_REGRESSION as LOGISTIC
+from .constants import LINEAR_REGRESSION as LINEAR, LOGISTIC_REGRESSION as LOGISTIC, POISSON_REGRESSION as POISSON
 from .io import avro, tfrecord
 
 USERS, MOVIES, RATINGS = 943, 1682, 100_000        # MovieLens-100K (scripts/download_process_movieLens_data.py:378-462)
@@ -131,13 +131,14 @@ def _feature_file(path, dim, prefix):
 
 
 def labels_of(data, model_type):
-    """The label column of the chain: the 0/1 response, or the rating itself for linear_regression."""
-    return data["rating"] if model_type == LINEAR else data["response"]
+    """The label column of the chain: the 0/1 response, or the rating itself for linear_regression and for poisson_regression (1 .. 5
+    stars are valid counts)."""
+    return data["rating"] if model_type in (LINEAR, POISSON) else data["response"]
 
 
 def write_global_inputs(root, data, files=4, model_type=LOGISTIC):
     """The fixed-effect stage's inputs: per-record tf.train.Example files (train / validation), metadata, feature list."""
-    linear = model_type == LINEAR
+    linear = model_type in (LINEAR, POISSON)      # real-valued labels
     label = labels_of(data, model_type)
     d = os.path.join(root, "global")
     for name, rows in (("trainingData", np.flatnonzero(data["train"])), ("validationData", np.flatnonzero(~data["train"]))):
@@ -181,7 +182,7 @@ def partition_stage(root, data, stage, prev_train_scores, prev_valid_scores, num
     ent_col = data["entity"][stage]
     ent = data["user"] if stage == "per_user" else data["movie"]
     out = os.path.join(root, stage, "partition")
-    linear = model_type == LINEAR
+    linear = model_type in (LINEAR, POISSON)      # real-valued labels
     label = labels_of(data, model_type)
     parts = set()
     for name, mask, scores, split in (("trainingData", data["train"], prev_train_scores, True), ("validationData", ~data["train"], prev_valid_scores, False)):
@@ -247,14 +248,14 @@ def stage_argv(root, stage, model_type=LOGISTIC, device_metrics=False, l2_grids=
             "--enable_local_indexing=False", "--num_of_consumers=1", "--max_training_queue_size=10"] + common
 
 
-def global_training_scores_argv(root):
-    """linear_regression: the fixed effect writes no training scores after training (fe_model.py, as the reference:
+def global_training_scores_argv(root, model_type=LINEAR):
+    """linear_regression and poisson_regression: the fixed effect writes no training scores after training (fe_model.py, as the reference:
     fixed_effect_lr_lbfgs_model.py:106-110), and the per-user partition job needs them as offsets. They come from an inference run of the
     trained model over the training data — the fixed-effect driver scores --validation_data_dir into --validation_score_dir."""
     d, out = os.path.join(root, "global"), os.path.join(root, "global")
     return ["gdmix", "--stage=fixed_effect", "--action=inference", f"--validation_data_dir={d}/trainingData", f"--metadata_file={d}/metadata/tensor_metadata.json",
             f"--feature_file={d}/featureList", "--feature_bag=global", f"--output_model_dir={out}/models", f"--validation_score_dir={out}/trainingScores",
-            f"--model_type={LINEAR}"] + COMMON
+            f"--model_type={model_type}"] + COMMON
 
 
 def run_stage(argv, child_process=False):
@@ -296,18 +297,28 @@ def mse(label, score):
     return float(np.mean(d * d)) if d.size else float("nan")
 
 
+def poisson_loss(label, score):
+    """Mean of exp(score) - label score: what a poisson_regression stage reports (metrics.poisson_loss_terms states the terms)."""
+    from .metrics import poisson_loss_terms
+    t = poisson_loss_terms(score, label)
+    return float(np.mean(t)) if t.size else float("nan")
+
+
 def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper_bounds=None, model_type=LOGISTIC, device_metrics=True, l2_grids=None):
     """global -> per_user -> per_movie under `root`; -> {stage: {"s", "partition_s", "train_auc", "validation_auc"}, "total_s"}.
     device_metrics: the two random-effect stages also report the metric they computed on the device while scoring
     ("train_<metric>_device", "validation_<metric>_device", from <root>/<stage>/metrics/evalSummary.json).
     upper_bounds: {stage: active-data bound per entity} (the rest of a larger entity's samples is passive data).
     model_type="linear_regression": every stage gets that model type, the labels are the ratings (real-valued), and a stage reports
-    "train_mse" / "validation_mse" instead of the AUC.
+    "train_mse" / "validation_mse" instead of the AUC. model_type="poisson_regression": the same with the ratings as counts and
+    "train_poisson_loss" / "validation_poisson_loss".
     l2_grids: {stage: "w0,w1,..."} — a stage listed there sweeps l2_reg_weight inside the stage (stage_argv); its result gains
     "l2_reg_weight" (the winner, from <root>/<stage>/metrics/sweep/evals.json) and the device metrics, the global stage's too."""
-    if model_type not in (LOGISTIC, LINEAR):
-        raise ValueError(f"model type {model_type!r}: the chain runs logistic_regression and linear_regression")
-    metric = "mse" if model_type == LINEAR else "auc"
+    if model_type not in (LOGISTIC, LINEAR, POISSON):
+        raise ValueError(f"model type {model_type!r}: the chain runs logistic_regression and linear_regression, and poisson_regression on count labels")
+    if model_type == POISSON and l2_grids:
+        raise ValueError("l2_grids does not run with poisson_regression: the sweep compares auc or mse")
+    metric = {LINEAR: "mse", POISSON: "poisson_loss"}.get(model_type, "auc")
     os.makedirs(root, exist_ok=True)
     write_global_inputs(root, data, model_type=model_type)
     out = {}
@@ -323,13 +334,13 @@ def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper
         t = time.perf_counter()
         swept = (l2_grids or {}).get(stage) is not None
         run_stage(stage_argv(root, stage, model_type, device_metrics, l2_grids), child_process)
-        if stage == "global" and model_type == LINEAR:
-            run_stage(global_training_scores_argv(root), child_process)
+        if stage == "global" and model_type in (LINEAR, POISSON):
+            run_stage(global_training_scores_argv(root, model_type), child_process)
         dt = time.perf_counter() - t
         r = {"s": dt, "partition_s": t_part}
         for which, d in (("train", "trainingScores"), ("validation", "validationScores")):
             uid, sc, _, lab = read_scores(os.path.join(root, stage, d))
-            r[f"{which}_{metric}"] = mse(lab, sc) if metric == "mse" else auc(lab, sc)
+            r[f"{which}_{metric}"] = {"mse": mse, "poisson_loss": poisson_loss}.get(metric, auc)(lab, sc)
             r[which + "_samples"] = int(uid.size)
         summary = os.path.join(metric_dir(root, stage), "evalSummary.json")
         if ((device_metrics and stage != "global") or swept) and os.path.exists(summary):

@@ -7,6 +7,7 @@ by what uses them."""
 ACTION_TRAIN, ACTION_INFERENCE = "train", "inference"
 FIXED_EFFECT, RANDOM_EFFECT, DETEXT = "fixed_effect", "random_effect", "detext"
 LOGISTIC_REGRESSION, LINEAR_REGRESSION = "logistic_regression", "linear_regression"
+POISSON_REGRESSION = "poisson_regression"      # count targets: the loss exp(z) - y z (include/gdmix_re.h, "poisson")
 
 # data layout: <training_data_dir>/{active,passive}/partitionId=K/*.tfrecord; variance modes; the intercept's feature name
 ACTIVE, PASSIVE = "active", "passive"
@@ -23,4 +24,6 @@ TF_CONFIG = "TF_CONFIG"
     "active_training_output_file", "passive_training_output_file", "validation_output_file", "passive_training_data_dir")
 
 # modelClass written into the photon-ml model records
+LBFGS_MODEL_TYPES = (LOGISTIC_REGRESSION, LINEAR_REGRESSION, POISSON_REGRESSION)      # what the two L-BFGS stages train
 PHOTON_LR_MODEL_CLASS = "com.linkedin.photon.ml.supervised.classification.LogisticRegressionModel"
+PHOTON_POISSON_MODEL_CLASS = "com.linkedin.photon.ml.supervised.regression.PoissonRegressionModel"

@@ -166,9 +166,13 @@ __device__ __forceinline__ void fe_emit_row(const FeDev& F, const SolveParams& o
   const double yi = (double)F.y[s];
   const double wi = F.w ? (double)F.w[s] : 1.0;
   double ri;
-  if (HESS) {
+  if (HESS && o.linear == LOSS_POISSON) {
+    ri = wi * exp_any(zi);      // d_i = w_i exp(z_i) (include/gdmix_fe.h, "poisson")
+  } else if (HESS) {
     const double rho = sigmoid_full(zi);
     ri = wi * rho * (1.0 - rho);
+  } else if (o.linear == LOSS_POISSON) {
+    dd_add(loss, loss_lo, poisson_terms(zi, yi, wi, ri));
   } else if (o.linear) {
     const double e = zi - yi;
     dd_add(loss, loss_lo, wi * e * e);
@@ -1417,6 +1421,7 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   if (!ctx || !b || !opts) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
   if (b->E != 1) { set_error("the shard must be packed as one entity (E = %lld)", (long long)b->E); return GDMIX_RE_EINVAL; }
   if (opts->m < 1 || opts->m > TEAM_MCAP) { set_error("1 <= m <= %d", TEAM_MCAP); return GDMIX_RE_EINVAL; }
+  if (!loss_code_ok(opts->linear, "gdmix_fe_create")) return GDMIX_RE_EINVAL;
   if (opts->regularize_bias && !opts->has_intercept) { set_error("regularize_bias requires has_intercept"); return GDMIX_RE_EINVAL; }
   if (num_features < 1 || num_features > 0x7ffffff0ll) { set_error("bad num_features"); return GDMIX_RE_EINVAL; }
   if (b->Z > 0x7ffffff0ll || b->N > 0x7ffffff0ll) { set_error("shard exceeds 2^31 samples or non-zeros"); return GDMIX_RE_ERANGE; }
@@ -1457,7 +1462,7 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   SolveParams& o = p->o;
   o.l2 = opts->l2; o.ftol = opts->ftol; o.pgtol = opts->pgtol; o.threshold = 0.0; o.regularize_bias = opts->regularize_bias;
   o.has_intercept = ic; o.m = opts->m; o.max_iter = opts->max_iter; o.maxfun = opts->maxfun; o.maxls = opts->maxls;
-  o.variance_mode = 0; o.sum_loss = 1; o.linear = opts->linear ? 1 : 0;
+  o.variance_mode = 0; o.sum_loss = 1; o.linear = opts->linear;
   // row pass: outputs = rows, gathered = x by local column: from the column-major arrays. Column pass: the other way round.
   std::vector<int32_t> uf_r, uf_c;
   int rc2 = fe_build_copy(s, ci->num_cus, b->col_ptr, F.d, b->csc_row, b->csc_val, F.z, F.n, false, (p->compress & 1) != 0, &F.rc, &p->copies[0],
@@ -1524,9 +1529,9 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
 GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, const double* theta0, void* stream) {
   if (!p || !opts) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
   const FeDev& F = p->F;
-  if ((opts->has_intercept ? 1 : 0) != F.ic || opts->m != F.m || (opts->linear ? 1 : 0) != p->o.linear) {
+  if ((opts->has_intercept ? 1 : 0) != F.ic || opts->m != F.m || opts->linear != p->o.linear) {
     set_error("gdmix_fe_restart: has_intercept, linear and m must be the creation's (%d, %d, %d), not (%d, %d, %d): the pool is sized by them",
-              F.ic, p->o.linear, F.m, opts->has_intercept ? 1 : 0, opts->linear ? 1 : 0, opts->m);
+              F.ic, p->o.linear, F.m, opts->has_intercept ? 1 : 0, opts->linear, opts->m);
     return GDMIX_RE_EINVAL;
   }
   if (opts->regularize_bias && !opts->has_intercept) { set_error("regularize_bias requires has_intercept"); return GDMIX_RE_EINVAL; }
@@ -1606,8 +1611,8 @@ GDMIX_API size_t gdmix_fe_hessian_dense_scratch_bytes(const gdmix_re_packed* sha
   return shard ? hessian_dense_scratch_doubles(shard->N) * 8 : 0;
 }
 
-GDMIX_API int gdmix_fe_hessian_dense(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int has_intercept, const double* theta_local, double* H,
-                                     int64_t ld, void* scratch, size_t scratch_bytes, void* stream) {
+static int fe_hessian_dense(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int has_intercept, int loss, const double* theta_local, double* H,
+                            int64_t ld, void* scratch, size_t scratch_bytes, void* stream) {
   if (!ctx || !b || !theta_local || !H || !scratch) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
   if (b->E != 1) { set_error("gdmix_fe_hessian_dense takes a one-entity batch (a worker's shard)"); return GDMIX_RE_EINVAL; }
   const int ic = has_intercept ? 1 : 0;
@@ -1616,8 +1621,19 @@ GDMIX_API int gdmix_fe_hessian_dense(gdmix_re_ctx* ctx, const gdmix_re_packed* b
   if (scratch_bytes < hessian_dense_scratch_doubles(b->N) * 8) { set_error("scratch too small"); return GDMIX_RE_ENOMEM; }
   HIP_TRY(hipSetDevice(ctx->impl.device));
   const BatchDev B = batch_dev(b);
-  HIP_TRY(launch_hessian_dense(&ctx->impl, B, b->N, b->D, ic, theta_local, H, ld, static_cast<double*>(scratch), static_cast<hipStream_t>(stream)));
+  HIP_TRY(launch_hessian_dense(&ctx->impl, B, b->N, b->D, ic, theta_local, H, ld, static_cast<double*>(scratch), static_cast<hipStream_t>(stream), loss));
   return GDMIX_RE_OK;
+}
+
+GDMIX_API int gdmix_fe_hessian_dense(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int has_intercept, const double* theta_local, double* H,
+                                     int64_t ld, void* scratch, size_t scratch_bytes, void* stream) {
+  return fe_hessian_dense(ctx, b, has_intercept, GDMIX_RE_LOSS_LOGISTIC, theta_local, H, ld, scratch, scratch_bytes, stream);
+}
+
+GDMIX_API int gdmix_fe_hessian_dense_loss(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int has_intercept, int loss, const double* theta_local,
+                                          double* H, int64_t ld, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!loss_code_ok(loss, "gdmix_fe_hessian_dense_loss")) return GDMIX_RE_EINVAL;
+  return fe_hessian_dense(ctx, b, has_intercept, loss, theta_local, H, ld, scratch, scratch_bytes, stream);
 }
 
 GDMIX_API int gdmix_fe_variance_of_hessian(gdmix_re_ctx* ctx, double* H, int64_t p, int64_t ld, double l2, int64_t unregularised_index,

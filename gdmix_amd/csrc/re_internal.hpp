@@ -401,6 +401,12 @@ hipError_t launch_solve_tall(int variant, const BatchDev& B, const OutDev& O, co
 hipError_t launch_solve_tall_team(const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0, int begin, int count,
                                   int num_cus, int64_t Z, void* tail_buf, void* team_buf, int xcd_fast, hipStream_t s);
 void launch_sort_class(int32_t* list, int count, const int64_t* ent_nnz_ptr, hipStream_t s);
+static_assert(LOSS_LOGISTIC == GDMIX_RE_LOSS_LOGISTIC && LOSS_SQUARED == GDMIX_RE_LOSS_SQUARED && LOSS_POISSON == GDMIX_RE_LOSS_POISSON,
+              "the device's loss codes are the header's");
+// gdmix_re_opts.linear is a loss code: anything but the three is refused (sets the error text)
+bool loss_code_ok(int code, const char* who);
+hipError_t launch_variance_simple_poi(const BatchDev& B, const SolveParams& o, const double* theta, double* variance, int begin, int count,
+                                      double* scratch, size_t slot_doubles, int slots, hipStream_t s);
 hipError_t launch_variance_simple_lin(const BatchDev& B, const SolveParams& o, double* variance, int begin, int count, int num_cus, hipStream_t s);
 hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams& o, const double* theta, double* variance,
                                 double* scratch, size_t slot_doubles, int slots, int64_t max_p, hipStream_t s);
@@ -412,7 +418,7 @@ hipError_t launch_variance_full_big(gdmix_ctx_impl* ci, const BatchDev& B, int64
                                     double* variance, double* scratch, int64_t max_p, int64_t max_n, hipStream_t s);
 size_t hessian_dense_scratch_doubles(int64_t n);
 hipError_t launch_hessian_dense(gdmix_ctx_impl* ci, const BatchDev& B, int64_t n, int64_t d, int ic, const double* theta, double* H, int64_t ld,
-                                double* scratch, hipStream_t s);
+                                double* scratch, hipStream_t s, int loss = LOSS_LOGISTIC);
 hipError_t launch_variance_of_hessian(gdmix_ctx_impl* ci, double* H, double* M, int64_t p, int64_t ld, double l2, int64_t unreg, double* variance,
                                       hipStream_t s);
 inline size_t var_full_slot_doubles(int64_t max_p) { return (size_t)2 * max_p * max_p + max_p + 8; }

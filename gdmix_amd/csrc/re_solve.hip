@@ -48,9 +48,9 @@ __device__ __forceinline__ void write_results(G& grp, const OutDev& O, const Sol
 // offset is an instruction immediate off one base register (runtime offsets cost ~12 VGPRs of addresses).
 // G < 64: 64/G entities per wavefront; G = 64: one; G > 64: one entity per workgroup of G/64 wavefronts
 // (cross-wave stage of every reduction through LDS + one barrier).
-// LIN: the loss of the instantiation (re_device.hpp, loss_terms), a template parameter of every solve kernel: the <false> instantiations
-// hold the code they held before the squared loss existed; the launchers choose by SolveParams::linear.
-template <int G, int EPL, int NCAP, int ZCAP, bool LIN>
+// LOSS: the loss code of the instantiation (re_device.hpp, loss_terms), a template parameter of every solve kernel: the <LOSS_LOGISTIC>
+// instantiations hold the code they held before the other losses existed; the launchers choose by SolveParams::linear.
+template <int G, int EPL, int NCAP, int ZCAP, int LOSS>
 __global__ __launch_bounds__(G > WAVE ? G : WAVE)
 __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 ? GDMIX_QUAD_WAVES_EPL4 : 1)))) void re_solve_grp_kernel(
     BatchDev B, OutDev O, SolveParams o, const double* __restrict__ theta0, int begin, int count) {
@@ -113,7 +113,7 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
   }
   grp_fence<G>();
   SolveStats st;
-  quad_solve<G, EPL, (NCAP > G), LIN>(L, o, gl, n, p, ic, valid, rowc, colc, V, X, st);
+  quad_solve<G, EPL, (NCAP > G), LOSS>(L, o, gl, n, p, ic, valid, rowc, colc, V, X, st);
   if (!valid) return;
 
 #pragma unroll
@@ -147,8 +147,12 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
     double dpart = 0.0;
     for (int i = gl; i < n; i += G) {
       double di;
-      if constexpr (LIN) {   // D_i = 2 w_i: the squared loss has the same curvature at every theta
+      if constexpr (LOSS == LOSS_SQUARED) {   // D_i = 2 w_i: the squared loss has the same curvature at every theta
         di = 2.0 * (L.has_w ? (double)L.w()[i] : 1.0);
+      } else if constexpr (LOSS == LOSS_POISSON) {   // D_i = w_i exp(z_i)
+        const int k0 = L.row_ptr()[i], k1 = L.row_ptr()[i + 1];
+        const double z = gather_dot(L.csr() + k0, k1 - k0, xs + ic, x0) + (double)L.o()[i];
+        di = exp_any(z) * (L.has_w ? (double)L.w()[i] : 1.0);
       } else {
         const int k0 = L.row_ptr()[i], k1 = L.row_ptr()[i + 1];
         const double z = gather_dot(L.csr() + k0, k1 - k0, xs + ic, x0) + (double)L.o()[i];
@@ -188,15 +192,15 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
   }
 }
 
-template <int G, int EPL, int NCAP, int ZCAP, bool LIN>
+template <int G, int EPL, int NCAP, int ZCAP, int LOSS>
 static hipError_t launch_quad_t(const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0,
                                 int begin, int count, hipStream_t s) {
   constexpr int NG = G >= WAVE ? 1 : WAVE / G;
   constexpr int NWG = G > WAVE ? G / WAVE : 1;
   const int row_lds_bytes = quad_layout(G * EPL, NCAP, ZCAP, NWG).bytes;
   static DynLdsOnce lds_attr;
-  if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_grp_kernel<G, EPL, NCAP, ZCAP, LIN>)); rc != hipSuccess) return rc;
-  hipLaunchKernelGGL((re_solve_grp_kernel<G, EPL, NCAP, ZCAP, LIN>), dim3((count + NG - 1) / NG), dim3(G > WAVE ? G : WAVE),
+  if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_grp_kernel<G, EPL, NCAP, ZCAP, LOSS>)); rc != hipSuccess) return rc;
+  hipLaunchKernelGGL((re_solve_grp_kernel<G, EPL, NCAP, ZCAP, LOSS>), dim3((count + NG - 1) / NG), dim3(G > WAVE ? G : WAVE),
                      (size_t)row_lds_bytes * NG, s, B, O, o, theta0, begin, count);
   return hipGetLastError();
 }
@@ -206,7 +210,9 @@ hipError_t launch_solve_quad(int g, int epl, const BatchDev& B, const OutDev& O,
   if (count <= 0) return hipSuccess;
 #define GDMIX_GRP_CASE(GG, EE, NN, ZZ) \
   if (g == GG && epl == EE && ncap == NN && zcap == ZZ)                                                            \
-    return o.linear ? launch_quad_t<GG, EE, NN, ZZ, true>(B, O, o, theta0, begin, count, s) : launch_quad_t<GG, EE, NN, ZZ, false>(B, O, o, theta0, begin, count, s);
+    return o.linear == LOSS_POISSON ? launch_quad_t<GG, EE, NN, ZZ, LOSS_POISSON>(B, O, o, theta0, begin, count, s)                 \
+           : o.linear ? launch_quad_t<GG, EE, NN, ZZ, LOSS_SQUARED>(B, O, o, theta0, begin, count, s)                                \
+                      : launch_quad_t<GG, EE, NN, ZZ, LOSS_LOGISTIC>(B, O, o, theta0, begin, count, s);
   GDMIX_GRP_CASE(16, 2, 16, 64) GDMIX_GRP_CASE(16, 2, 32, 128) GDMIX_GRP_CASE(16, 2, 128, 512)
   GDMIX_GRP_CASE(16, 3, 16, 64) GDMIX_GRP_CASE(16, 3, 32, 128) GDMIX_GRP_CASE(16, 3, 128, 512)
   GDMIX_GRP_CASE(16, 4, 16, 64) GDMIX_GRP_CASE(16, 4, 32, 128) GDMIX_GRP_CASE(16, 4, 128, 512)
@@ -223,7 +229,7 @@ hipError_t launch_solve_quad(int g, int epl, const BatchDev& B, const OutDev& O,
 // ---------------------------------------------------------------------------------------------------
 // one wavefront per entity, everything LDS-resident
 // ---------------------------------------------------------------------------------------------------
-template <bool LIN>
+template <int LOSS>
 __global__ __launch_bounds__(WAVE) void re_solve_wave_kernel(BatchDev B, OutDev O, SolveParams o,
                                                              const double* __restrict__ theta0, int begin) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -284,29 +290,34 @@ __global__ __launch_bounds__(WAVE) void re_solve_wave_kernel(BatchDev B, OutDev 
   grp.sync();
   EntityView P{n, d, p, ic, s_row_ptr, s_csr_col, s_csr_val, s_col_ptr, s_csc_row, s_csc_val, s_y, s_o, s_w};
   SolveStats st;
-  lbfgs_solve<LIN>(grp, P, o, W, st);
+  lbfgs_solve<LOSS>(grp, P, o, W, st);
   write_results(grp, O, o, e, c0, p, W.x, st);
-  if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) variance_simple<false, LIN>(grp, P, o, W, O.variance + c0);
+  if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) variance_simple<false, LOSS>(grp, P, o, W, O.variance + c0);
 }
 
 hipError_t launch_solve_wave(const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0,
                              int begin, int count, int lds_bytes, hipStream_t s) {
   if (count <= 0) return hipSuccess;
-  static DynLdsOnce lds_attr, lin_attr;
-  if (o.linear) {
-    if (hipError_t rc = lin_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<true>)); rc != hipSuccess) return rc;
-    hipLaunchKernelGGL(re_solve_wave_kernel<true>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
+  static DynLdsOnce lds_attr, lin_attr, poi_attr;
+  if (o.linear == LOSS_POISSON) {
+    if (hipError_t rc = poi_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<LOSS_POISSON>)); rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(re_solve_wave_kernel<LOSS_POISSON>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
     return hipGetLastError();
   }
-  if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<false>)); rc != hipSuccess) return rc;
-  hipLaunchKernelGGL(re_solve_wave_kernel<false>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
+  if (o.linear) {
+    if (hipError_t rc = lin_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<LOSS_SQUARED>)); rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(re_solve_wave_kernel<LOSS_SQUARED>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
+    return hipGetLastError();
+  }
+  if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<LOSS_LOGISTIC>)); rc != hipSuccess) return rc;
+  hipLaunchKernelGGL(re_solve_wave_kernel<LOSS_LOGISTIC>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
   return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------
 // one workgroup per entity, state in a global scratch slot, X streamed from HBM/L2
 // ---------------------------------------------------------------------------------------------------
-template <bool LIN>
+template <int LOSS>
 __global__ __launch_bounds__(WAVE* BLOCK_NW) void re_solve_block_kernel(BatchDev B, OutDev O, SolveParams o,
                                                                         const double* __restrict__ theta0,
                                                                         int begin, int count, double* scratch,
@@ -340,9 +351,9 @@ __global__ __launch_bounds__(WAVE* BLOCK_NW) void re_solve_block_kernel(BatchDev
     EntityView P{n, d, p, ic, B.row_ptr + r0 + e, B.csr_col + z0, B.csr_val + z0, B.col_ptr + z0 + e,
                  B.csc_row + z0, B.csc_val + z0, B.y + r0, B.offset + r0, B.weight ? B.weight + r0 : nullptr};
     SolveStats st;
-    lbfgs_solve<LIN>(grp, P, o, W, st);
+    lbfgs_solve<LOSS>(grp, P, o, W, st);
     write_results(grp, O, o, e, c0, p, W.x, st);
-    if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) variance_simple<false, LIN>(grp, P, o, W, O.variance + c0);
+    if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) variance_simple<false, LOSS>(grp, P, o, W, O.variance + c0);
     grp.sync();   // the slot is reused by the next entity
   }
 }
@@ -569,11 +580,14 @@ hipError_t launch_solve_block(const BatchDev& B, const OutDev& O, const SolvePar
   if (count <= 0) return hipSuccess;
   if (o.m > TEAM_MCAP) {   // two-loop form, any m
     int grid = count < slots ? count : slots;
-    if (o.linear)
-      hipLaunchKernelGGL(re_solve_block_kernel<true>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
+    if (o.linear == LOSS_POISSON)
+      hipLaunchKernelGGL(re_solve_block_kernel<LOSS_POISSON>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
+                         scratch, slot_doubles, max_p);
+    else if (o.linear)
+      hipLaunchKernelGGL(re_solve_block_kernel<LOSS_SQUARED>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
                          scratch, slot_doubles, max_p);
     else
-      hipLaunchKernelGGL(re_solve_block_kernel<false>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
+      hipLaunchKernelGGL(re_solve_block_kernel<LOSS_LOGISTIC>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
                          scratch, slot_doubles, max_p);
     return hipGetLastError();
   }
@@ -673,8 +687,8 @@ hipError_t launch_variance_simple_lin(const BatchDev& B, const SolveParams& o, d
 // inverse comes from a Cholesky factor: diag(H^-1)_j = sum_i (L^-1)_ij^2 (the reference uses LU,
 // np.linalg.inv; both agree to rounding on these well-conditioned matrices).
 // ---------------------------------------------------------------------------------------------------
-// LIN: D_i = 2 w_i (the squared loss; include/gdmix_re.h, `linear`)
-template <bool LIN>
+// LOSS: the loss code; squared: D_i = 2 w_i, Poisson: D_i = w_i exp(z_i) (include/gdmix_re.h, `linear`)
+template <int LOSS>
 __global__ __launch_bounds__(256) void re_variance_full_kernel(BatchDev B, int64_t E, SolveParams o,
                                                                const double* __restrict__ theta,
                                                                double* __restrict__ variance, double* scratch,
@@ -703,8 +717,12 @@ __global__ __launch_bounds__(256) void re_variance_full_kernel(BatchDev B, int64
       const int k0 = rp[i], k1 = rp[i + 1];
       // logit and D_i (every lane computes the same scalar)
       double di;
-      if constexpr (LIN) {
+      if constexpr (LOSS == LOSS_SQUARED) {
         di = 2.0 * (B.weight ? (double)B.weight[r0 + i] : 1.0);
+      } else if constexpr (LOSS == LOSS_POISSON) {
+        double acc = ic ? th[0] : 0.0;
+        for (int k = k0; k < k1; ++k) acc += (double)B.csr_val[z0 + k] * th[ic + B.csr_col[z0 + k]];
+        di = exp_any(acc + (double)B.offset[r0 + i]) * (B.weight ? (double)B.weight[r0 + i] : 1.0);
       } else {
         double acc = ic ? th[0] : 0.0;
         for (int k = k0; k < k1; ++k) acc += (double)B.csr_val[z0 + k] * th[ic + B.csr_col[z0 + k]];
@@ -770,6 +788,38 @@ __global__ __launch_bounds__(256) void re_variance_full_kernel(BatchDev B, int64
   }
 }
 
+// The same for the Poisson loss, whose D_i = w_i exp(z_i) needs the margins at the returned theta: variance_simple<false, LOSS_POISSON> of
+// re_solve_core.hpp, one workgroup per entity, D in the head of the workgroup's scratch slot (the team kernels that used it are done).
+__global__ __launch_bounds__(WAVE* BLOCK_NW) void re_variance_simple_poi_kernel(BatchDev B, SolveParams o, const double* __restrict__ theta,
+                                                                                double* __restrict__ variance, int begin, int count,
+                                                                                double* scratch, size_t slot_doubles) {
+  __shared__ double red[2 * BLOCK_NW];
+  const int ic = o.has_intercept ? 1 : 0;
+  BlockGroup<BLOCK_NW> grp{(int)threadIdx.x, red, 0};
+  Work W{};
+  W.rs = scratch + (size_t)blockIdx.x * slot_doubles;   // [n] of the slot's >= max_n doubles
+  for (int idx = blockIdx.x; idx < count; idx += gridDim.x) {
+    const int64_t e = B.order[begin + idx];
+    const int64_t r0 = B.ent_row_ptr[e], z0 = B.ent_nnz_ptr[e], f0 = B.ent_feat_ptr[e];
+    const int n = (int)(B.ent_row_ptr[e + 1] - r0);
+    const int d = (int)(B.ent_feat_ptr[e + 1] - f0);
+    const int64_t c0 = f0 + e * ic;
+    W.x = const_cast<double*>(theta) + c0;
+    EntityView P{n, d, d + ic, ic, B.row_ptr + r0 + e, B.csr_col + z0, B.csr_val + z0, B.col_ptr + z0 + e,
+                 B.csc_row + z0, B.csc_val + z0, B.y + r0, B.offset + r0, B.weight ? B.weight + r0 : nullptr};
+    variance_simple<false, LOSS_POISSON>(grp, P, o, W, variance + c0);   // (ends on a barrier: the slot is free for the next entity)
+  }
+}
+
+hipError_t launch_variance_simple_poi(const BatchDev& B, const SolveParams& o, const double* theta, double* variance, int begin, int count,
+                                      double* scratch, size_t slot_doubles, int slots, hipStream_t s) {
+  if (count <= 0) return hipSuccess;
+  const int grid = count < slots ? count : slots;
+  hipLaunchKernelGGL(re_variance_simple_poi_kernel, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, o, theta, variance, begin, count, scratch,
+                     slot_doubles);
+  return hipGetLastError();
+}
+
 hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams& o, const double* theta, double* variance,
                                 double* scratch, size_t slot_doubles, int slots, int64_t max_p, hipStream_t s) {
   if (E <= 0) return hipSuccess;
@@ -777,11 +827,14 @@ hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams&
   if ((int64_t)waves > E) waves = (int)E;
   const int blocks = (waves + 3) / 4;
   // every wave of the grid owns one slot: grid = blocks * 4 waves <= slots is ensured by the caller
-  if (o.linear)
-    hipLaunchKernelGGL(re_variance_full_kernel<true>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
+  if (o.linear == LOSS_POISSON)
+    hipLaunchKernelGGL(re_variance_full_kernel<LOSS_POISSON>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
+                       slot_doubles, max_p);
+  else if (o.linear)
+    hipLaunchKernelGGL(re_variance_full_kernel<LOSS_SQUARED>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
                        slot_doubles, max_p);
   else
-    hipLaunchKernelGGL(re_variance_full_kernel<false>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
+    hipLaunchKernelGGL(re_variance_full_kernel<LOSS_LOGISTIC>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
                        slot_doubles, max_p);
   return hipGetLastError();
 }

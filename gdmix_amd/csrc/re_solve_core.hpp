@@ -13,7 +13,7 @@ namespace gdmix {
 struct SolveParams {
   double l2, ftol, pgtol, threshold;
   int regularize_bias, has_intercept, m, max_iter, maxfun, maxls, variance_mode;
-  int sum_loss, linear;   // sum_loss: fixed-effect objective (team kernels only); linear: squared loss (the launchers pick the <LIN> kernels by it)
+  int sum_loss, linear;   // sum_loss: fixed-effect objective (team kernels only); linear: the loss code, LOSS_* of re_device.hpp (the launchers pick the <LOSS> kernels by it)
 };
 
 // One entity's data, pointers into LDS (wave kernel) or HBM (block kernel).
@@ -48,8 +48,8 @@ struct Work {
 constexpr double EPSMCH = 2.220446049250313e-16;
 
 // f and g at W.x. Returns f; leaves g in W.g. One pass over the CSR copy for the logits, one pass over
-// the CSC copy for X'r: both are ordered sums, no atomics. LIN: squared loss (re_device.hpp, loss_terms).
-template <bool LIN = false, class G>
+// the CSC copy for X'r: both are ordered sums, no atomics. LOSS: the loss code (re_device.hpp, loss_terms).
+template <int LOSS = LOSS_LOGISTIC, class G>
 __device__ __forceinline__ double eval_fg(G& grp, const EntityView& P, const SolveParams& o, const Work& W) {
   const int n = P.n, p = P.p, ic = P.ic;
   const double* __restrict__ x = W.x;
@@ -64,7 +64,7 @@ __device__ __forceinline__ double eval_fg(G& grp, const EntityView& P, const Sol
     const double yi = (double)P.y[i];
     const double wi = P.w ? (double)P.w[i] : 1.0;
     double ri;
-    part += loss_terms<LIN>(z, yi, wi, ri);
+    part += loss_terms<LOSS>(z, yi, wi, ri);
     W.rs[i] = ri;
     rpart += ri;
   }
@@ -275,12 +275,12 @@ __device__ void lbfgs_advance(G& grp, int p, const SolveParams& o, const Work& W
 }
 
 // The whole fmin_l_bfgs_b run for one entity (wave-per-entity LDS kernel, workgroup-per-entity kernel).
-template <bool LIN = false, class G>
+template <int LOSS = LOSS_LOGISTIC, class G>
 __device__ void lbfgs_solve(G& grp, const EntityView& P, const SolveParams& o, const Work& W, SolveStats& out) {
   LbfgsState T;
   lbfgs_init(T);
   do {
-    const double f = eval_fg<LIN>(grp, P, o, W);
+    const double f = eval_fg<LOSS>(grp, P, o, W);
     lbfgs_advance(grp, P.p, o, W, T, f);
   } while (T.status < 0);
   out.f = T.f;
@@ -294,8 +294,9 @@ __device__ void lbfgs_solve(G& grp, const EntityView& P, const SolveParams& o, c
 // D_i = rho_i (1-rho_i) w_i. Duplicate (row, col) entries are summed before squaring, as the reference's
 // toarray() does. W.rs is reused for D. Squared loss: D_i = 2 w_i (include/gdmix_re.h, `linear`).
 // SC1: the team's exchanged vectors (W.x, W.rs) are accessed through sc1 loads / stores (re_device.hpp, ld_x / st_x)
-// LIN: the squared loss (the team kernels hold both losses in one instantiation and stay logistic here: re_solve.hip, re_variance_simple_lin_kernel)
-template <bool SC1 = false, bool LIN = false, class G>
+// LOSS: the loss code; Poisson: D_i = w_i exp(z_i) (the team kernels hold the losses in one instantiation and stay logistic here: re_solve.hip,
+// re_variance_simple_lin_kernel, re_variance_simple_poi_kernel)
+template <bool SC1 = false, int LOSS = LOSS_LOGISTIC, class G>
 __device__ __forceinline__ void variance_simple(G& grp, const EntityView& P, const SolveParams& o, const Work& W,
                                                 double* var_out) {
   const int n = P.n, p = P.p, ic = P.ic;
@@ -307,8 +308,10 @@ __device__ __forceinline__ void variance_simple(G& grp, const EntityView& P, con
     const int k1 = P.row_ptr[i + 1];
     for (int k = P.row_ptr[i]; k < k1; ++k) acc += (double)P.csr_val[k] * ld_x<SC1>(x + ic + P.csr_col[k]);
     double di;
-    if constexpr (LIN) {
+    if constexpr (LOSS == LOSS_SQUARED) {
       di = 2.0 * (P.w ? (double)P.w[i] : 1.0);
+    } else if constexpr (LOSS == LOSS_POISSON) {
+      di = exp_any(acc + (double)P.o[i]) * (P.w ? (double)P.w[i] : 1.0);
     } else {
       const double z = acc + (double)P.o[i];
       const double rho = 1.0 / (1.0 + exp(-z));

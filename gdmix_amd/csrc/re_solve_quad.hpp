@@ -402,8 +402,8 @@ __device__ __forceinline__ void gather_dot1_cols(const int2* csc, const unsigned
 
 // f and g at xt. rowc: packed (start | len << 16) of the lane's first sample; colc[s]: same for the
 // lane's coefficient slots (len = 0 for the intercept / unused slots).
-// LIN: squared loss (re_device.hpp, loss_terms).
-template <int G, int EPL, bool LONG_COLS = true, bool LIN = false>
+// LOSS: the loss code (re_device.hpp, loss_terms).
+template <int G, int EPL, bool LONG_COLS = true, int LOSS = LOSS_LOGISTIC>
 __device__ __forceinline__ double quad_eval(const QuadLds& L, const SolveParams& o, int gl, int n, int p, int ic,
                                             unsigned rowc, const unsigned (&colc)[EPL], const double (&xt)[EPL],
                                             double (&g)[EPL], XWave& X, bool first, bool& counted) {
@@ -435,7 +435,7 @@ __device__ __forceinline__ double quad_eval(const QuadLds& L, const SolveParams&
   if (gl < n) {
     const double z = gather_dot(L.csr() + (rowc & 0xffffu), (int)(rowc >> 16), xs + ic, x0) + (double)L.o()[gl];
     double ri;
-    part = loss_terms<LIN>(z, (double)L.y()[gl], L.has_w ? (double)L.w()[gl] : 1.0, ri);
+    part = loss_terms<LOSS>(z, (double)L.y()[gl], L.has_w ? (double)L.w()[gl] : 1.0, ri);
     rs[gl] = ri;
     rpart = ri;
   }
@@ -443,7 +443,7 @@ __device__ __forceinline__ double quad_eval(const QuadLds& L, const SolveParams&
     const int k0 = L.row_ptr()[i], k1 = L.row_ptr()[i + 1];
     const double z = gather_dot(L.csr() + k0, k1 - k0, xs + ic, x0) + (double)L.o()[i];
     double ri;
-    part += loss_terms<LIN>(z, (double)L.y()[i], L.has_w ? (double)L.w()[i] : 1.0, ri);
+    part += loss_terms<LOSS>(z, (double)L.y()[i], L.has_w ? (double)L.w()[i] : 1.0, ri);
     rs[i] = ri;
     rpart += ri;
   }
@@ -504,7 +504,7 @@ struct QuadState {
 // LONG_COLS: the class holds entities with more samples than the group has lanes (columns of several entries are the rule): the
 // EPL = 4 kernels then gather their four columns in one loop too, an entry of each per trip (C5-shaped classes - 1 to - 3 %); where
 // columns mostly hold one entry (C2's <16,4>: n <= 16) the four short loops are as fast and spill less (+ 0.5 % with the fused loop)
-template <int G, int EPL, bool LONG_COLS = true, bool LIN = false>
+template <int G, int EPL, bool LONG_COLS = true, int LOSS = LOSS_LOGISTIC>
 __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& o, int gl, int n, int p, int ic,
                                            bool valid, unsigned rowc, const unsigned (&colc)[EPL], QuadState<EPL>& V,
                                            XWave& X, SolveStats& out) {
@@ -541,7 +541,7 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
     if (status < 0) {
       // ---- f, g at the trial point; g'd, y'y and max|g| in one reduction pass ------------------------
       bool counted;
-      f = quad_eval<G, EPL, LONG_COLS, LIN>(L, o, gl, n, p, ic, rowc, colc, V.x, V.g, X, first, counted);
+      f = quad_eval<G, EPL, LONG_COLS, LOSS>(L, o, gl, n, p, ic, rowc, colc, V.x, V.g, X, first, counted);
       nfev += counted ? 1 : 0;
       {
         double a = 0.0, b = 0.0, c = 0.0;

@@ -288,7 +288,9 @@ __device__ __forceinline__ double team_fg(Team<NW>& tm, const EntityView& P, con
     const double yi = (double)P.y[i];
     const double wi = P.w ? (double)P.w[i] : 1.0;
     double ri;
-    if (o.linear) {   // squared loss, fixed_effect_lr_lbfgs_model.py:356-358
+    if (o.linear == LOSS_POISSON) {   // include/gdmix_re.h, "poisson"
+      pr[0] += poisson_terms(z, yi, wi, ri);
+    } else if (o.linear) {   // squared loss, fixed_effect_lr_lbfgs_model.py:356-358
       const double e = z - yi;
       pr[0] += wi * e * e;
       ri = 2.0 * wi * e;

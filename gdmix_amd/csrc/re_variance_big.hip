@@ -55,6 +55,17 @@ __global__ void vf_rows_lin_kernel(BatchDev B, VfEntity V, double* __restrict__ 
     dvec[i] = 2.0 * (B.weight ? (double)B.weight[V.r0 + i] : 1.0);
 }
 
+// Poisson loss: D_i = w_i exp(z_i) at the returned theta (include/gdmix_re.h, "poisson")
+__global__ void vf_rows_poi_kernel(BatchDev B, VfEntity V, int ic, const double* __restrict__ theta, double* __restrict__ dvec) {
+  const double* th = theta + V.c0;
+  const int32_t* rp = B.row_ptr + V.r0 + V.e;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V.n; i += gridDim.x * blockDim.x) {
+    double acc = ic ? th[0] : 0.0;
+    for (int k = rp[i]; k < rp[i + 1]; ++k) acc += (double)B.csr_val[V.z0 + k] * th[ic + B.csr_col[V.z0 + k]];
+    dvec[i] = exp_any(acc + (double)B.offset[V.r0 + i]) * (B.weight ? (double)B.weight[V.r0 + i] : 1.0);
+  }
+}
+
 // H = identity on the padding, zero elsewhere
 __global__ void vf_clear_kernel(double* __restrict__ H, int p, int ld) {
   const size_t total = (size_t)ld * ld;
@@ -319,7 +330,8 @@ hipError_t launch_variance_full_big(gdmix_ctx_impl* ci, const BatchDev& B, int64
   double* wslots = dvec + max_n;
   for (int q = 0; q < n_big; ++q) {
     const VfEntity& V = host[(size_t)q];
-    if (o.linear) hipLaunchKernelGGL(vf_rows_lin_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, dvec);
+    if (o.linear == LOSS_POISSON) hipLaunchKernelGGL(vf_rows_poi_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
+    else if (o.linear) hipLaunchKernelGGL(vf_rows_lin_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, dvec);
     else hipLaunchKernelGGL(vf_rows_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
     hipLaunchKernelGGL(vf_clear_kernel, dim3(ci->num_cus * 8), dim3(256), 0, s, H, V.p, V.ld);
     rc = hipMemsetAsync(wslots, 0, (size_t)V.n * VAR_BIG_BUILD_GROUPS * 8, s);
@@ -338,7 +350,7 @@ hipError_t launch_variance_full_big(gdmix_ctx_impl* ci, const BatchDev& B, int64
 size_t hessian_dense_scratch_doubles(int64_t n) { return (size_t)n * (1 + VAR_BIG_BUILD_GROUPS) + 64; }
 
 hipError_t launch_hessian_dense(gdmix_ctx_impl* ci, const BatchDev& B, int64_t n, int64_t d, int ic, const double* theta, double* H, int64_t ld,
-                                double* scratch, hipStream_t s) {
+                                double* scratch, hipStream_t s, int loss) {
   VfEntity V;
   V.e = 0; V.r0 = 0; V.z0 = 0; V.c0 = 0;
   V.n = (int)n; V.d = (int)d; V.p = (int)d + ic; V.ld = (int)ld;
@@ -347,7 +359,9 @@ hipError_t launch_hessian_dense(gdmix_ctx_impl* ci, const BatchDev& B, int64_t n
   o.has_intercept = ic;
   double* dvec = scratch;
   double* wslots = dvec + n;
-  hipLaunchKernelGGL(vf_rows_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
+  if (loss == LOSS_POISSON) hipLaunchKernelGGL(vf_rows_poi_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
+  else if (loss == LOSS_SQUARED) hipLaunchKernelGGL(vf_rows_lin_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, dvec);
+  else hipLaunchKernelGGL(vf_rows_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
   hipLaunchKernelGGL(vf_clear_kernel, dim3(ci->num_cus * 8), dim3(256), 0, s, H, V.ld, V.ld);   // (p = ld: all zero, no identity on the padding)
   hipError_t rc = hipMemsetAsync(wslots, 0, (size_t)V.n * VAR_BIG_BUILD_GROUPS * 8, s);
   if (rc != hipSuccess) return rc;

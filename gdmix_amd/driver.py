@@ -40,8 +40,8 @@ class RandomEffectDriver:
         self.effect_name = constants.RANDOM_EFFECT
 
     def _validate_params(self):
-        assert self.base_training_params.model_type in (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION), \
-            "Random effect supports logistic_regression and linear_regression"
+        assert self.base_training_params.model_type in constants.LBFGS_MODEL_TYPES, \
+            "Random effect supports logistic_regression and linear_regression, and poisson_regression on count labels"
         assert self.base_training_params.partition_list_file is not None, \
             "Random effect requires partition list file"
 

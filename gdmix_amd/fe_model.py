@@ -39,7 +39,7 @@ from typing import Optional
 import numpy as np
 
 from . import constants
-from .fixed_effect import LINEAR_REGRESSION, LOGISTIC_REGRESSION, FixedEffectDeviceSolver
+from .fixed_effect import LINEAR_REGRESSION, LOGISTIC_REGRESSION, POISSON_REGRESSION, FixedEffectDeviceSolver
 from .io import avro, native_reader, tfrecord
 from .io.features import read_feature_list
 from .io.grouped_reader import resolve_input_files
@@ -51,7 +51,8 @@ logger.setLevel(logging.INFO)
 
 GLOBAL_MODEL_ID = "global model"
 MODEL_CLASS = {LOGISTIC_REGRESSION: "com.linkedin.photon.ml.supervised.classification.LogisticRegressionModel",
-               LINEAR_REGRESSION: "com.linkedin.photon.ml.supervised.regression.LinearRegressionModel"}
+               LINEAR_REGRESSION: "com.linkedin.photon.ml.supervised.regression.LinearRegressionModel",
+               POISSON_REGRESSION: constants.PHOTON_POISSON_MODEL_CLASS}
 
 
 @dataclass
@@ -229,6 +230,8 @@ class FixedEffectLRModelLBFGS:
         from . import sweep
         mp = self.model_params
         grid = mp.l2_grid() if action == constants.ACTION_TRAIN else None
+        if grid is not None:
+            sweep.refuse_poisson(self.model_type)
         if grid is None and not mp.metric_output_dir:
             return
         sweep.refuse_several_workers(execution_context, "--l2_reg_weights" if grid is not None else "--metric_output_dir")
@@ -239,6 +242,8 @@ class FixedEffectLRModelLBFGS:
     # ---- the stage metric (--metric_output_dir) ---------------------------------------------------------------------
     def _metric_name(self):
         from . import metrics
+        if self.model_type == constants.POISSON_REGRESSION:
+            return metrics.POISSON_LOSS
         return metrics.MSE if self.model_type == constants.LINEAR_REGRESSION else metrics.AUC
 
     def _begin_metrics(self):
@@ -413,7 +418,8 @@ class FixedEffectLRModelLBFGS:
             _, per_dev = fe.score_device(shard, theta if bag else theta[1:], self.has_intercept)
             if data["has_label"]:
                 if which not in self._metrics.ev:
-                    self._metrics.ev[which] = fe.new_evaluator()
+                    poisson = self._metrics.metric == "poisson_loss"
+                    self._metrics.ev[which] = fe.new_evaluator(self._metrics.metric) if poisson else fe.new_evaluator()
                 self._metrics.ev[which].add(fe.file_scores(shard, per_dev), shard.y)
             per_coord = fe.to_host(per_dev)
         else:

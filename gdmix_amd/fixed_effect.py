@@ -32,6 +32,8 @@ from .solver import REDeviceSolver, SolverOptions
 
 LOGISTIC_REGRESSION = "logistic_regression"
 LINEAR_REGRESSION = "linear_regression"
+POISSON_REGRESSION = "poisson_regression"      # loss exp(z) - y z on count labels (include/gdmix_fe.h, "poisson")
+LOSS_OF_MODEL_TYPE = {LOGISTIC_REGRESSION: "logistic", LINEAR_REGRESSION: "squared", POISSON_REGRESSION: "poisson"}
 
 
 def shard_as_batch(row_nnz_ptr, col_global, val, y, offset=None, weight=None, has_intercept=True, binary_labels=True,
@@ -132,10 +134,11 @@ class FixedEffectDeviceSolver:
     def to_host(x):
         return x.cpu().numpy()
 
-    def new_evaluator(self):
-        """An accumulator of the exact stage metric for scores that stay on the device (metrics.DeviceEvaluator)."""
+    def new_evaluator(self, metric=None):
+        """An accumulator of the exact stage metric for scores that stay on the device (metrics.DeviceEvaluator; metrics.PoissonEvaluator
+        for metric "poisson_loss")."""
         from . import metrics
-        return metrics.DeviceEvaluator(self.solver)
+        return metrics.PoissonEvaluator(self.solver) if metric == metrics.POISSON_LOSS else metrics.DeviceEvaluator(self.solver)
 
     def models_per_chunk(self, K, P, n_eval):
         """How many of K models are scored at once (sweep.models_per_chunk): a model is its coefficients and two rows of the output,
@@ -147,7 +150,7 @@ class FixedEffectDeviceSolver:
             regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12, dummy=None):
         """-> (theta [num_features + has_intercept], intercept last; info dict with f, nit, nfev, status, gnorm)."""
         opts = fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance)
-        batch, dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, has_intercept, binary_labels=not opts.linear, dummy=dummy)
+        batch, dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, has_intercept, binary_labels=opts.loss_name() == "logistic", dummy=dummy)
         if not dummy and batch.col_global.size and (batch.col_global.min() < 0 or batch.col_global.max() >= num_features):
             raise ValueError(f"feature index outside [0, {num_features})")
         packed = self.solver.pack(batch, has_intercept=has_intercept)
@@ -207,10 +210,11 @@ class FixedEffectDeviceSolver:
 
 def fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance):
     """The solver's options of a fixed-effect fit: the objective is not divided by n, the model is stored unthresholded."""
-    if model_type not in (LOGISTIC_REGRESSION, LINEAR_REGRESSION):
+    if model_type not in LOSS_OF_MODEL_TYPE:
         raise ValueError(f"unknown model type {model_type!r}")
     return SolverOptions(l2=l2, regularize_bias=bool(regularize_bias) and bool(has_intercept), has_intercept=has_intercept, m=m,
-                         max_iter=max_iter, ftol=tolerance, threshold=0.0, sum_loss=True, linear=(model_type == LINEAR_REGRESSION))
+                         max_iter=max_iter, ftol=tolerance, threshold=0.0, sum_loss=True, linear=(model_type == LINEAR_REGRESSION),
+                         loss="poisson" if model_type == POISSON_REGRESSION else None)
 
 
 class DeviceShard:
@@ -472,7 +476,10 @@ class _SteppingFit:
         if prior is not None and feature_scale is not None:
             raise ValueError("feature normalisation does not compose with a prior model")
         self.batch, self.dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, opts.has_intercept,
-                                                binary_labels=not opts.linear, dummy=dummy)
+                                                binary_labels=opts.loss_name() == "logistic", dummy=dummy)
+        if opts.loss_name() == "poisson":
+            from .batch import check_count_labels
+            check_count_labels(self.batch.y, "poisson_regression, the fixed effect's shard")
         D = 1 if self.dummy else int(num_features)   # the dummy zero feature of an intercept-only model occupies global index 0
         if not self.dummy and self.batch.col_global.size and (self.batch.col_global.min() < 0 or self.batch.col_global.max() >= D):
             raise ValueError(f"feature index outside [0, {D})")
@@ -545,7 +552,7 @@ class _SteppingFit:
             o = self.opts
             info["variances"] = self.strip_dummy(_variances(self.solver, self.prob, self.batch, th, self.D, o.has_intercept, float(l2), o.regularize_bias,
                                                             str(self.variance_mode).upper(), self.all_reduce, self.group, packed=self.packed,
-                                                            dummy=self.dummy, scale=self.prior_scale))
+                                                            dummy=self.dummy, scale=self.prior_scale, poisson=o.loss_name() == "poisson"))
         return self.strip_dummy(theta), info
 
 
@@ -633,13 +640,16 @@ def full_variances_of(H, l2, ic, regularize_bias, scale=None):
     return np.diagonal(np.linalg.inv(H + np.diag(reg))).copy()
 
 
-def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias, mode, all_reduce, group, packed=None, dummy=False, scale=None):
+def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias, mode, all_reduce, group, packed=None, dummy=False, scale=None,
+               poisson=False):
     """variance of every coefficient (intercept last). SIMPLE: 1 / (diag(X~' D X~) + l2 [regularised] + 1e-12), the diagonal by two
     more streaming passes on the device and the same all-reduce as an evaluation. FULL: diag((X~' D X~ + (l2 + 1e-12) I - l2
     [intercept unregularised])^-1): the dense matrix is built on the host from the shard (scipy), summed over the workers and
     inverted with numpy, exactly as the reference does (:296-305, 457-463) — only sensible for small feature spaces.
     scale: the prior scale [D + ic] of an incremental fit (include/gdmix_fe.h, "incremental training"): the same mode applied in phi-space
-    to S H S and mapped back, Var(theta_j) = s_j^2 Var'(phi_j); theta is theta, and the curvature the device returns is theta-space's."""
+    to S H S and mapped back, Var(theta_j) = s_j^2 Var'(phi_j); theta is theta, and the curvature the device returns is theta-space's.
+    poisson: the curvature weight is D_i = w_i exp(z_i) (include/gdmix_fe.h, "poisson"): SIMPLE takes it from the problem's loss, the FULL
+    routes are told."""
     eps = 1.0e-12
     ic = 1 if has_intercept else 0
     P = D + ic
@@ -661,14 +671,15 @@ def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias
     check_variance_request(mode, P, _world_size(group))
     if P > FULL_VARIANCE_HOST_MAX and (_world_size(group) > 1 or scale is not None):
         # (with a prior any number of workers: the one-worker shortcut below, solver.variance_full, knows no prior)
-        return _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2, regularize_bias, group, dummy, scale=scale)
+        return _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2, regularize_bias, group, dummy, scale=scale,
+                                               loss="poisson" if poisson else None)
     if P > FULL_VARIANCE_HOST_MAX:
         # on the device, in the shard's local index space (intercept first): the random-effect FULL variance of a one-entity
         # batch is this very matrix (binary_logistic_regression.py:181-187 = fixed_effect_lr_lbfgs_model.py:296-305, 457-463).
         # Features without a non-zero in the shard have a zero row and column in X~' D X~: their variance is 1 / (l2 + 1e-12).
         uniq = packed.unique_global().cpu().numpy()
         local = to_local(theta, uniq, D, has_intercept, dummy)
-        o = SolverOptions(l2=l2, regularize_bias=regularize_bias, has_intercept=has_intercept)
+        o = SolverOptions(l2=l2, regularize_bias=regularize_bias, has_intercept=has_intercept, loss="poisson" if poisson else None)
         v_local = solver.variance_full(packed, o, local).cpu().numpy()
         out = np.full(P, 1.0 / (l2 + eps))
         out[uniq] = v_local[ic:]
@@ -682,7 +693,7 @@ def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias
         X = sp.hstack([X, sp.csr_matrix(np.ones((n, 1)))], format="csr")
     z = X @ theta + batch.offset.astype(np.float64)
     rho = 1.0 / (1.0 + np.exp(-z))
-    d = rho * (1.0 - rho) * (1.0 if batch.weight is None else batch.weight.astype(np.float64))
+    d = (np.exp(z) if poisson else rho * (1.0 - rho)) * (1.0 if batch.weight is None else batch.weight.astype(np.float64))
     H = np.asarray((X.T @ X.multiply(d[:, None])).todense(), np.float64)
     try:
         import torch
@@ -706,7 +717,7 @@ def _variances(solver, prob, batch, theta, D, has_intercept, l2, regularize_bias
     return np.diagonal(np.linalg.inv(H)).copy()
 
 
-def _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2, regularize_bias, group, dummy=False, scale=None):
+def _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2, regularize_bias, group, dummy=False, scale=None, loss=None):
     """FULL variances on the device with the Hessian summed over the workers (fixed_effect_lr_lbfgs_model.py:291-305, 384-389,
     457-463). Coefficient order: features 0 .. D-1, intercept last. scale: the prior scale of an incremental fit — rows and columns of
     the summed matrix are scaled by it (S H S), the variances of that by s^2; with it also the route of a single worker."""
@@ -731,7 +742,7 @@ def _full_variances_several_workers(solver, packed, theta, D, has_intercept, l2,
     Hg = torch.zeros((ld, ld), dtype=torch.float64, device=solver.device)
     if not dummy and p_l > 0:     # (a worker without data trains on one weight-0 sample: its curvature is exactly zero — nothing to build or scatter)
         local = to_local(theta, uniq, D, has_intercept, dummy)
-        Hl = solver.hessian_dense(packed, local, has_intercept)            # [ld_l, ld_l], local order: intercept first
+        Hl = solver.hessian_dense(packed, local, has_intercept, **({} if loss is None else {"loss": loss}))   # [ld_l, ld_l], local order: intercept first
         idx = torch.cat([torch.full((ic,), D, dtype=torch.int64, device=solver.device), uniq_dev.to(torch.int64)])   # local -> global coefficient
         Hg.index_put_((idx[:, None], idx[None, :]), Hl[:p_l, :p_l])       # one 2-D scatter into the common index space
         del Hl

@@ -5,8 +5,9 @@ shared by Params, SchemaParams and REParams, unknown flags are ignored, any fail
     python -m gdmix_amd.gdmix --stage=random_effect --action=train --model_type=logistic_regression \\
         --partition_list_file=... --training_data_dir=... --metadata_file=... --output_model_dir=... ...
 
---model_type=linear_regression trains the per-entity squared loss on real-valued labels (model.py). --stage=fixed_effect runs the linear /
-logistic fixed-effect model (fe_model.py); the DeText stage is out of scope.
+--model_type=linear_regression trains the per-entity squared loss on real-valued labels, --model_type=poisson_regression the Poisson loss
+on count labels (model.py). --stage=fixed_effect runs the linear / logistic / Poisson fixed-effect model (fe_model.py); the DeText stage is
+out of scope.
 """
 import logging
 import sys
@@ -25,13 +26,13 @@ def run(args):
     schema_params = SchemaParams.__from_argv__(args, error_on_unknown=False)
     logger.info(f"Parsed schema params amd gdmix args (params): {params}")
     if params.stage == constants.FIXED_EFFECT:
-        if params.model_type not in (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION):
-            raise NotImplementedError(f"model type {params.model_type!r}: the fixed effect runs logistic_regression and linear_regression")
+        if params.model_type not in constants.LBFGS_MODEL_TYPES:
+            raise NotImplementedError(f"model type {params.model_type!r}: the fixed effect runs logistic_regression and linear_regression, and poisson_regression on count labels")
         from .fe_model import FixedEffectLRModelLBFGS
         driver = FixedEffectDriver(base_training_params=params, model=FixedEffectLRModelLBFGS(raw_model_params=args, base_training_params=params))
     elif params.stage == constants.RANDOM_EFFECT:
-        if params.model_type not in (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION):
-            raise ValueError(f"model type {params.model_type!r}: the random effect runs logistic_regression and linear_regression")
+        if params.model_type not in constants.LBFGS_MODEL_TYPES:
+            raise ValueError(f"model type {params.model_type!r}: the random effect runs logistic_regression and linear_regression, and poisson_regression on count labels")
         driver = RandomEffectDriver(base_training_params=params,
                                     model=RandomEffectLRLBFGSModel(raw_model_params=args, base_training_params=params))
     else:

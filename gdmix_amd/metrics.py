@@ -16,6 +16,19 @@ import numpy as np
 from . import solver as _solver
 
 AUC, MSE = "auc", "mse"
+POISSON_LOSS = "poisson_loss"        # mean of exp(s) - y s: the metric of a poisson_regression stage (include/gdmix_re.h, "poisson evaluation")
+
+
+def metric_of_loss(loss) -> str:
+    """The stage metric of a loss name of solver.LOSS_CODES."""
+    return {"logistic": AUC, "squared": MSE, "poisson": POISSON_LOSS}[loss]
+
+
+def poisson_loss_terms(score, label) -> np.ndarray:
+    """The host statement of the device's Poisson-loss terms: exp(s) - y s in fp64, the fp32 score and label widened first. It states the
+    definition (tests add the terms up with math.fsum); it does not evaluate a stage."""
+    s = np.asarray(score, np.float32).astype(np.float64)
+    return np.exp(s) - np.asarray(label, np.float32).astype(np.float64) * s
 EXACT_DEVICE_DIVISION = 1 << 26      # entities below this many samples: auc[e] of the device is the correctly rounded quotient
 
 
@@ -53,6 +66,97 @@ def entities_to_host(res) -> dict:
     mse[n_nan > 0] = np.nan
     h.update(n=n + n_nan, auc=auc, mse=mse)
     return h
+
+
+def poisson_entities_to_host(res) -> dict:
+    """The tensors of PoissonEvaluator.entities -> numpy arrays, with `n` (every sample, NaN scores included) and `poisson_loss`
+    (pl / n, NaN for an entity without samples or with a NaN score)."""
+    h = {k: _solver.host_array(v) for k, v in res.items()}
+    n, n_nan = h["n"].astype(np.int64), h["n_nan"].astype(np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = h["pl"] / n.astype(np.float64)
+    mean[(n == 0) | (n_nan > 0)] = np.nan
+    h.update(n=n + n_nan, poisson_loss=mean)
+    return h
+
+
+class PoissonEvaluator:
+    """The Poisson loss on one MI355X through the solver's context, with DeviceEvaluator's interface: `entities` per entity of a scored
+    batch, `add` ... `finish` over everything a stage scores."""
+
+    def __init__(self, solver):
+        self.solver = solver
+        self.torch = solver.torch
+        self.lib = solver.lib
+        self._state = self.torch.empty(_solver.EVAL_PL_STATE_BYTES, dtype=self.torch.uint8, device=solver.device)
+        self._acc = _solver._EvalPlAcc(self._state.data_ptr(), 0)
+        self.reset()
+
+    def set_small_max(self, small_max: int):
+        """Testing knob: entities of more than small_max samples are summed by a workgroup each (0: every entity). Default 64."""
+        with self.solver._ctx_lock:
+            _solver._check(self.lib.gdmix_re_set_eval_small_max(self.solver._h, int(small_max)), "gdmix_re_set_eval_small_max")
+
+    def entities(self, packed_or_ent_row_ptr, score, label=None) -> dict:
+        """-> {"pl" float64, "n", "n_nan" int32}: device tensors, one entry per entity (n: the samples whose score is not NaN)."""
+        t, s = self.torch, self.solver
+        if isinstance(packed_or_ent_row_ptr, _solver.PackedBatch):
+            pb = packed_or_ent_row_ptr
+            rp = pb._raw_dev["ent_row_ptr"]
+            if label is None:
+                label = pb._raw_dev["y"]
+        else:
+            rp = packed_or_ent_row_ptr
+            if isinstance(rp, np.ndarray):
+                rp = t.from_numpy(np.ascontiguousarray(rp, np.int64)).to(s.device)
+        if label is None:
+            raise _solver.GdmixReError("entities: no labels")
+        if not rp.is_cuda or rp.dtype != t.int64 or rp.numel() < 1:
+            raise _solver.GdmixReError("ent_row_ptr must be int64 on the solver's device, one entry more than entities")
+        score, label = self._f32(score, "score"), self._f32(label, "label")
+        E, N = int(rp.numel()) - 1, int(score.numel())
+        if label.numel() != N:
+            raise _solver.GdmixReError("score and label differ in length")
+        if E > 0 and (int(rp[0]) != 0 or int(rp[-1]) != N):
+            raise _solver.GdmixReError(f"ent_row_ptr runs from {int(rp[0])} to {int(rp[-1])}; the batch has {N} samples")
+        dev = s.device
+        res = dict(pl=t.zeros(E, dtype=t.float64, device=dev), n=t.zeros(E, dtype=t.int32, device=dev), n_nan=t.zeros(E, dtype=t.int32, device=dev))
+        c_out = _solver._EvalPlOut(*(res[k].data_ptr() if E else None for k in ("pl", "n", "n_nan")))
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_pl_entities(s._h, rp.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
+                                                              C.byref(c_out), s._stream()), "gdmix_re_eval_pl_entities")
+        return res
+
+    def reset(self):
+        s = self.solver
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_pl_acc_reset(s._h, C.byref(self._acc), s._stream()), "gdmix_re_eval_pl_acc_reset")
+
+    @property
+    def count(self) -> int:
+        return int(self._acc.count)
+
+    def add(self, score, label):
+        score, label = self._f32(score, "score"), self._f32(label, "label")
+        N = int(score.numel())
+        if label.numel() != N:
+            raise _solver.GdmixReError("score and label differ in length")
+        if N == 0:
+            return
+        s = self.solver
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_pl_acc_add(s._h, C.byref(self._acc), score.data_ptr(), label.data_ptr(), N, s._stream()),
+                           "gdmix_re_eval_pl_acc_add")
+
+    def finish(self) -> dict:
+        """-> {"poisson_loss", "pl", "n", "n_nan"}: the mean (NaN when a score was NaN or nothing was added), the sum over the scores that
+        are not NaN, every sample added, the NaN scores. The accumulator stays as it is: more batches may follow."""
+        s = self.solver
+        tot = _solver._EvalPlTotals()
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_pl_acc_finish(s._h, C.byref(self._acc), C.byref(tot), s._stream()), "gdmix_re_eval_pl_acc_finish")
+        n, n_nan = int(tot.n), int(tot.n_nan)
+        return {POISSON_LOSS: float("nan") if n_nan > 0 or n == 0 else float(tot.pl) / n, "pl": float(tot.pl), "n": n + n_nan, "n_nan": n_nan}
 
 
 class DeviceEvaluator:
@@ -173,12 +277,19 @@ class DeviceEvaluator:
                 "n": int(tot.n), "n_pos": n_pos, "n_neg": n_neg, "n_nan": n_nan, "two_u": int(tot.two_u), "sse": float(tot.sse)}
 
 
+PoissonEvaluator._f32 = DeviceEvaluator._f32      # the two evaluators check their inputs alike
+
+
 # ---- a stage that reports its metric while it scores (REParams.metric_output_dir) ----------------------------------------------------
 EVAL_SUMMARY_JSON = "evalSummary.json"
 PER_ENTITY_DIR = "perEntity"
 PER_ENTITY_SCHEMA = {"type": "record", "name": "EntityMetricAvro", "namespace": "gdmix_amd", "fields": [
     {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "n_pos", "type": "long"},
     {"name": "auc", "type": ["null", "double"]}, {"name": "mse", "type": "double"}]}
+PER_ENTITY_POISSON_SCHEMA = {"type": "record", "name": "EntityPoissonMetricAvro", "namespace": "gdmix_amd", "fields": [
+    {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "poisson_loss", "type": "double"}]}
+SUMMARY_KEYS = ("n", "n_pos", "n_neg", "n_nan", "two_u", "sse")
+POISSON_SUMMARY_KEYS = ("n", "n_nan", "pl")
 TRAINING, VALIDATION = "training", "validation"
 
 logger = logging.getLogger(__name__)
@@ -196,6 +307,7 @@ class StageMetrics:
                                    "training": {the same keys}, "validation": {...}} — the top level repeats the validation block
                                    (the data the workflow's evaluator reads), or the training block of a stage without validation data
         perEntity/part-<data>-<partition directory>-<score file>.avro     records {entityId, n, n_pos, auc (null: one class), mse}
+    A Poisson stage (metric "poisson_loss"): the summary's keys are {"poisson_loss", "n", "n_nan", "pl"}, the records {entityId, n, poisson_loss}.
     One worker, one summary: workers of a multi-process job need a directory each."""
 
     def __init__(self, solver, out_dir, metric_name):
@@ -205,7 +317,7 @@ class StageMetrics:
 
     def _evaluator(self, which):
         if which not in self.ev:
-            self.ev[which] = DeviceEvaluator(self.solver)
+            self.ev[which] = PoissonEvaluator(self.solver) if self.metric == POISSON_LOSS else DeviceEvaluator(self.solver)
         return self.ev[which]
 
     def no_labels(self, what):
@@ -217,7 +329,7 @@ class StageMetrics:
         """The scores of a packed batch (device) -> added to `which`'s accumulator; -> per-entity results on the host."""
         ev = self._evaluator(which)
         ev.add(logit, packed._raw_dev["y"])
-        return entities_to_host(ev.entities(packed, logit))
+        return (poisson_entities_to_host if self.metric == POISSON_LOSS else entities_to_host)(ev.entities(packed, logit))
 
     def write_entities(self, which, output_file, entity_ids, host, e0=0, e1=None):
         from .io import avro
@@ -227,6 +339,11 @@ class StageMetrics:
         stem = os.path.basename(output_file)
         stem = stem[len("part-"):] if stem.startswith("part-") else stem
         name = f"part-{which}-{os.path.basename(os.path.dirname(os.path.abspath(output_file)))}-{stem}"
+        if self.metric == POISSON_LOSS:
+            n, pl = host["n"][e0:e1], host[POISSON_LOSS][e0:e1]
+            recs = [{"entityId": str(entity_ids[i]), "n": int(n[i]), POISSON_LOSS: float(pl[i])} for i in range(e1 - e0)]
+            avro.write_file(os.path.join(d, name), PER_ENTITY_POISSON_SCHEMA, recs)
+            return
         n, n_pos, auc, mse = host["n"][e0:e1], host["n_pos"][e0:e1], host["auc"][e0:e1], host["mse"][e0:e1]
         recs = [{"entityId": str(entity_ids[i]), "n": int(n[i]), "n_pos": int(n_pos[i]), "auc": None if auc[i] != auc[i] else float(auc[i]),
                  "mse": float(mse[i])} for i in range(e1 - e0)]
@@ -238,7 +355,7 @@ class StageMetrics:
         blocks = {}
         for which, ev in self.ev.items():
             r = ev.finish()
-            blocks[which] = {k: _json_number(r[k]) for k in (self.metric, "n", "n_pos", "n_neg", "n_nan", "two_u", "sse")}
+            blocks[which] = {k: _json_number(r[k]) for k in (self.metric,) + (POISSON_SUMMARY_KEYS if self.metric == POISSON_LOSS else SUMMARY_KEYS)}
         top = VALIDATION if VALIDATION in blocks else TRAINING
         out = dict(blocks[top], data=top, **blocks)
         os.makedirs(self.out_dir, exist_ok=True)

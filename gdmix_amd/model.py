@@ -22,7 +22,7 @@ from .io.features import get_feature_map, read_feature_list
 from .io.grouped_reader import read_grouped_partition
 from .io.metadata import DatasetMetadata, read_json_file
 from .params import REParams
-from .batch import WireRawBatch
+from .batch import WireRawBatch, check_count_labels
 from .solver import REDeviceSolver, SolverOptions, VARIANCE_MODES, host_array
 
 logger = logging.getLogger(__name__)
@@ -470,14 +470,19 @@ class RandomEffectLRLBFGSModel:
     """Per-entity L2-regularised logistic regression, all entities of a partition solved on one MI355X.
     base_training_params.model_type == linear_regression: the per-entity squared loss on real-valued labels instead (include/gdmix_re.h,
     `linear`); everything else — grouping, warm start, variance modes, scoring, inference, re-balancing — is the same path. Unlike the
-    fixed effect, scoring after training stays on: a random effect's scores are the next coordinate's offsets."""
+    fixed effect, scoring after training stays on: a random effect's scores are the next coordinate's offsets.
+    model_type == poisson_regression: the per-entity Poisson loss exp(z) - y z on count labels (include/gdmix_re.h, "poisson"), the same
+    path again; labels are checked to be finite and >= 0 when a partition is read, the stage metric is poisson_loss, and the model files
+    carry Photon-ML's PoissonRegressionModel class name. The score stays the margin z."""
 
     def __init__(self, raw_model_params, device=None, base_training_params=None):
         self.model_params: REParams = self._parse_parameters(raw_model_params)
         self.model_type = constants.LOGISTIC_REGRESSION if base_training_params is None else base_training_params.model_type
-        if self.model_type not in (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION):
-            raise ValueError(f"model type {self.model_type!r}: the random effect runs logistic_regression and linear_regression")
+        if self.model_type not in constants.LBFGS_MODEL_TYPES:
+            raise ValueError(f"model type {self.model_type!r}: the random effect runs logistic_regression and linear_regression, and poisson_regression on count labels")
         self.linear = self.model_type == constants.LINEAR_REGRESSION
+        self.poisson = self.model_type == constants.POISSON_REGRESSION
+        self.loss = "poisson" if self.poisson else ("squared" if self.linear else "logistic")
         self.checkpoint_path = os.path.join(self.model_params.output_model_dir)
         self.metadata_file = self.model_params.metadata_file
         self.feature_bag_name = self.model_params.feature_bag
@@ -513,7 +518,7 @@ class RandomEffectLRLBFGSModel:
             return None
         if self._stage_metrics is None:
             from . import metrics
-            self._stage_metrics = metrics.StageMetrics(self._get_solver(), out_dir, metrics.MSE if self.linear else metrics.AUC)
+            self._stage_metrics = metrics.StageMetrics(self._get_solver(), out_dir, metrics.metric_of_loss(self.loss))
         return self._stage_metrics
 
     def _metric_data(self, input_path):
@@ -575,7 +580,7 @@ class RandomEffectLRLBFGSModel:
                              has_intercept=self.has_intercept,
                              m=mp.num_of_lbfgs_curvature_pairs, max_iter=mp.num_of_lbfgs_iterations,
                              ftol=mp.lbfgs_tolerance, variance_mode=VARIANCE_MODES[mp.random_effect_variance_mode],
-                             threshold=mp.sparsity_threshold, linear=self.linear)
+                             threshold=mp.sparsity_threshold, linear=self.linear, loss="poisson" if self.poisson else None)
 
     def _action(self, action, action_context, metadata_file, checkpoint_path, execution_context, schema_params):
         partition_index = execution_context[constants.PARTITION_INDEX]
@@ -709,12 +714,18 @@ class RandomEffectLRLBFGSModel:
         return batch
 
     def _read_files(self, input_path, tensor_metadata, schema_params, num_features):
+        batch = self._read_grouped(input_path, tensor_metadata, schema_params, num_features)
+        if self.poisson and batch.has_label:
+            check_count_labels(batch.y, f"poisson_regression, {input_path}")
+        return batch
+
+    def _read_grouped(self, input_path, tensor_metadata, schema_params, num_features):
         return read_grouped_partition(
             input_path, tensor_metadata, entity_name=self.model_params.partition_entity,
             feature_bag=self.feature_bag_name, offset_column_name=self.model_params.offset_column_name,
             uid_column_name=schema_params.uid_column_name,
             label_column_name=schema_params.label_column_name, weight_column_name=schema_params.weight_column_name,
-            num_features=num_features, wire=self._wants_wire(), binary_labels=not self.linear)
+            num_features=num_features, wire=self._wants_wire(), binary_labels=self.loss == "logistic")
 
     def _wants_wire(self):
         """The reader narrows the partition to the 32-bit hand-over form when a device solver will take it (it uploads that form as it
@@ -1255,7 +1266,8 @@ class RandomEffectLRLBFGSModel:
             assert num_features == 1   # intercept only model
         with_variance = self.model_params.random_effect_variance_mode is not None
         n = _export_models_to_avro(output_file, model_coefficients, feature_list, self.has_intercept, with_variance,
-                                   sparsity_threshold=1.0e-4)   # export threshold is always the default
+                                   sparsity_threshold=1.0e-4,   # export threshold is always the default
+                                   model_class=constants.PHOTON_POISSON_MODEL_CLASS if self.poisson else None)
         logger.info(f"dumped {n} models to avro file at {output_file}.")
 
     def _load_weights(self, model_file, catch_exception=False):

@@ -11,7 +11,7 @@ from .argv import from_argv, to_argv
 
 _ACTIONS = (constants.ACTION_INFERENCE, constants.ACTION_TRAIN)
 _STAGES = (constants.FIXED_EFFECT, constants.RANDOM_EFFECT)
-_MODEL_TYPES = (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION, constants.DETEXT)
+_MODEL_TYPES = (constants.LOGISTIC_REGRESSION, constants.LINEAR_REGRESSION, constants.POISSON_REGRESSION, constants.DETEXT)
 _VARIANCE_MODE = (constants.FULL, constants.SIMPLE)
 
 
@@ -129,7 +129,7 @@ class REParams(LRParams):
     disable_random_effect_scoring_after_training: bool = False
     # not in the reference: move entities between the workers of a node when partitions are skewed (rebalance.py)
     rebalance_entities: bool = False
-    # not in the reference: the stage writes its metric (evalSummary.json: auc, or mse for linear_regression) and the per-entity
+    # not in the reference: the stage writes its metric (evalSummary.json: auc, mse for linear_regression, poisson_loss for poisson_regression) and the per-entity
     # metrics of everything it scores under this directory, computed on the device while the scores are there (metrics.py)
     metric_output_dir: Optional[str] = None
     # not in the reference: --action=train sweeps these weights inside the stage (sweep.py: every partition solved once per weight, the

@@ -78,6 +78,21 @@ class _EvalAcc(C.Structure):
 EVAL_ACC_STATE_BYTES = 33024
 
 
+class _EvalPlOut(C.Structure):
+    _fields_ = [("pl", C.c_void_p), ("n", C.c_void_p), ("n_nan", C.c_void_p)]
+
+
+class _EvalPlAcc(C.Structure):
+    _fields_ = [("state", C.c_void_p), ("count", C.c_int64)]
+
+
+class _EvalPlTotals(C.Structure):
+    _fields_ = [("pl", C.c_double), ("n", C.c_int64), ("n_nan", C.c_int64)]
+
+
+EVAL_PL_STATE_BYTES = 33024
+
+
 class _EvalTotals(C.Structure):
     _fields_ = [("two_u", C.c_uint64), ("n", C.c_int64), ("n_pos", C.c_int64), ("n_neg", C.c_int64), ("n_nan", C.c_int64), ("sse", C.c_double)]
 
@@ -88,10 +103,11 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_solve_scratch_bytes", "gdmix_re_set_scratch", "gdmix_re_variance_full", "gdmix_re_set_wave_lds_limit", "gdmix_re_score",
     "gdmix_re_widen_workspace_bytes", "gdmix_re_widen", "gdmix_re_set_timing", "gdmix_re_last_solve_ms", "gdmix_re_set_kernel_mask", "gdmix_re_set_giant_nnz", "gdmix_re_set_team_nnz", "gdmix_re_set_tall_min_n", "gdmix_re_set_tall_split_n", "gdmix_re_set_tall_team_n", "gdmix_re_set_tall_mid_n", "gdmix_re_set_spread",
     "gdmix_fe_create", "gdmix_fe_destroy", "gdmix_fe_eval", "gdmix_fe_reduce_buffer", "gdmix_fe_step", "gdmix_fe_step_async", "gdmix_fe_step_status", "gdmix_fe_solve", "gdmix_fe_result",
-    "gdmix_fe_last_eval_ms", "gdmix_fe_stream_bytes", "gdmix_fe_score", "gdmix_fe_hessian_diag", "gdmix_fe_hessian_dense_scratch_bytes", "gdmix_fe_hessian_dense",
+    "gdmix_fe_last_eval_ms", "gdmix_fe_stream_bytes", "gdmix_fe_score", "gdmix_fe_hessian_diag", "gdmix_fe_hessian_dense_scratch_bytes", "gdmix_fe_hessian_dense", "gdmix_fe_hessian_dense_loss",
     "gdmix_fe_variance_of_hessian", "gdmix_fe_restart", "gdmix_fe_set_prior", "gdmix_fe_score_models_workspace_bytes", "gdmix_fe_score_models",
     "gdmix_re_eval_workspace_bytes", "gdmix_re_eval_entities", "gdmix_re_set_eval_small_max", "gdmix_re_eval_acc_reset", "gdmix_re_eval_acc_add",
     "gdmix_re_eval_acc_workspace_bytes", "gdmix_re_eval_acc_finish",
+    "gdmix_re_eval_pl_entities", "gdmix_re_eval_pl_acc_reset", "gdmix_re_eval_pl_acc_add", "gdmix_re_eval_pl_acc_finish",
     "gdmix_re_join_features", "gdmix_re_score_models_workspace_bytes", "gdmix_re_score_models",
     "gdmix_re_prior_workspace_bytes", "gdmix_re_prior_apply", "gdmix_re_prior_restore",
     "gdmix_re_feature_extent", "gdmix_re_feature_moments", "gdmix_re_feature_scale_expand",
@@ -169,6 +185,8 @@ def load_library():
     lib.gdmix_fe_hessian_dense_scratch_bytes.argtypes = [C.POINTER(_Packed)]
     lib.gdmix_fe_hessian_dense_scratch_bytes.restype = C.c_size_t
     lib.gdmix_fe_hessian_dense.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.gdmix_fe_hessian_dense_loss.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]
     lib.gdmix_fe_variance_of_hessian.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gdmix_fe_last_eval_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.gdmix_fe_restart.argtypes = [C.c_void_p, C.POINTER(_Opts), C.c_void_p, C.c_void_p]
@@ -204,6 +222,10 @@ def load_library():
     lib.gdmix_re_eval_acc_workspace_bytes.argtypes = [C.c_int64]
     lib.gdmix_re_eval_acc_workspace_bytes.restype = C.c_size_t
     lib.gdmix_re_eval_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalAcc), C.c_void_p, C.c_size_t, C.POINTER(_EvalTotals), C.c_void_p]
+    lib.gdmix_re_eval_pl_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(_EvalPlOut), C.c_void_p]
+    lib.gdmix_re_eval_pl_acc_reset.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.c_void_p]
+    lib.gdmix_re_eval_pl_acc_add.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.gdmix_re_eval_pl_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.POINTER(_EvalPlTotals), C.c_void_p]
     lib.gdmix_re_join_features.argtypes = [C.c_void_p, C.POINTER(_Packed), C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gdmix_re_score_models_workspace_bytes.argtypes = [C.c_int64, C.c_int]
     lib.gdmix_re_score_models_workspace_bytes.restype = C.c_size_t
@@ -218,7 +240,7 @@ def load_library():
     lib.gdmix_re_feature_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]
     lib.gdmix_re_feature_scale_expand.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    if lib.gdmix_re_abi_version() != 18:
+    if lib.gdmix_re_abi_version() != 19:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib
@@ -228,6 +250,9 @@ def _check(rc, what):
     if rc != 0:
         msg = load_library().gdmix_re_last_error().decode("utf-8", "replace")
         raise GdmixReError(f"{what} failed ({rc}): {msg}")
+
+
+LOSS_CODES = {"logistic": 0, "squared": 1, "poisson": 2}      # GDMIX_RE_LOSS_*
 
 
 @dataclass
@@ -246,13 +271,27 @@ class SolverOptions:
     variance_mode: int = VAR_NONE
     threshold: float = 1e-4       # sparsity_threshold (base_lr_params.py:32)
     sum_loss: bool = False        # fixed-effect objective: not divided by n (fixed_effect_lr_lbfgs_model.py:363-381)
-    linear: bool = False          # squared loss instead of the logistic loss (:356-358)
+    linear: bool = False          # squared loss instead of the logistic loss (:356-358); the older spelling of loss="squared"
+    loss: str = None              # "logistic" | "squared" | "poisson" (include/gdmix_re.h, GDMIX_RE_LOSS_*); None: what `linear` says
+
+    def loss_name(self):
+        """The loss these options name: `loss`, or what `linear` says when it is None; both given is an error."""
+        if self.loss is None:
+            return "squared" if self.linear else "logistic"
+        if self.linear:
+            raise ValueError("SolverOptions: give either linear=True or loss=..., not both")
+        if self.loss not in LOSS_CODES:
+            raise ValueError(f"SolverOptions.loss must be one of {sorted(LOSS_CODES)}, not {self.loss!r}")
+        return self.loss
+
+    def loss_code(self):
+        return LOSS_CODES[self.loss_name()]
 
     def to_c(self):
         return _Opts(float(self.l2), int(bool(self.regularize_bias)), int(bool(self.has_intercept)),
                      int(self.m), int(self.max_iter), int(self.maxfun), int(self.maxls), float(self.ftol),
                      float(self.pgtol), int(VARIANCE_MODES[self.variance_mode]), float(self.threshold),
-                     int(bool(self.sum_loss)), int(bool(self.linear)))
+                     int(bool(self.sum_loss)), self.loss_code())
 
 
 def java_string_hash(s: str) -> int:
@@ -711,9 +750,9 @@ class REDeviceSolver:
 
     # ---- fixed effect, FULL variances with several workers (include/gdmix_fe.h) -----------------------
     @_serialised
-    def hessian_dense(self, packed: PackedBatch, theta_local, has_intercept=True):
+    def hessian_dense(self, packed: PackedBatch, theta_local, has_intercept=True, loss=None):
         """X~' D X~ of a one-entity batch (a worker's shard) at theta_local (the shard's local order, intercept first) as a dense
-        [ld, ld] device tensor, ld = p rounded up to 64; no regulariser."""
+        [ld, ld] device tensor, ld = p rounded up to 64; no regulariser. loss: None (the logistic curvature weight) or a name of LOSS_CODES."""
         t = self.torch
         if isinstance(theta_local, np.ndarray):
             theta_local = t.from_numpy(np.ascontiguousarray(theta_local, np.float64)).to(self.device)
@@ -722,8 +761,12 @@ class REDeviceSolver:
         H = t.empty((ld, ld), dtype=t.float64, device=self.device)
         nbytes = self.lib.gdmix_fe_hessian_dense_scratch_bytes(C.byref(packed.c))
         scratch = t.empty(nbytes, dtype=t.uint8, device=self.device)
-        _check(self.lib.gdmix_fe_hessian_dense(self._h, C.byref(packed.c), int(bool(has_intercept)), theta_local.data_ptr(), H.data_ptr(), ld,
-                                               scratch.data_ptr(), nbytes, self._stream()), "gdmix_fe_hessian_dense")
+        if loss is None:
+            _check(self.lib.gdmix_fe_hessian_dense(self._h, C.byref(packed.c), int(bool(has_intercept)), theta_local.data_ptr(), H.data_ptr(), ld,
+                                                   scratch.data_ptr(), nbytes, self._stream()), "gdmix_fe_hessian_dense")
+        else:
+            _check(self.lib.gdmix_fe_hessian_dense_loss(self._h, C.byref(packed.c), int(bool(has_intercept)), LOSS_CODES[loss], theta_local.data_ptr(),
+                                                        H.data_ptr(), ld, scratch.data_ptr(), nbytes, self._stream()), "gdmix_fe_hessian_dense_loss")
         return H
 
     @_serialised

@@ -141,6 +141,11 @@ def refuse_several_workers(execution_context, flag="--l2_reg_weights"):
         raise SweepError(f"{flag} runs on one worker: the AUC of several workers cannot be combined from their counts")
 
 
+def refuse_poisson(model_type):
+    if model_type == constants.POISSON_REGRESSION:
+        raise SweepError("--l2_reg_weights does not run with --model_type=poisson_regression: the sweep compares auc or mse, not poisson_loss")
+
+
 def refuse_blind_or_warm(mp, prior, prior_is=""):
     """No validation data, no metric directory, or a prior model (`prior`: the model files found where the stage would look for one)."""
     if not mp.validation_data_dir:
@@ -154,6 +159,7 @@ def refuse_blind_or_warm(mp, prior, prior_is=""):
 def validate(model, execution_context):
     """Everything a sweep does not do is refused here, before a partition is read or a solver created."""
     mp = model.model_params
+    refuse_poisson(getattr(model, "model_type", None))
     refuse_blind_or_warm(mp, sorted(glob.glob(os.path.join(mp.output_model_dir, "part-*.avro"))))
     if mp.rebalance_entities:
         raise SweepError("--l2_reg_weights does not run with --rebalance_entities=True")

@@ -80,6 +80,16 @@ def with_real_labels(batch, seed=0, scale=2.0, noise=1.0):
     return dataclasses.replace(batch, y=y, binary_labels=False)
 
 
+def with_count_labels(batch, seed=0):
+    """The same batch with count labels for --model_type=poisson_regression: y ~ Poisson(exp(0.7 y01 + 0.3 N(0, 1))) over the 0/1 labels
+    the generator planted, fp32 — counts whose rate still carries the planted effects. The counterpart of with_real_labels: every other
+    array is shared with `batch`, the result has binary_labels=False."""
+    import dataclasses
+    rng = np.random.default_rng([int(seed), 0xC0])
+    rate = np.exp(0.7 * np.asarray(batch.y, np.float64) + 0.3 * rng.standard_normal(batch.N))
+    return dataclasses.replace(batch, y=rng.poisson(rate).astype(np.float32), binary_labels=False)
+
+
 def make_survey_batch(E, mean_n=16, k=4, D=1024, seed=C2_SEED, size_dist="poisson", entity_id_base=0, with_uid=False):
     """The generator SURVEY.md §8(d) states for the measured configurations, to the letter: n_e = max(1, Poisson(mean_n)); per
     sample k DISTINCT columns drawn uniformly from [0, D) (in draw order, not sorted); values ~ N(0,1) fp32; offset ~ N(0,1)

@@ -40,6 +40,11 @@ typedef struct gdmix_fe_problem gdmix_fe_problem;
  * num_features: size of the global feature space D; coefficients are [D + has_intercept], intercept last.
  * opts: l2, regularize_bias, has_intercept, m (<= 10), max_iter, maxfun, maxls, ftol, pgtol, linear are used.
  * theta0: device pointer [D + has_intercept] or NULL (zeros).
+ * ---- poisson (ABI 19) ---- opts->linear is the loss code of include/gdmix_re.h (GDMIX_RE_LOSS_*; any other value is refused, also by
+ * gdmix_fe_restart, whose code must be the creation's). GDMIX_RE_LOSS_POISSON: the objective of gdmix_re.h's section "poisson" summed, not
+ * divided by n: f = sum_i w_i (exp(z_i) - y_i z_i) + (l2/2) |theta_reg|^2, g = X~' (w (exp(z) - y)) + l2 theta_reg, labels y >= 0
+ * real-valued; gdmix_fe_hessian_diag leaves sum_i X~_ij^2 w_i exp(z_i). The value is added up error-free as for the other losses, exp
+ * is the library's own (<= 0.98 ulp) and IEEE at the ends; gdmix_fe_score is unchanged (the margin z, never exp(z)).
  * The problem builds its own two copies of the non-zeros (8 B per non-zero each, 10 B when a unit of a pass spans more than 2^21
  * elements; temporary: 40 B per non-zero) and keeps reading the shard's y / offset / weight / unique_global, which must outlive it.
  * Synchronises the stream. Test hooks (environment): GDMIX_FE_CHUNK = entries per unit of a pass, GDMIX_FE_PACK=0 = the
@@ -74,6 +79,10 @@ GDMIX_API int gdmix_fe_hessian_diag(gdmix_fe_problem* p, const double* theta, vo
 GDMIX_API size_t gdmix_fe_hessian_dense_scratch_bytes(const gdmix_re_packed* shard);
 GDMIX_API int gdmix_fe_hessian_dense(gdmix_re_ctx* ctx, const gdmix_re_packed* shard, int has_intercept, const double* theta_local,
                                      double* H, int64_t ld, void* scratch, size_t scratch_bytes, void* stream);
+/* (ABI 19) The same with the curvature weight of a loss code (GDMIX_RE_LOSS_*, include/gdmix_re.h): D_i = w_i rho_i (1 - rho_i) for the
+ * logistic loss (what gdmix_fe_hessian_dense computes, whatever the problem's loss), 2 w_i for the squared, w_i exp(z_i) for the Poisson loss. */
+GDMIX_API int gdmix_fe_hessian_dense_loss(gdmix_re_ctx* ctx, const gdmix_re_packed* shard, int has_intercept, int loss, const double* theta_local,
+                                          double* H, int64_t ld, void* scratch, size_t scratch_bytes, void* stream);
 GDMIX_API int gdmix_fe_variance_of_hessian(gdmix_re_ctx* ctx, double* H, int64_t p, int64_t ld, double l2, int64_t unregularised_index,
                                            double* work, double* variance, void* stream);
 

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 18
+#define GDMIX_RE_ABI_VERSION 19
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -164,7 +164,8 @@ typedef struct {
    * (fixed_effect_lr_lbfgs_model.py:309-392): a batch with one "entity" = one worker's shard. Defaults 0.
    * sum_loss != 0 routes every entity to the device-wide team kernel, needs m <= 10 and refuses a variance mode. */
   int32_t sum_loss;         /* 1: f = sum_i w_i l_i + (l2/2)|theta_reg|^2, not divided by n (:363-381)            */
-  int32_t linear;           /* 1: l_i = (y_i - z_i)^2 (linear regression, :356-358) instead of the logistic loss */
+  int32_t linear;           /* the loss code, GDMIX_RE_LOSS_* below (ABI 19; until then a flag: 0 logistic, non-zero squared). 1: l_i = (y_i - z_i)^2
+                             * (linear regression, :356-358), 2: l_i = exp(z_i) - y_i z_i (section "poisson" below). Any other value is refused. */
   /* linear != 0 with sum_loss == 0 is the random effect's linear regression (--model_type=linear_regression; the reference has none: this
    * is its per-entity objective with its fixed-effect loss put in). For one entity of n samples, theta in local index space, intercept
    * first, labels y real-valued:
@@ -177,8 +178,28 @@ typedef struct {
    * weight D_i = 2 w_i in place of rho_i (1 - rho_i) w_i — it does not depend on theta:
    *     SIMPLE  1 / (sum_i D_i X~_ij^2 + l2 [- l2 for an unregularised intercept] + 1e-12)
    *     FULL    diag((X~' D X~ + (l2 + 1e-12) I [- l2 e0 e0'])^-1)      (gdmix_re_variance_full takes the loss from opts->linear too)
-   * neither divided by n, as in the reference. gdmix_re_score is the same for both losses: x . theta + offset. */
+   * neither divided by n, as in the reference. gdmix_re_score is the same for every loss: x . theta + offset.
+   *
+   * ---- poisson (ABI 19) ----
+   * linear == GDMIX_RE_LOSS_POISSON is Poisson regression (--model_type=poisson_regression; Photon-ML's PoissonLossFunction). For one
+   * entity of n samples, theta in local index space, the intercept first, labels y >= 0 real-valued:
+   *     z_i = x_i . theta + offset_i
+   *     f   = (1/n) ( sum_i w_i (exp(z_i) - y_i z_i) + (l2/2) |theta_reg|^2 )
+   *     g   = (1/n) ( X~' (w (exp(z) - y)) + l2 theta_reg )
+   *     D_i = w_i exp(z_i)            curvature weight for SIMPLE / FULL variance, at the returned theta
+   * The constant log(y!) is dropped. Everything else is exactly as for the other two losses (the loop, every stop and status code,
+   * thresholding, the size classes: a batch lands in the classes it lands in with the logistic loss), and every solve kernel has an
+   * instantiation of its own for this loss. The variances are those above with this D_i, not divided by n. With SIMPLE variance the
+   * classes of the team kernels need out->theta (D is evaluated at it by a kernel that follows them). gdmix_re_score is unchanged: the
+   * score is the margin z, never exp(z), which is what lets a stage's scores be the next stage's offsets.
+   * exp is the library's own (one range reduction, a degree-13 polynomial, ldexp: <= 0.98 ulp on normal results, gradual underflow) and
+   * IEEE at the ends: +inf past z ~ 709.78, NaN for NaN. The solver does nothing special about either: every loop is bounded by maxls,
+   * max_iter and maxfun, so such an entity ends with a status code. Keeping negative and non-finite labels out is the host's business. */
 } gdmix_re_opts;
+
+#define GDMIX_RE_LOSS_LOGISTIC 0
+#define GDMIX_RE_LOSS_SQUARED  1
+#define GDMIX_RE_LOSS_POISSON  2
 
 /* fills *o with the defaults above */
 GDMIX_API void gdmix_re_default_opts(gdmix_re_opts* o);
@@ -429,6 +450,45 @@ GDMIX_API int gdmix_re_eval_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_acc* acc, c
 GDMIX_API size_t gdmix_re_eval_acc_workspace_bytes(int64_t N);      /* N = acc->count */
 GDMIX_API int gdmix_re_eval_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_acc* acc, void* workspace, size_t workspace_bytes,
                                        gdmix_re_eval_totals* host_out, void* stream);
+
+/* ---- (ABI 19) poisson evaluation: the Poisson loss of a scored set, per entity and over a whole stage ---------------------------
+ * The metric of a --model_type=poisson_regression stage, where a linear stage reports MSE. csrc/re_evaluate_poisson.hip. The structs and
+ * entry points above are not involved.
+ *   PL          sum_i (exp(s_i) - y_i s_i) in fp64, the fp32 score s and label y widened first (log(y!) dropped, as in training); the mean
+ *               poisson_loss = PL / n is the caller's division. Unweighted, as the other metrics are.
+ *   trees       added in trees of a fixed shape, the shapes SSE is added in (at most 2 048 terms in a row per lane, 64 such sums in a row,
+ *               64 of those, the 256-lane tree, for the accumulator the workgroup sums in 16-term runs and one more tree): the same bits from
+ *               run to run. The accumulator adds the sums of its batches to a (hi, lo) pair without losing the additions' rounding errors: the
+ *               total is the rounded exact sum of the batches' sums, so it does not depend on the order the batches came in (two orders could
+ *               differ only if that exact sum lay within 2^-100 of the midpoint of two doubles). The terms have either sign, so the bound is
+ *               relative to the sum of magnitudes: |PL - exact| <= 3e-13 * sum_i (exp(s_i) + |y_i s_i|) — SSE's 2.5e-13 for the longest
+ *               chain of additions (< 2 211 roundings) plus exp (<= 0.98 ulp) and the one rounding of exp(s) - y s (a fused multiply-add).
+ *   NaN         a NaN score is counted (n_nan) and left out of the sum and of n. exp is IEEE: a score past ~88.7 (fp32) stays finite in fp64.
+ *   limits      fewer than 2^31 samples per evaluation and fewer than 2^31 entities (GDMIX_RE_ERANGE).
+ * Entities of at most 64 samples are summed in registers (four entities per wavefront, as gdmix_re_eval_entities does), larger ones by a
+ * workgroup each; gdmix_re_set_eval_small_max moves the limit for both evaluations. No workspace, no synchronisation per entity call. */
+typedef struct {          /* device pointers, [E] each; any may be NULL */
+  double*  pl;
+  int32_t* n;             /* samples with a score that is not NaN */
+  int32_t* n_nan;
+} gdmix_re_eval_pl_out;
+typedef struct {          /* host */
+  double  pl;
+  int64_t n;              /* samples added whose score is not NaN */
+  int64_t n_nan;
+} gdmix_re_eval_pl_totals;
+GDMIX_API int gdmix_re_eval_pl_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                        const gdmix_re_eval_pl_out* out, void* stream);
+/* The accumulator of a stage: `state` (GDMIX_RE_EVAL_PL_STATE_BYTES on the device) is the caller's buffer, `count` is kept by the library.
+ * `finish` synchronises `stream` and fills *host_out; the accumulator stays as it is, more batches may follow. */
+#define GDMIX_RE_EVAL_PL_STATE_BYTES 33024
+typedef struct {
+  void*   state;
+  int64_t count;
+} gdmix_re_eval_pl_acc;
+GDMIX_API int gdmix_re_eval_pl_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, void* stream);
+GDMIX_API int gdmix_re_eval_pl_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, const float* score, const float* label, int64_t N, void* stream);
+GDMIX_API int gdmix_re_eval_pl_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_pl_acc* acc, gdmix_re_eval_pl_totals* host_out, void* stream);
 
 /* ---- (ABI 14) sweep: K models trained on one batch score another batch in one pass over its non-zeros ----------------------------
  * A stage that sweeps l2_reg_weight (gdmix_amd/sweep.py) solves a training partition K times and scores the validation partition under

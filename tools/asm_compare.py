@@ -3,10 +3,13 @@ assembly with the build's flags (`hipcc -S --cuda-device-only`) and compared ker
 directives and per-compile labels. Kernels are matched by demangled name; --gained-false names kernels whose template list gained a
 trailing `false` argument since the other commit (a new compile-time parameter whose `false` instantiation must be the old kernel);
 --renamed old=new,... names kernels and types that were renamed since: the other commit's names and lines are read under the new names.
+--bool-as-int reads a boolean template argument and an integer one of the same value as one (a template parameter that went from
+`bool` to `int`: the symbols' `Lb0E` / `Lb1E` became `Li0E` / `Li1E`, in the kernels' own names and in every call of a device function).
 A kernel that moved to another unit is found there by its name.
 
     python tools/asm_compare.py --parent HEAD~1 \\
         --gained-false re_solve_grp_kernel,re_solve_wave_kernel,re_solve_block_kernel,re_variance_full_kernel,re_solve_tall_kernel,re_solve_tall_team_kernel
+    python tools/asm_compare.py --parent HEAD~1 --bool-as-int
 
 Prints per unit: kernels identical / different / only in this tree; exit status 1 if a kernel of the other commit differs or is missing.
 """
@@ -38,10 +41,15 @@ def compile_units(csrc, out):
         return dict(zip(units, ex.map(one, units)))
 
 
+BOOL_AS_INT = False
+
+
 def functions(path, renamed=()):
     """-> {mangled name: [normalised lines]}, {mangled name: kernel descriptor text}; `renamed`: (old, new) identifiers, applied to the
     text in their mangled (length-prefixed) spelling"""
     txt = open(path).read()
+    if BOOL_AS_INT:
+        txt = re.sub(r"L[bi]([01])E", r"Li\1E", txt)
     for o, n in renamed:
         txt = txt.replace(f"{len(o)}{o}", f"{len(n)}{n}")
     out, cur, buf = {}, None, []
@@ -75,7 +83,10 @@ def main():
     ap.add_argument("--gained-false", default="", help="comma list of kernel names whose template arguments gained a trailing `false`")
     ap.add_argument("--renamed", default="", help="comma list of old=new: kernel or type names of the other commit that were renamed since")
     ap.add_argument("--diff", action="store_true", help="print the lines of a kernel that differs")
+    ap.add_argument("--bool-as-int", action="store_true", help="template arguments false / true and 0 / 1 are the same argument")
     a = ap.parse_args()
+    global BOOL_AS_INT
+    BOOL_AS_INT = a.bool_as_int
     renamed = [tuple(r.split("=")) for r in a.renamed.split(",") if r]
     gained = [g for g in a.gained_false.split(",") if g]
 
