@@ -166,14 +166,16 @@ __device__ __forceinline__ void fe_emit_row(const FeDev& F, const SolveParams& o
   const double yi = (double)F.y[s];
   const double wi = F.w ? (double)F.w[s] : 1.0;
   double ri;
-  if (HESS && o.linear == LOSS_POISSON) {
+  // The test stays "Poisson, else non-zero, else logistic": it is sound because every entry point refuses a code outside the three
+  // (loss_code_ok), and spelling it == LOSS_SQUARED moves the code of the scatter and row kernels.
+  if (HESS && o.loss == LOSS_POISSON) {
     ri = wi * exp_any(zi);      // d_i = w_i exp(z_i) (include/gdmix_fe.h, "poisson")
   } else if (HESS) {
     const double rho = sigmoid_full(zi);
     ri = wi * rho * (1.0 - rho);
-  } else if (o.linear == LOSS_POISSON) {
+  } else if (o.loss == LOSS_POISSON) {
     dd_add(loss, loss_lo, poisson_terms(zi, yi, wi, ri));
-  } else if (o.linear) {
+  } else if (o.loss) {
     const double e = zi - yi;
     dd_add(loss, loss_lo, wi * e * e);
     ri = 2.0 * wi * e;
@@ -1421,7 +1423,7 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   if (!ctx || !b || !opts) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
   if (b->E != 1) { set_error("the shard must be packed as one entity (E = %lld)", (long long)b->E); return GDMIX_RE_EINVAL; }
   if (opts->m < 1 || opts->m > TEAM_MCAP) { set_error("1 <= m <= %d", TEAM_MCAP); return GDMIX_RE_EINVAL; }
-  if (!loss_code_ok(opts->linear, "gdmix_fe_create")) return GDMIX_RE_EINVAL;
+  if (!loss_code_ok(opts->loss, "gdmix_fe_create")) return GDMIX_RE_EINVAL;
   if (opts->regularize_bias && !opts->has_intercept) { set_error("regularize_bias requires has_intercept"); return GDMIX_RE_EINVAL; }
   if (num_features < 1 || num_features > 0x7ffffff0ll) { set_error("bad num_features"); return GDMIX_RE_EINVAL; }
   if (b->Z > 0x7ffffff0ll || b->N > 0x7ffffff0ll) { set_error("shard exceeds 2^31 samples or non-zeros"); return GDMIX_RE_ERANGE; }
@@ -1462,7 +1464,7 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   SolveParams& o = p->o;
   o.l2 = opts->l2; o.ftol = opts->ftol; o.pgtol = opts->pgtol; o.threshold = 0.0; o.regularize_bias = opts->regularize_bias;
   o.has_intercept = ic; o.m = opts->m; o.max_iter = opts->max_iter; o.maxfun = opts->maxfun; o.maxls = opts->maxls;
-  o.variance_mode = 0; o.sum_loss = 1; o.linear = opts->linear;
+  o.variance_mode = 0; o.sum_loss = 1; o.loss = opts->loss;
   // row pass: outputs = rows, gathered = x by local column: from the column-major arrays. Column pass: the other way round.
   std::vector<int32_t> uf_r, uf_c;
   int rc2 = fe_build_copy(s, ci->num_cus, b->col_ptr, F.d, b->csc_row, b->csc_val, F.z, F.n, false, (p->compress & 1) != 0, &F.rc, &p->copies[0],
@@ -1529,9 +1531,9 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
 GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, const double* theta0, void* stream) {
   if (!p || !opts) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
   const FeDev& F = p->F;
-  if ((opts->has_intercept ? 1 : 0) != F.ic || opts->m != F.m || opts->linear != p->o.linear) {
-    set_error("gdmix_fe_restart: has_intercept, linear and m must be the creation's (%d, %d, %d), not (%d, %d, %d): the pool is sized by them",
-              F.ic, p->o.linear, F.m, opts->has_intercept ? 1 : 0, opts->linear, opts->m);
+  if ((opts->has_intercept ? 1 : 0) != F.ic || opts->m != F.m || opts->loss != p->o.loss) {
+    set_error("gdmix_fe_restart: has_intercept, loss and m must be the creation's (%d, %d, %d), not (%d, %d, %d): the pool is sized by them",
+              F.ic, p->o.loss, F.m, opts->has_intercept ? 1 : 0, opts->loss, opts->m);
     return GDMIX_RE_EINVAL;
   }
   if (opts->regularize_bias && !opts->has_intercept) { set_error("regularize_bias requires has_intercept"); return GDMIX_RE_EINVAL; }

@@ -34,7 +34,7 @@ void set_error(const char* fmt, ...) {
 
 bool loss_code_ok(int code, const char* who) {
   if (code == GDMIX_RE_LOSS_LOGISTIC || code == GDMIX_RE_LOSS_SQUARED || code == GDMIX_RE_LOSS_POISSON) return true;
-  set_error("%s: opts->linear = %d is no loss code (GDMIX_RE_LOSS_LOGISTIC 0, GDMIX_RE_LOSS_SQUARED 1, GDMIX_RE_LOSS_POISSON 2)", who, code);
+  set_error("%s: opts->loss = %d is no loss code (GDMIX_RE_LOSS_LOGISTIC 0, GDMIX_RE_LOSS_SQUARED 1, GDMIX_RE_LOSS_POISSON 2)", who, code);
   return false;
 }
 
@@ -339,7 +339,7 @@ GDMIX_API void gdmix_re_default_opts(gdmix_re_opts* o) {
   o->l2 = 1.0; o->regularize_bias = 1; o->has_intercept = 1; o->m = 10; o->max_iter = 100;
   o->maxfun = 15000; o->maxls = 20; o->ftol = 1e-12; o->pgtol = 1e-5;
   o->variance_mode = GDMIX_RE_VAR_NONE; o->threshold = 1e-4;
-  o->sum_loss = 0; o->linear = 0;
+  o->sum_loss = 0; o->loss = 0;
 }
 
 GDMIX_API int gdmix_re_create(int hip_device, gdmix_re_ctx** out) {
@@ -745,13 +745,15 @@ int team_count(int tier_max, unsigned long long total_nnz, unsigned long long la
 // the workgroup kernel on the same stream, so its slots are free again), the device-wide class.
 int launch_slot_classes(gdmix_ctx_impl* ci, const gdmix_re_packed* b, const ClassCounts& hc, const BatchDev& B, OutDev O, const SolveParams& P,
                         const double* theta0, const Slots& slots, int n_slot_users, hipStream_t s) {
-  // squared loss, SIMPLE variance: the compact-form team kernels hold both losses and their epilogue is the logistic one. They get no
-  // variance pointer; re_variance_simple_lin_kernel fills these classes' entities in behind them (re_solve.hip)
-  const bool poi_var = P.linear == LOSS_POISSON && P.variance_mode == GDMIX_RE_VAR_SIMPLE && P.m <= TEAM_MCAP;   // D_i = w_i exp(z_i): needs theta
-  if (poi_var && !O.theta) { set_error("variance_mode SIMPLE with the Poisson loss needs out->theta"); return GDMIX_RE_EINVAL; }
-  const bool lin_var = P.linear == LOSS_SQUARED && P.variance_mode == GDMIX_RE_VAR_SIMPLE && P.m <= TEAM_MCAP;
+  // squared or Poisson loss, SIMPLE variance: the compact-form team kernels hold the losses in one instantiation and their epilogue is
+  // the logistic one. They get no variance pointer; re_variance_simple_kernel<LOSS> fills these classes' entities in behind them (re_solve.hip)
+  const bool follow_var = P.loss != LOSS_LOGISTIC && P.variance_mode == GDMIX_RE_VAR_SIMPLE && P.m <= TEAM_MCAP;
+  if (follow_var && P.loss == LOSS_POISSON && !O.theta) {   // D_i = w_i exp(z_i) is evaluated at theta; the squared loss's 2 w_i is not
+    set_error("variance_mode SIMPLE with the Poisson loss needs out->theta");
+    return GDMIX_RE_EINVAL;
+  }
   double* const variance = O.variance;
-  if (lin_var || poi_var) O.variance = nullptr;
+  if (follow_var) O.variance = nullptr;
   if (hc.count[BLOCK_CLASS] > 0) {
     const int rc = timed(ci, BLOCK_CLASS, s, [&] {
       return launch_solve_block(B, O, P, theta0, hc.base[BLOCK_CLASS], hc.count[BLOCK_CLASS], slots.scratch, slots.doubles, slots.n, b->max_p, s);
@@ -767,8 +769,7 @@ int launch_slot_classes(gdmix_ctx_impl* ci, const gdmix_re_packed* b, const Clas
     });
     if (rc != GDMIX_RE_OK) return rc;
   }
-  if (lin_var) HIP_TRY(launch_variance_simple_lin(B, P, variance, hc.base[BLOCK_CLASS], n_slot_users, ci->num_cus, s));
-  if (poi_var) HIP_TRY(launch_variance_simple_poi(B, P, O.theta, variance, hc.base[BLOCK_CLASS], n_slot_users, slots.scratch, slots.doubles, slots.n, s));
+  if (follow_var) HIP_TRY(launch_variance_simple(B, P, O.theta, variance, hc.base[BLOCK_CLASS], n_slot_users, slots.scratch, slots.doubles, slots.n, s));
   return GDMIX_RE_OK;
 }
 
@@ -780,7 +781,7 @@ GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
                    const gdmix_re_result* out, void* stream) {
   if (!ctx || !b || !opts || !out) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
   if (opts->m < 1 || opts->max_iter < 0 || opts->maxls < 1) { set_error("bad solver options (m, max_iter, maxls)"); return GDMIX_RE_EINVAL; }
-  if (!loss_code_ok(opts->linear, "gdmix_re_solve")) return GDMIX_RE_EINVAL;
+  if (!loss_code_ok(opts->loss, "gdmix_re_solve")) return GDMIX_RE_EINVAL;
   // regularize_bias without an intercept is legal for the random effect (REParams skips LRParams' check,
   // random_effect_lr_lbfgs_model.py:48-53): the whole theta is regularised (binary_logistic_regression.py:72-82)
   if (opts->variance_mode == GDMIX_RE_VAR_FULL) {
@@ -808,7 +809,7 @@ GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
   P.l2 = opts->l2; P.ftol = opts->ftol; P.pgtol = opts->pgtol; P.threshold = opts->threshold;
   P.regularize_bias = opts->regularize_bias; P.has_intercept = opts->has_intercept ? 1 : 0; P.m = opts->m; P.max_iter = opts->max_iter;
   P.maxfun = opts->maxfun; P.maxls = opts->maxls; P.variance_mode = opts->variance_mode;
-  P.sum_loss = opts->sum_loss ? 1 : 0; P.linear = opts->linear;
+  P.sum_loss = opts->sum_loss ? 1 : 0; P.loss = opts->loss;
   const BatchDev B = batch_dev(b);
   const OutDev O{out->theta, out->theta_thr, out->variance, out->fval, out->gnorm, out->nit, out->nfev, out->status};
   for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c) ci->ev_used[c] = false;
@@ -852,7 +853,7 @@ GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
 GDMIX_API int gdmix_re_variance_full(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const gdmix_re_opts* opts, const double* theta,
                                      double* variance, void* stream) {
   if (!ctx || !b || !opts || !theta || !variance) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
-  if (!loss_code_ok(opts->linear, "gdmix_re_variance_full")) return GDMIX_RE_EINVAL;
+  if (!loss_code_ok(opts->loss, "gdmix_re_variance_full")) return GDMIX_RE_EINVAL;
   if (b->max_p > VAR_FULL_BIG_MAX_P) {
     set_error("variance_mode FULL densifies a p x p Hessian per entity; largest entity has p = %d > %lld", b->max_p, (long long)VAR_FULL_BIG_MAX_P);
     return GDMIX_RE_ERANGE;
@@ -864,7 +865,7 @@ GDMIX_API int gdmix_re_variance_full(gdmix_re_ctx* ctx, const gdmix_re_packed* b
   P.l2 = opts->l2; P.ftol = opts->ftol; P.pgtol = opts->pgtol; P.threshold = opts->threshold;
   P.regularize_bias = opts->regularize_bias; P.has_intercept = opts->has_intercept ? 1 : 0; P.m = opts->m; P.max_iter = opts->max_iter;
   P.maxfun = opts->maxfun; P.maxls = opts->maxls; P.variance_mode = GDMIX_RE_VAR_FULL;
-  P.sum_loss = 0; P.linear = opts->linear;
+  P.sum_loss = 0; P.loss = opts->loss;
   return run_variance_full(ctx, b, batch_dev(b), P, theta, variance, static_cast<hipStream_t>(stream));
 }
 

@@ -252,11 +252,11 @@ __device__ __forceinline__ double poisson_terms(double z, double yi, double wi, 
   return wi * (e - yi * z);
 }
 
-// The loss codes of gdmix_re_opts.linear / SolveParams::linear (GDMIX_RE_LOSS_* in include/gdmix_re.h).
+// The loss codes of gdmix_re_opts.loss / SolveParams::loss (GDMIX_RE_LOSS_* in include/gdmix_re.h).
 constexpr int LOSS_LOGISTIC = 0, LOSS_SQUARED = 1, LOSS_POISSON = 2;
 
 // The per-sample loss of a solver instantiation, chosen at compile time (a run-time branch in the evaluation would move the register
-// allocation of the logistic kernels). LOSS_SQUARED: the squared loss of --model_type=linear_regression (include/gdmix_re.h, `linear`):
+// allocation of the logistic kernels). LOSS_SQUARED: the squared loss of --model_type=linear_regression (include/gdmix_re.h, `loss`):
 // returns w (y - z)^2, writes r = 2 w (z - y). No exp, log or reciprocal. LOSS_POISSON: poisson_terms above, one exp.
 template <int LOSS>
 __device__ __forceinline__ double loss_terms(double z, double yi, double wi, double& ri) {

@@ -15,12 +15,8 @@
 //                         sort over the bits in use (the only vendor call besides the prefix sum that numbers the large entities),
 //                         then the rank-sum pass, reduce-then-scan in two launches (rank_reduce_kernel, rank_scan_kernel): no
 //                         workgroup waits for another. Its time is the radix sort's passes over 8 B keys (profiles/evaluate_bench.txt).
-//   SSE                   fixed-shape trees of non-negative fp64 terms: a lane adds at most SSE_RUN = 2 048 terms in a row, at most 64
-//                         such sums in a row and at most 64 of those (a large entity: one workgroup, strided over its samples; the
-//                         accumulator: up to 4 096 workgroups, at most 2 048 terms per lane), then a 256-lane tree (8 levels) and,
-//                         for the accumulator, the workgroup sums in 16-term runs and one more tree. Longest chain of roundings:
-//                         2 048 + 64 + 64 + 8 + 16 + 8 + 3 < 4 096 -> relative error below 2.5e-13. The shape depends on the sample
-//                         count alone: two runs give the same bits. Never a floating-point atomic.
+//   SSE                   the fixed-shape sum of re_eval_sum.hpp over the non-negative fp64 terms (y - s)^2 (a large entity: one workgroup;
+//                         the accumulator: its batches' sums are added in the order they were given). Relative error below 2.5e-13.
 #include <stdint.h>
 #include <math.h>
 
@@ -28,16 +24,12 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "re_internal.hpp"
+#include "re_eval_sum.hpp"
 
 namespace gdmix {
 
 constexpr uint32_t KEY_NAN = 0xFFFFFFFFu;   // the key of no score (it is the image of a NaN): sorts behind +inf, counted apart
 constexpr int RANK_THREADS = 256, RANK_ITEMS = 16, RANK_TILE = RANK_THREADS * RANK_ITEMS;
-constexpr int SSE_RUN = 2048;               // terms a lane adds in a row,
-constexpr int SSE_RUNS = 64;                // sums of such runs it adds in a row
-constexpr int SSE_THREADS = 256;
-constexpr int ACC_MAX_GROUPS = 4096;        // workgroups of an accumulator batch (their sums: 16 per lane of the last tree)
-constexpr int ACC_PER_THREAD = 16;
 
 // fp32 score -> uint32 that orders as the floats do; -0 and +0 get one key
 __device__ __forceinline__ uint32_t sortable_key(float s) {
@@ -286,21 +278,8 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_scan_kernel(const uint64_t*
   }
 }
 
-// ---- SSE, fixed shapes ----------------------------------------------------------------------------------------------------------------
-// the 256 lane sums of a workgroup -> one (the same tree whatever the data)
-__device__ __forceinline__ double sse_block_tree(double v, double* lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int off = SSE_THREADS / 2; off > 0; off >>= 1) {
-    if (t < off) lds[t] += lds[t + off];
-    __syncthreads();
-  }
-  const double r = lds[0];
-  __syncthreads();
-  return r;
-}
-// lane t of `stride` lanes adds the terms i = begin + t, begin + t + stride, ...: SSE_RUN in a row, SSE_RUNS such runs in a row, and those
+// ---- SSE: the fixed-shape sum of re_eval_sum.hpp ---------------------------------------------------------------------------------------
+// lane t of `stride` lanes adds the terms i = begin + t, begin + t + stride, ...: EVAL_RUN in a row, EVAL_RUNS such runs in a row, and those
 // sums in a row (at most 64 of them below 2^31 samples on 256 lanes)
 __device__ __forceinline__ double sse_lane(const float* __restrict__ score, const float* __restrict__ label, int64_t begin, int64_t end, int64_t stride) {
   double top = 0.0, total = 0.0, run = 0.0;
@@ -308,53 +287,49 @@ __device__ __forceinline__ double sse_lane(const float* __restrict__ score, cons
   for (int64_t i = begin; i < end; i += stride) {
     const float s = score[i];
     if (s == s) run += sq_err(s, label[i]);
-    if (++in_run == SSE_RUN) {
+    if (++in_run == EVAL_RUN) {
       total += run; run = 0.0; in_run = 0;
-      if (++runs == SSE_RUNS) { top += total; total = 0.0; runs = 0; }
+      if (++runs == EVAL_RUNS) { top += total; total = 0.0; runs = 0; }
     }
   }
   return top + (total + run);
 }
 
 // one workgroup per large entity: its SSE, then its outputs from the rank-sum totals
-__global__ __launch_bounds__(SSE_THREADS) void eval_big_finish_kernel(const int64_t* __restrict__ ent_row_ptr, const int32_t* __restrict__ big_list,
-                                                                      const float* __restrict__ score, const float* __restrict__ label,
-                                                                      const uint64_t* __restrict__ acc_two_u, const uint32_t* __restrict__ acc_cnt, EvalOutDev O) {
-  __shared__ double lds[SSE_THREADS];
+__global__ __launch_bounds__(EVAL_THREADS) void eval_big_finish_kernel(const int64_t* __restrict__ ent_row_ptr, const int32_t* __restrict__ big_list,
+                                                                       const float* __restrict__ score, const float* __restrict__ label,
+                                                                       const uint64_t* __restrict__ acc_two_u, const uint32_t* __restrict__ acc_cnt, EvalOutDev O) {
+  __shared__ double lds[EVAL_THREADS];
   const int b = blockIdx.x;
   const int64_t e = big_list[b];
   const int64_t r0 = ent_row_ptr[e], r1 = ent_row_ptr[e + 1];
   double sse = 0.0;
-  if (O.sse) sse = sse_block_tree(sse_lane(score, label, r0 + threadIdx.x, r1, SSE_THREADS), lds);
+  if (O.sse) sse = eval_block_tree(sse_lane(score, label, r0 + threadIdx.x, r1, EVAL_THREADS), lds);
   if (threadIdx.x == 0)
     write_entity(O, e, acc_two_u[b], (int)acc_cnt[3 * (size_t)b], (int)acc_cnt[3 * (size_t)b + 1], (int)acc_cnt[3 * (size_t)b + 2], sse);
 }
 
-// accumulator: a batch's keys appended (segment 0) and its SSE, in the one read of the samples
-__global__ __launch_bounds__(SSE_THREADS) void eval_acc_add_kernel(const float* __restrict__ score, const float* __restrict__ label, int64_t N,
-                                                                   uint64_t* __restrict__ keys, double* __restrict__ group_sum) {
-  __shared__ double lds[SSE_THREADS];
-  const int64_t stride = (int64_t)gridDim.x * SSE_THREADS;
+// accumulator: a batch's keys appended (segment 0) and its SSE, in the one read of the samples (the accumulator's
+// lane sum of re_eval_sum.hpp: one level of runs)
+__global__ __launch_bounds__(EVAL_THREADS) void eval_acc_add_kernel(const float* __restrict__ score, const float* __restrict__ label, int64_t N,
+                                                                    uint64_t* __restrict__ keys, double* __restrict__ group_sum) {
+  __shared__ double lds[EVAL_THREADS];
+  const int64_t stride = (int64_t)gridDim.x * EVAL_THREADS;
   double total = 0.0, run = 0.0;
   int in_run = 0;
-  for (int64_t i = (int64_t)blockIdx.x * SSE_THREADS + threadIdx.x; i < N; i += stride) {
+  for (int64_t i = (int64_t)blockIdx.x * EVAL_THREADS + threadIdx.x; i < N; i += stride) {
     const float s = score[i], y = label[i];
     keys[i] = key33(s, y);
     if (s == s) run += sq_err(s, y);
-    if (++in_run == SSE_RUN) { total += run; run = 0.0; in_run = 0; }
+    if (++in_run == EVAL_RUN) { total += run; run = 0.0; in_run = 0; }
   }
-  const double v = sse_block_tree(total + run, lds);
+  const double v = eval_block_tree(total + run, lds);
   if (threadIdx.x == 0) group_sum[blockIdx.x] = v;
 }
 // the workgroup sums of a batch -> added to the accumulator's SSE (one workgroup; batches add up in the order they were given)
-__global__ __launch_bounds__(SSE_THREADS) void eval_acc_sum_kernel(const double* __restrict__ group_sum, int groups, double* __restrict__ sse) {
-  __shared__ double lds[SSE_THREADS];
-  double v = 0.0;
-  for (int j = 0; j < ACC_PER_THREAD; ++j) {
-    const int i = threadIdx.x * ACC_PER_THREAD + j;
-    if (i < groups) v += group_sum[i];
-  }
-  v = sse_block_tree(v, lds);
+__global__ __launch_bounds__(EVAL_THREADS) void eval_acc_sum_kernel(const double* __restrict__ group_sum, int groups, double* __restrict__ sse) {
+  __shared__ double lds[EVAL_THREADS];
+  const double v = acc_group_tree(group_sum, groups, lds);
   if (threadIdx.x == 0) *sse += v;
 }
 
@@ -427,9 +402,6 @@ static AccLayout acc_layout(int64_t N) {
   L.total = off;
   return L;
 }
-
-constexpr int64_t EVAL_LIMIT = (int64_t)1 << 31;
-constexpr size_t ACC_STATE_BYTES = 256 + (size_t)ACC_MAX_GROUPS * 8;   // the accumulator's SSE, then a batch's workgroup sums
 
 }  // namespace gdmix
 
@@ -507,7 +479,7 @@ GDMIX_API int gdmix_re_eval_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_p
   }
   rc = rank_sum(keys_b, M, nbig, partial, acc_two_u, acc_cnt, s);
   if (rc != GDMIX_RE_OK) return rc;
-  hipLaunchKernelGGL(eval_big_finish_kernel, dim3((unsigned)nbig), dim3(SSE_THREADS), 0, s, ent_row_ptr, (const int32_t*)big_list, score, label,
+  hipLaunchKernelGGL(eval_big_finish_kernel, dim3((unsigned)nbig), dim3(EVAL_THREADS), 0, s, ent_row_ptr, (const int32_t*)big_list, score, label,
                      (const uint64_t*)acc_two_u, (const uint32_t*)acc_cnt, O);
   HIP_TRY(hipGetLastError());
   return GDMIX_RE_OK;
@@ -516,7 +488,7 @@ GDMIX_API int gdmix_re_eval_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_p
 GDMIX_API int gdmix_re_eval_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_acc* acc, void* stream) {
   if (!ctx || !acc || acc->capacity < 0 || !acc->state) { set_error("gdmix_re_eval_acc_reset: bad argument (acc->state is required)"); return GDMIX_RE_EINVAL; }
   static_assert(GDMIX_RE_EVAL_ACC_STATE_BYTES >= ACC_STATE_BYTES, "the accumulator's device state");
-  HIP_TRY(hipMemsetAsync(acc->state, 0, 256, static_cast<hipStream_t>(stream)));
+  HIP_TRY(hipMemsetAsync(acc->state, 0, ACC_HEAD_BYTES, static_cast<hipStream_t>(stream)));
   acc->count = 0;
   return GDMIX_RE_OK;
 }
@@ -534,12 +506,11 @@ GDMIX_API int gdmix_re_eval_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_acc* acc, c
   }
   if (!score || !label) { set_error("gdmix_re_eval_acc_add: NULL input"); return GDMIX_RE_EINVAL; }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int64_t groups = (N + (int64_t)SSE_THREADS * 16 - 1) / ((int64_t)SSE_THREADS * 16);   // 16 samples per lane until the grid is full
-  if (groups > ACC_MAX_GROUPS) groups = ACC_MAX_GROUPS;
+  const int64_t groups = acc_groups(N);
   double* sse = static_cast<double*>(acc->state);
-  double* group_sum = reinterpret_cast<double*>(static_cast<char*>(acc->state) + 256);
-  hipLaunchKernelGGL(eval_acc_add_kernel, dim3((unsigned)groups), dim3(SSE_THREADS), 0, s, score, label, N, acc->keys + acc->count, group_sum);
-  hipLaunchKernelGGL(eval_acc_sum_kernel, dim3(1), dim3(SSE_THREADS), 0, s, (const double*)group_sum, (int)groups, sse);
+  double* group_sum = acc_group_sums(acc->state);
+  hipLaunchKernelGGL(eval_acc_add_kernel, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, s, score, label, N, acc->keys + acc->count, group_sum);
+  hipLaunchKernelGGL(eval_acc_sum_kernel, dim3(1), dim3(EVAL_THREADS), 0, s, (const double*)group_sum, (int)groups, sse);
   HIP_TRY(hipGetLastError());
   acc->count += N;
   return GDMIX_RE_OK;

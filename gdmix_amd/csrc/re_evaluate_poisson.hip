@@ -5,22 +5,19 @@
 //   eval_pl_small_kernel   entities of at most 64 samples (the testing knob of re_evaluate.hip, gdmix_re_set_eval_small_max, applies): a
 //                          wavefront takes FOUR consecutive entities and chooses its width from their sizes as eval_small_kernel does (16, 32
 //                          or 64 lanes per entity); lane i holds sample i; one fp64 xor-butterfly over the group (the same tree on every lane).
-//   eval_pl_big_kernel     every larger entity: one workgroup, strided over its samples, the lane sums in the fixed shape of re_evaluate.hip's
-//                          SSE (runs of 2 048 terms, 64 such runs, those in a row), then a 256-lane tree.
-//   accumulator            a batch: up to 4 096 workgroups, at most 2 048 terms per lane in a row, the 256-lane tree, the workgroup sums in 16-term
-//                          runs and one more tree: the shape depends on the batch's sample count alone. The batches' sums are added to a (hi, lo)
-//                          pair with TwoSum, so the stage's total is the rounded exact sum of its batches' sums, in whatever order they came.
+//   eval_pl_big_kernel     every larger entity: one workgroup, the fixed-shape sum of re_eval_sum.hpp.
+//   accumulator            a batch: the accumulator's sum of re_eval_sum.hpp. The batches' sums are added to a (hi, lo) pair with TwoSum, so
+//                          the stage's total is the rounded exact sum of its batches' sums, in whatever order they came.
+// The shape of every sum is SSE's: the constants, the trees and the accumulator's geometry are the same code (re_eval_sum.hpp).
 // Never a floating-point atomic; NaN scores are left out and counted (integer atomics: their sum has no order).
 #include <stdint.h>
 #include <math.h>
 #include <string.h>
 
 #include "re_internal.hpp"
+#include "re_eval_sum.hpp"
 
 namespace gdmix {
-
-constexpr int PL_RUN = 2048, PL_RUNS = 64, PL_THREADS = 256, PL_MAX_GROUPS = 4096, PL_PER_THREAD = 16;
-constexpr int64_t PL_LIMIT = (int64_t)1 << 31;
 
 // exp(s) - y s: exp_any (<= 0.98 ulp), then ONE rounding (the product is not rounded apart)
 __device__ __forceinline__ double pl_term(float s, float y) {
@@ -72,43 +69,29 @@ __global__ __launch_bounds__(64) void eval_pl_small_kernel(const int64_t* __rest
   }
 }
 
-// the 256 lane sums of a workgroup -> one (the same tree whatever the data)
-__device__ __forceinline__ double pl_block_tree(double v, double* lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int off = PL_THREADS / 2; off > 0; off >>= 1) {
-    if (t < off) lds[t] += lds[t + off];
-    __syncthreads();
-  }
-  const double r = lds[0];
-  __syncthreads();
-  return r;
-}
-
 // one workgroup per entity of the batch; those of the small path leave at once (the choice is uniform over the workgroup)
-__global__ __launch_bounds__(PL_THREADS) void eval_pl_big_kernel(const int64_t* __restrict__ ent_row_ptr, const float* __restrict__ score,
-                                                                 const float* __restrict__ label, PlOutDev O, int small_max) {
-  __shared__ double lds[PL_THREADS];
+__global__ __launch_bounds__(EVAL_THREADS) void eval_pl_big_kernel(const int64_t* __restrict__ ent_row_ptr, const float* __restrict__ score,
+                                                                   const float* __restrict__ label, PlOutDev O, int small_max) {
+  __shared__ double lds[EVAL_THREADS];
   __shared__ unsigned nan_count;
   const int64_t e = blockIdx.x;
   const int64_t r0 = ent_row_ptr[e], r1 = ent_row_ptr[e + 1];
   if (r1 - r0 <= small_max) return;
   if (threadIdx.x == 0) nan_count = 0u;
   __syncthreads();
-  double top = 0.0, total = 0.0, run = 0.0;
+  double top = 0.0, total = 0.0, run = 0.0;   // the lane sum of re_eval_sum.hpp, as sse_lane of re_evaluate.hip
   int in_run = 0, runs = 0;
   unsigned nans = 0u;
-  for (int64_t i = r0 + threadIdx.x; i < r1; i += PL_THREADS) {
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += EVAL_THREADS) {
     const float s = score[i];
     if (s == s) run += pl_term(s, label[i]); else ++nans;
-    if (++in_run == PL_RUN) {
+    if (++in_run == EVAL_RUN) {
       total += run; run = 0.0; in_run = 0;
-      if (++runs == PL_RUNS) { top += total; total = 0.0; runs = 0; }
+      if (++runs == EVAL_RUNS) { top += total; total = 0.0; runs = 0; }
     }
   }
   if (nans) atomicAdd(&nan_count, nans);
-  const double pl = pl_block_tree(top + (total + run), lds);   // (its barriers order the count too)
+  const double pl = eval_block_tree(top + (total + run), lds);   // (its barriers order the count too)
   if (threadIdx.x == 0) {
     if (O.pl) O.pl[e] = pl;
     if (O.n) O.n[e] = (int)((r1 - r0) - (int64_t)nan_count);
@@ -116,33 +99,29 @@ __global__ __launch_bounds__(PL_THREADS) void eval_pl_big_kernel(const int64_t* 
   }
 }
 
-// the accumulator's device state: [0] hi, [1] lo of the total, [2] the NaN scores (u64); from byte 256 a batch's workgroup sums
-__global__ __launch_bounds__(PL_THREADS) void eval_pl_acc_add_kernel(const float* __restrict__ score, const float* __restrict__ label, int64_t N,
-                                                                     double* __restrict__ group_sum, unsigned long long* __restrict__ n_nan) {
-  __shared__ double lds[PL_THREADS];
-  const int64_t stride = (int64_t)gridDim.x * PL_THREADS;
+// the accumulator's device state: [0] hi, [1] lo of the total, [2] the NaN scores (u64) in its head; then a batch's workgroup sums.
+// The lane loop is the accumulator's of re_eval_sum.hpp (one level of runs), as in eval_acc_add_kernel.
+__global__ __launch_bounds__(EVAL_THREADS) void eval_pl_acc_add_kernel(const float* __restrict__ score, const float* __restrict__ label, int64_t N,
+                                                                       double* __restrict__ group_sum, unsigned long long* __restrict__ n_nan) {
+  __shared__ double lds[EVAL_THREADS];
+  const int64_t stride = (int64_t)gridDim.x * EVAL_THREADS;
   double total = 0.0, run = 0.0;
   int in_run = 0;
   unsigned nans = 0u;
-  for (int64_t i = (int64_t)blockIdx.x * PL_THREADS + threadIdx.x; i < N; i += stride) {
+  for (int64_t i = (int64_t)blockIdx.x * EVAL_THREADS + threadIdx.x; i < N; i += stride) {
     const float s = score[i];
     if (s == s) run += pl_term(s, label[i]); else ++nans;
-    if (++in_run == PL_RUN) { total += run; run = 0.0; in_run = 0; }
+    if (++in_run == EVAL_RUN) { total += run; run = 0.0; in_run = 0; }
   }
   if (nans) atomicAdd(n_nan, (unsigned long long)nans);
-  const double v = pl_block_tree(total + run, lds);
+  const double v = eval_block_tree(total + run, lds);
   if (threadIdx.x == 0) group_sum[blockIdx.x] = v;
 }
 
 // the workgroup sums of a batch -> one sum, added to the accumulator's (hi, lo) without losing the rounding error of the addition
-__global__ __launch_bounds__(PL_THREADS) void eval_pl_acc_sum_kernel(const double* __restrict__ group_sum, int groups, double* __restrict__ state) {
-  __shared__ double lds[PL_THREADS];
-  double v = 0.0;
-  for (int j = 0; j < PL_PER_THREAD; ++j) {
-    const int i = threadIdx.x * PL_PER_THREAD + j;
-    if (i < groups) v += group_sum[i];
-  }
-  v = pl_block_tree(v, lds);
+__global__ __launch_bounds__(EVAL_THREADS) void eval_pl_acc_sum_kernel(const double* __restrict__ group_sum, int groups, double* __restrict__ state) {
+  __shared__ double lds[EVAL_THREADS];
+  const double v = acc_group_tree(group_sum, groups, lds);
   if (threadIdx.x == 0) {
     const double hi = state[0], lo = state[1];
     const double s = hi + v, bb = s - hi;
@@ -163,7 +142,7 @@ extern "C" {
 GDMIX_API int gdmix_re_eval_pl_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
                                         const gdmix_re_eval_pl_out* out, void* stream) {
   if (!ctx || !out || E < 0 || N < 0) { set_error("gdmix_re_eval_pl_entities: bad argument"); return GDMIX_RE_EINVAL; }
-  if (N >= PL_LIMIT || E >= PL_LIMIT) {
+  if (N >= EVAL_LIMIT || E >= EVAL_LIMIT) {
     set_error("gdmix_re_eval_pl_entities: %lld samples / %lld entities; an evaluation takes fewer than 2^31 of each", (long long)N, (long long)E);
     return GDMIX_RE_ERANGE;
   }
@@ -175,16 +154,16 @@ GDMIX_API int gdmix_re_eval_pl_entities(gdmix_re_ctx* ctx, const int64_t* ent_ro
   const int small_max = ci->eval_small_set ? ci->eval_small_max : 64;
   const PlOutDev O = {out->pl, out->n, out->n_nan};
   hipLaunchKernelGGL(eval_pl_small_kernel, dim3((unsigned)((E + 3) / 4)), dim3(64), 0, s, ent_row_ptr, E, score, label, O, small_max);
-  hipLaunchKernelGGL(eval_pl_big_kernel, dim3((unsigned)E), dim3(PL_THREADS), 0, s, ent_row_ptr, score, label, O, small_max);
+  hipLaunchKernelGGL(eval_pl_big_kernel, dim3((unsigned)E), dim3(EVAL_THREADS), 0, s, ent_row_ptr, score, label, O, small_max);
   HIP_TRY(hipGetLastError());
   return GDMIX_RE_OK;
 }
 
 GDMIX_API int gdmix_re_eval_pl_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, void* stream) {
   if (!ctx || !acc || !acc->state) { set_error("gdmix_re_eval_pl_acc_reset: bad argument (acc->state is required)"); return GDMIX_RE_EINVAL; }
-  static_assert(GDMIX_RE_EVAL_PL_STATE_BYTES >= 256 + (size_t)PL_MAX_GROUPS * 8, "the accumulator's device state");
+  static_assert(GDMIX_RE_EVAL_PL_STATE_BYTES >= ACC_STATE_BYTES, "the accumulator's device state");
   HIP_TRY(hipSetDevice(ctx->impl.device));
-  HIP_TRY(hipMemsetAsync(acc->state, 0, 256, static_cast<hipStream_t>(stream)));
+  HIP_TRY(hipMemsetAsync(acc->state, 0, ACC_HEAD_BYTES, static_cast<hipStream_t>(stream)));
   acc->count = 0;
   return GDMIX_RE_OK;
 }
@@ -192,20 +171,19 @@ GDMIX_API int gdmix_re_eval_pl_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc
 GDMIX_API int gdmix_re_eval_pl_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, const float* score, const float* label, int64_t N, void* stream) {
   if (!ctx || !acc || !acc->state || N < 0 || acc->count < 0) { set_error("gdmix_re_eval_pl_acc_add: bad argument"); return GDMIX_RE_EINVAL; }
   if (N == 0) return GDMIX_RE_OK;
-  if (acc->count + N >= PL_LIMIT) {
+  if (acc->count + N >= EVAL_LIMIT) {
     set_error("gdmix_re_eval_pl_acc_add: %lld + %lld samples; an evaluation takes fewer than 2^31", (long long)acc->count, (long long)N);
     return GDMIX_RE_ERANGE;
   }
   if (!score || !label) { set_error("gdmix_re_eval_pl_acc_add: NULL input"); return GDMIX_RE_EINVAL; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(ctx->impl.device));
-  int64_t groups = (N + (int64_t)PL_THREADS * 16 - 1) / ((int64_t)PL_THREADS * 16);   // 16 samples per lane until the grid is full
-  if (groups > PL_MAX_GROUPS) groups = PL_MAX_GROUPS;
+  const int64_t groups = acc_groups(N);
   double* state = static_cast<double*>(acc->state);
-  double* group_sum = reinterpret_cast<double*>(static_cast<char*>(acc->state) + 256);
-  hipLaunchKernelGGL(eval_pl_acc_add_kernel, dim3((unsigned)groups), dim3(PL_THREADS), 0, s, score, label, N, group_sum,
+  double* group_sum = acc_group_sums(acc->state);
+  hipLaunchKernelGGL(eval_pl_acc_add_kernel, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, s, score, label, N, group_sum,
                      reinterpret_cast<unsigned long long*>(state + 2));
-  hipLaunchKernelGGL(eval_pl_acc_sum_kernel, dim3(1), dim3(PL_THREADS), 0, s, (const double*)group_sum, (int)groups, state);
+  hipLaunchKernelGGL(eval_pl_acc_sum_kernel, dim3(1), dim3(EVAL_THREADS), 0, s, (const double*)group_sum, (int)groups, state);
   HIP_TRY(hipGetLastError());
   acc->count += N;
   return GDMIX_RE_OK;

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <type_traits>
+
 #include "../../include/gdmix_re.h"
 #include "re_solve_core.hpp"
 #include "re_solve_wreg.hpp"
@@ -403,11 +405,21 @@ hipError_t launch_solve_tall_team(const BatchDev& B, const OutDev& O, const Solv
 void launch_sort_class(int32_t* list, int count, const int64_t* ent_nnz_ptr, hipStream_t s);
 static_assert(LOSS_LOGISTIC == GDMIX_RE_LOSS_LOGISTIC && LOSS_SQUARED == GDMIX_RE_LOSS_SQUARED && LOSS_POISSON == GDMIX_RE_LOSS_POISSON,
               "the device's loss codes are the header's");
-// gdmix_re_opts.linear is a loss code: anything but the three is refused (sets the error text)
+// gdmix_re_opts.loss is a loss code: anything but the three is refused (sets the error text)
 bool loss_code_ok(int code, const char* who);
-hipError_t launch_variance_simple_poi(const BatchDev& B, const SolveParams& o, const double* theta, double* variance, int begin, int count,
-                                      double* scratch, size_t slot_doubles, int slots, hipStream_t s);
-hipError_t launch_variance_simple_lin(const BatchDev& B, const SolveParams& o, double* variance, int begin, int count, int num_cus, hipStream_t s);
+// The one place where a run-time loss code becomes a kernel's <LOSS>: f(std::integral_constant<int, LOSS_*>{}) -> hipError_t of the
+// code's loss. A code that is none of the three is an error here too, never some loss's kernel.
+template <class F>
+inline hipError_t with_loss(int code, F&& f) {
+  switch (code) {
+    case LOSS_LOGISTIC: return f(std::integral_constant<int, LOSS_LOGISTIC>{});
+    case LOSS_SQUARED: return f(std::integral_constant<int, LOSS_SQUARED>{});
+    case LOSS_POISSON: return f(std::integral_constant<int, LOSS_POISSON>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t launch_variance_simple(const BatchDev& B, const SolveParams& o, const double* theta, double* variance, int begin, int count,
+                                  double* scratch, size_t slot_doubles, int slots, hipStream_t s);
 hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams& o, const double* theta, double* variance,
                                 double* scratch, size_t slot_doubles, int slots, int64_t max_p, hipStream_t s);
 constexpr int64_t VAR_FULL_MAX_P = 2048;   // FULL variance densifies p x p (as the reference does): one wavefront per entity up to here,

@@ -48,7 +48,7 @@ int make_class_table(const gdmix_ctx_impl* ci, const gdmix_re_opts* opts, ClassT
     if (opts->variance_mode != GDMIX_RE_VAR_NONE) { set_error("variance is not available with sum_loss"); return GDMIX_RE_EINVAL; }
     tab.giant_nnz = 1;
   }
-  // linear without sum_loss is the random effect's squared loss: the normal class table, every launcher picks its <LOSS> kernels by P.linear
+  // a loss without sum_loss is the random effect's: the normal class table, every launcher picks its <LOSS> kernels by P.loss (with_loss)
   return GDMIX_RE_OK;
 }
 

@@ -49,7 +49,7 @@ __device__ __forceinline__ void write_results(G& grp, const OutDev& O, const Sol
 // G < 64: 64/G entities per wavefront; G = 64: one; G > 64: one entity per workgroup of G/64 wavefronts
 // (cross-wave stage of every reduction through LDS + one barrier).
 // LOSS: the loss code of the instantiation (re_device.hpp, loss_terms), a template parameter of every solve kernel: the <LOSS_LOGISTIC>
-// instantiations hold the code they held before the other losses existed; the launchers choose by SolveParams::linear.
+// instantiations hold the code they held before the other losses existed; the launchers choose by SolveParams::loss (with_loss).
 template <int G, int EPL, int NCAP, int ZCAP, int LOSS>
 __global__ __launch_bounds__(G > WAVE ? G : WAVE)
 __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 ? GDMIX_QUAD_WAVES_EPL4 : 1)))) void re_solve_grp_kernel(
@@ -210,9 +210,7 @@ hipError_t launch_solve_quad(int g, int epl, const BatchDev& B, const OutDev& O,
   if (count <= 0) return hipSuccess;
 #define GDMIX_GRP_CASE(GG, EE, NN, ZZ) \
   if (g == GG && epl == EE && ncap == NN && zcap == ZZ)                                                            \
-    return o.linear == LOSS_POISSON ? launch_quad_t<GG, EE, NN, ZZ, LOSS_POISSON>(B, O, o, theta0, begin, count, s)                 \
-           : o.linear ? launch_quad_t<GG, EE, NN, ZZ, LOSS_SQUARED>(B, O, o, theta0, begin, count, s)                                \
-                      : launch_quad_t<GG, EE, NN, ZZ, LOSS_LOGISTIC>(B, O, o, theta0, begin, count, s);
+    return with_loss(o.loss, [&](auto L) { return launch_quad_t<GG, EE, NN, ZZ, decltype(L)::value>(B, O, o, theta0, begin, count, s); });
   GDMIX_GRP_CASE(16, 2, 16, 64) GDMIX_GRP_CASE(16, 2, 32, 128) GDMIX_GRP_CASE(16, 2, 128, 512)
   GDMIX_GRP_CASE(16, 3, 16, 64) GDMIX_GRP_CASE(16, 3, 32, 128) GDMIX_GRP_CASE(16, 3, 128, 512)
   GDMIX_GRP_CASE(16, 4, 16, 64) GDMIX_GRP_CASE(16, 4, 32, 128) GDMIX_GRP_CASE(16, 4, 128, 512)
@@ -298,20 +296,13 @@ __global__ __launch_bounds__(WAVE) void re_solve_wave_kernel(BatchDev B, OutDev 
 hipError_t launch_solve_wave(const BatchDev& B, const OutDev& O, const SolveParams& o, const double* theta0,
                              int begin, int count, int lds_bytes, hipStream_t s) {
   if (count <= 0) return hipSuccess;
-  static DynLdsOnce lds_attr, lin_attr, poi_attr;
-  if (o.linear == LOSS_POISSON) {
-    if (hipError_t rc = poi_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<LOSS_POISSON>)); rc != hipSuccess) return rc;
-    hipLaunchKernelGGL(re_solve_wave_kernel<LOSS_POISSON>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
+  return with_loss(o.loss, [&](auto L) {
+    constexpr int LOSS = decltype(L)::value;
+    static DynLdsOnce lds_attr;   // one per instantiation of this lambda, i.e. per kernel
+    if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<LOSS>)); rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(re_solve_wave_kernel<LOSS>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
     return hipGetLastError();
-  }
-  if (o.linear) {
-    if (hipError_t rc = lin_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<LOSS_SQUARED>)); rc != hipSuccess) return rc;
-    hipLaunchKernelGGL(re_solve_wave_kernel<LOSS_SQUARED>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
-    return hipGetLastError();
-  }
-  if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_solve_wave_kernel<LOSS_LOGISTIC>)); rc != hipSuccess) return rc;
-  hipLaunchKernelGGL(re_solve_wave_kernel<LOSS_LOGISTIC>, dim3(count), dim3(WAVE), (size_t)lds_bytes, s, B, O, o, theta0, begin);
-  return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -580,16 +571,11 @@ hipError_t launch_solve_block(const BatchDev& B, const OutDev& O, const SolvePar
   if (count <= 0) return hipSuccess;
   if (o.m > TEAM_MCAP) {   // two-loop form, any m
     int grid = count < slots ? count : slots;
-    if (o.linear == LOSS_POISSON)
-      hipLaunchKernelGGL(re_solve_block_kernel<LOSS_POISSON>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
+    return with_loss(o.loss, [&](auto L) {
+      hipLaunchKernelGGL(re_solve_block_kernel<decltype(L)::value>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
                          scratch, slot_doubles, max_p);
-    else if (o.linear)
-      hipLaunchKernelGGL(re_solve_block_kernel<LOSS_SQUARED>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
-                         scratch, slot_doubles, max_p);
-    else
-      hipLaunchKernelGGL(re_solve_block_kernel<LOSS_LOGISTIC>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, O, o, theta0, begin, count,
-                         scratch, slot_doubles, max_p);
-    return hipGetLastError();
+      return hipGetLastError();
+    });
   }
   return launch_team_block<TEAM_BLOCK_NW>(B, O, o, theta0, begin, count, scratch, slot_doubles, slots, max_p, s);
 }
@@ -625,69 +611,12 @@ hipError_t launch_solve_grid(const BatchDev& B, const OutDev& O, const SolvePara
 }
 
 // ---------------------------------------------------------------------------------------------------
-// SIMPLE variance of the squared loss for the classes of the team kernels (workgroup, team tiers, device-wide). Those kernels hold both
-// losses in one instantiation (SolveParams::linear at run time, the fixed-effect path) and their epilogue is the logistic variance_simple:
-// rather than a run-time branch in them, the launcher withholds O.variance from them and this kernel follows. D_i = 2 w_i does not
-// depend on theta: 1 / (sum_i 2 w_i X~_ij^2 + l2 [j regularised] + 1e-12), duplicates of a cell summed before squaring as in variance_simple.
-// One workgroup per entity of order[begin, begin + count), grid-stride.
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WAVE* BLOCK_NW) void re_variance_simple_lin_kernel(BatchDev B, SolveParams o, double* __restrict__ variance, int begin, int count) {
-  __shared__ double red[2 * BLOCK_NW];
-  const int ic = o.has_intercept ? 1 : 0;
-  const int first_reg = (ic && !o.regularize_bias) ? 1 : 0;
-  BlockGroup<BLOCK_NW> grp{(int)threadIdx.x, red, 0};
-  for (int idx = blockIdx.x; idx < count; idx += gridDim.x) {
-    const int64_t e = B.order[begin + idx];
-    const int64_t r0 = B.ent_row_ptr[e], z0 = B.ent_nnz_ptr[e], f0 = B.ent_feat_ptr[e];
-    const int n = (int)(B.ent_row_ptr[e + 1] - r0);
-    const int p = (int)(B.ent_feat_ptr[e + 1] - f0) + ic;
-    const int64_t c0 = f0 + e * ic;
-    const float* const w = B.weight ? B.weight + r0 : nullptr;
-    const int32_t* const col_ptr = B.col_ptr + z0 + e;
-    const int32_t* const csc_row = B.csc_row + z0;
-    const float* const csc_val = B.csc_val + z0;
-    double dpart = 0.0;
-    if (ic)
-      for (int i = grp.tid; i < n; i += grp.NT) dpart += 2.0 * (w ? (double)w[i] : 1.0);
-    const double dsum = grp.sum(dpart);   // (uniform trip: every thread of the workgroup reduces, whatever ic is)
-    for (int j = grp.tid; j < p; j += grp.NT) {
-      double h;
-      if (ic && j == 0) {
-        h = dsum;
-      } else {
-        h = 0.0;
-        const int c = j - ic;
-        const int k1 = col_ptr[c + 1];
-        int k = col_ptr[c];
-        while (k < k1) {   // runs of equal row = duplicates of one matrix cell
-          const int row = csc_row[k];
-          double v = (double)csc_val[k];
-          ++k;
-          while (k < k1 && csc_row[k] == row) { v += (double)csc_val[k]; ++k; }
-          h += v * v * (2.0 * (w ? (double)w[row] : 1.0));
-        }
-      }
-      h += (j < first_reg) ? 0.0 : o.l2;
-      variance[c0 + j] = 1.0 / (h + 1.0e-12);
-    }
-  }
-}
-
-hipError_t launch_variance_simple_lin(const BatchDev& B, const SolveParams& o, double* variance, int begin, int count, int num_cus, hipStream_t s) {
-  if (count <= 0) return hipSuccess;
-  int grid = 8 * num_cus;
-  if (grid > count) grid = count;
-  hipLaunchKernelGGL(re_variance_simple_lin_kernel, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, o, variance, begin, count);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------
 // FULL variance: diag((X~' D X~ + (l2 + 1e-12) I - l2 e0 e0')^-1)   (binary_logistic_regression.py:181-187)
 // One wavefront per entity, H and L^-1 in a global scratch slot (2 p^2 + p + n doubles). H is SPD, so the
 // inverse comes from a Cholesky factor: diag(H^-1)_j = sum_i (L^-1)_ij^2 (the reference uses LU,
 // np.linalg.inv; both agree to rounding on these well-conditioned matrices).
 // ---------------------------------------------------------------------------------------------------
-// LOSS: the loss code; squared: D_i = 2 w_i, Poisson: D_i = w_i exp(z_i) (include/gdmix_re.h, `linear`)
+// LOSS: the loss code; squared: D_i = 2 w_i, Poisson: D_i = w_i exp(z_i) (include/gdmix_re.h, `loss`)
 template <int LOSS>
 __global__ __launch_bounds__(256) void re_variance_full_kernel(BatchDev B, int64_t E, SolveParams o,
                                                                const double* __restrict__ theta,
@@ -788,11 +717,18 @@ __global__ __launch_bounds__(256) void re_variance_full_kernel(BatchDev B, int64
   }
 }
 
-// The same for the Poisson loss, whose D_i = w_i exp(z_i) needs the margins at the returned theta: variance_simple<false, LOSS_POISSON> of
-// re_solve_core.hpp, one workgroup per entity, D in the head of the workgroup's scratch slot (the team kernels that used it are done).
-__global__ __launch_bounds__(WAVE* BLOCK_NW) void re_variance_simple_poi_kernel(BatchDev B, SolveParams o, const double* __restrict__ theta,
-                                                                                double* __restrict__ variance, int begin, int count,
-                                                                                double* scratch, size_t slot_doubles) {
+// ---------------------------------------------------------------------------------------------------
+// SIMPLE variance of the squared and the Poisson loss for the classes of the team kernels (workgroup, team tiers, device-wide). Those
+// kernels hold the losses in one instantiation (SolveParams::loss at run time, the fixed-effect path) and their epilogue is the logistic
+// variance_simple: rather than a run-time branch in them, the launcher withholds O.variance from them and this kernel follows:
+// variance_simple<false, LOSS> of re_solve_core.hpp, one workgroup per entity of order[begin, begin + count), grid-stride, D in the head
+// of the workgroup's scratch slot (the team kernels that used it are done). Poisson's D_i = w_i exp(z_i) needs the margins at the
+// returned theta; the squared loss's D_i = 2 w_i does not, and its instantiation never reads theta (which may be NULL then).
+// ---------------------------------------------------------------------------------------------------
+template <int LOSS>
+__global__ __launch_bounds__(WAVE* BLOCK_NW) void re_variance_simple_kernel(BatchDev B, SolveParams o, const double* __restrict__ theta,
+                                                                            double* __restrict__ variance, int begin, int count,
+                                                                            double* scratch, size_t slot_doubles) {
   __shared__ double red[2 * BLOCK_NW];
   const int ic = o.has_intercept ? 1 : 0;
   BlockGroup<BLOCK_NW> grp{(int)threadIdx.x, red, 0};
@@ -807,17 +743,24 @@ __global__ __launch_bounds__(WAVE* BLOCK_NW) void re_variance_simple_poi_kernel(
     W.x = const_cast<double*>(theta) + c0;
     EntityView P{n, d, d + ic, ic, B.row_ptr + r0 + e, B.csr_col + z0, B.csr_val + z0, B.col_ptr + z0 + e,
                  B.csc_row + z0, B.csc_val + z0, B.y + r0, B.offset + r0, B.weight ? B.weight + r0 : nullptr};
-    variance_simple<false, LOSS_POISSON>(grp, P, o, W, variance + c0);   // (ends on a barrier: the slot is free for the next entity)
+    variance_simple<false, LOSS>(grp, P, o, W, variance + c0);   // (ends on a barrier: the slot is free for the next entity)
   }
 }
 
-hipError_t launch_variance_simple_poi(const BatchDev& B, const SolveParams& o, const double* theta, double* variance, int begin, int count,
-                                      double* scratch, size_t slot_doubles, int slots, hipStream_t s) {
+hipError_t launch_variance_simple(const BatchDev& B, const SolveParams& o, const double* theta, double* variance, int begin, int count,
+                                  double* scratch, size_t slot_doubles, int slots, hipStream_t s) {
   if (count <= 0) return hipSuccess;
   const int grid = count < slots ? count : slots;
-  hipLaunchKernelGGL(re_variance_simple_poi_kernel, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, o, theta, variance, begin, count, scratch,
-                     slot_doubles);
-  return hipGetLastError();
+  return with_loss(o.loss, [&](auto L) {
+    constexpr int LOSS = decltype(L)::value;
+    if constexpr (LOSS == LOSS_LOGISTIC) {
+      return hipErrorInvalidValue;   // the team kernels' own epilogue: no follow-up kernel
+    } else {
+      hipLaunchKernelGGL(re_variance_simple_kernel<LOSS>, dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, B, o, theta, variance, begin, count, scratch,
+                         slot_doubles);
+      return hipGetLastError();
+    }
+  });
 }
 
 hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams& o, const double* theta, double* variance,
@@ -827,16 +770,11 @@ hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams&
   if ((int64_t)waves > E) waves = (int)E;
   const int blocks = (waves + 3) / 4;
   // every wave of the grid owns one slot: grid = blocks * 4 waves <= slots is ensured by the caller
-  if (o.linear == LOSS_POISSON)
-    hipLaunchKernelGGL(re_variance_full_kernel<LOSS_POISSON>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
+  return with_loss(o.loss, [&](auto L) {
+    hipLaunchKernelGGL(re_variance_full_kernel<decltype(L)::value>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
                        slot_doubles, max_p);
-  else if (o.linear)
-    hipLaunchKernelGGL(re_variance_full_kernel<LOSS_SQUARED>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
-                       slot_doubles, max_p);
-  else
-    hipLaunchKernelGGL(re_variance_full_kernel<LOSS_LOGISTIC>, dim3(blocks), dim3(256), 0, s, B, E, o, theta, variance, scratch,
-                       slot_doubles, max_p);
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ namespace gdmix {
 struct SolveParams {
   double l2, ftol, pgtol, threshold;
   int regularize_bias, has_intercept, m, max_iter, maxfun, maxls, variance_mode;
-  int sum_loss, linear;   // sum_loss: fixed-effect objective (team kernels only); linear: the loss code, LOSS_* of re_device.hpp (the launchers pick the <LOSS> kernels by it)
+  int sum_loss, loss;   // sum_loss: fixed-effect objective (team kernels only); loss: the loss code, LOSS_* of re_device.hpp (the launchers pick the <LOSS> kernels by it: with_loss)
 };
 
 // One entity's data, pointers into LDS (wave kernel) or HBM (block kernel).
@@ -292,10 +292,10 @@ __device__ void lbfgs_solve(G& grp, const EntityView& P, const SolveParams& o, c
 
 // _compute_variance, SIMPLE mode (binary_logistic_regression.py:175-180): 1/(sum_i X~_ij^2 D_i + l2*[j reg] + 1e-12),
 // D_i = rho_i (1-rho_i) w_i. Duplicate (row, col) entries are summed before squaring, as the reference's
-// toarray() does. W.rs is reused for D. Squared loss: D_i = 2 w_i (include/gdmix_re.h, `linear`).
+// toarray() does. W.rs is reused for D. Squared loss: D_i = 2 w_i (include/gdmix_re.h, `loss`).
 // SC1: the team's exchanged vectors (W.x, W.rs) are accessed through sc1 loads / stores (re_device.hpp, ld_x / st_x)
 // LOSS: the loss code; Poisson: D_i = w_i exp(z_i) (the team kernels hold the losses in one instantiation and stay logistic here: re_solve.hip,
-// re_variance_simple_lin_kernel, re_variance_simple_poi_kernel)
+// re_variance_simple_kernel<LOSS>)
 template <bool SC1 = false, int LOSS = LOSS_LOGISTIC, class G>
 __device__ __forceinline__ void variance_simple(G& grp, const EntityView& P, const SolveParams& o, const Work& W,
                                                 double* var_out) {

@@ -288,9 +288,11 @@ __device__ __forceinline__ double team_fg(Team<NW>& tm, const EntityView& P, con
     const double yi = (double)P.y[i];
     const double wi = P.w ? (double)P.w[i] : 1.0;
     double ri;
-    if (o.linear == LOSS_POISSON) {   // include/gdmix_re.h, "poisson"
+    // The test stays "Poisson, else non-zero, else logistic": it is sound because every entry point refuses a code outside the three
+    // (loss_code_ok), and spelling it == LOSS_SQUARED moves this kernel's code.
+    if (o.loss == LOSS_POISSON) {   // include/gdmix_re.h, "poisson"
       pr[0] += poisson_terms(z, yi, wi, ri);
-    } else if (o.linear) {   // squared loss, fixed_effect_lr_lbfgs_model.py:356-358
+    } else if (o.loss) {   // squared loss, fixed_effect_lr_lbfgs_model.py:356-358
       const double e = z - yi;
       pr[0] += wi * e * e;
       ri = 2.0 * wi * e;

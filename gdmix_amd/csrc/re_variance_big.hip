@@ -1,7 +1,7 @@
 // re_variance_big.hip — FULL coefficient variances of entities too large for one wavefront (p > VAR_FULL_MAX_P):
 // diag((X~' D X~ + (l2 + 1e-12) I - l2 e0 e0')^-1), binary_logistic_regression.py:181-187 (the reference densifies the Hessian
 // and calls np.linalg.inv whatever p is). One entity at a time, the whole device on it:
-//   vf_rows_kernel      d_i = w_i rho_i (1 - rho_i)      (vf_rows_lin_kernel: d_i = 2 w_i, the squared loss)
+//   vf_rows_kernel<LOSS>  d_i = w_i rho_i (1 - rho_i)    (squared loss: d_i = 2 w_i, Poisson: d_i = w_i exp(z_i))
 //   vf_build_kernel     H = X~' D X~ column by column: workgroup a spreads d .* column a over the samples and takes its
 //                       products with the columns b >= a (ordered sums: deterministic), H symmetric, leading dimension padded to tiles
 //   vf_potrf / vf_trsm / vf_syrk   right-looking Cholesky H = L L' on 64 x 64 tiles
@@ -38,32 +38,32 @@ __global__ void vf_list_kernel(BatchDev B, int64_t E, int ic, int min_p, VfEntit
   }
 }
 
+// LOSS: the loss code. The squared loss's weight does not depend on theta: its instantiation reads neither theta nor the rows.
+template <int LOSS>
 __global__ void vf_rows_kernel(BatchDev B, VfEntity V, int ic, const double* __restrict__ theta, double* __restrict__ dvec) {
   const double* th = theta + V.c0;
   const int32_t* rp = B.row_ptr + V.r0 + V.e;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V.n; i += gridDim.x * blockDim.x) {
-    double acc = ic ? th[0] : 0.0;
-    for (int k = rp[i]; k < rp[i + 1]; ++k) acc += (double)B.csr_val[V.z0 + k] * th[ic + B.csr_col[V.z0 + k]];
-    const double rho = sigmoid_full(acc + (double)B.offset[V.r0 + i]);
-    dvec[i] = rho * (1.0 - rho) * (B.weight ? (double)B.weight[V.r0 + i] : 1.0);
+    double d = 2.0;   // the squared loss
+    if constexpr (LOSS != LOSS_SQUARED) {
+      double acc = ic ? th[0] : 0.0;
+      for (int k = rp[i]; k < rp[i + 1]; ++k) acc += (double)B.csr_val[V.z0 + k] * th[ic + B.csr_col[V.z0 + k]];
+      const double z = acc + (double)B.offset[V.r0 + i];
+      if constexpr (LOSS == LOSS_POISSON) {   // include/gdmix_re.h, "poisson"
+        d = exp_any(z);
+      } else {
+        const double rho = sigmoid_full(z);
+        d = rho * (1.0 - rho);
+      }
+    }
+    dvec[i] = d * (B.weight ? (double)B.weight[V.r0 + i] : 1.0);
   }
 }
-
-// squared loss: the curvature weight does not depend on theta
-__global__ void vf_rows_lin_kernel(BatchDev B, VfEntity V, double* __restrict__ dvec) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V.n; i += gridDim.x * blockDim.x)
-    dvec[i] = 2.0 * (B.weight ? (double)B.weight[V.r0 + i] : 1.0);
-}
-
-// Poisson loss: D_i = w_i exp(z_i) at the returned theta (include/gdmix_re.h, "poisson")
-__global__ void vf_rows_poi_kernel(BatchDev B, VfEntity V, int ic, const double* __restrict__ theta, double* __restrict__ dvec) {
-  const double* th = theta + V.c0;
-  const int32_t* rp = B.row_ptr + V.r0 + V.e;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V.n; i += gridDim.x * blockDim.x) {
-    double acc = ic ? th[0] : 0.0;
-    for (int k = rp[i]; k < rp[i + 1]; ++k) acc += (double)B.csr_val[V.z0 + k] * th[ic + B.csr_col[V.z0 + k]];
-    dvec[i] = exp_any(acc + (double)B.offset[V.r0 + i]) * (B.weight ? (double)B.weight[V.r0 + i] : 1.0);
-  }
+static hipError_t launch_vf_rows(int loss, const BatchDev& B, const VfEntity& V, int ic, const double* theta, double* dvec, hipStream_t s) {
+  return with_loss(loss, [&](auto L) {
+    hipLaunchKernelGGL(vf_rows_kernel<decltype(L)::value>, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
+    return hipGetLastError();
+  });
 }
 
 // H = identity on the padding, zero elsewhere
@@ -330,9 +330,8 @@ hipError_t launch_variance_full_big(gdmix_ctx_impl* ci, const BatchDev& B, int64
   double* wslots = dvec + max_n;
   for (int q = 0; q < n_big; ++q) {
     const VfEntity& V = host[(size_t)q];
-    if (o.linear == LOSS_POISSON) hipLaunchKernelGGL(vf_rows_poi_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
-    else if (o.linear) hipLaunchKernelGGL(vf_rows_lin_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, dvec);
-    else hipLaunchKernelGGL(vf_rows_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
+    rc = launch_vf_rows(o.loss, B, V, ic, theta, dvec, s);
+    if (rc != hipSuccess) return rc;
     hipLaunchKernelGGL(vf_clear_kernel, dim3(ci->num_cus * 8), dim3(256), 0, s, H, V.p, V.ld);
     rc = hipMemsetAsync(wslots, 0, (size_t)V.n * VAR_BIG_BUILD_GROUPS * 8, s);
     if (rc != hipSuccess) return rc;
@@ -359,9 +358,7 @@ hipError_t launch_hessian_dense(gdmix_ctx_impl* ci, const BatchDev& B, int64_t n
   o.has_intercept = ic;
   double* dvec = scratch;
   double* wslots = dvec + n;
-  if (loss == LOSS_POISSON) hipLaunchKernelGGL(vf_rows_poi_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
-  else if (loss == LOSS_SQUARED) hipLaunchKernelGGL(vf_rows_lin_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, dvec);
-  else hipLaunchKernelGGL(vf_rows_kernel, dim3((V.n + 255) / 256), dim3(256), 0, s, B, V, ic, theta, dvec);
+  if (hipError_t rc = launch_vf_rows(loss, B, V, ic, theta, dvec, s); rc != hipSuccess) return rc;
   hipLaunchKernelGGL(vf_clear_kernel, dim3(ci->num_cus * 8), dim3(256), 0, s, H, V.ld, V.ld);   // (p = ld: all zero, no identity on the padding)
   hipError_t rc = hipMemsetAsync(wslots, 0, (size_t)V.n * VAR_BIG_BUILD_GROUPS * 8, s);
   if (rc != hipSuccess) return rc;

@@ -9,7 +9,7 @@ worker's shard (gdmix-trainer/src/gdmix/models/custom/fixed_effect_lr_lbfgs_mode
     theta_reg = theta if regularize_bias or no intercept, else theta[:-1] (:367-369)
 
 That is the random-effect objective of one "entity" holding the whole shard, without the 1/n and with an optional
-squared loss — two switches of the same device solver (gdmix_re_opts.sum_loss / .linear, include/gdmix_re.h): the
+squared loss — two switches of the same device solver (gdmix_re_opts.sum_loss / .loss, include/gdmix_re.h): the
 shard is packed as a one-entity batch and solved by the device-wide team kernel (csrc/re_solve_team.hpp), X
 streaming from HBM twice per evaluation (CSR for the logits, the CSC copy for the gradient). This module maps
 between the reference's coefficient layout (global feature index, intercept last) and the solver's (features

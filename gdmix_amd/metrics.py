@@ -80,25 +80,50 @@ def poisson_entities_to_host(res) -> dict:
     return h
 
 
-class PoissonEvaluator:
-    """The Poisson loss on one MI355X through the solver's context, with DeviceEvaluator's interface: `entities` per entity of a scored
-    batch, `add` ... `finish` over everything a stage scores."""
+# what a stage writes per evaluator (StageMetrics): the summary's keys next to the metric, and the per-entity records
+PER_ENTITY_SCHEMA = {"type": "record", "name": "EntityMetricAvro", "namespace": "gdmix_amd", "fields": [
+    {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "n_pos", "type": "long"},
+    {"name": "auc", "type": ["null", "double"]}, {"name": "mse", "type": "double"}]}
+PER_ENTITY_POISSON_SCHEMA = {"type": "record", "name": "EntityPoissonMetricAvro", "namespace": "gdmix_amd", "fields": [
+    {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "poisson_loss", "type": "double"}]}
+SUMMARY_KEYS = ("n", "n_pos", "n_neg", "n_nan", "two_u", "sse")
+POISSON_SUMMARY_KEYS = ("n", "n_nan", "pl")
+
+
+class _Evaluator:
+    """What the evaluators share: the checks of their inputs. Each declares OUTPUTS (name and dtype of `entities`' tensors, in the order
+    of its C struct OUT_STRUCT), SUMMARY_KEYS and ENTITY_SCHEMA (what a stage writes from `finish`, next to its metric, and per entity) and `to_host`."""
 
     def __init__(self, solver):
         self.solver = solver
         self.torch = solver.torch
         self.lib = solver.lib
-        self._state = self.torch.empty(_solver.EVAL_PL_STATE_BYTES, dtype=self.torch.uint8, device=solver.device)
-        self._acc = _solver._EvalPlAcc(self._state.data_ptr(), 0)
-        self.reset()
+
+    def _f32(self, x, what):
+        t = self.torch
+        if isinstance(x, np.ndarray):
+            x = t.from_numpy(np.ascontiguousarray(x, np.float32)).to(self.solver.device)
+        if not x.is_cuda or x.dtype != t.float32 or not x.is_contiguous():
+            raise _solver.GdmixReError(f"{what} must be a contiguous float32 array on the solver's device")
+        return x
+
+    def _pair(self, score, label):
+        """-> (score, label, N), checked"""
+        score, label = self._f32(score, "score"), self._f32(label, "label")
+        N = int(score.numel())
+        if label.numel() != N:
+            raise _solver.GdmixReError("score and label differ in length")
+        return score, label, N
 
     def set_small_max(self, small_max: int):
-        """Testing knob: entities of more than small_max samples are summed by a workgroup each (0: every entity). Default 64."""
+        """Testing knob: entities of more than small_max samples take the path of the large ones (the sort path; for the Poisson loss a
+        workgroup each). 0: every entity. Default 64."""
         with self.solver._ctx_lock:
             _solver._check(self.lib.gdmix_re_set_eval_small_max(self.solver._h, int(small_max)), "gdmix_re_set_eval_small_max")
 
-    def entities(self, packed_or_ent_row_ptr, score, label=None) -> dict:
-        """-> {"pl" float64, "n", "n_nan" int32}: device tensors, one entry per entity (n: the samples whose score is not NaN)."""
+    def _entities_args(self, packed_or_ent_row_ptr, score, label):
+        """`entities`' arguments, checked -> (ent_row_ptr, score, label, E, N, the zeroed output tensors, their C struct).
+        packed_or_ent_row_ptr: a PackedBatch (its labels are the default for `label`) or the [E+1] int64 sample offsets."""
         t, s = self.torch, self.solver
         if isinstance(packed_or_ent_row_ptr, _solver.PackedBatch):
             pb = packed_or_ent_row_ptr
@@ -113,15 +138,37 @@ class PoissonEvaluator:
             raise _solver.GdmixReError("entities: no labels")
         if not rp.is_cuda or rp.dtype != t.int64 or rp.numel() < 1:
             raise _solver.GdmixReError("ent_row_ptr must be int64 on the solver's device, one entry more than entities")
-        score, label = self._f32(score, "score"), self._f32(label, "label")
-        E, N = int(rp.numel()) - 1, int(score.numel())
-        if label.numel() != N:
-            raise _solver.GdmixReError("score and label differ in length")
+        score, label, N = self._pair(score, label)
+        E = int(rp.numel()) - 1
         if E > 0 and (int(rp[0]) != 0 or int(rp[-1]) != N):
             raise _solver.GdmixReError(f"ent_row_ptr runs from {int(rp[0])} to {int(rp[-1])}; the batch has {N} samples")
-        dev = s.device
-        res = dict(pl=t.zeros(E, dtype=t.float64, device=dev), n=t.zeros(E, dtype=t.int32, device=dev), n_nan=t.zeros(E, dtype=t.int32, device=dev))
-        c_out = _solver._EvalPlOut(*(res[k].data_ptr() if E else None for k in ("pl", "n", "n_nan")))
+        res = {k: t.zeros(E, dtype=getattr(t, dtype), device=s.device) for k, dtype in self.OUTPUTS}
+        return rp, score, label, E, N, res, self.OUT_STRUCT(*(res[k].data_ptr() if E else None for k, _ in self.OUTPUTS))
+
+    @property
+    def count(self) -> int:
+        return int(self._acc.count)
+
+
+class PoissonEvaluator(_Evaluator):
+    """The Poisson loss on one MI355X through the solver's context, with DeviceEvaluator's interface: `entities` per entity of a scored
+    batch, `add` ... `finish` over everything a stage scores."""
+    OUTPUTS = (("pl", "float64"), ("n", "int32"), ("n_nan", "int32"))
+    OUT_STRUCT = _solver._EvalPlOut
+    SUMMARY_KEYS = POISSON_SUMMARY_KEYS
+    ENTITY_SCHEMA = PER_ENTITY_POISSON_SCHEMA
+    to_host = staticmethod(poisson_entities_to_host)
+
+    def __init__(self, solver):
+        super().__init__(solver)
+        self._state = self.torch.empty(_solver.EVAL_PL_STATE_BYTES, dtype=self.torch.uint8, device=solver.device)
+        self._acc = _solver._EvalPlAcc(self._state.data_ptr(), 0)
+        self.reset()
+
+    def entities(self, packed_or_ent_row_ptr, score, label=None) -> dict:
+        """-> {"pl" float64, "n", "n_nan" int32}: device tensors, one entry per entity (n: the samples whose score is not NaN)."""
+        s = self.solver
+        rp, score, label, E, N, res, c_out = self._entities_args(packed_or_ent_row_ptr, score, label)
         with s._ctx_lock:
             _solver._check(self.lib.gdmix_re_eval_pl_entities(s._h, rp.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
                                                               C.byref(c_out), s._stream()), "gdmix_re_eval_pl_entities")
@@ -132,15 +179,8 @@ class PoissonEvaluator:
         with s._ctx_lock:
             _solver._check(self.lib.gdmix_re_eval_pl_acc_reset(s._h, C.byref(self._acc), s._stream()), "gdmix_re_eval_pl_acc_reset")
 
-    @property
-    def count(self) -> int:
-        return int(self._acc.count)
-
     def add(self, score, label):
-        score, label = self._f32(score, "score"), self._f32(label, "label")
-        N = int(score.numel())
-        if label.numel() != N:
-            raise _solver.GdmixReError("score and label differ in length")
+        score, label, N = self._pair(score, label)
         if N == 0:
             return
         s = self.solver
@@ -159,63 +199,30 @@ class PoissonEvaluator:
         return {POISSON_LOSS: float("nan") if n_nan > 0 or n == 0 else float(tot.pl) / n, "pl": float(tot.pl), "n": n + n_nan, "n_nan": n_nan}
 
 
-class DeviceEvaluator:
+class DeviceEvaluator(_Evaluator):
     """AUC / MSE on one MI355X through the solver's context: `entities` per entity of a scored batch, `add` ... `finish` over everything
     a stage scores (one accumulator per object; a solver may serve several)."""
+    OUTPUTS = (("two_u", "int64"), ("n_pos", "int32"), ("n_neg", "int32"), ("n_nan", "int32"), ("sse", "float64"), ("auc", "float64"))
+    OUT_STRUCT = _solver._EvalOut
+    SUMMARY_KEYS = SUMMARY_KEYS
+    ENTITY_SCHEMA = PER_ENTITY_SCHEMA
+    to_host = staticmethod(entities_to_host)
 
     def __init__(self, solver):
-        self.solver = solver
-        self.torch = solver.torch
-        self.lib = solver.lib
+        super().__init__(solver)
         self._keys = None       # device int64 tensor behind the accumulator's uint64 keys
         self._state = None      # the accumulator's device state
         self._acc = _solver._EvalAcc(None, 0, 0, None)
         self.reset()
-
-    # ---- helpers -------------------------------------------------------------------------------------------------------------------
-    def _f32(self, x, what):
-        t = self.torch
-        if isinstance(x, np.ndarray):
-            x = t.from_numpy(np.ascontiguousarray(x, np.float32)).to(self.solver.device)
-        if not x.is_cuda or x.dtype != t.float32 or not x.is_contiguous():
-            raise _solver.GdmixReError(f"{what} must be a contiguous float32 array on the solver's device")
-        return x
-
-    def set_small_max(self, small_max: int):
-        """Testing knob: entities of more than small_max samples take the sort path (0: every entity). Default 64."""
-        with self.solver._ctx_lock:
-            _solver._check(self.lib.gdmix_re_set_eval_small_max(self.solver._h, int(small_max)), "gdmix_re_set_eval_small_max")
 
     # ---- per entity ----------------------------------------------------------------------------------------------------------------
     def entities(self, packed_or_ent_row_ptr, score, label=None, workspace_bytes=None) -> dict:
         """-> {"two_u" int64, "n_pos", "n_neg", "n_nan" int32, "sse", "auc" float64}: device tensors, one entry per entity.
         packed_or_ent_row_ptr: a PackedBatch (its labels are the default for `label`) or the [E+1] int64 sample offsets."""
         t, s = self.torch, self.solver
-        if isinstance(packed_or_ent_row_ptr, _solver.PackedBatch):
-            pb = packed_or_ent_row_ptr
-            rp = pb._raw_dev["ent_row_ptr"]
-            if label is None:
-                label = pb._raw_dev["y"]
-        else:
-            rp = packed_or_ent_row_ptr
-            if isinstance(rp, np.ndarray):
-                rp = t.from_numpy(np.ascontiguousarray(rp, np.int64)).to(s.device)
-        if label is None:
-            raise _solver.GdmixReError("entities: no labels")
-        if not rp.is_cuda or rp.dtype != t.int64 or rp.numel() < 1:
-            raise _solver.GdmixReError("ent_row_ptr must be int64 on the solver's device, one entry more than entities")
-        score, label = self._f32(score, "score"), self._f32(label, "label")
-        E, N = int(rp.numel()) - 1, int(score.numel())
-        if label.numel() != N:
-            raise _solver.GdmixReError("score and label differ in length")
-        if E > 0 and (int(rp[0]) != 0 or int(rp[-1]) != N):
-            raise _solver.GdmixReError(f"ent_row_ptr runs from {int(rp[0])} to {int(rp[-1])}; the batch has {N} samples")
-        dev = s.device
-        res = dict(two_u=t.zeros(E, dtype=t.int64, device=dev), n_pos=t.zeros(E, dtype=t.int32, device=dev), n_neg=t.zeros(E, dtype=t.int32, device=dev),
-                   n_nan=t.zeros(E, dtype=t.int32, device=dev), sse=t.zeros(E, dtype=t.float64, device=dev), auc=t.zeros(E, dtype=t.float64, device=dev))
-        c_out = _solver._EvalOut(*(res[k].data_ptr() if E else None for k in ("two_u", "n_pos", "n_neg", "n_nan", "sse", "auc")))
+        rp, score, label, E, N, res, c_out = self._entities_args(packed_or_ent_row_ptr, score, label)
         nbytes = int(self.lib.gdmix_re_eval_workspace_bytes(E, N)) if workspace_bytes is None else int(workspace_bytes)
-        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=dev)
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=s.device)
         with s._ctx_lock:
             _solver._check(self.lib.gdmix_re_eval_entities(s._h, rp.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
                                                            C.byref(c_out), ws.data_ptr(), nbytes, s._stream()), "gdmix_re_eval_entities")
@@ -230,10 +237,6 @@ class DeviceEvaluator:
         with s._ctx_lock:
             _solver._check(self.lib.gdmix_re_eval_acc_reset(s._h, C.byref(self._acc), s._stream()), "gdmix_re_eval_acc_reset")
 
-    @property
-    def count(self) -> int:
-        return int(self._acc.count)
-
     def reserve(self, samples: int):
         """Room for this many samples in the key buffer (8 bytes each). `add` grows it by itself; a stage that knows its size saves
         the copies."""
@@ -246,10 +249,7 @@ class DeviceEvaluator:
             self._acc.keys, self._acc.capacity = new.data_ptr(), int(new.numel())
 
     def add(self, score, label):
-        score, label = self._f32(score, "score"), self._f32(label, "label")
-        N = int(score.numel())
-        if label.numel() != N:
-            raise _solver.GdmixReError("score and label differ in length")
+        score, label, N = self._pair(score, label)
         if N == 0:
             return
         if self._keys is None or self._keys.numel() < self.count + N:
@@ -277,19 +277,12 @@ class DeviceEvaluator:
                 "n": int(tot.n), "n_pos": n_pos, "n_neg": n_neg, "n_nan": n_nan, "two_u": int(tot.two_u), "sse": float(tot.sse)}
 
 
-PoissonEvaluator._f32 = DeviceEvaluator._f32      # the two evaluators check their inputs alike
+EVALUATOR_OF_METRIC = {AUC: DeviceEvaluator, MSE: DeviceEvaluator, POISSON_LOSS: PoissonEvaluator}
 
 
 # ---- a stage that reports its metric while it scores (REParams.metric_output_dir) ----------------------------------------------------
 EVAL_SUMMARY_JSON = "evalSummary.json"
 PER_ENTITY_DIR = "perEntity"
-PER_ENTITY_SCHEMA = {"type": "record", "name": "EntityMetricAvro", "namespace": "gdmix_amd", "fields": [
-    {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "n_pos", "type": "long"},
-    {"name": "auc", "type": ["null", "double"]}, {"name": "mse", "type": "double"}]}
-PER_ENTITY_POISSON_SCHEMA = {"type": "record", "name": "EntityPoissonMetricAvro", "namespace": "gdmix_amd", "fields": [
-    {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "poisson_loss", "type": "double"}]}
-SUMMARY_KEYS = ("n", "n_pos", "n_neg", "n_nan", "two_u", "sse")
-POISSON_SUMMARY_KEYS = ("n", "n_nan", "pl")
 TRAINING, VALIDATION = "training", "validation"
 
 logger = logging.getLogger(__name__)
@@ -312,12 +305,13 @@ class StageMetrics:
 
     def __init__(self, solver, out_dir, metric_name):
         self.solver, self.out_dir, self.metric = solver, out_dir, metric_name
+        self.evaluator = EVALUATOR_OF_METRIC[metric_name]      # the class: it says what is summed, kept and written
         self.ev = {}
         self._warned = False
 
     def _evaluator(self, which):
         if which not in self.ev:
-            self.ev[which] = PoissonEvaluator(self.solver) if self.metric == POISSON_LOSS else DeviceEvaluator(self.solver)
+            self.ev[which] = self.evaluator(self.solver)
         return self.ev[which]
 
     def no_labels(self, what):
@@ -329,7 +323,7 @@ class StageMetrics:
         """The scores of a packed batch (device) -> added to `which`'s accumulator; -> per-entity results on the host."""
         ev = self._evaluator(which)
         ev.add(logit, packed._raw_dev["y"])
-        return (poisson_entities_to_host if self.metric == POISSON_LOSS else entities_to_host)(ev.entities(packed, logit))
+        return ev.to_host(ev.entities(packed, logit))
 
     def write_entities(self, which, output_file, entity_ids, host, e0=0, e1=None):
         from .io import avro
@@ -339,15 +333,12 @@ class StageMetrics:
         stem = os.path.basename(output_file)
         stem = stem[len("part-"):] if stem.startswith("part-") else stem
         name = f"part-{which}-{os.path.basename(os.path.dirname(os.path.abspath(output_file)))}-{stem}"
-        if self.metric == POISSON_LOSS:
-            n, pl = host["n"][e0:e1], host[POISSON_LOSS][e0:e1]
-            recs = [{"entityId": str(entity_ids[i]), "n": int(n[i]), POISSON_LOSS: float(pl[i])} for i in range(e1 - e0)]
-            avro.write_file(os.path.join(d, name), PER_ENTITY_POISSON_SCHEMA, recs)
-            return
-        n, n_pos, auc, mse = host["n"][e0:e1], host["n_pos"][e0:e1], host["auc"][e0:e1], host["mse"][e0:e1]
-        recs = [{"entityId": str(entity_ids[i]), "n": int(n[i]), "n_pos": int(n_pos[i]), "auc": None if auc[i] != auc[i] else float(auc[i]),
-                 "mse": float(mse[i])} for i in range(e1 - e0)]
-        avro.write_file(os.path.join(d, name), PER_ENTITY_SCHEMA, recs)
+        # a record per entity from the evaluator's schema: a long, a double, or a double that is null when it is NaN
+        as_type = {"long": int, "double": float}
+        nullable = lambda x: None if x != x else float(x)
+        fields = [(f["name"], as_type[f["type"]] if isinstance(f["type"], str) else nullable) for f in self.evaluator.ENTITY_SCHEMA["fields"][1:]]
+        recs = [dict({"entityId": str(entity_ids[i])}, **{k: conv(host[k][e0 + i]) for k, conv in fields}) for i in range(e1 - e0)]
+        avro.write_file(os.path.join(d, name), self.evaluator.ENTITY_SCHEMA, recs)
 
     def write_summary(self):
         if not self.ev:
@@ -355,7 +346,7 @@ class StageMetrics:
         blocks = {}
         for which, ev in self.ev.items():
             r = ev.finish()
-            blocks[which] = {k: _json_number(r[k]) for k in (self.metric,) + (POISSON_SUMMARY_KEYS if self.metric == POISSON_LOSS else SUMMARY_KEYS)}
+            blocks[which] = {k: _json_number(r[k]) for k in (self.metric,) + self.evaluator.SUMMARY_KEYS}
         top = VALIDATION if VALIDATION in blocks else TRAINING
         out = dict(blocks[top], data=top, **blocks)
         os.makedirs(self.out_dir, exist_ok=True)

@@ -58,7 +58,7 @@ class _Opts(C.Structure):
     _fields_ = [("l2", C.c_double), ("regularize_bias", C.c_int32), ("has_intercept", C.c_int32),
                 ("m", C.c_int32), ("max_iter", C.c_int32), ("maxfun", C.c_int32), ("maxls", C.c_int32),
                 ("ftol", C.c_double), ("pgtol", C.c_double), ("variance_mode", C.c_int32),
-                ("threshold", C.c_double), ("sum_loss", C.c_int32), ("linear", C.c_int32)]
+                ("threshold", C.c_double), ("sum_loss", C.c_int32), ("loss", C.c_int32)]
 
 
 class _Result(C.Structure):

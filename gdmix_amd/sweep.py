@@ -27,6 +27,7 @@ import os
 import numpy as np
 
 from . import constants
+from .metrics import SUMMARY_KEYS
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.INFO)
@@ -34,7 +35,6 @@ logger.setLevel(logging.INFO)
 SWEEP_DIR = "sweep"
 EVALS_JSON = "evals.json"
 BEST_MODEL_INDEX, MODEL_PARAMS = "best model index", "model params"      # BestModelSelector.scala's keys
-SUMMARY_KEYS = ("n", "n_pos", "n_neg", "n_nan", "two_u", "sse")
 
 
 class SweepError(ValueError):
@@ -236,7 +236,7 @@ def run(driver, schema_params):
     mp = model.model_params
     weights = mp.l2_grid()
     validate(model, driver.execution_context)
-    metric = metrics.MSE if model.linear else metrics.AUC
+    metric = metrics.metric_of_loss(model.loss)
     logger.info(f"sweeping l2_reg_weight over {list(weights)} by validation {metric}; --l2_reg_weight={mp.l2_reg_weight} is ignored")
     tensor_metadata = DatasetMetadata(read_json_file(model.metadata_file))
     num_features = 1 if model.feature_bag_name is None else tensor_metadata.get_feature_shape(model.feature_bag_name)[0]

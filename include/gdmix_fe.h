@@ -38,9 +38,9 @@ typedef struct gdmix_fe_problem gdmix_fe_problem;
 
 /* shard: a packed batch with E == 1 (gdmix_re_pack; has_intercept of the pack must equal opts->has_intercept).
  * num_features: size of the global feature space D; coefficients are [D + has_intercept], intercept last.
- * opts: l2, regularize_bias, has_intercept, m (<= 10), max_iter, maxfun, maxls, ftol, pgtol, linear are used.
+ * opts: l2, regularize_bias, has_intercept, m (<= 10), max_iter, maxfun, maxls, ftol, pgtol, loss are used.
  * theta0: device pointer [D + has_intercept] or NULL (zeros).
- * ---- poisson (ABI 19) ---- opts->linear is the loss code of include/gdmix_re.h (GDMIX_RE_LOSS_*; any other value is refused, also by
+ * ---- poisson (ABI 19) ---- opts->loss is the loss code of include/gdmix_re.h (GDMIX_RE_LOSS_*; any other value is refused, also by
  * gdmix_fe_restart, whose code must be the creation's). GDMIX_RE_LOSS_POISSON: the objective of gdmix_re.h's section "poisson" summed, not
  * divided by n: f = sum_i w_i (exp(z_i) - y_i z_i) + (l2/2) |theta_reg|^2, g = X~' (w (exp(z) - y)) + l2 theta_reg, labels y >= 0
  * real-valued; gdmix_fe_hessian_diag leaves sum_i X~_ij^2 w_i exp(z_i). The value is added up error-free as for the other losses, exp
@@ -126,7 +126,7 @@ GDMIX_API int gdmix_fe_score(gdmix_re_ctx* ctx, int64_t n, const int64_t* row_nn
  * the state the stop flag — which made every kernel of the stopped problem a no-op: a restart may come right behind a gdmix_fe_solve
  * that left `lookahead` no-op evaluations queued after the stop. Kept as they are: both copies of the non-zeros, their unit tables, the
  * frequent-column tables and the list of row blocks with several units — everything gdmix_fe_create sorted, split and synchronised for.
- * opts->has_intercept, opts->linear and opts->m must equal the creation's (the pool is sized and the copies are read by them):
+ * opts->has_intercept, opts->loss and opts->m must equal the creation's (the pool is sized and the copies are read by them):
  * GDMIX_RE_EINVAL otherwise. Stream-ordered, no synchronisation. The definition of the call: a solve after a restart gives the same
  * bits as gdmix_fe_create with those options and that start point followed by the same solve. */
 GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, const double* theta0, void* stream);
@@ -139,7 +139,7 @@ GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, c
  * Definition. theta = [w (D), b], intercept last; coefficient j has a prior mean mu_j and a prior variance v_j, s_j = sqrt(v_j); R = the
  * regularised coefficients: every j < D, and the intercept iff regularize_bias:
  *     F(theta) = sum_i w_i l(y_i, x_i . w + b + offset_i) + (l2/2) sum_{j in R} (theta_j - mu_j)^2 / v_j
- * not divided by n (the fixed effect's convention), l the logistic or the squared loss (opts->linear) as without a prior.
+ * not divided by n (the fixed effect's convention), l the logistic or the squared loss (opts->loss) as without a prior.
  * The prior is global. It applies to every coefficient of the model, whether or not this worker's shard holds a non-zero in that
  * column: a coefficient no worker has data for stays at its prior mean, exactly.
  * Defaults (the caller's, gdmix_amd/fe_model.py; those of the random effect). mu_j = 0 where the prior file has no mean for j — a

@@ -164,9 +164,10 @@ typedef struct {
    * (fixed_effect_lr_lbfgs_model.py:309-392): a batch with one "entity" = one worker's shard. Defaults 0.
    * sum_loss != 0 routes every entity to the device-wide team kernel, needs m <= 10 and refuses a variance mode. */
   int32_t sum_loss;         /* 1: f = sum_i w_i l_i + (l2/2)|theta_reg|^2, not divided by n (:363-381)            */
-  int32_t linear;           /* the loss code, GDMIX_RE_LOSS_* below (ABI 19; until then a flag: 0 logistic, non-zero squared). 1: l_i = (y_i - z_i)^2
-                             * (linear regression, :356-358), 2: l_i = exp(z_i) - y_i z_i (section "poisson" below). Any other value is refused. */
-  /* linear != 0 with sum_loss == 0 is the random effect's linear regression (--model_type=linear_regression; the reference has none: this
+  int32_t loss;             /* the loss code, GDMIX_RE_LOSS_* below (ABI 19; until then a flag: 0 logistic, non-zero squared). 1: l_i = (y_i - z_i)^2
+                             * (linear regression, :356-358), 2: l_i = exp(z_i) - y_i z_i (section "poisson" below). Any other value is refused.
+                             * (The field was called `linear` until the third loss; position and type are unchanged.) */
+  /* loss == GDMIX_RE_LOSS_SQUARED with sum_loss == 0 is the random effect's linear regression (--model_type=linear_regression; the reference has none: this
    * is its per-entity objective with its fixed-effect loss put in). For one entity of n samples, theta in local index space, intercept
    * first, labels y real-valued:
    *     z_i = x_i . theta + offset_i
@@ -177,11 +178,11 @@ typedef struct {
    * instantiation of its own for this loss. Variance is _compute_variance (binary_logistic_regression.py:144-189) with the curvature
    * weight D_i = 2 w_i in place of rho_i (1 - rho_i) w_i — it does not depend on theta:
    *     SIMPLE  1 / (sum_i D_i X~_ij^2 + l2 [- l2 for an unregularised intercept] + 1e-12)
-   *     FULL    diag((X~' D X~ + (l2 + 1e-12) I [- l2 e0 e0'])^-1)      (gdmix_re_variance_full takes the loss from opts->linear too)
+   *     FULL    diag((X~' D X~ + (l2 + 1e-12) I [- l2 e0 e0'])^-1)      (gdmix_re_variance_full takes the loss from opts->loss too)
    * neither divided by n, as in the reference. gdmix_re_score is the same for every loss: x . theta + offset.
    *
    * ---- poisson (ABI 19) ----
-   * linear == GDMIX_RE_LOSS_POISSON is Poisson regression (--model_type=poisson_regression; Photon-ML's PoissonLossFunction). For one
+   * loss == GDMIX_RE_LOSS_POISSON is Poisson regression (--model_type=poisson_regression; Photon-ML's PoissonLossFunction). For one
    * entity of n samples, theta in local index space, the intercept first, labels y >= 0 real-valued:
    *     z_i = x_i . theta + offset_i
    *     f   = (1/n) ( sum_i w_i (exp(z_i) - y_i z_i) + (l2/2) |theta_reg|^2 )
@@ -393,7 +394,7 @@ GDMIX_API const char* gdmix_re_class_kernel_name(int c);
  *               AUC = twoU / (2 n_pos n_neg), undefined (NaN) when n_pos == 0 or n_neg == 0: ties at half weight, what Spark's
  *               trapezoid over the distinct thresholds gives.
  *   SSE         sum of (label - score)^2 in fp64, both widened from fp32 first; MSE = SSE / n, n = n_pos + n_neg. Added in trees of a
- *               fixed shape (at most 2 048 terms in a row per lane; csrc/re_evaluate.hip states the shape): relative error below
+ *               fixed shape (at most 2 048 terms in a row per lane; csrc/re_eval_sum.hpp states the shape): relative error below
  *               2.5e-13, the same bits from run to run.
  *   NaN         a NaN score is counted (n_nan) and left out of every sum and count; gdmix_amd/metrics.py reports AUC and MSE as NaN
  *               when n_nan > 0. Infinities order as usual.
@@ -456,8 +457,7 @@ GDMIX_API int gdmix_re_eval_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_ac
  * entry points above are not involved.
  *   PL          sum_i (exp(s_i) - y_i s_i) in fp64, the fp32 score s and label y widened first (log(y!) dropped, as in training); the mean
  *               poisson_loss = PL / n is the caller's division. Unweighted, as the other metrics are.
- *   trees       added in trees of a fixed shape, the shapes SSE is added in (at most 2 048 terms in a row per lane, 64 such sums in a row,
- *               64 of those, the 256-lane tree, for the accumulator the workgroup sums in 16-term runs and one more tree): the same bits from
+ *   trees       added in the trees SSE is added in: both units take the shape from csrc/re_eval_sum.hpp, which states it. The same bits from
  *               run to run. The accumulator adds the sums of its batches to a (hi, lo) pair without losing the additions' rounding errors: the
  *               total is the rounded exact sum of the batches' sums, so it does not depend on the order the batches came in (two orders could
  *               differ only if that exact sum lay within 2^-100 of the midpoint of two doubles). The terms have either sign, so the bound is
@@ -539,7 +539,7 @@ GDMIX_API int gdmix_re_score_models(gdmix_re_ctx* ctx, const gdmix_re_packed* ev
  * Definition. One entity, theta in local index space, intercept first; coefficient j has a prior mean mu_j and a prior variance v_j,
  * s_j = sqrt(v_j):
  *     F(theta) = (1/n) ( sum_i w_i l(z_i, y_i) + (l2/2) sum_{j regularised} (theta_j - mu_j)^2 / v_j ),   z = X~ theta + offset
- * l the logistic or the squared loss (opts->linear) as without a prior.
+ * l the logistic or the squared loss (opts->loss) as without a prior.
  * Defaults. A coefficient has no prior when the entity is new, when the feature is new for the entity, when the coefficient was
  * thresholded out of the model file, when the record has no variances, or when its variance is missing, not finite or <= 0. Such a
  * coefficient gets mu_j = 0 where the mean is missing and v_j = 1 where the variance is missing: an entity without a prior has exactly

@@ -38,6 +38,25 @@ def test_default_opts_and_struct_layout(lib):
         assert getattr(c, f) == getattr(o, f), f
 
 
+def test_loss_codes_at_the_entry_points(lib):
+    """gdmix_re_opts.loss: 0, 1 and 2 are accepted, 3 and -1 refused, by gdmix_re_solve and gdmix_re_variance_full before anything is
+    launched. An empty batch (E = 0) returns right behind the argument checks, so no device and no real context is needed: the context
+    here is a zeroed buffer that is never read. (With a device: test_gpu_re_poisson.py, test_a_loss_code_outside_the_three_is_refused.)"""
+    ctx = C.create_string_buffer(64)
+    packed, res = solver._Packed(), solver._Result()
+    dummy = C.create_string_buffer(8)      # stands for theta and variance: non-NULL, never read
+    o = solver.SolverOptions().to_c()
+    assert solver._Opts._fields_[-1] == ("loss", C.c_int32) and solver._Opts.loss.offset == solver._Opts.sum_loss.offset + 4
+    for code in (0, 1, 2, 3, -1):
+        o.loss = code
+        rcs = (lib.gdmix_re_solve(C.addressof(ctx), C.byref(packed), C.byref(o), None, C.byref(res), None),
+               lib.gdmix_re_variance_full(C.addressof(ctx), C.byref(packed), C.byref(o), C.addressof(dummy), C.addressof(dummy), None))
+        if code in (0, 1, 2):
+            assert rcs == (0, 0), (code, lib.gdmix_re_last_error())
+        else:
+            assert rcs == (-1, -1) and f"opts->loss = {code} is no loss code".encode() in lib.gdmix_re_last_error(), (code, rcs)
+
+
 def test_workspace_size_is_monotone(lib):
     a = lib.gdmix_re_pack_workspace_bytes(10, 100, 1000)
     b = lib.gdmix_re_pack_workspace_bytes(20, 200, 2000)

@@ -1,4 +1,4 @@
-"""Fixed-effect objective (gdmix_re_opts.sum_loss / .linear): the oracle against fixtures produced by the reference's own
+"""Fixed-effect objective (gdmix_re_opts.sum_loss / .loss): the oracle against fixtures produced by the reference's own
 numpy + scipy ground truth (tests/golden/generate_fe_fixtures.py), and the device path against both."""
 import glob
 import os

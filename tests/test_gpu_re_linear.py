@@ -115,8 +115,10 @@ def test_linear_two_loop_kernels_and_full_variance(device_solver, m):
 
 
 def test_linear_simple_variance_on_team_classes(device_solver):
-    """The team kernels hold both losses in one instantiation and get no variance pointer for linear: re_variance_simple_lin_kernel
-    follows them. Workgroup class, the three team tiers and the device-wide class, with and without an intercept."""
+    """The team kernels hold the losses in one instantiation and get no variance pointer for linear: re_variance_simple_kernel<LOSS_SQUARED>
+    follows them, D in the head of a workgroup's scratch slot. Workgroup class, the three team tiers and the device-wide class, with and
+    without an intercept; then the workgroup class once more with fewer slots than it has entities, so that a workgroup writes D for a
+    second entity of another size into the slot it has just used."""
     for routing, b0 in ((dict(lds_limit=0, tall_min_n=0), BATCHES["ragged"]()), (dict(team_nnz=64, tall_min_n=0), BATCHES["zipf"]()),
                         (dict(giant_nnz=1, tall_min_n=0), BATCHES["tall"]())):
         for ic in (True, False):
@@ -131,6 +133,37 @@ def test_linear_simple_variance_on_team_classes(device_solver):
             finally:
                 H.reset_routing(device_solver)
             np.testing.assert_allclose(res["variance"], H.variance_numpy(b, pk, kw, 1), rtol=1e-7)
+
+    # the ragged batch again through the C ABI with a scratch buffer of 64 slots (gdmix_re_solve works with the slots it is given)
+    import ctypes as C
+    from gdmix_amd.solver import SolveResult, _Result
+    lib, t = device_solver.lib, device_solver.torch
+    kw = dict(l2=0.5, regularize_bias=False, has_intercept=True, m=10, max_iter=5, ftol=1e-12, variance_mode=1)
+    b = synthetic.with_real_labels(BATCHES["ragged"](), seed=3)
+    pk = oracle.pack(b.ent_row_ptr, b.row_nnz_ptr, b.col_global)
+    packed = device_solver.pack(b)
+    o = SolverOptions(linear=True, **kw).to_c()
+    slots = 64
+    need = lib.gdmix_re_solve_scratch_bytes(C.byref(packed.c), C.byref(o))
+    slot_bytes = need // min(b.E, 1024)      # (the library sizes min(E, 1024) slots)
+    scratch = t.empty(slots * slot_bytes, dtype=t.uint8, device=device_solver.device)
+    assert packed.c.scratch_bytes < scratch.numel() < need      # neither buffer holds every slot; the larger one, this one, is cut into slots
+    out = device_solver.alloc_result(packed, variance=True)
+    c_res = _Result(*(out[k].data_ptr() for k in ("theta", "theta_thr", "variance", "fval", "gnorm", "nit", "nfev", "status")))
+    H.set_routing(device_solver, lds_limit=0, tall_min_n=0)
+    try:
+        assert lib.gdmix_re_set_scratch(device_solver._h, scratch.data_ptr(), scratch.numel()) == 0
+        rc = lib.gdmix_re_solve(device_solver._h, C.byref(packed.c), C.byref(o), None, C.byref(c_res), device_solver._stream())
+        assert rc == 0, lib.gdmix_re_last_error()
+        res = SolveResult(out, packed.E, packed.P).to_host()
+    finally:
+        mine = device_solver._scratch
+        lib.gdmix_re_set_scratch(device_solver._h, None if mine is None else mine.data_ptr(), 0 if mine is None else mine.numel())
+        H.reset_routing(device_solver)
+    in_workgroup_class = dict(device_solver.class_counts(packed))["re_solve_team_kernel workgroup"]
+    print(f"workgroup class: {in_workgroup_class} entities on {slots} scratch slots")
+    assert in_workgroup_class > slots and len(np.unique(np.diff(b.ent_row_ptr))) > 1
+    np.testing.assert_allclose(res["variance"], H.variance_numpy(b, pk, kw, 1), rtol=1e-7)
 
 
 def test_linear_c2_batch_lands_in_the_logistic_classes(device_solver):

@@ -82,7 +82,7 @@ def test_poisson_two_loop_kernels_and_full_variance(device_solver, m):
 
 
 def test_poisson_simple_variance_on_team_classes(device_solver):
-    """The team kernels hold the losses in one instantiation and get no variance pointer for Poisson: re_variance_simple_poi_kernel follows
+    """The team kernels hold the losses in one instantiation and get no variance pointer for Poisson: re_variance_simple_kernel<LOSS_POISSON> follows
     them with D_i = w_i exp(z_i) at the returned theta. Workgroup class, the three team tiers and the device-wide class, with and without
     an intercept."""
     for routing, name in ((dict(lds_limit=0, tall_min_n=0), "ragged"), (dict(team_nnz=64, tall_min_n=0), "zipf"), (dict(giant_nnz=1, tall_min_n=0), "tall")):
@@ -138,17 +138,23 @@ def test_poisson_c2_batch_lands_in_the_logistic_classes(device_solver):
 
 
 def test_a_loss_code_outside_the_three_is_refused(device_solver):
-    """gdmix_re_opts.linear is a loss code since ABI 19: 0, 1, 2 and nothing else (it used to be a flag: every non-zero value meant squared)."""
+    """gdmix_re_opts.loss is a loss code since ABI 19: 0, 1, 2 and nothing else (it used to be a flag: every non-zero value meant squared).
+    The three codes reach their kernels through the launchers' one dispatch; 3 and -1 are refused at the entry point."""
     import ctypes as C
     b, _ = _batch("tall", 0)
     packed = device_solver.pack(b)
     o = SolverOptions().to_c()
-    o.linear = 3
     t = device_solver.torch
     theta = t.zeros(int(packed.P), dtype=t.float64, device=device_solver.device)
     var = t.zeros_like(theta)
-    rc = device_solver.lib.gdmix_re_variance_full(device_solver._h, C.byref(packed.c), C.byref(o), theta.data_ptr(), var.data_ptr(), None)
-    assert rc != 0 and b"no loss code" in device_solver.lib.gdmix_re_last_error()
+    for code in (0, 1, 2, 3, -1):
+        o.loss = code
+        rc = device_solver.lib.gdmix_re_variance_full(device_solver._h, C.byref(packed.c), C.byref(o), theta.data_ptr(), var.data_ptr(), None)
+        if code in (0, 1, 2):
+            assert rc == 0, (code, device_solver.lib.gdmix_re_last_error())
+        else:
+            assert rc != 0 and b"no loss code" in device_solver.lib.gdmix_re_last_error(), code
+    t.cuda.synchronize(device_solver.device)
 
 
 # ---- the product path --------------------------------------------------------------------------------------------------------------

@@ -40,7 +40,7 @@ class ScipySolver(OracleSolverDouble):
 
     def solve(self, packed, opts, theta0=None, out=None):
         b = packed.batch
-        type(self).seen.append(("solve", opts.to_c().linear, bool(opts.sum_loss), bool(b.binary_labels), b.to_wire()["y_width"], np.array(b.y, copy=True)))
+        type(self).seen.append(("solve", opts.to_c().loss, bool(opts.sum_loss), bool(b.binary_labels), b.to_wire()["y_width"], np.array(b.y, copy=True)))
         assert opts.loss_name() == "poisson"
         cp = packed.coef_ptr_host()
         kw = dict(l2=opts.l2, regularize_bias=opts.regularize_bias, has_intercept=opts.has_intercept, m=opts.m, max_iter=opts.max_iter, ftol=opts.ftol)
@@ -71,10 +71,10 @@ def test_params_and_constants_accept_poisson_regression():
 
 def test_solver_options_loss_code():
     assert LOSS_CODES == {"logistic": 0, "squared": 1, "poisson": 2}
-    assert SolverOptions().to_c().linear == 0
-    assert SolverOptions(linear=True).to_c().linear == 1 and SolverOptions(linear=True).loss_name() == "squared"      # linear=True still means squared
-    assert SolverOptions(loss="squared").to_c().linear == 1 and SolverOptions(loss="logistic").to_c().linear == 0
-    assert SolverOptions(loss="poisson").to_c().linear == 2
+    assert SolverOptions().to_c().loss == 0
+    assert SolverOptions(linear=True).to_c().loss == 1 and SolverOptions(linear=True).loss_name() == "squared"      # linear=True still means squared
+    assert SolverOptions(loss="squared").to_c().loss == 1 and SolverOptions(loss="logistic").to_c().loss == 0
+    assert SolverOptions(loss="poisson").to_c().loss == 2
     with pytest.raises(ValueError, match="not both"):
         SolverOptions(linear=True, loss="poisson").to_c()
     with pytest.raises(ValueError, match="must be one of"):
@@ -163,7 +163,7 @@ def test_an_unknown_model_type_is_still_refused(tmp_path, stand_in):
     from gdmix_amd import chain, fixed_effect
     with pytest.raises(ValueError, match="unknown model type"):
         fixed_effect.fit_options(True, 1.0, True, "detext", 10, 10, 1e-12)
-    assert fixed_effect.fit_options(True, 1.0, True, "poisson_regression", 10, 10, 1e-12).to_c().linear == 2
+    assert fixed_effect.fit_options(True, 1.0, True, "poisson_regression", 10, 10, 1e-12).to_c().loss == 2
     assert fixed_effect.fit_options(True, 1.0, True, "linear_regression", 10, 10, 1e-12).linear is True
     with pytest.raises(ValueError, match="the chain runs"):
         chain.run_chain(str(tmp_path / "c"), {}, model_type="detext")
