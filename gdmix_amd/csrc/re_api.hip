@@ -400,6 +400,8 @@ GDMIX_API int gdmix_re_create(int hip_device, gdmix_re_ctx** out) {
   if (const char* e = getenv("GDMIX_RE_TALL_TEAM")) { if (atoi(e) == 0) c->impl.tall_team_n = 0; }   // A/B switch
   if (const char* e = getenv("GDMIX_RE_TALL_TEAM_LIMIT")) { if (atoi(e) > 0 && atoi(e) <= TALL_TEAM_MAX) c->impl.tall_team_limit = atoi(e); }   // exploration knob
   c->impl.spread = spread_default();
+  c->impl.narrow = 1;
+  if (const char* e = getenv("GDMIX_RE_NARROW")) c->impl.narrow = atoi(e) != 0 ? 1 : 0;   // A/B switch (gdmix_re_set_narrow)
   c->impl.grid_sync = nullptr;
   c->impl.big_tmp = nullptr;
   c->impl.big_tmp_bytes = 0;
@@ -576,6 +578,12 @@ GDMIX_API int gdmix_re_set_spread(gdmix_re_ctx* ctx, int queues) {
   return GDMIX_RE_OK;
 }
 
+GDMIX_API int gdmix_re_set_narrow(gdmix_re_ctx* ctx, int on) {
+  if (!ctx) { set_error("ctx is NULL"); return GDMIX_RE_EINVAL; }
+  ctx->impl.narrow = on ? 1 : 0;
+  return GDMIX_RE_OK;
+}
+
 GDMIX_API int gdmix_re_set_tall_team_n(gdmix_re_ctx* ctx, int team_n) {
   if (!ctx) { set_error("bad argument"); return GDMIX_RE_EINVAL; }
   ctx->impl.tall_team_n = ctx->impl.num_cus < 8 * TALL_TEAM_C ? 0 : team_n;   // (a device too small for a round of teams never gets the class)
@@ -712,8 +720,13 @@ hipError_t launch_class(const gdmix_ctx_impl* ci, const gdmix_re_packed* b, cons
     case KIND_TALL_L: case KIND_TALL_S: case KIND_TALL_M: case KIND_TALL:
       return launch_solve_tall(d.tall_variant, B, O, P, theta0, L.begin, L.count, ci->num_cus, b->Z, GridSyncLayout::tall_tail(ci, d.tall_variant),
                                GridSyncLayout::tall_ticket(ci, d.tall_variant), d.kind == KIND_TALL_S ? lean_merged : 0, s);
-    default:   // the group kinds
-      return d.lanes > 0 ? launch_solve_quad(d.lanes, d.epl, B, O, P, theta0, L.begin, L.count, d.ncap, d.zcap, s) : hipErrorInvalidValue;
+    default: {   // the group kinds
+      if (d.lanes <= 0) return hipErrorInvalidValue;
+      // the narrow front part of the class's segment (re_order_kernel), then the rest with the class's own kernel: one stream, one event pair
+      const int nn = (L.c == NARROW_HOST_CLASS && L.narrow > 0) ? (L.narrow < L.count ? L.narrow : L.count) : 0;
+      if (hipError_t rc = launch_solve_quad(NARROW_LANES, NARROW_EPL, B, O, P, theta0, L.begin, nn, NARROW_NCAP, NARROW_ZCAP, s); rc != hipSuccess) return rc;
+      return launch_solve_quad(d.lanes, d.epl, B, O, P, theta0, L.begin + nn, L.count - nn, d.ncap, d.zcap, s);
+    }
   }
 }
 

@@ -164,6 +164,19 @@ constexpr bool class_table_consistent() {
 static_assert(class_table_consistent(), "group_lanes / group_epl and the class constants describe kClasses");
 static_assert(GIANT_CLASS == GDMIX_RE_NUM_CLASSES - 1 && BLOCK_CLASS - TALL_T_CLASS == TALL_VARIANTS, "the tall classes, the block class, three tiers and the giant class end the table");
 static_assert(TALL_L_CLASS + 1 == TALL_S_CLASS, "a merged lean class sits right in front of the one-wavefront class in `order`");
+// The NARROW part of the <32,3> n<=32 nnz<=128 class: its entities of at most 80 coefficients, 24 samples and 96 non-zeros (three quarters
+// of the class in a C2 partition, whose mean of 16 samples sits right at the 64-coefficient edge of <16,4>) are solved four to a wavefront
+// by re_solve_grp_kernel<16,5,24,96> instead of two to a wavefront. Not a class of its own (GDMIX_RE_NUM_CLASSES, the classes' names and
+// counts stay): re_classify_kernel marks them in cls, re_order_kernel puts them at the front of the class's segment of `order` and counts
+// them (ClassCounts::narrow_count), and the class's launch is two kernels on its stream. The caps keep eight wavefronts per CU in LDS
+// (4 x 4 712 B per wavefront; 32 samples / 128 non-zeros would be 173 KB). Narrow or not depends on (p, n, nnz) alone, never on the batch.
+constexpr int NARROW_HOST_CLASS = 9;
+static_assert(kClasses[NARROW_HOST_CLASS].kind == KIND_PAIR3 && kClasses[NARROW_HOST_CLASS].ncap == 32 && kClasses[NARROW_HOST_CLASS].zcap == 128 &&
+              class_of_kind(KIND_PAIR3) == NARROW_HOST_CLASS, "the narrow kernel takes its entities from <32,3> n<=32 nnz<=128");
+constexpr int NARROW_LANES = 16, NARROW_EPL = 5, NARROW_NCAP = 24, NARROW_ZCAP = 96;
+constexpr int NARROW_FLAG = 0x100;   // in cls between re_classify_kernel and re_order_kernel only
+static_assert(NARROW_FLAG > GDMIX_RE_NUM_CLASSES, "the mark is no class index");
+__host__ __device__ constexpr bool narrow_fits(int p, int n, int z) { return p <= NARROW_LANES * NARROW_EPL && n <= NARROW_NCAP && z <= NARROW_ZCAP; }
 constexpr int BLOCK_NW = 4;   // wavefronts per workgroup of the block kernel
 #ifndef GDMIX_TEAM_BLOCK_NW
 #define GDMIX_TEAM_BLOCK_NW 8
@@ -185,6 +198,7 @@ struct ClassTable {
   int tall_team_n;        // > 0: tall entities of at least this many samples may get a team of workgroups (TALL_T_CLASS); 0 = never
   int tall_team_limit;    // > 0: the class takes the entities above the lowest of tall_team_n x {1, 2, 4} that keeps it within this many
                           // entities (class_base_kernel decides, re_order_kernel moves them); 0 = everything from tall_team_n on
+  int narrow;             // != 0: the narrow entities of class NARROW_HOST_CLASS are marked for re_solve_grp_kernel<16,5,24,96>
   int tall_mid_n;         // (round 6) > 0: one-wavefront tall entities of at least this many samples go to the mid class whatever the batch
                           // holds (tests); 0: no mid class; < 0: chosen per batch, -tall_mid_n = the class's size limit (one round of its
                           // launch): the lowest of tall_mid_step(k) samples that keeps the class within it, in a small batch only
@@ -216,7 +230,8 @@ struct ClassCounts {
   int32_t cursor[GDMIX_RE_NUM_CLASSES];   // row 2: tickets handed out by re_order_kernel
   // row 3 has two tenants: the tall routing in its first words, the team tiers' largest entity (non-zeros) at the tiers' columns
   TallRouting tall;
-  int32_t row3_free[TEAM128_CLASS - (int)(sizeof(TallRouting) / sizeof(int32_t))];
+  int32_t narrow_count;                   // entities at the front of class NARROW_HOST_CLASS's segment that the narrow kernel solves (re_order_kernel)
+  int32_t row3_free[TEAM128_CLASS - 1 - (int)(sizeof(TallRouting) / sizeof(int32_t))];
   int32_t team_largest_nnz[GDMIX_RE_NUM_CLASSES - TEAM128_CLASS];   // of class TEAM128_CLASS + k (largest_nnz)
   unsigned long long team_nnz_total[GDMIX_RE_NUM_CLASSES];          // rows 4-5: non-zeros of the class, team tiers only
   __host__ __device__ int32_t& largest_nnz(int c) { return team_largest_nnz[c - TEAM128_CLASS]; }
@@ -228,6 +243,8 @@ static_assert(offsetof(ClassCounts, count) == 0 && offsetof(ClassCounts, base) =
               offsetof(ClassCounts, team_largest_nnz) == (3 * GDMIX_RE_NUM_CLASSES + TEAM128_CLASS) * sizeof(int32_t) &&
               offsetof(ClassCounts, team_nnz_total) == 4 * GDMIX_RE_NUM_CLASSES * sizeof(int32_t), "the rows of the count record");
 static_assert(offsetof(TallRouting, mid_from) / sizeof(int32_t) < (size_t)TEAM128_CLASS, "row 3: the last threshold slot stays below the team tiers' columns");
+static_assert(offsetof(ClassCounts, narrow_count) == (3 * GDMIX_RE_NUM_CLASSES + GDMIX_RE_NARROW_COUNT_WORD) * sizeof(int32_t) && GDMIX_RE_NARROW_COUNT_WORD < TEAM128_CLASS,
+              "row 3: the narrow count sits where include/gdmix_re.h says, below the team tiers' columns");
 
 // Device pointers of a packed batch, passed by value to kernels.
 struct BatchDev {
@@ -284,6 +301,7 @@ struct gdmix_ctx_impl {
   int tall_team_n;        // ClassTable::tall_team_n (gdmix_re_set_tall_team_n; GDMIX_RE_TALL_TEAM=0 switches the class off)
   int tall_team_limit;    // ClassTable::tall_team_limit: one round of teams on this device
   int tall_mid_n;         // ClassTable::tall_mid_n (gdmix_re_set_tall_mid_n; GDMIX_RE_TALL_MID=0 switches the class off)
+  int narrow;             // ClassTable::narrow (gdmix_re_set_narrow; GDMIX_RE_NARROW=0 switches the narrow kernel off)
   int spread;             // > 1: large classes are dealt over this many queues (the caller's stream + side streams); 0: one after another
   void* grid_sync;        // device: the sync and exchange buffers of the team and tall kernels, laid out by GridSyncLayout (re_solve_team.hpp)
   void* big_tmp;          // device: grow-only temporary of the big-entity pack path
@@ -379,7 +397,8 @@ struct SideJoin {
 // into the context's pinned buffer, good until the next solve); the launches of the classes below the block class
 int make_class_table(const gdmix_ctx_impl* ci, const gdmix_re_opts* opts, ClassTable* out);
 int route(gdmix_ctx_impl* ci, const gdmix_re_packed* b, const ClassTable& tab, const gdmix_re_opts* opts, hipStream_t s, const ClassCounts** host);
-struct Launch { int c, begin, count, stream; };   // entities order[begin, begin + count) of class c; stream -1: the caller's, k >= 0: side stream k
+struct Launch { int c, begin, count, stream, narrow; };   // entities order[begin, begin + count) of class c; stream -1: the caller's, k >= 0: side stream k;
+                                                          // narrow: the first that many go to the narrow kernel (class NARROW_HOST_CLASS only)
 struct LaunchPlan {
   Launch launch[GDMIX_RE_NUM_CLASSES];
   int n;

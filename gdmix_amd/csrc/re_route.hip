@@ -42,6 +42,9 @@ int make_class_table(const gdmix_ctx_impl* ci, const gdmix_re_opts* opts, ClassT
   }
   // the mid class adapts with the split: a caller who pinned the split (gdmix_re_set_tall_split_n) pinned the routing — no per-batch class
   tab.tall_mid_n = (ci->tall_mid_n < 0 && ci->tall_split_set) ? 0 : ci->tall_mid_n;
+  // the narrow kernel: four rows of its layout per workgroup, within the same LDS limit as the classes
+  tab.narrow = (ci->narrow && tab.lds_bytes[NARROW_HOST_CLASS] > 0 &&
+                (WAVE / NARROW_LANES) * quad_layout(NARROW_LANES * NARROW_EPL, NARROW_NCAP, NARROW_ZCAP).bytes <= ci->wave_lds_limit) ? 1 : 0;
   if (opts->sum_loss) {
     // the fixed-effect objective lives in the team kernels only: every entity goes device-wide, one after another
     if (opts->m > TEAM_MCAP) { set_error("sum_loss needs m <= %d", TEAM_MCAP); return GDMIX_RE_EINVAL; }
@@ -92,7 +95,7 @@ __global__ void re_classify_kernel(const int64_t* __restrict__ ent_row_ptr, cons
       if (tab.team_nnz > 0 && z >= tab.team_nnz)
         c = (z >= 128 * tab.team_nnz) ? TEAM8_CLASS : ((z >= 8 * tab.team_nnz) ? TEAM32_CLASS : TEAM128_CLASS);
     }
-    cls_out[e] = c;
+    cls_out[e] = (c == NARROW_HOST_CLASS && tab.narrow && narrow_fits(p, n, z)) ? (c | NARROW_FLAG) : c;
     atomicAdd(&local[c], 1);
     if (c == TALL_S_CLASS && tab.tall_adapt_limit > 0 && n >= tall_adapt_n(0)) {
 #pragma unroll
@@ -190,36 +193,47 @@ __global__ void class_base_kernel(ClassCounts* cc, int tall_adapt_limit, int tal
 // does not influence any entity's result (every entity is solved independently and deterministically),
 // only which workgroup picks it up. Tickets are taken per workgroup (LDS histogram, then one global
 // atomic per class per workgroup): per-entity global atomics on 8 addresses serialise in L2.
+// The narrow entities of class NARROW_HOST_CLASS (marked by re_classify_kernel; the mark is taken off cls here) fill the class's segment
+// from the front, the others from the back, each with tickets of its own: the front part is the narrow kernel's launch (narrow_count).
 // split > 0 (class_base_kernel lowered the split of the tall classes for this batch): one-wavefront tall entities of at least
 // `split` samples move to the eight-wavefront class here, in cls as well (the per-class times are attributed through it).
 __global__ __launch_bounds__(256) void re_order_kernel(int32_t* __restrict__ cls, int64_t E, ClassCounts* __restrict__ cc,
                                                        int32_t* __restrict__ order, const int64_t* __restrict__ ent_row_ptr) {
   __shared__ int32_t cnt[GDMIX_RE_NUM_CLASSES], base[GDMIX_RE_NUM_CLASSES];
+  __shared__ int32_t nar_cnt, nar_base;
   const int split = cc->tall.split;
   const int team_from = cc->tall.team_from;   // > 0: eight-wavefront tall entities of at least this many samples get a team
   const int mid_from = cc->tall.mid_from;     // > 0: one-wavefront tall entities of at least this many samples (below the split) go to the mid class
   const int64_t chunk = (int64_t)blockDim.x * 8;
   for (int64_t start = (int64_t)blockIdx.x * chunk; start < E; start += (int64_t)gridDim.x * chunk) {
     if (threadIdx.x < GDMIX_RE_NUM_CLASSES) cnt[threadIdx.x] = 0;
+    if (threadIdx.x == 0) nar_cnt = 0;
     __syncthreads();
     int c[8], pos[8];
+    unsigned nar = 0;   // bit k: entity k of this thread is narrow
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int64_t e = start + (int64_t)k * blockDim.x + threadIdx.x;
       c[k] = (e < E) ? cls[e] : -1;
+      if (c[k] >= NARROW_FLAG) { c[k] -= NARROW_FLAG; cls[e] = c[k]; nar |= 1u << k; }
       if (split > 0 && c[k] == TALL_S_CLASS && ent_row_ptr[e + 1] - ent_row_ptr[e] >= split) { c[k] = TALL_CLASS; cls[e] = TALL_CLASS; }
       else if (team_from > 0 && c[k] == TALL_CLASS && ent_row_ptr[e + 1] - ent_row_ptr[e] >= team_from) { c[k] = TALL_T_CLASS; cls[e] = TALL_T_CLASS; }
       else if (mid_from > 0 && c[k] == TALL_S_CLASS && ent_row_ptr[e + 1] - ent_row_ptr[e] >= mid_from) { c[k] = TALL_M_CLASS; cls[e] = TALL_M_CLASS; }
-      pos[k] = (c[k] >= 0) ? atomicAdd(&cnt[c[k]], 1) : 0;
+      pos[k] = (c[k] >= 0) ? atomicAdd((nar >> k) & 1u ? &nar_cnt : &cnt[c[k]], 1) : 0;
     }
     __syncthreads();
     if (threadIdx.x < GDMIX_RE_NUM_CLASSES)
       base[threadIdx.x] = cnt[threadIdx.x] ? atomicAdd(&cc->cursor[threadIdx.x], cnt[threadIdx.x]) : 0;
+    if (threadIdx.x == GDMIX_RE_NUM_CLASSES) nar_base = nar_cnt ? atomicAdd(&cc->narrow_count, nar_cnt) : 0;
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int64_t e = start + (int64_t)k * blockDim.x + threadIdx.x;
-      if (c[k] >= 0) order[cc->base[c[k]] + base[c[k]] + pos[k]] = (int32_t)e;
+      if (c[k] < 0) continue;
+      const int seg = cc->base[c[k]];
+      if ((nar >> k) & 1u) order[seg + nar_base + pos[k]] = (int32_t)e;                                                   // from the front
+      else if (c[k] == NARROW_HOST_CLASS) order[seg + cc->count[c[k]] - 1 - (base[c[k]] + pos[k])] = (int32_t)e;           // from the back
+      else order[seg + base[c[k]] + pos[k]] = (int32_t)e;
     }
     __syncthreads();
   }
@@ -309,7 +323,7 @@ LaunchPlan plan_launches(const ClassCounts& counts, int num_cus, int n_side, int
     if (count[c] <= 0) continue;
     small[plan.n] = plan.fork && class_is_small(kClasses[c], count[c], num_cus);
     any_large = any_large || !small[plan.n];
-    plan.launch[plan.n++] = Launch{c, begin[c], count[c], -1};
+    plan.launch[plan.n++] = Launch{c, begin[c], count[c], -1, c == NARROW_HOST_CLASS ? counts.narrow_count : 0};
   }
   int spread_rr = 0;
   for (int k = 0; k < plan.n; ++k) {

@@ -50,6 +50,13 @@ __device__ __forceinline__ void write_results(G& grp, const OutDev& O, const Sol
 // (cross-wave stage of every reduction through LDS + one barrier).
 // LOSS: the loss code of the instantiation (re_device.hpp, loss_terms), a template parameter of every solve kernel: the <LOSS_LOGISTIC>
 // instantiations hold the code they held before the other losses existed; the launchers choose by SolveParams::loss (with_loss).
+// Five coefficient slots per lane (<16,5,24,96>, the narrow part of the <32,3> n<=32 nnz<=128 class: re_route.hip) keep only the newest
+// GDMIX_NARROW_KR pairs of the history in registers and the older ones in a per-lane ring (quad_solve, KR): ten pairs of five slots
+// are 200 VGPRs and spill 183 of them; with five in registers nothing spills. Every other kernel keeps all M_REG pairs in registers.
+#ifndef GDMIX_NARROW_KR
+#define GDMIX_NARROW_KR 5
+#endif
+constexpr int grp_reg_pairs(int epl) { return epl >= 5 ? GDMIX_NARROW_KR : M_REG; }
 template <int G, int EPL, int NCAP, int ZCAP, int LOSS>
 __global__ __launch_bounds__(G > WAVE ? G : WAVE)
 __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 ? GDMIX_QUAD_WAVES_EPL4 : 1)))) void re_solve_grp_kernel(
@@ -113,7 +120,7 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
   }
   grp_fence<G>();
   SolveStats st;
-  quad_solve<G, EPL, (NCAP > G), LOSS>(L, o, gl, n, p, ic, valid, rowc, colc, V, X, st);
+  quad_solve<G, EPL, (NCAP > G), LOSS, grp_reg_pairs(EPL)>(L, o, gl, n, p, ic, valid, rowc, colc, V, X, st);
   if (!valid) return;
 
 #pragma unroll
@@ -214,6 +221,7 @@ hipError_t launch_solve_quad(int g, int epl, const BatchDev& B, const OutDev& O,
   GDMIX_GRP_CASE(16, 2, 16, 64) GDMIX_GRP_CASE(16, 2, 32, 128) GDMIX_GRP_CASE(16, 2, 128, 512)
   GDMIX_GRP_CASE(16, 3, 16, 64) GDMIX_GRP_CASE(16, 3, 32, 128) GDMIX_GRP_CASE(16, 3, 128, 512)
   GDMIX_GRP_CASE(16, 4, 16, 64) GDMIX_GRP_CASE(16, 4, 32, 128) GDMIX_GRP_CASE(16, 4, 128, 512)
+  GDMIX_GRP_CASE(NARROW_LANES, NARROW_EPL, NARROW_NCAP, NARROW_ZCAP)
   GDMIX_GRP_CASE(32, 3, 32, 128) GDMIX_GRP_CASE(32, 3, 64, 256) GDMIX_GRP_CASE(32, 3, 256, 1024)
   GDMIX_GRP_CASE(32, 4, 32, 128) GDMIX_GRP_CASE(32, 4, 64, 256) GDMIX_GRP_CASE(32, 4, 256, 1024)
   GDMIX_GRP_CASE(64, 3, 64, 512) GDMIX_GRP_CASE(64, 3, 512, 2048) GDMIX_GRP_CASE(64, 4, 64, 512) GDMIX_GRP_CASE(64, 4, 512, 2048)

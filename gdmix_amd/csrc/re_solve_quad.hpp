@@ -504,13 +504,21 @@ struct QuadState {
 // LONG_COLS: the class holds entities with more samples than the group has lanes (columns of several entries are the rule): the
 // EPL = 4 kernels then gather their four columns in one loop too, an entry of each per trip (C5-shaped classes - 1 to - 3 %); where
 // columns mostly hold one entry (C2's <16,4>: n <= 16) the four short loops are as fast and spill less (+ 0.5 % with the fused loop)
-template <int G, int EPL, bool LONG_COLS = true, int LOSS = LOSS_LOGISTIC>
+// KR: how many of the M_REG pairs live in the register shift register. KR < M_REG (the EPL = 5 kernel: ten pairs of five slots would
+// be 200 VGPRs) splits the history by age: the newest KR pairs in registers as ever, and a pair that ages out of them is written ONCE
+// into a per-lane ring of M_REG - KR pairs (a private array indexed by a per-row slot, i.e. scratch memory). A push moves no old pair;
+// the ring is read only by the two-loop steps of rows whose history is longer than KR. Same pairs, same order of the steps, same
+// arithmetic: where a pair lives changes no bit. KR == M_REG is the code as it was (no ring, every `if constexpr` below folds away).
+template <int G, int EPL, bool LONG_COLS = true, int LOSS = LOSS_LOGISTIC, int KR = M_REG>
 __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& o, int gl, int n, int p, int ic,
                                            bool valid, unsigned rowc, const unsigned (&colc)[EPL], QuadState<EPL>& V,
                                            XWave& X, SolveStats& out) {
-  // pair a of M_REG, newest last: a register shift register (every index a compile-time constant)
-  constexpr int KR = M_REG;
+  // pair a of M_REG, newest last: the last KR in a register shift register (every index a compile-time constant), pair a < RN in the ring
+  static_assert(KR >= 1 && KR <= M_REG, "register-resident pairs");
+  constexpr int RN = M_REG - KR;
   double S[KR][EPL], Y[KR][EPL];
+  double RS[RN > 0 ? RN : 1][EPL], RY[RN > 0 ? RN : 1][EPL];   // the ring; `head`: the slot the next aged pair goes to (per row)
+  int head = 0;
 #pragma unroll
   for (int a = 0; a < KR; ++a) {
 #pragma unroll
@@ -611,6 +619,15 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
               // (Appending at the wavefront's next free slot instead: three times slower, rejected in round 6: profiles/r06_c2_ab.txt.)
 #pragma unroll
               for (int a = 0; a < M_REG - 1; ++a) rho[a] = rho[a + 1];
+              if constexpr (RN > 0) {
+                // the oldest register pair ages into the ring; one that no direction can use again (cnt < KR: it has never been
+                // within the row's last cnt pairs and every later push moves it further away; m <= KR) is not worth the stores
+                if (cnt >= KR && m > KR) {
+#pragma unroll
+                  for (int s = 0; s < EPL; ++s) { RS[head][s] = S[0][s]; RY[head][s] = Y[0][s]; }
+                }
+                head = (head + 1 == RN) ? 0 : head + 1;
+              }
 #pragma unroll
               for (int a = 0; a < KR - 1; ++a) {
 #pragma unroll
@@ -657,16 +674,28 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
       // (Zero-multiplier steps for the rows that do not use a pair, instead of masked ones: slower, rejected in round 6: profiles/r06_c2_ab.txt.)
       const int cmax = wave_max_nonneg_i32(need_dir ? cnt : 0);
       const int a0 = M_REG - cmax;
+      // ring slot of pair a < RN: the pair that aged last (a = RN - 1) sits at head - 1, the one before it at head - 2, ...
+      const auto ring_slot = [&](int a) { const int sl = head - (RN - a); return sl < 0 ? sl + RN : sl; };
+      (void)ring_slot;
 #define QUAD_FIRST_LOOP_STEP(a)                                                   \
       {                                                                           \
         if ((a) < a0) goto first_loop_done;                                       \
         const bool use = need_dir && ((a) >= M_REG - cnt);                        \
         if (use) {                                                                \
-          double t = 0.0;                                                         \
-          _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += S[a][s] * V.d[s];  \
-          const double al = rho[a] * grp_sum<G>(t, X);                            \
-          alpha[a] = al;                                                          \
-          _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] -= al * Y[a][s]; \
+          if constexpr ((a) >= RN) {                                              \
+            double t = 0.0;                                                       \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += S[(a) - RN][s] * V.d[s];  \
+            const double al = rho[a] * grp_sum<G>(t, X);                          \
+            alpha[a] = al;                                                        \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] -= al * Y[(a) - RN][s]; \
+          } else {                                                                \
+            const int sl = ring_slot(a);                                          \
+            double t = 0.0;                                                       \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += RS[sl][s] * V.d[s];       \
+            const double al = rho[a] * grp_sum<G>(t, X);                          \
+            alpha[a] = al;                                                        \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] -= al * RY[sl][s];      \
+          }                                                                       \
         }                                                                         \
       }
       static_assert(M_REG == 10, "the steps below are written out for ten pairs");
@@ -683,10 +712,18 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
       {                                                                           \
         const bool use = need_dir && ((a) >= M_REG - cnt);                        \
         if (use) {                                                                \
-          double t = 0.0;                                                         \
-          _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += Y[a][s] * V.d[s];  \
-          const double c = alpha[a] - rho[a] * grp_sum<G>(t, X);                  \
-          _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] += c * S[a][s];  \
+          if constexpr ((a) >= RN) {                                              \
+            double t = 0.0;                                                       \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += Y[(a) - RN][s] * V.d[s];  \
+            const double c = alpha[a] - rho[a] * grp_sum<G>(t, X);                \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] += c * S[(a) - RN][s];  \
+          } else {                                                                \
+            const int sl = ring_slot(a);                                          \
+            double t = 0.0;                                                       \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += RY[sl][s] * V.d[s];       \
+            const double c = alpha[a] - rho[a] * grp_sum<G>(t, X);                \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] += c * RS[sl][s];       \
+          }                                                                       \
         }                                                                         \
       }
       switch (a0) {

@@ -101,7 +101,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_abi_version", "gdmix_re_build_id", "gdmix_re_device_shared", "gdmix_re_grid_lock_acquire", "gdmix_re_grid_lock_release", "gdmix_re_grid_lock_stats", "gdmix_re_last_error", "gdmix_re_default_opts", "gdmix_re_create",
     "gdmix_re_destroy", "gdmix_re_pack_workspace_bytes", "gdmix_re_pack", "gdmix_re_set_defer_unique", "gdmix_re_pack_join", "gdmix_re_solve",
     "gdmix_re_solve_scratch_bytes", "gdmix_re_set_scratch", "gdmix_re_variance_full", "gdmix_re_set_wave_lds_limit", "gdmix_re_score",
-    "gdmix_re_widen_workspace_bytes", "gdmix_re_widen", "gdmix_re_set_timing", "gdmix_re_last_solve_ms", "gdmix_re_set_kernel_mask", "gdmix_re_set_giant_nnz", "gdmix_re_set_team_nnz", "gdmix_re_set_tall_min_n", "gdmix_re_set_tall_split_n", "gdmix_re_set_tall_team_n", "gdmix_re_set_tall_mid_n", "gdmix_re_set_spread",
+    "gdmix_re_widen_workspace_bytes", "gdmix_re_widen", "gdmix_re_set_timing", "gdmix_re_last_solve_ms", "gdmix_re_set_kernel_mask", "gdmix_re_set_giant_nnz", "gdmix_re_set_team_nnz", "gdmix_re_set_tall_min_n", "gdmix_re_set_tall_split_n", "gdmix_re_set_tall_team_n", "gdmix_re_set_tall_mid_n", "gdmix_re_set_spread", "gdmix_re_set_narrow",
     "gdmix_fe_create", "gdmix_fe_destroy", "gdmix_fe_eval", "gdmix_fe_reduce_buffer", "gdmix_fe_step", "gdmix_fe_step_async", "gdmix_fe_step_status", "gdmix_fe_solve", "gdmix_fe_result",
     "gdmix_fe_last_eval_ms", "gdmix_fe_stream_bytes", "gdmix_fe_score", "gdmix_fe_hessian_diag", "gdmix_fe_hessian_dense_scratch_bytes", "gdmix_fe_hessian_dense", "gdmix_fe_hessian_dense_loss",
     "gdmix_fe_variance_of_hessian", "gdmix_fe_restart", "gdmix_fe_set_prior", "gdmix_fe_score_models_workspace_bytes", "gdmix_fe_score_models",
@@ -201,6 +201,7 @@ def load_library():
     lib.gdmix_re_set_tall_team_n.argtypes = [C.c_void_p, C.c_int]
     lib.gdmix_re_set_tall_mid_n.argtypes = [C.c_void_p, C.c_int]
     lib.gdmix_re_set_spread.argtypes = [C.c_void_p, C.c_int]
+    lib.gdmix_re_set_narrow.argtypes = [C.c_void_p, C.c_int]
     lib.gdmix_re_set_timing.argtypes = [C.c_void_p, C.c_int]
     lib.gdmix_re_last_solve_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.gdmix_re_score.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p,
@@ -240,7 +241,7 @@ def load_library():
     lib.gdmix_re_feature_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]
     lib.gdmix_re_feature_scale_expand.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    if lib.gdmix_re_abi_version() != 19:
+    if lib.gdmix_re_abi_version() != 20:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib
@@ -580,6 +581,18 @@ class REDeviceSolver:
         """Large size classes are dealt over `queues` streams (the caller's + the context's side streams; default 4) so that their tails
         overlap; 0: one after another on the caller's stream (per-class durations then do not stretch each other)."""
         _check(self.lib.gdmix_re_set_spread(self._h, int(queues)), "set_spread")
+
+    def set_narrow(self, on: bool):
+        """The narrow kernel (re_solve_grp_kernel<16,5,24,96>: four entities per wavefront) for the entities of the <32,3> n<=32 nnz<=128
+        class with at most 80 coefficients, 24 samples and 96 non-zeros; off: the whole class two per wavefront. gdmix_re_set_narrow."""
+        _check(self.lib.gdmix_re_set_narrow(self._h, int(bool(on))), "set_narrow")
+
+    NARROW_COUNT_WORD = 15      # GDMIX_RE_NARROW_COUNT_WORD
+
+    def narrow_count(self, packed: PackedBatch) -> int:
+        """How many entities of the last solve on this batch the narrow kernel took (they are counted in their class by class_counts)."""
+        row3 = packed._view(packed.c.class_count, 4 * NUM_CLASSES, self.torch.int32)[3 * NUM_CLASSES:].cpu().numpy()
+        return int(row3[self.NARROW_COUNT_WORD])
 
     def set_timing(self, enabled: bool):
         _check(self.lib.gdmix_re_set_timing(self._h, int(bool(enabled))), "set_timing")

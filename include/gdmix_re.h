@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 19
+#define GDMIX_RE_ABI_VERSION 20
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -362,6 +362,17 @@ GDMIX_API int gdmix_re_set_tall_team_n(gdmix_re_ctx* ctx, int team_n);
  * caveat as the teams: the kernel an entity gets depends on the batch, its sums are added in another order (agreement to rounding);
  * gdmix_re_set_tall_split_n(ctx, default) pins this choice too. GDMIX_RE_TALL_MID=1 in the environment switches the per-batch class on. */
 GDMIX_API int gdmix_re_set_tall_mid_n(gdmix_re_ctx* ctx, int mid_n);
+
+/* (ABI 20) The NARROW kernel. Entities of the class "re_solve_grp_kernel<32,3> n<=32 nnz<=128" with at most 80 coefficients, 24 samples
+ * and 96 non-zeros are solved four to a wavefront by re_solve_grp_kernel<16,5,24,96> (five coefficients per lane; the older half of the
+ * L-BFGS history in a per-lane ring instead of registers) instead of two to a wavefront. They stay entities of that class: its index,
+ * name, count (gdmix_re_packed::class_count) and time (gdmix_re_last_solve_ms) are the class's; how many of them the narrow kernel took
+ * is word GDMIX_RE_NARROW_COUNT_WORD of row 3 of class_count. Which kernel an entity gets depends on its own (p, n, nnz) alone, so its
+ * result does not depend on the batch; the two kernels agree to rounding (a coefficient sum folds over 16 lanes instead of 32).
+ * on = 0 switches the kernel off (every entity of the class as before ABI 20); GDMIX_RE_NARROW=0 in the environment sets that default
+ * for new contexts. */
+#define GDMIX_RE_NARROW_COUNT_WORD 15
+GDMIX_API int gdmix_re_set_narrow(gdmix_re_ctx* ctx, int on);
 
 /* Launch schedule of a solve. Size classes too small to fill the device always run next to the others on the context's side streams
  * (three, created with the context). `queues` > 1 (default 4 = the caller's stream + the three side streams; GDMIX_RE_SPREAD in the

@@ -15,6 +15,7 @@ Recipes (what round 4's scripts were; DESIGN.md / docs/rounds cite the results):
     LDS vectors of the team kernel --env GDMIX_TEAM_ARENA_KB=0,200 --workloads zipf,c5share
     bitmap pack                    --env GDMIX_PACK_BITMAP=0,1 --workloads c2,ml20m_user --tests "pack"
     tall team class                --env GDMIX_RE_TALL_TEAM=0,1 --workloads ml20m_user,ml20m_movie
+    narrow kernel <16,5,24,96>     --env GDMIX_RE_NARROW=0,1 --workloads c2 --tests "narrow"
     history pairs (direction cost) --workloads c2 -- --lbfgs-m 1     (and again with --lbfgs-m 10)
     two builds                     --lib gdmix_amd/lib_a.so,gdmix_amd/lib_b.so
 """
