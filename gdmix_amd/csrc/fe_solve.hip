@@ -17,102 +17,15 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "re_internal.hpp"
+#include "fe_internal.hpp"
 #include "re_lbfgs_compact.hpp"
 #include "../../include/gdmix_fe.h"
 
-#include <algorithm>
+#include <memory>
 #include <new>
 #include <vector>
 
 namespace gdmix {
-
-#ifndef GDMIX_FE_B
-#define GDMIX_FE_B 2048
-#endif
-#ifndef GDMIX_FE_UNROLL
-#define GDMIX_FE_UNROLL 8
-#endif
-#ifndef GDMIX_FE_PACK
-#define GDMIX_FE_PACK 1      // 0: always the three-array form (tests of that path)
-#endif
-constexpr int FE_B = GDMIX_FE_B;        // accumulators (rows / columns) per block: 16 KiB of LDS per wavefront
-constexpr int FE_U = GDMIX_FE_UNROLL;   // entries per lane in flight
-constexpr int FE_THREADS = 256;
-constexpr int FE_XCDS = 8;           // accelerator dies of an MI355X, each with its own L2; workgroup i runs on die i % 8
-constexpr int FE_WAVES = FE_THREADS / WAVE;
-constexpr int FE_DOT_BLOCKS = 512;
-constexpr int FE_FIN_BLOCKS = 64;   // workgroups (= lanes of the final wavefront) that add up the per-unit partial sums
-static_assert(FE_U % 2 == 0 && FE_B <= 65536 && FE_B % FE_THREADS == 0, "16-bit accumulator index");
-
-// one pass's copy of the non-zeros
-constexpr int FE_LOC_BITS = 11;
-static_assert((1 << FE_LOC_BITS) == GDMIX_FE_B || !GDMIX_FE_PACK, "the packed word holds the accumulator index in its low bits");
-struct FeCopy {
-  const uint2* ent;        // packed [z]: x = (key - kbase[unit]) << FE_LOC_BITS | loc, y = bits of the value; else NULL and:
-  const int32_t* key;      // [z] element of the gathered vector: local column (row pass) / row (column pass)
-  const float* val;        // [z]
-  const uint16_t* loc;     // [z] accumulator within the block
-  const int32_t* kbase;    // [nunit] key of the unit's first entry (the smallest: a unit's keys ascend)
-  const int32_t* ustart;   // [nunit+1] unit -> first entry; units tile the copy
-  const int32_t* ublock;   // [nunit]
-  const int32_t* ufirst;   // [nblock+1] block -> first unit
-  const int32_t* order;    // [nlaunch] workgroup -> unit or -1: units that gather the same stretch of the vector on one XCD (fe_build_copy)
-  double* part;            // [nunit][FE_B] partial sums of the blocks that have several units (column pass: of all)
-  int nunit, nblock, nlaunch;
-  // the 6-byte form (round 5; fe_cpack_kernel): a unit's entries in trips of 512, per trip 2 KB of values + 1 KB of 16-bit words
-  // {5-bit key delta to the entry before, 11-bit accumulator}, keys rebuilt by a wavefront scan
-  const unsigned char* cdata;
-  const int64_t* cbase;    // [nunit] byte offset of the unit in cdata; -1: the unit is read in the 8-byte / three-array form (or NULL)
-  const int32_t* ctrip;    // [nunit] trips
-  int64_t stream_bytes;    // (host bookkeeping) bytes of entries one pass reads: 6-byte-form units incl. fillers and padding + 8 / 10 B per entry of the others
-};
-
-// Frequent features (real feature frequencies are Zipf-like: one feature can hold a tenth of the non-zeros): in the column pass
-// their adds pile up on one LDS address (of the 64 lanes of an instruction, those that hold an entry of the same column
-// serialise), 0.34 ms instead of 0.25 on the Zipf shard of tools/fe_bench.py. A dense pass per frequent column straight off the
-// column-major arrays was tried and lost (0.52 ms): every such column then gathers the residuals on its own, 64 columns =
-// 64 sweeps over them instead of one. So the scatter form stays and the frequent columns (at least FE_HOT_MIN entries, the
-// FE_HOT_MAX most frequent of them) get FE_HOT_REP accumulators each: in the column pass's copy an entry of frequent column h in
-// row r goes to the virtual column vbase + h * FE_HOT_REP + r % FE_HOT_REP. The virtual columns form one more block at the end
-// (entries by ascending row like every block: one sweep over the residuals for all of them), neighbouring rows land on different
-// accumulators, and fe_hot_finish_block (the first workgroups of fe_finish_kernel) adds a column's FE_HOT_REP sums in replica order. No atomics across workgroups, fixed shape.
-constexpr int FE_HOT_MAX = 64;
-constexpr int FE_HOT_REP = 32;
-static_assert(FE_HOT_MAX * FE_HOT_REP <= FE_B && FE_B % FE_HOT_REP == 0, "the virtual columns are one block");
-struct FeHot {
-  int n, vbase;              // vbase: first virtual column (a multiple of FE_B, >= d)
-  const int32_t* col;        // [n] local column of frequent column h
-};
-
-struct FeSync;
-struct FeDev {
-  int n, d, ic, P, m;
-  int64_t z, D;
-  FeCopy rc, cc;            // row pass, column pass
-  FeHot hot;                // frequent columns: left out of cc
-  const int32_t* multi;     // [nmulti] row blocks cut into several units
-  int nmulti, nred;         // nred = rc.nunit + nmulti * (workgroups of fe_rows_fix_kernel per block) entries of loss_part / rsum_part
-  const float *y, *o, *w;   // w may be NULL
-  const int32_t* umap;      // [d] local -> global feature id
-  double* xl;               // [d] x of the features present in this shard
-  double* rs;               // [n] per-sample residual
-  double* fg;               // [P + 1] global data gradient (intercept last), then the data value
-  double *loss_part, *rsum_part, *loss_lo_part;   // [nred] each: value (hi), residual sum, value (lo)
-  double* acc_part;         // [FE_DOT_BLOCKS][COMPACT_KD]
-  double* fin_part;         // [FE_FIN_BLOCKS][3]: value hi, residual sum, value lo
-  unsigned* fin_count;      // workgroups of fe_finish_kernel that have delivered their range sums
-  int32_t* inv;             // [P] global coefficient -> local column of this shard, -1: absent (intercept: -1)
-  struct FeSync* sync;      // ticket + generation stamp of fe_tail_kernel
-  CompactState* state;
-  CompactPlan* plan;
-  CompactMats* mats;
-  Work W;                   // global coefficient space, P each; ws / wy m*P
-  const double *mu, *sc;    // [P] prior mean and scale (include/gdmix_fe.h, "incremental training"), NULL without one; read by the PRIOR variants only
-};
 
 // theta_j of the coefficient whose solver variable is xj: phi_j with a prior installed (W.x holds phi then), itself otherwise
 template <bool PRIOR>
@@ -202,14 +115,6 @@ __device__ __forceinline__ unsigned wave_iscan_pair(unsigned v) {
   return v;
 }
 
-#ifndef GDMIX_FE_COMPRESS_DEFAULT
-#define GDMIX_FE_COMPRESS_DEFAULT 2     // the column pass: 0.268 -> 0.235 ms; the row pass gets slower in this form (0.246 -> 0.257): measured, docs/rounds/r05.md
-#endif
-constexpr int FE_COMPRESS_DEFAULT = GDMIX_FE_COMPRESS_DEFAULT;
-constexpr int FE_CTRIP = WAVE * 8;            // entries per trip of the 6-byte form
-constexpr int FE_CTRIP_BYTES = FE_CTRIP * 6;  // [2][64] x 16 B of values, then [64] x 16 B of index words
-constexpr int FE_CDELTA_MAX = 31;
-static_assert(FE_LOC_BITS == 11, "index word = delta << 11 | accumulator");
 
 // One unit in the 6-byte form. Trip t: lane l holds entries q * 64 + l, q = 0..7 — every gather instruction covers 64 consecutive
 // entries (~100 consecutive elements of the gathered vector), and the adds of one accumulator happen in exact key order.
@@ -417,7 +322,7 @@ __global__ __launch_bounds__(FE_THREADS) void fe_rows_fix_kernel(FeDev F, SolveP
   }
 }
 
-// ---- frequent columns: FE_HOT_REP accumulators each (FeHot above) -------------------------------------------------------------
+// ---- frequent columns: FE_HOT_REP accumulators each (fe_internal.hpp: FeHot) -------------------------------------------------------------
 // next to fe_finish_kernel's own workgroups (which find 0 for a frequent column — the copy holds no entry under its own number — and
 // write nothing then: the buffer is clear before an evaluation). One workgroup per
 // frequent column: replica r's sum over the virtual block's units by 8 strands, strands in order, then the replicas in order.
@@ -515,24 +420,6 @@ __global__ __launch_bounds__(FE_THREADS) void fe_finish_kernel(FeDev F) {
       if (F.ic) F.fg[F.D] = r;
       F.fg[F.P] = a + al;      // rounded once
       *F.fin_count = 0u;
-    }
-  }
-}
-
-// the column pass's source columns with the frequent ones replaced by their virtual columns; one thread per row
-__global__ void fe_hot_remap_kernel(const int32_t* __restrict__ ptr, int n, const int32_t* __restrict__ col, const int32_t* __restrict__ hotmap,
-                                    int vbase, int32_t* __restrict__ col2) {
-  for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < n; row += gridDim.x * blockDim.x) {
-    const int k1 = ptr[row + 1];
-    for (int k = ptr[row]; k < k1; ++k) {
-      const int c = col[k];
-      const int h = hotmap[c];
-      // the replica by the entry's POSITION, not by its row (round 4): a wavefront's 128 entries in flight are consecutive in row
-      // order and span only ~4 rows of a 32-non-zero shard, so row % 32 sent all entries of all frequent columns of an instruction to
-      // four replica slots = four LDS bank pairs (replicas of different columns 256 B apart share banks): SQ_LDS_BANK_CONFLICT + 62 %
-      // against a uniform shard (profiles/r04_fe_counters.txt). The position spreads them over all 32; still a fixed assignment, so a
-      // replica's terms are added in row order and two fits give the same bits.
-      col2[k] = h >= 0 ? vbase + h * FE_HOT_REP + (k % FE_HOT_REP) : c;
     }
   }
 }
@@ -717,7 +604,6 @@ __device__ __forceinline__ void fe_update_one(const FeDev& F, const CompactPlan&
 // relaxed agent atomics for ticket and stamp, one lane's agent-scope acquire, workgroup barrier, plain loads.
 // A stopped problem (status >= 0 from an earlier launch) makes this and every pass kernel return at once: the host may enqueue
 // evaluations ahead of the status it has read (gdmix_fe_step_async).
-struct FeSync { unsigned arrive, gen, aborted; };      // aborted: sticky, set by a waiter whose watchdog fired (never cleared: the problem is dead)
 
 template <bool PRIOR = false>
 __global__ __launch_bounds__(FE_THREADS) void fe_tail_kernel(FeDev F, SolveParams o, int dot_blocks, int32_t* status_out, unsigned seq) {
@@ -835,10 +721,6 @@ __global__ void fe_init_kernel(FeDev F, const double* __restrict__ theta0) {
   }
 }
 
-// ---- the passes' copies of the non-zeros ---------------------------------------------------------------------------------
-// From the packed shard's CSR (for the column pass) and CSC (for the row pass) arrays: segment of every entry (flag + scan),
-// stable sort by block of the entry's index (rocPRIM radix sort on the block number alone, so the source order — the order of
-// the gathered vector — survives inside a block), units = the blocks' runs cut every `chunk` entries.
 // ---- incremental training: what only a problem with a prior launches ------------------------------------------------------------------
 // *bad = 1 if a scale is not finite or not > 0 (gdmix_fe_set_prior reads it back before anything of the problem is touched)
 __global__ void fe_prior_check_kernel(const double* __restrict__ scale, int P, int32_t* __restrict__ bad) {
@@ -853,173 +735,6 @@ __global__ void fe_prior_theta_kernel(FeDev F, double* __restrict__ theta) {
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < F.P; j += gridDim.x * blockDim.x) theta[j] = fe_theta_of<true>(F, j, F.W.x[j]);
 }
 
-__global__ void fe_flag_kernel(const int32_t* __restrict__ ptr, int nseg, int64_t z, int32_t* __restrict__ flag) {
-  for (int s = blockIdx.x * blockDim.x + threadIdx.x + 1; s < nseg; s += gridDim.x * blockDim.x) {
-    const int p = ptr[s];
-    if (p < z) atomicAdd(&flag[p], 1);   // empty segments pile up on the next entry
-  }
-}
-
-struct FeEnt { int32_t seg, idx; float val; };   // an entry on its way through the sort
-
-// Sort key: the block, refined by the window of 2^FE_SPAN_BITS gathered elements the entry's key lies in. The entries of a block
-// already come by ascending key, so the windows do not change the sorted order; they only add cut points, so that no unit's keys
-// span more than the packed word can hold (a block with few entries is one unit over the whole vector otherwise, and one such
-// unit would send the whole copy to the three-array form: the Zipf shard of tools/fe_bench.py, 0.34 ms instead of 0.26).
-constexpr int FE_SPAN_BITS = 32 - FE_LOC_BITS;
-__global__ void fe_ent_kernel(const int32_t* __restrict__ seg, const int32_t* __restrict__ idx, const float* __restrict__ val, int64_t z,
-                              int nwin, int wbits, uint32_t* __restrict__ skey, FeEnt* __restrict__ ent) {
-  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < z; k += (int64_t)gridDim.x * blockDim.x) {
-    const int i = idx[k], sg = seg[k];
-    skey[k] = (uint32_t)(i / FE_B) * (uint32_t)nwin + (uint32_t)(sg >> wbits);
-    ent[k] = FeEnt{sg, i, val[k]};
-  }
-}
-
-// widest unit: key of its last entry - key of its first (keys ascend inside a unit)
-__global__ void fe_span_kernel(const FeEnt* __restrict__ ent, const int32_t* __restrict__ ustart, int nunit, int32_t* __restrict__ kbase,
-                               int32_t* __restrict__ max_span) {
-  for (int u = blockIdx.x * blockDim.x + threadIdx.x; u < nunit; u += gridDim.x * blockDim.x) {
-    const int k0 = ustart[u], k1 = ustart[u + 1];
-    const int first = k1 > k0 ? ent[k0].seg : 0;
-    kbase[u] = first;
-    if (k1 > k0) atomicMax(max_span, ent[k1 - 1].seg - first);
-  }
-}
-
-// the copy in the form the pass reads; one workgroup per unit
-template <bool PACKED>
-__global__ __launch_bounds__(256) void fe_pack_kernel(const FeEnt* __restrict__ ent, const int32_t* __restrict__ ustart,
-                                                      const int32_t* __restrict__ kbase, uint2* __restrict__ out, int32_t* __restrict__ ckey,
-                                                      float* __restrict__ cval, uint16_t* __restrict__ cloc) {
-  const int u = blockIdx.x;
-  const int k0 = ustart[u], k1 = ustart[u + 1], kb = kbase[u];
-  for (int k = k0 + threadIdx.x; k < k1; k += 256) {
-    const FeEnt e = ent[k];
-    const int l = e.idx % FE_B;
-    if (PACKED) {
-      out[k] = make_uint2(((uint32_t)(e.seg - kb) << FE_LOC_BITS) | (uint32_t)l, __float_as_uint(e.val));
-    } else {
-      ckey[k] = e.seg;
-      cval[k] = e.val;
-      cloc[k] = (uint16_t)l;
-    }
-  }
-}
-
-// ---- the 6-byte form of a unit's entries --------------------------------------------------------------------------------------
-// fillers an entry needs in front of it so that every key delta fits FE_CDELTA_MAX: a gap g > 31 takes (g - 1) / 31 fillers of
-// delta 31 (value 0, accumulator 0) and leaves a delta in [1, 31] for the entry itself
-__device__ __forceinline__ int fe_fillers(int gap) { return gap > FE_CDELTA_MAX ? (gap - 1) / FE_CDELTA_MAX : 0; }
-
-// entries of unit u in the 6-byte form, fillers included (one workgroup per unit)
-__global__ __launch_bounds__(256) void fe_ccount_kernel(const FeEnt* __restrict__ ent, const int32_t* __restrict__ ustart, const int32_t* __restrict__ kbase,
-                                                        int32_t* __restrict__ cnt) {
-  __shared__ int red[256 / WAVE];
-  const int u = blockIdx.x, k0 = ustart[u], k1 = ustart[u + 1], kb = kbase[u];
-  int f = 0;
-  for (int k = k0 + threadIdx.x; k < k1; k += 256) f += fe_fillers(ent[k].seg - (k > k0 ? ent[k - 1].seg : kb));
-  for (int sh = 32; sh > 0; sh >>= 1) f += __shfl_down(f, sh);
-  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x >> 6] = f;
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[u] = (k1 - k0) + red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ __forceinline__ void fe_cput(unsigned char* base, int pos, float val, unsigned word) {
-  const int t = pos / FE_CTRIP, w = pos % FE_CTRIP, q = w / WAVE, l = w % WAVE;
-  unsigned char* tp = base + (size_t)t * FE_CTRIP_BYTES;
-  *reinterpret_cast<float*>(tp + (q >> 2) * 1024 + l * 16 + (q & 3) * 4) = val;
-  *reinterpret_cast<uint16_t*>(tp + 2048 + l * 16 + q * 2) = (uint16_t)word;
-}
-
-// the units that take the form (cbase[u] >= 0), written into a zeroed buffer: what stays zero is padding (delta 0, value 0)
-__global__ __launch_bounds__(256) void fe_cpack_kernel(const FeEnt* __restrict__ ent, const int32_t* __restrict__ ustart, const int32_t* __restrict__ kbase,
-                                                       const int64_t* __restrict__ cbase, unsigned char* __restrict__ cdata) {
-  __shared__ int wsum[256 / WAVE];
-  __shared__ int carry;
-  const int u = blockIdx.x;
-  if (cbase[u] < 0) return;
-  const int k0 = ustart[u], k1 = ustart[u + 1], kb = kbase[u];
-  unsigned char* base = cdata + cbase[u];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int c0 = k0; c0 < k1; c0 += 256) {
-    const int k = c0 + tid;
-    int gap = 0, f = 0;
-    FeEnt e{0, 0, 0.0f};
-    if (k < k1) {
-      e = ent[k];
-      gap = e.seg - (k > k0 ? ent[k - 1].seg : kb);
-      f = fe_fillers(gap);
-    }
-    // exclusive prefix of f over the 256 entries of this chunk
-    int incl = f;
-    for (int sh = 1; sh < WAVE; sh <<= 1) {
-      const int up = __shfl_up(incl, sh);
-      if (lane >= sh) incl += up;
-    }
-    if (lane == WAVE - 1) wsum[wv] = incl;
-    __syncthreads();
-    int before = carry;
-    for (int w2 = 0; w2 < wv; ++w2) before += wsum[w2];
-    const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    if (k < k1) {
-      const int first = (k - k0) + before + (incl - f);      // position of this entry's first filler (or of the entry)
-      for (int j = 0; j < f; ++j) fe_cput(base, first + j, 0.0f, (unsigned)FE_CDELTA_MAX << FE_LOC_BITS);
-      fe_cput(base, first + f, e.val, ((unsigned)(gap - FE_CDELTA_MAX * f) << FE_LOC_BITS) | (unsigned)(e.idx % FE_B));
-    }
-    __syncthreads();
-    if (tid == 0) carry += total;
-    __syncthreads();
-  }
-}
-
-// bp[b] = first sorted entry of a block >= b
-__global__ void fe_block_kernel(const uint32_t* __restrict__ sorted, int64_t z, int nblock, int32_t* __restrict__ bp) {
-  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b <= nblock; b += gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = z;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sorted[mid] < (uint32_t)b) lo = mid + 1; else hi = mid;
-    }
-    bp[b] = (int32_t)lo;
-  }
-}
-
-// Entries per unit of a (block, window) with len entries. A unit is one wavefront; where a block has fewer than four entries
-// per 128-byte line of the gathered vector, nearly every gather is a line of its own out of the far cache and the unit crawls
-// at a few microseconds per trip of 512 entries: 62 500 entries = 0.3 ms, the length of the whole pass (the rare features' blocks
-// of a Zipf shard). Such blocks get units an eighth as long (sparse_chunk; 0 = never).
-__device__ __forceinline__ int fe_block_chunk(int len, int chunk, int sparse_chunk, int extent) {
-  return (sparse_chunk > 0 && (int64_t)len * 4 < (int64_t)extent) ? sparse_chunk : chunk;
-}
-
-// units of (block, window) b; the first window of a block keeps one even when empty: the block's outputs are still due
-__global__ void fe_chunks_kernel(const int32_t* __restrict__ bp, int nblock, int nwin, int chunk, int sparse_chunk, int extent,
-                                 int32_t* __restrict__ nch) {
-  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b <= nblock; b += gridDim.x * blockDim.x) {
-    const int len = b < nblock ? bp[b + 1] - bp[b] : 0;
-    const int c = fe_block_chunk(len, chunk, sparse_chunk, extent);
-    nch[b] = b < nblock ? (len == 0 ? (b % nwin == 0 ? 1 : 0) : (len + c - 1) / c) : 0;
-  }
-}
-
-// ufirst: first unit per (block, window); out: the units' first entries and blocks, and first unit per block
-__global__ void fe_units_kernel(const int32_t* __restrict__ bp, const int32_t* __restrict__ ufirst, int nblock, int nwin, int chunk,
-                                int sparse_chunk, int extent, int64_t z, int32_t* __restrict__ ustart, int32_t* __restrict__ ublock,
-                                int32_t* __restrict__ block_first) {
-  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < nblock; b += gridDim.x * blockDim.x) {
-    const int u0 = ufirst[b], u1 = ufirst[b + 1];
-    const int c = fe_block_chunk(bp[b + 1] - bp[b], chunk, sparse_chunk, extent);
-    for (int u = u0; u < u1; ++u) {
-      ustart[u] = bp[b] + (u - u0) * c;
-      ublock[u] = b / nwin;
-    }
-    if (b % nwin == 0) block_first[b / nwin] = u0;
-    if (b == nblock - 1) { ustart[u1] = (int32_t)z; block_first[nblock / nwin] = u1; }
-  }
-}
 
 }  // namespace gdmix
 
@@ -1055,306 +770,46 @@ __global__ __launch_bounds__(256) void fe_score_kernel(int64_t n, const int64_t*
   per_coord[i] = (float)(z - off);
 }
 
-struct gdmix_fe_problem {
-  gdmix_re_ctx* ctx;
-  FeDev F;
-  SolveParams o;
-  void* pool;            // one device allocation carved into the vectors and partial sums
-  size_t pool_bytes, pool_multi, pool_multi_end, pool_inv;   // its size; the part gdmix_fe_restart keeps (F.multi); where F.inv lies
-  void* copies[2];       // the row pass's and the column pass's copy of the non-zeros, with their unit tables
-  void* ccopies[2];      // ... and their units in the 6-byte form
-  int compress;          // bit 0: row pass, bit 1: column pass may use the 6-byte form (GDMIX_FE_COMPRESS; default: FE_COMPRESS_DEFAULT)
-  void* hot_mem;         // the frequent columns' tables
-  double* prior_mem;     // [2 P] the problem's copy of the prior mean and scale, then the check's flag (gdmix_fe_set_prior); NULL until the first prior
-  int32_t* status_dev;
-  hipEvent_t ev[3];
-  bool timed;
-  bool dirty;            // the reduce buffer holds a result no step has consumed (and cleared) yet
-  bool fused_tail;       // the step is one launch (fe_tail_kernel); GDMIX_FE_FUSED_TAIL=0: dots / step / update as three (A/B)
-  unsigned gen;          // launches of fe_tail_kernel so far (its generation stamp)
-  int64_t evals;         // gdmix_fe_eval calls so far
-  int64_t seq;           // steps enqueued so far; step k's status lands in status_ring[k % FE_RING] behind ring_ev[k % FE_RING]
-  int32_t* status_ring;  // page-locked
-  hipEvent_t ring_ev[8];
-  std::vector<int32_t> uf_c;
-};
+
 constexpr int FE_RING = 8;
 
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct gdmix_fe_problem {
+  gdmix_re_ctx* ctx = nullptr;
+  FeDev F{};
+  SolveParams o{};
+  DevBuf pool;           // one device allocation carved into the vectors and partial sums
+  size_t pool_bytes = 0, pool_multi = 0, pool_multi_end = 0, pool_inv = 0;   // its size; the part gdmix_fe_restart keeps (F.multi); where F.inv lies
+  DevBuf copies[2];      // the row pass's and the column pass's copy of the non-zeros, with their unit tables
+  DevBuf ccopies[2];     // ... and their units in the 6-byte form
+  DevBuf hot_mem;        // the frequent columns' list
+  DevBuf prior_mem;      // [2 P] the problem's copy of the prior mean and scale, then the check's flag (gdmix_fe_set_prior); empty until the first prior
+  int32_t* status_dev = nullptr;
+  hipEvent_t ev[3] = {};
+  bool timed = false;
+  bool dirty = false;        // the reduce buffer holds a result no step has consumed (and cleared) yet
+  bool fused_tail = true;    // the step is one launch (fe_tail_kernel); GDMIX_FE_FUSED_TAIL=0: dots / step / update as three (A/B)
+  unsigned gen = 0;      // launches of fe_tail_kernel so far (its generation stamp)
+  int64_t evals = 0;     // gdmix_fe_eval calls so far
+  int64_t seq = 0;       // steps enqueued so far; step k's status lands in status_ring[k % FE_RING] behind ring_ev[k % FE_RING]
+  PinnedBuf status_ring; // [FE_RING] int32_t
+  hipEvent_t ring_ev[FE_RING] = {};
 
-// Entries per unit. Blocks stay whole (a row block then finishes its rows itself) when that still gives the device enough
-// units; otherwise every block is cut so that there are about eight wavefronts per CU.
-static int fe_chunk_len(int64_t z, int nblock, int num_cus) {
-  const int64_t target = (z + (int64_t)num_cus * 8 - 1) / ((int64_t)num_cus * 8);
-  const int64_t avg = (z + nblock - 1) / nblock;
-  int64_t c = (avg <= 2 * target) ? 2 * avg : target;
-  if (c < 8192) c = 8192;
-  if (const char* e = getenv("GDMIX_FE_CHUNK")) {   // test hook: small shards through the several-units-per-block code
-    const long v = atol(e);
-    if (v >= 64) c = v;
+  ~gdmix_fe_problem() {
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ring_ev) if (e) (void)hipEventDestroy(e);
   }
-  if (c > (1 << 28)) c = 1 << 28;
-  return (int)c;
-}
+};
 
-// Build one pass's copy from segment-major source arrays (ptr [nseg+1], idx / val [z]); `len` = extent of idx (outputs of the
-// pass). Device memory of the result in *owned; the block -> unit table is also returned on the host (ufirst).
-static int fe_build_copy(hipStream_t s, int num_cus, const int32_t* ptr, int nseg, const int32_t* idx, const float* val, int64_t z,
-                         int len, bool cut_sparse, bool compress, FeCopy* out, void** owned, void** owned_c, std::vector<int32_t>* ufirst_host) {
-  *owned = nullptr;
-  *owned_c = nullptr;
-  const int nblock = len > 0 ? (len + FE_B - 1) / FE_B : 1;
-  const int chunk = fe_chunk_len(z, nblock, num_cus);
-  const size_t zz = (size_t)(z > 0 ? z : 1);
-  int wbits = FE_SPAN_BITS;
-  if (const char* e = getenv("GDMIX_FE_WINDOW_BITS")) {   // test hook: several windows on a small shard (narrower is always valid)
-    const int v = atoi(e);
-    if (v >= 1 && v < FE_SPAN_BITS) wbits = v;
-  }
-  const int nwin = ((nseg > 0 ? nseg - 1 : 0) >> wbits) + 1;   // windows of the gathered vector (fe_ent_kernel)
-  if ((int64_t)nblock * nwin > 0x7fffff00ll) { set_error("shard too large for the pass tables"); return GDMIX_RE_ERANGE; }
-  const int nbw = nblock * nwin;
-  const int extent = nseg < (1 << wbits) ? (nseg > 0 ? nseg : 1) : (1 << wbits);   // gathered elements per window
-  const int sparse_chunk = cut_sparse ? (chunk / 8 > 4096 ? chunk / 8 : (chunk < 4096 ? chunk : 4096)) : 0;
-  unsigned bits = 1;
-  while (bits < 32 && (1u << bits) < (unsigned)nbw) ++bits;
-  size_t sort_tmp = 0, scan_tmp = 0, scan2_tmp = 0;
-  hipError_t rc = rocprim::radix_sort_pairs(nullptr, sort_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (FeEnt*)nullptr, (FeEnt*)nullptr,
-                                            zz, 0u, bits, s);
-  if (rc == hipSuccess) rc = rocprim::inclusive_scan(nullptr, scan_tmp, (int32_t*)nullptr, (int32_t*)nullptr, zz, rocprim::plus<int32_t>(), s);
-  if (rc == hipSuccess) rc = rocprim::exclusive_scan(nullptr, scan2_tmp, (int32_t*)nullptr, (int32_t*)nullptr, 0, (size_t)nbw + 1, rocprim::plus<int32_t>(), s);
-  if (rc != hipSuccess) { set_error("rocPRIM sizing failed: %s", hipGetErrorString(rc)); return GDMIX_RE_EHIP; }
-  size_t lib = sort_tmp > scan_tmp ? sort_tmp : scan_tmp;
-  if (scan2_tmp > lib) lib = scan2_tmp;
-  // upper bound of the unit count: a block of len entries has at most len / chunk + 1 units
-  const size_t max_units = (size_t)nbw + (size_t)(z / (sparse_chunk > 0 ? sparse_chunk : chunk)) + 1;
-  size_t woff = 0;
-  auto wtake = [&](size_t bytes) { size_t r = woff; woff = up256(woff + bytes); return r; };
-  const size_t w_a = wtake(zz * 4), w_seg = wtake(zz * 4), w_key = wtake(zz * 4), w_ent = wtake(zz * sizeof(FeEnt)), w_ent2 = wtake(zz * sizeof(FeEnt));
-  const size_t w_bp = wtake(((size_t)nbw + 1) * 4), w_nch = wtake(((size_t)nbw + 1) * 4), w_uf = wtake(((size_t)nbw + 1) * 4);
-  const size_t w_span = wtake(64), w_lib = wtake(lib);
-  void* tmp = nullptr;
-  rc = hipMalloc(&tmp, woff);
-  if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", woff, hipGetErrorString(rc)); return GDMIX_RE_ENOMEM; }
-  char* wb = static_cast<char*>(tmp);
-  int32_t* flag = reinterpret_cast<int32_t*>(wb + w_a);      // later: the sorted block numbers
-  int32_t* seg = reinterpret_cast<int32_t*>(wb + w_seg);
-  uint32_t* skey = reinterpret_cast<uint32_t*>(wb + w_key);
-  uint32_t* skey2 = reinterpret_cast<uint32_t*>(wb + w_a);
-  FeEnt* ent = reinterpret_cast<FeEnt*>(wb + w_ent);
-  FeEnt* ent2 = reinterpret_cast<FeEnt*>(wb + w_ent2);
-  int32_t* bp = reinterpret_cast<int32_t*>(wb + w_bp);
-  int32_t* nch = reinterpret_cast<int32_t*>(wb + w_nch);
-  int32_t* ufw = reinterpret_cast<int32_t*>(wb + w_uf);     // first unit per (block, window)
-  int32_t* span = reinterpret_cast<int32_t*>(wb + w_span);
-  // the unit tables; the entries follow once their form is known
-  size_t toff = 0;
-  auto ttake = [&](size_t bytes) { size_t r = toff; toff = up256(toff + bytes); return r; };
-  const size_t c_uf = ttake(((size_t)nblock + 1) * 4), c_us = ttake((max_units + 1) * 4), c_ub = ttake(max_units * 4), c_kb = ttake(max_units * 4), c_ord = ttake((max_units + FE_XCDS) * 4);
-  const size_t c_ent = ttake(zz * 10 + 512);   // 8 B per entry packed, 4 + 4 + 2 otherwise
-  void* mem = nullptr;
-  rc = hipMalloc(&mem, toff);
-  if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", toff, hipGetErrorString(rc)); (void)hipFree(tmp); return GDMIX_RE_ENOMEM; }
-  char* cb = static_cast<char*>(mem);
-  int32_t* ufirst = reinterpret_cast<int32_t*>(cb + c_uf);
-  int32_t* ustart = reinterpret_cast<int32_t*>(cb + c_us);
-  int32_t* ublock = reinterpret_cast<int32_t*>(cb + c_ub);
-  int32_t* kbase = reinterpret_cast<int32_t*>(cb + c_kb);
-  const int ge = num_cus * 16;
-  int gb = (nbw + 1 + 255) / 256;
-  if (gb > 4096) gb = 4096;
-  (void)hipMemsetAsync(span, 0, 64, s);
-  if (z > 0) {
-    (void)hipMemsetAsync(flag, 0, zz * 4, s);
-    int gs = (nseg + 255) / 256;
-    if (gs > 4096) gs = 4096;
-    if (gs < 1) gs = 1;
-    hipLaunchKernelGGL(fe_flag_kernel, dim3(gs), dim3(256), 0, s, ptr, nseg, z, flag);
-    size_t lt = scan_tmp;
-    rc = rocprim::inclusive_scan(wb + w_lib, lt, flag, seg, (size_t)z, rocprim::plus<int32_t>(), s);
-    hipLaunchKernelGGL(fe_ent_kernel, dim3(ge), dim3(256), 0, s, seg, idx, val, z, nwin, wbits, skey, ent);
-    lt = sort_tmp;
-    if (rc == hipSuccess) rc = rocprim::radix_sort_pairs(wb + w_lib, lt, skey, skey2, ent, ent2, (size_t)z, 0u, bits, s);
-  }
-  hipLaunchKernelGGL(fe_block_kernel, dim3(gb), dim3(256), 0, s, skey2, z, nbw, bp);
-  hipLaunchKernelGGL(fe_chunks_kernel, dim3(gb), dim3(256), 0, s, bp, nbw, nwin, chunk, sparse_chunk, extent, nch);
-  size_t lt = scan2_tmp;
-  if (rc == hipSuccess) rc = rocprim::exclusive_scan(wb + w_lib, lt, nch, ufw, 0, (size_t)nbw + 1, rocprim::plus<int32_t>(), s);
-  hipLaunchKernelGGL(fe_units_kernel, dim3(gb), dim3(256), 0, s, bp, ufw, nbw, nwin, chunk, sparse_chunk, extent, z, ustart, ublock, ufirst);
-  ufirst_host->resize((size_t)nblock + 1);
-  if (rc == hipSuccess) rc = hipMemcpyAsync(ufirst_host->data(), ufirst, ((size_t)nblock + 1) * 4, hipMemcpyDeviceToHost, s);
-  if (rc == hipSuccess) rc = hipStreamSynchronize(s);
-  const int nunit = rc == hipSuccess ? (*ufirst_host)[(size_t)nblock] : 0;
-  int32_t max_span = 0;
-  if (rc == hipSuccess) {
-    int gu = (nunit + 255) / 256;
-    if (gu > 4096) gu = 4096;
-    hipLaunchKernelGGL(fe_span_kernel, dim3(gu), dim3(256), 0, s, ent2, ustart, nunit, kbase, span);
-    rc = hipMemcpyAsync(&max_span, span, 4, hipMemcpyDeviceToHost, s);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(s);
-  }
-  // Launch order. Workgroups go to the XCDs round robin and every XCD has its own L2: units that gather the same stretch of the
-  // vector should meet in one L2 rather than pull it over the fabric eight times (column pass on 4 M samples: 256 MB of
-  // residuals on top of 1 GB of entries). Units sorted by first gathered element, the sorted list cut into one run per XCD,
-  // run x dealt to the workgroups x, x + XCDS, ...
-  std::vector<int32_t> order;
-  if (rc == hipSuccess) {
-    std::vector<int32_t> kb((size_t)nunit), by((size_t)nunit);
-    if (nunit) rc = hipMemcpy(kb.data(), kbase, (size_t)nunit * 4, hipMemcpyDeviceToHost);
-    for (int u = 0; u < nunit; ++u) by[(size_t)u] = u;
-    std::stable_sort(by.begin(), by.end(), [&](int32_t a, int32_t b) { return kb[(size_t)a] < kb[(size_t)b]; });
-    const int per = (nunit + FE_XCDS - 1) / FE_XCDS;
-    order.assign((size_t)per * FE_XCDS, -1);
-    for (int x = 0; x < FE_XCDS; ++x)
-      for (int j = 0; j < per && x * per + j < nunit; ++j) order[(size_t)j * FE_XCDS + x] = by[(size_t)x * per + j];
-    if (rc == hipSuccess && !order.empty()) rc = hipMemcpy(cb + c_ord, order.data(), order.size() * 4, hipMemcpyHostToDevice);
-  }
-  bool packed = GDMIX_FE_PACK && max_span < (1 << (32 - FE_LOC_BITS));
-  if (const char* e = getenv("GDMIX_FE_PACK")) packed = packed && atoi(e) != 0;   // test hook: the three-array form on a small shard
-  uint2* pent = reinterpret_cast<uint2*>(cb + c_ent);
-  int32_t* ckey = reinterpret_cast<int32_t*>(cb + c_ent);
-  float* cval = reinterpret_cast<float*>(cb + c_ent + up256(zz * 4));
-  uint16_t* cloc = reinterpret_cast<uint16_t*>(cb + c_ent + 2 * up256(zz * 4));
-  if (rc == hipSuccess && nunit > 0 && z > 0) {
-    if (packed) hipLaunchKernelGGL((fe_pack_kernel<true>), dim3(nunit), dim3(256), 0, s, ent2, ustart, kbase, pent, ckey, cval, cloc);
-    else hipLaunchKernelGGL((fe_pack_kernel<false>), dim3(nunit), dim3(256), 0, s, ent2, ustart, kbase, pent, ckey, cval, cloc);
-    rc = hipStreamSynchronize(s);
-  }
-  if (rc == hipSuccess) rc = hipGetLastError();
-  out->stream_bytes = (int64_t)z * (packed ? 8 : 10);
-  // ---- the 6-byte form for the units it shortens (round 5) ----
-  void* cmem = nullptr;
-  out->cdata = nullptr; out->cbase = nullptr; out->ctrip = nullptr;
-  if (rc == hipSuccess && compress && nunit > 0 && z > 0) {
-    int32_t* cnt_dev = nullptr;
-    void* cnt_mem = nullptr;
-    rc = hipMalloc(&cnt_mem, (size_t)nunit * 4);
-    std::vector<int32_t> cnt((size_t)nunit), us((size_t)nunit + 1);
-    if (rc == hipSuccess) {
-      cnt_dev = static_cast<int32_t*>(cnt_mem);
-      hipLaunchKernelGGL(fe_ccount_kernel, dim3(nunit), dim3(256), 0, s, ent2, ustart, kbase, cnt_dev);
-      rc = hipMemcpyAsync(cnt.data(), cnt_dev, (size_t)nunit * 4, hipMemcpyDeviceToHost, s);
-      if (rc == hipSuccess) rc = hipMemcpyAsync(us.data(), ustart, ((size_t)nunit + 1) * 4, hipMemcpyDeviceToHost, s);
-      if (rc == hipSuccess) rc = hipStreamSynchronize(s);
-    }
-    if (cnt_mem) (void)hipFree(cnt_mem);
-    std::vector<int64_t> cb((size_t)nunit, -1);
-    std::vector<int32_t> ct((size_t)nunit, 0);
-    size_t total = 0;
-    int taken = 0;
-    for (int u = 0; rc == hipSuccess && u < nunit; ++u) {
-      const int64_t nu = (int64_t)us[(size_t)u + 1] - us[(size_t)u];
-      const int64_t trips = ((int64_t)cnt[(size_t)u] + FE_CTRIP - 1) / FE_CTRIP;
-      // the form pays when it is shorter than 8 bytes per entry with room to spare (fillers of sparse blocks, padding of short units)
-      if (nu > 0 && trips * FE_CTRIP_BYTES * 10 <= nu * 8 * 9) { cb[(size_t)u] = (int64_t)total; ct[(size_t)u] = (int32_t)trips; total += (size_t)trips * FE_CTRIP_BYTES; ++taken; }
-    }
-    if (rc == hipSuccess && taken > 0) {
-      const size_t o_cb = 0, o_ct = up256((size_t)nunit * 8), o_data = o_ct + up256((size_t)nunit * 4);
-      rc = hipMalloc(&cmem, o_data + total + 256);
-      if (rc == hipSuccess) {
-        char* cm = static_cast<char*>(cmem);
-        rc = hipMemsetAsync(cm + o_data, 0, total, s);
-        if (rc == hipSuccess) rc = hipMemcpyAsync(cm + o_cb, cb.data(), (size_t)nunit * 8, hipMemcpyHostToDevice, s);
-        if (rc == hipSuccess) rc = hipMemcpyAsync(cm + o_ct, ct.data(), (size_t)nunit * 4, hipMemcpyHostToDevice, s);
-        if (rc == hipSuccess) {
-          hipLaunchKernelGGL(fe_cpack_kernel, dim3(nunit), dim3(256), 0, s, ent2, ustart, kbase, reinterpret_cast<const int64_t*>(cm + o_cb),
-                             reinterpret_cast<unsigned char*>(cm + o_data));
-          rc = hipStreamSynchronize(s);      // (cb / ct go out of scope; tmp is freed below)
-        }
-        if (rc == hipSuccess) {
-          int64_t plain = 0;
-          for (int u = 0; u < nunit; ++u) if (cb[(size_t)u] < 0) plain += (int64_t)us[(size_t)u + 1] - us[(size_t)u];
-          out->stream_bytes = (int64_t)total + plain * (packed ? 8 : 10);
-          out->cdata = reinterpret_cast<const unsigned char*>(cm + o_data);
-          out->cbase = reinterpret_cast<const int64_t*>(cm + o_cb);
-          out->ctrip = reinterpret_cast<const int32_t*>(cm + o_ct);
-        }
-      }
-    }
-  }
-  *owned_c = cmem;
-  (void)hipFree(tmp);
-  if (rc != hipSuccess) { set_error("building a pass's copy failed: %s", hipGetErrorString(rc)); (void)hipFree(mem); if (cmem) (void)hipFree(cmem); *owned_c = nullptr; return GDMIX_RE_EHIP; }
-  out->ent = packed ? pent : nullptr;
-  out->key = ckey; out->val = cval; out->loc = cloc; out->kbase = kbase; out->ustart = ustart; out->ublock = ublock; out->ufirst = ufirst;
-  out->part = nullptr;
-  out->nblock = nblock;
-  out->nunit = nunit;
-  out->order = reinterpret_cast<const int32_t*>(cb + c_ord);
-  out->nlaunch = (int)order.size();
-  *owned = mem;
-  return GDMIX_RE_OK;
-}
-
-static void fe_free(gdmix_fe_problem* p) {
-  for (auto& e : p->ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : p->ring_ev) if (e) (void)hipEventDestroy(e);
-  if (p->status_ring) (void)hipHostFree(p->status_ring);
-  if (p->pool) (void)hipFree(p->pool);
-  for (auto& c : p->copies) if (c) (void)hipFree(c);
-  for (auto& c : p->ccopies) if (c) (void)hipFree(c);
-  if (p->hot_mem) (void)hipFree(p->hot_mem);
-  if (p->prior_mem) (void)hipFree(p->prior_mem);
-  delete p;
-}
-
-// The column pass's copy, frequent columns under their virtual numbers (FeHot above). Entry counts per column come from the
-// packed shard's column pointers (one read-back at creation).
-static int fe_split_hot(gdmix_fe_problem* p, const gdmix_re_packed* b, hipStream_t s) {
-  FeDev& F = p->F;
-  gdmix_ctx_impl* ci = &p->ctx->impl;
-  F.hot = FeHot{0, 0, nullptr};
-  long hot_min = 1 << 16;
-  if (const char* e = getenv("GDMIX_FE_HOT_MIN")) hot_min = atol(e);   // test hook (0 = no frequent columns)
-  std::vector<int32_t> cp((size_t)F.d + 1), hot_cols;
-  if (hot_min > 0 && F.d > 0 && F.z > 0) {
-    HIP_TRY(hipMemcpyAsync(cp.data(), b->col_ptr, ((size_t)F.d + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    std::vector<std::pair<int32_t, int32_t>> cand;   // (-count, column): most frequent first, ties by column
-    for (int c = 0; c < F.d; ++c)
-      if (cp[(size_t)c + 1] - cp[(size_t)c] >= hot_min) cand.emplace_back(-(cp[(size_t)c + 1] - cp[(size_t)c]), c);
-    std::sort(cand.begin(), cand.end());
-    if (cand.size() > (size_t)FE_HOT_MAX) cand.resize(FE_HOT_MAX);
-    for (auto& q : cand) hot_cols.push_back(q.second);
-    std::sort(hot_cols.begin(), hot_cols.end());
-  }
-  if (hot_cols.empty())
-    return fe_build_copy(s, ci->num_cus, b->row_ptr, F.n, b->csr_col, b->csr_val, F.z, F.d, true, (p->compress & 2) != 0, &F.cc, &p->copies[1],
-                         &p->ccopies[1], &p->uf_c);
-  const int nh = (int)hot_cols.size();
-  const int vbase = (F.d + FE_B - 1) / FE_B * FE_B;
-  std::vector<int32_t> hotmap((size_t)F.d, -1);
-  for (int h = 0; h < nh; ++h) hotmap[(size_t)hot_cols[(size_t)h]] = h;
-  const size_t zz = (size_t)F.z;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off = up256(off + bytes); return r; };
-  const size_t o_map = take((size_t)F.d * 4), o_col2 = take(zz * 4);
-  void* mem = nullptr;
-  hipError_t rc = hipMalloc(&mem, off);
-  if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", off, hipGetErrorString(rc)); return GDMIX_RE_ENOMEM; }
-  void* small = nullptr;
-  rc = hipMalloc(&small, (size_t)nh * 4);
-  if (rc != hipSuccess) { (void)hipFree(mem); set_error("hipMalloc failed: %s", hipGetErrorString(rc)); return GDMIX_RE_ENOMEM; }
-  p->hot_mem = small;                                  // freed with the problem
-  char* m = static_cast<char*>(mem);
-  int32_t* col2 = reinterpret_cast<int32_t*>(m + o_col2);
-  rc = hipMemcpyAsync(m + o_map, hotmap.data(), (size_t)F.d * 4, hipMemcpyHostToDevice, s);
-  if (rc == hipSuccess) rc = hipMemcpyAsync(small, hot_cols.data(), (size_t)nh * 4, hipMemcpyHostToDevice, s);
-  if (rc == hipSuccess) {
-    int g = (F.n + 255) / 256;
-    if (g > ci->num_cus * 32) g = ci->num_cus * 32;
-    hipLaunchKernelGGL(fe_hot_remap_kernel, dim3(g), dim3(256), 0, s, b->row_ptr, F.n, b->csr_col, reinterpret_cast<const int32_t*>(m + o_map), vbase, col2);
-    rc = hipStreamSynchronize(s);                      // (also: the host vectors above are done with)
-  }
-  if (rc != hipSuccess) { (void)hipFree(mem); set_error("frequent-column tables: %s", hipGetErrorString(rc)); return GDMIX_RE_EHIP; }
-  const int rc2 = fe_build_copy(s, ci->num_cus, b->row_ptr, F.n, col2, b->csr_val, F.z, vbase + nh * FE_HOT_REP, true, (p->compress & 2) != 0, &F.cc,
-                                &p->copies[1], &p->ccopies[1], &p->uf_c);
-  (void)hipFree(mem);
-  if (rc2 != GDMIX_RE_OK) return rc2;
-  F.hot.n = nh;
-  F.hot.vbase = vbase;
-  F.hot.col = static_cast<const int32_t*>(small);
-  return GDMIX_RE_OK;
+// The test hooks of include/gdmix_fe.h, read once per problem (the top of gdmix_fe_create); a value out of range is no value.
+static FeHooks fe_hooks_from_env() {
+  FeHooks h;
+  if (const char* e = getenv("GDMIX_FE_CHUNK")) { const long v = atol(e); if (v >= 64) h.chunk = v; }
+  if (const char* e = getenv("GDMIX_FE_WINDOW_BITS")) { const int v = atoi(e); if (v >= 1 && v < FE_SPAN_BITS) h.window_bits = v; }
+  if (const char* e = getenv("GDMIX_FE_PACK")) h.pack = atoi(e) != 0;
+  if (const char* e = getenv("GDMIX_FE_HOT_MIN")) h.hot_min = atol(e);
+  if (const char* e = getenv("GDMIX_FE_COMPRESS")) h.compress = atoi(e) & 3;
+  if (const char* e = getenv("GDMIX_FE_FUSED_TAIL")) h.fused_tail = e[0] != '0';
+  return h;
 }
 
 // prior: x of F is phi (a prior is installed and the pass runs at the solver's point): the row pass reads theta = mu + s (.) phi
@@ -1363,31 +818,25 @@ static int fe_passes(gdmix_fe_problem* p, const FeDev& F, hipStream_t s, bool ti
   // features absent from this shard must read 0 in the reduce buffer; fe_dots_kernel leaves it cleared behind a step
   if (p->dirty) HIP_TRY(hipMemsetAsync(F.fg, 0, ((size_t)F.P + 1) * 8, s));
   p->dirty = true;
-  int gd = (F.d + 255) / 256;
-  if (gd > 2048) gd = 2048;
-  if (gd < 1) gd = 1;
   // xl (x in the shard's local order) is kept current by the step's update (fe_update_one); the Hessian passes may run at
   // another point: they gather it themselves and put the solver's back afterwards
-  if (HESS && prior) hipLaunchKernelGGL(fe_prepare_kernel<true>, dim3(gd), dim3(256), 0, s, F);
-  else if (HESS) hipLaunchKernelGGL(fe_prepare_kernel<false>, dim3(gd), dim3(256), 0, s, F);
+  const auto prepare = [&](const FeDev& G, bool with_prior) {
+    with_flag(with_prior, [&](auto PR) { hipLaunchKernelGGL(fe_prepare_kernel<decltype(PR)::value>, dim3(grid_for(G.d, 256, 2048)), dim3(256), 0, s, G); });
+  };
+  if (HESS) prepare(F, prior);
   if (timed) HIP_TRY(hipEventRecord(p->ev[0], s));
-  if (prior) {
-    if (F.rc.ent) hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, true, true>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
-    else hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, false, true>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
-    if (F.nmulti) hipLaunchKernelGGL((fe_rows_fix_kernel<HESS, true>), dim3(F.nmulti * FE_FIX_PER_BLOCK), dim3(FE_THREADS), 0, s, F, p->o);
-  } else {
-    if (F.rc.ent) hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, true>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
-    else hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, false>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o);
-    if (F.nmulti) hipLaunchKernelGGL((fe_rows_fix_kernel<HESS>), dim3(F.nmulti * FE_FIX_PER_BLOCK), dim3(FE_THREADS), 0, s, F, p->o);
-  }
+  with_flag(prior, [&](auto PR) {
+    constexpr bool PRIOR = decltype(PR)::value;
+    with_flag(F.rc.ent != nullptr, [&](auto PK) { hipLaunchKernelGGL((fe_scatter_kernel<true, HESS, decltype(PK)::value, PRIOR>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, p->o); });
+    if (F.nmulti) hipLaunchKernelGGL((fe_rows_fix_kernel<HESS, PRIOR>), dim3(F.nmulti * FE_FIX_PER_BLOCK), dim3(FE_THREADS), 0, s, F, p->o);
+  });
   if (timed) HIP_TRY(hipEventRecord(p->ev[1], s));
-  if (F.cc.ent) hipLaunchKernelGGL((fe_scatter_kernel<false, HESS, true>), dim3(F.cc.nlaunch), dim3(WAVE), 0, s, F, p->o);
-  else hipLaunchKernelGGL((fe_scatter_kernel<false, HESS, false>), dim3(F.cc.nlaunch), dim3(WAVE), 0, s, F, p->o);
+  // (the column pass gathers residuals: it has no prior variant)
+  with_flag(F.cc.ent != nullptr, [&](auto PK) { hipLaunchKernelGGL((fe_scatter_kernel<false, HESS, decltype(PK)::value>), dim3(F.cc.nlaunch), dim3(WAVE), 0, s, F, p->o); });
   if (timed) HIP_TRY(hipEventRecord(p->ev[2], s));
   int gf = (F.d + FE_RED_OUT - 1) / FE_RED_OUT;
   hipLaunchKernelGGL(fe_finish_kernel<HESS>, dim3((gf < FE_FIN_BLOCKS ? FE_FIN_BLOCKS : gf) + F.hot.n), dim3(FE_THREADS), 0, s, F);
-  if (HESS && p->F.mu) hipLaunchKernelGGL(fe_prepare_kernel<true>, dim3(gd), dim3(256), 0, s, p->F);      // the solver's point back into xl
-  else if (HESS) hipLaunchKernelGGL(fe_prepare_kernel<false>, dim3(gd), dim3(256), 0, s, p->F);
+  if (HESS) prepare(p->F, p->F.mu != nullptr);      // the solver's point back into xl
   HIP_TRY(hipGetLastError());
   return GDMIX_RE_OK;
 }
@@ -1397,20 +846,58 @@ static int fe_passes(gdmix_fe_problem* p, const FeDev& F, hipStream_t s, bool ti
 // written by the same fe_init_kernel, the host's counters put back. Everything is enqueued behind whatever the stream still holds.
 static int fe_reset(gdmix_fe_problem* p, const double* theta0, hipStream_t s) {
   const FeDev& F = p->F;
-  char* base = static_cast<char*>(p->pool);
+  char* base = p->pool.as<char>();
   HIP_TRY(hipMemsetAsync(base, 0, p->pool_multi, s));
   HIP_TRY(hipMemsetAsync(base + p->pool_multi_end, 0, p->pool_bytes - p->pool_multi_end, s));
   HIP_TRY(hipMemsetAsync(base + p->pool_inv, 0xff, (size_t)F.P * 4, s));
-  int gp = (F.P + 255) / 256;
-  if (gp > 1024) gp = 1024;
-  if (F.mu) hipLaunchKernelGGL(fe_init_kernel<true>, dim3(gp), dim3(256), 0, s, F, theta0);
-  else hipLaunchKernelGGL(fe_init_kernel<false>, dim3(gp), dim3(256), 0, s, F, theta0);
+  with_flag(F.mu != nullptr, [&](auto PR) { hipLaunchKernelGGL(fe_init_kernel<decltype(PR)::value>, dim3(grid_for(F.P, 256, 1024)), dim3(256), 0, s, F, theta0); });
   HIP_TRY(hipGetLastError());
   p->timed = false;
   p->dirty = false;
   p->gen = 0u;
   p->seq = 0;
   p->evals = 0;
+  return GDMIX_RE_OK;
+}
+
+// The pool: every vector and partial sum of the problem in one allocation, zeroed (F.inv: -1, the coefficient is not a column of this
+// shard), F's pointers into it, the list of the row blocks with several units. Needs the unit counts of both copies.
+static int fe_make_pool(gdmix_fe_problem* p, const std::vector<int32_t>& multi, int m, hipStream_t s) {
+  FeDev& F = p->F;
+  const size_t P = (size_t)F.P;
+  Arena a;
+  const size_t o_xl = a.take((size_t)(F.d + 1) * 8), o_rs = a.take((size_t)(F.n + 1) * 8), o_fg = a.take((P + 1) * 8);
+  const size_t o_pr = a.take((size_t)F.rc.nunit * FE_B * 8), o_pc = a.take((size_t)F.cc.nunit * FE_B * 8);
+  const size_t o_multi = a.take((multi.size() + 1) * 4), o_red = a.take((size_t)F.nred * 3 * 8 + 16);
+  const size_t o_acc = a.take((size_t)FE_DOT_BLOCKS * COMPACT_KD * 8), o_fin = a.take((size_t)FE_FIN_BLOCKS * 3 * 8 + 64);
+  const size_t o_state = a.take(sizeof(CompactState)), o_plan = a.take(sizeof(CompactPlan)), o_mats = a.take(sizeof(CompactMats));
+  const size_t o_vec = a.take(((size_t)5 * P + compact_hist_doubles((int64_t)P, m)) * 8 + 16), o_status = a.take(64);
+  const size_t o_inv = a.take(P * 4), o_sync = a.take(sizeof(FeSync));
+  const hipError_t rc = p->pool.alloc(a.off);
+  if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", a.off, hipGetErrorString(rc)); return GDMIX_RE_ENOMEM; }
+  p->pool_bytes = a.off; p->pool_multi = o_multi; p->pool_multi_end = o_red; p->pool_inv = o_inv;
+  const DevBuf& pool = p->pool;
+  HIP_TRY(hipMemsetAsync(pool.get(), 0, a.off, s));
+  HIP_TRY(hipMemsetAsync(pool.as<char>(o_inv), 0xff, P * 4, s));
+  F.xl = pool.as<double>(o_xl); F.rs = pool.as<double>(o_rs);
+  F.fg = pool.as<double>(o_fg);
+  F.rc.part = pool.as<double>(o_pr); F.cc.part = pool.as<double>(o_pc);
+  F.multi = pool.as<const int32_t>(o_multi);
+  F.loss_part = pool.as<double>(o_red); F.rsum_part = F.loss_part + F.nred; F.loss_lo_part = F.rsum_part + F.nred;
+  F.acc_part = pool.as<double>(o_acc);
+  F.fin_part = pool.as<double>(o_fin);
+  F.fin_count = pool.as<unsigned>(o_fin + (size_t)FE_FIN_BLOCKS * 3 * 8);
+  F.state = pool.as<CompactState>(o_state);
+  F.plan = pool.as<CompactPlan>(o_plan);
+  F.mats = pool.as<CompactMats>(o_mats);
+  double* v = pool.as<double>(o_vec);
+  F.W.x = v; F.W.g = v + P; F.W.d = v + 2 * P; F.W.t = v + 3 * P; F.W.r = v + 4 * P;
+  F.W.ws = v + 5 * P + ((5 * P) & 1);   // 16-byte aligned: the interleaved history (re_lbfgs_compact.hpp) is read with 16-byte loads
+  F.W.wy = F.W.ws + (size_t)m * P;
+  F.W.rs = F.rs; F.W.alpha = nullptr; F.W.rho = nullptr; F.W.part = nullptr;
+  p->status_dev = pool.as<int32_t>(o_status);
+  F.inv = pool.as<int32_t>(o_inv);
+  F.sync = pool.as<FeSync>(o_sync);
   return GDMIX_RE_OK;
 }
 
@@ -1427,103 +914,46 @@ GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* b, int64
   if (opts->regularize_bias && !opts->has_intercept) { set_error("regularize_bias requires has_intercept"); return GDMIX_RE_EINVAL; }
   if (num_features < 1 || num_features > 0x7ffffff0ll) { set_error("bad num_features"); return GDMIX_RE_EINVAL; }
   if (b->Z > 0x7ffffff0ll || b->N > 0x7ffffff0ll) { set_error("shard exceeds 2^31 samples or non-zeros"); return GDMIX_RE_ERANGE; }
+  const FeHooks hooks = fe_hooks_from_env();
   hipStream_t s = static_cast<hipStream_t>(stream);
   gdmix_ctx_impl* ci = &ctx->impl;
   HIP_TRY(hipSetDevice(ci->device));
   HIP_TRY(join_unique(ci, s));   // the shard's unique_global is read here
-  gdmix_fe_problem* p = new (std::nothrow) gdmix_fe_problem();
+  std::unique_ptr<gdmix_fe_problem> p(new (std::nothrow) gdmix_fe_problem());
   if (!p) { set_error("out of host memory"); return GDMIX_RE_ENOMEM; }
   p->ctx = ctx;
-  p->pool = nullptr;
-  p->copies[0] = p->copies[1] = nullptr;
-  p->ccopies[0] = p->ccopies[1] = nullptr;
-  p->compress = FE_COMPRESS_DEFAULT;
-  if (const char* e = getenv("GDMIX_FE_COMPRESS")) p->compress = atoi(e) & 3;
-  p->hot_mem = nullptr;
-  p->prior_mem = nullptr;
-  p->timed = false;
-  p->dirty = false;      // the pool is zeroed at creation
-  for (auto& e : p->ev) e = nullptr;
-  for (auto& e : p->ring_ev) e = nullptr;
-  p->status_ring = nullptr;
-  p->gen = 0u;
-  p->seq = 0;
-  p->evals = 0;
-  {
-    // the one-launch step has workgroups waiting for the last arriver: next to ANOTHER process's persistent grid neither might get
-    // all its workgroups placed (re_internal.hpp: why this kernel is not behind the inter-process lock). A device that another
-    // process is present on gets the three-launch step; GDMIX_FE_FUSED_TAIL=0 / 1 decides whatever the device looks like.
-    const char* e = getenv("GDMIX_FE_FUSED_TAIL");
-    p->fused_tail = e ? e[0] != '0' : !device_has_another_process(ci->device);
-  }
+  // the one-launch step has workgroups waiting for the last arriver: next to ANOTHER process's persistent grid neither might get
+  // all its workgroups placed (re_internal.hpp: why this kernel is not behind the inter-process lock). A device that another
+  // process is present on gets the three-launch step; GDMIX_FE_FUSED_TAIL=0 / 1 decides whatever the device looks like.
+  p->fused_tail = hooks.fused_tail ? *hooks.fused_tail : !device_has_another_process(ci->device);
   FeDev& F = p->F;
   const int ic = opts->has_intercept ? 1 : 0;
   F.n = (int)b->N; F.z = b->Z; F.d = (int)b->D; F.ic = ic; F.D = num_features; F.P = (int)num_features + ic; F.m = opts->m;
   F.y = b->y; F.o = b->offset; F.w = b->weight; F.umap = b->unique_global;
-  F.mu = nullptr; F.sc = nullptr;
-  SolveParams& o = p->o;
-  o.l2 = opts->l2; o.ftol = opts->ftol; o.pgtol = opts->pgtol; o.threshold = 0.0; o.regularize_bias = opts->regularize_bias;
-  o.has_intercept = ic; o.m = opts->m; o.max_iter = opts->max_iter; o.maxfun = opts->maxfun; o.maxls = opts->maxls;
-  o.variance_mode = 0; o.sum_loss = 1; o.loss = opts->loss;
-  // row pass: outputs = rows, gathered = x by local column: from the column-major arrays. Column pass: the other way round.
-  std::vector<int32_t> uf_r, uf_c;
-  int rc2 = fe_build_copy(s, ci->num_cus, b->col_ptr, F.d, b->csc_row, b->csc_val, F.z, F.n, false, (p->compress & 1) != 0, &F.rc, &p->copies[0],
-                          &p->ccopies[0], &uf_r);
-  if (rc2 == GDMIX_RE_OK) rc2 = fe_split_hot(p, b, s);    // the frequent columns, and the column pass's copy of the others
-  if (rc2 != GDMIX_RE_OK) { fe_free(p); return rc2; }
-  uf_c = p->uf_c;
+  p->o = fe_solve_params(*opts);
+  // row pass: outputs = rows, gathered = x by local column: from the column-major arrays. Column pass: the other way round,
+  // the frequent columns apart.
+  const int compress = hooks.compress.value_or(FE_COMPRESS_DEFAULT);
+  const FeSource rows{b->col_ptr, F.d, b->csc_row, b->csc_val, F.z, F.n, false, (compress & 1) != 0};
+  std::vector<int32_t> uf_r;
+  int rc = fe_build_copy(s, ci->num_cus, hooks, rows, &F.rc, &p->copies[0], &p->ccopies[0], &uf_r);
+  if (rc == GDMIX_RE_OK) rc = fe_build_column_copy(s, ci->num_cus, hooks, b, F.n, F.d, F.z, &F.cc, &F.hot, &p->copies[1], &p->ccopies[1], &p->hot_mem);
+  if (rc != GDMIX_RE_OK) return rc;
   std::vector<int32_t> multi;
   for (int rb = 0; rb < F.rc.nblock; ++rb) if (uf_r[(size_t)rb + 1] - uf_r[(size_t)rb] > 1) multi.push_back(rb);
   F.nmulti = (int)multi.size();
   F.nred = F.rc.nunit + F.nmulti * FE_FIX_PER_BLOCK;
-  const size_t P = (size_t)F.P;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off = up256(off + bytes); return r; };
-  const size_t o_xl = take((size_t)(F.d + 1) * 8), o_rs = take((size_t)(F.n + 1) * 8), o_fg = take((P + 1) * 8);
-  const size_t o_pr = take((size_t)F.rc.nunit * FE_B * 8), o_pc = take((size_t)F.cc.nunit * FE_B * 8);
-  const size_t o_multi = take((multi.size() + 1) * 4), o_red = take((size_t)F.nred * 3 * 8 + 16);
-  const size_t o_acc = take((size_t)FE_DOT_BLOCKS * COMPACT_KD * 8), o_fin = take((size_t)FE_FIN_BLOCKS * 3 * 8 + 64);
-  const size_t o_state = take(sizeof(CompactState)), o_plan = take(sizeof(CompactPlan)), o_mats = take(sizeof(CompactMats));
-  const size_t o_vec = take(((size_t)5 * P + compact_hist_doubles((int64_t)P, opts->m)) * 8 + 16), o_status = take(64);
-  const size_t o_inv = take(P * 4), o_sync = take(sizeof(FeSync));
-  hipError_t rc = hipMalloc(&p->pool, off);
-  if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", off, hipGetErrorString(rc)); fe_free(p); return GDMIX_RE_ENOMEM; }
-  p->pool_bytes = off; p->pool_multi = o_multi; p->pool_multi_end = o_red; p->pool_inv = o_inv;
-  char* base = static_cast<char*>(p->pool);
-  rc = hipMemsetAsync(base, 0, off, s);
-  if (rc == hipSuccess) rc = hipMemsetAsync(base + o_inv, 0xff, P * 4, s);   // -1: the coefficient is not a column of this shard
-  if (rc == hipSuccess) rc = hipHostMalloc(reinterpret_cast<void**>(&p->status_ring), FE_RING * sizeof(int32_t), hipHostMallocDefault);
-  for (auto& e : p->ring_ev) if (rc == hipSuccess) rc = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-  if (rc == hipSuccess && !multi.empty()) {
-    rc = hipMemcpyAsync(base + o_multi, multi.data(), multi.size() * 4, hipMemcpyHostToDevice, s);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(s);   // `multi` goes out of scope
+  rc = fe_make_pool(p.get(), multi, opts->m, s);
+  if (rc != GDMIX_RE_OK) return rc;
+  HIP_TRY(p->status_ring.alloc(FE_RING * sizeof(int32_t)));
+  for (auto& e : p->ring_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (!multi.empty()) {
+    HIP_TRY(hipMemcpyAsync(p->pool.as<char>(p->pool_multi), multi.data(), multi.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));   // `multi` goes out of scope
   }
-  if (rc != hipSuccess) { set_error("initialising the problem failed: %s", hipGetErrorString(rc)); fe_free(p); return GDMIX_RE_EHIP; }
-  F.xl = reinterpret_cast<double*>(base + o_xl); F.rs = reinterpret_cast<double*>(base + o_rs);
-  F.fg = reinterpret_cast<double*>(base + o_fg);
-  F.rc.part = reinterpret_cast<double*>(base + o_pr); F.cc.part = reinterpret_cast<double*>(base + o_pc);
-  F.multi = reinterpret_cast<const int32_t*>(base + o_multi);
-  F.loss_part = reinterpret_cast<double*>(base + o_red); F.rsum_part = F.loss_part + F.nred; F.loss_lo_part = F.rsum_part + F.nred;
-  F.acc_part = reinterpret_cast<double*>(base + o_acc);
-  F.fin_part = reinterpret_cast<double*>(base + o_fin);
-  F.fin_count = reinterpret_cast<unsigned*>(base + o_fin + (size_t)FE_FIN_BLOCKS * 3 * 8);
-  F.state = reinterpret_cast<CompactState*>(base + o_state);
-  F.plan = reinterpret_cast<CompactPlan*>(base + o_plan);
-  F.mats = reinterpret_cast<CompactMats*>(base + o_mats);
-  double* v = reinterpret_cast<double*>(base + o_vec);
-  F.W.x = v; F.W.g = v + P; F.W.d = v + 2 * P; F.W.t = v + 3 * P; F.W.r = v + 4 * P;
-  F.W.ws = v + 5 * P + ((5 * P) & 1);   // 16-byte aligned: the interleaved history (re_lbfgs_compact.hpp) is read with 16-byte loads
-  F.W.wy = F.W.ws + (size_t)opts->m * P;
-  F.W.rs = F.rs; F.W.alpha = nullptr; F.W.rho = nullptr; F.W.part = nullptr;
-  p->status_dev = reinterpret_cast<int32_t*>(base + o_status);
-  F.inv = reinterpret_cast<int32_t*>(base + o_inv);
-  F.sync = reinterpret_cast<FeSync*>(base + o_sync);
-  int gp = (int)((P + 255) / 256);
-  if (gp > 1024) gp = 1024;
-  hipLaunchKernelGGL(fe_init_kernel<false>, dim3(gp), dim3(256), 0, s, F, theta0);
-  rc = hipGetLastError();
-  if (rc != hipSuccess) { set_error("launch failed: %s", hipGetErrorString(rc)); fe_free(p); return GDMIX_RE_EHIP; }
-  *out = p;
+  hipLaunchKernelGGL(fe_init_kernel<false>, dim3(grid_for(F.P, 256, 1024)), dim3(256), 0, s, F, theta0);
+  HIP_TRY(hipGetLastError());
+  *out = p.release();
   return GDMIX_RE_OK;
 }
 
@@ -1539,9 +969,7 @@ GDMIX_API int gdmix_fe_restart(gdmix_fe_problem* p, const gdmix_re_opts* opts, c
   if (opts->regularize_bias && !opts->has_intercept) { set_error("regularize_bias requires has_intercept"); return GDMIX_RE_EINVAL; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(p->ctx->impl.device));
-  SolveParams& o = p->o;
-  o.l2 = opts->l2; o.ftol = opts->ftol; o.pgtol = opts->pgtol; o.regularize_bias = opts->regularize_bias;
-  o.max_iter = opts->max_iter; o.maxfun = opts->maxfun; o.maxls = opts->maxls;
+  p->o = fe_solve_params(*opts);      // (has_intercept, m and loss are the creation's: checked above)
   return fe_reset(p, theta0, s);
 }
 
@@ -1557,30 +985,27 @@ GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const 
   }
   const size_t P = (size_t)F.P;
   if (!p->prior_mem) {
-    void* mem = nullptr;
-    const hipError_t rc = hipMalloc(&mem, 2 * P * 8 + 64);
+    const hipError_t rc = p->prior_mem.alloc(2 * P * 8 + 64);
     if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", 2 * P * 8 + 64, hipGetErrorString(rc)); return GDMIX_RE_ENOMEM; }
-    p->prior_mem = static_cast<double*>(mem);
   }
+  double* prior = p->prior_mem.as<double>();
   // the caller's scale is checked before the problem's copy — a prior an earlier call installed — is overwritten
-  int32_t* bad_dev = reinterpret_cast<int32_t*>(p->prior_mem + 2 * P);
-  int gp = (F.P + 255) / 256;
-  if (gp > 1024) gp = 1024;
+  int32_t* bad_dev = reinterpret_cast<int32_t*>(prior + 2 * P);
   HIP_TRY(hipMemsetAsync(bad_dev, 0, sizeof(int32_t), s));
-  hipLaunchKernelGGL(fe_prior_check_kernel, dim3(gp), dim3(256), 0, s, scale, F.P, bad_dev);
+  hipLaunchKernelGGL(fe_prior_check_kernel, dim3(grid_for(F.P, 256, 1024)), dim3(256), 0, s, scale, F.P, bad_dev);
   HIP_TRY(hipGetLastError());
   int32_t bad = 0;
   HIP_TRY(hipMemcpyAsync(&bad, bad_dev, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));      // the one wait of this call
   if (bad) { set_error("gdmix_fe_set_prior: every scale must be finite and > 0"); return GDMIX_RE_EINVAL; }
-  HIP_TRY(hipMemcpyAsync(p->prior_mem, mean, P * 8, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(p->prior_mem + P, scale, P * 8, hipMemcpyDeviceToDevice, s));
-  F.mu = p->prior_mem; F.sc = p->prior_mem + P;
+  HIP_TRY(hipMemcpyAsync(prior, mean, P * 8, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(prior + P, scale, P * 8, hipMemcpyDeviceToDevice, s));
+  F.mu = prior; F.sc = prior + P;
   return fe_reset(p, nullptr, s);
 }
 
 GDMIX_API void gdmix_fe_destroy(gdmix_fe_problem* p) {
-  if (p) fe_free(p);
+  delete p;
 }
 
 GDMIX_API double* gdmix_fe_reduce_buffer(gdmix_fe_problem* p, int64_t* count) {
@@ -1649,28 +1074,26 @@ GDMIX_API int gdmix_fe_variance_of_hessian(gdmix_re_ctx* ctx, double* H, int64_t
 
 static int fe_enqueue_step(gdmix_fe_problem* p, hipStream_t s) {
   const FeDev& F = p->F;
-  int gp = (F.P + 255) / 256;
-  const int dot_blocks = gp < FE_DOT_BLOCKS ? gp : FE_DOT_BLOCKS;
+  const int dot_blocks = grid_for(F.P, 256, FE_DOT_BLOCKS);
+  const int tail_blocks = grid_for(dot_blocks, 1, p->ctx->impl.num_cus);      // at most one workgroup per CU: all resident, the wait inside cannot starve one
   if (p->fused_tail) {
-    int g = p->ctx->impl.num_cus;          // at most one workgroup per CU: all resident, the wait inside cannot starve one
-    if (g > dot_blocks) g = dot_blocks;
-    if (g < 1) g = 1;
     ++p->gen;
     if (p->gen == 0u) ++p->gen;
-    if (F.mu) hipLaunchKernelGGL(fe_tail_kernel<true>, dim3(g), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev, p->gen);
-    else hipLaunchKernelGGL(fe_tail_kernel<false>, dim3(g), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev, p->gen);
-  } else {
-    if (F.mu) hipLaunchKernelGGL(fe_dots_kernel<true>, dim3(dot_blocks), dim3(FE_THREADS), 0, s, F, p->o);
-    else hipLaunchKernelGGL(fe_dots_kernel<false>, dim3(dot_blocks), dim3(FE_THREADS), 0, s, F, p->o);
-    hipLaunchKernelGGL(fe_step_kernel, dim3(1), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev);
-    if (gp > 1024) gp = 1024;
-    if (F.mu) hipLaunchKernelGGL(fe_update_kernel<true>, dim3(gp), dim3(256), 0, s, F, p->o.m);
-    else hipLaunchKernelGGL(fe_update_kernel<false>, dim3(gp), dim3(256), 0, s, F, p->o.m);
   }
+  with_flag(F.mu != nullptr, [&](auto PR) {
+    constexpr bool PRIOR = decltype(PR)::value;
+    if (p->fused_tail) {
+      hipLaunchKernelGGL(fe_tail_kernel<PRIOR>, dim3(tail_blocks), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev, p->gen);
+    } else {
+      hipLaunchKernelGGL(fe_dots_kernel<PRIOR>, dim3(dot_blocks), dim3(FE_THREADS), 0, s, F, p->o);
+      hipLaunchKernelGGL(fe_step_kernel, dim3(1), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev);
+      hipLaunchKernelGGL(fe_update_kernel<PRIOR>, dim3(grid_for(F.P, 256, 1024)), dim3(256), 0, s, F, p->o.m);
+    }
+  });
   p->dirty = false;
   HIP_TRY(hipGetLastError());
   const int slot = (int)(p->seq % FE_RING);
-  HIP_TRY(hipMemcpyAsync(p->status_ring + slot, p->status_dev, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(p->status_ring.as<int32_t>() + slot, p->status_dev, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipEventRecord(p->ring_ev[slot], s));
   ++p->seq;
   return GDMIX_RE_OK;
@@ -1698,7 +1121,7 @@ GDMIX_API int gdmix_fe_step_status(gdmix_fe_problem* p, int64_t seq, int32_t* st
   }
   const int slot = (int)(seq % FE_RING);
   HIP_TRY(hipEventSynchronize(p->ring_ev[slot]));
-  *status = p->status_ring[slot];
+  *status = p->status_ring.as<int32_t>()[slot];
   return GDMIX_RE_OK;
 }
 
@@ -1733,9 +1156,7 @@ GDMIX_API int gdmix_fe_result(gdmix_fe_problem* p, double* theta, double* fval, 
   if (!p) { set_error("problem is NULL"); return GDMIX_RE_EINVAL; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (theta && p->F.mu) {
-    int gp = (p->F.P + 255) / 256;
-    if (gp > 1024) gp = 1024;
-    hipLaunchKernelGGL(fe_prior_theta_kernel, dim3(gp), dim3(256), 0, s, p->F, theta);
+    hipLaunchKernelGGL(fe_prior_theta_kernel, dim3(grid_for(p->F.P, 256, 1024)), dim3(256), 0, s, p->F, theta);
     HIP_TRY(hipGetLastError());
   } else if (theta) {
     HIP_TRY(hipMemcpyAsync(theta, p->F.W.x, (size_t)p->F.P * 8, hipMemcpyDeviceToDevice, s));

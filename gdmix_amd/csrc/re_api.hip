@@ -818,11 +818,7 @@ GDMIX_API int gdmix_re_solve(gdmix_re_ctx* ctx, const gdmix_re_packed* b, const 
   rc = route(ci, b, tab, opts, s, &hc);
   if (rc != GDMIX_RE_OK) return rc;
 
-  SolveParams P;
-  P.l2 = opts->l2; P.ftol = opts->ftol; P.pgtol = opts->pgtol; P.threshold = opts->threshold;
-  P.regularize_bias = opts->regularize_bias; P.has_intercept = opts->has_intercept ? 1 : 0; P.m = opts->m; P.max_iter = opts->max_iter;
-  P.maxfun = opts->maxfun; P.maxls = opts->maxls; P.variance_mode = opts->variance_mode;
-  P.sum_loss = opts->sum_loss ? 1 : 0; P.loss = opts->loss;
+  const SolveParams P = solve_params(*opts);
   const BatchDev B = batch_dev(b);
   const OutDev O{out->theta, out->theta_thr, out->variance, out->fval, out->gnorm, out->nit, out->nfev, out->status};
   for (int c = 0; c < GDMIX_RE_NUM_CLASSES; ++c) ci->ev_used[c] = false;
@@ -874,11 +870,8 @@ GDMIX_API int gdmix_re_variance_full(gdmix_re_ctx* ctx, const gdmix_re_packed* b
   if (b->E == 0) return GDMIX_RE_OK;
   HIP_TRY(hipSetDevice(ctx->impl.device));
   HIP_TRY(join_unique(&ctx->impl, static_cast<hipStream_t>(stream)));
-  SolveParams P;
-  P.l2 = opts->l2; P.ftol = opts->ftol; P.pgtol = opts->pgtol; P.threshold = opts->threshold;
-  P.regularize_bias = opts->regularize_bias; P.has_intercept = opts->has_intercept ? 1 : 0; P.m = opts->m; P.max_iter = opts->max_iter;
-  P.maxfun = opts->maxfun; P.maxls = opts->maxls; P.variance_mode = GDMIX_RE_VAR_FULL;
-  P.sum_loss = 0; P.loss = opts->loss;
+  SolveParams P = solve_params(*opts);
+  P.variance_mode = GDMIX_RE_VAR_FULL; P.sum_loss = 0;
   return run_variance_full(ctx, b, batch_dev(b), P, theta, variance, static_cast<hipStream_t>(stream));
 }
 

@@ -437,6 +437,67 @@ inline hipError_t with_loss(int code, F&& f) {
     default: return hipErrorInvalidValue;
   }
 }
+// ... and where a run-time flag becomes a kernel's bool argument (the fixed effect's PRIOR and PACKED): f(std::bool_constant<flag>{})
+template <class F>
+inline void with_flag(bool flag, F&& f) {
+  if (flag) f(std::bool_constant<true>{});
+  else f(std::bool_constant<false>{});
+}
+// workgroups of per_block threads for a grid-stride loop over count items: at least one, at most cap
+inline int grid_for(int64_t count, int per_block, int cap) {
+  const int64_t g = (count + per_block - 1) / per_block;
+  return g > cap ? cap : (g < 1 ? 1 : (int)g);
+}
+// The solver's options as the kernels take them. The fixed effect (fe_solve.hip) has no threshold and no variance inside a solve, and
+// its objective is the sum over the samples.
+inline SolveParams solve_params(const gdmix_re_opts& o) {
+  SolveParams P;
+  P.l2 = o.l2; P.ftol = o.ftol; P.pgtol = o.pgtol; P.threshold = o.threshold;
+  P.regularize_bias = o.regularize_bias; P.has_intercept = o.has_intercept ? 1 : 0; P.m = o.m; P.max_iter = o.max_iter;
+  P.maxfun = o.maxfun; P.maxls = o.maxls; P.variance_mode = o.variance_mode;
+  P.sum_loss = o.sum_loss ? 1 : 0; P.loss = o.loss;
+  return P;
+}
+inline SolveParams fe_solve_params(const gdmix_re_opts& o) {
+  SolveParams P = solve_params(o);
+  P.threshold = 0.0; P.variance_mode = 0; P.sum_loss = 1;
+  return P;
+}
+
+// Move-only owner of one hipMalloc block (PINNED: of one page-locked hipHostMalloc block), released in the destructor.
+template <bool PINNED>
+class HipBuf {
+ public:
+  HipBuf() = default;
+  HipBuf(HipBuf&& o) noexcept : p_(o.release()) {}
+  HipBuf& operator=(HipBuf&& o) noexcept {
+    if (this != &o) { reset(); p_ = o.release(); }
+    return *this;
+  }
+  HipBuf(const HipBuf&) = delete;
+  HipBuf& operator=(const HipBuf&) = delete;
+  ~HipBuf() { reset(); }
+  hipError_t alloc(size_t bytes) {      // (what the owner held before is released first)
+    reset();
+    const hipError_t rc = PINNED ? hipHostMalloc(&p_, bytes, hipHostMallocDefault) : hipMalloc(&p_, bytes);
+    if (rc != hipSuccess) p_ = nullptr;
+    return rc;
+  }
+  void* get() const { return p_; }
+  template <class T>
+  T* as(size_t byte_offset = 0) const { return reinterpret_cast<T*>(static_cast<char*>(p_) + byte_offset); }
+  explicit operator bool() const { return p_ != nullptr; }
+  void* release() { void* p = p_; p_ = nullptr; return p; }
+  void reset() {
+    if (p_) (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+    p_ = nullptr;
+  }
+ private:
+  void* p_ = nullptr;
+};
+using DevBuf = HipBuf<false>;
+using PinnedBuf = HipBuf<true>;
+
 hipError_t launch_variance_simple(const BatchDev& B, const SolveParams& o, const double* theta, double* variance, int begin, int count,
                                   double* scratch, size_t slot_doubles, int slots, hipStream_t s);
 hipError_t launch_variance_full(const BatchDev& B, int64_t E, const SolveParams& o, const double* theta, double* variance,

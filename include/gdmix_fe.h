@@ -47,9 +47,10 @@ typedef struct gdmix_fe_problem gdmix_fe_problem;
  * is the library's own (<= 0.98 ulp) and IEEE at the ends; gdmix_fe_score is unchanged (the margin z, never exp(z)).
  * The problem builds its own two copies of the non-zeros (8 B per non-zero each, 10 B when a unit of a pass spans more than 2^21
  * elements; temporary: 40 B per non-zero) and keeps reading the shard's y / offset / weight / unique_global, which must outlive it.
- * Synchronises the stream. Test hooks (environment): GDMIX_FE_CHUNK = entries per unit of a pass, GDMIX_FE_PACK=0 = the
- * three-array form of the entries, GDMIX_FE_COMPRESS = which passes may read units in the 6-byte form (bit 0 rows, bit 1 columns;
- * default 2). */
+ * Synchronises the stream. Test hooks (environment; read when a problem is created and at no other time — a problem keeps what it
+ * was created under, whatever the environment holds when it is restarted or solved): GDMIX_FE_CHUNK = entries per unit of a pass,
+ * GDMIX_FE_PACK=0 = the three-array form of the entries, GDMIX_FE_COMPRESS = which passes may read units in the 6-byte form (bit 0
+ * rows, bit 1 columns; default 2); GDMIX_FE_WINDOW_BITS, GDMIX_FE_HOT_MIN and GDMIX_FE_FUSED_TAIL likewise. */
 GDMIX_API int gdmix_fe_create(gdmix_re_ctx* ctx, const gdmix_re_packed* shard, int64_t num_features,
                               const gdmix_re_opts* opts, const double* theta0, gdmix_fe_problem** out, void* stream);
 GDMIX_API void gdmix_fe_destroy(gdmix_fe_problem* p);

@@ -181,6 +181,22 @@ def test_one_launch_step_and_look_ahead_give_the_bits_of_the_plain_loop(device_s
         assert np.array_equal(th_v, ref[0]) and np.all(info_v["variances"] > 0)
 
 
+def _zipf_shard():
+    """9 000 samples of up to 23 entries (three of 3 000) over 7 000 features, feature j with probability ~ 1 / (j + 1): several row and
+    column blocks, a frequent feature, empty rows and features that never occur."""
+    rng = np.random.default_rng(11)
+    n, D = 9000, 7000
+    k = rng.integers(0, 24, n)
+    k[rng.integers(0, n, 3)] = 3000
+    rp = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
+    cols = np.minimum((float(D + 1) ** rng.random(rp[-1])).astype(np.int64) - 1, D - 1)     # feature j with probability ~ 1/(j+1)
+    vals = (rng.standard_normal(rp[-1]) * 0.3).astype(np.float32)
+    y = (rng.random(n) < 0.3).astype(np.float32)
+    off = (0.2 * rng.standard_normal(n)).astype(np.float32)
+    wt = (0.5 + rng.random(n)).astype(np.float32)
+    return n, D, k, rp, cols, vals, y, off, wt
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("compress", ["3", "0"])
 @pytest.mark.parametrize("chunk,pack,hot,window", [(None, "1", None, None), ("8192", "1", None, None), ("257", "1", None, None),
@@ -213,16 +229,7 @@ def test_passes_cut_into_units_are_deterministic_and_agree(device_solver, monkey
     # read in the 6-byte form (values + 16-bit {delta, accumulator} words, keys rebuilt by a wavefront scan); the sparse blocks of
     # this Zipf-distributed shard keep the 8-byte form, units of 257 entries are mostly padding and keep it too: both forms in one launch
     monkeypatch.setenv("GDMIX_FE_COMPRESS", compress)
-    rng = np.random.default_rng(11)
-    n, D = 9000, 7000
-    k = rng.integers(0, 24, n)
-    k[rng.integers(0, n, 3)] = 3000
-    rp = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
-    cols = np.minimum((float(D + 1) ** rng.random(rp[-1])).astype(np.int64) - 1, D - 1)     # feature j with probability ~ 1/(j+1)
-    vals = (rng.standard_normal(rp[-1]) * 0.3).astype(np.float32)
-    y = (rng.random(n) < 0.3).astype(np.float32)
-    off = (0.2 * rng.standard_normal(n)).astype(np.float32)
-    wt = (0.5 + rng.random(n)).astype(np.float32)
+    n, D, k, rp, cols, vals, y, off, wt = _zipf_shard()
     s = fe.FixedEffectDeviceSolver(solver=device_solver)
     kw = dict(offset=off, weight=wt, l2=1.5, regularize_bias=False, max_iter=40)
     th1, info1 = s.fit_stepping(rp, cols, vals, y, D, **kw)
@@ -244,6 +251,39 @@ def test_passes_cut_into_units_are_deterministic_and_agree(device_solver, monkey
     d = rho * (1 - rho) * wt
     H = np.concatenate([np.bincount(cols, weights=vals.astype(np.float64) ** 2 * d[rows], minlength=D) + 1.5, [d.sum()]])
     np.testing.assert_allclose(info3["variances"], 1.0 / (H + 1e-12), rtol=1e-10)
+
+
+@pytest.mark.gpu
+def test_the_test_hooks_belong_to_creation(device_solver, monkeypatch):
+    """The GDMIX_FE_* test hooks are read when a problem is created (include/gdmix_fe.h) and at no other time: a problem created with
+    GDMIX_FE_CHUNK=257, GDMIX_FE_PACK=0 and GDMIX_FE_HOT_MIN=300 set, restarted and solved after they have left the environment, gives
+    the bits — coefficients, value, nit, nfev, the bytes either pass streams — of one that had them set throughout. That the hooks
+    took effect at all shows in the streamed bytes: the three-array form is 10 bytes per entry of the row pass, not 8."""
+    n, D, k, rp, cols, vals, y, off, wt = _zipf_shard()
+    for name in ("GDMIX_FE_WINDOW_BITS", "GDMIX_FE_COMPRESS", "GDMIX_FE_FUSED_TAIL"):
+        monkeypatch.delenv(name, raising=False)
+    hooks = {"GDMIX_FE_CHUNK": "257", "GDMIX_FE_PACK": "0", "GDMIX_FE_HOT_MIN": "300"}
+    batch, _ = fe.shard_as_batch(rp, cols, vals, y, off, wt, True, dummy=False)
+    packed = device_solver.pack(batch, has_intercept=True)
+    opts = SolverOptions(l2=1.5, regularize_bias=False, has_intercept=True, m=10, max_iter=40, threshold=0.0, sum_loss=True)
+
+    def run(at_creation, afterwards):
+        for name, v in hooks.items():
+            monkeypatch.setenv(name, v) if at_creation else monkeypatch.delenv(name, raising=False)
+        prob = fe._SteppingProblem(device_solver, packed, D, opts, None)
+        for name, v in hooks.items():
+            monkeypatch.setenv(name, v) if afterwards else monkeypatch.delenv(name, raising=False)
+        prob.restart(opts)
+        status, _ = prob.solve()
+        theta, info = prob.result()
+        out = (theta, status, info["fval"], info["nit"], info["nfev"], prob.stream_bytes())
+        prob.close()
+        return out
+
+    kept, dropped, never = run(True, True), run(True, False), run(False, False)
+    assert kept[1] >= 0 and kept[3] > 5 and np.abs(kept[0]).max() > 0
+    assert np.array_equal(dropped[0], kept[0]) and dropped[1:] == kept[1:]
+    assert never[5][0] > 0 and kept[5][0] * 8 == never[5][0] * 10
 
 
 @pytest.mark.gpu

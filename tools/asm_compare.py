@@ -118,20 +118,21 @@ def main():
             same = diff = moved = 0
             for k in fo:
                 k2 = k if k in fn else new_by_key.get(do[k])      # same symbol, or the symbol that gained its `false`
+                f2, m2 = fn, mn
                 if k2 is None and (k in fn_all or do[k] in moved_by_key):
                     k2 = k if k in fn_all else moved_by_key[do[k]]
                     print(f"{unit}: {do[k]} is in another unit now")
                     moved += 1
-                    fn, mn = {**fn_all, **fn}, {**mn_all, **mn}
+                    f2, m2 = fn_all, mn_all
                 if k2 is None:
                     print(f"{unit}: MISSING {do[k]}")
                     bad += 1
-                elif fo[k] == fn[k2] and mo.get(k) == mn.get(k2):
+                elif fo[k] == f2[k2] and mo.get(k) == m2.get(k2):
                     same += 1
                 else:
-                    print(f"{unit}: DIFFERENT {do[k]} ({len(fo[k])} -> {len(fn[k2])} lines)")
+                    print(f"{unit}: DIFFERENT {do[k]} ({len(fo[k])} -> {len(f2[k2])} lines)")
                     if a.diff:
-                        print("\n".join(difflib.unified_diff(fo[k] + mo.get(k, "").splitlines(), fn[k2] + mn.get(k2, "").splitlines(), "other", "this tree", lineterm="", n=1)))
+                        print("\n".join(difflib.unified_diff(fo[k] + mo.get(k, "").splitlines(), f2[k2] + m2.get(k2, "").splitlines(), "other", "this tree", lineterm="", n=1)))
                     diff += 1
                     bad += 1
             print(f"{unit}: {same} identical, {diff} different, {len(new[unit][0]) - same - diff + moved} only in this tree")
