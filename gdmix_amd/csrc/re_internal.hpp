@@ -324,6 +324,10 @@ struct gdmix_ctx_impl {
   int eval_small_set, eval_small_max;   // gdmix_re_set_eval_small_max was called / its value (otherwise 64)
   void* eval_tmp;                       // device: grow-only temporary storage of the sort and the prefix sum
   size_t eval_tmp_bytes;
+  // down-sampling (re_downsample.hip): the workspace, the row count and the totals of the last gdmix_re_downsample_plan of this context,
+  // so that gdmix_re_downsample_apply can refuse counts that are not that plan's (ds_plan_ws == nullptr: no plan yet)
+  const void* ds_plan_ws;
+  int64_t ds_plan_rows, ds_plan_kept, ds_plan_nnz;
 };
 
 // A few bytes from the device to the host WITHOUT a stream synchronise (round 5). The counts a pack or a solve decides its next

@@ -75,6 +75,12 @@ class FixedLRParams(LRParams):
     # normalised units, the factors from exact column statistics of all workers' training data (all-reduced integers)
     feature_normalization: Optional[str] = None
     feature_statistics_file: Optional[str] = None
+    # not in the reference: Photon-ML's downSamplingRate. The solver's training shard is down-sampled on the device (include/gdmix_re.h,
+    # "down-sampling"): a row is kept by a hash of (seed, uid) with probability `rate` and then weighs 1 / rate; a logistic stage keeps
+    # every positive as it is. Scores, metrics, feature statistics and validation data see every row. 1.0: no sampling. The random-effect
+    # stage has no such flag.
+    down_sampling_rate: float = 1.0
+    down_sampling_seed: int = 0
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -84,9 +90,20 @@ class FixedLRParams(LRParams):
         """The value of --feature_normalization ("none" without the flag)."""
         return "none" if self.feature_normalization is None else self.feature_normalization
 
+    def down_sampling_given(self):
+        """Was one of the two down-sampling flags set to something other than its default?"""
+        return self.down_sampling_rate != 1.0 or self.down_sampling_seed != 0
+
     def __post_init__(self):
         super().__post_init__()
         self.l2_grid()      # a bad list is an error at parse time
+        from .downsample import check_rate
+        try:
+            self.down_sampling_rate = check_rate(self.down_sampling_rate)
+        except TypeError:
+            raise ValueError(f"--down_sampling_rate={self.down_sampling_rate!r} is not a number") from None
+        if isinstance(self.down_sampling_seed, bool) or not isinstance(self.down_sampling_seed, int):
+            raise ValueError(f"--down_sampling_seed={self.down_sampling_seed!r} is not an integer")
         check_feature_normalization(self, (
             (self.incremental_training, "--incremental_training", "prior variances are in the original feature units, and composing the two is not implemented"),
             (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep in normalised units is not implemented")))
@@ -229,6 +246,8 @@ class FixedEffectLRModelLBFGS:
         is formed or a solver created (as sweep.validate does for the random effect). Inference ignores --l2_reg_weights."""
         from . import sweep
         mp = self.model_params
+        if action != constants.ACTION_TRAIN and mp.down_sampling_given():
+            raise ValueError("--down_sampling_rate / --down_sampling_seed sample the training shard of a fit: they do not run with --action=inference")
         grid = mp.l2_grid() if action == constants.ACTION_TRAIN else None
         if grid is not None:
             sweep.refuse_poisson(self.model_type)
@@ -287,6 +306,16 @@ class FixedEffectLRModelLBFGS:
             None if shard is None else shard.vl, data["n"], is_chief=is_chief)
         return factor
 
+    # ---- down-sampling (--down_sampling_rate) -----------------------------------------------------------------------------
+    def _down_sampling(self, data):
+        """fit_stepping's / fit_sweep's down_sampling argument for this stage's training shard: {} at rate 1.0 (the call is skipped)."""
+        mp = self.model_params
+        if mp.down_sampling_rate == 1.0:
+            if mp.down_sampling_seed != 0:
+                logger.warning(f"--down_sampling_seed={mp.down_sampling_seed} has no effect: --down_sampling_rate is 1.0, the stage trains on every row")
+            return {}
+        return {"down_sampling": (mp.down_sampling_rate, mp.down_sampling_seed, data["uid"])}
+
     # ---- the sweep (--l2_reg_weights) ----------------------------------------------------------------------------------
     def _stage_coefficients(self, theta):
         """fit_stepping's coefficients as the stage keeps them: the dummy weight of an intercept-only model in front
@@ -328,7 +357,7 @@ class FixedEffectLRModelLBFGS:
             *self._shard_arrays(data, fit=True), data["y"], self.num_features, l2_grid=grid, select=select, offset=data["offset"],
             weight=data["weight"] if data["has_weight"] else None, has_intercept=self.has_intercept, regularize_bias=self.is_regularize_bias, model_type=self.model_type, max_iter=self.max_iteration,
             m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
-            variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold)
+            variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold, **self._down_sampling(data))
         self.l2_reg_weight = self.model_params.l2_reg_weight = float(grid[best])
         return theta, info
 
@@ -372,7 +401,8 @@ class FixedEffectLRModelLBFGS:
             extra = {} if prior is None else {"prior": prior}
             kind = self.model_params.normalization()
             if kind != "none" and bag:
-                extra["feature_scale"] = self._feature_factors(kind, data, is_chief)
+                extra["feature_scale"] = self._feature_factors(kind, data, is_chief)      # (the statistics of every row, sampled or not)
+            extra.update(self._down_sampling(data))
             theta, info = self._solver().fit_stepping(
                 *self._shard_arrays(data, fit=True), data["y"], D, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
                 has_intercept=self.has_intercept, l2=self.l2_reg_weight, regularize_bias=self.is_regularize_bias,
@@ -383,6 +413,10 @@ class FixedEffectLRModelLBFGS:
         if not bag and self.variances is not None:
             self.variances = np.concatenate([[0.0], self.variances])   # next to the dummy weight of an intercept-only model
         self.last_training_info = info
+        if "down_sampling" in info:
+            c = info["down_sampling"]
+            logger.info(f"down-sampling at rate {c['rate']} (seed {c['seed']}): {c['kept']} of {c['rows']} rows kept, {c['positives']} positives in the "
+                        f"shard, {c['negatives_kept']} negatives kept, {c['kept_nnz']} non-zeros")
         logger.info(f"f_min: {info['fval']} num of funcalls: {info['nfev']} status: {info['status']}")
         self.model_coefficients = theta = self._stage_coefficients(theta)
         # the reference's variance computation rides on the scoring pass over the training data, which therefore runs (and writes

@@ -165,7 +165,8 @@ class FixedEffectDeviceSolver:
 
     def fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
                      regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
-                     group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0, prior=None, feature_scale=None):
+                     group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0, prior=None, feature_scale=None,
+                     down_sampling=None):
         """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
         worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
         model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
@@ -175,10 +176,14 @@ class FixedEffectDeviceSolver:
         (theta0 must be None), and the variances returned are the posterior's. Every worker passes the same prior.
         feature_scale = s [num_features]: feature normalisation (include/gdmix_re.h, "feature normalisation") — the penalty is
         (l2/2) sum (theta_j / s_j)^2, i.e. a prior of mean 0 and variance s^2 with s = 1 for the intercept; theta0, in theta units, is
-        honoured; not together with `prior`. Every worker passes the same factors."""
+        honoured; not together with `prior`. Every worker passes the same factors.
+        down_sampling = (rate, seed, uid [n] int64): the fit is that of a sample of the shard, drawn on the device (include/gdmix_re.h,
+        "down-sampling"; gdmix_amd/downsample.py states it): a row is kept when draw(seed, uid) < rate * 2^32 and then weighs w / rate; with
+        the logistic loss every positive is kept as it is. Variances are those of the sampled, re-weighted objective; info["down_sampling"]
+        holds the counts. Every worker passes the same rate and seed. Rate 1.0 is the plain fit."""
         opts = fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance)
         fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode,
-                           prior=prior, feature_scale=feature_scale)
+                           prior=prior, feature_scale=feature_scale, down_sampling=down_sampling)
         theta, info = fit.stage_result(*fit.run(), l2, threshold)
         if return_problem:
             return theta, info, fit.prob
@@ -187,16 +192,18 @@ class FixedEffectDeviceSolver:
 
     def fit_sweep(self, row_nnz_ptr, col_global, val, y, num_features, l2_grid, select, offset=None, weight=None, has_intercept=True,
                   regularize_bias=True, model_type=LOGISTIC_REGRESSION, max_iter=100, m=10, tolerance=1e-12, dummy=None, variance_mode=None,
-                  threshold=0.0):
+                  threshold=0.0, down_sampling=None):
         """One worker's fit for every weight of l2_grid on ONE problem: the shard is packed and gdmix_fe_create runs once; per weight, in the
         order given, gdmix_fe_restart (cold: zeros) + the same loop and status check as fit_stepping — by the restart's contract the bits
         of a fresh fit_stepping at that weight. select(thetas) — the K coefficient vectors as fit_stepping would have returned them — names
-        the winner; -> (theta, info, best) of the winner as fit_stepping returns them, its variances (at its weight, for it alone) included."""
+        the winner; -> (theta, info, best) of the winner as fit_stepping returns them, its variances (at its weight, for it alone) included.
+        down_sampling: as fit_stepping takes it; the shard is sampled once, in front of the one pack."""
         import dataclasses
         if _world_size(None) > 1:
             raise ValueError("a sweep over l2_reg_weight runs on one worker")
         opts = fit_options(has_intercept, float(l2_grid[0]), regularize_bias, model_type, max_iter, m, tolerance)
-        fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, None, None, dummy, variance_mode)
+        fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, None, None, dummy, variance_mode,
+                           down_sampling=down_sampling)
         try:
             fits = []
             for w in l2_grid:
@@ -469,26 +476,40 @@ class _SteppingFit:
     and the all-reduce of this process group; then the loop, and the result as the stage takes it."""
 
     def __init__(self, solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode,
-                 prior=None, feature_scale=None):
+                 prior=None, feature_scale=None, down_sampling=None):
         ic = 1 if opts.has_intercept else 0
         if prior is not None and theta0 is not None:
             raise ValueError("a fit with a prior starts at the prior mean: theta0 must be None")
         if prior is not None and feature_scale is not None:
             raise ValueError("feature normalisation does not compose with a prior model")
-        self.batch, self.dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, opts.has_intercept,
-                                                binary_labels=opts.loss_name() == "logistic", dummy=dummy)
+        n_rows = np.asarray(row_nnz_ptr).size - 1
+        shard, self.dummy = shard_as_batch(row_nnz_ptr, col_global, val, y, offset, weight, opts.has_intercept,
+                                           binary_labels=opts.loss_name() == "logistic", dummy=dummy)
         if opts.loss_name() == "poisson":
             from .batch import check_count_labels
-            check_count_labels(self.batch.y, "poisson_regression, the fixed effect's shard")
+            check_count_labels(shard.y, "poisson_regression, the fixed effect's shard")
         D = 1 if self.dummy else int(num_features)   # the dummy zero feature of an intercept-only model occupies global index 0
-        if not self.dummy and self.batch.col_global.size and (self.batch.col_global.min() < 0 or self.batch.col_global.max() >= D):
+        if not self.dummy and shard.col_global.size and (shard.col_global.min() < 0 or shard.col_global.max() >= D):
             raise ValueError(f"feature index outside [0, {D})")
+        self.down_sampling = None      # the counts of the down-sampling pass, when there was one
+        if down_sampling is not None:
+            from .downsample import check_rate
+            rate, seed, uid = check_rate(down_sampling[0]), int(down_sampling[1]), np.ascontiguousarray(down_sampling[2], np.int64)
+            if uid.shape != (n_rows,):
+                raise ValueError(f"down_sampling: one uid per row of the shard ({n_rows}), not {uid.shape}")
+            if rate == 1.0:
+                down_sampling = None   # the plain fit: not a call, not a bit of difference
         # whether the variances can be computed is decided before any training (a job that trains for its whole budget and
         # then dies on the variances loses the model)
         if variance_mode is not None:
             check_variance_request(str(variance_mode).upper(), D + ic, _world_size(group))
         self.solver, self.opts, self.D, self.group, self.variance_mode = solver, opts, D, group, variance_mode
-        self.packed = solver.pack(self.batch, has_intercept=opts.has_intercept)
+        self._sample = None            # the down-sampled arrays in HBM while self.batch has not been asked for
+        if down_sampling is None:
+            self._batch = shard
+            self.packed = solver.pack(shard, has_intercept=opts.has_intercept)
+        else:
+            self._batch, self.packed = self._pack_sample(shard, n_rows, rate, seed, uid)
         t0 = None
         if theta0 is not None:
             full = np.zeros(D + ic)
@@ -533,6 +554,43 @@ class _SteppingFit:
         except ImportError:
             pass
 
+    def _pack_sample(self, shard, n_rows, rate, seed, uid):
+        """Upload the shard, down-sample it on the device, pack the sample -> (the host batch of the sample or None while it stays in HBM,
+        the packed sample). A sample without a row or without a non-zero becomes the weight-0 sample shard_as_batch builds for an empty
+        bagged shard: the worker still joins every all-reduce with a full-size buffer."""
+        solver, opts = self.solver, self.opts
+        logistic = opts.loss_name() == "logistic"
+        if shard.N == n_rows + 1:
+            # the shard held no non-zero and carries shard_as_batch's weight-0 sample at its end. Whatever uid that row gets, the outcome
+            # is what sampling the shard's own rows first gives: kept, it is the same row (0 / rate = 0); dropped, the sample has no
+            # non-zero and gets the row back below.
+            uid = np.concatenate([uid, np.zeros(1, np.int64)])
+        sample, counts = solver.downsample(solver.upload(shard), uid, rate, seed, negatives_only=logistic)
+        self.down_sampling = dict(counts, rate=rate, seed=seed, rows=n_rows)      # (the shard's own rows: never the appended weight-0 sample)
+        if shard.N == n_rows + 1 and bool(sample["kept_rows"][-1:].eq(n_rows).any()):
+            self.down_sampling["kept"] -= 1      # ... which holds the sample's one non-zero and, label 0, counts as a negative when kept
+            self.down_sampling["kept_nnz"] -= 1
+            self.down_sampling["negatives_kept"] -= 1
+        if counts["kept"] > 0 and counts["kept_nnz"] > 0:
+            self._sample = sample
+            return None, solver.pack(sample, has_intercept=opts.has_intercept)
+        h = lambda k: sample[k].cpu().numpy()
+        batch, _ = shard_as_batch(h("row_nnz_ptr"), [], [], h("y"), h("offset"), h("weight"), opts.has_intercept, binary_labels=logistic,
+                                  dummy=self.dummy)
+        return batch, solver.pack(batch, has_intercept=opts.has_intercept)
+
+    @property
+    def batch(self):
+        """The host batch the problem was built from: the shard, or its sample — copied back from HBM when first asked for (the FULL
+        variances of a small model are computed on the host from it: never from the full shard when the fit came from the sample)."""
+        if self._batch is None:
+            s = self._sample
+            h = lambda k: s[k].cpu().numpy()
+            self._batch = RawBatch(ent_row_ptr=h("ent_row_ptr"), row_nnz_ptr=h("row_nnz_ptr"), col_global=h("col_global"), val=h("val"), y=h("y"),
+                                   offset=h("offset"), weight=h("weight"), uid=np.arange(int(s["N"]), dtype=np.int64),
+                                   entity_ids=["fixed_effect"], has_label=True, binary_labels=self.opts.loss_name() == "logistic")
+        return self._batch
+
     def run(self):
         """The loop on the problem as it stands -> (theta, info) in the problem's layout (the dummy feature still in front)."""
         status = run_stepping_loop(self.prob, self.all_reduce)
@@ -553,6 +611,8 @@ class _SteppingFit:
             info["variances"] = self.strip_dummy(_variances(self.solver, self.prob, self.batch, th, self.D, o.has_intercept, float(l2), o.regularize_bias,
                                                             str(self.variance_mode).upper(), self.all_reduce, self.group, packed=self.packed,
                                                             dummy=self.dummy, scale=self.prior_scale, poisson=o.loss_name() == "poisson"))
+        if self.down_sampling is not None:
+            info["down_sampling"] = dict(self.down_sampling)
         return self.strip_dummy(theta), info
 
 

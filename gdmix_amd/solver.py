@@ -93,6 +93,19 @@ class _EvalPlTotals(C.Structure):
 EVAL_PL_STATE_BYTES = 33024
 
 
+class _DownsampleOpts(C.Structure):
+    _fields_ = [("rate", C.c_double), ("seed", C.c_uint64), ("negatives_only", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _DownsampleCounts(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("kept", C.c_int64), ("kept_nnz", C.c_int64), ("positives", C.c_int64), ("negatives_kept", C.c_int64)]
+
+
+class _DownsampleOut(C.Structure):
+    _fields_ = [("N", C.c_int64), ("Z", C.c_int64), ("ent_row_ptr", C.c_void_p), ("row_nnz_ptr", C.c_void_p), ("col_global", C.c_void_p),
+                ("val", C.c_void_p), ("y", C.c_void_p), ("offset", C.c_void_p), ("weight", C.c_void_p)]
+
+
 class _EvalTotals(C.Structure):
     _fields_ = [("two_u", C.c_uint64), ("n", C.c_int64), ("n_pos", C.c_int64), ("n_neg", C.c_int64), ("n_nan", C.c_int64), ("sse", C.c_double)]
 
@@ -111,6 +124,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_join_features", "gdmix_re_score_models_workspace_bytes", "gdmix_re_score_models",
     "gdmix_re_prior_workspace_bytes", "gdmix_re_prior_apply", "gdmix_re_prior_restore",
     "gdmix_re_feature_extent", "gdmix_re_feature_moments", "gdmix_re_feature_scale_expand",
+    "gdmix_re_downsample_workspace_bytes", "gdmix_re_downsample_plan", "gdmix_re_downsample_apply",
     "gdmix_re_class_kernel_name", "gdmix_java_string_hash", "gdmix_java_partition_id",
     "gdmix_java_partition_ids_i64")
 
@@ -241,7 +255,13 @@ def load_library():
     lib.gdmix_re_feature_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]
     lib.gdmix_re_feature_scale_expand.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    if lib.gdmix_re_abi_version() != 20:
+    lib.gdmix_re_downsample_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.gdmix_re_downsample_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_downsample_plan.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.c_void_p, C.POINTER(_DownsampleOpts), C.c_void_p, C.c_size_t,
+                                             C.POINTER(_DownsampleCounts), C.c_void_p]
+    lib.gdmix_re_downsample_apply.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.POINTER(_DownsampleOpts), C.c_void_p, C.c_size_t,
+                                              C.POINTER(_DownsampleOut), C.c_void_p, C.c_void_p]
+    if lib.gdmix_re_abi_version() != 21:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib
@@ -703,6 +723,41 @@ class REDeviceSolver:
                                       C.byref(c_packed), st), "gdmix_re_pack")
         self._pack_gen += 1
         return PackedBatch(c_packed, {"workspace": ws}, rd, has_intercept, join=functools.partial(self._pack_join_of, self._pack_gen, st))
+
+    # ---- down-sampling in front of the pack (include/gdmix_re.h, "down-sampling"; gdmix_amd/downsample.py states it in numpy) -------
+    @_serialised
+    def downsample(self, raw, uid, rate, seed=0, negatives_only=True):
+        """gdmix_re_downsample_plan + _apply on a raw device batch (the dict upload() / widen() return): every row with label > 0.5 is kept
+        when negatives_only, every other row when draw(seed, uid) < rate * 2^32, with weight w / rate. uid: [N] int64, numpy or a device
+        tensor. -> (a device dict of the shape upload() returns, so that pack() takes it as is, with "kept_rows" [N_out] int32 besides: the
+        source row of each kept row; counts: dict(rows, kept, kept_nnz, positives, negatives_kept))."""
+        t = self.torch
+        E, N, Z = int(raw["E"]), int(raw["N"]), int(raw["Z"])
+        if isinstance(uid, np.ndarray):
+            uid = t.from_numpy(np.ascontiguousarray(uid, np.int64)).to(self.device)
+        if uid.dtype != t.int64 or uid.numel() != N or not uid.is_cuda or not uid.is_contiguous():
+            raise GdmixReError(f"downsample: uid must be a contiguous int64 array of {N} entries")
+        ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()
+        c_raw = _RawBatch(E, N, Z, raw["ent_row_ptr"].data_ptr(), raw["row_nnz_ptr"].data_ptr(), ptr(raw["col_global"]),
+                          ptr(raw["val"]), ptr(raw["y"]), ptr(raw["offset"]), ptr(raw["weight"]))
+        c_opts = _DownsampleOpts(float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(negatives_only)), 0)
+        nbytes = int(self.lib.gdmix_re_downsample_workspace_bytes(E, N))
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=self.device)
+        c_counts = _DownsampleCounts()
+        st = self._stream()
+        _check(self.lib.gdmix_re_downsample_plan(self._h, C.byref(c_raw), ptr(uid), C.byref(c_opts), ws.data_ptr(), nbytes, C.byref(c_counts), st),
+               "gdmix_re_downsample_plan")
+        n_out, z_out = int(c_counts.kept), int(c_counts.kept_nnz)
+        new = lambda count, dtype: t.empty(count, dtype=dtype, device=self.device)
+        d = dict(E=E, N=n_out, Z=z_out, ent_row_ptr=new(E + 1, t.int64), row_nnz_ptr=new(n_out + 1, t.int64), col_global=new(z_out, t.int64),
+                 val=new(z_out, t.float32), y=new(n_out, t.float32), offset=new(n_out, t.float32), weight=new(n_out, t.float32),
+                 kept_rows=new(n_out, t.int32))
+        c_out = _DownsampleOut(n_out, z_out, d["ent_row_ptr"].data_ptr(), d["row_nnz_ptr"].data_ptr(), ptr(d["col_global"]), ptr(d["val"]),
+                               ptr(d["y"]), ptr(d["offset"]), ptr(d["weight"]))
+        _check(self.lib.gdmix_re_downsample_apply(self._h, C.byref(c_raw), C.byref(c_opts), ws.data_ptr(), nbytes, C.byref(c_out),
+                                                  ptr(d["kept_rows"]), st), "gdmix_re_downsample_apply")
+        counts = {k: int(getattr(c_counts, k)) for k in ("rows", "kept", "kept_nnz", "positives", "negatives_kept")}
+        return d, counts
 
     # ---- solve -----------------------------------------------------------------------------------
     def alloc_result(self, packed: PackedBatch, variance=False):

@@ -193,6 +193,16 @@ GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const 
  * incremental section states for a prior holds: the stop tests apply in phi = theta / s, the threshold to theta, Var(theta_j) = s_j^2 Var'(phi_j).
  * No entry point is added to this header. */
 
+/* ---- (ABI 21) down-sampling ---------------------------------------------------------------------------------------------------------------
+ * --down_sampling_rate / --down_sampling_seed (gdmix_amd/fe_model.py; Photon-ML's downSamplingRate): the stage's training shard is
+ * down-sampled in HBM before it is packed, by gdmix_re.h's section "down-sampling", which holds the definition (the hash of (seed, uid), the
+ * threshold, the weight 1 / rate of a kept row, every positive kept under the logistic loss). The problem of this header is then created on
+ * the packed sample as on any shard: no kernel of this header knows of it, and the variances are those of the sampled, re-weighted
+ * objective. Each worker samples its own shard with the same seed; the union of the kept rows does not depend on the number of workers. A
+ * worker whose sample has no row or no non-zero trains on the weight-0 sample of an empty shard. Scoring, metrics, feature statistics and
+ * validation data see every row. The random-effect stage has no such flag (an entity could lose all its rows; a follow-up). No entry point
+ * is added to this header. */
+
 /* gdmix_fe_score under K coefficient vectors in ONE pass over the shard's non-zeros (csrc/fe_sweep.hip). thetas: HOST array of K device
  * pointers, each [num_features + has_intercept] with the intercept last; score / per_coord: [K][n] float, row k for thetas[k]
  * (per_coord may be NULL). Defined by equivalence: row k is bit for bit what gdmix_fe_score writes for thetas[k] — a row's products

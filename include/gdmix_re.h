@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 20
+#define GDMIX_RE_ABI_VERSION 21
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -649,6 +649,69 @@ GDMIX_API int gdmix_re_feature_moments(gdmix_re_ctx* ctx, const void* col, int c
                                        void* stream);
 GDMIX_API int gdmix_re_feature_scale_expand(gdmix_re_ctx* ctx, const gdmix_re_packed* packed, int has_intercept, const double* factor,
                                             int64_t num_features, double* scale, void* stream);
+
+/* ---- (ABI 21) down-sampling: a row subset of a raw batch, chosen by a hash of (seed, uid), before gdmix_re_pack ------------------------
+ * Photon-ML's downSamplingRate for the fixed-effect stage (--down_sampling_rate / --down_sampling_seed, gdmix_amd/fe_model.py; not in
+ * the reference): the stage trains on a sample of its shard that keeps every positive (logistic loss) and a negative with probability
+ * `rate`, kept negatives weighted 1 / rate, so that the objective stays an unbiased estimate of the full one and l2_reg_weight keeps its
+ * meaning. csrc/re_downsample.hip; a pass over a gdmix_re_raw_batch (any E) in front of gdmix_re_pack, of which no pack or solve kernel
+ * knows. The random-effect stage has no such flag (an entity could lose all its rows; a follow-up).
+ *
+ * Definition. All arithmetic on unsigned 64-bit integers, wrapping.
+ *     mix(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  x = (x ^ (x >> 27)) * 0x94D049BB133111EB;
+ *              return x ^ (x >> 31)                    (splitmix64's output function; mix(0) = 0xE220A8397B1DCDAF)
+ *     draw(seed, uid) = mix((uint64)uid ^ mix(seed)) >> 32       the sample's int64 uid reinterpreted as unsigned
+ *     T = (uint64)(rate * 4294967296.0),  0 < rate <= 1          the product is exact; T may be 0 and is 2^32 at rate 1
+ * A row is SAMPLED if draw < T. With negatives_only (the logistic loss) a row with label > 0.5f is always kept, its weight unchanged, and
+ * only the other rows are subject to sampling; without it (squared and Poisson loss) every row is. A row that was subject to sampling and
+ * kept gets the weight (float)((double)w / rate), w = 1 where the batch has no weight array. Kept rows keep their order.
+ * A row's fate is a pure function of (seed, uid): it does not depend on the partitioning, on the order of the rows or on the number of
+ * workers, and rows with EQUAL uids share a fate. gdmix_amd/downsample.py is the numpy statement of this definition; the device gives the
+ * same bits.
+ *     draw(0, 0) = 2802244911   draw(1, 0) = 1581361928   draw(0, 1) = 146079144   draw(20240603, 123456789) = 3653550952
+ *     draw(7, -1) = 2846452585  draw(7, -2^63) = 2118445982
+ *
+ * gdmix_re_downsample_plan: uid [N] int64 on the device. Writes into `workspace` (gdmix_re_downsample_workspace_bytes(E, N) device bytes;
+ *   host only, 0 beyond the limits; less is GDMIX_RE_ENOMEM) a keep flag per row, the exclusive scan of the kept rows (int32) and the
+ *   exclusive int64 scan of their non-zeros, synchronises `stream` once and fills *counts (host). The caller allocates the output arrays of
+ *   exactly counts->kept rows and counts->kept_nnz non-zeros.
+ * gdmix_re_downsample_apply: the same raw batch, options and workspace; fills the arrays of *out (out->N = kept, out->Z = kept_nnz):
+ *     ent_row_ptr [E+1] = scan[ent_row_ptr_in[e]] (an entity may end with no rows), row_nnz_ptr [N_out+1] from 0, col_global, val [Z_out],
+ *     y, offset [N_out], weight [N_out] (always written), and kept_rows [N_out] (optional, NULL: not wanted): the source row of each kept row.
+ *   Stream-ordered. The workspace must hold the context's LAST plan, and out->N / out->Z must be its totals: anything else is
+ *   GDMIX_RE_EINVAL and nothing is written. The copy of the non-zeros is driven by output position (a lane takes four consecutive ones; a
+ *   workgroup finds its tile's rows by bisection of the output row pointers, a lane walks from there); stores are 16 bytes per lane where
+ *   the output arrays are 16-byte aligned, and so are the loads of a lane whose four positions lie in one source row at a source position
+ *   that is a multiple of four.
+ * rate outside (0, 1] or not finite: GDMIX_RE_EINVAL. 2^31 rows or more: GDMIX_RE_ERANGE. All offsets are 64-bit. */
+typedef struct {
+  double   rate;
+  uint64_t seed;
+  int32_t  negatives_only;
+  int32_t  reserved;
+} gdmix_re_downsample_opts;
+typedef struct {          /* host */
+  int64_t rows;           /* N of the input                                                     */
+  int64_t kept;           /* N_out                                                              */
+  int64_t kept_nnz;       /* Z_out                                                              */
+  int64_t positives;      /* input rows with label > 0.5f                                       */
+  int64_t negatives_kept; /* kept rows with label <= 0.5f                                       */
+} gdmix_re_downsample_counts;
+typedef struct {          /* device pointers of the caller's arrays */
+  int64_t  N, Z;          /* counts->kept, counts->kept_nnz */
+  int64_t* ent_row_ptr;
+  int64_t* row_nnz_ptr;
+  int64_t* col_global;
+  float*   val;
+  float*   y;
+  float*   offset;
+  float*   weight;
+} gdmix_re_downsample_out;
+GDMIX_API size_t gdmix_re_downsample_workspace_bytes(int64_t E, int64_t N);
+GDMIX_API int gdmix_re_downsample_plan(gdmix_re_ctx* ctx, const gdmix_re_raw_batch* raw_dev, const int64_t* uid_dev, const gdmix_re_downsample_opts* opts,
+                                       void* workspace, size_t workspace_bytes, gdmix_re_downsample_counts* counts, void* stream);
+GDMIX_API int gdmix_re_downsample_apply(gdmix_re_ctx* ctx, const gdmix_re_raw_batch* raw_dev, const gdmix_re_downsample_opts* opts, void* workspace,
+                                        size_t workspace_bytes, const gdmix_re_downsample_out* out_dev, int32_t* kept_rows, void* stream);
 
 /* ---- B4: the upstream Spark partitioner's hash, bit-exact (host functions) ------------------------
  * hashCode over UTF-16 code units in wrapping int32; Math.abs(Int.MinValue) stays negative; Scala %
