@@ -1022,3 +1022,127 @@ def test_the_tallest_entities_of_a_batch_get_a_team_of_workgroups(device_solver,
     # everybody outside the class: bit for bit what the run without the class gave
     keep = np.repeat(~went, np.diff(cp))
     assert np.array_equal(with_team["theta"][keep], without["theta"][keep])
+
+
+# ---- the tall kernels' slice edges: one workgroup per entity and a team of four on the same small batch ------------------------------
+SLICE_EDGE_N = (64, 65, 66, 67, 700, 200)
+SLICE_EDGE_ROWS = (4, 8, 9)      # every sample <= 4 entries | <= 8 entries | <= 4 but for one sample of 9 (the general pass)
+SLICE_EDGE_SOLO = dict(tall_min_n=1, tall_team_n=0, tall_split_n=4096)      # (the split pinned: a small batch would lower it and the 700s leave <1>)
+SLICE_EDGE_TEAM = dict(tall_min_n=1, tall_split_n=1, tall_team_n=-64)
+_SLICE_EDGE_CACHE = {}
+
+
+def _slice_edge_batch(weights):
+    """18 entities over 24 features (p <= 25): every row shape of SLICE_EDGE_ROWS at every sample count of SLICE_EDGE_N. 64 .. 67: a team's
+    last member gets a shorter slice, n mod 4 = 0 .. 3; 700: streamed on a one-wavefront workgroup (26 KB and more against its 20 KB arena);
+    200: resident, lean in the narrowest shape. The long samples sit at an entity's first and last sample, the last in the last member's
+    slice: a team's members then take different passes over one entity."""
+    if weights in _SLICE_EDGE_CACHE:
+        return _SLICE_EDGE_CACHE[weights]
+    from gdmix_amd.batch import RawBatch
+    rng = np.random.default_rng(97)
+    D = 24
+    n = np.array([k for _ in SLICE_EDGE_ROWS for k in SLICE_EDGE_N], np.int64)
+    lens = []
+    for rows, k in ((r, k) for r in SLICE_EDGE_ROWS for k in SLICE_EDGE_N):
+        ln = rng.integers(1, 5, size=k)
+        if rows == 8:
+            pick = rng.choice(k, size=k // 10, replace=False)
+            ln[pick] = rng.integers(5, 9, size=pick.size)
+            ln[0] = ln[k - 1] = 8
+        elif rows == 9:
+            ln[k - 1] = 9
+        lens.append(ln)
+    lens = np.concatenate(lens)
+    N = int(lens.size)
+    cols = np.concatenate([rng.permutation(D)[:k] for k in lens]).astype(np.int64)
+    vals = rng.standard_normal(cols.size).astype(np.float32)
+    ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    offset = (0.5 * rng.standard_normal(N)).astype(np.float32)
+    w_star = 0.5 * rng.standard_normal(D)
+    logit = np.add.reduceat(vals.astype(np.float64) * w_star[cols], ptr[:-1]) + np.repeat(0.5 * rng.standard_normal(n.size), n) + offset
+    y = (rng.random(N) < 1.0 / (1.0 + np.exp(-logit))).astype(np.float32)
+    weight = (0.25 + 2.0 * rng.random(N)).astype(np.float32)
+    b = RawBatch(ent_row_ptr=np.concatenate([[0], np.cumsum(n)]), row_nnz_ptr=ptr, col_global=cols, val=vals, y=y, offset=offset,
+                 weight=weight if weights else None, entity_ids=[str(i) for i in range(n.size)])
+    _SLICE_EDGE_CACHE[weights] = b
+    return b
+
+
+def _slice_edge_case(loss, weights):
+    """-> (batch with the loss's labels, SolverOptions keywords of the loss)."""
+    b = _slice_edge_batch(weights)
+    if loss == "squared":
+        return synthetic.with_real_labels(b, seed=3), dict(linear=True)
+    if loss == "poisson":
+        return synthetic.with_count_labels(b, seed=3), dict(loss="poisson")
+    return b, {}
+
+
+def _slice_edge_compare(loss, b, pk, kw, res, coef_ptr, key):
+    """One solve against the CPU reference of its loss on every entity of the batch, by the rule its own tests use: the oracle (logistic,
+    squared) or scipy on the numpy objective (Poisson). Entities the reference reproduces under a start moved by 1e-15 .. 1e-13 are strict:
+    held to REL_TOL_DEVICE on theta and to the same nit / nfev / status; they must be at least half, and every sample count must have
+    one, so that every slice edge is compared iteration for iteration. SIMPLE variance to rtol 1e-7 on every entity."""
+    import re_linear_helpers as H
+    import re_poisson_helpers as P
+    n = b.ent_n()
+    if loss == "poisson":
+        ref = P.reference(b, pk, {k: v for k, v in kw.items() if k != "variance_mode"}, None, coef_ptr, key=key, entities=np.arange(b.E))
+        assert all(ref["strict"][n == k].any() for k in SLICE_EDGE_N), ref["strict"]
+        P.compare(res, ref, coef_ptr)
+        np.testing.assert_allclose(res["variance"], P.variance_numpy(b, pk, kw, 1, res["theta"], coef_ptr), rtol=1e-7)
+        return
+    if loss == "squared":
+        j = H.judge(b, pk, kw, None, res, coef_ptr, theta_tol=REL_TOL_DEVICE)      # (SIMPLE variance at rtol 1e-7 is one of its problems)
+        assert not j["problems"], j["problems"][:3]
+        ok, ref, err = j["strict_ok"], j["ref"], j["err"]
+    else:
+        ref, ok, _, _ = H.oracle_strict(b, pk, oracle.make_opts(**kw), None, int(coef_ptr[-1]))
+        assert well_posed_mask(b, kw).all()
+        err = per_entity_rel_err(res["theta"], ref["theta"], coef_ptr)
+        np.testing.assert_allclose(res["variance"], ref["variance"], rtol=1e-7)
+    print(f"{loss}: {int(ok.sum())} of {b.E} entities strict, worst theta error {float(err[ok].max()):.3e}")
+    assert ok.mean() >= 0.5 and all(ok[n == k].any() for k in SLICE_EDGE_N), ok
+    assert err[ok].max() <= REL_TOL_DEVICE, float(err[ok].max())
+    for k in ("nit", "nfev", "status"):
+        assert np.array_equal(res[k][ok], ref[k][ok]), k
+    np.testing.assert_allclose(res["fval"][ok], ref["fval"][ok], rtol=1e-9, atol=1e-13)
+
+
+@pytest.mark.parametrize("has_intercept", [True, False])
+@pytest.mark.parametrize("weights", [True, False])
+@pytest.mark.parametrize("loss", ["logistic", "squared", "poisson"])
+def test_tall_slice_edges_on_one_workgroup_and_on_a_team(device_solver, loss, weights, has_intercept):
+    """The one-workgroup tall kernels and the team kernel stage an entity through one setup and run one master (csrc/re_solve_tall.hip);
+    what no fixture pins is where a slice ends. The batch of _slice_edge_batch, SIMPLE variance on, solved through the one-workgroup
+    kernels (lean and <1>, resident and streamed) and through teams of four (every entity: n >= 64): each path against the CPU reference
+    and, solved again, bit for bit itself. The two paths are not compared bit for bit: they group the sums differently by design."""
+    import re_linear_helpers as H
+    b, loss_kw = _slice_edge_case(loss, weights)
+    kw = dict(l2=1.0, regularize_bias=False, has_intercept=has_intercept, m=10, max_iter=100, ftol=1e-12, variance_mode=1)
+    pk = oracle.pack(b.ent_row_ptr, b.row_nnz_ptr, b.col_global)
+    packed = device_solver.pack(b, has_intercept=has_intercept)
+    coef_ptr = packed.coef_ptr_host()
+    assert np.diff(coef_ptr).max() <= 25
+    n = b.ent_n()
+    lean, one, team = "re_solve_tall_kernel<1> lean p<=64", "re_solve_tall_kernel<1> p<=64", "re_solve_tall_team_kernel<8> x4 p<=64"
+    for path, routing in (("one workgroup", SLICE_EDGE_SOLO), ("team", SLICE_EDGE_TEAM)):
+        H.set_routing(device_solver, **routing)
+        try:
+            res = device_solver.solve(packed, SolverOptions(**kw, **loss_kw)).to_host()
+            counts = dict(device_solver.class_counts(packed))
+            idx = {name: i for i, (name, _) in enumerate(device_solver.class_counts(packed))}
+            cls = packed._view(packed.c.cls_tmp, packed.E, device_solver.torch.int32).cpu().numpy().copy()
+            again = device_solver.solve(packed, SolverOptions(**kw, **loss_kw)).to_host()
+        finally:
+            H.reset_routing(device_solver)
+        if path == "team":
+            assert counts[team] == b.E, counts
+        else:
+            assert counts[lean] + counts[one] == b.E, counts
+            assert np.all(cls[n == 700] == idx[one]) and np.all(cls[n < 100] == idx[lean]) and cls[5] == idx[lean], cls      # (entity 5: 200 samples of <= 4 entries)
+        assert np.all(res["status"] >= 0) and np.all(res["status"] <= 4), (path, np.unique(res["status"]))      # (no GDMIX_RE_ST_ABORTED)
+        for k in ("theta", "theta_thr", "variance", "fval", "gnorm", "nit", "nfev", "status"):
+            assert np.array_equal(res[k], again[k]), (path, k)
+        _slice_edge_compare(loss, b, pk, kw, res, coef_ptr, key=("slice_edges", loss, weights, has_intercept))

@@ -18,6 +18,7 @@ Recipes (what round 4's scripts were; DESIGN.md / docs/rounds cite the results):
     narrow kernel <16,5,24,96>     --env GDMIX_RE_NARROW=0,1 --workloads c2 --tests "narrow"
     history pairs (direction cost) --workloads c2 -- --lbfgs-m 1     (and again with --lbfgs-m 10)
     two builds                     --lib gdmix_amd/lib_a.so,gdmix_amd/lib_b.so
+    against the parent commit      --lib gdmix_amd/lib_parent.so,gdmix_amd/lib_new.so --workloads ml20m_movie,ml20m_user --reps 3   (lib_new.so: a COPY of the product's library)
 """
 import argparse
 import itertools
