@@ -337,7 +337,7 @@ static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int64_t rank_tiles(int64_t M) { return (M + RANK_TILE - 1) / RANK_TILE; }
 
 // device temporary of the context (grow-only): rocPRIM's temporary storage, whose size only the library can tell
-static int eval_tmp(gdmix_ctx_impl* ci, size_t bytes, hipStream_t s, void** out) {
+int eval_tmp(gdmix_ctx_impl* ci, size_t bytes, hipStream_t s, void** out) {
   if (ci->eval_tmp_bytes < bytes) {
     HIP_TRY(hipStreamSynchronize(s));
     if (ci->eval_tmp) { HIP_TRY(hipFree(ci->eval_tmp)); ci->eval_tmp = nullptr; ci->eval_tmp_bytes = 0; }

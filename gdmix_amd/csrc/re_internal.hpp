@@ -328,6 +328,11 @@ struct gdmix_ctx_impl {
   // so that gdmix_re_downsample_apply can refuse counts that are not that plan's (ds_plan_ws == nullptr: no plan yet)
   const void* ds_plan_ws;
   int64_t ds_plan_rows, ds_plan_kept, ds_plan_nnz;
+  // feature selection (re_select.hip): gdmix_re_set_select_small_max was called / its value (otherwise 1024); the workspace, the batch
+  // dimensions and kept_nnz of the last gdmix_re_select_plan of this context (sel_plan_ws == nullptr: no plan yet)
+  int sel_small_set, sel_small_max;
+  const void* sel_plan_ws;
+  int64_t sel_plan_E, sel_plan_N, sel_plan_Z, sel_plan_D, sel_plan_nnz;
 };
 
 // A few bytes from the device to the host WITHOUT a stream synchronise (round 5). The counts a pack or a solve decides its next
@@ -566,6 +571,8 @@ hipError_t launch_partition_ids(const int64_t* ids, int64_t count, int32_t num_p
                                 hipStream_t s);
 
 void set_error(const char* fmt, ...);
+// device temporary of the context (grow-only; re_evaluate.hip): rocPRIM's temporary storage, whose size only the library can tell
+int eval_tmp(gdmix_ctx_impl* ci, size_t bytes, hipStream_t s, void** out);
 
 // a HIP call inside a function of the C ABI: on failure the error text is set and the function returns GDMIX_RE_EHIP
 #define HIP_TRY(expr)                                                                        \

@@ -772,6 +772,25 @@ class RandomEffectLRLBFGSModel:
                 v.record_stream(cur)
         return solver.pack(solver.widen(raw) if "ent_n" in raw else raw, has_intercept=self.has_intercept)
 
+    def _select_ratio(self):
+        """The value of --features_to_samples_ratio, or None without the flag."""
+        return getattr(self.model_params, "features_to_samples_ratio", None)
+
+    def _pack_for_training(self, solver, batch):
+        """The batch the solve sees. With --features_to_samples_ratio: pack, choose every entity's features on the packed batch, filter the
+        raw non-zeros in HBM and pack again (include/gdmix_re.h, "feature selection"); only this batch is filtered, so a dropped feature is
+        from here on — model file, starting point, variances, scores — a feature the entity's data does not contain."""
+        packed = self._pack(solver, batch)
+        ratio = self._select_ratio()
+        if ratio is None:
+            return packed
+        filtered, _, counts = solver.select_features(packed._raw_dev, packed, ratio)
+        logger.info(f"feature selection at ratio {ratio:g}: {counts['affected']} of {counts['entities']} entities lose features, "
+                    f"{counts['kept']} of {counts['features']} entity features kept ({counts['dropped']} dropped), "
+                    f"{counts['kept_nnz']} of {packed.Z} non-zeros kept")
+        self.last_selection_counts = counts
+        return solver.pack(filtered, has_intercept=self.has_intercept)
+
     def _train(self, input_path, tensor_metadata, model_weights, num_features, schema_params, output_model_file):
         logger.info(f"Start training with {f'loaded {len(model_weights)} previous models' if model_weights else 'zeros'} "
                     f"as the model initial value.")
@@ -821,7 +840,7 @@ class RandomEffectLRLBFGSModel:
         between any two batch compositions: include/gdmix_re.h). -> the number of partitions taken (0: not grouping)."""
         self._group = None      # (what an unused group decoded stays in _decoded / _prefetched for _read)
         if GROUP_MAX < 2 or len(input_paths) < 2 or self._io_pool is None or self.model_params.rebalance_entities \
-                or not self._wants_wire():
+                or not self._wants_wire() or self._select_ratio() is not None:      # (the selection logs its counts per partition)
             return 0
         if self._solver is None:
             try:
@@ -1050,7 +1069,7 @@ class RandomEffectLRLBFGSModel:
             feat_ptr = np.zeros(1, np.int64)
             stats = {k: np.zeros(0) for k in self._STAT_KEYS}
         else:
-            packed = self._pack(solver, batch)
+            packed = self._pack_for_training(solver, batch)
             feat_ptr = host_array(packed.ent_feat_ptr())
             uniq = host_array(packed.unique_global().to(torch_int64()))
             prior = None
@@ -1066,7 +1085,7 @@ class RandomEffectLRLBFGSModel:
                 theta0 = self._start_point(model_weights, batch.entity_ids, uniq, feat_ptr, batch.E, num_features)
             first = [packed]
             packed = None
-            packed, solved, res = self._pack_and_solve(solver, lambda: first.pop() if first else self._pack(solver, batch), opts, theta0,
+            packed, solved, res = self._pack_and_solve(solver, lambda: first.pop() if first else self._pack_for_training(solver, batch), opts, theta0,
                                                        prior=prior)
             theta_thr, variance = res["theta_thr"], res.get("variance")
             self._check_statuses(res["status"], batch.E)

@@ -28,6 +28,21 @@ def check_feature_normalization(p, stage_flags):
     return kind
 
 
+def check_features_to_samples_ratio(p, stage_flags):
+    """--features_to_samples_ratio of a random-effect stage's parameters: a finite ratio above 0, and none of the stage's flags the
+    selection does not run with, given as (set?, flag, why). -> the ratio, or None without the flag."""
+    ratio = p.features_to_samples_ratio
+    if ratio is None:
+        return None
+    ratio = float(ratio)
+    if not math.isfinite(ratio) or ratio <= 0.0:
+        raise ValueError(f"--features_to_samples_ratio={ratio!r}: a finite ratio above 0")
+    for is_set, flag, why in stage_flags:
+        if is_set:
+            raise ValueError(f"--features_to_samples_ratio does not run with {flag}: {why}")
+    return ratio
+
+
 def parse_l2_grid(text):
     """'100,10,3,1,0.1' -> (100.0, 10.0, 3.0, 1.0, 0.1): comma-separated finite floats >= 0, at least one, no duplicates."""
     out = []
@@ -149,6 +164,11 @@ class REParams(LRParams):
     feature_normalization: Optional[str] = None
     # the statistics as an .npz: read and used when the file exists (no statistics pass runs), computed and written there otherwise
     feature_statistics_file: Optional[str] = None
+    # not in the reference (Photon-ML's numFeaturesToSamplesRatioUpperBound): before an entity is trained it keeps only the
+    # ceil(ratio * n_e) features of its bag whose Pearson correlation with the label is largest in magnitude (include/gdmix_re.h, "feature
+    # selection"; feature_selection.py). The intercept is kept apart and takes no slot (in Photon-ML it takes one). A dropped feature is
+    # from there on a feature the entity's data does not contain. --action=inference accepts and ignores the flag.
+    features_to_samples_ratio: Optional[float] = None
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -164,6 +184,11 @@ class REParams(LRParams):
             (self.incremental_training, "--incremental_training", "prior variances are in the original feature units, and composing the two is not implemented"),
             (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep in normalised units is not implemented"),
             (self.rebalance_entities, "--rebalance_entities", "the factors do not travel with the exchange")))
+        check_features_to_samples_ratio(self, (
+            (self.incremental_training, "--incremental_training", "a prior feature the selection drops would keep its prior mean, and composing the two is not implemented"),
+            (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep over selected features is not implemented"),
+            (self.feature_normalization not in (None, "none"), "--feature_normalization", "the correlation is taken in the original feature units, and composing the two is not implemented"),
+            (self.rebalance_entities, "--rebalance_entities", "the selection does not travel with the exchange")))
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         if self.incremental_training and self.rebalance_entities:

@@ -106,6 +106,15 @@ class _DownsampleOut(C.Structure):
                 ("val", C.c_void_p), ("y", C.c_void_p), ("offset", C.c_void_p), ("weight", C.c_void_p)]
 
 
+class _SelectCounts(C.Structure):
+    _fields_ = [("entities", C.c_int64), ("affected", C.c_int64), ("features", C.c_int64), ("kept", C.c_int64), ("dropped", C.c_int64),
+                ("kept_nnz", C.c_int64)]
+
+
+class _SelectOut(C.Structure):
+    _fields_ = [("Z", C.c_int64), ("row_nnz_ptr", C.c_void_p), ("col_global", C.c_void_p), ("val", C.c_void_p)]
+
+
 class _EvalTotals(C.Structure):
     _fields_ = [("two_u", C.c_uint64), ("n", C.c_int64), ("n_pos", C.c_int64), ("n_neg", C.c_int64), ("n_nan", C.c_int64), ("sse", C.c_double)]
 
@@ -125,6 +134,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_prior_workspace_bytes", "gdmix_re_prior_apply", "gdmix_re_prior_restore",
     "gdmix_re_feature_extent", "gdmix_re_feature_moments", "gdmix_re_feature_scale_expand",
     "gdmix_re_downsample_workspace_bytes", "gdmix_re_downsample_plan", "gdmix_re_downsample_apply",
+    "gdmix_re_select_workspace_bytes", "gdmix_re_select_plan", "gdmix_re_select_apply", "gdmix_re_set_select_small_max",
     "gdmix_re_class_kernel_name", "gdmix_java_string_hash", "gdmix_java_partition_id",
     "gdmix_java_partition_ids_i64")
 
@@ -261,7 +271,13 @@ def load_library():
                                              C.POINTER(_DownsampleCounts), C.c_void_p]
     lib.gdmix_re_downsample_apply.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.POINTER(_DownsampleOpts), C.c_void_p, C.c_size_t,
                                               C.POINTER(_DownsampleOut), C.c_void_p, C.c_void_p]
-    if lib.gdmix_re_abi_version() != 21:
+    lib.gdmix_re_select_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+    lib.gdmix_re_select_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_select_plan.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.POINTER(_SelectCounts), C.c_void_p]
+    lib.gdmix_re_select_apply.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.POINTER(_Packed), C.c_void_p, C.POINTER(_SelectOut), C.c_void_p]
+    lib.gdmix_re_set_select_small_max.argtypes = [C.c_void_p, C.c_int]
+    if lib.gdmix_re_abi_version() != 22:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib
@@ -758,6 +774,46 @@ class REDeviceSolver:
                                                   ptr(d["kept_rows"]), st), "gdmix_re_downsample_apply")
         counts = {k: int(getattr(c_counts, k)) for k in ("rows", "kept", "kept_nnz", "positives", "negatives_kept")}
         return d, counts
+
+    # ---- feature selection between two packs (include/gdmix_re.h, "feature selection"; gdmix_amd/feature_selection.py states it in numpy) ---
+    SELECT_SMALL_MAX_DEFAULT = 1024
+
+    def set_select_small_max(self, small_max: int):
+        """Testing knob: entities of more than small_max features rank by the segmented sort instead of by counting (0 .. 1024)."""
+        _check(self.lib.gdmix_re_set_select_small_max(self._h, int(small_max)), "set_select_small_max")
+
+    @_serialised
+    def select_features(self, raw, packed: PackedBatch, ratio, want_keys=False):
+        """gdmix_re_select_plan + _apply: per entity the k_e = min(d_e, ceil(ratio n_e)) features with the largest fp32 key (Pearson
+        correlation with the label, squared, times a per-entity constant), ties by feature index. raw: the device dict (upload() / widen())
+        that `packed` was packed from. -> (the filtered raw batch: a device dict pack() takes as is, which shares ent_row_ptr, y, offset and
+        weight with `raw`; the keep mask, [D] uint8 on the device in the order of unique_global; counts: dict(entities, affected, features,
+        kept, dropped, kept_nnz), with "keys" ([D] float32 on the device) besides when want_keys)."""
+        t = self.torch
+        E, N, Z, D = int(raw["E"]), int(raw["N"]), int(raw["Z"]), packed.D
+        if (E, N, Z) != (packed.E, packed.N, packed.Z):
+            raise GdmixReError("select_features: the raw batch is not the one that was packed")
+        ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()
+        c_raw = _RawBatch(E, N, Z, raw["ent_row_ptr"].data_ptr(), raw["row_nnz_ptr"].data_ptr(), ptr(raw["col_global"]),
+                          ptr(raw["val"]), ptr(raw["y"]), ptr(raw["offset"]), ptr(raw["weight"]))
+        nbytes = int(self.lib.gdmix_re_select_workspace_bytes(E, N, Z))
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=self.device)
+        keep = t.empty(D, dtype=t.uint8, device=self.device)
+        keys = t.empty(D, dtype=t.float32, device=self.device) if want_keys else None
+        c_counts = _SelectCounts()
+        st = self._stream()
+        _check(self.lib.gdmix_re_select_plan(self._h, C.byref(packed.c), float(ratio), ws.data_ptr(), nbytes, ptr(keys), keep.data_ptr() if D else None,
+                                             C.byref(c_counts), st), "gdmix_re_select_plan")
+        z_out = int(c_counts.kept_nnz)
+        d = dict(raw)
+        d.update(Z=z_out, row_nnz_ptr=t.empty(N + 1, dtype=t.int64, device=self.device), col_global=t.empty(z_out, dtype=t.int64, device=self.device),
+                 val=t.empty(z_out, dtype=t.float32, device=self.device), _select_source=raw)
+        c_out = _SelectOut(z_out, d["row_nnz_ptr"].data_ptr(), ptr(d["col_global"]), ptr(d["val"]))
+        _check(self.lib.gdmix_re_select_apply(self._h, C.byref(c_raw), C.byref(packed.c), ws.data_ptr(), C.byref(c_out), st), "gdmix_re_select_apply")
+        counts = {k: int(getattr(c_counts, k)) for k in ("entities", "affected", "features", "kept", "dropped", "kept_nnz")}
+        if want_keys:
+            counts["keys"] = keys
+        return d, keep, counts
 
     # ---- solve -----------------------------------------------------------------------------------
     def alloc_result(self, packed: PackedBatch, variance=False):

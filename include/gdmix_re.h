@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 21
+#define GDMIX_RE_ABI_VERSION 22
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -712,6 +712,68 @@ GDMIX_API int gdmix_re_downsample_plan(gdmix_re_ctx* ctx, const gdmix_re_raw_bat
                                        void* workspace, size_t workspace_bytes, gdmix_re_downsample_counts* counts, void* stream);
 GDMIX_API int gdmix_re_downsample_apply(gdmix_re_ctx* ctx, const gdmix_re_raw_batch* raw_dev, const gdmix_re_downsample_opts* opts, void* workspace,
                                         size_t workspace_bytes, const gdmix_re_downsample_out* out_dev, int32_t* kept_rows, void* stream);
+
+/* ---- (ABI 22) feature selection: per entity, the features most correlated with the label, before gdmix_re_pack ----------------------------
+ * Photon-ML's numFeaturesToSamplesRatioUpperBound for a random-effect stage (--features_to_samples_ratio=R, gdmix_amd/model.py; not in the
+ * reference): before an entity is trained it keeps only the ceil(R n_e) features whose Pearson correlation with the label is largest in
+ * magnitude. csrc/re_select.hip; a pass between two packs (pack -> plan on the packed CSC -> apply on the raw non-zeros -> pack again), of
+ * which no pack or solve kernel knows: a dropped feature is from there on a feature the entity's data does not contain.
+ *
+ * Definition, for one entity with n samples, labels y_i (fp32 widened to fp64) and cells x_ij: a cell is the fp64 sum of the entity's
+ * duplicates of (sample i, feature j), in CSC order, and zero where there is none. Unweighted; offsets are ignored; the intercept is not a
+ * feature (it is kept apart and takes no slot — Photon-ML counts it as one of the kept features).
+ *     Sy = sum y_i, Syy = sum y_i^2 over the samples in order; per feature, over its cells in sample order: Sx, Sxx, Sxy
+ *     A = n Sxy - Sx Sy,  Bx = n Sxx - Sx^2,  By = n Syy - Sy^2
+ *     q = A^2 / Bx  if Bx > 2^-30 n Sxx and By > 2^-30 n Syy, else 0   (a constant column, constant labels, n = 1)
+ *     key = (float)q  (a NaN, from infinite sums, is 0.0f);  r^2 = q / By, and By is common to an entity's features, so it is dropped
+ *     rank by key descending, then by feature index ascending; keep the first k_e = min(d_e, (int64)ceil(R (double)n_e))
+ * A feature that occurs in one sample only has q = (n y_i - Sy)^2 / (n - 1) whatever its value: exact ties at the boundary are the rule,
+ * which is why the rank is taken on the fp32 key with the index as the tie-break. A column's sums are plain fp64 sums by one lane, one term
+ * after another; Sy and Syy are 64 partial sums over the samples i = l, l + 64, ... added by a butterfly, a shape that depends on n alone:
+ * a key is a function of the entity's own data alone and has the same bits whichever ranking path takes the entity, wherever the entity
+ * sits in the batch and however partitions are grouped. gdmix_amd/feature_selection.py is the numpy statement.
+ *
+ * Error of a key against the exact q (u = 2^-53; inputs are fp32, so x^2 and x y are exact in fp64 unless a cell is a sum of duplicates):
+ * a sum of c <= n terms carries at most (c + 1) u sum|terms|; with M = n sum|x y| + |Sx| |Sy| the computed A is within
+ * delta = (n + 4) 2^-52 M of the exact one (twice the first-order bound (n + 3) u M, for columns whose values share a sign, as sum|x| = |Sx|
+ * there), so A^2 is within 2 M delta + delta^2, divided by Bx. The computed Bx is within (n + 4) 2^-52 (n Sxx + Sx^2) of the exact one: where
+ * that is at most 2^-24 Bx its share stays inside the 2^-22 q that also holds the fp32 rounding (2^-24 q). So where the exact
+ * Bx >= 2^-20 n Sxx and By >= 2^-20 n Syy:   |key - q| <= 2^-22 q + (2 M delta + delta^2) / Bx.
+ * Where the exact Bx or By is 0 the computed one is at most (n + 4) 2^-51 n Sxx < 2^-30 n Sxx (n < 2^20) and the key is exactly 0.0f.
+ *
+ * gdmix_re_select_plan: `packed` is the pack of the raw batch (gdmix_re_pack, has_intercept either way). Column moments come from csc_val,
+ *   csc_row and y, a wavefront per entity and a lane per column. Entities of at most 1024 features rank by counting,
+ *   #{key_j > key_i or (== and j < i)} < k_e (up to 64 features across the lanes' registers, above that against the keys in LDS); larger ones by a segmented
+ *   radix sort of (~key bits, local index). Both give the same mask. Writes the plan into `workspace`
+ *   (gdmix_re_select_workspace_bytes(E, N, Z) device bytes; host only, 0 beyond the limits; less is GDMIX_RE_ENOMEM), keep_out [D] uint8 and,
+ *   unless NULL, keys_out [D] float, both in the order of unique_global; synchronises `stream` once and fills *counts (host). rocPRIM's
+ *   temporary storage is the context's own (grow-only).
+ * gdmix_re_select_apply: the raw batch that was packed, the pack, the workspace; fills row_nnz_ptr [N+1], col_global and val [kept_nnz] of
+ *   *out. A non-zero z is kept iff keep[ent_feat_ptr[e] + csr_col[z]]; kept non-zeros keep their order. Rows, y, offset and weight are not
+ *   touched: the caller's raw batch keeps them. Stream-ordered. The workspace must hold the context's LAST plan, and out->Z must be its
+ *   kept_nnz: anything else is GDMIX_RE_EINVAL and nothing is written.
+ * R not finite or <= 0: GDMIX_RE_EINVAL. 2^31 entities, samples or non-zeros or more: GDMIX_RE_ERANGE. All offsets are 64-bit. */
+typedef struct {          /* host */
+  int64_t entities;       /* E                                                                  */
+  int64_t affected;       /* entities with k_e < d_e                                            */
+  int64_t features;       /* D, the sum of d_e                                                  */
+  int64_t kept;           /* the sum of k_e                                                     */
+  int64_t dropped;        /* features - kept                                                    */
+  int64_t kept_nnz;       /* non-zeros of the kept features                                     */
+} gdmix_re_select_counts;
+typedef struct {          /* device pointers of the caller's arrays */
+  int64_t  Z;             /* counts->kept_nnz */
+  int64_t* row_nnz_ptr;   /* [N+1] */
+  int64_t* col_global;    /* [Z]   */
+  float*   val;           /* [Z]   */
+} gdmix_re_select_out;
+GDMIX_API size_t gdmix_re_select_workspace_bytes(int64_t E, int64_t N, int64_t Z);
+GDMIX_API int gdmix_re_select_plan(gdmix_re_ctx* ctx, const gdmix_re_packed* packed, double R, void* workspace, size_t workspace_bytes, float* keys_out,
+                                   uint8_t* keep_out, gdmix_re_select_counts* counts, void* stream);
+GDMIX_API int gdmix_re_select_apply(gdmix_re_ctx* ctx, const gdmix_re_raw_batch* raw_dev, const gdmix_re_packed* packed, void* workspace,
+                                    const gdmix_re_select_out* out_dev, void* stream);
+/* Testing knob: entities of more than `small_max` features take the sort path (0 => every entity that has a feature). 0 .. 1024, default 1024. */
+GDMIX_API int gdmix_re_set_select_small_max(gdmix_re_ctx* ctx, int small_max);
 
 /* ---- B4: the upstream Spark partitioner's hash, bit-exact (host functions) ------------------------
  * hashCode over UTF-16 code units in wrapping int32; Math.abs(Int.MinValue) stays negative; Scala %
