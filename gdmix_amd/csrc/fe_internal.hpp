@@ -146,4 +146,9 @@ int fe_build_copy(hipStream_t s, int num_cus, const FeHooks& hooks, const FeSour
 int fe_build_column_copy(hipStream_t s, int num_cus, const FeHooks& hooks, const gdmix_re_packed* b, int n, int d, int64_t z, FeCopy* out,
                          FeHot* hot, DevBuf* tables, DevBuf* cdata, DevBuf* hot_mem);
 
+// ---- fe_owlqn.hip ----
+// One OWL-QN step (products, decision, update: three launches) on the reduced [gradient, value] buffer of a problem with l1 > 0;
+// the status lands in *status_dev as the L-BFGS-B step's does.
+void fe_owlqn_enqueue_step(const FeDev& F, const SolveParams& o, double l1, int32_t* status_dev, hipStream_t s);
+
 }  // namespace gdmix

@@ -783,6 +783,7 @@ struct gdmix_fe_problem {
   DevBuf ccopies[2];     // ... and their units in the 6-byte form
   DevBuf hot_mem;        // the frequent columns' list
   DevBuf prior_mem;      // [2 P] the problem's copy of the prior mean and scale, then the check's flag (gdmix_fe_set_prior); empty until the first prior
+  double l1 = 0.0;       // weight of the L1 term (gdmix_fe_set_l1); > 0: the step is OWL-QN's (fe_owlqn.hip)
   int32_t* status_dev = nullptr;
   hipEvent_t ev[3] = {};
   bool timed = false;
@@ -979,6 +980,7 @@ GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const 
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(p->ctx->impl.device));
   FeDev& F = p->F;
+  if (mean && p->l1 > 0.0) { set_error("gdmix_fe_set_prior: the problem has an L1 term (gdmix_fe_set_l1), which does not compose with a prior"); return GDMIX_RE_EINVAL; }
   if (!mean) {
     F.mu = nullptr; F.sc = nullptr;      // (the copy stays allocated: kernels of an earlier solve may still be queued on it)
     return fe_reset(p, nullptr, s);
@@ -1002,6 +1004,15 @@ GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const 
   HIP_TRY(hipMemcpyAsync(prior + P, scale, P * 8, hipMemcpyDeviceToDevice, s));
   F.mu = prior; F.sc = prior + P;
   return fe_reset(p, nullptr, s);
+}
+
+GDMIX_API int gdmix_fe_set_l1(gdmix_fe_problem* p, double l1, void* stream) {
+  if (!p) { set_error("problem is NULL"); return GDMIX_RE_EINVAL; }
+  if (!(l1 >= 0.0) || l1 == __builtin_inf()) { set_error("gdmix_fe_set_l1: l1 must be finite and >= 0"); return GDMIX_RE_EINVAL; }
+  if (p->F.mu) { set_error("gdmix_fe_set_l1: the problem has a prior (gdmix_fe_set_prior), which does not compose with an L1 term"); return GDMIX_RE_EINVAL; }
+  HIP_TRY(hipSetDevice(p->ctx->impl.device));
+  p->l1 = l1;
+  return fe_reset(p, nullptr, static_cast<hipStream_t>(stream));
 }
 
 GDMIX_API void gdmix_fe_destroy(gdmix_fe_problem* p) {
@@ -1076,11 +1087,12 @@ static int fe_enqueue_step(gdmix_fe_problem* p, hipStream_t s) {
   const FeDev& F = p->F;
   const int dot_blocks = grid_for(F.P, 256, FE_DOT_BLOCKS);
   const int tail_blocks = grid_for(dot_blocks, 1, p->ctx->impl.num_cus);      // at most one workgroup per CU: all resident, the wait inside cannot starve one
-  if (p->fused_tail) {
+  if (p->fused_tail && !(p->l1 > 0.0)) {
     ++p->gen;
     if (p->gen == 0u) ++p->gen;
   }
-  with_flag(F.mu != nullptr, [&](auto PR) {
+  if (p->l1 > 0.0) fe_owlqn_enqueue_step(F, p->o, p->l1, p->status_dev, s);      // (never with a prior: gdmix_fe_set_l1)
+  else with_flag(F.mu != nullptr, [&](auto PR) {
     constexpr bool PRIOR = decltype(PR)::value;
     if (p->fused_tail) {
       hipLaunchKernelGGL(fe_tail_kernel<PRIOR>, dim3(tail_blocks), dim3(FE_THREADS), 0, s, F, p->o, dot_blocks, p->status_dev, p->gen);
@@ -1159,7 +1171,8 @@ GDMIX_API int gdmix_fe_result(gdmix_fe_problem* p, double* theta, double* fval, 
     hipLaunchKernelGGL(fe_prior_theta_kernel, dim3(grid_for(p->F.P, 256, 1024)), dim3(256), 0, s, p->F, theta);
     HIP_TRY(hipGetLastError());
   } else if (theta) {
-    HIP_TRY(hipMemcpyAsync(theta, p->F.W.x, (size_t)p->F.P * 8, hipMemcpyDeviceToDevice, s));
+    // under the OWL-QN step W.x is the trial point and W.t the last accepted one (fe_owlqn.hip)
+    HIP_TRY(hipMemcpyAsync(theta, p->l1 > 0.0 ? p->F.W.t : p->F.W.x, (size_t)p->F.P * 8, hipMemcpyDeviceToDevice, s));
   }
   CompactState S;
   HIP_TRY(hipMemcpyAsync(&S, p->F.state, sizeof(S), hipMemcpyDeviceToHost, s));

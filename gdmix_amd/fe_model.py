@@ -29,6 +29,10 @@ Not in the reference either, any number of workers:
        the variances written are the posterior's: training on a new day's data alone is the Bayesian update of yesterday's model
        (include/gdmix_fe.h, "incremental training"; the reference leaves it open, :361-367). Every worker reads the same model file.
        Without a prior model the stage is a plain cold run. Refused with --l2_reg_weights and with --action=inference.
+  --l1_reg_weight=W   the objective gains W |theta_R|_1 (R: what l2_reg_weight regularises) and the stage trains by OWL-QN on the device
+       (include/gdmix_fe.h, "(ABI 23) L1 / elastic net"): coefficients outside the support are exactly 0 and stay out of the model file; the
+       number of non-zeros is logged. Photon-ML's elastic net (lambda, alpha) is W = alpha lambda, l2_reg_weight = (1 - alpha) lambda.
+       Refused with --l2_reg_weights, --incremental_training and --feature_normalization; --action=inference ignores it.
 """
 import glob
 import logging
@@ -44,7 +48,7 @@ from .io import avro, native_reader, tfrecord
 from .io.features import read_feature_list
 from .io.grouped_reader import resolve_input_files
 from .io.metadata import DatasetMetadata
-from .params import LRParams, check_feature_normalization, parse_l2_grid
+from .params import LRParams, check_feature_normalization, check_l1_reg_weight, parse_l2_grid
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.INFO)
@@ -81,6 +85,11 @@ class FixedLRParams(LRParams):
     # stage has no such flag.
     down_sampling_rate: float = 1.0
     down_sampling_seed: int = 0
+    # not in the reference: Photon-ML's regularizationType = L1 / ELASTIC_NET. The objective gains l1 |theta_R|_1 (R as for the L2 term) and
+    # the stage trains by OWL-QN on the device (include/gdmix_fe.h, "(ABI 23) L1 / elastic net"): coefficients outside the support are
+    # exactly 0 and stay out of the model file. Photon-ML's (lambda, alpha) is l1 = alpha lambda, l2 = (1 - alpha) lambda. 0: no L1 term.
+    # --action=inference accepts and ignores the flag.
+    l1_reg_weight: float = 0.0
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -107,6 +116,14 @@ class FixedLRParams(LRParams):
         check_feature_normalization(self, (
             (self.incremental_training, "--incremental_training", "prior variances are in the original feature units, and composing the two is not implemented"),
             (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep in normalised units is not implemented")))
+        self.l1_reg_weight = check_l1_reg_weight(self.l1_reg_weight)
+        if self.l1_reg_weight > 0.0:
+            for is_set, flag, why in (
+                    (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep with an L1 term is not implemented"),
+                    (self.incremental_training, "--incremental_training", "the L1 term is not invariant under the prior's change of variables"),
+                    (self.normalization() != "none", "--feature_normalization", "the L1 term is not invariant under the change to normalised units")):
+                if is_set:
+                    raise ValueError(f"--l1_reg_weight does not run with {flag}: {why}")
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         assert self.fixed_effect_variance_mode is None or self.fixed_effect_variance_mode in (constants.FULL, constants.SIMPLE), \
@@ -403,6 +420,8 @@ class FixedEffectLRModelLBFGS:
             if kind != "none" and bag:
                 extra["feature_scale"] = self._feature_factors(kind, data, is_chief)      # (the statistics of every row, sampled or not)
             extra.update(self._down_sampling(data))
+            if self.model_params.l1_reg_weight > 0.0:
+                extra["l1"] = self.model_params.l1_reg_weight
             theta, info = self._solver().fit_stepping(
                 *self._shard_arrays(data, fit=True), data["y"], D, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
                 has_intercept=self.has_intercept, l2=self.l2_reg_weight, regularize_bias=self.is_regularize_bias,
@@ -418,6 +437,8 @@ class FixedEffectLRModelLBFGS:
             logger.info(f"down-sampling at rate {c['rate']} (seed {c['seed']}): {c['kept']} of {c['rows']} rows kept, {c['positives']} positives in the "
                         f"shard, {c['negatives_kept']} negatives kept, {c['kept_nnz']} non-zeros")
         logger.info(f"f_min: {info['fval']} num of funcalls: {info['nfev']} status: {info['status']}")
+        if self.model_params.l1_reg_weight > 0.0:
+            logger.info(f"l1_reg_weight {self.model_params.l1_reg_weight}: {int(np.count_nonzero(theta))} of {theta.size} coefficients are non-zero")
         self.model_coefficients = theta = self._stage_coefficients(theta)
         # the reference's variance computation rides on the scoring pass over the training data, which therefore runs (and writes
         # its scores) whenever a variance mode is set (:650-661)

@@ -166,7 +166,7 @@ class FixedEffectDeviceSolver:
     def fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
                      regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
                      group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0, prior=None, feature_scale=None,
-                     down_sampling=None):
+                     down_sampling=None, l1=0.0):
         """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
         worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
         model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
@@ -180,11 +180,26 @@ class FixedEffectDeviceSolver:
         down_sampling = (rate, seed, uid [n] int64): the fit is that of a sample of the shard, drawn on the device (include/gdmix_re.h,
         "down-sampling"; gdmix_amd/downsample.py states it): a row is kept when draw(seed, uid) < rate * 2^32 and then weighs w / rate; with
         the logistic loss every positive is kept as it is. Variances are those of the sampled, re-weighted objective; info["down_sampling"]
-        holds the counts. Every worker passes the same rate and seed. Rate 1.0 is the plain fit."""
+        holds the counts. Every worker passes the same rate and seed. Rate 1.0 is the plain fit.
+        l1 > 0: the objective gains l1 |theta_R|_1 and the step is OWL-QN's (include/gdmix_fe.h, "(ABI 23) L1 / elastic net"); theta0 is its
+        start point; not together with `prior` or `feature_scale`. Coefficients outside the support are exactly 0.0; info["nnz"] counts
+        the others. l1 = 0 is the plain fit: set_l1 is never called."""
+        l1 = float(l1)
+        if not (np.isfinite(l1) and l1 >= 0.0):
+            raise ValueError(f"l1 must be finite and >= 0, not {l1}")
+        if l1 > 0.0 and (prior is not None or feature_scale is not None):
+            raise ValueError("the L1 term does not compose with a prior model or with feature normalisation")
         opts = fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance)
         fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode,
                            prior=prior, feature_scale=feature_scale, down_sampling=down_sampling)
+        if l1 > 0.0:
+            t0 = fit.prob.theta0
+            fit.prob.set_l1(l1)      # (leaves the problem at zeros)
+            if t0 is not None:
+                fit.prob.restart(opts, t0)
         theta, info = fit.stage_result(*fit.run(), l2, threshold)
+        info["l1"] = l1
+        info["nnz"] = int(np.count_nonzero(theta))
         if return_problem:
             return theta, info, fit.prob
         fit.prob.close()
@@ -351,6 +366,12 @@ class _SteppingProblem:
                 raise GdmixReError(f"a prior vector is a contiguous float64 device array of {self.count - 1} entries (intercept last)")
         self._check(self.lib.gdmix_fe_set_prior(self._h, None if mean_dev is None else mean_dev.data_ptr(),
                                                 None if scale_dev is None else scale_dev.data_ptr(), self.solver._stream()), "gdmix_fe_set_prior")
+        self.theta0 = None
+
+    def set_l1(self, l1):
+        """gdmix_fe_set_l1: l1 > 0 puts the problem on the OWL-QN step, 0 back on the L-BFGS-B step. Leaves the problem as a restart with
+        its current options at zeros does. Stream-ordered."""
+        self._check(self.lib.gdmix_fe_set_l1(self._h, float(l1), self.solver._stream()), "gdmix_fe_set_l1")
         self.theta0 = None
 
     def reduce_tensor(self):

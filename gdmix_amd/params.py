@@ -43,6 +43,17 @@ def check_features_to_samples_ratio(p, stage_flags):
     return ratio
 
 
+def check_l1_reg_weight(value):
+    """--l1_reg_weight: a finite weight >= 0 -> float."""
+    try:
+        w = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"--l1_reg_weight={value!r} is not a number") from None
+    if not math.isfinite(w) or w < 0.0:
+        raise ValueError(f"--l1_reg_weight={value!r}: a finite weight >= 0")
+    return w
+
+
 def parse_l2_grid(text):
     """'100,10,3,1,0.1' -> (100.0, 10.0, 3.0, 1.0, 0.1): comma-separated finite floats >= 0, at least one, no duplicates."""
     out = []
@@ -169,6 +180,9 @@ class REParams(LRParams):
     # selection"; feature_selection.py). The intercept is kept apart and takes no slot (in Photon-ML it takes one). A dropped feature is
     # from there on a feature the entity's data does not contain. --action=inference accepts and ignores the flag.
     features_to_samples_ratio: Optional[float] = None
+    # the fixed-effect stage's flag (fe_model.FixedLRParams). This stage's parser ignores flags it does not know, so the field exists to
+    # refuse a non-zero value instead of training a ridge model in silence.
+    l1_reg_weight: float = 0.0
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -180,6 +194,8 @@ class REParams(LRParams):
 
     def __post_init__(self):
         self.l2_grid()      # a bad list is an error at parse time
+        if check_l1_reg_weight(self.l1_reg_weight) != 0.0:
+            raise ValueError(f"--l1_reg_weight={self.l1_reg_weight}: the random effect has no L1 term (the flag belongs to the fixed-effect stage)")
         check_feature_normalization(self, (
             (self.incremental_training, "--incremental_training", "prior variances are in the original feature units, and composing the two is not implemented"),
             (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep in normalised units is not implemented"),

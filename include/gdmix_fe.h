@@ -203,6 +203,39 @@ GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const 
  * validation data see every row. The random-effect stage has no such flag (an entity could lose all its rows; a follow-up). No entry point
  * is added to this header. */
 
+/* ---- (ABI 23) L1 / elastic net ------------------------------------------------------------------------------------------------------------
+ * --l1_reg_weight (gdmix_amd/fe_model.py; Photon-ML's regularizationType = L1 / ELASTIC_NET, solved there by OWL-QN as well):
+ *     F(theta) = sum_i w_i l(y_i, x_i . w + b + offset_i) + (l2/2) |theta_R|^2 + l1 |theta_R|_1
+ * R the regularised set of the options (every feature; the intercept iff regularize_bias), l any of the three losses, the sum not divided by
+ * n. Photon-ML's elastic net (lambda, alpha) is l1 = alpha lambda, l2 = (1 - alpha) lambda.
+ * gdmix_fe_set_l1: l1 must be finite and >= 0 (GDMIX_RE_EINVAL otherwise). l1 > 0 makes the problem take the OWL-QN step (csrc/fe_owlqn.hip)
+ *   from its next step on; l1 == 0 puts it back on the L-BFGS-B step. Either way the call leaves the problem in the state of a
+ *   gdmix_fe_restart with its current options at zeros. Stream-ordered; it waits for nothing. gdmix_fe_restart keeps the problem's l1; its
+ *   theta0 is the OWL-QN start point. While a prior is installed the call is refused (GDMIX_RE_EINVAL), and so is gdmix_fe_set_prior with a
+ *   prior while l1 > 0: the L1 term is not invariant under the diagonal substitution phi = (theta - mu) / s.
+ * Every other entry point keeps its contract: gdmix_fe_eval is the same two passes, gdmix_fe_step / _step_async / _step_status / _solve, the
+ * status ring, the lookahead and the stop flag work as before, the step leaves the reduce buffer cleared, and the -inf mark of an aborted
+ * peer in the value slot stops every worker with GDMIX_RE_ST_ABORTED_PEER.
+ * The step (Andrew & Gao 2007). g is the gradient of the smooth part (data + l2 theta_R) at the accepted point x.
+ *   pseudo-gradient  j in R: pg_j = g_j + l1 (x_j > 0), g_j - l1 (x_j < 0); at x_j = 0: g_j + l1 if that is < 0, g_j - l1 if that is > 0, else 0.
+ *                    j not in R: pg_j = g_j.
+ *   direction        d = -H pg, H the L-BFGS inverse-Hessian approximation over the last <= m stored pairs s = x+ - x, y = g+ - g (smooth
+ *                    gradients), H0 = (s'y / y'y) I from the newest pair; then d_j = 0 wherever d_j pg_j >= 0. No pair stored: d = -pg.
+ *   orthant          xi_j = sign(x_j) if x_j != 0, else sign(-pg_j).
+ *   trial            x(t)_j = x_j + t d_j if its sign equals xi_j, else exactly 0.0.
+ *   search           t = 1 / |pg|_2 while no pair is stored, else 1; accepted when F(x(t)) <= F(x) + 1e-4 pg'(x(t) - x), else t is halved.
+ *                    After maxls rejected trials in one iteration: the memory is cleared and the search starts again along -pg if a pair
+ *                    was stored, else the solve stops with status 4 at x.
+ *   pair storage     only if s'y > 2.2e-16 y'y.
+ *   stops            after each accepted iterate, in this order: |pg|_inf <= pgtol -> 0 (also tested at the start point);
+ *                    F_old - F <= ftol max(|F_old|, |F|, 1) -> 1; nit >= max_iter -> 2; nfev > maxfun -> 3. Every evaluation counts in nfev.
+ * gdmix_fe_result returns the last accepted point, never a rejected trial: coordinates the orthant projection set to zero are exactly 0.0.
+ * fval = F with the L1 term, gnorm = |pg|_inf, nit, nfev as above.
+ * Variances are those of the smooth part at the returned theta: gdmix_fe_hessian_diag plus l2, as without an L1 term. A coefficient at
+ * exactly 0 gets one too: this feature's own choice (the L1 term has no curvature; the variance says how well the data determine the
+ * coefficient, not whether it was selected). */
+GDMIX_API int gdmix_fe_set_l1(gdmix_fe_problem* p, double l1, void* stream);
+
 /* gdmix_fe_score under K coefficient vectors in ONE pass over the shard's non-zeros (csrc/fe_sweep.hip). thetas: HOST array of K device
  * pointers, each [num_features + has_intercept] with the intercept last; score / per_coord: [K][n] float, row k for thetas[k]
  * (per_coord may be NULL). Defined by equivalence: row k is bit for bit what gdmix_fe_score writes for thetas[k] — a row's products
