@@ -96,6 +96,52 @@ struct FeDev {
   const double *mu, *sc;    // [P] prior mean and scale (include/gdmix_fe.h, "incremental training"), NULL without one; read by the PRIOR variants only
 };
 
+// ---- the trust-region Newton step (include/gdmix_fe.h, "(ABI 24) TRON"; csrc/fe_tron.hip) ------------------------------------------------
+// A buffer of the problem's own, allocated when TRON is first selected (or gdmix_fe_hessian_vec first called): this record, then the
+// vectors below. What a pass pair computes is decided on the device: the HV variant of the row kernels reads `mode` at entry.
+enum {
+  FE_TM_EVAL = 0,        // evaluation at the trial point (xl, intercept xt[D]); the emit writes the curvature of that point into c[1 - cur]
+  FE_TM_PRODUCT = 1,     // X~' D X~ d: gathers vl, intercept d[D], D = c[cur], the accepted point's
+  FE_TM_CURVATURE = 2,   // gdmix_fe_hessian_vec, first row pass: as FE_TM_EVAL at F.W.x[D] / xl, whatever the status
+  FE_TM_VECTOR = 3       // gdmix_fe_hessian_vec, second row pass: as FE_TM_PRODUCT with intercept `vb` and D = c[1 - cur], whatever the status
+};
+struct FeTronState {
+  int mode, cur;                 // what the next pass pair computes; which of c[2] belongs to the accepted point
+  int ncg, nrej, moved;          // products of this outer iteration; consecutive rejected trials; a step has been accepted
+  int action;                    // what the update does (fe_tron.hip: TA_*)
+  int saved_mode, pad;           // gdmix_fe_hessian_vec puts `mode` back
+  long long nhv;                 // products so far (gdmix_fe_products)
+  double delta, gnorm, gg, rr;   // radius; |g|_2, g'g at the accepted point; r'r of the CG residual
+  double coef, beta;             // the update: s += coef d, r -= coef Hd; d = r + beta d
+  double vb;                     // intercept entry of gdmix_fe_hessian_vec's v
+};
+struct FeTron {                  // the buffer's parts, P (or d, n) doubles each
+  FeTronState* st;
+  double *s, *r, *d, *h, *xt, *g;   // CG iterate, residual, direction; what the last pass pair left (H d, or the gradient at the trial); trial point; accepted gradient
+  double* vl;                    // [d] the direction in the shard's local order (what the product's row pass gathers)
+  double* c[2];                  // [n] curvature weights w rho (1 - rho) | 2 w | w exp(z)
+};
+constexpr size_t FE_TRON_HEAD = 256;      // bytes kept for the record
+__host__ __device__ inline size_t fe_tron_pad(size_t k) { return (k + 31) & ~(size_t)31; }      // doubles: every part 256-byte aligned
+__host__ __device__ inline size_t fe_tron_bytes(int P, int d, int n) {
+  return FE_TRON_HEAD + (6 * fe_tron_pad((size_t)P) + fe_tron_pad((size_t)d + 1) + 2 * fe_tron_pad((size_t)n + 1)) * 8;
+}
+// The buffer's address travels in W.part — a field of Work that only the team kernels use, NULL in a fixed-effect problem until the problem
+// first needs the buffer — so that FeDev keeps its size and layout, and with them every existing kernel its argument offsets and its code.
+__host__ __device__ inline FeTronState* fe_tron_state(const FeDev& F) { return reinterpret_cast<FeTronState*>(F.W.part); }
+__host__ __device__ inline FeTron fe_tron_of(const FeDev& F) {
+  FeTron T;
+  T.st = fe_tron_state(F);
+  double* v = reinterpret_cast<double*>(reinterpret_cast<char*>(T.st) + FE_TRON_HEAD);
+  const size_t p = fe_tron_pad((size_t)F.P);
+  T.s = v; T.r = v + p; T.d = v + 2 * p; T.h = v + 3 * p; T.xt = v + 4 * p; T.g = v + 5 * p;
+  T.vl = v + 6 * p;
+  T.c[0] = T.vl + fe_tron_pad((size_t)F.d + 1);
+  T.c[1] = T.c[0] + fe_tron_pad((size_t)F.n + 1);
+  return T;
+}
+static_assert(sizeof(FeTronState) <= FE_TRON_HEAD, "the record fits its slot");
+
 // Sort key of an entry on its way into a copy: the block, refined by the window of 2^FE_SPAN_BITS gathered elements the entry's key
 // lies in. The entries of a block already come by ascending key, so the windows do not change the sorted order; they only add cut
 // points, so that no unit's keys span more than the packed word can hold (a block with few entries is one unit over the whole vector
@@ -150,5 +196,16 @@ int fe_build_column_copy(hipStream_t s, int num_cus, const FeHooks& hooks, const
 // One OWL-QN step (products, decision, update: three launches) on the reduced [gradient, value] buffer of a problem with l1 > 0;
 // the status lands in *status_dev as the L-BFGS-B step's does.
 void fe_owlqn_enqueue_step(const FeDev& F, const SolveParams& o, double l1, int32_t* status_dev, hipStream_t s);
+
+// ---- fe_tron.hip ----
+// One TRON step (products, decision, update: three launches) on the reduced buffer of a problem whose optimiser is TRON: the buffer
+// holds [gradient, value] after an evaluation and [X~' D X~ d, 0] after a product; the step knows which from the record.
+void fe_tron_enqueue_step(const FeDev& F, const SolveParams& o, int32_t* status_dev, hipStream_t s);
+// The buffer as a restart leaves it: record cleared (an evaluation at the start point comes first), trial point = theta0 (NULL: zeros).
+void fe_tron_enqueue_reset(const FeDev& F, const double* theta0, hipStream_t s);
+// gdmix_fe_hessian_vec: `mode` set to FE_TM_CURVATURE (the old one kept), then to FE_TM_VECTOR with vl filled from v; then put back.
+void fe_tron_enqueue_hv_begin(const FeDev& F, hipStream_t s);
+void fe_tron_enqueue_hv_vector(const FeDev& F, const double* v, hipStream_t s);
+void fe_tron_enqueue_hv_end(const FeDev& F, hipStream_t s);
 
 }  // namespace gdmix

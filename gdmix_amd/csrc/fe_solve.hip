@@ -99,6 +99,53 @@ __device__ __forceinline__ void fe_emit_row(const FeDev& F, const SolveParams& o
   rsum += ri;
 }
 
+// The HV variant's emit (include/gdmix_fe.h, "(ABI 24) TRON"). A product: rs_i = D_i (x_i . d + d_b) with the curvature weights the
+// evaluation of the accepted point left, no loss term. An evaluation: the residual and loss of fe_emit_row<false>, and next to them the
+// curvature weight of this point — w rho (1 - rho), 2 w or w exp(z) — for the products that follow if the point is accepted.
+__device__ __forceinline__ void fe_emit_row_hv(const FeDev& F, const SolveParams& o, int mode, double* __restrict__ cw, int s, double sum, double xb,
+                                               double& loss, double& loss_lo, double& rsum) {
+  double ri;
+  if (mode & 1) {
+    ri = cw[s] * (sum + xb);
+  } else {
+    const double zi = sum + xb + (double)F.o[s];
+    const double yi = (double)F.y[s];
+    const double wi = F.w ? (double)F.w[s] : 1.0;
+    double ci;
+    if (o.loss == LOSS_POISSON) {
+      dd_add(loss, loss_lo, poisson_terms(zi, yi, wi, ri));
+      ci = wi * exp_any(zi);
+    } else if (o.loss) {
+      const double e = zi - yi;
+      dd_add(loss, loss_lo, wi * e * e);
+      ri = 2.0 * wi * e;
+      ci = 2.0 * wi;
+    } else {
+      dd_add(loss, loss_lo, logistic_terms(zi, yi, wi, ri));
+      const double rho = sigmoid_full(zi);
+      ci = wi * rho * (1.0 - rho);
+    }
+    cw[s] = ci;
+  }
+  F.rs[s] = ri;
+  rsum += ri;
+}
+
+// what the HV variant of a row kernel reads at entry (uniform): the mode, the gathered vector, the intercept's entry, the curvature array
+struct FeHvEntry { int mode; bool run; const double* vec; double xb; double* cw; };
+__device__ __forceinline__ FeHvEntry fe_hv_entry(const FeDev& F) {
+  const FeTron T = fe_tron_of(F);
+  FeHvEntry e;
+  e.mode = T.st->mode;
+  e.run = e.mode >= FE_TM_CURVATURE || F.state->status < 0;      // the stop flag makes the solver's own pass pairs no-ops
+  e.vec = (e.mode & 1) ? T.vl : F.xl;
+  const bool second = (e.mode == FE_TM_PRODUCT) == (T.st->cur != 0);      // c[cur] for the solver's product, c[1 - cur] otherwise
+  e.cw = second ? T.c[1] : T.c[0];      // (a select, not an index: an array indexed at run time lives in scratch)
+  e.xb = 0.0;
+  if (F.ic) e.xb = e.mode == FE_TM_EVAL ? T.xt[F.D] : e.mode == FE_TM_PRODUCT ? T.d[F.D] : e.mode == FE_TM_CURVATURE ? F.W.x[F.D] : T.st->vb;
+  return e;
+}
+
 // acc[loc] += term, in LDS, nothing returned
 __device__ __forceinline__ void lds_add(double* acc, int loc, double term) {
   __hip_atomic_fetch_add(acc + loc, term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -154,9 +201,12 @@ __device__ __forceinline__ void fe_scatter_compressed(double* acc, const unsigne
   }
 }
 
-template <bool ROWS, bool HESS, bool PACKED, bool PRIOR = false>
+// HV (include/gdmix_fe.h, "(ABI 24) TRON"): the row pass of a TRON problem — an evaluation or a Hessian-vector product, whichever the
+// record says (fe_hv_entry); the column pass behind a product of gdmix_fe_hessian_vec, which runs whatever the status.
+template <bool ROWS, bool HESS, bool PACKED, bool PRIOR = false, bool HV = false>
 __global__ __launch_bounds__(WAVE) void fe_scatter_kernel(FeDev F, SolveParams o) {
   static_assert(ROWS || !PRIOR, "the column pass gathers residuals: it has no prior variant");
+  static_assert(!HV || (!HESS && !PRIOR), "the product has no Hessian-diagonal and no prior variant");
   // exactly 16 KiB: ten wavefronts per CU (160 KiB of LDS). Round 5: a spare accumulator for the lanes beyond the end of the last
   // trip made it 16 400 B = nine; those lanes now add 0.0 to accumulator 0 (x + 0.0 == x bit for bit; an accumulator that is still
   // -0.0 cannot occur: they start at +0.0). Measured: nine or ten makes no difference (0.556 ms either way, three runs each):
@@ -166,21 +216,27 @@ __global__ __launch_bounds__(WAVE) void fe_scatter_kernel(FeDev F, SolveParams o
   const FeCopy& C = ROWS ? F.rc : F.cc;
   const int u = C.order[blockIdx.x];
   if (u < 0) return;
-  if (!HESS && F.state->status >= 0) return;   // the driver has stopped: evaluations enqueued ahead of the status are no-ops
+  if (!HESS && !HV && F.state->status >= 0) return;   // the driver has stopped: evaluations enqueued ahead of the status are no-ops
+  FeHvEntry hv{};
+  if constexpr (HV && ROWS) {
+    hv = fe_hv_entry(F);
+    if (!hv.run) return;
+  }
   const int k0 = C.ustart[u], k1 = C.ustart[u + 1], b = C.ublock[u];
   const int kb = PACKED ? C.kbase[u] : 0;
   const bool whole = ROWS && (C.ufirst[b + 1] - C.ufirst[b] == 1);
-  const double xb = (ROWS && F.ic) ? fe_theta_of<PRIOR>(F, F.D, F.W.x[F.D]) : 0.0;
+  const double xb = (HV && ROWS) ? hv.xb : (ROWS && F.ic) ? fe_theta_of<PRIOR>(F, F.D, F.W.x[F.D]) : 0.0;
+  const double* __restrict__ gathered = (HV && ROWS) ? hv.vec : (ROWS ? F.xl : F.rs);
   const uint2* __restrict__ ent = C.ent;
   const int32_t* __restrict__ key = C.key;
   const float* __restrict__ val = C.val;
   const uint16_t* __restrict__ loc = C.loc;
-  const double* __restrict__ vec = (ROWS ? F.xl : F.rs) + kb;
+  const double* __restrict__ vec = gathered + kb;
 #pragma unroll
   for (int i = 0; i < FE_B / WAVE; i += 2) *reinterpret_cast<double2*>(acc + (i * WAVE + 2 * lane)) = make_double2(0.0, 0.0);
   const int64_t cb = C.cbase ? C.cbase[u] : -1;      // uniform
   if (cb >= 0) {
-    fe_scatter_compressed<ROWS, HESS>(acc, C.cdata + cb, C.ctrip[u], (ROWS ? F.xl : F.rs) + C.kbase[u], lane);   // (keys are relative to the unit's first in this form, always)
+    fe_scatter_compressed<ROWS, HESS>(acc, C.cdata + cb, C.ctrip[u], gathered + C.kbase[u], lane);   // (keys are relative to the unit's first in this form, always)
   } else {
   // full trips without a guard in sight (a load under a branch is waited for inside the branch); the last, partial trip
   // reads clamped addresses and sends what is beyond the end to a spare accumulator.
@@ -256,7 +312,10 @@ __global__ __launch_bounds__(WAVE) void fe_scatter_kernel(FeDev F, SolveParams o
     double loss = 0.0, loss_lo = 0.0, rsum = 0.0;
     const int r0 = b * FE_B;
     const int nr = (F.n - r0 < FE_B) ? F.n - r0 : FE_B;
-    for (int i = lane; i < nr; i += WAVE) fe_emit_row<HESS>(F, o, r0 + i, acc[i], xb, loss, loss_lo, rsum);
+    for (int i = lane; i < nr; i += WAVE) {
+      if constexpr (HV) fe_emit_row_hv(F, o, hv.mode, hv.cw, r0 + i, acc[i], xb, loss, loss_lo, rsum);
+      else fe_emit_row<HESS>(F, o, r0 + i, acc[i], xb, loss, loss_lo, rsum);
+    }
     wave_sum_dd(loss, loss_lo);
     rsum = wave_sum(rsum);
     if (lane == 0) { F.loss_part[u] = loss; F.loss_lo_part[u] = loss_lo; F.rsum_part[u] = rsum; }
@@ -299,18 +358,26 @@ __device__ __forceinline__ double fe_strand_sum(const double* __restrict__ part,
 
 // rows of the blocks that were cut into several units
 constexpr int FE_FIX_PER_BLOCK = FE_B / FE_RED_OUT;   // workgroups of fe_rows_fix_kernel per block
-template <bool HESS = false, bool PRIOR = false>
+template <bool HESS = false, bool PRIOR = false, bool HV = false>
 __global__ __launch_bounds__(FE_THREADS) void fe_rows_fix_kernel(FeDev F, SolveParams o) {
   __shared__ double lds[FE_STRANDS][FE_RED_OUT];
-  if (!HESS && F.state->status >= 0) return;
+  if (!HESS && !HV && F.state->status >= 0) return;
+  FeHvEntry hv{};
+  if constexpr (HV) {
+    hv = fe_hv_entry(F);
+    if (!hv.run) return;      // (uniform over the grid)
+  }
   const int tid = threadIdx.x, out = tid % FE_RED_OUT, strand = tid / FE_RED_OUT;
   const int b = F.multi[blockIdx.x / FE_FIX_PER_BLOCK];
   const int i = (blockIdx.x % FE_FIX_PER_BLOCK) * FE_RED_OUT + out;
   const int row = b * FE_B + i;
-  const double xb = F.ic ? fe_theta_of<PRIOR>(F, F.D, F.W.x[F.D]) : 0.0;
+  const double xb = HV ? hv.xb : F.ic ? fe_theta_of<PRIOR>(F, F.D, F.W.x[F.D]) : 0.0;
   const double t = fe_strand_sum(F.rc.part, F.rc.ufirst[b], F.rc.ufirst[b + 1], i, strand, lds, out);
   double loss = 0.0, loss_lo = 0.0, rsum = 0.0;
-  if (strand == 0 && row < F.n) fe_emit_row<HESS>(F, o, row, t, xb, loss, loss_lo, rsum);
+  if (strand == 0 && row < F.n) {
+    if constexpr (HV) fe_emit_row_hv(F, o, hv.mode, hv.cw, row, t, xb, loss, loss_lo, rsum);
+    else fe_emit_row<HESS>(F, o, row, t, xb, loss, loss_lo, rsum);
+  }
   if (tid < WAVE) {   // the outputs' threads are the first FE_RED_OUT lanes of wavefront 0
     wave_sum_dd(loss, loss_lo);
     rsum = wave_sum(rsum);
@@ -784,6 +851,8 @@ struct gdmix_fe_problem {
   DevBuf hot_mem;        // the frequent columns' list
   DevBuf prior_mem;      // [2 P] the problem's copy of the prior mean and scale, then the check's flag (gdmix_fe_set_prior); empty until the first prior
   double l1 = 0.0;       // weight of the L1 term (gdmix_fe_set_l1); > 0: the step is OWL-QN's (fe_owlqn.hip)
+  DevBuf tron_mem;       // the TRON buffer (fe_internal.hpp: FeTron); empty until TRON is first selected or gdmix_fe_hessian_vec first called
+  int optimizer = GDMIX_FE_OPT_LBFGS;      // gdmix_fe_set_optimizer; TRON: the pass pairs are the HV variant's, the step fe_tron.hip's
   int32_t* status_dev = nullptr;
   hipEvent_t ev[3] = {};
   bool timed = false;
@@ -842,6 +911,40 @@ static int fe_passes(gdmix_fe_problem* p, const FeDev& F, hipStream_t s, bool ti
   return GDMIX_RE_OK;
 }
 
+// The row pass of the HV variant: what it computes is the record's business (fe_hv_entry).
+static void fe_rows_hv(const FeDev& F, const SolveParams& o, hipStream_t s) {
+  with_flag(F.rc.ent != nullptr, [&](auto PK) { hipLaunchKernelGGL((fe_scatter_kernel<true, false, decltype(PK)::value, false, true>), dim3(F.rc.nlaunch), dim3(WAVE), 0, s, F, o); });
+  if (F.nmulti) hipLaunchKernelGGL((fe_rows_fix_kernel<false, false, true>), dim3(F.nmulti * FE_FIX_PER_BLOCK), dim3(FE_THREADS), 0, s, F, o);
+}
+
+// A pass pair of a TRON problem: the HV row pass, then the column pass and the finish of an evaluation, unchanged — they gather and add
+// up whatever the row pass left in rs, and stop on the same flag.
+static int fe_passes_tron(gdmix_fe_problem* p, hipStream_t s, bool timed) {
+  const FeDev& F = p->F;
+  if (p->dirty) HIP_TRY(hipMemsetAsync(F.fg, 0, ((size_t)F.P + 1) * 8, s));
+  p->dirty = true;
+  if (timed) HIP_TRY(hipEventRecord(p->ev[0], s));
+  fe_rows_hv(F, p->o, s);
+  if (timed) HIP_TRY(hipEventRecord(p->ev[1], s));
+  with_flag(F.cc.ent != nullptr, [&](auto PK) { hipLaunchKernelGGL((fe_scatter_kernel<false, false, decltype(PK)::value>), dim3(F.cc.nlaunch), dim3(WAVE), 0, s, F, p->o); });
+  if (timed) HIP_TRY(hipEventRecord(p->ev[2], s));
+  const int gf = (F.d + FE_RED_OUT - 1) / FE_RED_OUT;
+  hipLaunchKernelGGL(fe_finish_kernel<false>, dim3((gf < FE_FIN_BLOCKS ? FE_FIN_BLOCKS : gf) + F.hot.n), dim3(FE_THREADS), 0, s, F);
+  HIP_TRY(hipGetLastError());
+  return GDMIX_RE_OK;
+}
+
+// The TRON buffer, allocated on first need (the pool's size and layout do not depend on the optimiser).
+static int fe_tron_alloc(gdmix_fe_problem* p, hipStream_t s) {
+  if (p->tron_mem) return GDMIX_RE_OK;
+  const size_t bytes = fe_tron_bytes(p->F.P, p->F.d, p->F.n);
+  const hipError_t rc = p->tron_mem.alloc(bytes);
+  if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(rc)); return GDMIX_RE_ENOMEM; }
+  HIP_TRY(hipMemsetAsync(p->tron_mem.get(), 0, bytes, s));
+  p->F.W.part = p->tron_mem.as<double>();      // (fe_internal.hpp: fe_tron_state)
+  return GDMIX_RE_OK;
+}
+
 // The problem as gdmix_fe_create leaves it, at its current options and prior, from start point theta0 (gdmix_fe_restart, gdmix_fe_set_prior):
 // the pool is zeroed again but for the list of row blocks with several units, F.inv refilled, the start point and a fresh L-BFGS state
 // written by the same fe_init_kernel, the host's counters put back. Everything is enqueued behind whatever the stream still holds.
@@ -852,6 +955,7 @@ static int fe_reset(gdmix_fe_problem* p, const double* theta0, hipStream_t s) {
   HIP_TRY(hipMemsetAsync(base + p->pool_multi_end, 0, p->pool_bytes - p->pool_multi_end, s));
   HIP_TRY(hipMemsetAsync(base + p->pool_inv, 0xff, (size_t)F.P * 4, s));
   with_flag(F.mu != nullptr, [&](auto PR) { hipLaunchKernelGGL(fe_init_kernel<decltype(PR)::value>, dim3(grid_for(F.P, 256, 1024)), dim3(256), 0, s, F, theta0); });
+  if (fe_tron_state(F)) fe_tron_enqueue_reset(F, theta0, s);      // (also on a problem set back to L-BFGS-B: the record is what gdmix_fe_hessian_vec finds)
   HIP_TRY(hipGetLastError());
   p->timed = false;
   p->dirty = false;
@@ -981,6 +1085,10 @@ GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const 
   HIP_TRY(hipSetDevice(p->ctx->impl.device));
   FeDev& F = p->F;
   if (mean && p->l1 > 0.0) { set_error("gdmix_fe_set_prior: the problem has an L1 term (gdmix_fe_set_l1), which does not compose with a prior"); return GDMIX_RE_EINVAL; }
+  if (mean && p->optimizer == GDMIX_FE_OPT_TRON) {
+    set_error("gdmix_fe_set_prior: the problem's optimiser is TRON (gdmix_fe_set_optimizer), whose product has no prior variant yet");
+    return GDMIX_RE_EINVAL;
+  }
   if (!mean) {
     F.mu = nullptr; F.sc = nullptr;      // (the copy stays allocated: kernels of an earlier solve may still be queued on it)
     return fe_reset(p, nullptr, s);
@@ -1010,9 +1118,49 @@ GDMIX_API int gdmix_fe_set_l1(gdmix_fe_problem* p, double l1, void* stream) {
   if (!p) { set_error("problem is NULL"); return GDMIX_RE_EINVAL; }
   if (!(l1 >= 0.0) || l1 == __builtin_inf()) { set_error("gdmix_fe_set_l1: l1 must be finite and >= 0"); return GDMIX_RE_EINVAL; }
   if (p->F.mu) { set_error("gdmix_fe_set_l1: the problem has a prior (gdmix_fe_set_prior), which does not compose with an L1 term"); return GDMIX_RE_EINVAL; }
+  if (l1 > 0.0 && p->optimizer == GDMIX_FE_OPT_TRON) {
+    set_error("gdmix_fe_set_l1: the problem's optimiser is TRON (gdmix_fe_set_optimizer), which minimises a smooth objective: no L1 term");
+    return GDMIX_RE_EINVAL;
+  }
   HIP_TRY(hipSetDevice(p->ctx->impl.device));
   p->l1 = l1;
   return fe_reset(p, nullptr, static_cast<hipStream_t>(stream));
+}
+
+GDMIX_API int gdmix_fe_set_optimizer(gdmix_fe_problem* p, int optimizer, void* stream) {
+  if (!p) { set_error("problem is NULL"); return GDMIX_RE_EINVAL; }
+  if (optimizer != GDMIX_FE_OPT_LBFGS && optimizer != GDMIX_FE_OPT_TRON) {
+    set_error("gdmix_fe_set_optimizer: unknown optimiser %d (GDMIX_FE_OPT_LBFGS = %d, GDMIX_FE_OPT_TRON = %d)", optimizer, GDMIX_FE_OPT_LBFGS, GDMIX_FE_OPT_TRON);
+    return GDMIX_RE_EINVAL;
+  }
+  if (optimizer == GDMIX_FE_OPT_TRON && p->l1 > 0.0) {
+    set_error("gdmix_fe_set_optimizer: the problem has an L1 term (gdmix_fe_set_l1); TRON minimises a smooth objective");
+    return GDMIX_RE_EINVAL;
+  }
+  if (optimizer == GDMIX_FE_OPT_TRON && p->F.mu) {
+    set_error("gdmix_fe_set_optimizer: the problem has a prior (gdmix_fe_set_prior); TRON's product has no prior variant yet");
+    return GDMIX_RE_EINVAL;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(p->ctx->impl.device));
+  if (optimizer == GDMIX_FE_OPT_TRON) {
+    const int rc = fe_tron_alloc(p, s);
+    if (rc != GDMIX_RE_OK) return rc;
+  }
+  p->optimizer = optimizer;
+  return fe_reset(p, nullptr, s);
+}
+
+GDMIX_API int gdmix_fe_products(gdmix_fe_problem* p, int64_t* nhv, void* stream) {
+  if (!p || !nhv) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
+  *nhv = 0;
+  if (!fe_tron_state(p->F)) return GDMIX_RE_OK;      // never a TRON problem: no product taken
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  FeTronState st;
+  HIP_TRY(hipMemcpyAsync(&st, fe_tron_state(p->F), sizeof(st), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *nhv = (int64_t)st.nhv;
+  return GDMIX_RE_OK;
 }
 
 GDMIX_API void gdmix_fe_destroy(gdmix_fe_problem* p) {
@@ -1031,7 +1179,8 @@ GDMIX_API int gdmix_fe_eval(gdmix_fe_problem* p, void* stream) {
   // the first two evaluations of a problem are timed (gdmix_fe_last_eval_ms reports the second): with the status read a few steps
   // late the LAST evaluations of a solve are no-ops
   const bool timed = p->evals < 2;
-  const int rc = fe_passes<false>(p, p->F, static_cast<hipStream_t>(stream), timed, p->F.mu != nullptr);
+  const int rc = p->optimizer == GDMIX_FE_OPT_TRON ? fe_passes_tron(p, static_cast<hipStream_t>(stream), timed)
+                                                   : fe_passes<false>(p, p->F, static_cast<hipStream_t>(stream), timed, p->F.mu != nullptr);
   if (rc == GDMIX_RE_OK) { if (timed) p->timed = true; ++p->evals; }
   return rc;
 }
@@ -1043,6 +1192,44 @@ GDMIX_API int gdmix_fe_hessian_diag(gdmix_fe_problem* p, const double* theta, vo
   p->dirty = true;   // (a step enqueued behind the stop leaves the buffer as it was)
   // theta is in theta units whatever the problem holds: only the current point of a problem with a prior is phi
   return fe_passes<true>(p, F, static_cast<hipStream_t>(stream), false, !theta && F.mu != nullptr);
+}
+
+GDMIX_API int gdmix_fe_hessian_vec(gdmix_fe_problem* p, const double* theta, const double* v, void* stream) {
+  if (!p || !v) { set_error("NULL argument"); return GDMIX_RE_EINVAL; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(p->ctx->impl.device));
+  int rc = fe_tron_alloc(p, s);
+  if (rc != GDMIX_RE_OK) return rc;
+  FeDev F = p->F;
+  const bool prior = !theta && F.mu != nullptr;      // theta is in theta units; only the current point of a problem with a prior is phi
+  // the current accepted point of a TRON problem is W.x as well (fe_tron.hip); under the OWL-QN step it is W.t
+  if (theta) F.W.x = const_cast<double*>(theta);
+  else if (p->l1 > 0.0) F.W.x = F.W.t;
+  HIP_TRY(hipMemsetAsync(F.fg, 0, ((size_t)F.P + 1) * 8, s));
+  p->dirty = true;
+  const auto prepare = [&](const FeDev& G, bool with_prior) {
+    with_flag(with_prior, [&](auto PR) { hipLaunchKernelGGL(fe_prepare_kernel<decltype(PR)::value>, dim3(grid_for(G.d, 256, 2048)), dim3(256), 0, s, G); });
+  };
+  if (prior) {
+    // the HV row pass has no prior variant: theta = mu + s (.) phi is formed once, in the buffer's trial-point slot (a TRON problem has no prior)
+    double* th = fe_tron_of(F).xt;
+    hipLaunchKernelGGL(fe_prior_theta_kernel, dim3(grid_for(F.P, 256, 1024)), dim3(256), 0, s, F, th);
+    F.W.x = th;
+  }
+  prepare(F, false);
+  fe_tron_enqueue_hv_begin(F, s);
+  fe_rows_hv(F, p->o, s);                 // the curvature weights at theta
+  fe_tron_enqueue_hv_vector(F, v, s);
+  fe_rows_hv(F, p->o, s);                 // rs = D (X~ v)
+  with_flag(F.cc.ent != nullptr, [&](auto PK) { hipLaunchKernelGGL((fe_scatter_kernel<false, false, decltype(PK)::value, false, true>), dim3(F.cc.nlaunch), dim3(WAVE), 0, s, F, p->o); });
+  const int gf = (F.d + FE_RED_OUT - 1) / FE_RED_OUT;
+  hipLaunchKernelGGL(fe_finish_kernel<true>, dim3((gf < FE_FIN_BLOCKS ? FE_FIN_BLOCKS : gf) + F.hot.n), dim3(FE_THREADS), 0, s, F);
+  fe_tron_enqueue_hv_end(F, s);
+  // the solver's point back into xl: the trial point of a TRON problem, x otherwise
+  if (p->optimizer == GDMIX_FE_OPT_TRON) { FeDev G = p->F; G.W.x = fe_tron_of(G).xt; prepare(G, false); }
+  else prepare(p->F, p->F.mu != nullptr);
+  HIP_TRY(hipGetLastError());
+  return GDMIX_RE_OK;
 }
 
 GDMIX_API size_t gdmix_fe_hessian_dense_scratch_bytes(const gdmix_re_packed* shard) {
@@ -1087,11 +1274,12 @@ static int fe_enqueue_step(gdmix_fe_problem* p, hipStream_t s) {
   const FeDev& F = p->F;
   const int dot_blocks = grid_for(F.P, 256, FE_DOT_BLOCKS);
   const int tail_blocks = grid_for(dot_blocks, 1, p->ctx->impl.num_cus);      // at most one workgroup per CU: all resident, the wait inside cannot starve one
-  if (p->fused_tail && !(p->l1 > 0.0)) {
+  if (p->fused_tail && !(p->l1 > 0.0) && p->optimizer != GDMIX_FE_OPT_TRON) {
     ++p->gen;
     if (p->gen == 0u) ++p->gen;
   }
-  if (p->l1 > 0.0) fe_owlqn_enqueue_step(F, p->o, p->l1, p->status_dev, s);      // (never with a prior: gdmix_fe_set_l1)
+  if (p->optimizer == GDMIX_FE_OPT_TRON) fe_tron_enqueue_step(F, p->o, p->status_dev, s);      // (never with a prior or an L1 term: gdmix_fe_set_optimizer)
+  else if (p->l1 > 0.0) fe_owlqn_enqueue_step(F, p->o, p->l1, p->status_dev, s);      // (never with a prior: gdmix_fe_set_l1)
   else with_flag(F.mu != nullptr, [&](auto PR) {
     constexpr bool PRIOR = decltype(PR)::value;
     if (p->fused_tail) {

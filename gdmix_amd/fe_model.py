@@ -33,6 +33,11 @@ Not in the reference either, any number of workers:
        (include/gdmix_fe.h, "(ABI 23) L1 / elastic net"): coefficients outside the support are exactly 0 and stay out of the model file; the
        number of non-zeros is logged. Photon-ML's elastic net (lambda, alpha) is W = alpha lambda, l2_reg_weight = (1 - alpha) lambda.
        Refused with --l2_reg_weights, --incremental_training and --feature_normalization; --action=inference ignores it.
+  --optimizer=LBFGS|TRON   (case-insensitive; Photon-ML's OptimizerType; default LBFGS, a stage without the flag is bit for bit what it was)
+       TRON trains the stage by trust-region Newton on the device (include/gdmix_fe.h, "(ABI 24) TRON"): conjugate gradients on
+       Hessian-vector products, each the same two streaming passes as an evaluation. The number of products is logged. With
+       --l2_reg_weights the sweep keeps the optimiser. Refused with a non-zero --l1_reg_weight, --incremental_training and
+       --feature_normalization; --action=inference ignores it.
 """
 import glob
 import logging
@@ -90,6 +95,9 @@ class FixedLRParams(LRParams):
     # exactly 0 and stay out of the model file. Photon-ML's (lambda, alpha) is l1 = alpha lambda, l2 = (1 - alpha) lambda. 0: no L1 term.
     # --action=inference accepts and ignores the flag.
     l1_reg_weight: float = 0.0
+    # not in the reference: Photon-ML's OptimizerType. TRON: trust-region Newton on the device (include/gdmix_fe.h, "(ABI 24) TRON"); LBFGS: the
+    # stage as it was. Any case. --action=inference accepts and ignores the flag.
+    optimizer: str = "LBFGS"
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -124,6 +132,15 @@ class FixedLRParams(LRParams):
                     (self.normalization() != "none", "--feature_normalization", "the L1 term is not invariant under the change to normalised units")):
                 if is_set:
                     raise ValueError(f"--l1_reg_weight does not run with {flag}: {why}")
+        from .fixed_effect import TRON, check_optimizer
+        self.optimizer = check_optimizer(self.optimizer)
+        if self.optimizer == TRON:
+            for is_set, flag, why in (
+                    (self.l1_reg_weight > 0.0, "--l1_reg_weight", "TRON minimises a smooth objective; the L1 term has its own optimiser, OWL-QN"),
+                    (self.incremental_training, "--incremental_training", "the Hessian-vector product has no variant for the prior's change of variables yet"),
+                    (self.normalization() != "none", "--feature_normalization", "the Hessian-vector product has no variant for normalised units yet")):
+                if is_set:
+                    raise ValueError(f"--optimizer=TRON does not run with {flag}: {why}")
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         assert self.fixed_effect_variance_mode is None or self.fixed_effect_variance_mode in (constants.FULL, constants.SIMPLE), \
@@ -374,9 +391,14 @@ class FixedEffectLRModelLBFGS:
             *self._shard_arrays(data, fit=True), data["y"], self.num_features, l2_grid=grid, select=select, offset=data["offset"],
             weight=data["weight"] if data["has_weight"] else None, has_intercept=self.has_intercept, regularize_bias=self.is_regularize_bias, model_type=self.model_type, max_iter=self.max_iteration,
             m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
-            variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold, **self._down_sampling(data))
+            variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold, **self._optimizer(), **self._down_sampling(data))
         self.l2_reg_weight = self.model_params.l2_reg_weight = float(grid[best])
         return theta, info
+
+    def _optimizer(self):
+        """{"optimizer": ...} for fit_stepping / fit_sweep, or {} with the default: the call is then what it was before the flag existed."""
+        opt = self.model_params.optimizer
+        return {} if opt == "LBFGS" else {"optimizer": opt}
 
     # ---- train ----------------------------------------------------------------------------------------------------
     def train(self, training_data_dir, validation_data_dir, metadata_file, checkpoint_path, execution_context, schema_params):
@@ -422,6 +444,7 @@ class FixedEffectLRModelLBFGS:
             extra.update(self._down_sampling(data))
             if self.model_params.l1_reg_weight > 0.0:
                 extra["l1"] = self.model_params.l1_reg_weight
+            extra.update(self._optimizer())
             theta, info = self._solver().fit_stepping(
                 *self._shard_arrays(data, fit=True), data["y"], D, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
                 has_intercept=self.has_intercept, l2=self.l2_reg_weight, regularize_bias=self.is_regularize_bias,
@@ -439,6 +462,8 @@ class FixedEffectLRModelLBFGS:
         logger.info(f"f_min: {info['fval']} num of funcalls: {info['nfev']} status: {info['status']}")
         if self.model_params.l1_reg_weight > 0.0:
             logger.info(f"l1_reg_weight {self.model_params.l1_reg_weight}: {int(np.count_nonzero(theta))} of {theta.size} coefficients are non-zero")
+        if self._optimizer():
+            logger.info(f"optimizer {self.model_params.optimizer}: {info['nit']} iterations, {info['nfev']} evaluations, {info.get('nhv', 0)} Hessian-vector products")
         self.model_coefficients = theta = self._stage_coefficients(theta)
         # the reference's variance computation rides on the scoring pass over the training data, which therefore runs (and writes
         # its scores) whenever a variance mode is set (:650-661)

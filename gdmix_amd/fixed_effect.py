@@ -34,6 +34,16 @@ LOGISTIC_REGRESSION = "logistic_regression"
 LINEAR_REGRESSION = "linear_regression"
 POISSON_REGRESSION = "poisson_regression"      # loss exp(z) - y z on count labels (include/gdmix_fe.h, "poisson")
 LOSS_OF_MODEL_TYPE = {LOGISTIC_REGRESSION: "logistic", LINEAR_REGRESSION: "squared", POISSON_REGRESSION: "poisson"}
+LBFGS, TRON = "LBFGS", "TRON"                  # --optimizer (Photon-ML's OptimizerType); include/gdmix_fe.h, "(ABI 24) TRON"
+OPTIMIZER_CODE = {LBFGS: 0, TRON: 1}           # GDMIX_FE_OPT_LBFGS, GDMIX_FE_OPT_TRON
+
+
+def check_optimizer(value):
+    """'tron' -> 'TRON': one of Photon-ML's names, in any case."""
+    name = str(value).strip().upper()
+    if name not in OPTIMIZER_CODE:
+        raise ValueError(f"--optimizer={value!r}: one of {', '.join(OPTIMIZER_CODE)}")
+    return name
 
 
 def shard_as_batch(row_nnz_ptr, col_global, val, y, offset=None, weight=None, has_intercept=True, binary_labels=True,
@@ -166,7 +176,7 @@ class FixedEffectDeviceSolver:
     def fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
                      regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
                      group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0, prior=None, feature_scale=None,
-                     down_sampling=None, l1=0.0):
+                     down_sampling=None, l1=0.0, optimizer=LBFGS):
         """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
         worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
         model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
@@ -183,22 +193,32 @@ class FixedEffectDeviceSolver:
         holds the counts. Every worker passes the same rate and seed. Rate 1.0 is the plain fit.
         l1 > 0: the objective gains l1 |theta_R|_1 and the step is OWL-QN's (include/gdmix_fe.h, "(ABI 23) L1 / elastic net"); theta0 is its
         start point; not together with `prior` or `feature_scale`. Coefficients outside the support are exactly 0.0; info["nnz"] counts
-        the others. l1 = 0 is the plain fit: set_l1 is never called."""
+        the others. l1 = 0 is the plain fit: set_l1 is never called.
+        optimizer="TRON": the smooth objective is minimised by trust-region Newton on the device (include/gdmix_fe.h, "(ABI 24) TRON"); theta0
+        is its start point; not together with l1 > 0, `prior` or `feature_scale`. info["nhv"] counts the Hessian-vector products (0 under
+        "LBFGS", the plain fit: set_optimizer is never called), info["optimizer"] names the optimiser."""
+        optimizer = check_optimizer(optimizer)
         l1 = float(l1)
         if not (np.isfinite(l1) and l1 >= 0.0):
             raise ValueError(f"l1 must be finite and >= 0, not {l1}")
         if l1 > 0.0 and (prior is not None or feature_scale is not None):
             raise ValueError("the L1 term does not compose with a prior model or with feature normalisation")
+        if optimizer == TRON and (l1 > 0.0 or prior is not None or feature_scale is not None):
+            raise ValueError("TRON minimises the smooth objective in theta units: it does not run with an L1 term, a prior model or feature normalisation")
         opts = fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance)
         fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode,
                            prior=prior, feature_scale=feature_scale, down_sampling=down_sampling)
-        if l1 > 0.0:
+        if l1 > 0.0 or optimizer == TRON:
             t0 = fit.prob.theta0
-            fit.prob.set_l1(l1)      # (leaves the problem at zeros)
+            if l1 > 0.0:
+                fit.prob.set_l1(l1)      # (leaves the problem at zeros)
+            else:
+                fit.prob.set_optimizer(optimizer)
             if t0 is not None:
                 fit.prob.restart(opts, t0)
         theta, info = fit.stage_result(*fit.run(), l2, threshold)
         info["l1"] = l1
+        info["optimizer"] = optimizer
         info["nnz"] = int(np.count_nonzero(theta))
         if return_problem:
             return theta, info, fit.prob
@@ -207,24 +227,29 @@ class FixedEffectDeviceSolver:
 
     def fit_sweep(self, row_nnz_ptr, col_global, val, y, num_features, l2_grid, select, offset=None, weight=None, has_intercept=True,
                   regularize_bias=True, model_type=LOGISTIC_REGRESSION, max_iter=100, m=10, tolerance=1e-12, dummy=None, variance_mode=None,
-                  threshold=0.0, down_sampling=None):
+                  threshold=0.0, down_sampling=None, optimizer=LBFGS):
         """One worker's fit for every weight of l2_grid on ONE problem: the shard is packed and gdmix_fe_create runs once; per weight, in the
         order given, gdmix_fe_restart (cold: zeros) + the same loop and status check as fit_stepping — by the restart's contract the bits
         of a fresh fit_stepping at that weight. select(thetas) — the K coefficient vectors as fit_stepping would have returned them — names
         the winner; -> (theta, info, best) of the winner as fit_stepping returns them, its variances (at its weight, for it alone) included.
-        down_sampling: as fit_stepping takes it; the shard is sampled once, in front of the one pack."""
+        down_sampling: as fit_stepping takes it; the shard is sampled once, in front of the one pack. optimizer: as fit_stepping takes it;
+        the restarts keep it."""
         import dataclasses
+        optimizer = check_optimizer(optimizer)
         if _world_size(None) > 1:
             raise ValueError("a sweep over l2_reg_weight runs on one worker")
         opts = fit_options(has_intercept, float(l2_grid[0]), regularize_bias, model_type, max_iter, m, tolerance)
         fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, None, None, dummy, variance_mode,
                            down_sampling=down_sampling)
         try:
+            if optimizer == TRON:
+                fit.prob.set_optimizer(optimizer)
             fits = []
             for w in l2_grid:
                 fit.prob.restart(dataclasses.replace(opts, l2=float(w)), None)
                 fits.append(fit.run())
             best = int(select([fit.strip_dummy(th) for th, _ in fits]))
+            fits[best][1]["optimizer"] = optimizer
             return fit.stage_result(*fits[best], l2_grid[best], threshold) + (best,)
         finally:
             fit.prob.close()
@@ -373,6 +398,31 @@ class _SteppingProblem:
         its current options at zeros does. Stream-ordered."""
         self._check(self.lib.gdmix_fe_set_l1(self._h, float(l1), self.solver._stream()), "gdmix_fe_set_l1")
         self.theta0 = None
+
+    def set_optimizer(self, optimizer):
+        """gdmix_fe_set_optimizer: "TRON" puts the problem on the trust-region Newton step, "LBFGS" back on the L-BFGS-B step. Leaves the
+        problem as a restart with its current options at zeros does. Stream-ordered."""
+        self._check(self.lib.gdmix_fe_set_optimizer(self._h, OPTIMIZER_CODE[check_optimizer(optimizer)], self.solver._stream()), "gdmix_fe_set_optimizer")
+        self.theta0 = None
+
+    def products(self):
+        """Hessian-vector products the problem has taken since its last restart (gdmix_fe_products); 0 on a problem that never was TRON's."""
+        n = C.c_int64(0)
+        self._check(self.lib.gdmix_fe_products(self._h, C.byref(n), self.solver._stream()), "gdmix_fe_products")
+        return int(n.value)
+
+    def hessian_vec(self, theta_dev, v_dev):
+        """X~' D X~ v of the shard at theta (device tensors [D + has_intercept], intercept last; theta None = the current accepted point)
+        into the reduce buffer, no regulariser (gdmix_fe_hessian_vec)."""
+        for x in (theta_dev, v_dev):
+            if x is not None and (not x.is_cuda or x.dtype != self.solver.torch.float64 or not x.is_contiguous() or x.numel() != self.count - 1):
+                from .solver import GdmixReError
+                raise GdmixReError(f"a coefficient vector is a contiguous float64 device array of {self.count - 1} entries (intercept last)")
+        if v_dev is None:
+            from .solver import GdmixReError
+            raise GdmixReError("hessian_vec: v is None")
+        self._check(self.lib.gdmix_fe_hessian_vec(self._h, None if theta_dev is None else theta_dev.data_ptr(), v_dev.data_ptr(), self.solver._stream()),
+                    "gdmix_fe_hessian_vec")
 
     def reduce_tensor(self):
         """The [gradient, value] buffer as a torch tensor view (no copy), for torch.distributed.all_reduce."""
@@ -617,6 +667,7 @@ class _SteppingFit:
         status = run_stepping_loop(self.prob, self.all_reduce)
         theta, info = self.prob.result()
         info["status"] = status
+        info["nhv"] = self.prob.products()
         return theta, info
 
     def strip_dummy(self, x):

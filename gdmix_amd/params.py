@@ -183,6 +183,9 @@ class REParams(LRParams):
     # the fixed-effect stage's flag (fe_model.FixedLRParams). This stage's parser ignores flags it does not know, so the field exists to
     # refuse a non-zero value instead of training a ridge model in silence.
     l1_reg_weight: float = 0.0
+    # ... and so is --optimizer: anything but LBFGS is refused. The random-effect kernels run scipy's L-BFGS-B loop on chip; a trust-region
+    # Newton solver inside them is another project.
+    optimizer: str = "LBFGS"
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -196,6 +199,8 @@ class REParams(LRParams):
         self.l2_grid()      # a bad list is an error at parse time
         if check_l1_reg_weight(self.l1_reg_weight) != 0.0:
             raise ValueError(f"--l1_reg_weight={self.l1_reg_weight}: the random effect has no L1 term (the flag belongs to the fixed-effect stage)")
+        if str(self.optimizer).strip().upper() != "LBFGS":
+            raise ValueError(f"--optimizer={self.optimizer}: the random effect trains by L-BFGS-B only (the flag belongs to the fixed-effect stage)")
         check_feature_normalization(self, (
             (self.incremental_training, "--incremental_training", "prior variances are in the original feature units, and composing the two is not implemented"),
             (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep in normalised units is not implemented"),

@@ -236,6 +236,57 @@ GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const 
  * coefficient, not whether it was selected). */
 GDMIX_API int gdmix_fe_set_l1(gdmix_fe_problem* p, double l1, void* stream);
 
+/* ---- (ABI 24) TRON: trust-region Newton ------------------------------------------------------------------------------------------------------
+ * --optimizer=TRON (gdmix_amd/fe_model.py; Photon-ML's OptimizerType = TRON; Lin, Weng & Keerthi 2008, LIBLINEAR's tron) minimises the smooth
+ *     F(theta) = sum_i w_i l(y_i, x_i . w + b + offset_i) + (l2/2) |theta_R|^2
+ * of any of the three losses by Newton steps inside a trust region, each found by conjugate gradients on Hessian-vector products
+ *     H v = X~' D X~ v + l2 v_R,   D_i = w_i rho_i (1 - rho_i) | 2 w_i | w_i exp(z_i)   (logistic | squared | Poisson).
+ * A product is the same two streaming passes as an evaluation: the row pass gathers v instead of theta and a finished row leaves
+ * D_i (x_i . v + v_b) instead of the residual; the column pass is the evaluation's. It needs no exp and no log: D_i is written by the
+ * evaluation of the point it belongs to. An evaluation runs at a trial point, so there are two arrays of weights and a word that says which
+ * is the accepted point's; the step flips it on acceptance, and a rejected trial leaves the accepted point's weights in force.
+ * gdmix_fe_set_optimizer: GDMIX_FE_OPT_LBFGS (the default of gdmix_fe_create) or GDMIX_FE_OPT_TRON; stream-ordered; leaves the problem in the
+ *   state of a gdmix_fe_restart with its current options at zeros, like gdmix_fe_set_l1. gdmix_fe_restart keeps the optimiser; its theta0 is
+ *   the start point. The first selection of TRON allocates a buffer of the problem's own (6 P + d + 2 n doubles); the pool does not change.
+ *   Refused with GDMIX_RE_EINVAL: TRON while l1 > 0, and gdmix_fe_set_l1 > 0 on a TRON problem (the objective must be smooth); TRON while a
+ *   prior is installed, and gdmix_fe_set_prior with a prior on a TRON problem. The substitution phi = (theta - mu) / s for TRON is a
+ *   follow-up, per-coefficient work only: gather s_j d_j and scale the reduced product by s_j. A refused call leaves the problem as it was.
+ * What a pass pair of a TRON problem computes — an evaluation at the trial point or a product with the CG direction — is decided on the
+ * device: the step writes a mode word, the row kernels read it at entry. gdmix_fe_eval therefore launches the same kernels every time, the
+ * loop "eval; all-reduce; step" with its lookahead, status ring and stop flag is the one of the other steps, the step leaves the reduce
+ * buffer cleared, and -inf in the value slot stops every worker with GDMIX_RE_ST_ABORTED_PEER. After a product the buffer holds
+ * [X~' D X~ d, 0]; l2 d_R is added once, in the step, behind the reduce.
+ * The step. g, f: gradient and value of F (with the l2 term) at the accepted point x; norms are 2-norms unless marked.
+ *   start     evaluate at x0 (nfev = 1). |g|_inf <= pgtol -> status 0 with nit = 0. Delta = |g|.
+ *   CG        (Steihaug) s = 0, r = -g, d = r. Per product: Hd; alpha = r'r / d'Hd. If d'Hd <= 0 or |s + alpha d| > Delta (taken as
+ *             s's + 2 alpha s'd + alpha^2 d'd > Delta^2): go to the boundary with the non-negative root tau of |s + tau d| = Delta,
+ *             rad = sqrt((s'd)^2 + d'd (Delta^2 - s's)), tau = (Delta^2 - s's) / (s'd + rad) if s'd >= 0, else (rad - s'd) / d'd;
+ *             s += tau d, r -= tau Hd, and CG ends. Else s += alpha d, r -= alpha Hd with r'r_new taken as
+ *             max(0, r'r - 2 alpha r'Hd + alpha^2 Hd'Hd); CG ends if |r_new| <= 0.1 |g| or after GDMIX_FE_TRON_MAX_CG products in this outer
+ *             iteration (this feature's own cap); else d = r + (r'r_new / r'r) d.
+ *   trial     prered = -(g's - s'r) / 2. Evaluate at x + s; actred = f - f_new. On every trial before the first accepted step
+ *             Delta = min(Delta, |s|). ah = 4 if f_new - f - g's <= 0, else max(0.25, -(g's / (f_new - f - g's)) / 2).
+ *   radius    actred < 1e-4 prered (or not a number): Delta = min(max(ah, 0.25) |s|, Delta / 2); else if actred < prered / 4:
+ *             Delta = max(Delta / 4, min(ah |s|, Delta / 2)); else if actred < 3 prered / 4: Delta = max(Delta / 4, min(ah |s|, 4 Delta));
+ *             else Delta = max(Delta, min(ah |s|, 4 Delta)).
+ *   accept    iff actred > 1e-4 prered: x, f, g move, the curvature word flips, nit += 1. A rejected trial starts CG again from the same
+ *             x, g with the new Delta.
+ *   stops     after an accepted step, in this order: |g|_inf <= pgtol -> 0; f_old - f <= ftol max(|f_old|, |f|, 1) -> 1; nit >= max_iter -> 2;
+ *             nfev > maxfun -> 3. After a rejected trial: nfev > maxfun -> 3; maxls consecutive rejections -> 4, at the accepted point.
+ * nfev counts evaluations only; products are counted apart (gdmix_fe_products). gdmix_fe_result returns the last accepted point, fval = F,
+ * gnorm = |g|_inf, nit, nfev. gdmix_fe_last_eval_ms: on a TRON problem the timed second pass pair is the first product.
+ * gdmix_fe_hessian_vec, the sibling of gdmix_fe_hessian_diag: leaves the data term's X~' D X~ v of the shard at theta (device pointers
+ *   [D + has_intercept], intercept last; theta NULL: the current accepted point) in the reduce buffer — the intercept's entry last of the
+ *   coefficients, the value slot 0, no regulariser; the same all-reduce as an evaluation makes it the whole data set's. On any problem,
+ *   TRON or not (it allocates the buffer if need be and computes the weights at theta itself: two row passes, one column pass), between a
+ *   step and the next gdmix_fe_eval; it puts the solver's point and mode back, so that a solve gives the bits it gives without the call. */
+#define GDMIX_FE_OPT_LBFGS 0
+#define GDMIX_FE_OPT_TRON 1
+#define GDMIX_FE_TRON_MAX_CG 50
+GDMIX_API int gdmix_fe_set_optimizer(gdmix_fe_problem* p, int optimizer, void* stream);
+GDMIX_API int gdmix_fe_products(gdmix_fe_problem* p, int64_t* nhv, void* stream);
+GDMIX_API int gdmix_fe_hessian_vec(gdmix_fe_problem* p, const double* theta, const double* v, void* stream);
+
 /* gdmix_fe_score under K coefficient vectors in ONE pass over the shard's non-zeros (csrc/fe_sweep.hip). thetas: HOST array of K device
  * pointers, each [num_features + has_intercept] with the intercept last; score / per_coord: [K][n] float, row k for thetas[k]
  * (per_coord may be NULL). Defined by equivalence: row k is bit for bit what gdmix_fe_score writes for thetas[k] — a row's products
