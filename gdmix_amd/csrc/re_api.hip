@@ -408,6 +408,7 @@ GDMIX_API int gdmix_re_create(int hip_device, gdmix_re_ctx** out) {
   c->impl.eval_small_set = 0; c->impl.eval_small_max = 64;
   c->impl.eval_tmp = nullptr; c->impl.eval_tmp_bytes = 0;
   c->impl.sel_small_set = 0; c->impl.sel_small_max = 1024; c->impl.sel_plan_ws = nullptr;
+  c->impl.cap_small_set = 0; c->impl.cap_small_max = 128; c->impl.cap_plan_ws = nullptr;
   c->impl.n_side = 0; c->impl.side_fork = nullptr;
   c->impl.aux_ev[0] = c->impl.aux_ev[1] = nullptr;
   c->impl.defer_unique = 0; c->impl.unique_pending = false; c->impl.unique_ev = nullptr;

@@ -333,6 +333,11 @@ struct gdmix_ctx_impl {
   int sel_small_set, sel_small_max;
   const void* sel_plan_ws;
   int64_t sel_plan_E, sel_plan_N, sel_plan_Z, sel_plan_D, sel_plan_nnz;
+  // active-data cap (re_cap.hip): gdmix_re_set_cap_small_max was called / its value (otherwise 128); the workspace, the dimensions, the
+  // bound and the totals of the last gdmix_re_cap_plan of this context (cap_plan_ws == nullptr: no plan yet)
+  int cap_small_set, cap_small_max;
+  const void* cap_plan_ws;
+  int64_t cap_plan_rows, cap_plan_entities, cap_plan_bound, cap_plan_kept, cap_plan_nnz;
 };
 
 // A few bytes from the device to the host WITHOUT a stream synchronise (round 5). The counts a pack or a solve decides its next

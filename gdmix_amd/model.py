@@ -772,6 +772,46 @@ class RandomEffectLRLBFGSModel:
                 v.record_stream(cur)
         return solver.pack(solver.widen(raw) if "ent_n" in raw else raw, has_intercept=self.has_intercept)
 
+    def _cap_bound(self):
+        """The value of --active_data_upper_bound, or None without the flag."""
+        return getattr(self.model_params, "active_data_upper_bound", None)
+
+    def _raw_device(self, solver, batch):
+        """The raw (64-bit) form of a partition in HBM — the dict gdmix_re_pack takes: its copy when _read_ahead made one, uploaded now
+        otherwise; widened on the device when it travelled in the wire form."""
+        ahead = batch.__dict__.pop("_device", None)
+        if ahead is None:
+            return solver.widen(solver.upload_wire(batch.to_wire())) if isinstance(batch, WireRawBatch) else solver.upload(batch)
+        import torch
+        raw, ev = ahead
+        cur = torch.cuda.current_stream(solver.device)
+        cur.wait_event(ev)
+        for v in raw.values():       # allocated on the upload stream, used (and later freed) on this one
+            if isinstance(v, torch.Tensor):
+                v.record_stream(cur)
+        return solver.widen(raw) if "ent_n" in raw else raw
+
+    def _pack_capped(self, solver, batch, bound):
+        """gdmix_re_pack of the partition under --active_data_upper_bound: the raw batch in HBM loses, per entity of more than `bound`
+        rows, all but `bound` of them, the kept ones weighted n_e / bound (include/gdmix_re.h, "active-data cap"), and is packed then.
+        Only this batch is cut: the partition's scores and metrics are taken over every row of `batch`."""
+        if not isinstance(solver, REDeviceSolver):
+            raise RuntimeError("--active_data_upper_bound runs on the device solver only (there is no CPU fallback)")
+        if batch.uid is None:
+            raise KeyError("--active_data_upper_bound needs the uid column: the sample is chosen by a hash of (seed, uid)")
+        seed = int(getattr(self.model_params, "active_data_seed", 0))
+        raw = self._raw_device(solver, batch)
+        capped, counts = solver.cap_samples(raw, batch.uid, bound, seed=seed)
+        if not self.model_params.disable_random_effect_scoring_after_training:
+            import torch
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(solver.device))
+            batch._device = (raw, ev)      # every row stays in HBM for the scoring pass of this partition (_pack)
+        logger.info(f"active-data cap at {bound}: {counts['capped']} of {counts['entities']} entities capped, {counts['kept']} of {counts['rows']} rows "
+                    f"kept, largest entity {counts['largest']} rows before the cap")
+        self.last_cap_counts = counts
+        return solver.pack(capped, has_intercept=self.has_intercept)
+
     def _select_ratio(self):
         """The value of --features_to_samples_ratio, or None without the flag."""
         return getattr(self.model_params, "features_to_samples_ratio", None)
@@ -779,8 +819,10 @@ class RandomEffectLRLBFGSModel:
     def _pack_for_training(self, solver, batch):
         """The batch the solve sees. With --features_to_samples_ratio: pack, choose every entity's features on the packed batch, filter the
         raw non-zeros in HBM and pack again (include/gdmix_re.h, "feature selection"); only this batch is filtered, so a dropped feature is
-        from here on — model file, starting point, variances, scores — a feature the entity's data does not contain."""
-        packed = self._pack(solver, batch)
+        from here on — model file, starting point, variances, scores — a feature the entity's data does not contain. With
+        --active_data_upper_bound the cap runs first, on the raw batch in HBM, and the selection then sees the capped batch."""
+        bound = self._cap_bound()
+        packed = self._pack(solver, batch) if bound is None else self._pack_capped(solver, batch, bound)
         ratio = self._select_ratio()
         if ratio is None:
             return packed
@@ -840,7 +882,7 @@ class RandomEffectLRLBFGSModel:
         between any two batch compositions: include/gdmix_re.h). -> the number of partitions taken (0: not grouping)."""
         self._group = None      # (what an unused group decoded stays in _decoded / _prefetched for _read)
         if GROUP_MAX < 2 or len(input_paths) < 2 or self._io_pool is None or self.model_params.rebalance_entities \
-                or not self._wants_wire() or self._select_ratio() is not None:      # (the selection logs its counts per partition)
+                or not self._wants_wire() or self._select_ratio() is not None or self._cap_bound() is not None:      # (the selection and the cap log their counts per partition)
             return 0
         if self._solver is None:
             try:
@@ -1092,6 +1134,8 @@ class RandomEffectLRLBFGSModel:
             theta_dev = getattr(solved, "theta_thr", None)    # still in HBM: what the scoring pass of this partition reads
             stats = {k: res[k] for k in self._STAT_KEYS}
         resident = None if packed is None else (packed, theta_dev if theta_dev is not None else theta_thr)
+        if self._cap_bound() is not None:
+            resident = None     # the solver's pack lacks the passive rows: the partition is scored from a pack of every row
         return theta_thr, variance, uniq, feat_ptr, stats, resident
 
     def _start_point(self, model_weights, entity_ids, uniq, feat_ptr, E, num_features):

@@ -43,6 +43,19 @@ def check_features_to_samples_ratio(p, stage_flags):
     return ratio
 
 
+def check_active_data_upper_bound(p, stage_flags):
+    """--active_data_upper_bound of a random-effect stage's parameters: an integer >= 1, and none of the stage's flags the cap does not
+    run with, given as (set?, flag, why). -> the bound, or None without the flag."""
+    if p.active_data_upper_bound is None:
+        return None
+    from . import active_data
+    bound = active_data.check_upper_bound(p.active_data_upper_bound)
+    for is_set, flag, why in stage_flags:
+        if is_set:
+            raise ValueError(f"--active_data_upper_bound does not run with {flag}: {why}")
+    return bound
+
+
 def check_l1_reg_weight(value):
     """--l1_reg_weight: a finite weight >= 0 -> float."""
     try:
@@ -180,6 +193,12 @@ class REParams(LRParams):
     # selection"; feature_selection.py). The intercept is kept apart and takes no slot (in Photon-ML it takes one). A dropped feature is
     # from there on a feature the entity's data does not contain. --action=inference accepts and ignores the flag.
     features_to_samples_ratio: Optional[float] = None
+    # not in the reference (Photon-ML's activeDataUpperBound): an entity of more than this many samples trains on a uniform sample of that
+    # many, each weighted n_e / bound, chosen by a hash of (active_data_seed, uid) (include/gdmix_re.h, "active-data cap"; active_data.py).
+    # Only the solver's batch is cut: scores and metrics see every row. Runs before the feature selection, which then sees the capped
+    # batch. --action=inference accepts and ignores both flags.
+    active_data_upper_bound: Optional[int] = None
+    active_data_seed: int = 0
     # the fixed-effect stage's flag (fe_model.FixedLRParams). This stage's parser ignores flags it does not know, so the field exists to
     # refuse a non-zero value instead of training a ridge model in silence.
     l1_reg_weight: float = 0.0
@@ -210,6 +229,13 @@ class REParams(LRParams):
             (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep over selected features is not implemented"),
             (self.feature_normalization not in (None, "none"), "--feature_normalization", "the correlation is taken in the original feature units, and composing the two is not implemented"),
             (self.rebalance_entities, "--rebalance_entities", "the selection does not travel with the exchange")))
+        bound = check_active_data_upper_bound(self, (
+            (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep over capped entities is not implemented"),
+            (self.rebalance_entities, "--rebalance_entities", "sample uids do not travel with the exchange"),
+            (self.incremental_training, "--incremental_training", "the prior precisions were fitted on uncapped data, and composing the two is not implemented"),
+            (self.feature_normalization not in (None, "none"), "--feature_normalization", "the column statistics are those of the uncapped data, and composing the two is not implemented")))
+        if bound is not None:
+            self.active_data_upper_bound = bound
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         if self.incremental_training and self.rebalance_entities:

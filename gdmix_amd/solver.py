@@ -106,6 +106,15 @@ class _DownsampleOut(C.Structure):
                 ("val", C.c_void_p), ("y", C.c_void_p), ("offset", C.c_void_p), ("weight", C.c_void_p)]
 
 
+class _CapOpts(C.Structure):
+    _fields_ = [("upper_bound", C.c_int64), ("seed", C.c_uint64)]
+
+
+class _CapCounts(C.Structure):
+    _fields_ = [("entities", C.c_int64), ("capped", C.c_int64), ("rows", C.c_int64), ("kept", C.c_int64), ("kept_nnz", C.c_int64),
+                ("largest", C.c_int64)]
+
+
 class _SelectCounts(C.Structure):
     _fields_ = [("entities", C.c_int64), ("affected", C.c_int64), ("features", C.c_int64), ("kept", C.c_int64), ("dropped", C.c_int64),
                 ("kept_nnz", C.c_int64)]
@@ -135,6 +144,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_feature_extent", "gdmix_re_feature_moments", "gdmix_re_feature_scale_expand",
     "gdmix_re_downsample_workspace_bytes", "gdmix_re_downsample_plan", "gdmix_re_downsample_apply",
     "gdmix_re_select_workspace_bytes", "gdmix_re_select_plan", "gdmix_re_select_apply", "gdmix_re_set_select_small_max",
+    "gdmix_re_cap_workspace_bytes", "gdmix_re_cap_plan", "gdmix_re_cap_apply", "gdmix_re_set_cap_small_max",
     "gdmix_re_class_kernel_name", "gdmix_java_string_hash", "gdmix_java_partition_id",
     "gdmix_java_partition_ids_i64")
 
@@ -281,7 +291,14 @@ def load_library():
                                          C.POINTER(_SelectCounts), C.c_void_p]
     lib.gdmix_re_select_apply.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.POINTER(_Packed), C.c_void_p, C.POINTER(_SelectOut), C.c_void_p]
     lib.gdmix_re_set_select_small_max.argtypes = [C.c_void_p, C.c_int]
-    if lib.gdmix_re_abi_version() != 24:
+    lib.gdmix_re_cap_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.gdmix_re_cap_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_cap_plan.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.c_void_p, C.POINTER(_CapOpts), C.c_void_p, C.c_size_t, C.POINTER(_CapCounts),
+                                      C.c_void_p]
+    lib.gdmix_re_cap_apply.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.POINTER(_CapOpts), C.c_void_p, C.c_size_t, C.POINTER(_DownsampleOut),
+                                       C.c_void_p, C.c_void_p]
+    lib.gdmix_re_set_cap_small_max.argtypes = [C.c_void_p, C.c_int]
+    if lib.gdmix_re_abi_version() != 25:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib
@@ -777,6 +794,49 @@ class REDeviceSolver:
         _check(self.lib.gdmix_re_downsample_apply(self._h, C.byref(c_raw), C.byref(c_opts), ws.data_ptr(), nbytes, C.byref(c_out),
                                                   ptr(d["kept_rows"]), st), "gdmix_re_downsample_apply")
         counts = {k: int(getattr(c_counts, k)) for k in ("rows", "kept", "kept_nnz", "positives", "negatives_kept")}
+        return d, counts
+
+    # ---- the active-data cap in front of the pack (include/gdmix_re.h, "active-data cap"; gdmix_amd/active_data.py states it in numpy) -------
+    CAP_SMALL_MAX_DEFAULT, CAP_SMALL_MAX_LIMIT = 128, 1024
+
+    def set_cap_small_max(self, small_max: int):
+        """Where the two paths part: capped entities of more than small_max rows take the radix-select path instead of ranking by counting
+        (0 .. 1024; the flags do not depend on it)."""
+        _check(self.lib.gdmix_re_set_cap_small_max(self._h, int(small_max)), "set_cap_small_max")
+
+    @_serialised
+    def cap_samples(self, raw, uid, upper_bound, seed=0):
+        """gdmix_re_cap_plan + _apply on a raw device batch (the dict upload() / widen() return): an entity of more than upper_bound rows
+        keeps the upper_bound rows smallest by (key(seed, uid), row), each with weight w n_e / upper_bound; every other entity keeps its
+        rows as they are. uid: [N] int64, numpy or a device tensor. -> (a device dict of the shape upload() returns, so that pack() takes it
+        as is, with "kept_rows" [N_out] int32 besides: the source row of each kept row; counts: dict(entities, capped, rows, kept, kept_nnz,
+        largest))."""
+        t = self.torch
+        E, N, Z = int(raw["E"]), int(raw["N"]), int(raw["Z"])
+        if isinstance(uid, np.ndarray):
+            uid = t.from_numpy(np.ascontiguousarray(uid, np.int64)).to(self.device)
+        if uid.dtype != t.int64 or uid.numel() != N or not uid.is_cuda or not uid.is_contiguous():
+            raise GdmixReError(f"cap_samples: uid must be a contiguous int64 array of {N} entries")
+        ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()
+        c_raw = _RawBatch(E, N, Z, raw["ent_row_ptr"].data_ptr(), raw["row_nnz_ptr"].data_ptr(), ptr(raw["col_global"]),
+                          ptr(raw["val"]), ptr(raw["y"]), ptr(raw["offset"]), ptr(raw["weight"]))
+        c_opts = _CapOpts(int(upper_bound), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        nbytes = int(self.lib.gdmix_re_cap_workspace_bytes(E, N))
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=self.device)
+        c_counts = _CapCounts()
+        st = self._stream()
+        _check(self.lib.gdmix_re_cap_plan(self._h, C.byref(c_raw), ptr(uid), C.byref(c_opts), ws.data_ptr(), nbytes, C.byref(c_counts), st),
+               "gdmix_re_cap_plan")
+        n_out, z_out = int(c_counts.kept), int(c_counts.kept_nnz)
+        new = lambda count, dtype: t.empty(count, dtype=dtype, device=self.device)
+        d = dict(E=E, N=n_out, Z=z_out, ent_row_ptr=new(E + 1, t.int64), row_nnz_ptr=new(n_out + 1, t.int64), col_global=new(z_out, t.int64),
+                 val=new(z_out, t.float32), y=new(n_out, t.float32), offset=new(n_out, t.float32), weight=new(n_out, t.float32),
+                 kept_rows=new(n_out, t.int32))
+        c_out = _DownsampleOut(n_out, z_out, d["ent_row_ptr"].data_ptr(), d["row_nnz_ptr"].data_ptr(), ptr(d["col_global"]), ptr(d["val"]),
+                               ptr(d["y"]), ptr(d["offset"]), ptr(d["weight"]))
+        _check(self.lib.gdmix_re_cap_apply(self._h, C.byref(c_raw), C.byref(c_opts), ws.data_ptr(), nbytes, C.byref(c_out), ptr(d["kept_rows"]), st),
+               "gdmix_re_cap_apply")
+        counts = {k: int(getattr(c_counts, k)) for k in ("entities", "capped", "rows", "kept", "kept_nnz", "largest")}
         return d, counts
 
     # ---- feature selection between two packs (include/gdmix_re.h, "feature selection"; gdmix_amd/feature_selection.py states it in numpy) ---

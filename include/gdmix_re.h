@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 24
+#define GDMIX_RE_ABI_VERSION 25
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -655,7 +655,8 @@ GDMIX_API int gdmix_re_feature_scale_expand(gdmix_re_ctx* ctx, const gdmix_re_pa
  * the reference): the stage trains on a sample of its shard that keeps every positive (logistic loss) and a negative with probability
  * `rate`, kept negatives weighted 1 / rate, so that the objective stays an unbiased estimate of the full one and l2_reg_weight keeps its
  * meaning. csrc/re_downsample.hip; a pass over a gdmix_re_raw_batch (any E) in front of gdmix_re_pack, of which no pack or solve kernel
- * knows. The random-effect stage has no such flag (an entity could lose all its rows; a follow-up).
+ * knows. The random-effect stage has no such flag (an entity could lose all its rows); what it has is a cap on every entity's rows, which
+ * can never empty one: "(ABI 25) active-data cap" below.
  *
  * Definition. All arithmetic on unsigned 64-bit integers, wrapping.
  *     mix(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  x = (x ^ (x >> 27)) * 0x94D049BB133111EB;
@@ -774,6 +775,64 @@ GDMIX_API int gdmix_re_select_apply(gdmix_re_ctx* ctx, const gdmix_re_raw_batch*
                                     const gdmix_re_select_out* out_dev, void* stream);
 /* Testing knob: entities of more than `small_max` features take the sort path (0 => every entity that has a feature). 0 .. 1024, default 1024. */
 GDMIX_API int gdmix_re_set_select_small_max(gdmix_re_ctx* ctx, int small_max);
+
+/* ---- (ABI 25) active-data cap: at most K rows of every entity, a uniform sample with rescaled weights, before gdmix_re_pack --------------
+ * Photon-ML's activeDataUpperBound for a random-effect stage (--active_data_upper_bound=K / --active_data_seed, gdmix_amd/model.py; not in
+ * the reference): an entity of more than K samples trains on a uniform sample of K of them, each weighted n_e / K, so that the objective
+ * stays an unbiased estimate of the full one and l2_reg_weight keeps its meaning. The head of a skewed population is bounded; no entity
+ * can lose all its rows. csrc/re_cap.hip; a pass over a gdmix_re_raw_batch in front of gdmix_re_pack, of which no pack or solve kernel
+ * knows. Only the batch the solver sees is cut: scores and metrics are taken over every row.
+ *
+ * Definition, for one entity with rows i = 0 .. n_e - 1 in batch order and row uids u_i; mix is the function of the down-sampling section.
+ *     key(seed, uid) = mix((uint64)uid ^ mix(seed))                all 64 bits (down-sampling's draw is key >> 32)
+ *     n_e <= K :  every row is kept, its weight unchanged (1 where the batch has no weight array)
+ *     n_e >  K :  kept = the K rows smallest by (key, i); kept rows keep their order;
+ *                 weight of a kept row = (float)(((double)w * (double)n_e) / (double)K)
+ * Every operation is a single IEEE fp64 step followed by one rounding to fp32: gdmix_amd/active_data.py, the numpy statement of this
+ * definition, and the device give the same bits.
+ *   - With distinct uids the kept set is a function of (seed, the entity's set of uids, K) alone: it does not depend on the order of the
+ *     rows, on where the entity sits or on how partitions are grouped.
+ *   - The kept set at K is a subset of the kept set at K' > K.
+ *   - Rows with EQUAL uids tie on the key and are admitted in row order: the only place where the order matters.
+ *     key(0, 0) = 0xa706dd2f4d197e6f   key(1, 0) = 0x5e41ab087439611e   key(0, 1) = 0x08b4fda8c892b50e
+ *     key(20240603, 123456789) = 0xd9c4c3685399dfb6   key(7, -1) = 0xa9a96b699dc41760   key(7, -2^63) = 0x7e44eb9e75b86b14
+ *     seed 5, one entity with uids 100 .. 111: K = 4 keeps rows {0, 5, 8, 10}, K = 5 keeps rows {0, 5, 8, 9, 10}.
+ * The stage's objective, (1/n) ( sum w l + (l2/2) |theta_reg|^2 ), is divided by the number of rows the solver sees, which is K for a
+ * capped entity and not n_e. That constant multiplies the whole objective and does not move the minimiser of sum w l + (l2/2) |theta|^2
+ * (fval and the gradient norm the stopping tests see are scaled by n_e / K against an uncapped entity's).
+ *
+ * gdmix_re_cap_plan: uid [N] int64 on the device. Lists the capped entities (n_e > K; in any order, which no output depends on); those of at
+ *   most 128 rows (gdmix_re_set_cap_small_max: up to 1024) take a wavefront each, hash their keys once into LDS and keep row i iff #{j : (key_j, j) < (key_i, i)} < K; larger ones
+ *   take a workgroup each and find the K-th smallest key by an exact radix select, most significant byte first, with a 256-bin histogram
+ *   in LDS per pass (at most eight passes over the entity's uids, the key hashed again from the uid each time: no key array in HBM), then
+ *   keep key < tau and, of key == tau, the first rows in row order until K is reached, by an ordered count across the workgroup. Both give
+ *   the same flags; all counts are integers. Then the exclusive scans of down-sampling. Writes into `workspace`
+ *   (gdmix_re_cap_workspace_bytes(E, N) device bytes; host only, 0 beyond the limits; less is GDMIX_RE_ENOMEM), synchronises `stream` once
+ *   and fills *counts (host). The caller allocates the output arrays of exactly counts->kept rows and counts->kept_nnz non-zeros.
+ * gdmix_re_cap_apply: the same raw batch, options and workspace; fills the arrays of *out as gdmix_re_downsample_apply does (weight is
+ *   always written) and kept_rows [N_out] (optional). Stream-ordered. The workspace must hold the context's LAST plan, and out->N / out->Z
+ *   must be its totals: anything else is GDMIX_RE_EINVAL and nothing is written.
+ * upper_bound < 1: GDMIX_RE_EINVAL. 2^31 rows or entities or more: GDMIX_RE_ERANGE. All offsets are 64-bit. */
+typedef struct {
+  int64_t  upper_bound;   /* K >= 1 */
+  uint64_t seed;
+} gdmix_re_cap_opts;
+typedef struct {          /* host */
+  int64_t entities;       /* E                                                                  */
+  int64_t capped;         /* entities with n_e > K                                              */
+  int64_t rows;           /* N of the input                                                     */
+  int64_t kept;           /* N_out                                                              */
+  int64_t kept_nnz;       /* Z_out                                                              */
+  int64_t largest;        /* the largest n_e before the cap                                     */
+} gdmix_re_cap_counts;
+GDMIX_API size_t gdmix_re_cap_workspace_bytes(int64_t E, int64_t N);
+GDMIX_API int gdmix_re_cap_plan(gdmix_re_ctx* ctx, const gdmix_re_raw_batch* raw_dev, const int64_t* uid_dev, const gdmix_re_cap_opts* opts, void* workspace,
+                                size_t workspace_bytes, gdmix_re_cap_counts* counts, void* stream);
+GDMIX_API int gdmix_re_cap_apply(gdmix_re_ctx* ctx, const gdmix_re_raw_batch* raw_dev, const gdmix_re_cap_opts* opts, void* workspace, size_t workspace_bytes,
+                                 const gdmix_re_downsample_out* out_dev, int32_t* kept_rows, void* stream);
+/* Where the two paths part: capped entities of more than `small_max` rows take the radix-select path (0 => every capped entity). 0 .. 1024;
+ * the default, 128, is where counting stops paying on a C5-shaped batch (profiles/active_data.txt). The flags do not depend on it. */
+GDMIX_API int gdmix_re_set_cap_small_max(gdmix_re_ctx* ctx, int small_max);
 
 /* ---- B4: the upstream Spark partitioner's hash, bit-exact (host functions) ------------------------
  * hashCode over UTF-16 code units in wrapping int32; Math.abs(Int.MinValue) stays negative; Scala %
