@@ -57,6 +57,105 @@ __device__ __forceinline__ void write_results(G& grp, const OutDev& O, const Sol
 #define GDMIX_NARROW_KR 5
 #endif
 constexpr int grp_reg_pairs(int epl) { return epl >= 5 ? GDMIX_NARROW_KR : M_REG; }
+
+// ---- staging of an entity's block (docs/kernels.md, "Staging") --------------------------------------------------------------------
+// A round of staging is load() of one or more of the structs below, stage_issued(), then their store(): all global loads of the round
+// are in flight before the first LDS store waits for one. Lane gl takes elements gl, gl + G, ...: the trip counts T are compile-time
+// (the class's caps), every trip is predicated by the element's own bound, and a dead trip neither loads nor stores.
+constexpr int STAGE_CHUNK_TRIPS = 8;   // CSR / CSC trips of one round: four loads each, 32 loads per lane
+
+// Between a round's loads and its stores. The compiler may not move a memory access across this point, so it cannot sink a load to
+// its store; and the bounds come out of it as new values, so the stores' predicates are compared again instead of being kept in
+// scalar registers across the round (up to 22 pairs of them: the chunked classes spilled scalar registers).
+__device__ __forceinline__ void stage_new_value(int& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ int stage_opaque(int v) { stage_new_value(v); return v; }
+template <class... T>
+__device__ __forceinline__ void stage_issued(T&... bound) {
+  (stage_new_value(bound), ...);
+  asm volatile("" ::: "memory");
+}
+
+template <int G, int T>
+struct StageCsr {   // elements k0, k0 + G, ... of csr_col / csr_val / csc_row / csc_val below nnz
+  int ccol[T], cval[T], srow[T], sval[T];
+  __device__ __forceinline__ void load(const BatchDev& B, int64_t z0, int k0, int nnz) {
+    const int32_t* const pc = B.csr_col + z0 + k0;
+    const float* const pv = B.csr_val + z0 + k0;
+    const int32_t* const qr = B.csc_row + z0 + k0;
+    const float* const qv = B.csc_val + z0 + k0;
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+      if (k0 + G * t < nnz) {
+        ccol[t] = pc[G * t];
+        cval[t] = __float_as_int(pv[G * t]);
+        srow[t] = qr[G * t];
+        sval[t] = __float_as_int(qv[G * t]);
+      }
+  }
+  __device__ __forceinline__ void store(const QuadLds& L, int k0, int nnz) const {
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+      if (k0 + G * t < nnz) {
+        L.csr()[k0 + G * t] = make_int2(ccol[t], cval[t]);
+        L.csc()[k0 + G * t] = make_int2(srow[t], sval[t]);
+      }
+  }
+};
+
+template <int G, int NT, int RT, int CT>
+struct StageSamples {   // y, offset (i < n), row_ptr (i < nrp = n + 1), col_ptr (i < ncp = d + 1)
+  float y[NT], o[NT];
+  int rp[RT], cp[CT];
+  __device__ __forceinline__ void load(const BatchDev& B, int64_t r0, int64_t z0, int64_t e, int gl, int n, int nrp, int ncp) {
+    const float* const py = B.y + r0 + gl;
+    const float* const po = B.offset + r0 + gl;
+    const int32_t* const pr = B.row_ptr + r0 + e + gl;
+    const int32_t* const pc = B.col_ptr + z0 + e + gl;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (gl + G * t < n) {
+        y[t] = py[G * t];
+        o[t] = po[G * t];
+      }
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+      if (gl + G * t < nrp) rp[t] = pr[G * t];
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+      if (gl + G * t < ncp) cp[t] = pc[G * t];
+  }
+  __device__ __forceinline__ void store(const QuadLds& L, int gl, int n, int nrp, int ncp) const {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (gl + G * t < n) {
+        L.y()[gl + G * t] = y[t];
+        L.o()[gl + G * t] = o[t];
+      }
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+      if (gl + G * t < nrp) L.row_ptr()[gl + G * t] = rp[t];
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+      if (gl + G * t < ncp) L.col_ptr()[gl + G * t] = cp[t];
+  }
+};
+
+template <int G, int NT>
+struct StageWeights {   // weight (i < n), for batches that have the column
+  float w[NT];
+  __device__ __forceinline__ void load(const BatchDev& B, int64_t r0, int gl, int n) {
+    const float* const pw = B.weight + r0 + gl;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (gl + G * t < n) w[t] = pw[G * t];
+  }
+  __device__ __forceinline__ void store(const QuadLds& L, int gl, int n) const {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (gl + G * t < n) L.w()[gl + G * t] = w[t];
+  }
+};
+
 template <int G, int EPL, int NCAP, int ZCAP, int LOSS>
 __global__ __launch_bounds__(G > WAVE ? G : WAVE)
 __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 ? GDMIX_QUAD_WAVES_EPL4 : 1)))) void re_solve_grp_kernel(
@@ -65,16 +164,26 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
   constexpr int NG = G >= WAVE ? 1 : WAVE / G;   // entities per workgroup
   constexpr int NWG = G > WAVE ? G / WAVE : 1;   // wavefronts per entity
   const int tid = threadIdx.x;
-  const int row = (G >= WAVE) ? 0 : (tid / G);
+  // (stage_opaque: the row's LDS offset was otherwise computed a second time for the epilogue and spilled: one register on the EPL = 4 kernels)
+  const int row = (G >= WAVE) ? 0 : stage_opaque(tid / G);
   const int gl = (G >= WAVE) ? tid : (tid & (G - 1));
   const int slot = blockIdx.x * NG + row;
   const bool valid = slot < count;
+  // ---- staging: three rounds of global loads (order -> the six extents -> the entity's block), each behind one wait ----
   const int64_t e = valid ? (int64_t)B.order[begin + slot] : 0;
   const int ic = o.has_intercept ? 1 : 0;
+  // [e] and [e + 1] of the three tables in one round: the tables have E + 1 entries, so none of the six loads needs a predicate (a load
+  // under `valid ?` is an exec region of its own, with its own wait). An empty slot reads entity 0 twice: its extents are 0 without a
+  // select (selected values next to the plain differences were two more registers live through the solve).
+  const int64_t e1 = e + (valid ? 1 : 0);
   const int64_t r0 = B.ent_row_ptr[e], z0 = B.ent_nnz_ptr[e], f0 = B.ent_feat_ptr[e];
-  const int n = valid ? (int)(B.ent_row_ptr[e + 1] - r0) : 0;
-  const int nnz = valid ? (int)(B.ent_nnz_ptr[e + 1] - z0) : 0;
-  const int d = valid ? (int)(B.ent_feat_ptr[e + 1] - f0) : 0;
+  const int64_t r1 = B.ent_row_ptr[e1], z1 = B.ent_nnz_ptr[e1], f1 = B.ent_feat_ptr[e1];
+  // All six are waited for here, before the first load of the block is issued: the wait counter is in order, so a wait for one of them
+  // behind younger loads of the block would wait for those too (one more exposed latency per table).
+  asm volatile("" ::"v"(r0), "v"(r1), "v"(z0), "v"(z1), "v"(f0), "v"(f1) : "memory");
+  const int n = (int)(r1 - r0);
+  const int nnz = (int)(z1 - z0);
+  const int d = (int)(f1 - f0);
   const int p = valid ? d + ic : 0;
   const int64_t c0 = f0 + e * ic;
 
@@ -87,38 +196,73 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
   X.buf = reinterpret_cast<double*>(L.base + QUAD_HDR_BYTES * NWG);
   X.phase = 0;
 
-  if (valid) {
-    for (int k = gl; k < nnz; k += G) {
-      L.csr()[k] = make_int2(B.csr_col[z0 + k], __float_as_int(B.csr_val[z0 + k]));
-      L.csc()[k] = make_int2(B.csc_row[z0 + k], __float_as_int(B.csc_val[z0 + k]));
-    }
-    for (int i = gl; i < n; i += G) {
-      L.y()[i] = B.y[r0 + i];
-      L.o()[i] = B.offset[r0 + i];
-      if (L.has_w) L.w()[i] = B.weight[r0 + i];
-    }
-    for (int i = gl; i <= n; i += G) L.row_ptr()[i] = B.row_ptr[r0 + e + i];
-    for (int i = gl; i <= d; i += G) L.col_ptr()[i] = B.col_ptr[z0 + e + i];
-  }
-  // packed (start | len << 16) extents of the lane's first sample and of its coefficient slots
-  unsigned rowc = 0, colc[EPL];
-  if (gl < n) {
-    const int k0 = B.row_ptr[r0 + e + gl], k1 = B.row_ptr[r0 + e + gl + 1];
-    rowc = (unsigned)k0 | ((unsigned)(k1 - k0) << 16);
-  }
+  // The block: every load of a round is issued before the round's first LDS store. The trip counts are the class's caps (compile-time),
+  // and EVERY LOAD KEEPS ITS OWN BOUND: the arrays of the batch end with the last entity (csr_val is the caller's val, Z elements; y,
+  // offset and weight have N), so a load up to the cap would read past them for the last entities of a batch.
+  constexpr int ZT = ZCAP / G;              // CSR / CSC entries per lane
+  constexpr int NT = (NCAP + G - 1) / G;    // samples per lane
+  constexpr int RT = NCAP / G + 1;          // row_ptr entries per lane (n + 1 of them)
+  constexpr int CT = EPL + 1;               // col_ptr entries per lane (d + 1 of them)
+  static_assert(ZCAP % G == 0, "the CSR copy takes ZCAP / G trips");
+  int zb = nnz, nb = n, nrp = valid ? n + 1 : 0, ncp = valid ? d + 1 : 0;   // the bounds of the rounds (stage_issued)
+  StageSamples<G, NT, RT, CT> ss;
+  StageWeights<G, NT> sw;
   QuadState<EPL> V;
+  if constexpr (ZT <= STAGE_CHUNK_TRIPS) {   // one round for the whole block
+    StageCsr<G, ZT> sc;
+    sc.load(B, z0, gl, zb);
+    ss.load(B, r0, z0, e, gl, nb, nrp, ncp);
+    if (L.has_w) sw.load(B, r0, gl, nb);
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+      const int j = gl + G * s;
+      V.x[s] = (theta0 && j < p) ? theta0[c0 + j] : 0.0;
+    }
+    stage_issued(zb, nb, nrp, ncp);
+    sc.store(L, gl, zb);
+    ss.store(L, gl, nb, nrp, ncp);
+    if (L.has_w) sw.store(L, gl, nb);
+  } else {   // the big-NCAP rows: rounds of at most 32 loads per lane, which keeps the prologue below the solve's register peak
+    static_assert(2 * NT + RT + CT <= 4 * STAGE_CHUNK_TRIPS && NT <= 4 * STAGE_CHUNK_TRIPS, "a round is at most 32 loads per lane");
+    for (int kb = gl; kb < nnz; kb += STAGE_CHUNK_TRIPS * G) {
+      StageCsr<G, STAGE_CHUNK_TRIPS> sc;
+      sc.load(B, z0, kb, zb);
+      stage_issued(zb);
+      sc.store(L, kb, zb);
+    }
+    ss.load(B, r0, z0, e, gl, nb, nrp, ncp);
+#pragma unroll
+    for (int s = 0; s < EPL; ++s) {
+      const int j = gl + G * s;
+      V.x[s] = (theta0 && j < p) ? theta0[c0 + j] : 0.0;
+    }
+    stage_issued(nb, nrp, ncp);
+    ss.store(L, gl, nb, nrp, ncp);
+    if (L.has_w) {
+      sw.load(B, r0, gl, nb);
+      stage_issued(nb);
+      sw.store(L, gl, nb);
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < EPL; ++s) { V.g[s] = 0.0; V.d[s] = 0.0; }
+  grp_fence<G>();
+  // packed (start | len << 16) extents of the lane's first sample and of its coefficient slots, from the staged copies
+  // (one round of LDS reads: a lane without a sample or a coefficient reads the block's entry 0 and drops it)
+  unsigned rowc, colc[EPL];
+  {
+    const int i = gl < n ? gl : 0;
+    const int k0 = L.row_ptr()[i], k1 = L.row_ptr()[i + 1];
+    rowc = gl < n ? (unsigned)k0 | ((unsigned)(k1 - k0) << 16) : 0u;
+  }
 #pragma unroll
   for (int s = 0; s < EPL; ++s) {
     const int j = gl + G * s;
-    colc[s] = 0;
-    if (j < p && j >= ic) {
-      const int k0 = B.col_ptr[z0 + e + (j - ic)], k1 = B.col_ptr[z0 + e + (j - ic) + 1];
-      colc[s] = (unsigned)k0 | ((unsigned)(k1 - k0) << 16);
-    }
-    V.x[s] = (theta0 && j < p) ? theta0[c0 + j] : 0.0;
-    V.g[s] = 0.0; V.d[s] = 0.0;
+    const bool live = j < p && j >= ic;
+    const int c = live ? j - ic : 0;
+    const int k0 = L.col_ptr()[c], k1 = L.col_ptr()[c + 1];
+    colc[s] = live ? (unsigned)k0 | ((unsigned)(k1 - k0) << 16) : 0u;
   }
-  grp_fence<G>();
   SolveStats st;
   quad_solve<G, EPL, (NCAP > G), LOSS, grp_reg_pairs(EPL)>(L, o, gl, n, p, ic, valid, rowc, colc, V, X, st);
   if (!valid) return;
