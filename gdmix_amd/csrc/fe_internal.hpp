@@ -208,4 +208,13 @@ void fe_tron_enqueue_hv_begin(const FeDev& F, hipStream_t s);
 void fe_tron_enqueue_hv_vector(const FeDev& F, const double* v, hipStream_t s);
 void fe_tron_enqueue_hv_end(const FeDev& F, hipStream_t s);
 
+// ---- fe_box.hip ----
+// One projected L-BFGS step (products, decision, update: three launches) on the reduced [gradient, value] buffer of a problem with bounds
+// (include/gdmix_fe.h, "(ABI 26) box constraints"); lower / upper: [P] device doubles of the problem's own, the intercept's infinite.
+void fe_box_enqueue_step(const FeDev& F, const SolveParams& o, const double* lower, const double* upper, int32_t* status_dev, hipStream_t s);
+// gdmix_fe_set_bounds' check of the caller's arrays: bad_dev[0] a NaN, [1] lower > upper, [2] a finite bound on the intercept (the caller clears them).
+void fe_box_enqueue_check(const double* lower, const double* upper, int P, int ic, int32_t* bad_dev, hipStream_t s);
+// Behind fe_init_kernel: the start point clamped into the box (W.x, W.t, xl).
+void fe_box_enqueue_start(const FeDev& F, const double* lower, const double* upper, hipStream_t s);
+
 }  // namespace gdmix

@@ -853,6 +853,10 @@ struct gdmix_fe_problem {
   double l1 = 0.0;       // weight of the L1 term (gdmix_fe_set_l1); > 0: the step is OWL-QN's (fe_owlqn.hip)
   DevBuf tron_mem;       // the TRON buffer (fe_internal.hpp: FeTron); empty until TRON is first selected or gdmix_fe_hessian_vec first called
   int optimizer = GDMIX_FE_OPT_LBFGS;      // gdmix_fe_set_optimizer; TRON: the pass pairs are the HV variant's, the step fe_tron.hip's
+  DevBuf box_mem;        // [2 P] the problem's copy of the lower and upper bounds, then the check's flags (gdmix_fe_set_bounds); empty until the first bounds
+  bool box = false;      // bounds are installed: the step is the projected L-BFGS of fe_box.hip
+  const double* box_lo() const { return box_mem.as<double>(); }
+  const double* box_hi() const { return box_mem.as<double>() + F.P; }
   int32_t* status_dev = nullptr;
   hipEvent_t ev[3] = {};
   bool timed = false;
@@ -956,6 +960,7 @@ static int fe_reset(gdmix_fe_problem* p, const double* theta0, hipStream_t s) {
   HIP_TRY(hipMemsetAsync(base + p->pool_inv, 0xff, (size_t)F.P * 4, s));
   with_flag(F.mu != nullptr, [&](auto PR) { hipLaunchKernelGGL(fe_init_kernel<decltype(PR)::value>, dim3(grid_for(F.P, 256, 1024)), dim3(256), 0, s, F, theta0); });
   if (fe_tron_state(F)) fe_tron_enqueue_reset(F, theta0, s);      // (also on a problem set back to L-BFGS-B: the record is what gdmix_fe_hessian_vec finds)
+  if (p->box) fe_box_enqueue_start(F, p->box_lo(), p->box_hi(), s);      // the start point is the clamped one, zeros included
   HIP_TRY(hipGetLastError());
   p->timed = false;
   p->dirty = false;
@@ -1089,6 +1094,10 @@ GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const 
     set_error("gdmix_fe_set_prior: the problem's optimiser is TRON (gdmix_fe_set_optimizer), whose product has no prior variant yet");
     return GDMIX_RE_EINVAL;
   }
+  if (mean && p->box) {
+    set_error("gdmix_fe_set_prior: the problem has bounds (gdmix_fe_set_bounds), which are not carried through the prior's change of variables yet");
+    return GDMIX_RE_EINVAL;
+  }
   if (!mean) {
     F.mu = nullptr; F.sc = nullptr;      // (the copy stays allocated: kernels of an earlier solve may still be queued on it)
     return fe_reset(p, nullptr, s);
@@ -1122,6 +1131,10 @@ GDMIX_API int gdmix_fe_set_l1(gdmix_fe_problem* p, double l1, void* stream) {
     set_error("gdmix_fe_set_l1: the problem's optimiser is TRON (gdmix_fe_set_optimizer), which minimises a smooth objective: no L1 term");
     return GDMIX_RE_EINVAL;
   }
+  if (l1 > 0.0 && p->box) {
+    set_error("gdmix_fe_set_l1: the problem has bounds (gdmix_fe_set_bounds), whose step minimises a smooth objective: no L1 term");
+    return GDMIX_RE_EINVAL;
+  }
   HIP_TRY(hipSetDevice(p->ctx->impl.device));
   p->l1 = l1;
   return fe_reset(p, nullptr, static_cast<hipStream_t>(stream));
@@ -1141,6 +1154,10 @@ GDMIX_API int gdmix_fe_set_optimizer(gdmix_fe_problem* p, int optimizer, void* s
     set_error("gdmix_fe_set_optimizer: the problem has a prior (gdmix_fe_set_prior); TRON's product has no prior variant yet");
     return GDMIX_RE_EINVAL;
   }
+  if (optimizer == GDMIX_FE_OPT_TRON && p->box) {
+    set_error("gdmix_fe_set_optimizer: the problem has bounds (gdmix_fe_set_bounds); TRON minimises without constraints");
+    return GDMIX_RE_EINVAL;
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(p->ctx->impl.device));
   if (optimizer == GDMIX_FE_OPT_TRON) {
@@ -1148,6 +1165,47 @@ GDMIX_API int gdmix_fe_set_optimizer(gdmix_fe_problem* p, int optimizer, void* s
     if (rc != GDMIX_RE_OK) return rc;
   }
   p->optimizer = optimizer;
+  return fe_reset(p, nullptr, s);
+}
+
+GDMIX_API int gdmix_fe_set_bounds(gdmix_fe_problem* p, const double* lower, const double* upper, void* stream) {
+  if (!p) { set_error("problem is NULL"); return GDMIX_RE_EINVAL; }
+  if ((lower == nullptr) != (upper == nullptr)) { set_error("gdmix_fe_set_bounds: lower and upper are given together, or both NULL"); return GDMIX_RE_EINVAL; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(p->ctx->impl.device));
+  if (!lower) {
+    p->box = false;      // (the copy stays allocated: kernels of an earlier solve may still be queued on it)
+    return fe_reset(p, nullptr, s);
+  }
+  if (p->l1 > 0.0) { set_error("gdmix_fe_set_bounds: the problem has an L1 term (gdmix_fe_set_l1); the bounded step minimises a smooth objective"); return GDMIX_RE_EINVAL; }
+  if (p->optimizer == GDMIX_FE_OPT_TRON) {
+    set_error("gdmix_fe_set_bounds: the problem's optimiser is TRON (gdmix_fe_set_optimizer), which minimises without constraints");
+    return GDMIX_RE_EINVAL;
+  }
+  if (p->F.mu) {
+    set_error("gdmix_fe_set_bounds: the problem has a prior (gdmix_fe_set_prior); bounds are not carried through its change of variables yet");
+    return GDMIX_RE_EINVAL;
+  }
+  const size_t P = (size_t)p->F.P;
+  if (!p->box_mem) {
+    const hipError_t rc = p->box_mem.alloc(2 * P * 8 + 64);
+    if (rc != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", 2 * P * 8 + 64, hipGetErrorString(rc)); return GDMIX_RE_ENOMEM; }
+  }
+  double* box = p->box_mem.as<double>();
+  // the caller's bounds are checked before the problem's copy — bounds an earlier call installed — is overwritten
+  int32_t* bad_dev = reinterpret_cast<int32_t*>(box + 2 * P);
+  HIP_TRY(hipMemsetAsync(bad_dev, 0, 3 * sizeof(int32_t), s));
+  fe_box_enqueue_check(lower, upper, p->F.P, p->F.ic, bad_dev, s);
+  HIP_TRY(hipGetLastError());
+  int32_t bad[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(bad, bad_dev, sizeof(bad), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));      // the one wait of this call
+  if (bad[0]) { set_error("gdmix_fe_set_bounds: a bound is not a number"); return GDMIX_RE_EINVAL; }
+  if (bad[1]) { set_error("gdmix_fe_set_bounds: a lower bound exceeds its upper bound"); return GDMIX_RE_EINVAL; }
+  if (bad[2]) { set_error("gdmix_fe_set_bounds: the intercept is never bounded: its bounds must be -inf and +inf"); return GDMIX_RE_EINVAL; }
+  HIP_TRY(hipMemcpyAsync(box, lower, P * 8, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(box + P, upper, P * 8, hipMemcpyDeviceToDevice, s));
+  p->box = true;
   return fe_reset(p, nullptr, s);
 }
 
@@ -1204,7 +1262,7 @@ GDMIX_API int gdmix_fe_hessian_vec(gdmix_fe_problem* p, const double* theta, con
   const bool prior = !theta && F.mu != nullptr;      // theta is in theta units; only the current point of a problem with a prior is phi
   // the current accepted point of a TRON problem is W.x as well (fe_tron.hip); under the OWL-QN step it is W.t
   if (theta) F.W.x = const_cast<double*>(theta);
-  else if (p->l1 > 0.0) F.W.x = F.W.t;
+  else if (p->l1 > 0.0 || p->box) F.W.x = F.W.t;
   HIP_TRY(hipMemsetAsync(F.fg, 0, ((size_t)F.P + 1) * 8, s));
   p->dirty = true;
   const auto prepare = [&](const FeDev& G, bool with_prior) {
@@ -1274,12 +1332,13 @@ static int fe_enqueue_step(gdmix_fe_problem* p, hipStream_t s) {
   const FeDev& F = p->F;
   const int dot_blocks = grid_for(F.P, 256, FE_DOT_BLOCKS);
   const int tail_blocks = grid_for(dot_blocks, 1, p->ctx->impl.num_cus);      // at most one workgroup per CU: all resident, the wait inside cannot starve one
-  if (p->fused_tail && !(p->l1 > 0.0) && p->optimizer != GDMIX_FE_OPT_TRON) {
+  if (p->fused_tail && !(p->l1 > 0.0) && !p->box && p->optimizer != GDMIX_FE_OPT_TRON) {
     ++p->gen;
     if (p->gen == 0u) ++p->gen;
   }
   if (p->optimizer == GDMIX_FE_OPT_TRON) fe_tron_enqueue_step(F, p->o, p->status_dev, s);      // (never with a prior or an L1 term: gdmix_fe_set_optimizer)
   else if (p->l1 > 0.0) fe_owlqn_enqueue_step(F, p->o, p->l1, p->status_dev, s);      // (never with a prior: gdmix_fe_set_l1)
+  else if (p->box) fe_box_enqueue_step(F, p->o, p->box_lo(), p->box_hi(), p->status_dev, s);      // (never with a prior or an L1 term: gdmix_fe_set_bounds)
   else with_flag(F.mu != nullptr, [&](auto PR) {
     constexpr bool PRIOR = decltype(PR)::value;
     if (p->fused_tail) {
@@ -1359,8 +1418,8 @@ GDMIX_API int gdmix_fe_result(gdmix_fe_problem* p, double* theta, double* fval, 
     hipLaunchKernelGGL(fe_prior_theta_kernel, dim3(grid_for(p->F.P, 256, 1024)), dim3(256), 0, s, p->F, theta);
     HIP_TRY(hipGetLastError());
   } else if (theta) {
-    // under the OWL-QN step W.x is the trial point and W.t the last accepted one (fe_owlqn.hip)
-    HIP_TRY(hipMemcpyAsync(theta, p->l1 > 0.0 ? p->F.W.t : p->F.W.x, (size_t)p->F.P * 8, hipMemcpyDeviceToDevice, s));
+    // under the OWL-QN step and the bounded step W.x is the trial point and W.t the last accepted one (fe_owlqn.hip, fe_box.hip)
+    HIP_TRY(hipMemcpyAsync(theta, (p->l1 > 0.0 || p->box) ? p->F.W.t : p->F.W.x, (size_t)p->F.P * 8, hipMemcpyDeviceToDevice, s));
   }
   CompactState S;
   HIP_TRY(hipMemcpyAsync(&S, p->F.state, sizeof(S), hipMemcpyDeviceToHost, s));

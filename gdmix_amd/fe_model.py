@@ -38,6 +38,14 @@ Not in the reference either, any number of workers:
        Hessian-vector products, each the same two streaming passes as an evaluation. The number of products is logged. With
        --l2_reg_weights the sweep keeps the optimiser. Refused with a non-zero --l1_reg_weight, --incremental_training and
        --feature_normalization; --action=inference ignores it.
+  --coefficient_constraints=PATH   box constraints on coefficients (Photon-ML's coefficient constraints): the stage minimises its smooth
+       objective subject to lowerBound <= theta <= upperBound by projected L-BFGS on the device (include/gdmix_fe.h, "(ABI 26) box
+       constraints"). PATH is a JSON array of {"name", "term", "lowerBound", "upperBound"} in the names and terms of --feature_file; either
+       bound may be absent (infinite); "term": "*" covers every term of a name, "name": "*", "term": "*" every feature not named otherwise,
+       an exact record beats a wildcard (params.coefficient_bounds). The intercept is never bounded. The bounds are in original feature
+       units; a warm start is clamped into the box; with --l2_reg_weights every model of the sweep keeps them. How many coefficients ended
+       at a bound is logged. The stage does not threshold to 0 a coefficient whose box excludes 0. Refused without --feature_file, with a non-zero
+       --l1_reg_weight, --optimizer=TRON, --incremental_training and a --feature_normalization other than none; --action=inference ignores it.
 """
 import glob
 import logging
@@ -53,7 +61,7 @@ from .io import avro, native_reader, tfrecord
 from .io.features import read_feature_list
 from .io.grouped_reader import resolve_input_files
 from .io.metadata import DatasetMetadata
-from .params import LRParams, check_feature_normalization, check_l1_reg_weight, parse_l2_grid
+from .params import LRParams, check_feature_normalization, check_l1_reg_weight, parse_l2_grid, read_coefficient_constraints
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.INFO)
@@ -98,6 +106,10 @@ class FixedLRParams(LRParams):
     # not in the reference: Photon-ML's OptimizerType. TRON: trust-region Newton on the device (include/gdmix_fe.h, "(ABI 24) TRON"); LBFGS: the
     # stage as it was. Any case. --action=inference accepts and ignores the flag.
     optimizer: str = "LBFGS"
+    # not in the reference: Photon-ML's coefficient box constraints, a JSON file of {"name", "term", "lowerBound", "upperBound"} records
+    # (params.coefficient_bounds). The stage trains by projected L-BFGS on the device (include/gdmix_fe.h, "(ABI 26) box constraints").
+    # --action=inference accepts and ignores the flag.
+    coefficient_constraints: Optional[str] = None
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -141,6 +153,16 @@ class FixedLRParams(LRParams):
                     (self.normalization() != "none", "--feature_normalization", "the Hessian-vector product has no variant for normalised units yet")):
                 if is_set:
                     raise ValueError(f"--optimizer=TRON does not run with {flag}: {why}")
+        if self.coefficient_constraints is not None:
+            if not (self.feature_bag and self.feature_file):
+                raise ValueError("--coefficient_constraints names features by the names and terms of --feature_file: it does not run without --feature_file")
+            for is_set, flag, why in (
+                    (self.l1_reg_weight > 0.0, "--l1_reg_weight", "the bounded step minimises a smooth objective"),
+                    (self.optimizer == TRON, "--optimizer=TRON", "TRON minimises without constraints"),
+                    (self.incremental_training, "--incremental_training", "the bounds are not carried through the prior's change of variables yet"),
+                    (self.normalization() != "none", "--feature_normalization", "the bounds are in original units and are not carried into normalised units yet")):
+                if is_set:
+                    raise ValueError(f"--coefficient_constraints does not run with {flag}: {why}")
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         assert self.fixed_effect_variance_mode is None or self.fixed_effect_variance_mode in (constants.FULL, constants.SIMPLE), \
@@ -252,6 +274,7 @@ class FixedEffectLRModelLBFGS:
         self._fe = None
         self.metric_output_dir = p.metric_output_dir
         self._metrics = None      # metrics.StageMetrics while a stage with --metric_output_dir runs
+        self._coefficient_bounds = None      # (lower, upper) of --coefficient_constraints once the file has been read
 
     # ---- helpers ------------------------------------------------------------------------------------------------
     def _parse_parameters(self, raw_model_parameters):
@@ -391,7 +414,7 @@ class FixedEffectLRModelLBFGS:
             *self._shard_arrays(data, fit=True), data["y"], self.num_features, l2_grid=grid, select=select, offset=data["offset"],
             weight=data["weight"] if data["has_weight"] else None, has_intercept=self.has_intercept, regularize_bias=self.is_regularize_bias, model_type=self.model_type, max_iter=self.max_iteration,
             m=self.num_correction_pairs, tolerance=self.model_params.lbfgs_tolerance, dummy=not bag,
-            variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold, **self._optimizer(), **self._down_sampling(data))
+            variance_mode=self.fixed_effect_variance_mode, threshold=self.sparsity_threshold, **self._optimizer(), **self._bounds(), **self._down_sampling(data))
         self.l2_reg_weight = self.model_params.l2_reg_weight = float(grid[best])
         return theta, info
 
@@ -400,6 +423,20 @@ class FixedEffectLRModelLBFGS:
         opt = self.model_params.optimizer
         return {} if opt == "LBFGS" else {"optimizer": opt}
 
+    def _bounds(self):
+        """{"bounds": (lower, upper)} for fit_stepping / fit_sweep from --coefficient_constraints, or {} without the flag: the call is then
+        what it was before the flag existed. The file is read once per stage; every worker reads the same file."""
+        path = self.model_params.coefficient_constraints
+        if path is None:
+            return {}
+        if self._coefficient_bounds is None:
+            lower, upper = read_coefficient_constraints(path, read_feature_list(self.feature_file), self.has_intercept)
+            if lower.size != self.num_features + (1 if self.has_intercept else 0):
+                raise ValueError(f"--coefficient_constraints: --feature_file lists {lower.size - (1 if self.has_intercept else 0)} features, the metadata's "
+                                 f"feature bag has {self.num_features}")
+            self._coefficient_bounds = (lower, upper)
+        return {"bounds": self._coefficient_bounds}
+
     # ---- train ----------------------------------------------------------------------------------------------------
     def train(self, training_data_dir, validation_data_dir, metadata_file, checkpoint_path, execution_context, schema_params):
         task_index = execution_context[constants.TASK_INDEX]
@@ -407,6 +444,7 @@ class FixedEffectLRModelLBFGS:
         is_chief = execution_context[constants.IS_CHIEF]
         self.check_request(execution_context, constants.ACTION_TRAIN)
         grid = self.model_params.l2_grid()
+        self._bounds()      # a bad constraints file is an error before any data is read
         self._begin_metrics()
         data = self._read(training_data_dir, num_workers, task_index, schema_params)
         D = self.num_features
@@ -445,6 +483,7 @@ class FixedEffectLRModelLBFGS:
             if self.model_params.l1_reg_weight > 0.0:
                 extra["l1"] = self.model_params.l1_reg_weight
             extra.update(self._optimizer())
+            extra.update(self._bounds())
             theta, info = self._solver().fit_stepping(
                 *self._shard_arrays(data, fit=True), data["y"], D, offset=data["offset"], weight=data["weight"] if data["has_weight"] else None,
                 has_intercept=self.has_intercept, l2=self.l2_reg_weight, regularize_bias=self.is_regularize_bias,
@@ -464,7 +503,14 @@ class FixedEffectLRModelLBFGS:
             logger.info(f"l1_reg_weight {self.model_params.l1_reg_weight}: {int(np.count_nonzero(theta))} of {theta.size} coefficients are non-zero")
         if self._optimizer():
             logger.info(f"optimizer {self.model_params.optimizer}: {info['nit']} iterations, {info['nfev']} evaluations, {info.get('nhv', 0)} Hessian-vector products")
-        self.model_coefficients = theta = self._stage_coefficients(theta)
+        if self._bounds():
+            lower, upper = self._coefficient_bounds
+            at_bound = info.get("at_bound", int(np.count_nonzero((theta == lower) | (theta == upper))))
+            logger.info(f"coefficient_constraints: {at_bound} of {theta.size} coefficients ended at a bound")
+            kept = self._stage_coefficients(theta)
+            self.model_coefficients = theta = np.where((kept < lower) | (kept > upper), theta, kept)      # 0 outside the box: not thresholded
+        else:
+            self.model_coefficients = theta = self._stage_coefficients(theta)
         # the reference's variance computation rides on the scoring pass over the training data, which therefore runs (and writes
         # its scores) whenever a variance mode is set (:650-661)
         if not self.disable_fixed_effect_scoring_after_training or self.fixed_effect_variance_mode is not None:

@@ -176,7 +176,7 @@ class FixedEffectDeviceSolver:
     def fit_stepping(self, row_nnz_ptr, col_global, val, y, num_features, offset=None, weight=None, has_intercept=True, l2=1.0,
                      regularize_bias=True, model_type=LOGISTIC_REGRESSION, theta0=None, max_iter=100, m=10, tolerance=1e-12,
                      group=None, return_problem=False, dummy=None, variance_mode=None, threshold=0.0, prior=None, feature_scale=None,
-                     down_sampling=None, l1=0.0, optimizer=LBFGS):
+                     down_sampling=None, l1=0.0, optimizer=LBFGS, bounds=None):
         """Same contract as fit(), through include/gdmix_fe.h. With torch.distributed initialised (or `group` given) every
         worker calls this with its own shard; the coefficients returned are identical on all workers. dummy: True for a
         model without a feature bag (intercept only), False for a bagged model — also when this worker's shard happens to
@@ -196,7 +196,12 @@ class FixedEffectDeviceSolver:
         the others. l1 = 0 is the plain fit: set_l1 is never called.
         optimizer="TRON": the smooth objective is minimised by trust-region Newton on the device (include/gdmix_fe.h, "(ABI 24) TRON"); theta0
         is its start point; not together with l1 > 0, `prior` or `feature_scale`. info["nhv"] counts the Hessian-vector products (0 under
-        "LBFGS", the plain fit: set_optimizer is never called), info["optimizer"] names the optimiser."""
+        "LBFGS", the plain fit: set_optimizer is never called), info["optimizer"] names the optimiser.
+        bounds = (lower, upper), numpy arrays of num_features + has_intercept entries, intercept last and infinite: the smooth objective is
+        minimised subject to lower <= theta <= upper by projected L-BFGS on the device (include/gdmix_fe.h, "(ABI 26) box constraints");
+        theta0 is clamped into the box; not together with l1 > 0, TRON, `prior` or `feature_scale`. The coefficients returned lie in the box, a
+        coefficient at a bound is the bound's double, info["at_bound"] counts those. Every worker passes the same bounds. None is the plain
+        fit: set_bounds is never called."""
         optimizer = check_optimizer(optimizer)
         l1 = float(l1)
         if not (np.isfinite(l1) and l1 >= 0.0):
@@ -205,13 +210,20 @@ class FixedEffectDeviceSolver:
             raise ValueError("the L1 term does not compose with a prior model or with feature normalisation")
         if optimizer == TRON and (l1 > 0.0 or prior is not None or feature_scale is not None):
             raise ValueError("TRON minimises the smooth objective in theta units: it does not run with an L1 term, a prior model or feature normalisation")
+        if bounds is not None:
+            if l1 > 0.0 or optimizer == TRON or prior is not None or feature_scale is not None:
+                raise ValueError("bounds constrain the smooth objective in theta units under projected L-BFGS: they do not run with an L1 term, TRON, "
+                                 "a prior model or feature normalisation")
+            bounds = check_bounds(bounds, int(num_features) + (1 if has_intercept else 0), has_intercept)
         opts = fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance)
         fit = _SteppingFit(self.solver, opts, row_nnz_ptr, col_global, val, y, num_features, offset, weight, theta0, group, dummy, variance_mode,
                            prior=prior, feature_scale=feature_scale, down_sampling=down_sampling)
-        if l1 > 0.0 or optimizer == TRON:
+        if l1 > 0.0 or optimizer == TRON or bounds is not None:
             t0 = fit.prob.theta0
             if l1 > 0.0:
                 fit.prob.set_l1(l1)      # (leaves the problem at zeros)
+            elif bounds is not None:
+                fit.prob.set_bounds(*fit.device_bounds(bounds))      # (leaves the problem at the clamped zeros)
             else:
                 fit.prob.set_optimizer(optimizer)
             if t0 is not None:
@@ -220,6 +232,8 @@ class FixedEffectDeviceSolver:
         info["l1"] = l1
         info["optimizer"] = optimizer
         info["nnz"] = int(np.count_nonzero(theta))
+        if bounds is not None:
+            info["at_bound"] = count_at_bound(theta, bounds)
         if return_problem:
             return theta, info, fit.prob
         fit.prob.close()
@@ -227,15 +241,19 @@ class FixedEffectDeviceSolver:
 
     def fit_sweep(self, row_nnz_ptr, col_global, val, y, num_features, l2_grid, select, offset=None, weight=None, has_intercept=True,
                   regularize_bias=True, model_type=LOGISTIC_REGRESSION, max_iter=100, m=10, tolerance=1e-12, dummy=None, variance_mode=None,
-                  threshold=0.0, down_sampling=None, optimizer=LBFGS):
+                  threshold=0.0, down_sampling=None, optimizer=LBFGS, bounds=None):
         """One worker's fit for every weight of l2_grid on ONE problem: the shard is packed and gdmix_fe_create runs once; per weight, in the
         order given, gdmix_fe_restart (cold: zeros) + the same loop and status check as fit_stepping — by the restart's contract the bits
         of a fresh fit_stepping at that weight. select(thetas) — the K coefficient vectors as fit_stepping would have returned them — names
         the winner; -> (theta, info, best) of the winner as fit_stepping returns them, its variances (at its weight, for it alone) included.
         down_sampling: as fit_stepping takes it; the shard is sampled once, in front of the one pack. optimizer: as fit_stepping takes it;
-        the restarts keep it."""
+        the restarts keep it. bounds: as fit_stepping takes them; the restarts keep them, every model of the sweep lies in the box."""
         import dataclasses
         optimizer = check_optimizer(optimizer)
+        if bounds is not None:
+            if optimizer == TRON:
+                raise ValueError("bounds do not run with TRON, which minimises without constraints")
+            bounds = check_bounds(bounds, int(num_features) + (1 if has_intercept else 0), has_intercept)
         if _world_size(None) > 1:
             raise ValueError("a sweep over l2_reg_weight runs on one worker")
         opts = fit_options(has_intercept, float(l2_grid[0]), regularize_bias, model_type, max_iter, m, tolerance)
@@ -244,15 +262,45 @@ class FixedEffectDeviceSolver:
         try:
             if optimizer == TRON:
                 fit.prob.set_optimizer(optimizer)
+            if bounds is not None:
+                fit.prob.set_bounds(*fit.device_bounds(bounds))
             fits = []
             for w in l2_grid:
                 fit.prob.restart(dataclasses.replace(opts, l2=float(w)), None)
                 fits.append(fit.run())
             best = int(select([fit.strip_dummy(th) for th, _ in fits]))
             fits[best][1]["optimizer"] = optimizer
-            return fit.stage_result(*fits[best], l2_grid[best], threshold) + (best,)
+            theta, info = fit.stage_result(*fits[best], l2_grid[best], threshold)
+            if bounds is not None:
+                info["at_bound"] = count_at_bound(theta, bounds)
+            return theta, info, best
         finally:
             fit.prob.close()
+
+
+def check_bounds(bounds, P, has_intercept):
+    """(lower, upper) of fit_stepping -> two contiguous float64 arrays of P entries: no NaN, lower <= upper, the intercept (last) infinite.
+    (gdmix_fe_set_bounds refuses the same; here the message can name the coefficient.)"""
+    try:
+        lower, upper = (np.array(b, np.float64) for b in bounds)      # (copies: the caller's arrays may be read-only)
+    except (TypeError, ValueError):
+        raise ValueError("bounds are a pair (lower, upper) of arrays") from None
+    if lower.shape != (P,) or upper.shape != (P,):
+        raise ValueError(f"bounds: lower and upper hold {P} entries each (num_features + has_intercept, intercept last), not {lower.shape} and {upper.shape}")
+    bad = np.flatnonzero(np.isnan(lower) | np.isnan(upper))
+    if bad.size:
+        raise ValueError(f"bounds: coefficient {int(bad[0])} has a bound that is not a number")
+    bad = np.flatnonzero(lower > upper)
+    if bad.size:
+        raise ValueError(f"bounds: coefficient {int(bad[0])} has lower {lower[bad[0]]} > upper {upper[bad[0]]}")
+    if has_intercept and (lower[-1] != -np.inf or upper[-1] != np.inf):
+        raise ValueError("bounds: the intercept (the last entry) is never bounded: -inf and +inf")
+    return lower, upper
+
+
+def count_at_bound(theta, bounds):
+    """How many coefficients equal one of their bounds."""
+    return int(np.count_nonzero((theta == bounds[0]) | (theta == bounds[1])))
 
 
 def fit_options(has_intercept, l2, regularize_bias, model_type, max_iter, m, tolerance):
@@ -397,6 +445,18 @@ class _SteppingProblem:
         """gdmix_fe_set_l1: l1 > 0 puts the problem on the OWL-QN step, 0 back on the L-BFGS-B step. Leaves the problem as a restart with
         its current options at zeros does. Stream-ordered."""
         self._check(self.lib.gdmix_fe_set_l1(self._h, float(l1), self.solver._stream()), "gdmix_fe_set_l1")
+        self.theta0 = None
+
+    def set_bounds(self, lower_dev=None, upper_dev=None):
+        """gdmix_fe_set_bounds: float64 device tensors [D + has_intercept], intercept last and infinite (copied by the library) put the problem
+        on the projected L-BFGS step; None, None back on the L-BFGS-B step. Leaves the problem as a restart with its current options at the
+        clamped zeros does; a restart keeps the bounds."""
+        for x in (lower_dev, upper_dev):
+            if x is not None and (not x.is_cuda or x.dtype != self.solver.torch.float64 or not x.is_contiguous() or x.numel() != self.count - 1):
+                from .solver import GdmixReError
+                raise GdmixReError(f"a bound vector is a contiguous float64 device array of {self.count - 1} entries (intercept last)")
+        self._check(self.lib.gdmix_fe_set_bounds(self._h, None if lower_dev is None else lower_dev.data_ptr(),
+                                                 None if upper_dev is None else upper_dev.data_ptr(), self.solver._stream()), "gdmix_fe_set_bounds")
         self.theta0 = None
 
     def set_optimizer(self, optimizer):
@@ -624,6 +684,12 @@ class _SteppingFit:
                 self.all_reduce = all_reduce
         except ImportError:
             pass
+
+    def device_bounds(self, bounds):
+        """(lower, upper) of check_bounds as the device tensors set_bounds takes."""
+        if self.dummy:
+            raise ValueError("bounds name features: a model without a feature bag has none")
+        return tuple(self.solver.torch.from_numpy(b).to(self.solver.device) for b in bounds)
 
     def _pack_sample(self, shard, n_rows, rate, seed, uid):
         """Upload the shard, down-sample it on the device, pack the sample -> (the host batch of the sample or None while it stays in HBM,

@@ -6,6 +6,8 @@ import math
 from dataclasses import dataclass
 from typing import ClassVar, Optional
 
+import numpy as np
+
 from . import constants
 from .argv import from_argv, to_argv
 
@@ -65,6 +67,72 @@ def check_l1_reg_weight(value):
     if not math.isfinite(w) or w < 0.0:
         raise ValueError(f"--l1_reg_weight={value!r}: a finite weight >= 0")
     return w
+
+
+def coefficient_bounds(records, features, has_intercept, where="--coefficient_constraints"):
+    """Photon-ML's coefficient constraints as arrays. records: a list of {"name", "term", "lowerBound", "upperBound"} (either bound may be
+    absent: infinite); features: the (name, term) list of --feature_file, in coefficient order. "term": "*" covers every term of a name,
+    "name": "*" with "term": "*" every feature not named otherwise; an exact record beats a term wildcard, which beats the all-wildcard.
+    -> (lower, upper), float64 [len(features) + has_intercept], the intercept last and infinite. Every refusal names the record."""
+    if not isinstance(records, list):
+        raise ValueError(f"{where}: the file holds a JSON array of records, not {type(records).__name__}")
+    D = len(features)
+    lower, upper = np.full(D + (1 if has_intercept else 0), -np.inf), np.full(D + (1 if has_intercept else 0), np.inf)
+    by_name = {}
+    index = {}
+    for j, (name, term) in enumerate(features):
+        index[(name, term)] = j
+        by_name.setdefault(name, []).append(j)
+    level = np.full(D, -1)      # specificity of the record that set a feature's bounds: 0 all-wildcard, 1 term wildcard, 2 exact
+    seen = {}
+    for r in records:
+        if not isinstance(r, dict) or not isinstance(r.get("name"), str) or not isinstance(r.get("term"), str):
+            raise ValueError(f"{where}: record {r!r} needs a \"name\" and a \"term\", both strings")
+        unknown = set(r) - {"name", "term", "lowerBound", "upperBound"}
+        if unknown:
+            raise ValueError(f"{where}: record {r!r} has unknown keys {sorted(unknown)}")
+        lo, hi = r.get("lowerBound"), r.get("upperBound")
+        for key, v in (("lowerBound", lo), ("upperBound", hi)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v)):
+                raise ValueError(f"{where}: record {r!r}: {key} must be a finite number (leave it out for no bound)")
+        lo, hi = -np.inf if lo is None else float(lo), np.inf if hi is None else float(hi)
+        if lo > hi:
+            raise ValueError(f"{where}: record {r!r}: lowerBound > upperBound")
+        name, term = r["name"], r["term"]
+        if name == constants.INTERCEPT:
+            raise ValueError(f"{where}: record {r!r} names the intercept, which is never bounded")
+        if name == "*" and term != "*":
+            raise ValueError(f"{where}: record {r!r}: a wildcard name goes with a wildcard term")
+        if (name, term) in seen:
+            raise ValueError(f"{where}: records {seen[name, term]!r} and {r!r} are for the same features")
+        seen[name, term] = r
+        if name == "*":
+            spec, cover = 0, range(D)
+        elif term == "*":
+            spec, cover = 1, by_name.get(name, [])
+        else:
+            spec, cover = 2, [index[name, term]] if (name, term) in index else []
+        if len(cover) == 0:
+            raise ValueError(f"{where}: record {r!r} matches no feature of the feature file")
+        for j in cover:
+            if spec > level[j]:
+                level[j], lower[j], upper[j] = spec, lo, hi
+    return lower, upper
+
+
+def read_coefficient_constraints(path, features, has_intercept):
+    """--coefficient_constraints=PATH -> (lower, upper) of coefficient_bounds; the file is a JSON array in the shape of Photon-ML's
+    constraint string. Python's NaN / Infinity literals are refused like any non-finite number."""
+    import json
+
+    def refuse(literal):
+        raise ValueError(f"--coefficient_constraints={path}: {literal} is not a finite number (leave the bound out for no bound)")
+    with open(path) as f:
+        try:
+            records = json.load(f, parse_constant=refuse)
+        except json.JSONDecodeError as e:
+            raise ValueError(f"--coefficient_constraints={path}: not JSON ({e})") from None
+    return coefficient_bounds(records, features, has_intercept, where=f"--coefficient_constraints={path}")
 
 
 def parse_l2_grid(text):
@@ -205,6 +273,8 @@ class REParams(LRParams):
     # ... and so is --optimizer: anything but LBFGS is refused. The random-effect kernels run scipy's L-BFGS-B loop on chip; a trust-region
     # Newton solver inside them is another project.
     optimizer: str = "LBFGS"
+    # ... and so is --coefficient_constraints: box constraints for per-entity models are a follow-up.
+    coefficient_constraints: Optional[str] = None
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -216,6 +286,8 @@ class REParams(LRParams):
 
     def __post_init__(self):
         self.l2_grid()      # a bad list is an error at parse time
+        if self.coefficient_constraints is not None:
+            raise ValueError(f"--coefficient_constraints={self.coefficient_constraints}: the random effect has no box constraints (the flag belongs to the fixed-effect stage)")
         if check_l1_reg_weight(self.l1_reg_weight) != 0.0:
             raise ValueError(f"--l1_reg_weight={self.l1_reg_weight}: the random effect has no L1 term (the flag belongs to the fixed-effect stage)")
         if str(self.optimizer).strip().upper() != "LBFGS":

@@ -135,7 +135,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_widen_workspace_bytes", "gdmix_re_widen", "gdmix_re_set_timing", "gdmix_re_last_solve_ms", "gdmix_re_set_kernel_mask", "gdmix_re_set_giant_nnz", "gdmix_re_set_team_nnz", "gdmix_re_set_tall_min_n", "gdmix_re_set_tall_split_n", "gdmix_re_set_tall_team_n", "gdmix_re_set_tall_mid_n", "gdmix_re_set_spread", "gdmix_re_set_narrow",
     "gdmix_fe_create", "gdmix_fe_destroy", "gdmix_fe_eval", "gdmix_fe_reduce_buffer", "gdmix_fe_step", "gdmix_fe_step_async", "gdmix_fe_step_status", "gdmix_fe_solve", "gdmix_fe_result",
     "gdmix_fe_last_eval_ms", "gdmix_fe_stream_bytes", "gdmix_fe_score", "gdmix_fe_hessian_diag", "gdmix_fe_hessian_dense_scratch_bytes", "gdmix_fe_hessian_dense", "gdmix_fe_hessian_dense_loss",
-    "gdmix_fe_variance_of_hessian", "gdmix_fe_restart", "gdmix_fe_set_prior", "gdmix_fe_set_l1", "gdmix_fe_set_optimizer", "gdmix_fe_products", "gdmix_fe_hessian_vec", "gdmix_fe_score_models_workspace_bytes", "gdmix_fe_score_models",
+    "gdmix_fe_variance_of_hessian", "gdmix_fe_restart", "gdmix_fe_set_prior", "gdmix_fe_set_l1", "gdmix_fe_set_optimizer", "gdmix_fe_set_bounds", "gdmix_fe_products", "gdmix_fe_hessian_vec", "gdmix_fe_score_models_workspace_bytes", "gdmix_fe_score_models",
     "gdmix_re_eval_workspace_bytes", "gdmix_re_eval_entities", "gdmix_re_set_eval_small_max", "gdmix_re_eval_acc_reset", "gdmix_re_eval_acc_add",
     "gdmix_re_eval_acc_workspace_bytes", "gdmix_re_eval_acc_finish",
     "gdmix_re_eval_pl_entities", "gdmix_re_eval_pl_acc_reset", "gdmix_re_eval_pl_acc_add", "gdmix_re_eval_pl_acc_finish",
@@ -227,6 +227,7 @@ def load_library():
     lib.gdmix_fe_set_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gdmix_fe_set_l1.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
     lib.gdmix_fe_set_optimizer.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.gdmix_fe_set_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gdmix_fe_products.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
     lib.gdmix_fe_hessian_vec.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gdmix_fe_score_models_workspace_bytes.argtypes = [C.c_int64, C.c_int]
@@ -298,7 +299,7 @@ def load_library():
     lib.gdmix_re_cap_apply.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.POINTER(_CapOpts), C.c_void_p, C.c_size_t, C.POINTER(_DownsampleOut),
                                        C.c_void_p, C.c_void_p]
     lib.gdmix_re_set_cap_small_max.argtypes = [C.c_void_p, C.c_int]
-    if lib.gdmix_re_abi_version() != 25:
+    if lib.gdmix_re_abi_version() != 26:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib

@@ -287,6 +287,44 @@ GDMIX_API int gdmix_fe_set_optimizer(gdmix_fe_problem* p, int optimizer, void* s
 GDMIX_API int gdmix_fe_products(gdmix_fe_problem* p, int64_t* nhv, void* stream);
 GDMIX_API int gdmix_fe_hessian_vec(gdmix_fe_problem* p, const double* theta, const double* v, void* stream);
 
+/* ---- (ABI 26) box constraints: projected L-BFGS ----------------------------------------------------------------------------------------------
+ * --coefficient_constraints (gdmix_amd/fe_model.py; Photon-ML's coefficient box constraints) minimises the smooth
+ *     F(theta) = sum_i w_i l(y_i, x_i . w + b + offset_i) + (l2/2) |theta_R|^2     subject to  lo_j <= theta_j <= hi_j
+ * of any of the three losses. lo_j may be -inf, hi_j may be +inf, lo_j == hi_j pins a coefficient; the intercept is never bounded.
+ * gdmix_fe_set_bounds: lower, upper are device pointers to [D + has_intercept] doubles, intercept last (copied by the library: 2 P doubles of
+ *   the problem's own, allocated at the first selection; the pool does not change). Bounds make the problem take the projected L-BFGS step
+ *   (csrc/fe_box.hip) from its next step on; both NULL puts it back on the L-BFGS-B step. Either way the call leaves the problem in the state
+ *   of a gdmix_fe_restart with its current options at the clamped zeros. Stream-ordered but for one wait, on the check of the caller's arrays.
+ *   gdmix_fe_restart keeps the bounds; its theta0 (NULL: zeros) is clamped into the box and that is the start point.
+ *   Refused with GDMIX_RE_EINVAL, the problem left as it was: a NaN bound; lo_j > hi_j; a bound on the intercept other than -inf / +inf;
+ *   bounds while l1 > 0, on a TRON problem, or while a prior is installed — and the mirror calls gdmix_fe_set_l1 > 0,
+ *   gdmix_fe_set_optimizer(TRON) and gdmix_fe_set_prior with a prior on a problem that has bounds. (Bounds under the substitution
+ *   phi = (theta - mu) / s are per-coefficient work, (lo - mu) / s and (hi - mu) / s: a follow-up.)
+ * Every other entry point keeps its contract: gdmix_fe_eval is the same two passes, gdmix_fe_step / _step_async / _step_status / _solve, the
+ * status ring, the lookahead and the stop flag work as before, the step leaves the reduce buffer cleared, and the -inf mark of an aborted
+ * peer in the value slot stops every worker with GDMIX_RE_ST_ABORTED_PEER.
+ * The step. g is the gradient of F (with the l2 term) at the accepted point x; clamp(v)_j = min(max(v_j, lo_j), hi_j), exactly the bound's
+ * double where it clamps.
+ *   binding set      B = { j : (x_j <= lo_j and g_j > 0) or (x_j >= hi_j and g_j < 0) or lo_j == hi_j }. Reduced gradient: q_j = 0 on B, g_j off B.
+ *   direction        d = -H q, H the L-BFGS inverse-Hessian approximation over the last <= m stored pairs s = x+ - x, y = g+ - g,
+ *                    H0 = (s'y / y'y) I from the newest pair; then d_j = 0 on B, and wherever x_j <= lo_j and d_j < 0 or x_j >= hi_j and
+ *                    d_j > 0. No pair stored: d = -q.
+ *   trial            x(t) = clamp(x + t d).
+ *   search           t = 1 / |q|_2 while no pair is stored, else 1; accepted when F(x(t)) <= F(x) + 1e-4 g'(x(t) - x), else t is halved.
+ *                    After maxls rejected trials in one iteration: the memory is cleared and the search starts again along -q if a pair
+ *                    was stored, else the solve stops with status 4 at x.
+ *   pair storage     only if s'y > 2.2e-16 y'y.
+ *   stops            after each accepted iterate, in this order: max_j |x_j - clamp(x - g)_j| <= pgtol -> 0 (scipy's projected gradient; also
+ *                    tested at the start point); F_old - F <= ftol max(|F_old|, |F|, 1) -> 1; nit >= max_iter -> 2; nfev > maxfun -> 3. Every
+ *                    evaluation counts in nfev.
+ *   start point      clamp(theta0); zeros are clamped too.
+ * gdmix_fe_result returns the last accepted point, never a rejected trial: lo <= theta <= hi holds exactly and a coefficient at a bound is
+ * the bound's double. fval = F, gnorm = the projected-gradient norm above, nit, nfev as above.
+ * gdmix_fe_hessian_diag and the FULL variance path are unchanged. Variances are those of the smooth objective at the returned theta,
+ * gdmix_fe_hessian_diag plus l2, as without bounds. A coefficient at a bound gets one too: this feature's own choice (the variance says how
+ * well the data determine the coefficient, not whether a constraint holds it). */
+GDMIX_API int gdmix_fe_set_bounds(gdmix_fe_problem* p, const double* lower, const double* upper, void* stream);
+
 /* gdmix_fe_score under K coefficient vectors in ONE pass over the shard's non-zeros (csrc/fe_sweep.hip). thetas: HOST array of K device
  * pointers, each [num_features + has_intercept] with the intercept last; score / per_coord: [K][n] float, row k for thetas[k]
  * (per_coord may be NULL). Defined by equivalence: row k is bit for bit what gdmix_fe_score writes for thetas[k] — a row's products
