@@ -57,13 +57,14 @@ def tall_resident_bytes(nw, sets, d, n, nnz, has_w):
     return nw * (d + 1) * (sets + 1) * 8 + 8 * (nnz + 8) + 4 * (n + 2) + (12 if has_w else 8) * n + 16
 
 
-def route(p, n, nnz, m, has_w, tall_min_n, ic=1):
+def route(p, n, nnz, m, has_w, tall_min_n, ic=1, team_nnz=16384):
     """The class of an entity of p coefficients (ic of them the intercept), n samples and nnz non-zeros: the first group class whose three
     caps hold it (m <= 10 only), then the first wavefront bucket that holds its wave_lds_bytes, else the workgroup class; with
     tall_min_n > 0 an entity of p <= 64 and n >= tall_min_n (m <= 10) is tall instead: the lean one-wavefront class when it is resident
     in a lean workgroup's arena, else the one-wavefront class. The team, giant and tall-split thresholds are at their defaults
-    (16 384 non-zeros and more, 512 samples and more at p <= 64), out of reach of the shapes of this file."""
-    assert nnz < 16384 and not (p <= TALL_MAX_P and n >= 512)
+    (16 384 non-zeros and more, 512 samples and more at p <= 64), out of reach of the shapes of this file. team_nnz: the first non-zero
+    count this rule does not speak for (team_edges_helpers.route_large states the tiers from there on and passes its own)."""
+    assert nnz < team_nnz and not (p <= TALL_MAX_P and n >= 512)
     d = p - ic
     c = BLOCK_CLASS
     for k, (g, epl, ncap, zcap) in enumerate(GROUP_CLASSES):
