@@ -943,6 +943,8 @@ int pack_impl(gdmix_ctx_impl* ctx, const gdmix_re_raw_batch* raw, int has_interc
     HIP_TRY(fetch_small(ctx, 1, stats, sizeof(PackStats), hs, s));
   }
   if (hs->err) {
+    // a refused batch has no reader to wait for a deferred compaction: the caller's stream does, before the caller gives the workspace back
+    if (defer) HIP_TRY(join_unique(ctx, s));
     set_error("pack: an entity exceeds a per-entity int32 limit or a feature index is outside [0, 2^31)");
     return hs->err;
   }
