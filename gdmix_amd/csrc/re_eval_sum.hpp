@@ -1,4 +1,4 @@
-// re_eval_sum.hpp — what the two evaluation units (re_evaluate.hip: SSE; re_evaluate_poisson.hip: PL) share: the shape of the fixed-shape
+// re_eval_sum.hpp — what the two evaluation units (re_evaluate.hip: SSE; re_evaluate_poisson.hip: PL and the logistic loss LL) share: the shape of the fixed-shape
 // fp64 sum of one term per sample — its constants, its block tree, the accumulator's geometry — stated HERE and only here; the error
 // bounds of include/gdmix_re.h ("SSE", "poisson evaluation") are bounds of this shape.
 //

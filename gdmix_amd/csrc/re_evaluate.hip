@@ -17,6 +17,11 @@
 //                         workgroup waits for another. Its time is the radix sort's passes over 8 B keys (profiles/evaluate_bench.txt).
 //   SSE                   the fixed-shape sum of re_eval_sum.hpp over the non-negative fp64 terms (y - s)^2 (a large entity: one workgroup;
 //                         the accumulator: its batches' sums are added in the order they were given). Relative error below 2.5e-13.
+//   ranking               gdmix_re_eval_topk_entities (include/gdmix_re.h, "ranking evaluation"): the four integers of precision@k for up to
+//                         four k. topk_small_kernel: eval_small_kernel's geometry with the keys of all valid samples through LDS, and that
+//                         kernel's outputs from the same read when the caller wants them; topk_big_kernel: a workgroup per large entity on
+//                         its sorted segment (binary searches for the tie group of the cut). The sort path's steps up to the sorted keys
+//                         (sort_big_entities) and from them to the AUC outputs (rank_and_finish) are shared by the two entry points.
 #include <stdint.h>
 #include <math.h>
 
@@ -333,6 +338,152 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_acc_sum_kernel(const double
   if (threadIdx.x == 0) *sse += v;
 }
 
+// ---- ranking: the four integers of precision@k per entity (include/gdmix_re.h, "ranking evaluation") --------------------------------------
+constexpr int TOPK_MAX = 4, TOPK_THREADS = 256;
+struct TopkKs { int32_t k[TOPK_MAX]; int nk; };
+struct TopkOutDev { int32_t* hits_sure; int32_t* slots; int32_t* tie_pos; int32_t* tie_size; };   // [nk][E] each, k-major
+__device__ __forceinline__ void write_topk(const TopkOutDev& T, int64_t E, int kk, int64_t e, int hits_sure, int slots, int tie_pos, int tie_size) {
+  const size_t at = (size_t)kk * (size_t)E + (size_t)e;
+  if (T.hits_sure) T.hits_sure[at] = hits_sure;
+  if (T.slots) T.slots[at] = slots;
+  if (T.tie_pos) T.tie_pos[at] = tie_pos;
+  if (T.tie_size) T.tie_size[at] = tie_size;
+}
+
+// Small entities: eval_small_kernel's geometry (four entities per wavefront, 16 / 32 / 64 lanes each, lane i holds sample i), with the keys
+// of ALL valid samples through LDS (every other lane stores KEY_NAN, which is above every score's key): lane i counts lt = #{k_j < k_i} and
+// le = #{k_j <= k_i}; with n valid samples gt = n - le and ge = n - lt. Sample i is above the cut <=> ge <= k - 1, in the tie group of the
+// cut <=> gt < k <= ge. The four integers of a k are sums of flags over the group, four 8-bit fields of one word (each at most 64).
+// The loop over k runs on the counts in registers. WITH_AUC: the wavefront also does what eval_small_kernel does, with that
+// kernel's operations in that kernel's order (the same integers, the same bits of sse), from the one read of the samples.
+template <bool WITH_AUC>
+__global__ __launch_bounds__(64) void topk_small_kernel(const int64_t* __restrict__ ent_row_ptr, int64_t E, const float* __restrict__ score,
+                                                        const float* __restrict__ label, TopkOutDev T, TopkKs K, EvalOutDev O, int small_max) {
+  __shared__ __attribute__((aligned(16))) uint32_t all_keys[64];
+  __shared__ __attribute__((aligned(16))) uint32_t neg_keys[64];
+  const int lane = threadIdx.x;
+  const int64_t e0 = (int64_t)blockIdx.x * 4;
+  const int64_t last = e0 + 4 < E ? e0 + 4 : E;
+  const int64_t mine = ent_row_ptr[e0 + lane < last ? e0 + lane : last];   // lanes 0 .. 4 matter
+  int64_t rp[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) rp[k] = __shfl(mine, k);
+  int nmax = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t n = rp[k + 1] - rp[k];
+    if (n <= small_max && (int)n > nmax) nmax = (int)n;
+  }
+  const int W = nmax <= 16 ? 16 : (nmax <= 32 ? 32 : 64);
+  const int per_pass = 64 / W;
+  const int g = lane / W, li = lane & (W - 1), base = lane & ~(W - 1);
+  for (int pass = 0; pass < W / 16; ++pass) {
+    const int k = pass * per_pass + g;
+    const int64_t start = k == 0 ? rp[0] : (k == 1 ? rp[1] : (k == 2 ? rp[2] : rp[3]));
+    const int64_t end = k == 0 ? rp[1] : (k == 1 ? rp[2] : (k == 2 ? rp[3] : rp[4]));
+    const int64_t n = end - start;
+    const bool ent_ok = e0 + k < E && n <= small_max;
+    const bool have = ent_ok && li < n;
+    float s = 0.0f, y = 0.0f;
+    if (have) { s = score[start + li]; y = label[start + li]; }
+    const uint32_t key = have ? sortable_key(s) : KEY_NAN;
+    const bool nan = have && key == KEY_NAN;
+    const bool pos = have && !nan && y > 0.5f;
+    const bool neg = have && !nan && !pos;
+    all_keys[lane] = key;                       // KEY_NAN for a NaN score and for a lane without a sample
+    if (WITH_AUC) neg_keys[lane] = neg ? key : KEY_NAN;
+    __syncthreads();
+    uint32_t lt = 0, le = 0, cnt = 0;
+    for (int j = 0; j < W; j += 4) {
+      const uint4 v = *reinterpret_cast<const uint4*>(&all_keys[base + j]);
+      lt += (uint32_t)(v.x < key) + (uint32_t)(v.y < key) + (uint32_t)(v.z < key) + (uint32_t)(v.w < key);
+      le += (uint32_t)(v.x <= key) + (uint32_t)(v.y <= key) + (uint32_t)(v.z <= key) + (uint32_t)(v.w <= key);
+      if (WITH_AUC) {
+        const uint4 u = *reinterpret_cast<const uint4*>(&neg_keys[base + j]);
+        cnt += (uint32_t)(u.x < key) + (uint32_t)(u.x <= key) + (uint32_t)(u.y < key) + (uint32_t)(u.y <= key) +
+               (uint32_t)(u.z < key) + (uint32_t)(u.z <= key) + (uint32_t)(u.w < key) + (uint32_t)(u.w <= key);
+      }
+    }
+    __syncthreads();   // the next pass overwrites the keys
+    uint32_t a = (pos ? cnt : 0u) | ((pos ? 1u : 0u) << 16);
+    uint32_t b = (neg ? 1u : 0u) | ((nan ? 1u : 0u) << 16);
+    double sse = (WITH_AUC && have && !nan) ? sq_err(s, y) : 0.0;
+    for (int off = 1; off < W; off <<= 1) {
+      a += __shfl_xor(a, off);
+      b += __shfl_xor(b, off);
+      if (WITH_AUC) sse += __shfl_xor(sse, off);
+    }
+    const int n_pos = (int)(a >> 16), n_neg = (int)(b & 0xFFFFu);
+    if (WITH_AUC && ent_ok && li == 0) write_entity(O, e0 + k, a & 0xFFFFu, n_pos, n_neg, (int)(b >> 16), sse);
+    const int nv = n_pos + n_neg;               // valid samples; a valid lane's le counts valid keys only (KEY_NAN is above its key)
+    const int gt = nv - (int)le, ge = nv - (int)lt;
+    const bool valid = have && !nan;
+    for (int kk = 0; kk < K.nk; ++kk) {
+      const int64_t kv = K.k[kk];
+      const bool above = valid && (int64_t)ge <= kv - 1;
+      const bool tie = valid && (int64_t)gt < kv && kv <= (int64_t)ge;
+      // fields: hits (pos & above) | above << 8 | tie_pos << 16 | tie_size << 24
+      uint32_t w = ((pos && above) ? 1u : 0u) | ((above ? 1u : 0u) << 8) | (((pos && tie) ? 1u : 0u) << 16) | ((tie ? 1u : 0u) << 24);
+      for (int off = 1; off < W; off <<= 1) w += __shfl_xor(w, off);
+      if (ent_ok && li == 0) {
+        if ((int64_t)nv <= kv) write_topk(T, E, kk, e0 + k, n_pos, 0, 0, 0);
+        else write_topk(T, E, kk, e0 + k, (int)(w & 0xFFu), (int)(kv - (int64_t)((w >> 8) & 0xFFu)), (int)((w >> 16) & 0xFFu), (int)(w >> 24));
+      }
+    }
+  }
+}
+
+// Large entities: one workgroup on the entity's sorted segment (ascending 33-bit keys under the segment number; a tie's negatives in front
+// of its positives; NaN keys last). With n valid keys and n > k the cut key c is at position n - k; three binary searches in the segment
+// (c << 1, c << 1 | 1, (c + 1) << 1) give the tie group and its positives; the positives above the cut are counted by the workgroup over
+// the keys behind the tie group — fewer than k of them (n <= k: over all n valid keys).
+__device__ __forceinline__ int64_t seg_lower_bound(const uint64_t* __restrict__ seg, int64_t n, uint64_t want33) {   // first i < n with key33 >= want33, or n
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if ((seg[mid] & 0x1FFFFFFFFull) < want33) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(TOPK_THREADS) void topk_big_kernel(const int64_t* __restrict__ ent_row_ptr, const int32_t* __restrict__ big_list,
+                                                                const int32_t* __restrict__ big_off, const uint64_t* __restrict__ sorted, int64_t E,
+                                                                TopkOutDev T, TopkKs K) {
+  __shared__ int64_t sh_from, sh_nv;
+  __shared__ int sh_out[3];
+  __shared__ unsigned sh_hits;
+  const int b = blockIdx.x;
+  const int64_t e = big_list[b];
+  const int64_t n_all = ent_row_ptr[e + 1] - ent_row_ptr[e];
+  const uint64_t* seg = sorted + big_off[b];
+  for (int kk = 0; kk < K.nk; ++kk) {
+    const int64_t kv = K.k[kk];
+    if (threadIdx.x == 0) {
+      const int64_t nv = seg_lower_bound(seg, n_all, (uint64_t)KEY_NAN << 1);
+      int64_t from = 0;
+      int slots = 0, tie_pos = 0, tie_size = 0;
+      if (nv > kv) {
+        const uint64_t c = (seg[nv - kv] & 0x1FFFFFFFFull) >> 1;
+        const int64_t lo = seg_lower_bound(seg, nv, c << 1), mid = seg_lower_bound(seg, nv, (c << 1) | 1ull), hi = seg_lower_bound(seg, nv, (c + 1ull) << 1);
+        slots = (int)(kv - (nv - hi));
+        tie_pos = (int)(hi - mid);
+        tie_size = (int)(hi - lo);
+        from = hi;
+      }
+      sh_from = from; sh_nv = nv;
+      sh_out[0] = slots; sh_out[1] = tie_pos; sh_out[2] = tie_size;
+      sh_hits = 0u;
+    }
+    __syncthreads();
+    const int64_t from = sh_from, nv = sh_nv;
+    unsigned hits = 0u;
+    for (int64_t i = from + threadIdx.x; i < nv; i += TOPK_THREADS) hits += (unsigned)(seg[i] & 1ull);
+    if (hits) atomicAdd(&sh_hits, hits);
+    __syncthreads();
+    if (threadIdx.x == 0) write_topk(T, E, kk, e, (int)sh_hits, sh_out[0], sh_out[1], sh_out[2]);
+    __syncthreads();   // the next k resets the shared words
+  }
+}
+
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int64_t rank_tiles(int64_t M) { return (M + RANK_TILE - 1) / RANK_TILE; }
 
@@ -403,6 +554,60 @@ static AccLayout acc_layout(int64_t N) {
   return L;
 }
 
+// ---- the sort path's steps, shared by gdmix_re_eval_entities and gdmix_re_eval_topk_entities --------------------------------------------
+// mark -> one prefix sum -> (the one synchronisation: how many entities are large) -> list -> keys -> radix sort. `sorted` holds the
+// segments of the large entities in their order, segment b at big_off[b], a NaN score's key last in its segment.
+struct SortedBig { int64_t nbig, M; int32_t* big_list; int32_t* big_off; uint64_t* sorted; RankState* partial; uint64_t* acc_two_u; uint32_t* acc_cnt; };
+static int sort_big_entities(gdmix_ctx_impl* ci, const char* who, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                             int small_max, const EvalLayout& L, char* base, hipStream_t s, SortedBig* B) {
+  int64_t* mark = reinterpret_cast<int64_t*>(base + L.mark);
+  int64_t* offs = reinterpret_cast<int64_t*>(base + L.offs);
+  int32_t* big_list = reinterpret_cast<int32_t*>(base + L.big_list);
+  int32_t* big_off = reinterpret_cast<int32_t*>(base + L.big_off);
+  uint64_t* keys_a = reinterpret_cast<uint64_t*>(base + L.keys_a);
+  uint64_t* keys_b = reinterpret_cast<uint64_t*>(base + L.keys_b);
+  B->nbig = 0; B->M = 0;
+  B->big_list = big_list; B->big_off = big_off; B->sorted = keys_b;
+  B->partial = reinterpret_cast<RankState*>(base + L.partial);
+  B->acc_two_u = reinterpret_cast<uint64_t*>(base + L.acc_two_u);
+  B->acc_cnt = reinterpret_cast<uint32_t*>(base + L.acc_cnt);
+  // the entities of the sort path: numbered and laid out by one prefix sum
+  hipLaunchKernelGGL(eval_mark_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, s, ent_row_ptr, E, small_max, mark);
+  HIP_TRY(hipGetLastError());
+  size_t scan_bytes = 0;
+  HIP_TRY((rocprim::exclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)E + 1, rocprim::plus<int64_t>(), s)));
+  void* tmp = nullptr;
+  int rc = eval_tmp(ci, scan_bytes ? scan_bytes : 1, s, &tmp);
+  if (rc != GDMIX_RE_OK) return rc;
+  HIP_TRY((rocprim::exclusive_scan(tmp, scan_bytes, mark, offs, (int64_t)0, (size_t)E + 1, rocprim::plus<int64_t>(), s)));
+  int64_t total = 0;
+  HIP_TRY(fetch_small(ci, 2, offs + E, sizeof(int64_t), &total, s));
+  const int64_t nbig = total >> 32, M = total & 0xFFFFFFFFll;
+  if (nbig == 0) return GDMIX_RE_OK;
+  if (M > N) { set_error("%s: ent_row_ptr covers %lld samples, N is %lld", who, (long long)M, (long long)N); return GDMIX_RE_EINVAL; }
+  hipLaunchKernelGGL(eval_big_list_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, (const int64_t*)mark, (const int64_t*)offs, E, big_list, big_off);
+  if (M > 0) hipLaunchKernelGGL(eval_big_keys_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, ent_row_ptr, (const int32_t*)big_list,
+                                (const int32_t*)big_off, (int)nbig, M, score, label, keys_a);
+  HIP_TRY(hipGetLastError());
+  unsigned sbits = 0;
+  while (((int64_t)1 << sbits) < nbig) ++sbits;
+  if (M > 0) {
+    rc = sort_keys(ci, keys_a, keys_b, M, 33u + sbits, s);
+    if (rc != GDMIX_RE_OK) return rc;
+  }
+  B->nbig = nbig; B->M = M;
+  return GDMIX_RE_OK;
+}
+// the rank-sum pass over the sorted segments, then a workgroup per large entity: its SSE and its outputs
+static int rank_and_finish(const SortedBig& B, const int64_t* ent_row_ptr, const float* score, const float* label, const EvalOutDev& O, hipStream_t s) {
+  const int rc = rank_sum(B.sorted, B.M, B.nbig, B.partial, B.acc_two_u, B.acc_cnt, s);
+  if (rc != GDMIX_RE_OK) return rc;
+  hipLaunchKernelGGL(eval_big_finish_kernel, dim3((unsigned)B.nbig), dim3(EVAL_THREADS), 0, s, ent_row_ptr, (const int32_t*)B.big_list, score, label,
+                     (const uint64_t*)B.acc_two_u, (const uint32_t*)B.acc_cnt, O);
+  HIP_TRY(hipGetLastError());
+  return GDMIX_RE_OK;
+}
+
 }  // namespace gdmix
 
 using namespace gdmix;
@@ -439,50 +644,58 @@ GDMIX_API int gdmix_re_eval_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_p
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int small_max = ci->eval_small_set ? ci->eval_small_max : 64;
   const EvalOutDev O = {out->two_u, out->n_pos, out->n_neg, out->n_nan, out->sse, out->auc};
-  char* base = static_cast<char*>(workspace);
-  int64_t* mark = reinterpret_cast<int64_t*>(base + L.mark);
-  int64_t* offs = reinterpret_cast<int64_t*>(base + L.offs);
-  int32_t* big_list = reinterpret_cast<int32_t*>(base + L.big_list);
-  int32_t* big_off = reinterpret_cast<int32_t*>(base + L.big_off);
-  uint64_t* keys_a = reinterpret_cast<uint64_t*>(base + L.keys_a);
-  uint64_t* keys_b = reinterpret_cast<uint64_t*>(base + L.keys_b);
-  RankState* partial = reinterpret_cast<RankState*>(base + L.partial);
-  uint64_t* acc_two_u = reinterpret_cast<uint64_t*>(base + L.acc_two_u);
-  uint32_t* acc_cnt = reinterpret_cast<uint32_t*>(base + L.acc_cnt);
-
   // (with a limit of 0 — every entity through the sort path — this launch still writes the entities of no samples)
   hipLaunchKernelGGL(eval_small_kernel, dim3((unsigned)((E + 3) / 4)), dim3(64), 0, s, ent_row_ptr, E, score, label, O, small_max);
   HIP_TRY(hipGetLastError());
-  // the entities of the sort path: numbered and laid out by one prefix sum
-  hipLaunchKernelGGL(eval_mark_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, s, ent_row_ptr, E, small_max, mark);
-  HIP_TRY(hipGetLastError());
-  size_t scan_bytes = 0;
-  HIP_TRY((rocprim::exclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)E + 1, rocprim::plus<int64_t>(), s)));
-  void* tmp = nullptr;
-  int rc = eval_tmp(ci, scan_bytes ? scan_bytes : 1, s, &tmp);
-  if (rc != GDMIX_RE_OK) return rc;
-  HIP_TRY((rocprim::exclusive_scan(tmp, scan_bytes, mark, offs, (int64_t)0, (size_t)E + 1, rocprim::plus<int64_t>(), s)));
-  int64_t total = 0;
-  HIP_TRY(fetch_small(ci, 2, offs + E, sizeof(int64_t), &total, s));
-  const int64_t nbig = total >> 32, M = total & 0xFFFFFFFFll;
-  if (nbig == 0) return GDMIX_RE_OK;
-  if (M > N) { set_error("gdmix_re_eval_entities: ent_row_ptr covers %lld samples, N is %lld", (long long)M, (long long)N); return GDMIX_RE_EINVAL; }
-  hipLaunchKernelGGL(eval_big_list_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, (const int64_t*)mark, (const int64_t*)offs, E, big_list, big_off);
-  if (M > 0) hipLaunchKernelGGL(eval_big_keys_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, ent_row_ptr, (const int32_t*)big_list,
-                                (const int32_t*)big_off, (int)nbig, M, score, label, keys_a);
-  HIP_TRY(hipGetLastError());
-  unsigned sbits = 0;
-  while (((int64_t)1 << sbits) < nbig) ++sbits;
-  if (M > 0) {
-    rc = sort_keys(ci, keys_a, keys_b, M, 33u + sbits, s);
-    if (rc != GDMIX_RE_OK) return rc;
+  SortedBig B;
+  int rc = sort_big_entities(ci, "gdmix_re_eval_entities", ent_row_ptr, E, N, score, label, small_max, L, static_cast<char*>(workspace), s, &B);
+  if (rc != GDMIX_RE_OK || B.nbig == 0) return rc;
+  return rank_and_finish(B, ent_row_ptr, score, label, O, s);
+}
+
+GDMIX_API size_t gdmix_re_eval_topk_workspace_bytes(int64_t E, int64_t N) { return gdmix_re_eval_workspace_bytes(E, N); }
+
+GDMIX_API int gdmix_re_eval_topk_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                          const int32_t* ks, int nk, const gdmix_re_eval_topk_out* out, const gdmix_re_eval_out* auc_out,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ctx || !out || E < 0 || N < 0) { set_error("gdmix_re_eval_topk_entities: bad argument"); return GDMIX_RE_EINVAL; }
+  if (!ks || nk < 1 || nk > TOPK_MAX) { set_error("gdmix_re_eval_topk_entities: nk = %d; 1 .. %d values of k in ks", nk, TOPK_MAX); return GDMIX_RE_EINVAL; }
+  TopkKs K;
+  K.nk = nk;
+  for (int i = 0; i < TOPK_MAX; ++i) K.k[i] = i < nk ? ks[i] : 0;
+  for (int i = 0; i < nk; ++i) {
+    if (ks[i] < 1) { set_error("gdmix_re_eval_topk_entities: ks[%d] = %d; every k is at least 1", i, (int)ks[i]); return GDMIX_RE_EINVAL; }
+    for (int j = 0; j < i; ++j)
+      if (ks[j] == ks[i]) { set_error("gdmix_re_eval_topk_entities: ks[%d] = ks[%d] = %d; the values of k are distinct", j, i, (int)ks[i]); return GDMIX_RE_EINVAL; }
   }
-  rc = rank_sum(keys_b, M, nbig, partial, acc_two_u, acc_cnt, s);
-  if (rc != GDMIX_RE_OK) return rc;
-  hipLaunchKernelGGL(eval_big_finish_kernel, dim3((unsigned)nbig), dim3(EVAL_THREADS), 0, s, ent_row_ptr, (const int32_t*)big_list, score, label,
-                     (const uint64_t*)acc_two_u, (const uint32_t*)acc_cnt, O);
+  if (N >= EVAL_LIMIT || E >= EVAL_LIMIT) {
+    set_error("gdmix_re_eval_topk_entities: %lld samples / %lld entities; an evaluation takes fewer than 2^31 of each", (long long)N, (long long)E);
+    return GDMIX_RE_ERANGE;
+  }
+  if (E == 0) return GDMIX_RE_OK;
+  if (!ent_row_ptr || (N > 0 && (!score || !label))) { set_error("gdmix_re_eval_topk_entities: NULL input"); return GDMIX_RE_EINVAL; }
+  const EvalLayout L = eval_layout(E, N);
+  if (!workspace || workspace_bytes < L.total) {
+    set_error("gdmix_re_eval_topk_entities: workspace of %zu bytes, %zu needed (gdmix_re_eval_topk_workspace_bytes)", workspace_bytes, L.total);
+    return GDMIX_RE_ENOMEM;
+  }
+  gdmix_ctx_impl* ci = &ctx->impl;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int small_max = ci->eval_small_set ? ci->eval_small_max : 64;
+  const bool with_auc = auc_out != nullptr;
+  EvalOutDev O = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (with_auc) O = {auc_out->two_u, auc_out->n_pos, auc_out->n_neg, auc_out->n_nan, auc_out->sse, auc_out->auc};
+  const TopkOutDev T = {out->hits_sure, out->slots, out->tie_pos, out->tie_size};
+  if (with_auc) hipLaunchKernelGGL(topk_small_kernel<true>, dim3((unsigned)((E + 3) / 4)), dim3(64), 0, s, ent_row_ptr, E, score, label, T, K, O, small_max);
+  else hipLaunchKernelGGL(topk_small_kernel<false>, dim3((unsigned)((E + 3) / 4)), dim3(64), 0, s, ent_row_ptr, E, score, label, T, K, O, small_max);
   HIP_TRY(hipGetLastError());
-  return GDMIX_RE_OK;
+  SortedBig B;
+  int rc = sort_big_entities(ci, "gdmix_re_eval_topk_entities", ent_row_ptr, E, N, score, label, small_max, L, static_cast<char*>(workspace), s, &B);
+  if (rc != GDMIX_RE_OK || B.nbig == 0) return rc;
+  hipLaunchKernelGGL(topk_big_kernel, dim3((unsigned)B.nbig), dim3(TOPK_THREADS), 0, s, ent_row_ptr, (const int32_t*)B.big_list, (const int32_t*)B.big_off,
+                     (const uint64_t*)B.sorted, E, T, K);
+  HIP_TRY(hipGetLastError());
+  return with_auc ? rank_and_finish(B, ent_row_ptr, score, label, O, s) : GDMIX_RE_OK;
 }
 
 GDMIX_API int gdmix_re_eval_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_acc* acc, void* stream) {

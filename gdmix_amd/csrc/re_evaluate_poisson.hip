@@ -10,6 +10,8 @@
 //                          the stage's total is the rounded exact sum of its batches' sums, in whatever order they came.
 // The shape of every sum is SSE's: the constants, the trees and the accumulator's geometry are the same code (re_eval_sum.hpp).
 // Never a floating-point atomic; NaN scores are left out and counted (integer atomics: their sum has no order).
+// The kernels and the entry points' bodies are templates over the per-sample term: PlTerm (gdmix_re_eval_pl_*) and LlTerm, the logistic loss
+// (gdmix_re_eval_ll_*; include/gdmix_re.h, "ranking evaluation"). The Poisson instantiation does the operations it did as plain kernels, in their order.
 #include <stdint.h>
 #include <math.h>
 #include <string.h>
@@ -25,8 +27,22 @@ __device__ __forceinline__ double pl_term(float s, float y) {
   return __builtin_fma(-(double)y, z, exp_any(z));
 }
 
+struct PlTerm { static __device__ __forceinline__ double term(float s, float y) { return pl_term(s, y); } };
+
+// the logistic loss of a score: max(z, 0) - z [y > 0.5] + log(1 + exp(-|z|)) (include/gdmix_re.h, "ranking evaluation", log loss). The first two
+// terms are formed as max(-z, 0) for a positive and max(z, 0) for a negative: the same number without a rounding, and no inf - inf.
+// u = 1 + e is rounded before the logarithm, as in the solve kernels' logistic_terms: an absolute error, not a relative one
+// (tools/logloss_check.c measures it).
+__device__ __forceinline__ double ll_term(float s, float y) {
+  const double z = (double)s;
+  const double e = exp_neg(fabs(z));
+  return fmax(y > 0.5f ? -z : z, 0.0) + log_1_2(1.0 + e);
+}
+struct LlTerm { static __device__ __forceinline__ double term(float s, float y) { return ll_term(s, y); } };
+
 struct PlOutDev { double* pl; int32_t* n; int32_t* n_nan; };
 
+template <class Term>
 __global__ __launch_bounds__(64) void eval_pl_small_kernel(const int64_t* __restrict__ ent_row_ptr, int64_t E, const float* __restrict__ score,
                                                            const float* __restrict__ label, PlOutDev O, int small_max) {
   const int lane = threadIdx.x;
@@ -55,7 +71,7 @@ __global__ __launch_bounds__(64) void eval_pl_small_kernel(const int64_t* __rest
     float s = 0.0f, y = 0.0f;
     if (have) { s = score[start + li]; y = label[start + li]; }
     const bool nan = have && s != s;
-    double pl = (have && !nan) ? pl_term(s, y) : 0.0;
+    double pl = (have && !nan) ? Term::term(s, y) : 0.0;
     uint32_t c = ((have && !nan) ? 1u : 0u) | ((nan ? 1u : 0u) << 16);   // two counts <= 64 in one word
     for (int off = 1; off < W; off <<= 1) {
       pl += __shfl_xor(pl, off);
@@ -70,6 +86,7 @@ __global__ __launch_bounds__(64) void eval_pl_small_kernel(const int64_t* __rest
 }
 
 // one workgroup per entity of the batch; those of the small path leave at once (the choice is uniform over the workgroup)
+template <class Term>
 __global__ __launch_bounds__(EVAL_THREADS) void eval_pl_big_kernel(const int64_t* __restrict__ ent_row_ptr, const float* __restrict__ score,
                                                                    const float* __restrict__ label, PlOutDev O, int small_max) {
   __shared__ double lds[EVAL_THREADS];
@@ -84,7 +101,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pl_big_kernel(const int64_t
   unsigned nans = 0u;
   for (int64_t i = r0 + threadIdx.x; i < r1; i += EVAL_THREADS) {
     const float s = score[i];
-    if (s == s) run += pl_term(s, label[i]); else ++nans;
+    if (s == s) run += Term::term(s, label[i]); else ++nans;
     if (++in_run == EVAL_RUN) {
       total += run; run = 0.0; in_run = 0;
       if (++runs == EVAL_RUNS) { top += total; total = 0.0; runs = 0; }
@@ -101,6 +118,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pl_big_kernel(const int64_t
 
 // the accumulator's device state: [0] hi, [1] lo of the total, [2] the NaN scores (u64) in its head; then a batch's workgroup sums.
 // The lane loop is the accumulator's of re_eval_sum.hpp (one level of runs), as in eval_acc_add_kernel.
+template <class Term>
 __global__ __launch_bounds__(EVAL_THREADS) void eval_pl_acc_add_kernel(const float* __restrict__ score, const float* __restrict__ label, int64_t N,
                                                                        double* __restrict__ group_sum, unsigned long long* __restrict__ n_nan) {
   __shared__ double lds[EVAL_THREADS];
@@ -110,7 +128,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pl_acc_add_kernel(const flo
   unsigned nans = 0u;
   for (int64_t i = (int64_t)blockIdx.x * EVAL_THREADS + threadIdx.x; i < N; i += stride) {
     const float s = score[i];
-    if (s == s) run += pl_term(s, label[i]); else ++nans;
+    if (s == s) run += Term::term(s, label[i]); else ++nans;
     if (++in_run == EVAL_RUN) { total += run; run = 0.0; in_run = 0; }
   }
   if (nans) atomicAdd(n_nan, (unsigned long long)nans);
@@ -133,55 +151,52 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pl_acc_sum_kernel(const dou
   }
 }
 
-}  // namespace gdmix
-
-using namespace gdmix;
-
-extern "C" {
-
-GDMIX_API int gdmix_re_eval_pl_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
-                                        const gdmix_re_eval_pl_out* out, void* stream) {
-  if (!ctx || !out || E < 0 || N < 0) { set_error("gdmix_re_eval_pl_entities: bad argument"); return GDMIX_RE_EINVAL; }
+// ---- the entry points' bodies: one per call, instantiated for the two terms ("gdmix_re_eval_pl" / "gdmix_re_eval_ll" in the messages) ------
+template <class Term>
+static int term_entities(const char* who, gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                         const gdmix_re_eval_pl_out* out, void* stream) {
+  if (!ctx || !out || E < 0 || N < 0) { set_error("%s_entities: bad argument", who); return GDMIX_RE_EINVAL; }
   if (N >= EVAL_LIMIT || E >= EVAL_LIMIT) {
-    set_error("gdmix_re_eval_pl_entities: %lld samples / %lld entities; an evaluation takes fewer than 2^31 of each", (long long)N, (long long)E);
+    set_error("%s_entities: %lld samples / %lld entities; an evaluation takes fewer than 2^31 of each", who, (long long)N, (long long)E);
     return GDMIX_RE_ERANGE;
   }
   if (E == 0) return GDMIX_RE_OK;
-  if (!ent_row_ptr || (N > 0 && (!score || !label))) { set_error("gdmix_re_eval_pl_entities: NULL input"); return GDMIX_RE_EINVAL; }
+  if (!ent_row_ptr || (N > 0 && (!score || !label))) { set_error("%s_entities: NULL input", who); return GDMIX_RE_EINVAL; }
   gdmix_ctx_impl* ci = &ctx->impl;
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(ci->device));
   const int small_max = ci->eval_small_set ? ci->eval_small_max : 64;
   const PlOutDev O = {out->pl, out->n, out->n_nan};
-  hipLaunchKernelGGL(eval_pl_small_kernel, dim3((unsigned)((E + 3) / 4)), dim3(64), 0, s, ent_row_ptr, E, score, label, O, small_max);
-  hipLaunchKernelGGL(eval_pl_big_kernel, dim3((unsigned)E), dim3(EVAL_THREADS), 0, s, ent_row_ptr, score, label, O, small_max);
+  hipLaunchKernelGGL(eval_pl_small_kernel<Term>, dim3((unsigned)((E + 3) / 4)), dim3(64), 0, s, ent_row_ptr, E, score, label, O, small_max);
+  hipLaunchKernelGGL(eval_pl_big_kernel<Term>, dim3((unsigned)E), dim3(EVAL_THREADS), 0, s, ent_row_ptr, score, label, O, small_max);
   HIP_TRY(hipGetLastError());
   return GDMIX_RE_OK;
 }
 
-GDMIX_API int gdmix_re_eval_pl_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, void* stream) {
-  if (!ctx || !acc || !acc->state) { set_error("gdmix_re_eval_pl_acc_reset: bad argument (acc->state is required)"); return GDMIX_RE_EINVAL; }
-  static_assert(GDMIX_RE_EVAL_PL_STATE_BYTES >= ACC_STATE_BYTES, "the accumulator's device state");
+static int term_acc_reset(const char* who, gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, void* stream) {
+  if (!ctx || !acc || !acc->state) { set_error("%s_acc_reset: bad argument (acc->state is required)", who); return GDMIX_RE_EINVAL; }
+  static_assert(GDMIX_RE_EVAL_PL_STATE_BYTES >= ACC_STATE_BYTES && GDMIX_RE_EVAL_LL_STATE_BYTES == GDMIX_RE_EVAL_PL_STATE_BYTES, "the accumulator's device state");
   HIP_TRY(hipSetDevice(ctx->impl.device));
   HIP_TRY(hipMemsetAsync(acc->state, 0, ACC_HEAD_BYTES, static_cast<hipStream_t>(stream)));
   acc->count = 0;
   return GDMIX_RE_OK;
 }
 
-GDMIX_API int gdmix_re_eval_pl_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, const float* score, const float* label, int64_t N, void* stream) {
-  if (!ctx || !acc || !acc->state || N < 0 || acc->count < 0) { set_error("gdmix_re_eval_pl_acc_add: bad argument"); return GDMIX_RE_EINVAL; }
+template <class Term>
+static int term_acc_add(const char* who, gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, const float* score, const float* label, int64_t N, void* stream) {
+  if (!ctx || !acc || !acc->state || N < 0 || acc->count < 0) { set_error("%s_acc_add: bad argument", who); return GDMIX_RE_EINVAL; }
   if (N == 0) return GDMIX_RE_OK;
   if (acc->count + N >= EVAL_LIMIT) {
-    set_error("gdmix_re_eval_pl_acc_add: %lld + %lld samples; an evaluation takes fewer than 2^31", (long long)acc->count, (long long)N);
+    set_error("%s_acc_add: %lld + %lld samples; an evaluation takes fewer than 2^31", who, (long long)acc->count, (long long)N);
     return GDMIX_RE_ERANGE;
   }
-  if (!score || !label) { set_error("gdmix_re_eval_pl_acc_add: NULL input"); return GDMIX_RE_EINVAL; }
+  if (!score || !label) { set_error("%s_acc_add: NULL input", who); return GDMIX_RE_EINVAL; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(ctx->impl.device));
   const int64_t groups = acc_groups(N);
   double* state = static_cast<double*>(acc->state);
   double* group_sum = acc_group_sums(acc->state);
-  hipLaunchKernelGGL(eval_pl_acc_add_kernel, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, s, score, label, N, group_sum,
+  hipLaunchKernelGGL(eval_pl_acc_add_kernel<Term>, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, s, score, label, N, group_sum,
                      reinterpret_cast<unsigned long long*>(state + 2));
   hipLaunchKernelGGL(eval_pl_acc_sum_kernel, dim3(1), dim3(EVAL_THREADS), 0, s, (const double*)group_sum, (int)groups, state);
   HIP_TRY(hipGetLastError());
@@ -189,8 +204,8 @@ GDMIX_API int gdmix_re_eval_pl_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* 
   return GDMIX_RE_OK;
 }
 
-GDMIX_API int gdmix_re_eval_pl_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_pl_acc* acc, gdmix_re_eval_pl_totals* host_out, void* stream) {
-  if (!ctx || !acc || !acc->state || !host_out || acc->count < 0) { set_error("gdmix_re_eval_pl_acc_finish: bad argument"); return GDMIX_RE_EINVAL; }
+static int term_acc_finish(const char* who, gdmix_re_ctx* ctx, const gdmix_re_eval_pl_acc* acc, gdmix_re_eval_pl_totals* host_out, void* stream) {
+  if (!ctx || !acc || !acc->state || !host_out || acc->count < 0) { set_error("%s_acc_finish: bad argument", who); return GDMIX_RE_EINVAL; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(ctx->impl.device));
   double st[3] = {0.0, 0.0, 0.0};
@@ -203,5 +218,28 @@ GDMIX_API int gdmix_re_eval_pl_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval
   host_out->n = acc->count - (int64_t)n_nan;
   return GDMIX_RE_OK;
 }
+
+}  // namespace gdmix
+
+using namespace gdmix;
+
+extern "C" {
+
+#define GDMIX_TERM_FAMILY(prefix, Term)                                                                                                               \
+  GDMIX_API int prefix##_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,        \
+                                  const gdmix_re_eval_pl_out* out, void* stream) {                                                                    \
+    return term_entities<Term>(#prefix, ctx, ent_row_ptr, E, N, score, label, out, stream);                                                           \
+  }                                                                                                                                                   \
+  GDMIX_API int prefix##_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, void* stream) { return term_acc_reset(#prefix, ctx, acc, stream); }  \
+  GDMIX_API int prefix##_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, const float* score, const float* label, int64_t N, void* stream) {     \
+    return term_acc_add<Term>(#prefix, ctx, acc, score, label, N, stream);                                                                            \
+  }                                                                                                                                                   \
+  GDMIX_API int prefix##_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_pl_acc* acc, gdmix_re_eval_pl_totals* host_out, void* stream) {            \
+    return term_acc_finish(#prefix, ctx, acc, host_out, stream);                                                                                      \
+  }
+
+GDMIX_TERM_FAMILY(gdmix_re_eval_pl, PlTerm)
+GDMIX_TERM_FAMILY(gdmix_re_eval_ll, LlTerm)
+#undef GDMIX_TERM_FAMILY
 
 }  // extern "C"

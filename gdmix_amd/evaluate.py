@@ -1,7 +1,7 @@
 """Drop-in for gdmix-data's metric job (com.linkedin.gdmix.evaluation.Evaluator), on the device:
 
     python -m gdmix_amd.evaluate --metricsInputDir D --outputMetricFile F --labelColumnName response \\
-        --predictionColumnName predictionScore --metricName auc|mse|poisson_loss
+        --predictionColumnName predictionScore --metricName auc|mse|poisson_loss|logistic_loss
 
 reads every Avro file under D, evaluates (score, label) with gdmix_amd.metrics.DeviceEvaluator and writes F/evalSummary.json =
 {"<metricName>": value}: the Spark job's flags (all required) and its output. The score files are read with the Python Avro decoder
@@ -21,7 +21,8 @@ EVAL_SUMMARY_JSON = "evalSummary.json"
 
 def parse(argv) -> dict:
     """--flag value or --flag=value for the five required flags -> dict. ValueError for anything else, a missing flag, or a metric
-    other than auc / mse / poisson_loss (the Evaluator's wording for its two). Touches no device."""
+    other than auc / mse / poisson_loss / logistic_loss (the Evaluator's wording for its two). Touches no device. The grouped metrics of a
+    stage's --evaluators (auc:<id>, precision@K:<id>) are not offered here: score files carry no entity id."""
     out = {}
     it = iter(argv)
     for a in it:
@@ -44,7 +45,7 @@ def parse(argv) -> dict:
 
 
 def check_metric(name):
-    if name not in (metrics.AUC, metrics.MSE, metrics.POISSON_LOSS):      # (poisson_loss is this library's: the Evaluator has no such metric)
+    if name not in (metrics.AUC, metrics.MSE, metrics.POISSON_LOSS, metrics.LOGISTIC_LOSS):      # (the two losses are this library's: the Evaluator has no such metric)
         raise ValueError(f"Do not support metric {name}, currently only support 'auc' and 'mse'.")
 
 
@@ -72,7 +73,7 @@ def evaluate(score, label, metric_name, solver=None) -> dict:
         from .solver import REDeviceSolver
         solver = REDeviceSolver(0)
     try:
-        ev = metrics.PoissonEvaluator(solver) if metric_name == metrics.POISSON_LOSS else metrics.DeviceEvaluator(solver)
+        ev = {metrics.POISSON_LOSS: metrics.PoissonEvaluator, metrics.LOGISTIC_LOSS: metrics.LogLossEvaluator}.get(metric_name, metrics.DeviceEvaluator)(solver)
         ev.add(score, label)
         return ev.finish()
     finally:

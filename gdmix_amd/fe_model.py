@@ -61,7 +61,7 @@ from .io import avro, native_reader, tfrecord
 from .io.features import read_feature_list
 from .io.grouped_reader import resolve_input_files
 from .io.metadata import DatasetMetadata
-from .params import LRParams, check_feature_normalization, check_l1_reg_weight, parse_l2_grid, read_coefficient_constraints
+from .params import LRParams, check_evaluators_model_type, check_feature_normalization, check_l1_reg_weight, parse_l2_grid, read_coefficient_constraints
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.INFO)
@@ -110,6 +110,15 @@ class FixedLRParams(LRParams):
     # (params.coefficient_bounds). The stage trains by projected L-BFGS on the device (include/gdmix_fe.h, "(ABI 26) box constraints").
     # --action=inference accepts and ignores the flag.
     coefficient_constraints: Optional[str] = None
+    # not in the reference; the random-effect stage's flag of the same name (params.REParams). A fixed effect has no entities: the list
+    # holds LOGISTIC_LOSS only, and the stage's evalSummary.json gains "logistic_loss" and "ll". Needs metric_output_dir and
+    # --model_type=logistic_regression; does not run with l2_reg_weights.
+    evaluators: Optional[str] = None
+
+    def evaluator_spec(self):
+        """What --evaluators asks for (params.EvaluatorSpec), or None without the flag."""
+        from .params import check_evaluators
+        return check_evaluators(self, None, fixed_effect=True)
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -126,6 +135,7 @@ class FixedLRParams(LRParams):
     def __post_init__(self):
         super().__post_init__()
         self.l2_grid()      # a bad list is an error at parse time
+        self.evaluator_spec()
         from .downsample import check_rate
         try:
             self.down_sampling_rate = check_rate(self.down_sampling_rate)
@@ -248,6 +258,8 @@ class FixedEffectLRModelLBFGS:
         self.training_output_dir = base_training_params.training_score_dir
         self.validation_output_dir = base_training_params.validation_score_dir
         self.model_type = base_training_params.model_type
+        self.evaluator_spec = p.evaluator_spec()      # --evaluators (params.EvaluatorSpec: LOGISTIC_LOSS only here), or None
+        check_evaluators_model_type(self.evaluator_spec, self.model_type)
         self.training_data_dir = p.training_data_dir
         self.validation_data_dir = p.validation_data_dir
         self.metadata_file = p.metadata_file
@@ -329,7 +341,7 @@ class FixedEffectLRModelLBFGS:
             fe = self._solver()
             if not hasattr(fe, "score_device"):
                 raise NotImplementedError("--metric_output_dir needs the device scoring path (FixedEffectDeviceSolver.score_device)")
-            self._metrics = metrics.StageMetrics(getattr(fe, "solver", None), self.metric_output_dir, self._metric_name())
+            self._metrics = metrics.StageMetrics(getattr(fe, "solver", None), self.metric_output_dir, self._metric_name(), self.evaluator_spec)
 
     def _finish_metrics(self):
         m, self._metrics = self._metrics, None
@@ -546,7 +558,9 @@ class FixedEffectLRModelLBFGS:
                 if which not in self._metrics.ev:
                     poisson = self._metrics.metric == "poisson_loss"
                     self._metrics.ev[which] = fe.new_evaluator(self._metrics.metric) if poisson else fe.new_evaluator()
-                self._metrics.ev[which].add(fe.file_scores(shard, per_dev), shard.y)
+                file_scores = fe.file_scores(shard, per_dev)
+                self._metrics.ev[which].add(file_scores, shard.y)
+                self._metrics.add_log_loss(which, file_scores, shard.y)      # (--evaluators=LOGISTIC_LOSS; nothing without it)
             per_coord = fe.to_host(per_dev)
         else:
             fe = self._solver()

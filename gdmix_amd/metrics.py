@@ -17,6 +17,7 @@ from . import solver as _solver
 
 AUC, MSE = "auc", "mse"
 POISSON_LOSS = "poisson_loss"        # mean of exp(s) - y s: the metric of a poisson_regression stage (include/gdmix_re.h, "poisson evaluation")
+LOGISTIC_LOSS = "logistic_loss"      # mean of the logistic loss of a score (include/gdmix_re.h, "ranking evaluation"): --evaluators=LOGISTIC_LOSS
 
 
 def metric_of_loss(loss) -> str:
@@ -29,6 +30,15 @@ def poisson_loss_terms(score, label) -> np.ndarray:
     definition (tests add the terms up with math.fsum); it does not evaluate a stage."""
     s = np.asarray(score, np.float32).astype(np.float64)
     return np.exp(s) - np.asarray(label, np.float32).astype(np.float64) * s
+
+
+def logistic_loss_terms(score, label) -> np.ndarray:
+    """The host statement of the device's log-loss terms: log(1 + exp(s)) - [y > 0.5] s in fp64, the fp32 score widened first. It states
+    the definition (tests add the terms up with math.fsum); it does not evaluate a stage."""
+    s = np.asarray(score, np.float32).astype(np.float64)
+    return np.logaddexp(0.0, s) - (np.asarray(label, np.float32) > 0.5) * s
+
+
 EXACT_DEVICE_DIVISION = 1 << 26      # entities below this many samples: auc[e] of the device is the correctly rounded quotient
 
 
@@ -68,6 +78,43 @@ def entities_to_host(res) -> dict:
     return h
 
 
+def precision_from_counts(hits_sure, slots, tie_pos, tie_size, k) -> float:
+    """precision@k = (hits_sure + slots tie_pos / tie_size) / k from the device's exact integers, correctly rounded (the tie term is 0
+    when tie_size is 0): the expected share of positives among the k best under a uniformly random order inside tie groups."""
+    hits_sure, slots, tie_pos, tie_size, k = int(hits_sure), int(slots), int(tie_pos), int(tie_size), int(k)
+    if k < 1:
+        raise ValueError(f"precision@{k}: k is at least 1")
+    h = Fraction(hits_sure) + (Fraction(slots * tie_pos, tie_size) if tie_size else 0)
+    return float(h / k)
+
+
+def precision_key(k) -> str:
+    """The per-entity field of precision@k (an Avro name)."""
+    return f"precision_at_{int(k)}"
+
+
+def ranking_entities_to_host(res, ks) -> dict:
+    """The tensors of RankingEvaluator.entities -> numpy arrays: what entities_to_host gives, the four [nk, E] integer arrays, and per k
+    `precision_at_<k>` [E] float64 — one fp64 division of exactly converted int64 numerator and denominator (exact for entities below
+    2^26 samples: with ties n > k, so both stay below 2^53; larger entities go through Fraction). NaN with a NaN score, as auc is."""
+    counts = ("hits_sure", "slots", "tie_pos", "tie_size")
+    h = entities_to_host({k: v for k, v in res.items() if k not in counts})
+    c = {k: _solver.host_array(res[k]).astype(np.int64) for k in counts}
+    h.update({k: c[k].astype(np.int32) for k in counts})
+    big = np.flatnonzero(h["n"] >= EXACT_DEVICE_DIVISION)
+    for j, k in enumerate(ks):
+        hs, sl, tp, ts = (c[name][j] for name in counts)
+        tied = ts > 0
+        num = np.where(tied, hs * ts + sl * tp, hs).astype(np.float64)
+        den = np.where(tied, ts * np.int64(k), np.int64(k)).astype(np.float64)
+        p = num / den
+        for e in big:
+            p[e] = precision_from_counts(hs[e], sl[e], tp[e], ts[e], k)
+        p[h["n_nan"] > 0] = np.nan
+        h[precision_key(k)] = p
+    return h
+
+
 def poisson_entities_to_host(res) -> dict:
     """The tensors of PoissonEvaluator.entities -> numpy arrays, with `n` (every sample, NaN scores included) and `poisson_loss`
     (pl / n, NaN for an entity without samples or with a NaN score)."""
@@ -86,6 +133,11 @@ PER_ENTITY_SCHEMA = {"type": "record", "name": "EntityMetricAvro", "namespace": 
     {"name": "auc", "type": ["null", "double"]}, {"name": "mse", "type": "double"}]}
 PER_ENTITY_POISSON_SCHEMA = {"type": "record", "name": "EntityPoissonMetricAvro", "namespace": "gdmix_amd", "fields": [
     {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "poisson_loss", "type": "double"}]}
+def ranking_entity_schema(ks) -> dict:
+    """PER_ENTITY_SCHEMA with one nullable double per requested k behind it (null: a NaN score in the entity)."""
+    return dict(PER_ENTITY_SCHEMA, fields=PER_ENTITY_SCHEMA["fields"] + [{"name": precision_key(k), "type": ["null", "double"]} for k in ks])
+
+
 SUMMARY_KEYS = ("n", "n_pos", "n_neg", "n_nan", "two_u", "sse")
 POISSON_SUMMARY_KEYS = ("n", "n_nan", "pl")
 
@@ -152,12 +204,14 @@ class _Evaluator:
 
 class PoissonEvaluator(_Evaluator):
     """The Poisson loss on one MI355X through the solver's context, with DeviceEvaluator's interface: `entities` per entity of a scored
-    batch, `add` ... `finish` over everything a stage scores."""
+    batch, `add` ... `finish` over everything a stage scores. (LogLossEvaluator below is this class over the other family of entry
+    points: FAMILY names it, METRIC the mean `finish` reports.)"""
     OUTPUTS = (("pl", "float64"), ("n", "int32"), ("n_nan", "int32"))
     OUT_STRUCT = _solver._EvalPlOut
     SUMMARY_KEYS = POISSON_SUMMARY_KEYS
     ENTITY_SCHEMA = PER_ENTITY_POISSON_SCHEMA
     to_host = staticmethod(poisson_entities_to_host)
+    FAMILY, METRIC, SUM = "gdmix_re_eval_pl", POISSON_LOSS, "pl"
 
     def __init__(self, solver):
         super().__init__(solver)
@@ -165,19 +219,22 @@ class PoissonEvaluator(_Evaluator):
         self._acc = _solver._EvalPlAcc(self._state.data_ptr(), 0)
         self.reset()
 
+    def _fn(self, call):
+        return getattr(self.lib, f"{self.FAMILY}_{call}")
+
     def entities(self, packed_or_ent_row_ptr, score, label=None) -> dict:
         """-> {"pl" float64, "n", "n_nan" int32}: device tensors, one entry per entity (n: the samples whose score is not NaN)."""
         s = self.solver
         rp, score, label, E, N, res, c_out = self._entities_args(packed_or_ent_row_ptr, score, label)
         with s._ctx_lock:
-            _solver._check(self.lib.gdmix_re_eval_pl_entities(s._h, rp.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
-                                                              C.byref(c_out), s._stream()), "gdmix_re_eval_pl_entities")
+            _solver._check(self._fn("entities")(s._h, rp.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
+                                                              C.byref(c_out), s._stream()), self.FAMILY + "_entities")
         return res
 
     def reset(self):
         s = self.solver
         with s._ctx_lock:
-            _solver._check(self.lib.gdmix_re_eval_pl_acc_reset(s._h, C.byref(self._acc), s._stream()), "gdmix_re_eval_pl_acc_reset")
+            _solver._check(self._fn("acc_reset")(s._h, C.byref(self._acc), s._stream()), self.FAMILY + "_acc_reset")
 
     def add(self, score, label):
         score, label, N = self._pair(score, label)
@@ -185,8 +242,8 @@ class PoissonEvaluator(_Evaluator):
             return
         s = self.solver
         with s._ctx_lock:
-            _solver._check(self.lib.gdmix_re_eval_pl_acc_add(s._h, C.byref(self._acc), score.data_ptr(), label.data_ptr(), N, s._stream()),
-                           "gdmix_re_eval_pl_acc_add")
+            _solver._check(self._fn("acc_add")(s._h, C.byref(self._acc), score.data_ptr(), label.data_ptr(), N, s._stream()),
+                           self.FAMILY + "_acc_add")
 
     def finish(self) -> dict:
         """-> {"poisson_loss", "pl", "n", "n_nan"}: the mean (NaN when a score was NaN or nothing was added), the sum over the scores that
@@ -194,9 +251,28 @@ class PoissonEvaluator(_Evaluator):
         s = self.solver
         tot = _solver._EvalPlTotals()
         with s._ctx_lock:
-            _solver._check(self.lib.gdmix_re_eval_pl_acc_finish(s._h, C.byref(self._acc), C.byref(tot), s._stream()), "gdmix_re_eval_pl_acc_finish")
+            _solver._check(self._fn("acc_finish")(s._h, C.byref(self._acc), C.byref(tot), s._stream()), self.FAMILY + "_acc_finish")
         n, n_nan = int(tot.n), int(tot.n_nan)
-        return {POISSON_LOSS: float("nan") if n_nan > 0 or n == 0 else float(tot.pl) / n, "pl": float(tot.pl), "n": n + n_nan, "n_nan": n_nan}
+        return {self.METRIC: float("nan") if n_nan > 0 or n == 0 else float(tot.pl) / n, self.SUM: float(tot.pl), "n": n + n_nan, "n_nan": n_nan}
+
+
+def logloss_entities_to_host(res) -> dict:
+    """The tensors of LogLossEvaluator.entities -> numpy arrays, with `n` (every sample, NaN scores included) and `logistic_loss`
+    (ll / n, NaN for an entity without samples or with a NaN score)."""
+    h = poisson_entities_to_host(res)
+    h[LOGISTIC_LOSS] = h.pop(POISSON_LOSS)
+    h["ll"] = h["pl"]
+    return h
+
+
+class LogLossEvaluator(PoissonEvaluator):
+    """The logistic loss of (score, label) on the device, with PoissonEvaluator's interface (include/gdmix_re.h, "ranking evaluation": the
+    gdmix_re_eval_ll_ entry points share the Poisson family's structs, so `entities` returns the per-entity sums under "pl"; `finish`
+    -> {"logistic_loss", "ll", "n", "n_nan"})."""
+    SUMMARY_KEYS = ("n", "n_nan", "ll")
+    ENTITY_SCHEMA = None
+    to_host = staticmethod(logloss_entities_to_host)
+    FAMILY, METRIC, SUM = "gdmix_re_eval_ll", LOGISTIC_LOSS, "ll"
 
 
 class DeviceEvaluator(_Evaluator):
@@ -277,6 +353,40 @@ class DeviceEvaluator(_Evaluator):
                 "n": int(tot.n), "n_pos": n_pos, "n_neg": n_neg, "n_nan": n_nan, "two_u": int(tot.two_u), "sse": float(tot.sse)}
 
 
+class RankingEvaluator(_Evaluator):
+    """precision@k per entity for up to four k, and DeviceEvaluator's per-entity outputs, from ONE device call and one sort
+    (gdmix_re_eval_topk_entities). ks: distinct integers >= 1."""
+    COUNTS = ("hits_sure", "slots", "tie_pos", "tie_size")
+    OUTPUTS = DeviceEvaluator.OUTPUTS
+    OUT_STRUCT = _solver._EvalOut
+
+    def __init__(self, solver, ks):
+        super().__init__(solver)
+        self.ks = tuple(int(k) for k in ks)
+        if not 1 <= len(self.ks) <= _solver.EVAL_TOPK_MAX or len(set(self.ks)) != len(self.ks) or min(self.ks) < 1 or max(self.ks) >= 1 << 31:
+            raise _solver.GdmixReError(f"RankingEvaluator: ks = {list(ks)}; 1 .. {_solver.EVAL_TOPK_MAX} distinct integers, each in [1, 2^31)")
+
+    def to_host(self, res):
+        return ranking_entities_to_host(res, self.ks)
+
+    def entities(self, packed_or_ent_row_ptr, score, label=None, workspace_bytes=None, with_auc=True) -> dict:
+        """-> {"hits_sure", "slots", "tie_pos", "tie_size": int32 [nk, E]} and, with_auc, DeviceEvaluator.entities' tensors: all on the
+        device."""
+        t, s = self.torch, self.solver
+        rp, score, label, E, N, res, c_auc = self._entities_args(packed_or_ent_row_ptr, score, label)
+        nk = len(self.ks)
+        counts = {k: t.zeros((nk, E), dtype=t.int32, device=s.device) for k in self.COUNTS}
+        c_out = _solver._EvalTopkOut(*(counts[k].data_ptr() if E else None for k in self.COUNTS))
+        c_ks = (C.c_int32 * nk)(*self.ks)
+        nbytes = int(self.lib.gdmix_re_eval_topk_workspace_bytes(E, N)) if workspace_bytes is None else int(workspace_bytes)
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=s.device)
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_topk_entities(s._h, rp.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
+                                                                c_ks, nk, C.byref(c_out), C.byref(c_auc) if with_auc else None, ws.data_ptr(), nbytes,
+                                                                s._stream()), "gdmix_re_eval_topk_entities")
+        return dict(res, **counts) if with_auc else counts
+
+
 EVALUATOR_OF_METRIC = {AUC: DeviceEvaluator, MSE: DeviceEvaluator, POISSON_LOSS: PoissonEvaluator}
 
 
@@ -301,13 +411,38 @@ class StageMetrics:
                                    (the data the workflow's evaluator reads), or the training block of a stage without validation data
         perEntity/part-<data>-<partition directory>-<score file>.avro     records {entityId, n, n_pos, auc (null: one class), mse}
     A Poisson stage (metric "poisson_loss"): the summary's keys are {"poisson_loss", "n", "n_nan", "pl"}, the records {entityId, n, poisson_loss}.
-    One worker, one summary: workers of a multi-process job need a directory each."""
+    One worker, one summary: workers of a multi-process job need a directory each.
+    With `spec` (--evaluators; params.EvaluatorSpec) every block of the summary gains
+        "logistic_loss", "ll"                                  the mean and the sum of the logistic loss (LogLossEvaluator)
+        "auc:<id>", "auc:<id>_records"                         the mean of auc over the per-entity RECORDS (what write_entities wrote for
+                                                               that data: an entity with active and passive training data has two or more) that
+                                                               have both classes, and how many those are
+        "precision@K:<id>", "precision@K:<id>_records"         the mean of precision@K over the records with a sample, per requested K
+    and the records one nullable double precision_at_K per K. Each mean is math.fsum of the records' values over their number: the sum is
+    exact, so the value depends on no order or grouping of partitions. Any record with a NaN score makes it NaN (null), as the stage
+    metric. Without `spec` every file is byte for byte what it was."""
 
-    def __init__(self, solver, out_dir, metric_name):
+    def __init__(self, solver, out_dir, metric_name, spec=None):
         self.solver, self.out_dir, self.metric = solver, out_dir, metric_name
         self.evaluator = EVALUATOR_OF_METRIC[metric_name]      # the class: it says what is summed, kept and written
         self.ev = {}
         self._warned = False
+        self.spec = spec
+        self.entity_schema = self.evaluator.ENTITY_SCHEMA
+        self.ll = {}             # which -> LogLossEvaluator (spec.log_loss)
+        self.ranking = None      # RankingEvaluator (spec.ranking): one device call gives the per-entity AUC outputs and precision@k
+        self.records = {}        # which -> {"nan": records with a NaN score, "auc": [values], precision_key(k): [values]}
+        if spec is not None and spec.ranking:
+            self.ks = spec.ks if spec.ks else (1,)      # AUC:<id> alone still takes the one call; its k is not reported
+            self.entity_schema = ranking_entity_schema(spec.ks)
+
+    def add_log_loss(self, which, score, label):
+        """--evaluators=LOGISTIC_LOSS: the scores of a batch (device) -> `which`'s log-loss accumulator. Nothing without it."""
+        if self.spec is None or not self.spec.log_loss:
+            return
+        if which not in self.ll:
+            self.ll[which] = LogLossEvaluator(self.solver)
+        self.ll[which].add(score, label)
 
     def _evaluator(self, which):
         if which not in self.ev:
@@ -323,7 +458,23 @@ class StageMetrics:
         """The scores of a packed batch (device) -> added to `which`'s accumulator; -> per-entity results on the host."""
         ev = self._evaluator(which)
         ev.add(logit, packed._raw_dev["y"])
+        self.add_log_loss(which, logit, packed._raw_dev["y"])
+        if self.spec is not None and self.spec.ranking:
+            if self.ranking is None:
+                self.ranking = RankingEvaluator(self.solver, self.ks)
+            return self.ranking.to_host(self.ranking.entities(packed, logit))
         return ev.to_host(ev.entities(packed, logit))
+
+    def _collect(self, which, host, e0, e1):
+        """The records just written -> the values the aggregates of `which` are taken over."""
+        r = self.records.setdefault(which, dict({"nan": 0, "auc": []}, **{precision_key(k): [] for k in self.spec.ks}))
+        sl = slice(e0, e1)
+        r["nan"] += int(np.count_nonzero(host["n_nan"][sl] > 0))
+        both = (host["n_pos"][sl] > 0) & (host["n_neg"][sl] > 0) & (host["n_nan"][sl] == 0)
+        r["auc"].extend(host["auc"][sl][both].tolist())
+        some = (host["n"][sl] >= 1) & (host["n_nan"][sl] == 0)
+        for k in self.spec.ks:
+            r[precision_key(k)].extend(host[precision_key(k)][sl][some].tolist())
 
     def write_entities(self, which, output_file, entity_ids, host, e0=0, e1=None):
         from .io import avro
@@ -336,9 +487,28 @@ class StageMetrics:
         # a record per entity from the evaluator's schema: a long, a double, or a double that is null when it is NaN
         as_type = {"long": int, "double": float}
         nullable = lambda x: None if x != x else float(x)
-        fields = [(f["name"], as_type[f["type"]] if isinstance(f["type"], str) else nullable) for f in self.evaluator.ENTITY_SCHEMA["fields"][1:]]
+        fields = [(f["name"], as_type[f["type"]] if isinstance(f["type"], str) else nullable) for f in self.entity_schema["fields"][1:]]
         recs = [dict({"entityId": str(entity_ids[i])}, **{k: conv(host[k][e0 + i]) for k, conv in fields}) for i in range(e1 - e0)]
-        avro.write_file(os.path.join(d, name), self.evaluator.ENTITY_SCHEMA, recs)
+        avro.write_file(os.path.join(d, name), self.entity_schema, recs)
+        if self.spec is not None and self.spec.ranking:
+            self._collect(which, host, e0, e1)
+
+    def _aggregates(self, which) -> dict:
+        """The block's keys of --evaluators for `which` (in a fixed order: the log loss, the mean AUC, precision@k as listed)."""
+        import math
+        out = {}
+        if self.spec.log_loss and which in self.ll:
+            r = self.ll[which].finish()
+            out[LOGISTIC_LOSS], out["ll"] = _json_number(r[LOGISTIC_LOSS]), r["ll"]
+        if self.spec.ranking:
+            r = self.records.get(which, {"nan": 0, "auc": []})
+            mean = lambda v: None if r["nan"] > 0 or not v else math.fsum(v) / len(v)
+            if self.spec.auc:
+                out[f"auc:{self.spec.entity}"], out[f"auc:{self.spec.entity}_records"] = mean(r["auc"]), len(r["auc"])
+            for k in self.spec.ks:
+                v = r.get(precision_key(k), [])
+                out[f"precision@{k}:{self.spec.entity}"], out[f"precision@{k}:{self.spec.entity}_records"] = mean(v), len(v)
+        return out
 
     def write_summary(self):
         if not self.ev:
@@ -347,6 +517,8 @@ class StageMetrics:
         for which, ev in self.ev.items():
             r = ev.finish()
             blocks[which] = {k: _json_number(r[k]) for k in (self.metric,) + self.evaluator.SUMMARY_KEYS}
+            if self.spec is not None:
+                blocks[which].update(self._aggregates(which))
         top = VALIDATION if VALIDATION in blocks else TRAINING
         out = dict(blocks[top], data=top, **blocks)
         os.makedirs(self.out_dir, exist_ok=True)

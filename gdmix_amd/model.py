@@ -21,7 +21,7 @@ from .io import avro, native_reader
 from .io.features import get_feature_map, read_feature_list
 from .io.grouped_reader import read_grouped_partition
 from .io.metadata import DatasetMetadata, read_json_file
-from .params import REParams
+from .params import REParams, check_evaluators_model_type
 from .batch import WireRawBatch, check_count_labels
 from .solver import REDeviceSolver, SolverOptions, VARIANCE_MODES, host_array
 
@@ -483,6 +483,8 @@ class RandomEffectLRLBFGSModel:
         self.linear = self.model_type == constants.LINEAR_REGRESSION
         self.poisson = self.model_type == constants.POISSON_REGRESSION
         self.loss = "poisson" if self.poisson else ("squared" if self.linear else "logistic")
+        self.evaluator_spec = self.model_params.evaluator_spec()      # --evaluators (params.EvaluatorSpec), or None
+        check_evaluators_model_type(self.evaluator_spec, self.model_type)
         self.checkpoint_path = os.path.join(self.model_params.output_model_dir)
         self.metadata_file = self.model_params.metadata_file
         self.feature_bag_name = self.model_params.feature_bag
@@ -518,7 +520,7 @@ class RandomEffectLRLBFGSModel:
             return None
         if self._stage_metrics is None:
             from . import metrics
-            self._stage_metrics = metrics.StageMetrics(self._get_solver(), out_dir, metrics.metric_of_loss(self.loss))
+            self._stage_metrics = metrics.StageMetrics(self._get_solver(), out_dir, metrics.metric_of_loss(self.loss), self.evaluator_spec)
         return self._stage_metrics
 
     def _metric_data(self, input_path):

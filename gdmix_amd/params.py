@@ -154,6 +154,88 @@ def parse_l2_grid(text):
     return tuple(out)
 
 
+@dataclass(frozen=True)
+class EvaluatorSpec:
+    """What --evaluators asks for: the logistic loss, the mean per-entity AUC, precision@k for these k (in the order given)."""
+    log_loss: bool = False
+    auc: bool = False
+    ks: tuple = ()
+    entity: Optional[str] = None
+
+    @property
+    def ranking(self):
+        return self.auc or len(self.ks) > 0
+
+
+MAX_PRECISION_KS = 4      # values of K in one list: what one device call ranks (include/gdmix_re.h, "ranking evaluation")
+
+
+def parse_evaluators(text, entity, fixed_effect=False):
+    """--evaluators=LIST (Photon-ML's evaluator names, any case, comma-separated): LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, with <id>
+    the stage's --partition_entity (`entity`), K an integer >= 1, at most four distinct K, no item twice. A fixed-effect stage takes
+    LOGISTIC_LOSS only. -> EvaluatorSpec; ValueError for anything else."""
+    log_loss, auc, ks, seen = False, False, [], set()
+    for raw in str(text).split(","):
+        item = raw.strip()
+        if not item:
+            raise ValueError(f"--evaluators={text!r}: an empty item")
+        name, colon, ident = item.partition(":")
+        kind = name.strip().upper()
+        if kind.startswith("PRECISION@"):
+            k_text = kind[len("PRECISION@"):]
+            if not k_text.isdigit() or int(k_text) < 1:      # (a sign, a point or nothing: not an integer >= 1)
+                raise ValueError(f"--evaluators={text!r}: {item!r}: K is an integer >= 1")
+            k = int(k_text)
+            if k >= 1 << 31:
+                raise ValueError(f"--evaluators={text!r}: {item!r}: K is below 2^31")
+            key = ("PRECISION", k)
+        elif kind in ("AUC", "LOGISTIC_LOSS"):
+            key = (kind,)
+        else:
+            raise ValueError(f"--evaluators={text!r}: {item!r} is none of LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>")
+        if key[0] == "LOGISTIC_LOSS":
+            if colon:
+                raise ValueError(f"--evaluators={text!r}: {item!r}: LOGISTIC_LOSS is taken over all samples and names no entity")
+        else:
+            if fixed_effect:
+                raise ValueError(f"--evaluators={text!r}: {item!r}: a fixed effect has no entities (it takes LOGISTIC_LOSS only)")
+            if not colon or not ident.strip():
+                raise ValueError(f"--evaluators={text!r}: {item!r} names no entity: {name.strip()}:<id>, with <id> the stage's --partition_entity")
+            if entity is None or ident.strip() != entity:
+                raise ValueError(f"--evaluators={text!r}: {item!r} groups by {ident.strip()!r}; this stage's entity is --partition_entity={entity}")
+        if key in seen:
+            raise ValueError(f"--evaluators={text!r}: {item!r} is listed twice")
+        seen.add(key)
+        if key[0] == "LOGISTIC_LOSS":
+            log_loss = True
+        elif key[0] == "AUC":
+            auc = True
+        else:
+            ks.append(key[1])
+            if len(ks) > MAX_PRECISION_KS:
+                raise ValueError(f"--evaluators={text!r}: more than {MAX_PRECISION_KS} distinct K")
+    return EvaluatorSpec(log_loss, auc, tuple(ks), None if fixed_effect else entity)
+
+
+def check_evaluators(p, entity, fixed_effect=False):
+    """--evaluators of a stage's parameters: the list itself, and the flags it needs or does not run with. -> EvaluatorSpec, or None
+    without the flag."""
+    if p.evaluators is None:
+        return None
+    spec = parse_evaluators(p.evaluators, entity, fixed_effect)
+    if not p.metric_output_dir:
+        raise ValueError("--evaluators needs --metric_output_dir: the values go into its evalSummary.json")
+    if p.l2_reg_weights is not None:
+        raise ValueError("--evaluators does not run with --l2_reg_weights: choosing a sweep's winner by these metrics is not implemented")
+    return spec
+
+
+def check_evaluators_model_type(spec, model_type):
+    """--evaluators rank and weigh a probability: the stage is a logistic regression."""
+    if spec is not None and model_type != constants.LOGISTIC_REGRESSION:
+        raise ValueError(f"--evaluators needs --model_type={constants.LOGISTIC_REGRESSION}: this stage is a {model_type}")
+
+
 class _ArgvMixin:
     @classmethod
     def __from_argv__(cls, argv, error_on_unknown=False):
@@ -275,6 +357,11 @@ class REParams(LRParams):
     optimizer: str = "LBFGS"
     # ... and so is --coefficient_constraints: box constraints for per-entity models are a follow-up.
     coefficient_constraints: Optional[str] = None
+    # not in the reference (Photon-ML's evaluator names): LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, comma-separated, any case, <id> this
+    # stage's partition_entity. The stage's evalSummary.json gains the logistic loss and the means of the per-entity AUC and precision@K,
+    # its perEntity records precision_at_K (include/gdmix_re.h, "ranking evaluation"; metrics.py). Needs metric_output_dir and
+    # --model_type=logistic_regression; does not run with l2_reg_weights. --action=inference honours it when the data has labels.
+    evaluators: Optional[str] = None
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -284,8 +371,13 @@ class REParams(LRParams):
         """The value of --feature_normalization ("none" without the flag)."""
         return "none" if self.feature_normalization is None else self.feature_normalization
 
+    def evaluator_spec(self):
+        """What --evaluators asks for (EvaluatorSpec), or None without the flag."""
+        return check_evaluators(self, self.partition_entity)
+
     def __post_init__(self):
         self.l2_grid()      # a bad list is an error at parse time
+        self.evaluator_spec()
         if self.coefficient_constraints is not None:
             raise ValueError(f"--coefficient_constraints={self.coefficient_constraints}: the random effect has no box constraints (the flag belongs to the fixed-effect stage)")
         if check_l1_reg_weight(self.l1_reg_weight) != 0.0:

@@ -91,6 +91,13 @@ class _EvalPlTotals(C.Structure):
 
 
 EVAL_PL_STATE_BYTES = 33024
+EVAL_LL_STATE_BYTES = EVAL_PL_STATE_BYTES      # the log loss mirrors the Poisson family: its structs and its state size
+EVAL_LL_TERM_EPS = 1.5e-16                     # GDMIX_RE_EVAL_LL_TERM_EPS: the absolute part of a log-loss term's error
+EVAL_TOPK_MAX = 4                              # values of k in one gdmix_re_eval_topk_entities call
+
+
+class _EvalTopkOut(C.Structure):
+    _fields_ = [("hits_sure", C.c_void_p), ("slots", C.c_void_p), ("tie_pos", C.c_void_p), ("tie_size", C.c_void_p)]
 
 
 class _DownsampleOpts(C.Structure):
@@ -139,6 +146,8 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_eval_workspace_bytes", "gdmix_re_eval_entities", "gdmix_re_set_eval_small_max", "gdmix_re_eval_acc_reset", "gdmix_re_eval_acc_add",
     "gdmix_re_eval_acc_workspace_bytes", "gdmix_re_eval_acc_finish",
     "gdmix_re_eval_pl_entities", "gdmix_re_eval_pl_acc_reset", "gdmix_re_eval_pl_acc_add", "gdmix_re_eval_pl_acc_finish",
+    "gdmix_re_eval_topk_workspace_bytes", "gdmix_re_eval_topk_entities",
+    "gdmix_re_eval_ll_entities", "gdmix_re_eval_ll_acc_reset", "gdmix_re_eval_ll_acc_add", "gdmix_re_eval_ll_acc_finish",
     "gdmix_re_join_features", "gdmix_re_score_models_workspace_bytes", "gdmix_re_score_models",
     "gdmix_re_prior_workspace_bytes", "gdmix_re_prior_apply", "gdmix_re_prior_restore",
     "gdmix_re_feature_extent", "gdmix_re_feature_moments", "gdmix_re_feature_scale_expand",
@@ -266,6 +275,14 @@ def load_library():
     lib.gdmix_re_eval_pl_acc_reset.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.c_void_p]
     lib.gdmix_re_eval_pl_acc_add.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.gdmix_re_eval_pl_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.POINTER(_EvalPlTotals), C.c_void_p]
+    lib.gdmix_re_eval_ll_entities.argtypes = lib.gdmix_re_eval_pl_entities.argtypes
+    lib.gdmix_re_eval_ll_acc_reset.argtypes = lib.gdmix_re_eval_pl_acc_reset.argtypes
+    lib.gdmix_re_eval_ll_acc_add.argtypes = lib.gdmix_re_eval_pl_acc_add.argtypes
+    lib.gdmix_re_eval_ll_acc_finish.argtypes = lib.gdmix_re_eval_pl_acc_finish.argtypes
+    lib.gdmix_re_eval_topk_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.gdmix_re_eval_topk_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_eval_topk_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int,
+                                                C.POINTER(_EvalTopkOut), C.POINTER(_EvalOut), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.gdmix_re_join_features.argtypes = [C.c_void_p, C.POINTER(_Packed), C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gdmix_re_score_models_workspace_bytes.argtypes = [C.c_int64, C.c_int]
     lib.gdmix_re_score_models_workspace_bytes.restype = C.c_size_t
@@ -299,7 +316,7 @@ def load_library():
     lib.gdmix_re_cap_apply.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.POINTER(_CapOpts), C.c_void_p, C.c_size_t, C.POINTER(_DownsampleOut),
                                        C.c_void_p, C.c_void_p]
     lib.gdmix_re_set_cap_small_max.argtypes = [C.c_void_p, C.c_int]
-    if lib.gdmix_re_abi_version() != 26:
+    if lib.gdmix_re_abi_version() != 27:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
     return lib

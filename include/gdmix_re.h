@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GDMIX_RE_ABI_VERSION 26
+#define GDMIX_RE_ABI_VERSION 27
 
 #if defined(__GNUC__)
 #define GDMIX_API __attribute__((visibility("default")))
@@ -414,7 +414,8 @@ GDMIX_API const char* gdmix_re_class_kernel_name(int c);
  * The device returns the INTEGERS and the fp64 SSE; the global division is the caller's, from exact integers. Per entity the device also
  * writes auc[e] = (double)twoU / (2.0 * (double)n_pos * (double)n_neg), one division of exactly converted integers: exact (correctly
  * rounded) for entities below 2^26 samples — a caller redoes the division for larger ones.
- * Out of scope: sample weights in the metric; metrics other than AUC and MSE; combining the accumulators of several workers (each worker
+ * Out of scope: sample weights in the metric; AUPR and RMSE (the Poisson loss, precision@k and the logistic loss have sections of their own
+ * below); combining the accumulators of several workers (each worker
  * finishes its own; from the counts a caller can combine MSE exactly and AUC not at all). */
 typedef struct {          /* device pointers, [E] each; any may be NULL */
   uint64_t* two_u;
@@ -500,6 +501,68 @@ typedef struct {
 GDMIX_API int gdmix_re_eval_pl_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, void* stream);
 GDMIX_API int gdmix_re_eval_pl_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_pl_acc* acc, const float* score, const float* label, int64_t N, void* stream);
 GDMIX_API int gdmix_re_eval_pl_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_pl_acc* acc, gdmix_re_eval_pl_totals* host_out, void* stream);
+
+/* ---- (ABI 27) ranking evaluation: per-entity precision@k as exact integers, and the logistic loss of a scored set -----------------------
+ * What Photon-ML's multi-evaluators (AUC:<id>, PRECISION@K:<id>) and its LOGISTIC_LOSS evaluator report; the reference's Evaluator has
+ * neither. csrc/re_evaluate.hip (precision@k), csrc/re_evaluate_poisson.hip (the logistic loss, the Poisson unit's second term).
+ *
+ * Definitions, per entity over its VALID samples
+ *   valid       a sample whose score is not NaN. Label positive <=> label > 0.5f. Scores compare by the key of "evaluation" above: -0 equals
+ *               +0, infinities order as usual.
+ *   counts      n = n_pos + n_neg valid samples, an integer k >= 1.
+ *               n <= k:  hits_sure = n_pos, slots = tie_pos = tie_size = 0.
+ *               n > k:   c = the k-th largest score; `above` = the samples with score > c (a < k of them), `tie` = those with score == c
+ *                        (tie_size >= k - a >= 1); hits_sure = positives in `above`, slots = k - a, tie_pos = positives in `tie`.
+ *   H           expected hits = hits_sure + slots * tie_pos / tie_size (the last term 0 when tie_size == 0): the expectation of "sort
+ *               descending, take k, count the positives" under a uniformly random order inside tie groups — for precision what "ties at
+ *               half weight" is for AUC.
+ *   precision@k H / k. The denominator is k also for an entity of fewer than k samples.
+ * The device returns the four INTEGERS; the division is the caller's (gdmix_amd/metrics.py: precision_from_counts, correctly rounded).
+ * Aggregates over a data set (the mean of per-entity AUC or precision@k) are the caller's too: an exact sum of the per-entity values.
+ *
+ * One call does ONE sort. Entities of at most 64 samples are ranked in registers, four per wavefront as in gdmix_re_eval_entities (a lane
+ * counts the keys below and not above its own through LDS; the integers are sums of flags over the entity's lanes); larger ones go through
+ * the (entity, key) radix sort of gdmix_re_eval_entities, then a workgroup per entity finds the cut key at position n - k of the valid part
+ * of its sorted segment, the tie group by binary searches, and counts the positives above it. The two paths give identical integers;
+ * gdmix_re_set_eval_small_max moves the limit for this call too. With auc_out non-NULL the call also fills what gdmix_re_eval_entities
+ * fills, bit for bit (the same integers; sse from the same tree), so a stage that wants both pays one pass.
+ *   ks          host, nk of them, 1 <= nk <= 4, distinct, each >= 1: anything else is GDMIX_RE_EINVAL (checked before anything is launched,
+ *               also for an empty batch).
+ *   out         device, [nk][E] each, k-major (the values of ks[j] at [j * E, (j + 1) * E)); any pointer may be NULL.
+ * Limits, GDMIX_RE_ERANGE / GDMIX_RE_ENOMEM, the workspace and the single stream synchronisation are those of gdmix_re_eval_entities
+ * (gdmix_re_eval_topk_workspace_bytes equals gdmix_re_eval_workspace_bytes). */
+typedef struct {           /* device, [nk][E] each, k-major; any may be NULL */
+  int32_t* hits_sure;
+  int32_t* slots;
+  int32_t* tie_pos;
+  int32_t* tie_size;
+} gdmix_re_eval_topk_out;
+GDMIX_API size_t gdmix_re_eval_topk_workspace_bytes(int64_t E, int64_t N);
+GDMIX_API int gdmix_re_eval_topk_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                          const int32_t* ks /* host */, int nk /* 1..4, distinct, each >= 1 */, const gdmix_re_eval_topk_out* out,
+                                          const gdmix_re_eval_out* auc_out /* may be NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The logistic loss (log loss) of a scored set: LL = sum over valid samples of ce(s, y),
+ *   ce(s, y) = max(s, 0) - s [y > 0.5] + log(1 + exp(-|s|)), in fp64 from the widened fp32 score; logistic_loss = LL / n is the caller's.
+ * max(s, 0) - s [y > 0.5] is formed as max(-s, 0) for a positive and max(s, 0) for a negative (the same number, no rounding, no inf - inf);
+ * exp and log are the library's own (csrc/re_device.hpp: exp_neg, log_1_2), and u = 1 + exp(-|s|) is rounded before the logarithm, as in the
+ * solve kernels. That rounding is an ABSOLUTE error of the term, not a relative one. Measured against long double over every exponent of
+ * fp32 scores and both labels (tools/logloss_check.c, 2^25 scores per label): |ce - exact| <= 2^-53 ce + eps with
+ *   eps = GDMIX_RE_EVAL_LL_TERM_EPS,
+ * so with the trees of csrc/re_eval_sum.hpp (the Poisson loss's shape, trees, TwoSum accumulator, NaN handling and limits; the same bits
+ * from run to run; never a floating-point atomic):  |LL - exact| <= 2.5e-13 * sum_i ce_i + n * eps  (2.5e-13 covers the < 2 211 roundings of
+ * the longest chain of additions and the one of the term).
+ * The entry points mirror the gdmix_re_eval_pl_ family: the same structs (the field `pl` holds LL) and the same state size. */
+#define GDMIX_RE_EVAL_LL_TERM_EPS 1.5e-16   /* measured 1.413e-16 (at s = 0.5575137) */
+#define GDMIX_RE_EVAL_LL_STATE_BYTES GDMIX_RE_EVAL_PL_STATE_BYTES
+typedef gdmix_re_eval_pl_out    gdmix_re_eval_ll_out;
+typedef gdmix_re_eval_pl_totals gdmix_re_eval_ll_totals;
+typedef gdmix_re_eval_pl_acc    gdmix_re_eval_ll_acc;
+GDMIX_API int gdmix_re_eval_ll_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                        const gdmix_re_eval_ll_out* out, void* stream);
+GDMIX_API int gdmix_re_eval_ll_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_ll_acc* acc, void* stream);
+GDMIX_API int gdmix_re_eval_ll_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_ll_acc* acc, const float* score, const float* label, int64_t N, void* stream);
+GDMIX_API int gdmix_re_eval_ll_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_ll_acc* acc, gdmix_re_eval_ll_totals* host_out, void* stream);
 
 /* ---- (ABI 14) sweep: K models trained on one batch score another batch in one pass over its non-zeros ----------------------------
  * A stage that sweeps l2_reg_weight (gdmix_amd/sweep.py) solves a training partition K times and scores the validation partition under

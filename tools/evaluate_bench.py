@@ -6,6 +6,12 @@ gdmix_re_score on the same batch and next to the numpy reference on the host.
 Every figure is the median (and the range) of `reps` calls after three warm-up calls, a host clock around a call that ends in a device
 synchronise: (a) gdmix_re_eval_entities by default routing and with every entity forced through the sort path, (b) accumulate + finish of
 the same samples (as one batch, and as sixteen). Bytes are the algorithm's: 8 B per sample read, 40 B per entity written.
+
+    PYTHONPATH=. python tools/evaluate_bench.py ranking [reps] > profiles/eval_ranking.txt
+
+times what the ranking evaluation adds (include/gdmix_re.h, "ranking evaluation"): on a C2-shaped batch (1 M entities x 16 samples) and on a
+MovieLens-20M per-movie-shaped batch, gdmix_re_eval_entities alone (the baseline) next to gdmix_re_eval_topk_entities with auc_out and four
+values of k, the same way: one process, one session, median and range.
 """
 import os
 import statistics
@@ -20,7 +26,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 from gdmix_amd import metrics, synthetic  # noqa: E402
 from gdmix_amd.solver import REDeviceSolver  # noqa: E402
 
-E = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
+RANKING = sys.argv[1:2] == ["ranking"]
+E = int(sys.argv[1]) if len(sys.argv) > 1 and not RANKING else 1_000_000
 REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 12
 
 
@@ -42,6 +49,41 @@ def line(what, t, nbytes=None):
     extra = f", {nbytes / med / 1e6:.0f} GB/s of algorithmic bytes" if nbytes else ""
     print(f"{what:<58s} {med:9.3f} ms  (min {lo:.3f}, max {hi:.3f}, {REPS} calls){extra}", flush=True)
 
+
+def ranking_bench():
+    """Both calls on both shapes; the scores are standard normal, rounded to 1/64 so that ties occur, the labels drawn from their sigmoid."""
+    s = REDeviceSolver(0)
+    plain, ks = metrics.DeviceEvaluator(s), (1, 5, 10, 100)
+    ranker = metrics.RankingEvaluator(s, ks)
+    shapes = (("C2-shaped: 1 M entities x 16 samples", np.arange(0, 16 * 1_000_000 + 1, 16, dtype=np.int64)),
+              ("MovieLens-20M per movie", np.asarray(synthetic.make_movielens_20m(kind="per_movie", seed=200).ent_row_ptr, np.int64)))
+    gen = torch.Generator(device=s.device).manual_seed(5)
+    for what, rp in shapes:
+        n = np.diff(rp)
+        N = int(rp[-1])
+        score = (torch.randn(N, device=s.device, generator=gen) * 64.0).round() / 64.0
+        label = (torch.rand(N, device=s.device, generator=gen) < torch.sigmoid(score)).to(torch.float32)
+        rp_dev = torch.from_numpy(rp).to(s.device)
+        print(f"{what}: {n.size} entities, {N} samples (largest entity {int(n.max())}, {int((n > 64).sum())} entities / {int(n[n > 64].sum())} samples on the sort path)")
+        base = timed(lambda: plain.entities(rp_dev, score, label))
+        both = timed(lambda: ranker.entities(rp_dev, score, label))
+        only = timed(lambda: ranker.entities(rp_dev, score, label, with_auc=False))
+        line("  gdmix_re_eval_entities (baseline)", base)
+        line(f"  gdmix_re_eval_topk_entities, auc_out and k = {list(ks)}", both)
+        line("  gdmix_re_eval_topk_entities without auc_out", only)
+        print(f"  combined / baseline = {both[0] / base[0]:.3f} (the baseline run twice: 2.000)", flush=True)
+        a, r = plain.entities(rp_dev, score, label), ranker.entities(rp_dev, score, label)
+        assert all(torch.equal(a[k].view(torch.uint8), r[k].view(torch.uint8)) for k in a), "auc_out differs from gdmix_re_eval_entities"
+        h = ranker.to_host(r)
+        some = h["n"] >= 1
+        print("  auc_out: the baseline's bits; mean precision@k over the entities with a sample: " +
+              ", ".join(f"@{k} {float(np.mean(h[metrics.precision_key(k)][some])):.4f}" for k in ks))
+    s.close()
+
+
+if RANKING:
+    ranking_bench()
+    sys.exit(0)
 
 b = synthetic.make_batch(E, 16, 4, 1024, seed=synthetic.C2_SEED, with_uid=False)
 s = REDeviceSolver(0)
