@@ -264,7 +264,9 @@ __attribute__((amdgpu_waves_per_eu(EPL == 2 ? GDMIX_QUAD_WAVES_EPL2 : (EPL >= 3 
     colc[s] = live ? (unsigned)k0 | ((unsigned)(k1 - k0) << 16) : 0u;
   }
   SolveStats st;
-  quad_solve<G, EPL, (NCAP > G), LOSS, grp_reg_pairs(EPL)>(L, o, gl, n, p, ic, valid, rowc, colc, V, X, st);
+  // (an entity without samples runs in the first group class only: quad_eval, EMPTY)
+  constexpr bool FIRST_CLASS = G == kClasses[0].lanes && EPL == kClasses[0].epl && NCAP == kClasses[0].ncap && ZCAP == kClasses[0].zcap;
+  quad_solve<G, EPL, (NCAP > G), LOSS, grp_reg_pairs(EPL), FIRST_CLASS>(L, o, gl, n, p, ic, valid, rowc, colc, V, X, st);
   if (!valid) return;
 
 #pragma unroll

@@ -308,6 +308,11 @@ static_assert(sizeof(LineSearch) <= 128, "LineSearch must fit its LDS slot");
 
 enum { SC_FOLD = 0, SC_GDOLD = 1, SC_THETA = 2, SC_MOVED = 3 };
 
+// Which kernels keep the bounds test j < p on every coefficient slot of the trip (quad_eval, "dead slots"): those of several wavefronts
+// per entity with four slots per lane. Their register allocation is the tightest of all (60 to 90 spilled registers) and comes out 5 to
+// 17 registers worse without the masked regions; they are the code they were. Every other kernel runs the trip without the tests.
+constexpr bool grp_slot_tests(int g, int epl) { return g > WAVE && epl >= 4; }
+
 // (The per-entity rho, alpha and scalars in the lanes of a register pair instead of LDS: slower, rejected in round 6: profiles/r06_c2_ab.txt.)
 
 // Is `v` true in any lane of the entity's group? G <= 64: from the wavefront's ballot (all lanes of a group are active
@@ -403,20 +408,30 @@ __device__ __forceinline__ void gather_dot1_cols(const int2* csc, const unsigned
 // f and g at xt. rowc: packed (start | len << 16) of the lane's first sample; colc[s]: same for the
 // lane's coefficient slots (len = 0 for the intercept / unused slots).
 // LOSS: the loss code (re_device.hpp, loss_terms).
-template <int G, int EPL, bool LONG_COLS = true, int LOSS = LOSS_LOGISTIC>
+// DEAD SLOTS (docs/kernels.md, "Dead slots"): a slot j = gl + G s >= p has no column (colc[s] == 0), starts at x = +0.0 and has zeros
+// in xs, xo and go (quad_solve writes them once per entity), so the per-slot loops here and in quad_solve's trip do not test j < p
+// (`live`; what is left of the tests and why is said where it stands: two sites, and the kernels of grp_slot_tests). A dead slot's gradient
+// is inv_n * (0 + l2 * 0) = +0.0, its d, s and y are zeros of either sign, it adds exact zeros to every sum and |0| to the maximum, and
+// x stays +0.0: the bits the selects gave. That holds while inv_n, l2 and the residual of sample 0 (what an ended column of the fused
+// gathers multiplies by 0) are finite; the two cases where they are not on finite input are kept apart below.
+// EMPTY: the class can hold an entity without samples (n == 0: inv_n = inf). Such an entity has no column either (p = ic <= 1) and fits
+// every cap, so the first-fit rule sends it to the FIRST group class and to no other: only that class's kernel carries the guard.
+template <int G, int EPL, bool LONG_COLS = true, int LOSS = LOSS_LOGISTIC, bool EMPTY = true>
 __device__ __forceinline__ double quad_eval(const QuadLds& L, const SolveParams& o, int gl, int n, int p, int ic,
                                             unsigned rowc, const unsigned (&colc)[EPL], const double (&xt)[EPL],
                                             double (&g)[EPL], XWave& X, bool first, bool& counted) {
   double* const xs = L.xs();
   double* const rs = L.rs();
+  constexpr bool TESTS = grp_slot_tests(G, EPL);
+  const auto live = [&](int j) { return !TESTS || j < p; };
   // xs still holds the point of the previous evaluation: scipy's ScalarFunction serves an equal point from its cache without
   // counting it (nfev is its funcalls; a step too small to move x, _differentiable_functions.py)
   bool mv = first;
 #pragma unroll
   for (int s = 0; s < EPL; ++s) {
     const int j = gl + G * s;
-    if (j < p) {
-      mv = mv || (xs[j] != xt[s]);
+    if (live(j)) {
+      mv = mv || (xs[j] != xt[s]);   // (a dead slot: 0 != 0)
       xs[j] = xt[s];
     }
   }
@@ -452,7 +467,7 @@ __device__ __forceinline__ double quad_eval(const QuadLds& L, const SolveParams&
 #pragma unroll
   for (int s = 0; s < EPL; ++s) {
     const int j = gl + G * s;
-    if (j >= first_reg && j < p) sq += xt[s] * xt[s];
+    if (j >= first_reg && live(j)) sq += xt[s] * xt[s];   // (j < first_reg: slot 0 of lane 0 alone)
   }
   // cost.sum() and the regulariser are summed separately and added once, as the reference writes it
   // (binary_logistic_regression.py:105-108): spreading (l2/2) x_j^2 over the lanes' loss partials rounds differently, which
@@ -461,22 +476,32 @@ __device__ __forceinline__ double quad_eval(const QuadLds& L, const SolveParams&
   part += 0.5 * o.l2 * sq;
   grp_fence<G>();
   const double inv_n = 1.0 / (double)n;
+  // An entity without samples (the pack takes one) has inv_n = inf, and inf * 0 is no zero: its dead slots (every slot s >= 1, and slot 0
+  // of every lane but an intercept's) take the factor 0 instead, two selects per evaluation outside the slot loops. For n > 0, and in
+  // every kernel but the first class's, both are inv_n.
+  const double inv_hi = (!EMPTY || n > 0) ? inv_n : 0.0;
+  const double inv_lo = (!EMPTY || gl < p) ? inv_n : inv_hi;
   if (EPL <= 3 || LONG_COLS) {
     double acc[EPL];
-    unsigned cc[EPL];
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
       const int j = gl + G * s;
       acc[s] = (ic && j == 0) ? rpart : 0.0;
-      cc[s] = (j < p) ? colc[s] : 0u;
     }
-    if (EPL <= 3) gather_dot2_cols<EPL>(L.csc(), cc, rs, acc);
-    else gather_dot1_cols<EPL>(L.csc(), cc, rs, acc);
+    if (EPL <= 3) gather_dot2_cols<EPL>(L.csc(), colc, rs, acc);   // (a dead slot's colc is 0: an ended column from the start)
+    else gather_dot1_cols<EPL>(L.csc(), colc, rs, acc);
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
       const int j = gl + G * s;
       const double reg = (j < first_reg) ? 0.0 : o.l2 * xt[s];
-      g[s] = (j < p) ? inv_n * (acc[s] + reg) : 0.0;
+      double gj = (s == 0 ? inv_lo : inv_hi) * (acc[s] + reg);
+      // The product is rounded HERE, as it was when a select stood between it and its uses: left open, the compiler contracts it into
+      // the subtraction g - g_old of quad_solve (one fused multiply-add, one rounding fewer) and a trip in twenty changes its last bit.
+      asm("" : "+v"(gj));
+      // exp(z) of sample 0 overflows to inf at a trial point too far out (the line search comes back from f = inf), and an ended
+      // column has added 0 * inf: the Poisson kernels keep the select
+      if constexpr (LOSS == LOSS_POISSON || TESTS) g[s] = (j < p) ? gj : 0.0;
+      else g[s] = gj;
     }
     return inv_n * part;
   }
@@ -484,11 +509,13 @@ __device__ __forceinline__ double quad_eval(const QuadLds& L, const SolveParams&
   for (int s = 0; s < EPL; ++s) {
     const int j = gl + G * s;
     double gj = 0.0;
+    // (a dead slot's loop takes no trip and its gj is +0.0 either way, but this path is the EPL = 4 kernels' alone, and they spill a
+    // register more without the region)
     if (j < p) {
       double acc = (ic && j == 0) ? rpart : 0.0;
       acc = gather_dot(L.csc() + (colc[s] & 0xffffu), (int)(colc[s] >> 16), rs, acc);
       const double reg = (j < first_reg) ? 0.0 : o.l2 * xt[s];
-      gj = inv_n * (acc + reg);
+      gj = (s == 0 ? inv_lo : inv_hi) * (acc + reg);
     }
     g[s] = gj;
   }
@@ -509,7 +536,7 @@ struct QuadState {
 // into a per-lane ring of M_REG - KR pairs (a private array indexed by a per-row slot, i.e. scratch memory). A push moves no old pair;
 // the ring is read only by the two-loop steps of rows whose history is longer than KR. Same pairs, same order of the steps, same
 // arithmetic: where a pair lives changes no bit. KR == M_REG is the code as it was (no ring, every `if constexpr` below folds away).
-template <int G, int EPL, bool LONG_COLS = true, int LOSS = LOSS_LOGISTIC, int KR = M_REG>
+template <int G, int EPL, bool LONG_COLS = true, int LOSS = LOSS_LOGISTIC, int KR = M_REG, bool EMPTY = true>
 __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& o, int gl, int n, int p, int ic,
                                            bool valid, unsigned rowc, const unsigned (&colc)[EPL], QuadState<EPL>& V,
                                            XWave& X, SolveStats& out) {
@@ -529,6 +556,8 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
   double* const scal = L.scal();
   double* const xo = L.xo();
   double* const go = L.go();
+  constexpr bool TESTS = grp_slot_tests(G, EPL);
+  const auto live = [&](int j) { return !TESTS || j < p; };
   const int m = o.m;
   int cnt = 0;
   int nit = 0, nfev = 0, ifun = 0;
@@ -538,10 +567,14 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
   double f = 0.0, gd = 0.0, rr = 0.0, stp = 0.0, sbgnrm = 0.0;
   if (valid) {
     scal[SC_FOLD] = 0.0; scal[SC_GDOLD] = 0.0; scal[SC_THETA] = 1.0;
+    // every slot of the row's G * EPL, the dead ones (j >= p) included: what lets the trip below touch xs, xo and go without a bounds
+    // test (quad_eval, "dead slots"). The lanes' slots tile [0, G * EPL), the extent of the three arrays (quad_layout).
+    double* const xs = L.xs();
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
       const int j = gl + G * s;
-      if (j < p) { xo[j] = 0.0; go[j] = 0.0; }
+      if (!TESTS) xs[j] = 0.0;
+      if (live(j)) { xo[j] = 0.0; go[j] = 0.0; }
     }
   }
   while (__any(status < 0)) {
@@ -549,13 +582,15 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
     if (status < 0) {
       // ---- f, g at the trial point; g'd, y'y and max|g| in one reduction pass ------------------------
       bool counted;
-      f = quad_eval<G, EPL, LONG_COLS, LOSS>(L, o, gl, n, p, ic, rowc, colc, V.x, V.g, X, first, counted);
+      f = quad_eval<G, EPL, LONG_COLS, LOSS, EMPTY>(L, o, gl, n, p, ic, rowc, colc, V.x, V.g, X, first, counted);
       nfev += counted ? 1 : 0;
       {
         double a = 0.0, b = 0.0, c = 0.0;
 #pragma unroll
         for (int s = 0; s < EPL; ++s) {
           const int j = gl + G * s;
+          // (a bounds test that stays in every kernel: this is the trip's register peak, and EPL unconditional loads in flight together made every
+          // EPL = 4 kernel spill 10 to 25 registers more; the masked loads come one after the other)
           const double gold = (j < p) ? go[j] : 0.0;
           a += V.g[s] * V.d[s];
           const double yj = V.g[s] - gold;
@@ -592,7 +627,7 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
 #pragma unroll
             for (int s = 0; s < EPL; ++s) {
               const int j = gl + G * s;
-              if (j < p) V.x[s] = stp * V.d[s] + xo[j];   // stp == 1: exactly xo + d
+              if (live(j)) V.x[s] = stp * V.d[s] + xo[j];   // stp == 1: exactly xo + d
             }
           } else {
             restart = true;   // iback >= maxls
@@ -637,7 +672,7 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
               for (int s = 0; s < EPL; ++s) {
                 const int j = gl + G * s;
                 S[KR - 1][s] = stp * V.d[s];   // exact for stp == 1
-                Y[KR - 1][s] = V.g[s] - ((j < p) ? go[j] : 0.0);
+                Y[KR - 1][s] = V.g[s] - (live(j) ? go[j] : 0.0);
               }
               rho[M_REG - 1] = 1.0 / dr;
               scal[SC_THETA] = rr / dr;
@@ -653,7 +688,7 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
 #pragma unroll
         for (int s = 0; s < EPL; ++s) {
           const int j = gl + G * s;
-          if (j < p) { V.x[s] = xo[j]; V.g[s] = go[j]; }
+          if (live(j)) { V.x[s] = xo[j]; V.g[s] = go[j]; }
         }
         f = scal[SC_FOLD];
         restart = false;
@@ -750,7 +785,7 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
           const double z = xj + V.d[s];
           const double dj = z - xj;
           V.d[s] = dj;
-          if (j < p) { xo[j] = xj; go[j] = V.g[s]; }
+          if (live(j)) { xo[j] = xj; go[j] = V.g[s]; }
           dd += dj * dj;
           gdp += V.g[s] * dj;
         }
