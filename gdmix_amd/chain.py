@@ -14,7 +14,8 @@ What gdmix-workflow schedules for gdmix-workflow/test/resources/lr-movieLens.yam
 Every stage's predictionScore is the accumulated logit so far (X theta + offset), stored as Avro `float`; the next stage's offset is
 that float. With model_type="linear_regression" the three stages train the squared loss on the ratings themselves (data["rating"], real-valued labels)
 and report the mean squared error of the accumulated score instead of the AUC (the `mse` branch of gdmix-data's Evaluator.scala). Only the first iteration is run, as the reference's workflow does: no per-coordinate score is subtracted
-(OffsetUpdater's dFPerCoordinateScoreOpt = None), though update_offsets takes one.
+(OffsetUpdater's dFPerCoordinateScoreOpt = None), though update_offsets takes one. (Several passes, with the coordinates resident on the
+device instead of in files: run_resident at the end of this file, gdmix_amd/descent.py.)
 
 The stages run through `gdmix_amd.gdmix` exactly as gdmix-workflow would start them (in this process, or as child processes);
 the Spark partition job between them is partitioner.py. Nothing here touches the oracle: tests/chain_oracle.py restates the
@@ -369,3 +370,44 @@ def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper
         prev = stage
     out["total_s"] = time.perf_counter() - t_all
     return out
+
+
+# ---- the same coordinates resident on the device, any number of passes (gdmix_amd/descent.py) ---------------------------------------------
+FEATURE_PREFIX = {"global": "g", "per_user": "m", "per_movie": "u"}      # the feature files the stages of run_chain read
+
+
+def resident_coordinates(data, re_regularize_bias=False, rows=None, vrows=None, l2=1.0):
+    """make_dataset's dict -> the three descent.Coordinate objects over `rows` (default: the training rows), their validation bags over
+    `vrows` (default: the others). re_regularize_bias=False with l2 = 1 are the settings of run_chain's stages (COMMON)."""
+    from . import descent
+    rows = np.flatnonzero(data["train"]) if rows is None else rows
+    vrows = np.flatnonzero(~data["train"]) if vrows is None else vrows
+    ent = {"per_user": data["user"], "per_movie": data["movie"]}
+    out = []
+    for stage in STAGES:
+        dim = data["bags"][stage][3]
+        re = stage in ent
+        out.append(descent.Coordinate(name=stage, bag=bag_rows(data, stage, rows), entity=ent[stage][rows] if re else None, l2=l2,
+                                      regularize_bias=bool(re_regularize_bias) and re, has_intercept=True, validation_bag=bag_rows(data, stage, vrows),
+                                      validation_entity=ent[stage][vrows] if re else None,
+                                      features=[(f"{FEATURE_PREFIX[stage]}{j}", "") for j in range(dim)]))
+    return out
+
+
+def run_resident(data, passes=1, model_type=LOGISTIC, device=0, re_regularize_bias=False, record=False, log=None, solver=None):
+    """global -> per_user -> per_movie, `passes` times, with every coordinate grouped and packed once and resident on the device
+    (descent.CoordinateDescent; no file, no partition job, no upper bounds). passes=1 with the defaults computes what run_chain's three
+    stages compute. -> descent.DescentResult (write it with descent.write_models to serve it through --action=inference)."""
+    from . import descent
+    if model_type not in (LOGISTIC, LINEAR, POISSON):
+        raise ValueError(f"model type {model_type!r}: the chain runs logistic_regression and linear_regression, and poisson_regression on count labels")
+    tr, va = np.flatnonzero(data["train"]), np.flatnonzero(~data["train"])
+    label = labels_of(data, model_type).astype(np.float32)
+    cd = descent.CoordinateDescent(device=device, model_type=model_type, m=10, max_iter=100, tolerance=1.0e-12, threshold=1.0e-4, solver=solver)
+    res = cd.fit(descent.DataSet(label=label[tr], uid=data["uid"][tr]), resident_coordinates(data, re_regularize_bias, tr, va), passes=passes,
+                 validation=descent.DataSet(label=label[va], uid=data["uid"][va]), record=record)
+    if log:
+        for e in res.history:
+            log(f"pass {e['pass'] + 1} {e['coordinate']}: {res.metric.upper()} train {e['train_' + res.metric]:.4f} "
+                f"validation {e['validation_' + res.metric]:.4f} (most iterations {e['max_nit']})")
+    return res

@@ -131,6 +131,18 @@ class _SelectOut(C.Structure):
     _fields_ = [("Z", C.c_int64), ("row_nnz_ptr", C.c_void_p), ("col_global", C.c_void_p), ("val", C.c_void_p)]
 
 
+class _GroupOut(C.Structure):
+    _fields_ = [("row_of", C.c_void_p), ("present", C.c_void_p), ("ent_row_ptr", C.c_void_p), ("row_nnz_ptr", C.c_void_p), ("col_global", C.c_void_p),
+                ("val", C.c_void_p)]
+
+
+class _GroupCounts(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("grouped", C.c_int64), ("grouped_nnz", C.c_int64), ("entities", C.c_int64), ("left_out", C.c_int64)]
+
+
+COMBINE_MAX = 8      # GDMIX_RE_COMBINE_MAX
+
+
 class _EvalTotals(C.Structure):
     _fields_ = [("two_u", C.c_uint64), ("n", C.c_int64), ("n_pos", C.c_int64), ("n_neg", C.c_int64), ("n_nan", C.c_int64), ("sse", C.c_double)]
 
@@ -154,6 +166,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_downsample_workspace_bytes", "gdmix_re_downsample_plan", "gdmix_re_downsample_apply",
     "gdmix_re_select_workspace_bytes", "gdmix_re_select_plan", "gdmix_re_select_apply", "gdmix_re_set_select_small_max",
     "gdmix_re_cap_workspace_bytes", "gdmix_re_cap_plan", "gdmix_re_cap_apply", "gdmix_re_set_cap_small_max",
+    "gdmix_re_group_workspace_bytes", "gdmix_re_group_rows", "gdmix_re_rows_gather_f32", "gdmix_re_rows_scatter_f32", "gdmix_re_offsets_combine",
     "gdmix_re_class_kernel_name", "gdmix_java_string_hash", "gdmix_java_partition_id",
     "gdmix_java_partition_ids_i64")
 
@@ -316,6 +329,14 @@ def load_library():
     lib.gdmix_re_cap_apply.argtypes = [C.c_void_p, C.POINTER(_RawBatch), C.POINTER(_CapOpts), C.c_void_p, C.c_size_t, C.POINTER(_DownsampleOut),
                                        C.c_void_p, C.c_void_p]
     lib.gdmix_re_set_cap_small_max.argtypes = [C.c_void_p, C.c_int]
+    lib.gdmix_re_group_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.gdmix_re_group_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_group_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.POINTER(_GroupOut), C.POINTER(_GroupCounts), C.c_void_p]
+    lib.gdmix_re_rows_gather_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.gdmix_re_rows_scatter_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gdmix_re_offsets_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                             C.c_void_p]
     if lib.gdmix_re_abi_version() != 27:
         raise GdmixReError("libgdmix_re.so ABI version mismatch")
     _lib = lib
@@ -856,6 +877,101 @@ class REDeviceSolver:
                "gdmix_re_cap_apply")
         counts = {k: int(getattr(c_counts, k)) for k in ("entities", "capped", "rows", "kept", "kept_nnz", "largest")}
         return d, counts
+
+    # ---- row grouping (include/gdmix_re.h, "row grouping"; gdmix_amd/descent.py states it in numpy) -------
+    @_serialised
+    def group_rows(self, row_nnz_ptr, col_global, val, entity_index, E):
+        """gdmix_re_group_rows: a sample-major CSR bag (int64 / int64 / float32 device tensors) and entity_index [N] int32 (values in [0, E), or
+        -1 for a row of no entity) -> (a device dict of the shape upload() returns but for y / offset / weight, which the caller gathers with
+        rows_gather — E, N, Z are E', N', Z' — with "row_of" [N'] int32 and "present" [E'] int32 besides; counts: dict(rows, grouped,
+        grouped_nnz, entities, left_out)). The arrays are views of buffers sized by the input."""
+        t = self.torch
+        N, Z, E = int(entity_index.numel()), int(col_global.numel()), int(E)
+        for x, dt, n, what in ((row_nnz_ptr, t.int64, N + 1, "row_nnz_ptr"), (col_global, t.int64, Z, "col_global"), (val, t.float32, Z, "val"),
+                               (entity_index, t.int32, N, "entity_index")):
+            if x.dtype != dt or x.numel() != n or not x.is_cuda or not x.is_contiguous():
+                raise GdmixReError(f"group_rows: {what} must be a contiguous {dt} device array of {n} entries")
+        new = lambda count, dtype: t.empty(max(int(count), 1), dtype=dtype, device=self.device)
+        cap = min(N, E)
+        row_of, present, erp, rnp = new(N, t.int32), new(cap, t.int32), new(cap + 1, t.int64), new(N + 1, t.int64)
+        col, vl = new(Z, t.int64), new(Z, t.float32)
+        nbytes = int(self.lib.gdmix_re_group_workspace_bytes(N, E))
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=self.device)
+        ptr = lambda x: None if x.numel() == 0 else x.data_ptr()
+        c_out = _GroupOut(row_of.data_ptr(), present.data_ptr(), erp.data_ptr(), rnp.data_ptr(), col.data_ptr(), vl.data_ptr())
+        c_counts = _GroupCounts()
+        _check(self.lib.gdmix_re_group_rows(self._h, N, Z, E, row_nnz_ptr.data_ptr(), ptr(col_global), ptr(val), ptr(entity_index), ws.data_ptr(), nbytes,
+                                            C.byref(c_out), C.byref(c_counts), self._stream()), "gdmix_re_group_rows")
+        counts = {k: int(getattr(c_counts, k)) for k in ("rows", "grouped", "grouped_nnz", "entities", "left_out")}
+        n, z, e = counts["grouped"], counts["grouped_nnz"], counts["entities"]
+        d = dict(E=e, N=n, Z=z, ent_row_ptr=erp[:e + 1], row_nnz_ptr=rnp[:n + 1], col_global=col[:z], val=vl[:z], row_of=row_of[:n], present=present[:e])
+        return d, counts
+
+    def _row_map(self, row_of, what):
+        t = self.torch
+        if row_of.dtype != t.int32 or not row_of.is_cuda or not row_of.is_contiguous():
+            raise GdmixReError(f"{what}: row_of must be a contiguous int32 device array")
+        return row_of
+
+    def _f32_rows(self, x, what):
+        t = self.torch
+        if x.dtype != t.float32 or not x.is_cuda or not x.is_contiguous():
+            raise GdmixReError(f"{what}: a contiguous float32 device array is required")
+        return x
+
+    @_serialised
+    def rows_gather(self, src, row_of, out=None):
+        """gdmix_re_rows_gather_f32: out[i] = src[row_of[i]] (float32 device tensors) -> out [len(row_of)]."""
+        t = self.torch
+        src, row_of = self._f32_rows(src, "rows_gather"), self._row_map(row_of, "rows_gather")
+        n = int(row_of.numel())
+        out = t.empty(n, dtype=t.float32, device=self.device) if out is None else self._f32_rows(out, "rows_gather")
+        if out.numel() != n:
+            raise GdmixReError("rows_gather: the output has one entry per entry of row_of")
+        if n:
+            _check(self.lib.gdmix_re_rows_gather_f32(self._h, out.data_ptr(), n, src.data_ptr() if src.numel() else None, int(src.numel()), row_of.data_ptr(),
+                                                     self._stream()), "gdmix_re_rows_gather_f32")
+        return out
+
+    @_serialised
+    def rows_scatter(self, src, row_of, n_dst, out=None, keep_rest=False):
+        """gdmix_re_rows_scatter_f32: out = zeros(n_dst) (keep_rest: `out` as it is); out[row_of[i]] = src[i] (float32 device tensors) -> out."""
+        if keep_rest and out is None:
+            raise GdmixReError("rows_scatter: keep_rest needs the array whose other rows are kept")
+        t = self.torch
+        src, row_of = self._f32_rows(src, "rows_scatter"), self._row_map(row_of, "rows_scatter")
+        if src.numel() != row_of.numel():
+            raise GdmixReError("rows_scatter: one source value per entry of row_of")
+        out = t.empty(int(n_dst), dtype=t.float32, device=self.device) if out is None else self._f32_rows(out, "rows_scatter")
+        if out.numel() != int(n_dst):
+            raise GdmixReError(f"rows_scatter: the output has {int(n_dst)} entries")
+        if out.numel():
+            n = int(src.numel())
+            _check(self.lib.gdmix_re_rows_scatter_f32(self._h, out.data_ptr(), int(n_dst), src.data_ptr() if n else None, n, row_of.data_ptr() if n else None,
+                                                      int(bool(keep_rest)), self._stream()), "gdmix_re_rows_scatter_f32")
+        return out
+
+    @_serialised
+    def offsets_combine(self, n_src, base, parts, skip=-1, row_of=None, out=None):
+        """gdmix_re_offsets_combine: out[i] = base[r] + parts[0][r] + ... (fp32, left to right, parts[skip] left out), r = row_of[i] (row_of
+        None: r = i). base: [n_src] float32 device tensor or None; parts: up to COMBINE_MAX of them -> out [len(row_of) or n_src]."""
+        t = self.torch
+        n_src = int(n_src)
+        if len(parts) > COMBINE_MAX:
+            raise GdmixReError(f"offsets_combine: at most {COMBINE_MAX} parts, not {len(parts)}")
+        for x in list(parts) + ([] if base is None else [base]):
+            if self._f32_rows(x, "offsets_combine").numel() != n_src:
+                raise GdmixReError(f"offsets_combine: base and every part have {n_src} entries")
+        n = n_src if row_of is None else int(self._row_map(row_of, "offsets_combine").numel())
+        out = t.empty(n, dtype=t.float32, device=self.device) if out is None else self._f32_rows(out, "offsets_combine")
+        if out.numel() != n:
+            raise GdmixReError(f"offsets_combine: the output has {n} entries")
+        if n:
+            K = len(parts)
+            ptrs = (C.c_void_p * max(K, 1))(*[p.data_ptr() if n_src else None for p in parts])
+            _check(self.lib.gdmix_re_offsets_combine(self._h, out.data_ptr(), n, None if base is None or not n_src else base.data_ptr(), ptrs, K, int(skip),
+                                                     None if row_of is None else row_of.data_ptr(), n_src, self._stream()), "gdmix_re_offsets_combine")
+        return out
 
     # ---- feature selection between two packs (include/gdmix_re.h, "feature selection"; gdmix_amd/feature_selection.py states it in numpy) ---
     SELECT_SMALL_MAX_DEFAULT = 1024

@@ -897,6 +897,67 @@ GDMIX_API int gdmix_re_cap_apply(gdmix_re_ctx* ctx, const gdmix_re_raw_batch* ra
  * the default, 128, is where counting stops paying on a C5-shaped batch (profiles/active_data.txt). The flags do not depend on it. */
 GDMIX_API int gdmix_re_set_cap_small_max(gdmix_re_ctx* ctx, int small_max);
 
+/* ---- (ABI 27) row grouping: a sample-major data set grouped by entity on the device, and per-row values moved between the two orders ----
+ * What the partition job does between two stages of the coordinate chain, for coordinates that stay in HBM (gdmix_amd/descent.py, which
+ * also states all of this in numpy: group_rows_host, offsets_combine_host). csrc/re_group.hip. The entry points are additions: no struct
+ * and no entry point of ABI 27 changes, so the version number stays.
+ *
+ * Definition. Input: N rows of a CSR bag (row_nnz_ptr [N + 1], col_global [Z], val [Z]) and entity_index [N] int32; a row whose index is
+ * outside [0, E) (-1 by convention) belongs to no entity and is left out. With keep = {i : 0 <= entity_index[i] < E} in ascending order:
+ *     row_of      = keep reordered by a STABLE sort on entity_index: entities ascending, the rows of one entity in input order
+ *                   ( keep[np.argsort(entity_index[keep], kind="stable")] )                                  [N'] grouped position -> source row
+ *     present     = the distinct values of entity_index[keep], ascending                                     [E'] no empty entity
+ *     ent_row_ptr = where each present entity's rows start in row_of, and N'                                  [E' + 1]
+ *     row_nnz_ptr, col_global, val = the rows row_of[0], row_of[1], ... of the bag, one after another        [N' + 1], [Z'], [Z']
+ * Every intermediate is an integer (a stable radix sort of (entity, row) pairs, integer prefix sums): the same bits on every run and for
+ * every launch geometry.
+ *
+ * gdmix_re_group_rows: all array arguments are device pointers. The caller sizes the outputs by their upper bounds (below); the first
+ *   N' / E' / Z' entries are the result, what lies behind them is unspecified. Work is queued on `stream`, which is synchronised once, in
+ *   the middle, to read the counts back (the copy of the non-zeros is launched for exactly Z' positions); it returns with the copy queued.
+ *   The non-zeros move by OUTPUT position, 16 bytes per lane and store (csrc/re_rowsubset.hpp, ds_nnz_kernel). Row pointers that do not
+ *   describe Z non-zeros (a row outside [0, Z], or decreasing) are GDMIX_RE_EINVAL and no non-zero is copied. 2^31 rows or entities or
+ *   more: GDMIX_RE_ERANGE. `workspace`: gdmix_re_group_workspace_bytes(N, E) device bytes (host only; 0 beyond the limits).
+ *
+ * Row values. row_of is the array above (or any int32 map into the source); an entry outside the source's rows reads as 0 / is skipped.
+ *   gdmix_re_rows_gather_f32:   dst[i] = src[row_of[i]]                       i < n_dst            (labels, weights -> grouped order)
+ *   gdmix_re_rows_scatter_f32:  dst[:] = 0 unless keep_rest;  dst[row_of[i]] = src[i]    i < n_src (a coordinate's scores -> sample order;
+ *                                                                                                   rows that were left out keep 0, or, with
+ *                                                                                                   keep_rest != 0, what dst held)
+ *   gdmix_re_offsets_combine:   r = row_of ? row_of[i] : i
+ *                               acc = base ? base[r] : +0.0f
+ *                               for k = 0 .. K - 1, k != skip:  acc = acc + parts[k][r]            (fp32, in this order)
+ *                               dst[i] = acc                                  i < n_dst
+ *     Plain fp32 additions from left to right: no multiply (nothing to contract into an fma) and no reordering. This order is what makes
+ *     the first pass of a resident descent the file chain: there a stage's offset is the previous stage's score, an Avro `float`, and
+ *     float(double(a) + double(b)) is the fp32 sum of two floats. `parts` is a HOST array of K <= GDMIX_RE_COMBINE_MAX device pointers to
+ *     [n_src] floats; skip = -1 (or any value outside [0, K)) leaves nothing out. Stream-ordered, no synchronisation. */
+#define GDMIX_RE_COMBINE_MAX 8
+typedef struct {           /* device arrays the caller allocates, by upper bound                                  */
+  int32_t* row_of;         /* [N]                 the first N' entries                                            */
+  int32_t* present;        /* [min(N, E)]         the first E'                                                    */
+  int64_t* ent_row_ptr;    /* [min(N, E) + 1]     the first E' + 1                                                */
+  int64_t* row_nnz_ptr;    /* [N + 1]             the first N' + 1                                                */
+  int64_t* col_global;     /* [Z]                 the first Z'                                                    */
+  float*   val;            /* [Z]                 the first Z'                                                    */
+} gdmix_re_group_out;
+typedef struct {           /* host */
+  int64_t rows;            /* N of the input                                                                      */
+  int64_t grouped;         /* N'                                                                                  */
+  int64_t grouped_nnz;     /* Z'                                                                                  */
+  int64_t entities;        /* E'                                                                                  */
+  int64_t left_out;        /* N - N'                                                                              */
+} gdmix_re_group_counts;
+GDMIX_API size_t gdmix_re_group_workspace_bytes(int64_t N, int64_t E);
+GDMIX_API int gdmix_re_group_rows(gdmix_re_ctx* ctx, int64_t N, int64_t Z, int64_t E, const int64_t* row_nnz_ptr, const int64_t* col_global, const float* val,
+                                  const int32_t* entity_index, void* workspace, size_t workspace_bytes, const gdmix_re_group_out* out_dev,
+                                  gdmix_re_group_counts* counts, void* stream);
+GDMIX_API int gdmix_re_rows_gather_f32(gdmix_re_ctx* ctx, float* dst, int64_t n_dst, const float* src, int64_t n_src, const int32_t* row_of, void* stream);
+GDMIX_API int gdmix_re_rows_scatter_f32(gdmix_re_ctx* ctx, float* dst, int64_t n_dst, const float* src, int64_t n_src, const int32_t* row_of, int keep_rest,
+                                        void* stream);
+GDMIX_API int gdmix_re_offsets_combine(gdmix_re_ctx* ctx, float* dst, int64_t n_dst, const float* base, const float* const* parts, int K, int skip,
+                                       const int32_t* row_of, int64_t n_src, void* stream);
+
 /* ---- B4: the upstream Spark partitioner's hash, bit-exact (host functions) ------------------------
  * hashCode over UTF-16 code units in wrapping int32; Math.abs(Int.MinValue) stays negative; Scala %
  * keeps the dividend's sign (PartitionUtils.scala:31-37). */
