@@ -222,6 +222,8 @@ __device__ __forceinline__ double sigmoid_full(double z) { return 1.0 / (1.0 + e
 // What the second fma step rounds away of r is kept (rl) and added back in front of r: without it the transcription measures 0.990 ulp on
 // the grid below (and so does exp_neg: its 0.98 is the figure of tools/softplus_check.c's sample), with it 0.847.
 // Accuracy against long double on the 4e6-point grid over [-745, 709.78] (tools/exp_any_check.c): <= 0.85 ulp on normal results.
+// The device's own figure (tests/test_gpu_eval_edges.py: every fp32 exponent, the ends and the rint ties, 1 047 585 fp32 scores on an MI355X):
+// 0.802 ulp on normal results (at z = 0.38366151), 0.73 spacings on subnormal ones; +inf from 709.78271, 0 from -745.13324.
 __device__ __forceinline__ double exp_any(double z) {
   const double a = fmin(fmax(z, -1100.0), 1100.0);
   const double kf = __builtin_rint(a * 1.4426950408889634074);

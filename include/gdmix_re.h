@@ -476,6 +476,10 @@ GDMIX_API int gdmix_re_eval_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_ac
  *               relative to the sum of magnitudes: |PL - exact| <= 3e-13 * sum_i (exp(s_i) + |y_i s_i|) — SSE's 2.5e-13 for the longest
  *               chain of additions (< 2 211 roundings) plus exp (<= 0.98 ulp) and the one rounding of exp(s) - y s (a fused multiply-add).
  *   NaN         a NaN score is counted (n_nan) and left out of the sum and of n. exp is IEEE: a score past ~88.7 (fp32) stays finite in fp64.
+ *   infinities  an infinite score is a score like any other: it is counted in n and its term is what IEEE arithmetic makes of the statement.
+ *               s = +inf: exp(s) = +inf, so the term is +inf for y < 0 and NaN (inf - inf, or 0 * inf) for y >= 0. s = -inf: exp(s) = 0 and
+ *               the term is -y s: +inf for y > 0, -inf for y < 0, NaN for y = 0. A finite score past ~709.78 gives +inf (y s is finite), one
+ *               below ~-745.13 gives -y s. (The log loss of an infinite score is exactly 0 on the label's side and +inf on the other.)
  *   limits      fewer than 2^31 samples per evaluation and fewer than 2^31 entities (GDMIX_RE_ERANGE).
  * Entities of at most 64 samples are summed in registers (four entities per wavefront, as gdmix_re_eval_entities does), larger ones by a
  * workgroup each; gdmix_re_set_eval_small_max moves the limit for both evaluations. No workspace, no synchronisation per entity call. */
@@ -553,7 +557,7 @@ GDMIX_API int gdmix_re_eval_topk_entities(gdmix_re_ctx* ctx, const int64_t* ent_
  * from run to run; never a floating-point atomic):  |LL - exact| <= 2.5e-13 * sum_i ce_i + n * eps  (2.5e-13 covers the < 2 211 roundings of
  * the longest chain of additions and the one of the term).
  * The entry points mirror the gdmix_re_eval_pl_ family: the same structs (the field `pl` holds LL) and the same state size. */
-#define GDMIX_RE_EVAL_LL_TERM_EPS 1.5e-16   /* measured 1.413e-16 (at s = 0.5575137) */
+#define GDMIX_RE_EVAL_LL_TERM_EPS 1.5e-16   /* measured 1.413e-16 (at s = 0.5575137); on an MI355X 1.306e-16 (at s = 0.5658179) over the grid of tests/eval_edges_helpers.py */
 #define GDMIX_RE_EVAL_LL_STATE_BYTES GDMIX_RE_EVAL_PL_STATE_BYTES
 typedef gdmix_re_eval_pl_out    gdmix_re_eval_ll_out;
 typedef gdmix_re_eval_pl_totals gdmix_re_eval_ll_totals;
