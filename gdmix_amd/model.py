@@ -575,10 +575,17 @@ class RandomEffectLRLBFGSModel:
                 self._solver.pin_routing()
         return self._solver
 
+    def _elastic_net_l1(self):
+        """The L1 weight of the stage's solves (REParams.elastic_net_alpha x l2_reg_weight); 0.0 without the flag: the plain solve."""
+        mp = getattr(self, "model_params", None)
+        return mp.elastic_net()[0] if getattr(mp, "elastic_net_alpha", None) else 0.0
+
     def _solver_options(self):
         mp = self.model_params
         # without an intercept the whole theta is regularised whatever regularize_bias says (binary_logistic_regression.py:72-82)
-        return SolverOptions(l2=mp.l2_reg_weight, regularize_bias=bool(mp.regularize_bias) and bool(self.has_intercept),
+        # --elastic_net_alpha: the solve's l2 is (1 - alpha) l2_reg_weight, and _elastic_net_l1() goes with it; without the flag l2_reg_weight itself
+        l2 = mp.elastic_net()[1] if self._elastic_net_l1() > 0.0 else mp.l2_reg_weight
+        return SolverOptions(l2=l2, regularize_bias=bool(mp.regularize_bias) and bool(self.has_intercept),
                              has_intercept=self.has_intercept,
                              m=mp.num_of_lbfgs_curvature_pairs, max_iter=mp.num_of_lbfgs_iterations,
                              ftol=mp.lbfgs_tolerance, variance_mode=VARIANCE_MODES[mp.random_effect_variance_mode],
@@ -852,6 +859,9 @@ class RandomEffectLRLBFGSModel:
             theta_thr, variance, uniq, feat_ptr, stats, resident = self._solve_batch(batch, model_weights, num_features)
         ic = 1 if self.has_intercept else 0
         coef_ptr = feat_ptr + np.arange(batch.E + 1, dtype=np.int64) * ic
+        if self._elastic_net_l1() > 0.0:
+            logger.info(f"elastic net (l1 = {self._elastic_net_l1():g}): {int(np.count_nonzero(theta_thr))} of {int(np.size(theta_thr))} coefficients "
+                        f"of {batch.E} entities are non-zero")
         self.last_training_stats = dict(entities=batch.E, samples=batch.N, nnz=batch.Z, **stats)
         results = ModelTable()
         if self._incremental(model_weights):
@@ -1046,6 +1056,9 @@ class RandomEffectLRLBFGSModel:
             solve = lambda packed, opts, theta0=None: self._solve_with_prior(solver, packed, opts, prior)
         elif getattr(self, "_feature_factor", None) is not None:
             solve = lambda packed, opts, theta0=None: self._solve_normalised(solver, packed, opts, theta0)
+        elif RandomEffectLRLBFGSModel._elastic_net_l1(self) > 0.0:      # (REParams refuses it with a prior and with normalisation: the branches above)
+            l1 = RandomEffectLRLBFGSModel._elastic_net_l1(self)
+            solve = lambda packed, opts, theta0=None: solver.solve(packed, opts, theta0=theta0, l1=l1)
         else:
             solve = solver.solve
         packed = pack()

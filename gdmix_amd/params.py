@@ -69,6 +69,30 @@ def check_l1_reg_weight(value):
     return w
 
 
+def check_elastic_net_alpha(p, stage_flags):
+    """--elastic_net_alpha of a random-effect stage's parameters: a finite alpha in [0, 1], and (for alpha > 0) none of the stage's flags
+    the L1 term does not run with, given as (set?, flag, why). -> alpha as a float (0.0 without the flag)."""
+    if p.elastic_net_alpha is None:
+        return 0.0
+    try:
+        alpha = float(p.elastic_net_alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"--elastic_net_alpha={p.elastic_net_alpha!r} is not a number") from None
+    if not math.isfinite(alpha) or alpha < 0.0 or alpha > 1.0:
+        raise ValueError(f"--elastic_net_alpha={p.elastic_net_alpha!r}: a finite alpha in [0, 1]")
+    if alpha > 0.0:
+        for is_set, flag, why in stage_flags:
+            if is_set:
+                raise ValueError(f"--elastic_net_alpha={alpha} does not run with {flag}: {why}")
+    return alpha
+
+
+def elastic_net_weights(alpha, lam):
+    """Photon-ML's elastic net (alpha, lambda) -> (l1, l2) = (alpha lambda, (1 - alpha) lambda)."""
+    alpha, lam = float(alpha), float(lam)
+    return alpha * lam, (1.0 - alpha) * lam
+
+
 def coefficient_bounds(records, features, has_intercept, where="--coefficient_constraints"):
     """Photon-ML's coefficient constraints as arrays. records: a list of {"name", "term", "lowerBound", "upperBound"} (either bound may be
     absent: infinite); features: the (name, term) list of --feature_file, in coefficient order. "term": "*" covers every term of a name,
@@ -362,6 +386,15 @@ class REParams(LRParams):
     # its perEntity records precision_at_K (include/gdmix_re.h, "ranking evaluation"; metrics.py). Needs metric_output_dir and
     # --model_type=logistic_regression; does not run with l2_reg_weights. --action=inference honours it when the data has labels.
     evaluators: Optional[str] = None
+    # not in the reference (Photon-ML's elastic net per random-effect coordinate): alpha in [0, 1], with l2_reg_weight as its lambda: every
+    # entity minimises (1/n)(loss + (l2/2)|theta_R|^2 + l1 |theta_R|_1) with l1 = alpha lambda, l2 = (1 - alpha) lambda, by OWL-QN on the device
+    # (include/gdmix_re.h, "elastic net"). Coefficients at exactly 0 stay out of the model file. Absent or 0: the stage is what it was. The
+    # stage has a flag of its own because --l1_reg_weight is the fixed effect's: this stage's parser drops flags it does not know, so that
+    # field exists here to refuse a value that would otherwise train a ridge model in silence, and that refusal stays. From the fixed
+    # effect's (l1, l2): l2_reg_weight = l1 + l2, elastic_net_alpha = l1 / (l1 + l2). Does not run with incremental_training or a
+    # feature_normalization (the L1 term is not invariant under their diagonal substitution), l2_reg_weights or rebalance_entities.
+    # --action=inference accepts and ignores the flag.
+    elastic_net_alpha: Optional[float] = None
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -374,6 +407,11 @@ class REParams(LRParams):
     def evaluator_spec(self):
         """What --evaluators asks for (EvaluatorSpec), or None without the flag."""
         return check_evaluators(self, self.partition_entity)
+
+    def elastic_net(self):
+        """(l1, l2) of the stage's solves: Photon-ML's (alpha, lambda) = (elastic_net_alpha, l2_reg_weight); (0, l2_reg_weight) without the flag."""
+        alpha = 0.0 if self.elastic_net_alpha is None else float(self.elastic_net_alpha)
+        return elastic_net_weights(alpha, self.l2_reg_weight) if alpha > 0.0 else (0.0, float(self.l2_reg_weight))
 
     def __post_init__(self):
         self.l2_grid()      # a bad list is an error at parse time
@@ -400,6 +438,12 @@ class REParams(LRParams):
             (self.feature_normalization not in (None, "none"), "--feature_normalization", "the column statistics are those of the uncapped data, and composing the two is not implemented")))
         if bound is not None:
             self.active_data_upper_bound = bound
+        if self.elastic_net_alpha is not None:
+            self.elastic_net_alpha = check_elastic_net_alpha(self, (
+                (self.incremental_training, "--incremental_training", "the L1 term is not invariant under the substitution that centres the L2 term on the prior"),
+                (self.feature_normalization not in (None, "none"), "--feature_normalization", "the L1 term is not invariant under the diagonal substitution of the normalised units"),
+                (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep of elastic-net models is not implemented"),
+                (self.rebalance_entities, "--rebalance_entities", "the elastic-net solve of exchanged entities is not implemented")))
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         if self.incremental_training and self.rebalance_entities:

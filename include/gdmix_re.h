@@ -292,6 +292,43 @@ GDMIX_API int    gdmix_re_set_scratch(gdmix_re_ctx* ctx, void* scratch, size_t b
 GDMIX_API int gdmix_re_variance_full(gdmix_re_ctx* ctx, const gdmix_re_packed* batch, const gdmix_re_opts* opts, const double* theta,
                                      double* variance, void* stream);
 
+/* ---- elastic net: per-entity models with an L1 term, solved by OWL-QN on the device (no ABI bump: two new symbols, nothing else moves) ----
+ * --elastic_net_alpha (gdmix_amd/params.py, REParams; Photon-ML's elastic net per random-effect coordinate). For one entity of n samples, in
+ * the conventions of gdmix_re_opts (theta in local index space, the intercept first, f divided by n):
+ *     F(theta) = (1/n) ( sum_i w_i l(y_i, x_i . theta + offset_i) + (l2/2) |theta_R|^2 + l1 |theta_R|_1 )
+ * l any of the three losses (opts->loss), l2 = opts->l2, R the set l2 regularises: every feature, and the intercept iff regularize_bias.
+ * Photon-ML's (lambda, alpha) is l1 = alpha lambda, l2 = (1 - alpha) lambda. With l1 = 0 this is gdmix_re_solve's objective.
+ * The algorithm is the step of include/gdmix_fe.h, "(ABI 23) L1 / elastic net", applied to this F, per entity: the pseudo-gradient, the
+ * two-loop direction on it with H0 from the newest pair, the zeroing where d_j pg_j >= 0, the orthant, the projected trial point with
+ * exact 0.0, backtracking from t = 1 / |pg|_2 (no pair stored) or 1 with c = 1e-4 on pg'(x(t) - x) and halving, the memory cleared after
+ * maxls rejections and then status 4, pair storage iff s'y > 2.2e-16 y'y, and the stops 0 / 1 / 2 / 3 in that order. What differs from that
+ * section, and only this: every term carries the 1/n (g is the gradient of the smooth part divided by n, and the pseudo-gradient adds or
+ * subtracts l1 / n), R is the set above, and the intercept is coefficient 0 of the entity, not the last one. m, max_iter, maxfun, maxls, ftol
+ * and pgtol are those of gdmix_re_opts; gdmix_re_opts does not grow.
+ * Results: theta is the last accepted point, never a rejected trial, so coordinates the orthant projection set to zero are exactly 0.0;
+ * theta_thr is that point thresholded as by gdmix_re_solve; fval = F with the L1 term; gnorm = |pg|_inf; nit, nfev (every evaluation counts)
+ * and status follow the statement. Variances are those of the smooth part at the returned theta — SIMPLE inside the solve kernels, FULL by
+ * gdmix_re_variance_full with the same l2 — for a coefficient at 0 too, as in the fixed effect.
+ * gdmix_re_solve_l1: l1 must be finite and >= 0 (GDMIX_RE_EINVAL otherwise). l1 == 0 forwards to gdmix_re_solve: the plain fit, bit for bit.
+ *   sum_loss != 0 is refused (GDMIX_RE_EINVAL: the fixed effect's elastic net is gdmix_fe_set_l1). An empty batch returns right behind the
+ *   argument checks. theta0 is the OWL-QN start point (NULL: zeros).
+ * Routing. The size classes of gdmix_re_solve are not involved (GDMIX_RE_NUM_CLASSES and the class table are untouched). An entity is solved
+ *   by re_owlqn_wave_kernel — one wavefront, the entity's block and the whole solver state in LDS — iff its OWL-QN LDS footprint (the plain
+ *   wavefront kernel's plus one coefficient vector, rounded up to 16 bytes) is within the context's wave_lds_limit
+ *   (gdmix_re_set_wave_lds_limit; 0: no entity), and otherwise, whatever its size, by re_owlqn_block_kernel: one workgroup per entity, the
+ *   state in a global scratch slot per workgroup, X streamed. One kernel writes the two lists into the batch's solver-owned `order` (the
+ *   first from the front, the second from the back); after the call the first two words of class_count hold their lengths (a later
+ *   gdmix_re_solve overwrites the record). The wavefront kernel's workgroup is one wavefront and its LDS bounds how many a CU holds, so its
+ *   entities within 20 KB are launched apart from the others, with that much LDS (their list is in the solver-owned cls_tmp). The two launches run side by side where the context has side streams. No workgroup waits for
+ *   another. Limits: one workgroup per large entity (no team, device-wide, tall or several-entities-per-wavefront variants: the head of a
+ *   Zipf distribution runs one workgroup per entity); no l2 sweep, no prior, no normalisation and no re-balancing compose with it on the
+ *   host (gdmix_amd/params.py).
+ * gdmix_re_solve_l1_scratch_bytes: device scratch the call needs beyond the pack workspace (gdmix_re_set_scratch), never less than
+ *   gdmix_re_solve_scratch_bytes of the same arguments. With less, the workgroup kernel runs on as many slots as fit (at least one). */
+GDMIX_API int gdmix_re_solve_l1(gdmix_re_ctx* ctx, const gdmix_re_packed* batch, const gdmix_re_opts* opts, double l1,
+                                const double* theta0, const gdmix_re_result* out, void* stream);
+GDMIX_API size_t gdmix_re_solve_l1_scratch_bytes(const gdmix_re_packed* batch, const gdmix_re_opts* opts);
+
 /* Score: logit[i] = x_i . theta_e + offset[i] (fp64 accumulate, stored fp32 as the score Avro
  * does, io_utils.py:367-375), logit_per_coord[i] = logit[i] - offset[i] (job_consumers.py:145-150).
  * has_model: [E] uint8, 0 => entity has no model and logit = offset (job_consumers.py:145-146);
