@@ -192,7 +192,7 @@ int fe_build_copy(hipStream_t s, int num_cus, const FeHooks& hooks, const FeSour
 int fe_build_column_copy(hipStream_t s, int num_cus, const FeHooks& hooks, const gdmix_re_packed* b, int n, int d, int64_t z, FeCopy* out,
                          FeHot* hot, DevBuf* tables, DevBuf* cdata, DevBuf* hot_mem);
 
-// ---- fe_owlqn.hip ----
+// ---- fe_qn.hip: the two projected quasi-Newton steps ----
 // One OWL-QN step (products, decision, update: three launches) on the reduced [gradient, value] buffer of a problem with l1 > 0;
 // the status lands in *status_dev as the L-BFGS-B step's does.
 void fe_owlqn_enqueue_step(const FeDev& F, const SolveParams& o, double l1, int32_t* status_dev, hipStream_t s);
@@ -208,7 +208,7 @@ void fe_tron_enqueue_hv_begin(const FeDev& F, hipStream_t s);
 void fe_tron_enqueue_hv_vector(const FeDev& F, const double* v, hipStream_t s);
 void fe_tron_enqueue_hv_end(const FeDev& F, hipStream_t s);
 
-// ---- fe_box.hip ----
+// ---- fe_qn.hip, the bounded step ----
 // One projected L-BFGS step (products, decision, update: three launches) on the reduced [gradient, value] buffer of a problem with bounds
 // (include/gdmix_fe.h, "(ABI 26) box constraints"); lower / upper: [P] device doubles of the problem's own, the intercept's infinite.
 void fe_box_enqueue_step(const FeDev& F, const SolveParams& o, const double* lower, const double* upper, int32_t* status_dev, hipStream_t s);

@@ -850,11 +850,11 @@ struct gdmix_fe_problem {
   DevBuf ccopies[2];     // ... and their units in the 6-byte form
   DevBuf hot_mem;        // the frequent columns' list
   DevBuf prior_mem;      // [2 P] the problem's copy of the prior mean and scale, then the check's flag (gdmix_fe_set_prior); empty until the first prior
-  double l1 = 0.0;       // weight of the L1 term (gdmix_fe_set_l1); > 0: the step is OWL-QN's (fe_owlqn.hip)
+  double l1 = 0.0;       // weight of the L1 term (gdmix_fe_set_l1); > 0: the step is OWL-QN's (fe_qn.hip)
   DevBuf tron_mem;       // the TRON buffer (fe_internal.hpp: FeTron); empty until TRON is first selected or gdmix_fe_hessian_vec first called
   int optimizer = GDMIX_FE_OPT_LBFGS;      // gdmix_fe_set_optimizer; TRON: the pass pairs are the HV variant's, the step fe_tron.hip's
   DevBuf box_mem;        // [2 P] the problem's copy of the lower and upper bounds, then the check's flags (gdmix_fe_set_bounds); empty until the first bounds
-  bool box = false;      // bounds are installed: the step is the projected L-BFGS of fe_box.hip
+  bool box = false;      // bounds are installed: the step is the projected L-BFGS of fe_qn.hip
   const double* box_lo() const { return box_mem.as<double>(); }
   const double* box_hi() const { return box_mem.as<double>() + F.P; }
   int32_t* status_dev = nullptr;
@@ -1418,7 +1418,7 @@ GDMIX_API int gdmix_fe_result(gdmix_fe_problem* p, double* theta, double* fval, 
     hipLaunchKernelGGL(fe_prior_theta_kernel, dim3(grid_for(p->F.P, 256, 1024)), dim3(256), 0, s, p->F, theta);
     HIP_TRY(hipGetLastError());
   } else if (theta) {
-    // under the OWL-QN step and the bounded step W.x is the trial point and W.t the last accepted one (fe_owlqn.hip, fe_box.hip)
+    // under the OWL-QN step and the bounded step W.x is the trial point and W.t the last accepted one (fe_qn.hip)
     HIP_TRY(hipMemcpyAsync(theta, (p->l1 > 0.0 || p->box) ? p->F.W.t : p->F.W.x, (size_t)p->F.P * 8, hipMemcpyDeviceToDevice, s));
   }
   CompactState S;

@@ -9,13 +9,13 @@
 // (fe_internal.hpp: FeTron): s, r, d of Steihaug's CG, h = what the last pass pair left with the regulariser added (H d after a
 // product, the gradient at the trial after an evaluation), xt the trial point x + s, g the gradient at x, vl the direction in the
 // shard's local order, c[2] the curvature weights of the accepted point and of the trial.
-#include "fe_internal.hpp"
+#include "fe_step_shares.hpp"
 #include "re_lbfgs_compact.hpp"
 #include "../../include/gdmix_fe.h"
 
 namespace gdmix {
 
-// the sums of one step, per virtual block in F.acc_part and in total in the decision's LDS
+// the sums of one step, per virtual block in F.acc_part and in total in the decision's LDS (fe_step_shares.hpp)
 enum {
   // after an evaluation                        after a product
   TS_X2 = 0,      // sum over R of xt_j^2       d'Hd
@@ -46,11 +46,9 @@ constexpr double TRON_CG_TOL = 0.1;
 // ---- 1. products: one pass over the coefficients -------------------------------------------------------------------------------------
 // The share of virtual block vb of nvb — coefficients (vb * 256 + tid) + k * nvb * 256 — into acc_part[vb]; nvb is a function of P alone.
 __global__ __launch_bounds__(FE_THREADS) void fe_tron_products_kernel(FeDev F, SolveParams o) {
-  __shared__ double red[FE_WAVES][TRON_K];
   if (F.state->status >= 0) return;     // a step enqueued behind the stop is a no-op
   const FeTron T = fe_tron_of(F);
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid >> 6;
-  const int vb = blockIdx.x, nvb = gridDim.x, P = F.P;
+  const int tid = threadIdx.x, vb = blockIdx.x, nvb = gridDim.x, P = F.P;
   const bool product = T.st->mode == FE_TM_PRODUCT;      // uniform
   const bool first = F.state->first != 0;
   double acc[TRON_K];
@@ -84,20 +82,7 @@ __global__ __launch_bounds__(FE_THREADS) void fe_tron_products_kernel(FeDev F, S
       acc[TS_GMAX] = fmax(acc[TS_GMAX], fabs(gn));
     }
   }
-  double mine = 0.0;
-#pragma unroll
-  for (int k = 0; k < TRON_K; ++k) {
-    const double t = (k == TS_GMAX) ? wave_max_nonneg(acc[k]) : wave_sum(acc[k]);
-    if (lane == k) mine = t;
-  }
-  if (lane < TRON_K) red[wv][lane] = mine;
-  __syncthreads();
-  if (tid < TRON_K) {
-    double s = red[0][tid];
-#pragma unroll
-    for (int w = 1; w < FE_WAVES; ++w) s = (tid == TS_GMAX) ? fmax(s, red[w][tid]) : s + red[w][tid];
-    F.acc_part[(size_t)vb * TRON_K + tid] = s;
-  }
+  fe_shares_store<TRON_K, TS_GMAX>(acc, F.acc_part, vb);
 }
 
 // ---- 2. decision: one workgroup ------------------------------------------------------------------------------------------------------
@@ -111,37 +96,9 @@ __device__ __forceinline__ void tron_start_cg(FeTronState& R, int action) {
 
 __global__ __launch_bounds__(FE_THREADS) void fe_tron_decide_kernel(FeDev F, SolveParams o, int nvb, int32_t* status_out) {
   __shared__ double tot[TRON_K];
-  __shared__ double part4[4][WAVE];
   if (F.state->status >= 0) return;     // (status_out keeps the status of the stop; the update repeats the stop's plan: idempotent)
   const int tid = threadIdx.x;
-  {
-    // value v of block b by thread (b % 4) * 64 + v: four partial totals per value, combined in order
-    static_assert(FE_THREADS == 4 * WAVE, "four groups of one lane per value");
-    const int v = tid & (WAVE - 1), g = tid >> 6;
-    if (v < TRON_K) {
-      double s = 0.0;
-      int b = g;
-      for (; b + 28 < nvb; b += 32) {   // eight loads in flight
-        double t[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t[q] = F.acc_part[(size_t)(b + 4 * q) * TRON_K + v];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) s = (v == TS_GMAX) ? fmax(s, t[q]) : s + t[q];
-      }
-      for (; b < nvb; b += 4) {
-        const double t = F.acc_part[(size_t)b * TRON_K + v];
-        s = (v == TS_GMAX) ? fmax(s, t) : s + t;
-      }
-      part4[g][v] = s;
-    }
-    __syncthreads();
-    if (tid < TRON_K) {
-      double s = part4[0][tid];
-#pragma unroll
-      for (int k = 1; k < 4; ++k) s = (tid == TS_GMAX) ? fmax(s, part4[k][tid]) : s + part4[k][tid];
-      tot[tid] = s;
-    }
-  }
+  fe_shares_total<TRON_K, TS_GMAX>(F.acc_part, nvb, tot);
   __syncthreads();
   if (tid != 0) return;
   const FeTron T = fe_tron_of(F);

@@ -208,7 +208,7 @@ GDMIX_API int gdmix_fe_set_prior(gdmix_fe_problem* p, const double* mean, const 
  *     F(theta) = sum_i w_i l(y_i, x_i . w + b + offset_i) + (l2/2) |theta_R|^2 + l1 |theta_R|_1
  * R the regularised set of the options (every feature; the intercept iff regularize_bias), l any of the three losses, the sum not divided by
  * n. Photon-ML's elastic net (lambda, alpha) is l1 = alpha lambda, l2 = (1 - alpha) lambda.
- * gdmix_fe_set_l1: l1 must be finite and >= 0 (GDMIX_RE_EINVAL otherwise). l1 > 0 makes the problem take the OWL-QN step (csrc/fe_owlqn.hip)
+ * gdmix_fe_set_l1: l1 must be finite and >= 0 (GDMIX_RE_EINVAL otherwise). l1 > 0 makes the problem take the OWL-QN step (csrc/fe_qn.hip)
  *   from its next step on; l1 == 0 puts it back on the L-BFGS-B step. Either way the call leaves the problem in the state of a
  *   gdmix_fe_restart with its current options at zeros. Stream-ordered; it waits for nothing. gdmix_fe_restart keeps the problem's l1; its
  *   theta0 is the OWL-QN start point. While a prior is installed the call is refused (GDMIX_RE_EINVAL), and so is gdmix_fe_set_prior with a
@@ -293,7 +293,7 @@ GDMIX_API int gdmix_fe_hessian_vec(gdmix_fe_problem* p, const double* theta, con
  * of any of the three losses. lo_j may be -inf, hi_j may be +inf, lo_j == hi_j pins a coefficient; the intercept is never bounded.
  * gdmix_fe_set_bounds: lower, upper are device pointers to [D + has_intercept] doubles, intercept last (copied by the library: 2 P doubles of
  *   the problem's own, allocated at the first selection; the pool does not change). Bounds make the problem take the projected L-BFGS step
- *   (csrc/fe_box.hip) from its next step on; both NULL puts it back on the L-BFGS-B step. Either way the call leaves the problem in the state
+ *   (csrc/fe_qn.hip) from its next step on; both NULL puts it back on the L-BFGS-B step. Either way the call leaves the problem in the state
  *   of a gdmix_fe_restart with its current options at the clamped zeros. Stream-ordered but for one wait, on the check of the caller's arrays.
  *   gdmix_fe_restart keeps the bounds; its theta0 (NULL: zeros) is clamped into the box and that is the start point.
  *   Refused with GDMIX_RE_EINVAL, the problem left as it was: a NaN bound; lo_j > hi_j; a bound on the intercept other than -inf / +inf;

@@ -31,7 +31,7 @@ def problem(loss, size):
 @functools.lru_cache(maxsize=None)
 def bounds(size):
     """-> (lower, upper) [D + 1], the intercept last and free; read-only."""
-    c = SIZES[size]
+    c = L1.shape(size)
     D = c["D"]
     u = np.random.default_rng([c["seed"], 0xB0]).random(D)
     lo, hi = np.full(D + 1, -np.inf), np.full(D + 1, np.inf)

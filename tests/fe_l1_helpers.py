@@ -20,6 +20,10 @@ LOSSES = ("logistic", "squared", "poisson")
 MODEL_TYPE = {"logistic": "logistic_regression", "squared": "linear_regression", "poisson": "poisson_regression"}
 SIZES = {"small": dict(n=600, k=8, D=50, seed=61, l1=3.0, l2=1.0),
          "wide": dict(n=20000, k=6, D=5000, seed=62, l1=1.5, l2=1.0)}
+# the shapes of tests/step_edges_helpers.py, drawn by case() like the two above; a table of their own: nothing that is parametrised over SIZES grows
+EDGE_SIZES = {"share29": dict(n=6000, k=6, D=7199, seed=71, l1=1.0, l2=1.0),
+              "share33": dict(n=6000, k=6, D=8199, seed=72, l1=1.0, l2=1.0),
+              "capped": dict(n=40000, k=8, D=123200, seed=73, l1=0.5, l2=1.0)}
 FIT = dict(has_intercept=True, regularize_bias=True, m=10, max_iter=500, tolerance=1e-12)
 PGTOL, MAXFUN, MAXLS = 1e-5, 15000, 20      # the solver's defaults (gdmix_amd.solver.SolverOptions)
 SUPPORT_SLACK = 1e-3      # a zero of the reference with | |g_j| - l1 | < SUPPORT_SLACK l1 may be on either side of the support
@@ -27,10 +31,14 @@ SMALL_COEFFICIENT = 1e-4  # ... and so may a non-zero below the stage's own spar
 MAX_LEFT_OUT = 4
 
 
+def shape(size):
+    return SIZES[size] if size in SIZES else EDGE_SIZES[size]
+
+
 @functools.lru_cache(maxsize=None)
 def case(loss, size):
     """-> (row_nnz_ptr, col, val, y, offset, D, l1, l2): no weights, labels by `loss`."""
-    c = SIZES[size]
+    c = shape(size)
     n, k, D = c["n"], c["k"], c["D"]
     rng = np.random.default_rng(c["seed"])
     col = rng.integers(0, D, (n, k)).astype(np.int64).ravel()

@@ -1,5 +1,5 @@
 """GPU: box constraints on the fixed effect's coefficients by projected L-BFGS on the device (fit_stepping(bounds=...); include/gdmix_fe.h,
-"(ABI 26) box constraints"; csrc/fe_box.hip) against a reference that does not share its algorithm: scipy's fmin_l_bfgs_b with the same bounds
+"(ABI 26) box constraints"; csrc/fe_qn.hip) against a reference that does not share its algorithm: scipy's fmin_l_bfgs_b with the same bounds
 (tests/fe_box_helpers.py, which also states the bars). Three losses at two sizes, a wrapping history ring, start points, a problem solved at its
 start point, the plain fit bit for bit without bounds, the same bits across runs, lookaheads and restarts, every refusal, variances, two workers
 against one, and the stage through the command line."""

@@ -1,5 +1,5 @@
 """GPU: the fixed effect's L1 / elastic-net fit by OWL-QN on the device (fit_stepping(l1=...); include/gdmix_fe.h, "(ABI 23) L1 / elastic net";
-csrc/fe_owlqn.hip) against a reference that does not share its algorithm: scipy's bounded L-BFGS-B on the split problem (tests/fe_l1_helpers.py,
+csrc/fe_qn.hip) against a reference that does not share its algorithm: scipy's bounded L-BFGS-B on the split problem (tests/fe_l1_helpers.py,
 which also states the bars). Three losses at two sizes, a wrapping history ring, the all-zero solution, the plain fit bit for bit at l1 = 0, the
 same bits across runs, step forms and restarts, variances, two workers against one, and the stage through the command line."""
 import json

@@ -1,5 +1,5 @@
 """What the projected L-BFGS step of the fixed effect costs next to the L-BFGS-B and OWL-QN steps (include/gdmix_fe.h, "(ABI 26) box
-constraints"; csrc/fe_box.hip).
+constraints"; csrc/fe_qn.hip under BoxRule).
 
     python tools/fe_box_bench.py [--rows 4000000] [--evals 40] [--out profiles/fe_box.txt]
 

@@ -1,4 +1,4 @@
-"""What the OWL-QN step of the fixed effect costs next to the L-BFGS-B step (include/gdmix_fe.h, "(ABI 23) L1 / elastic net"; csrc/fe_owlqn.hip).
+"""What the OWL-QN step of the fixed effect costs next to the L-BFGS-B step (include/gdmix_fe.h, "(ABI 23) L1 / elastic net"; csrc/fe_qn.hip under OwlRule).
 
     python tools/fe_l1_bench.py [--rows 4000000] [--evals 40] [--out profiles/fe_l1_step.txt]
 

@@ -1,5 +1,5 @@
-"""What the TRON optimiser of the fixed effect costs and buys next to L-BFGS-B (include/gdmix_fe.h, "(ABI 24) TRON"; csrc/fe_tron.hip and the HV
-variant of the row kernels in csrc/fe_solve.hip).
+"""What the TRON optimiser of the fixed effect costs and buys next to L-BFGS-B (include/gdmix_fe.h, "(ABI 24) TRON"; csrc/fe_tron.hip with the share sums of
+csrc/fe_step_shares.hpp, and the HV variant of the row kernels in csrc/fe_solve.hip).
 
     python tools/fe_tron_bench.py [--rows 4000000] [--pairs 60] [--out profiles/fe_tron_bench.txt]
 
