@@ -14,6 +14,7 @@
 // What a rule derives — the pseudo-gradient and the orthant, or the binding set, the reduced and the projected gradient — is a function of
 // (g_j, x_j) and the rule's own data alone and is formed where it is needed, never stored. The intercept's bounds are -inf / +inf
 // (gdmix_fe_set_bounds checks it), so the bounded step does not treat it apart.
+#include "box_rule.hpp"
 #include "fe_step_shares.hpp"
 #include "re_lbfgs_compact.hpp"
 #include "../../include/gdmix_fe.h"
@@ -93,16 +94,7 @@ struct OwlRule {
   }
 };
 
-__device__ __forceinline__ double box_clamp(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }      // exactly the bound's double
-// j is in the binding set: at a bound with the gradient pushing out of the box, or pinned
-__device__ __forceinline__ bool box_binding(double g, double x, double lo, double hi) {
-  return (x <= lo && g > 0.0) || (x >= hi && g < 0.0) || lo == hi;
-}
-// the direction entry as it is used: 0 on the binding set, and where x sits at a bound and d points out of the box
-__device__ __forceinline__ double box_direction(double d, bool binding, double x, double lo, double hi) {
-  return (binding || (x <= lo && d < 0.0) || (x >= hi && d > 0.0)) ? 0.0 : d;
-}
-
+// box_clamp, box_binding, box_direction: box_rule.hpp (shared with the random effect's bounded solve)
 struct BoxRule {
   const double *lower, *upper;      // [P] device doubles
   static constexpr bool L1_TERM = false;

@@ -511,6 +511,8 @@ class RandomEffectLRLBFGSModel:
         self._decoded = {}          # read key -> RawBatch decoded for a group, until _read hands it out
         self.last_training_stats = None
         self._stage_metrics = None  # metrics.StageMetrics when model_params.metric_output_dir is set (created with the first scores)
+        self._entity_bounds_np = None   # --entity_coefficient_constraints: (lower, upper) [num_features] once the file has been read ...
+        self._entity_bounds_dev = None  # ... and the pair on the device once a solve has asked for it
         self._feature_factor = None # --feature_normalization: the stage's factors [num_features] on the device (set_feature_factors)
 
     # ---- the stage's metric, on the device while it scores (REParams.metric_output_dir) -------------------------------------------
@@ -580,6 +582,28 @@ class RandomEffectLRLBFGSModel:
         mp = getattr(self, "model_params", None)
         return mp.elastic_net()[0] if getattr(mp, "elastic_net_alpha", None) else 0.0
 
+    def _read_entity_bounds(self, num_features):
+        """--entity_coefficient_constraints: the file, read once per stage -> (lower, upper) [num_features] by global feature id (the order
+        of --feature_file). Without the flag nothing happens."""
+        path = getattr(self.model_params, "entity_coefficient_constraints", None)
+        if path is None or self._entity_bounds_np is not None:
+            return
+        from .params import read_coefficient_constraints
+        lower, upper = read_coefficient_constraints(path, read_feature_list(self.feature_file), False, flag="--entity_coefficient_constraints")
+        if lower.size != num_features:
+            raise ValueError(f"--entity_coefficient_constraints: --feature_file lists {lower.size} features, the metadata's bag "
+                             f"{self.feature_bag_name} has {num_features}")
+        self._entity_bounds_np = (lower, upper)
+
+    def _entity_bounds(self, solver):
+        """The stage's bound tables on the device, uploaded once; None without the flag."""
+        host = getattr(self, "_entity_bounds_np", None)
+        if host is None:
+            return None
+        if self._entity_bounds_dev is None:
+            self._entity_bounds_dev = solver.upload_bounds(*host)
+        return self._entity_bounds_dev
+
     def _solver_options(self):
         mp = self.model_params
         # without an intercept the whole theta is regularised whatever regularize_bias says (binary_logistic_regression.py:72-82)
@@ -608,6 +632,7 @@ class RandomEffectLRLBFGSModel:
                           schema_params=schema_params, num_features=num_features)
         elif action == constants.ACTION_TRAIN:
             training_data_dir, validation_data_dir = action_context
+            self._read_entity_bounds(num_features)
             model_file = os.path.join(self.model_params.output_model_dir, avro_filename)
             model_weights = self._load_weights(model_file, True)    # load initial model if available
             model_weights = self._train(training_data_dir, tensor_metadata, model_weights, num_features, schema_params,
@@ -862,6 +887,15 @@ class RandomEffectLRLBFGSModel:
         if self._elastic_net_l1() > 0.0:
             logger.info(f"elastic net (l1 = {self._elastic_net_l1():g}): {int(np.count_nonzero(theta_thr))} of {int(np.size(theta_thr))} coefficients "
                         f"of {batch.E} entities are non-zero")
+        if self._entity_bounds_np is not None:
+            lower, upper = self._entity_bounds_np
+            feat = np.ones(int(coef_ptr[-1]), bool)
+            if ic:
+                feat[coef_ptr[:-1]] = False
+            th = np.asarray(theta_thr)[feat]
+            at_bound = int(np.count_nonzero((th == lower[uniq]) | (th == upper[uniq])))
+            # (counted on the written model: a free coefficient that the sparsity threshold set to 0 counts where 0 is its bound)
+            logger.info(f"entity_coefficient_constraints: {at_bound} of {int(th.size)} written feature coefficients of {batch.E} entities equal a bound")
         self.last_training_stats = dict(entities=batch.E, samples=batch.N, nnz=batch.Z, **stats)
         results = ModelTable()
         if self._incremental(model_weights):
@@ -1059,6 +1093,9 @@ class RandomEffectLRLBFGSModel:
         elif RandomEffectLRLBFGSModel._elastic_net_l1(self) > 0.0:      # (REParams refuses it with a prior and with normalisation: the branches above)
             l1 = RandomEffectLRLBFGSModel._elastic_net_l1(self)
             solve = lambda packed, opts, theta0=None: solver.solve(packed, opts, theta0=theta0, l1=l1)
+        elif RandomEffectLRLBFGSModel._entity_bounds(self, solver) is not None:      # (REParams refuses it with every branch above)
+            bounds = RandomEffectLRLBFGSModel._entity_bounds(self, solver)
+            solve = lambda packed, opts, theta0=None: solver.solve(packed, opts, theta0=theta0, bounds=bounds)
         else:
             solve = solver.solve
         packed = pack()

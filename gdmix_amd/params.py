@@ -144,19 +144,20 @@ def coefficient_bounds(records, features, has_intercept, where="--coefficient_co
     return lower, upper
 
 
-def read_coefficient_constraints(path, features, has_intercept):
+def read_coefficient_constraints(path, features, has_intercept, flag="--coefficient_constraints"):
     """--coefficient_constraints=PATH -> (lower, upper) of coefficient_bounds; the file is a JSON array in the shape of Photon-ML's
-    constraint string. Python's NaN / Infinity literals are refused like any non-finite number."""
+    constraint string. Python's NaN / Infinity literals are refused like any non-finite number. flag: the name the messages give the
+    flag (the random effect's is --entity_coefficient_constraints)."""
     import json
 
     def refuse(literal):
-        raise ValueError(f"--coefficient_constraints={path}: {literal} is not a finite number (leave the bound out for no bound)")
+        raise ValueError(f"{flag}={path}: {literal} is not a finite number (leave the bound out for no bound)")
     with open(path) as f:
         try:
             records = json.load(f, parse_constant=refuse)
         except json.JSONDecodeError as e:
-            raise ValueError(f"--coefficient_constraints={path}: not JSON ({e})") from None
-    return coefficient_bounds(records, features, has_intercept, where=f"--coefficient_constraints={path}")
+            raise ValueError(f"{flag}={path}: not JSON ({e})") from None
+    return coefficient_bounds(records, features, has_intercept, where=f"{flag}={path}")
 
 
 def parse_l2_grid(text):
@@ -379,7 +380,7 @@ class REParams(LRParams):
     # ... and so is --optimizer: anything but LBFGS is refused. The random-effect kernels run scipy's L-BFGS-B loop on chip; a trust-region
     # Newton solver inside them is another project.
     optimizer: str = "LBFGS"
-    # ... and so is --coefficient_constraints: box constraints for per-entity models are a follow-up.
+    # ... and so is --coefficient_constraints: this stage's box constraints are --entity_coefficient_constraints (below).
     coefficient_constraints: Optional[str] = None
     # not in the reference (Photon-ML's evaluator names): LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, comma-separated, any case, <id> this
     # stage's partition_entity. The stage's evalSummary.json gains the logistic loss and the means of the per-entity AUC and precision@K,
@@ -395,6 +396,16 @@ class REParams(LRParams):
     # feature_normalization (the L1 term is not invariant under their diagonal substitution), l2_reg_weights or rebalance_entities.
     # --action=inference accepts and ignores the flag.
     elastic_net_alpha: Optional[float] = None
+    # not in the reference (Photon-ML's coefficient box constraints per random-effect coordinate): a JSON file in the format of the fixed
+    # effect's --coefficient_constraints (read_coefficient_constraints: records, wildcards and refusals are the same), names and terms those
+    # of this stage's --feature_file. Every entity minimises its smooth objective subject to lo_j <= theta_j <= hi_j, one box per feature
+    # for all entities, the intercept free, by projected L-BFGS on the device (include/gdmix_re.h, "box constraints"). The stage has a flag
+    # of its own for the reason --elastic_net_alpha has: --coefficient_constraints is the fixed effect's, this stage's parser drops flags
+    # it does not know, and the field above refuses it; that refusal stays. Needs --feature_file and --feature_bag. Does not run with
+    # elastic_net_alpha > 0, incremental_training or a feature_normalization (the bounds are in original units; the substitution is a
+    # follow-up, as in the fixed effect), l2_reg_weights or rebalance_entities. --action=inference accepts and ignores the flag: it does not
+    # open the file. These refusals are made where the parameters are parsed, whatever the action, as --elastic_net_alpha's are.
+    entity_coefficient_constraints: Optional[str] = None
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -444,6 +455,18 @@ class REParams(LRParams):
                 (self.feature_normalization not in (None, "none"), "--feature_normalization", "the L1 term is not invariant under the diagonal substitution of the normalised units"),
                 (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep of elastic-net models is not implemented"),
                 (self.rebalance_entities, "--rebalance_entities", "the elastic-net solve of exchanged entities is not implemented")))
+        if self.entity_coefficient_constraints is not None:
+            flag = "--entity_coefficient_constraints"
+            if not self.feature_file or not self.feature_bag:
+                raise ValueError(f"{flag} names features by the names and terms of --feature_file: it does not run without --feature_file and --feature_bag")
+            for is_set, other, why in (
+                    (bool(self.elastic_net_alpha), "--elastic_net_alpha", "bounds with an L1 term are not implemented"),
+                    (self.incremental_training, "--incremental_training", "the bounds are in original units, and bounds under the prior's substitution are not implemented"),
+                    (self.feature_normalization not in (None, "none"), "--feature_normalization", "the bounds are in original units, and bounds under the normalisation's substitution are not implemented"),
+                    (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep of bounded models is not implemented"),
+                    (self.rebalance_entities, "--rebalance_entities", "the bounded solve of exchanged entities is not implemented")):
+                if is_set:
+                    raise ValueError(f"{flag} does not run with {other}: {why}")
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         if self.incremental_training and self.rebalance_entities:

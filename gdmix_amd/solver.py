@@ -150,7 +150,7 @@ class _EvalTotals(C.Structure):
 EXPORTED_SYMBOLS = (
     "gdmix_re_abi_version", "gdmix_re_build_id", "gdmix_re_device_shared", "gdmix_re_grid_lock_acquire", "gdmix_re_grid_lock_release", "gdmix_re_grid_lock_stats", "gdmix_re_last_error", "gdmix_re_default_opts", "gdmix_re_create",
     "gdmix_re_destroy", "gdmix_re_pack_workspace_bytes", "gdmix_re_pack", "gdmix_re_set_defer_unique", "gdmix_re_pack_join", "gdmix_re_solve",
-    "gdmix_re_solve_l1", "gdmix_re_solve_l1_scratch_bytes",
+    "gdmix_re_solve_l1", "gdmix_re_solve_l1_scratch_bytes", "gdmix_re_solve_box", "gdmix_re_solve_box_scratch_bytes",
     "gdmix_re_solve_scratch_bytes", "gdmix_re_set_scratch", "gdmix_re_variance_full", "gdmix_re_set_wave_lds_limit", "gdmix_re_score",
     "gdmix_re_widen_workspace_bytes", "gdmix_re_widen", "gdmix_re_set_timing", "gdmix_re_last_solve_ms", "gdmix_re_set_kernel_mask", "gdmix_re_set_giant_nnz", "gdmix_re_set_team_nnz", "gdmix_re_set_tall_min_n", "gdmix_re_set_tall_split_n", "gdmix_re_set_tall_team_n", "gdmix_re_set_tall_mid_n", "gdmix_re_set_spread", "gdmix_re_set_narrow",
     "gdmix_fe_create", "gdmix_fe_destroy", "gdmix_fe_eval", "gdmix_fe_reduce_buffer", "gdmix_fe_step", "gdmix_fe_step_async", "gdmix_fe_step_status", "gdmix_fe_solve", "gdmix_fe_result",
@@ -222,6 +222,10 @@ def load_library():
                                       C.POINTER(_Result), C.c_void_p]
     lib.gdmix_re_solve_l1_scratch_bytes.argtypes = [C.POINTER(_Packed), C.POINTER(_Opts)]
     lib.gdmix_re_solve_l1_scratch_bytes.restype = C.c_size_t
+    lib.gdmix_re_solve_box.argtypes = [C.c_void_p, C.POINTER(_Packed), C.POINTER(_Opts), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.POINTER(_Result), C.c_void_p]
+    lib.gdmix_re_solve_box_scratch_bytes.argtypes = [C.POINTER(_Packed), C.POINTER(_Opts)]
+    lib.gdmix_re_solve_box_scratch_bytes.restype = C.c_size_t
     lib.gdmix_re_set_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.gdmix_re_set_wave_lds_limit.argtypes = [C.c_void_p, C.c_int]
     lib.gdmix_re_set_kernel_mask.argtypes = [C.c_void_p, C.c_int]
@@ -1029,18 +1033,32 @@ class REDeviceSolver:
                     status=t.full((E,), -1, dtype=t.int32, device=dev))
 
     @_serialised
-    def solve(self, packed: PackedBatch, opts: Optional[SolverOptions] = None, theta0=None, out=None, l1=0.0) -> SolveResult:
+    def solve(self, packed: PackedBatch, opts: Optional[SolverOptions] = None, theta0=None, out=None, l1=0.0, bounds=None) -> SolveResult:
         """l1 > 0: the elastic-net solve (include/gdmix_re.h, "elastic net"; opts.l2 is its l2, theta0 its start point); l1 == 0: the plain
-        solve, the same call as without the argument."""
+        solve, the same call as without the argument. bounds = (lower, upper): the box-constrained solve ("box constraints"): two float64
+        device tensors of one length, indexed by global feature id (upload_bounds makes them), either may be None; both None is the plain
+        solve. Bounds together with l1 != 0 are refused."""
         t = self.torch
         opts = opts or SolverOptions()
         if bool(opts.has_intercept) != packed.has_intercept:
             raise GdmixReError("has_intercept of the options differs from the packed batch")
         c_opts = opts.to_c()
         l1 = float(l1)
+        lower, upper = bounds if bounds is not None else (None, None)
+        boxed = lower is not None or upper is not None
+        if boxed:
+            if l1 != 0.0:
+                raise GdmixReError("bounds do not run with l1 != 0: bounds with an L1 term are not implemented")
+            for b in (lower, upper):
+                if b is not None and (not getattr(b, "is_cuda", False) or b.dtype != t.float64 or b.dim() != 1 or not b.is_contiguous()):
+                    raise GdmixReError("bounds are contiguous float64 device tensors, one entry per global feature id (upload_bounds)")
+            if lower is not None and upper is not None and lower.numel() != upper.numel():
+                raise GdmixReError("lower and upper bounds differ in length")
         need = self.lib.gdmix_re_solve_scratch_bytes(C.byref(packed.c), C.byref(c_opts))
         if l1 != 0.0:      # the larger of the two needs
             need = max(need, self.lib.gdmix_re_solve_l1_scratch_bytes(C.byref(packed.c), C.byref(c_opts)))
+        if boxed:
+            need = max(need, self.lib.gdmix_re_solve_box_scratch_bytes(C.byref(packed.c), C.byref(c_opts)))
         if need > packed.c.scratch_bytes and (self._scratch is None or self._scratch.numel() < need):
             self._scratch = t.empty(need, dtype=t.uint8, device=self.device)
         if self._scratch is not None:
@@ -1056,7 +1074,11 @@ class REDeviceSolver:
         p = lambda x: None if x is None else x.data_ptr()
         c_res = _Result(p(tensors["theta"]), p(tensors["theta_thr"]), p(tensors.get("variance")), p(tensors["fval"]),
                         p(tensors["gnorm"]), p(tensors["nit"]), p(tensors["nfev"]), p(tensors["status"]))
-        if l1 != 0.0:      # (a negative or non-finite weight is the library's to refuse)
+        if boxed:          # (what the tables hold is the library's to check, on the device)
+            n_feat = (lower if lower is not None else upper).numel()
+            _check(self.lib.gdmix_re_solve_box(self._h, C.byref(packed.c), C.byref(c_opts), p(lower), p(upper), n_feat, p(theta0), C.byref(c_res),
+                                               self._stream()), "gdmix_re_solve_box")
+        elif l1 != 0.0:      # (a negative or non-finite weight is the library's to refuse)
             _check(self.lib.gdmix_re_solve_l1(self._h, C.byref(packed.c), C.byref(c_opts), l1, p(theta0), C.byref(c_res),
                                               self._stream()), "gdmix_re_solve_l1")
         else:
@@ -1068,6 +1090,14 @@ class REDeviceSolver:
         """(entities the wavefront kernel took, entities the workgroup kernel took) of the last elastic-net solve on this batch."""
         cc = packed._view(packed.c.class_count, 2, self.torch.int32).cpu().numpy()
         return int(cc[0]), int(cc[1])
+
+    box_counts = l1_counts      # ... or of the last box-constrained solve: the routing and its record are one
+
+    def upload_bounds(self, lower, upper):
+        """Host arrays [num_features] by global feature id -> the (lower, upper) device pair solve(bounds=...) takes."""
+        t = self.torch
+        up = lambda a: None if a is None else t.from_numpy(np.array(a, np.float64)).to(self.device)      # (a copy: the caller's may be read-only)
+        return up(lower), up(upper)
 
     @_serialised
     def variance_full(self, packed: PackedBatch, opts: SolverOptions, theta):

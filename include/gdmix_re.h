@@ -259,7 +259,7 @@ GDMIX_API int gdmix_re_pack(gdmix_re_ctx* ctx, const gdmix_re_raw_batch* raw_dev
  * NEXT to the gdmix_re_solve the caller queues behind the pack: a copy-shaped kernel beside kernels bound by their arithmetic.
  * Every other member of gdmix_re_packed is ordered on `stream` as before. `unique_global` is ordered on the stream of the next of
  * these calls on the same context: gdmix_re_solve (on return the stream is behind the compaction as it is behind the solve),
- * gdmix_re_score, gdmix_re_variance_full, gdmix_fe_create, gdmix_re_pack (the next batch), gdmix_re_pack_join, gdmix_re_join_features,
+ * gdmix_re_solve_box (before its first kernel: it reads the array), gdmix_re_score, gdmix_re_variance_full, gdmix_fe_create, gdmix_re_pack (the next batch), gdmix_re_pack_join, gdmix_re_join_features,
  * gdmix_re_score_models. A caller that reads
  * unique_global itself, or frees / reuses the workspace, without one of them in between calls gdmix_re_pack_join(ctx, stream)
  * first. Default off (everything stream-ordered when gdmix_re_pack returns); gdmix_amd/solver.py switches it on. Results are the
@@ -328,6 +328,59 @@ GDMIX_API int gdmix_re_variance_full(gdmix_re_ctx* ctx, const gdmix_re_packed* b
 GDMIX_API int gdmix_re_solve_l1(gdmix_re_ctx* ctx, const gdmix_re_packed* batch, const gdmix_re_opts* opts, double l1,
                                 const double* theta0, const gdmix_re_result* out, void* stream);
 GDMIX_API size_t gdmix_re_solve_l1_scratch_bytes(const gdmix_re_packed* batch, const gdmix_re_opts* opts);
+
+/* ---- box constraints: per-entity models inside a box, solved by projected L-BFGS on the device (no ABI bump: two new symbols, nothing else moves) ----
+ * --entity_coefficient_constraints (gdmix_amd/params.py, REParams; Photon-ML's coefficient box constraints per random-effect coordinate). For
+ * one entity of n samples, in the conventions of gdmix_re_opts (theta in local index space, the intercept first, everything divided by n):
+ *     F(theta) = (1/n) ( sum_i w_i l(y_i, x_i . theta + offset_i) + (l2/2) |theta_R|^2 )      subject to  lo_j <= theta_j <= hi_j
+ * l any of the three losses (opts->loss), l2 = opts->l2, R the set l2 regularises: every feature, and the intercept iff regularize_bias.
+ * lo_j may be -inf, hi_j may be +inf, lo_j == hi_j pins a coefficient; the intercept is never bounded. One box per global feature id, the
+ * same for every entity that has the feature.
+ * The algorithm is the step of include/gdmix_fe.h, "(ABI 26) box constraints", applied to this F, per entity. With g the gradient of F
+ * (l2 term included) at the accepted point x and clamp(v)_j = min(max(v_j, lo_j), hi_j), exactly the bound's double where it clamps:
+ *   binding set      B = { j : (x_j <= lo_j and g_j > 0) or (x_j >= hi_j and g_j < 0) or lo_j == hi_j }; reduced gradient q_j = 0 on B, g_j off B.
+ *   direction        the two-loop recursion on q over the last <= m stored pairs s = x+ - x, y = g+ - g, H0 = (s'y / y'y) I from the newest
+ *                    pair, negated; then d_j = 0 on B and wherever x_j <= lo_j and d_j < 0 or x_j >= hi_j and d_j > 0. No pair stored: d = -q.
+ *   trial            x(t) = clamp(x + t d).
+ *   search           t = 1 / |q|_2 while no pair is stored, else 1; accepted when F(x(t)) <= F(x) + 1e-4 g'(x(t) - x), else t is halved. After
+ *                    maxls rejected trials in one iteration: the memory is cleared and the search starts again along -q if a pair was
+ *                    stored, else the solve stops with status 4 at x.
+ *   pair storage     only if s'y > 2.2e-16 y'y.
+ *   stops            after each accepted iterate, in this order: gnorm = max_j |x_j - clamp(x - g)_j| <= pgtol -> 0 (the projected-gradient
+ *                    norm; also tested at the start point); F_old - F <= ftol max(|F_old|, |F|, 1) -> 1; nit >= max_iter -> 2;
+ *                    nfev > maxfun -> 3. Every evaluation counts in nfev.
+ *   start point      clamp(theta0); zeros (theta0 NULL) are clamped too.
+ * What differs from the fixed effect's section, and only this: every term carries the 1/n, R is the set above, and the intercept is
+ * coefficient 0 of the entity, not the last one. m, max_iter, maxfun, maxls, ftol and pgtol are those of gdmix_re_opts; gdmix_re_opts does
+ * not grow.
+ * gdmix_re_solve_box: lower, upper are device pointers to num_features doubles each, indexed by GLOBAL feature id — the ids unique_global
+ *   holds — and shared by every entity; they are not expanded to the batch's P coefficients (16 B per coefficient of extra HBM and a pass to
+ *   build it, against two tables of D doubles that stay in L2). A solve kernel gathers lower[unique_global[f0 + j]] once per entity while it
+ *   stages the block and keeps lo and hi next to the solver state; the intercept's slot gets -inf / +inf. Either pointer may be NULL: no
+ *   bound on that side. Both NULL forwards to gdmix_re_solve: the plain fit, bit for bit. unique_global may come from a deferred compaction
+ *   (gdmix_re_set_defer_unique): the call orders `stream` behind it before its first kernel reads the array (it is one of the calls listed
+ *   there).
+ *   Refused with GDMIX_RE_EINVAL, the results untouched: a NaN bound; lo_j > hi_j; num_features not above the largest id of the batch (or
+ *   negative); sum_loss != 0 (the fixed effect's box is gdmix_fe_set_bounds); a loss code outside the three. The caller's arrays are checked
+ *   on the device and the verdict comes back with the read-back the call waits for anyway (the list lengths): one host wait per solve. An
+ *   empty batch returns right behind the host-side argument checks.
+ * Results: theta is the last accepted point, never a rejected trial: lo <= theta <= hi holds exactly and a clamped coordinate is the bound's
+ *   double. theta_thr is that point thresholded as by gdmix_re_solve, except that a coefficient whose box does not contain 0 (lo_j > 0 or
+ *   hi_j < 0) keeps its value: the written model lies in the box too. fval = F, gnorm = the projected-gradient norm above; nit, nfev and status
+ *   follow the statement. Variances are those of the smooth objective at the returned theta — SIMPLE inside the solve kernels, FULL by
+ *   gdmix_re_variance_full, unchanged — for a coefficient at a bound too (the fixed effect's choice).
+ * Routing is the elastic net's: the size classes are not involved; an entity is solved by re_owlqn_wave_kernel iff its footprint is within
+ *   the context's wave_lds_limit, otherwise by re_owlqn_block_kernel (one workgroup, a scratch slot); the lists, the first two words of
+ *   class_count and the two launches split at 20 KB are as there. The bounded step keeps x, g, d, xt, gt, lo and hi — seven coefficient vectors
+ *   where OWL-QN has six; it needs no pseudo-gradient, q being a function of (g, x, lo, hi) — so its LDS footprint is the plain wavefront
+ *   kernel's plus two coefficient vectors, rounded up to 16 bytes, and a scratch slot holds one vector more than the elastic net's. Limits
+ *   as there: one workgroup per large entity; no L1 term, no prior, no normalisation, no l2 sweep and no re-balancing compose with it on the
+ *   host (gdmix_amd/params.py).
+ * gdmix_re_solve_box_scratch_bytes: device scratch the call needs beyond the pack workspace, never less than gdmix_re_solve_scratch_bytes of
+ *   the same arguments. With less, the workgroup kernel runs on as many slots as fit (at least one). */
+GDMIX_API int gdmix_re_solve_box(gdmix_re_ctx* ctx, const gdmix_re_packed* batch, const gdmix_re_opts* opts, const double* lower,
+                                 const double* upper, int64_t num_features, const double* theta0, const gdmix_re_result* out, void* stream);
+GDMIX_API size_t gdmix_re_solve_box_scratch_bytes(const gdmix_re_packed* batch, const gdmix_re_opts* opts);
 
 /* Score: logit[i] = x_i . theta_e + offset[i] (fp64 accumulate, stored fp32 as the score Avro
  * does, io_utils.py:367-375), logit_per_coord[i] = logit[i] - offset[i] (job_consumers.py:145-150).
