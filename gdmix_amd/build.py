@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgdmix_re.so")
-SOURCES = ["re_api.hip", "re_route.hip", "re_solve.hip", "re_owlqn.hip", "re_solve_tall.hip", "re_pack.hip", "re_pack_big.hip", "re_wire.hip", "re_variance_big.hip", "re_evaluate.hip", "re_evaluate_poisson.hip", "re_sweep.hip", "re_prior.hip", "re_downsample.hip", "re_cap.hip", "re_group.hip", "re_select.hip", "feature_stats.hip", "fe_solve.hip", "fe_copy.hip", "fe_sweep.hip", "fe_qn.hip", "fe_tron.hip"]
+SOURCES = ["re_api.hip", "re_route.hip", "re_solve.hip", "re_owlqn.hip", "re_tron.hip", "re_solve_tall.hip", "re_pack.hip", "re_pack_big.hip", "re_wire.hip", "re_variance_big.hip", "re_evaluate.hip", "re_evaluate_poisson.hip", "re_sweep.hip", "re_prior.hip", "re_downsample.hip", "re_cap.hip", "re_group.hip", "re_select.hip", "feature_stats.hip", "fe_solve.hip", "fe_copy.hip", "fe_sweep.hip", "fe_qn.hip", "fe_tron.hip"]
 IO_LIB = os.path.join(HERE, "libgdmix_io.so")
 IO_SOURCES = ["io_reader.cpp", "io_avro.cpp"]
 IO_HEADERS = [os.path.join("..", "..", "include", "gdmix_io.h")]

@@ -224,17 +224,20 @@ def metric_dir(root, stage):
     return os.path.join(root, stage, "metrics")
 
 
-def stage_argv(root, stage, model_type=LOGISTIC, device_metrics=False, l2_grids=None, optimizer=None, evaluators=None):
+def stage_argv(root, stage, model_type=LOGISTIC, device_metrics=False, l2_grids=None, optimizer=None, evaluators=None, entity_optimizer=None):
     """The flat argv gdmix-workflow would hand the trainer for this stage of lr-movieLens.yaml (output under <root>/<stage>/).
     device_metrics: a random-effect stage also reports its metric (--metric_output_dir, not a flag of the reference).
     l2_grids: {stage: "w0,w1,..."} — a stage listed there, the global one included, sweeps l2_reg_weight itself (--l2_reg_weights) and
     reports its metric (a sweep needs the directory). None: the argv of every stage is what it was before the argument existed.
-    optimizer: the global stage's --optimizer (LBFGS | TRON; the random effect has one optimiser). None: no such flag in the argv.
+    optimizer: the global stage's --optimizer (LBFGS | TRON). None: no such flag in the argv.
+    entity_optimizer: the random-effect stages' --entity_optimizer (LBFGS | TRON). None: no such flag in the argv.
     evaluators: {stage: "LIST"} — a stage listed there gets --evaluators=LIST and reports its metric (the flag needs the directory)."""
     out = os.path.join(root, stage)
     common = [f"--model_type={model_type}"] + COMMON
     if optimizer is not None and stage == "global":
         common = common + [f"--optimizer={optimizer}"]
+    if entity_optimizer is not None and stage != "global":
+        common = common + [f"--entity_optimizer={entity_optimizer}"]
     grid = (l2_grids or {}).get(stage)
     listed = (evaluators or {}).get(stage)
     if (device_metrics and stage != "global") or grid is not None or listed is not None:
@@ -313,7 +316,7 @@ def poisson_loss(label, score):
 
 
 def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper_bounds=None, model_type=LOGISTIC, device_metrics=True, l2_grids=None,
-              optimizer=None, evaluators=None):
+              optimizer=None, evaluators=None, entity_optimizer=None):
     """global -> per_user -> per_movie under `root`; -> {stage: {"s", "partition_s", "train_auc", "validation_auc"}, "total_s"}.
     device_metrics: the two random-effect stages also report the metric they computed on the device while scoring
     ("train_<metric>_device", "validation_<metric>_device", from <root>/<stage>/metrics/evalSummary.json).
@@ -324,6 +327,7 @@ def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper
     l2_grids: {stage: "w0,w1,..."} — a stage listed there sweeps l2_reg_weight inside the stage (stage_argv); its result gains
     "l2_reg_weight" (the winner, from <root>/<stage>/metrics/sweep/evals.json) and the device metrics, the global stage's too.
     optimizer: passed to the global stage as --optimizer (stage_argv).
+    entity_optimizer: passed to the two random-effect stages as --entity_optimizer (stage_argv).
     evaluators: {stage: "LIST"}, passed to the stages listed as --evaluators (stage_argv)."""
     if model_type not in (LOGISTIC, LINEAR, POISSON):
         raise ValueError(f"model type {model_type!r}: the chain runs logistic_regression and linear_regression, and poisson_regression on count labels")
@@ -344,7 +348,7 @@ def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper
             t_part = time.perf_counter() - t
         t = time.perf_counter()
         swept = (l2_grids or {}).get(stage) is not None
-        run_stage(stage_argv(root, stage, model_type, device_metrics, l2_grids, optimizer, evaluators), child_process)
+        run_stage(stage_argv(root, stage, model_type, device_metrics, l2_grids, optimizer, evaluators, entity_optimizer), child_process)
         if stage == "global" and model_type in (LINEAR, POISSON):
             run_stage(global_training_scores_argv(root, model_type), child_process)
         dt = time.perf_counter() - t

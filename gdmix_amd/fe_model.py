@@ -114,6 +114,9 @@ class FixedLRParams(LRParams):
     # holds LOGISTIC_LOSS only, and the stage's evalSummary.json gains "logistic_loss" and "ll". Needs metric_output_dir and
     # --model_type=logistic_regression; does not run with l2_reg_weights.
     evaluators: Optional[str] = None
+    # the random-effect stage's flag (params.REParams). This stage's parser ignores flags it does not know, so the field exists to refuse
+    # TRON instead of training by L-BFGS in silence: the fixed effect's flag is --optimizer.
+    entity_optimizer: Optional[str] = None
 
     def evaluator_spec(self):
         """What --evaluators asks for (params.EvaluatorSpec), or None without the flag."""
@@ -136,6 +139,8 @@ class FixedLRParams(LRParams):
         super().__post_init__()
         self.l2_grid()      # a bad list is an error at parse time
         self.evaluator_spec()
+        if self.entity_optimizer is not None and str(self.entity_optimizer).strip().upper() != "LBFGS":
+            raise ValueError(f"--entity_optimizer={self.entity_optimizer}: the flag belongs to the random-effect stage (the fixed effect's is --optimizer)")
         from .downsample import check_rate
         try:
             self.down_sampling_rate = check_rate(self.down_sampling_rate)

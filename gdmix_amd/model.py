@@ -582,6 +582,10 @@ class RandomEffectLRLBFGSModel:
         mp = getattr(self, "model_params", None)
         return mp.elastic_net()[0] if getattr(mp, "elastic_net_alpha", None) else 0.0
 
+    def _entity_tron(self):
+        """Does the stage solve its entities by trust-region Newton (REParams.entity_optimizer)? False without the flag: the plain solve."""
+        return getattr(getattr(self, "model_params", None), "entity_optimizer", None) == "TRON"
+
     def _read_entity_bounds(self, num_features):
         """--entity_coefficient_constraints: the file, read once per stage -> (lower, upper) [num_features] by global feature id (the order
         of --feature_file). Without the flag nothing happens."""
@@ -1096,11 +1100,18 @@ class RandomEffectLRLBFGSModel:
         elif RandomEffectLRLBFGSModel._entity_bounds(self, solver) is not None:      # (REParams refuses it with every branch above)
             bounds = RandomEffectLRLBFGSModel._entity_bounds(self, solver)
             solve = lambda packed, opts, theta0=None: solver.solve(packed, opts, theta0=theta0, bounds=bounds)
+        elif RandomEffectLRLBFGSModel._entity_tron(self):      # (REParams refuses it with every branch above)
+            solve = solver.solve_tron
         else:
             solve = solver.solve
         packed = pack()
         solved = solve(packed, opts, theta0=theta0)
         res = solved.to_host(("theta_thr", "variance") + self._STAT_KEYS)
+        if RandomEffectLRLBFGSModel._entity_tron(self):
+            nhv, E = solved.nhv.cpu().numpy(), max(int(packed.E), 1)
+            ended = ", ".join(f"status {int(c)}: {int(k)}" for c, k in zip(*np.unique(res["status"], return_counts=True)))
+            logger.info(f"entity_optimizer TRON: {packed.E} entities, {res['nfev'].sum() / E:.2f} evaluations and {nhv.sum() / E:.2f} Hessian-vector "
+                        f"products per entity on average; {ended}")
         if (res["status"] == self.ST_ABORTED).any() and getattr(solver, "tall_team_n", 0) != 0:
             # a team of workgroups gave up waiting for a member (a device too busy, or too small, to keep four whole CUs per
             # team resident: csrc/re_solve_tall.hip). Not a reason to lose the job: the partition again with every tall

@@ -87,6 +87,24 @@ def check_elastic_net_alpha(p, stage_flags):
     return alpha
 
 
+ENTITY_OPTIMIZERS = ("LBFGS", "TRON")
+
+
+def check_entity_optimizer(p, stage_flags):
+    """--entity_optimizer of a random-effect stage's parameters: LBFGS or TRON in any case, and (for TRON) none of the stage's flags the
+    trust-region Newton solve does not run with, given as (set?, flag, why). -> "LBFGS" / "TRON", or None without the flag."""
+    if p.entity_optimizer is None:
+        return None
+    value = str(p.entity_optimizer).strip().upper()
+    if value not in ENTITY_OPTIMIZERS:
+        raise ValueError(f"--entity_optimizer={p.entity_optimizer!r}: one of {', '.join(ENTITY_OPTIMIZERS)}")
+    if value == "TRON":
+        for is_set, flag, why in stage_flags:
+            if is_set:
+                raise ValueError(f"--entity_optimizer=TRON does not run with {flag}: {why}")
+    return value
+
+
 def elastic_net_weights(alpha, lam):
     """Photon-ML's elastic net (alpha, lambda) -> (l1, l2) = (alpha lambda, (1 - alpha) lambda)."""
     alpha, lam = float(alpha), float(lam)
@@ -377,8 +395,7 @@ class REParams(LRParams):
     # the fixed-effect stage's flag (fe_model.FixedLRParams). This stage's parser ignores flags it does not know, so the field exists to
     # refuse a non-zero value instead of training a ridge model in silence.
     l1_reg_weight: float = 0.0
-    # ... and so is --optimizer: anything but LBFGS is refused. The random-effect kernels run scipy's L-BFGS-B loop on chip; a trust-region
-    # Newton solver inside them is another project.
+    # ... and so is --optimizer: anything but LBFGS is refused. The random effect's optimiser is chosen by --entity_optimizer (below).
     optimizer: str = "LBFGS"
     # ... and so is --coefficient_constraints: this stage's box constraints are --entity_coefficient_constraints (below).
     coefficient_constraints: Optional[str] = None
@@ -406,6 +423,14 @@ class REParams(LRParams):
     # follow-up, as in the fixed effect), l2_reg_weights or rebalance_entities. --action=inference accepts and ignores the flag: it does not
     # open the file. These refusals are made where the parameters are parsed, whatever the action, as --elastic_net_alpha's are.
     entity_coefficient_constraints: Optional[str] = None
+    # not in the reference (Photon-ML's OptimizerType per random-effect coordinate): LBFGS (the default, also when the flag is absent: the
+    # stage is byte for byte what it was) or TRON, any case: every entity minimises the stage's smooth objective by trust-region Newton on
+    # the device (include/gdmix_re.h, "TRON"). The stage has a flag of its own for the reason --elastic_net_alpha has: --optimizer is the
+    # fixed effect's, this stage's parser drops flags it does not know, and the field above refuses --optimizer=TRON; that refusal stays.
+    # Does not run with elastic_net_alpha > 0 or entity_coefficient_constraints (the objective must be smooth and unconstrained),
+    # incremental_training or a feature_normalization (both are changes of variables on the packed batch and compose in principle: a
+    # follow-up), l2_reg_weights or rebalance_entities. --action=inference accepts and ignores the flag.
+    entity_optimizer: Optional[str] = None
 
     def l2_grid(self):
         """The weights of --l2_reg_weights in the order given, or None without the flag."""
@@ -418,6 +443,10 @@ class REParams(LRParams):
     def evaluator_spec(self):
         """What --evaluators asks for (EvaluatorSpec), or None without the flag."""
         return check_evaluators(self, self.partition_entity)
+
+    def entity_tron(self):
+        """Does --entity_optimizer ask for the trust-region Newton solve?"""
+        return self.entity_optimizer == "TRON"
 
     def elastic_net(self):
         """(l1, l2) of the stage's solves: Photon-ML's (alpha, lambda) = (elastic_net_alpha, l2_reg_weight); (0, l2_reg_weight) without the flag."""
@@ -467,6 +496,13 @@ class REParams(LRParams):
                     (self.rebalance_entities, "--rebalance_entities", "the bounded solve of exchanged entities is not implemented")):
                 if is_set:
                     raise ValueError(f"{flag} does not run with {other}: {why}")
+        self.entity_optimizer = check_entity_optimizer(self, (
+            (bool(self.elastic_net_alpha), "--elastic_net_alpha", "TRON minimises a smooth objective; the L1 term has its own optimiser, OWL-QN"),
+            (self.entity_coefficient_constraints is not None, "--entity_coefficient_constraints", "TRON minimises without constraints"),
+            (self.incremental_training, "--incremental_training", "TRON under the substitution that centres the L2 term on the prior is not implemented"),
+            (self.feature_normalization not in (None, "none"), "--feature_normalization", "TRON under the diagonal substitution of the normalised units is not implemented"),
+            (self.l2_reg_weights is not None, "--l2_reg_weights", "a sweep of TRON solves is not implemented"),
+            (self.rebalance_entities, "--rebalance_entities", "the TRON solve of exchanged entities is not implemented")))
         if self.incremental_training and self.l2_reg_weights is not None:
             raise ValueError("--incremental_training does not run with --l2_reg_weights: the sweep is defined for a cold start")
         if self.incremental_training and self.rebalance_entities:

@@ -151,6 +151,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_abi_version", "gdmix_re_build_id", "gdmix_re_device_shared", "gdmix_re_grid_lock_acquire", "gdmix_re_grid_lock_release", "gdmix_re_grid_lock_stats", "gdmix_re_last_error", "gdmix_re_default_opts", "gdmix_re_create",
     "gdmix_re_destroy", "gdmix_re_pack_workspace_bytes", "gdmix_re_pack", "gdmix_re_set_defer_unique", "gdmix_re_pack_join", "gdmix_re_solve",
     "gdmix_re_solve_l1", "gdmix_re_solve_l1_scratch_bytes", "gdmix_re_solve_box", "gdmix_re_solve_box_scratch_bytes",
+    "gdmix_re_solve_tron", "gdmix_re_solve_tron_scratch_bytes",
     "gdmix_re_solve_scratch_bytes", "gdmix_re_set_scratch", "gdmix_re_variance_full", "gdmix_re_set_wave_lds_limit", "gdmix_re_score",
     "gdmix_re_widen_workspace_bytes", "gdmix_re_widen", "gdmix_re_set_timing", "gdmix_re_last_solve_ms", "gdmix_re_set_kernel_mask", "gdmix_re_set_giant_nnz", "gdmix_re_set_team_nnz", "gdmix_re_set_tall_min_n", "gdmix_re_set_tall_split_n", "gdmix_re_set_tall_team_n", "gdmix_re_set_tall_mid_n", "gdmix_re_set_spread", "gdmix_re_set_narrow",
     "gdmix_fe_create", "gdmix_fe_destroy", "gdmix_fe_eval", "gdmix_fe_reduce_buffer", "gdmix_fe_step", "gdmix_fe_step_async", "gdmix_fe_step_status", "gdmix_fe_solve", "gdmix_fe_result",
@@ -226,6 +227,9 @@ def load_library():
                                        C.POINTER(_Result), C.c_void_p]
     lib.gdmix_re_solve_box_scratch_bytes.argtypes = [C.POINTER(_Packed), C.POINTER(_Opts)]
     lib.gdmix_re_solve_box_scratch_bytes.restype = C.c_size_t
+    lib.gdmix_re_solve_tron.argtypes = [C.c_void_p, C.POINTER(_Packed), C.POINTER(_Opts), C.c_void_p, C.POINTER(_Result), C.c_void_p, C.c_void_p]
+    lib.gdmix_re_solve_tron_scratch_bytes.argtypes = [C.POINTER(_Packed), C.POINTER(_Opts)]
+    lib.gdmix_re_solve_tron_scratch_bytes.restype = C.c_size_t
     lib.gdmix_re_set_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.gdmix_re_set_wave_lds_limit.argtypes = [C.c_void_p, C.c_int]
     lib.gdmix_re_set_kernel_mask.argtypes = [C.c_void_p, C.c_int]
@@ -1086,12 +1090,49 @@ class REDeviceSolver:
                                            self._stream()), "gdmix_re_solve")
         return SolveResult(tensors, packed.E, packed.P)
 
+    def tron_scratch_bytes(self, packed: PackedBatch, opts: Optional[SolverOptions] = None) -> int:
+        """gdmix_re_solve_tron_scratch_bytes: the device scratch a solve_tron of this batch needs beyond the pack workspace."""
+        c_opts = (opts or SolverOptions()).to_c()
+        return int(self.lib.gdmix_re_solve_tron_scratch_bytes(C.byref(packed.c), C.byref(c_opts)))
+
+    @_serialised
+    def solve_tron(self, packed: PackedBatch, opts: Optional[SolverOptions] = None, theta0=None, out=None) -> SolveResult:
+        """The trust-region Newton solve (include/gdmix_re.h, "TRON"): the plain solve's objective, options (m is ignored) and results, and
+        `nhv`, the Hessian-vector products per entity ([E] int32 on the device), in the result's tensors."""
+        t = self.torch
+        opts = opts or SolverOptions()
+        if bool(opts.has_intercept) != packed.has_intercept:
+            raise GdmixReError("has_intercept of the options differs from the packed batch")
+        c_opts = opts.to_c()
+        need = self.lib.gdmix_re_solve_tron_scratch_bytes(C.byref(packed.c), C.byref(c_opts))
+        if need > packed.c.scratch_bytes and (self._scratch is None or self._scratch.numel() < need):
+            self._scratch = t.empty(need, dtype=t.uint8, device=self.device)
+        if self._scratch is not None:
+            _check(self.lib.gdmix_re_set_scratch(self._h, self._scratch.data_ptr(), self._scratch.numel()), "set_scratch")
+        if theta0 is not None:
+            if isinstance(theta0, np.ndarray):
+                theta0 = t.from_numpy(np.ascontiguousarray(theta0, np.float64)).to(self.device)
+            elif not theta0.is_cuda:
+                theta0 = theta0.to(self.device, non_blocking=theta0.is_pinned())
+            if theta0.numel() != packed.P or theta0.dtype != t.float64:
+                raise GdmixReError("theta0 must be float64 with one entry per coefficient")
+        tensors = out or self.alloc_result(packed, variance=c_opts.variance_mode != VAR_NONE)
+        if tensors.get("nhv") is None:
+            tensors["nhv"] = t.zeros(packed.E, dtype=t.int32, device=self.device)
+        p = lambda x: None if x is None else x.data_ptr()
+        c_res = _Result(p(tensors["theta"]), p(tensors["theta_thr"]), p(tensors.get("variance")), p(tensors["fval"]),
+                        p(tensors["gnorm"]), p(tensors["nit"]), p(tensors["nfev"]), p(tensors["status"]))
+        _check(self.lib.gdmix_re_solve_tron(self._h, C.byref(packed.c), C.byref(c_opts), p(theta0), C.byref(c_res), p(tensors["nhv"]),
+                                            self._stream()), "gdmix_re_solve_tron")
+        return SolveResult(tensors, packed.E, packed.P)
+
     def l1_counts(self, packed: PackedBatch):
         """(entities the wavefront kernel took, entities the workgroup kernel took) of the last elastic-net solve on this batch."""
         cc = packed._view(packed.c.class_count, 2, self.torch.int32).cpu().numpy()
         return int(cc[0]), int(cc[1])
 
     box_counts = l1_counts      # ... or of the last box-constrained solve: the routing and its record are one
+    tron_counts = l1_counts     # ... or of the last TRON solve: its routing keeps the two counts in the same words
 
     def upload_bounds(self, lower, upper):
         """Host arrays [num_features] by global feature id -> the (lower, upper) device pair solve(bounds=...) takes."""

@@ -382,6 +382,54 @@ GDMIX_API int gdmix_re_solve_box(gdmix_re_ctx* ctx, const gdmix_re_packed* batch
                                  const double* upper, int64_t num_features, const double* theta0, const gdmix_re_result* out, void* stream);
 GDMIX_API size_t gdmix_re_solve_box_scratch_bytes(const gdmix_re_packed* batch, const gdmix_re_opts* opts);
 
+/* ---- TRON: per-entity models by trust-region Newton on the device (no ABI bump: two new symbols, nothing else moves) ----
+ * --entity_optimizer=TRON (gdmix_amd/params.py, REParams; Photon-ML's OptimizerType = TRON per random-effect coordinate). For one entity of n
+ * samples, in the conventions of gdmix_re_opts (theta in local index space, the intercept first, everything divided by n):
+ *     F(theta) = (1/n) ( sum_i w_i l(y_i, x_i . theta + offset_i) + (l2/2) |theta_R|^2 )
+ * l any of the three losses (opts->loss), l2 = opts->l2, R the set l2 regularises: every feature, and the intercept iff regularize_bias. This
+ * is gdmix_re_solve's objective, scaling and regularised set.
+ * The algorithm is the section "(ABI 24) TRON" of include/gdmix_fe.h, applied to this F, per entity: Delta = |g|_2 at the start; Steihaug CG
+ * with the boundary root in its cancellation-free form; |r - alpha Hd|^2 = r'r - 2 alpha r'Hd + alpha^2 |Hd|^2, clamped at 0; CG ends at
+ * |r| <= 0.1 |g| or after GDMIX_FE_TRON_MAX_CG = 50 products in an outer iteration; eta = (1e-4, 0.25, 0.75), sigma = (0.25, 0.5, 4); every
+ * trial before the first accepted step clamps Delta to |s|; a trial is accepted iff actred > 1e-4 prered. The stops, in that section's
+ * order, with this solver's status codes: after an accepted step |g|_inf <= pgtol -> 0; f_old - f <= ftol max(|f_old|, |f|, 1) -> 1;
+ * nit >= max_iter -> 2; nfev > maxfun -> 3; after a rejected trial nfev > maxfun -> 3; maxls (20 by default) rejected trials in a row -> 4,
+ * at the accepted point. What differs from that section, and only this: every term carries the 1/n, R is the set above, and the intercept
+ * is coefficient 0 of the entity, not the last one:
+ *     H v = (1/n) ( X~' (D o X~ v) + l2 v_R ),   D_i = w_i rho_i (1 - rho_i) | 2 w_i | w_i exp(z_i)   (logistic | squared | Poisson)
+ * with D taken at the accepted point: an evaluation leaves the trial point's D beside the residual in an array of its own, acceptance
+ * exchanges the two arrays, and a rejected trial leaves the accepted point's D in force. A product is a row pass t_i = D_i (x_i . v) over
+ * the entity's CSR copy and a column pass h_j = sum_i t_i x_ij over its CSC copy: no exp, no log, no reciprocal. max_iter, maxfun, maxls,
+ * ftol and pgtol are those of gdmix_re_opts; m is ignored (there is no history); gdmix_re_opts does not grow.
+ * Order of the sums. A row's x_i . v runs over the row's CSR entries in storage order, from the intercept's term; a column's sum runs over
+ * its CSC entries in storage order. Of the NT threads that share an entity (64, or 256 in the workgroup kernel), thread t adds the samples
+ * (coefficients) t, t + NT, ... in that order; the 64 lanes of a wavefront are added by one fixed tree, a workgroup's four wavefronts in
+ * wavefront order. No atomics. A result therefore depends on the entity's own data, the options and the kernel that solves it, never on
+ * where in the batch the entity sits or on how many entities the batch has.
+ * Results: theta is the last accepted point, never a rejected trial; theta_thr is that point thresholded as by gdmix_re_solve; fval = F,
+ * gnorm = |g|_inf; nit counts accepted iterations, nfev evaluations only, nhv ([E] int32, device, may be NULL) products. Variances are at the
+ * returned theta — SIMPLE inside the solve kernels, from the D the solve holds (variance_simple's arithmetic, no second pass over exp), FULL
+ * by gdmix_re_variance_full. theta0 is the start point (NULL: zeros), as in gdmix_re_solve.
+ * gdmix_re_solve_tron refuses with GDMIX_RE_EINVAL: a NULL ctx, batch, opts or out; sum_loss != 0 (the fixed effect's TRON is
+ *   gdmix_fe_set_optimizer); a loss code outside the three; max_iter < 0 or maxls < 1; variance outputs missing as for gdmix_re_solve. An
+ *   empty batch returns right behind the argument checks.
+ * Routing is the elastic net's shape: the size classes are not involved. An entity is solved by re_tron_wave_kernel — one wavefront, the
+ *   entity's block and the whole solver state in LDS — iff its TRON LDS footprint is within the context's wave_lds_limit
+ *   (gdmix_re_set_wave_lds_limit; 0: no entity), and otherwise, whatever its size, by re_tron_block_kernel: one workgroup per entity, the
+ *   state in a global scratch slot per workgroup (7 max_p + 3 max_n + 8 doubles), X streamed. The footprint is the plain wavefront kernel's
+ *   without its 2 m p + 2 m doubles of history, plus two coefficient vectors and two sample vectors:
+ *   8 (7 p + 3 n) + 4 (4 nnz + (n + 1) + (d + 1) + (2 | 3) n) bytes, rounded up to 16 (seven coefficient vectors x g xt gt s r d — Hd lives
+ *   in gt —, the residuals / t, and D of the accepted and of the trial point). One kernel writes the two lists into the batch's solver-owned
+ *   `order`; after the call the first two words of class_count hold their lengths (a later solve overwrites the record). The wavefront
+ *   kernel's entities within 20 KB are launched apart from the others, with that much LDS (eight one-wavefront workgroups per CU; their list
+ *   is in the solver-owned cls_tmp). Limits: one workgroup per large entity (no size-class, tall, team or device-wide variants); no L1 term,
+ *   no box, no prior, no normalisation, no l2 sweep and no re-balancing compose with it on the host (gdmix_amd/params.py).
+ * gdmix_re_solve_tron_scratch_bytes: device scratch the call needs beyond the pack workspace (gdmix_re_set_scratch), never less than
+ *   gdmix_re_solve_scratch_bytes of the same arguments. With less, the workgroup kernel runs on as many slots as fit (at least one). */
+GDMIX_API int gdmix_re_solve_tron(gdmix_re_ctx* ctx, const gdmix_re_packed* batch, const gdmix_re_opts* opts, const double* theta0,
+                                  const gdmix_re_result* out, int32_t* nhv, void* stream);
+GDMIX_API size_t gdmix_re_solve_tron_scratch_bytes(const gdmix_re_packed* batch, const gdmix_re_opts* opts);
+
 /* Score: logit[i] = x_i . theta_e + offset[i] (fp64 accumulate, stored fp32 as the score Avro
  * does, io_utils.py:367-375), logit_per_coord[i] = logit[i] - offset[i] (job_consumers.py:145-150).
  * has_model: [E] uint8, 0 => entity has no model and logit = offset (job_consumers.py:145-146);
