@@ -18,7 +18,7 @@
 
 #include <mutex>
 
-#include "re_internal.hpp"
+#include "re_entity_scaffold.hpp"
 #include "re_solve_team.hpp"
 
 namespace gdmix {
@@ -507,14 +507,7 @@ GDMIX_API int gdmix_re_pack_join(gdmix_re_ctx* ctx, void* stream) {
 
 static int slots_for(const gdmix_re_packed* b, const gdmix_re_opts* o, size_t* slot_doubles) {
   *slot_doubles = block_slot_doubles(b->max_p, b->max_n, o->m);
-  // enough workgroups to fill the chip a few times over, bounded to ~4 GiB of scratch
-  size_t bytes = *slot_doubles * 8;
-  size_t by_budget = ((size_t)4 << 30) / (bytes ? bytes : 1);
-  size_t slots = 1024;
-  if (slots > by_budget) slots = by_budget;
-  if (slots < 8) slots = 8;
-  if ((int64_t)slots > b->E) slots = (size_t)(b->E > 0 ? b->E : 1);
-  return (int)slots;
+  return block_slots(*slot_doubles, b->E);
 }
 
 static int64_t var_small_p(const gdmix_re_packed* b) { return b->max_p < VAR_FULL_MAX_P ? b->max_p : VAR_FULL_MAX_P; }

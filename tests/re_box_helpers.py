@@ -225,7 +225,7 @@ def warm_start(theta_ref):
 
 
 def lds_bytes(p, n, nnz, d, m, has_w):
-    """The bounded step's LDS footprint of an entity (csrc/re_owlqn.hip, owlqn_lds_bytes with seven coefficient vectors): the plain wavefront
+    """The bounded step's LDS footprint of an entity (csrc/re_entity_scaffold.hpp, solver_lds_bytes with seven coefficient vectors): the plain wavefront
     kernel's (csrc/re_internal.hpp, wave_lds_bytes) plus two coefficient vectors, each rounded up to 16 bytes."""
     dbl = (5 + 2 * m) * p + n + 2 * m
     w32 = 4 * nnz + (n + 1) + (d + 1) + (3 if has_w else 2) * n

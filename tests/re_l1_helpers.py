@@ -347,7 +347,7 @@ def first_iteration(pb, theta0, m=10, **kw):
 
 
 def lds_bytes(p, n, nnz, d, m, has_w):
-    """The OWL-QN LDS footprint of an entity (csrc/re_owlqn.hip, owlqn_lds_bytes): the plain wavefront kernel's (csrc/re_internal.hpp,
+    """The OWL-QN LDS footprint of an entity (csrc/re_entity_scaffold.hpp, solver_lds_bytes with six coefficient vectors): the plain wavefront kernel's (csrc/re_internal.hpp,
     wave_lds_bytes) plus one coefficient vector, each rounded up to 16 bytes."""
     dbl = (5 + 2 * m) * p + n + 2 * m
     w32 = 4 * nnz + (n + 1) + (d + 1) + (3 if has_w else 2) * n

@@ -203,14 +203,14 @@ def compare(res, pbs, rest, refs, cp, distance=True, tight=True, what="", min_st
 
 
 def lds_bytes(p, n, nnz, d, has_w):
-    """The TRON LDS footprint of an entity (csrc/re_tron.hip, tron_lds_bytes): the plain wavefront kernel's without history (five
+    """The TRON LDS footprint of an entity (csrc/re_entity_scaffold.hpp, solver_lds_bytes at m = 0): the plain wavefront kernel's without history (five
     coefficient vectors, one sample vector, the staged block) plus two coefficient vectors and two sample vectors, each rounded up to 16."""
     w32 = 4 * nnz + (n + 1) + (d + 1) + (3 if has_w else 2) * n
     plain = ((5 * p + n) * 8 + w32 * 4 + 15) & ~15
     return (plain + 8 * (2 * p + 2 * n) + 15) & ~15
 
 
-SMALL_LDS = 20 * 1024      # csrc/re_tron.hip, TRON_SMALL_LDS: the wavefront kernel's entities within it are launched apart
+SMALL_LDS = 20 * 1024      # csrc/re_entity_scaffold.hpp, WAVE_SMALL_LDS: the wavefront kernel's entities within it are launched apart
 
 
 def first_branch(pb, theta0=None):

@@ -19,11 +19,11 @@ import numpy as np
 
 BAR = 1.05
 CU_LDS = 160 * 1024
-SMALL_LDS = 20 * 1024      # csrc/re_tron.hip, TRON_SMALL_LDS (and csrc/re_owlqn.hip, OWL_SMALL_LDS)
+SMALL_LDS = 20 * 1024      # csrc/re_entity_scaffold.hpp, WAVE_SMALL_LDS
 
 
 def footprints(batch, packed, m):
-    """(TRON, plain wavefront kernel) LDS bytes per entity: csrc/re_tron.hip tron_lds_bytes, csrc/re_internal.hpp wave_lds_bytes."""
+    """(TRON, plain wavefront kernel) LDS bytes per entity: csrc/re_entity_scaffold.hpp solver_lds_bytes, csrc/re_internal.hpp wave_lds_bytes."""
     n = np.diff(np.asarray(batch.ent_row_ptr))
     z = np.diff(packed.ent_nnz_ptr().cpu().numpy())
     d = np.diff(packed.ent_feat_ptr().cpu().numpy())
