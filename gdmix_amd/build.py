@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgdmix_re.so")
-SOURCES = ["re_api.hip", "re_route.hip", "re_solve.hip", "re_owlqn.hip", "re_tron.hip", "re_solve_tall.hip", "re_pack.hip", "re_pack_big.hip", "re_wire.hip", "re_variance_big.hip", "re_evaluate.hip", "re_evaluate_poisson.hip", "re_sweep.hip", "re_prior.hip", "re_downsample.hip", "re_cap.hip", "re_group.hip", "re_select.hip", "feature_stats.hip", "fe_solve.hip", "fe_copy.hip", "fe_sweep.hip", "fe_qn.hip", "fe_tron.hip"]
+SOURCES = ["re_api.hip", "re_route.hip", "re_solve.hip", "re_owlqn.hip", "re_tron.hip", "re_tron_rows.hip", "re_solve_tall.hip", "re_pack.hip", "re_pack_big.hip", "re_wire.hip", "re_variance_big.hip", "re_evaluate.hip", "re_evaluate_poisson.hip", "re_sweep.hip", "re_prior.hip", "re_downsample.hip", "re_cap.hip", "re_group.hip", "re_select.hip", "feature_stats.hip", "fe_solve.hip", "fe_copy.hip", "fe_sweep.hip", "fe_qn.hip", "fe_tron.hip"]
 IO_LIB = os.path.join(HERE, "libgdmix_io.so")
 IO_SOURCES = ["io_reader.cpp", "io_avro.cpp"]
 IO_HEADERS = [os.path.join("..", "..", "include", "gdmix_io.h")]
@@ -23,6 +23,12 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # main loop, where they stay live in VGPRs across the whole solve and cost a wave of occupancy.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-mllvm", "-disable-machine-licm"]
+# Flags of single units, behind FLAGS. re_tron_rows.hip is compiled with the packed fp32 instructions (v_pk_add_f32 and kin) switched off:
+# a guard, not a speed-up. Its kernel owes the bits of re_tron_wave_kernel and has no fp32 arithmetic but conversions to fp64, so the
+# packed forms are taken away from the compiler. Measured to cost nothing (profiles/re_tron_rows.txt: same time, same registers, no v_pk_*
+# either way). The same switch changes the instructions of the older kernels, so they keep the flags they were measured and compared
+# with; tools/asm_compare.py compiles every unit with these flags too.
+UNIT_FLAGS = {"re_tron_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def kernel_source_hash():
@@ -69,7 +75,8 @@ def flags_id(extra=None):
     only — an A/B build of the same sources with other flags is still a build of these sources for the loader."""
     import hashlib
     extra = os.environ.get("GDMIX_EXTRA_FLAGS", "").split() if extra is None else extra
-    return hashlib.sha256(" ".join(FLAGS + extra).encode()).hexdigest()[:16]
+    per_unit = [f"{u}:{' '.join(f)}" for u, f in sorted(UNIT_FLAGS.items())]
+    return hashlib.sha256(" ".join(FLAGS + extra + per_unit).encode()).hexdigest()[:16]
 
 
 def _headers():
@@ -142,10 +149,11 @@ def build_library(force=False, verbose=False, out=None):
 
     def compile_one(f):
         src, obj = os.path.join(CSRC, f), os.path.join(objdir, f + ".o")
-        key = _object_key(src, flags, headers)
+        unit_flags = flags + UNIT_FLAGS.get(f, [])
+        key = _object_key(src, unit_flags, headers)
         if not force and os.path.exists(obj) and os.path.exists(obj + ".key") and open(obj + ".key").read() == key:
             return obj
-        cmd = [HIPCC] + flags + ["-c", src, "-o", obj]
+        cmd = [HIPCC] + unit_flags + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)

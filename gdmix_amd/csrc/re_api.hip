@@ -373,6 +373,7 @@ GDMIX_API int gdmix_re_create(int hip_device, gdmix_re_ctx** out) {
   c->impl.scratch_bytes = 0;
   c->impl.host_pinned = nullptr;
   c->impl.wave_lds_limit = 65536;
+  c->impl.tron_row_lds_limit = GDMIX_RE_TRON_ROW_LDS_DEFAULT;
   c->impl.kernel_mask = 7;
   c->impl.timing = 0;
   c->impl.giant_nnz = 16777216;
@@ -540,6 +541,13 @@ GDMIX_API size_t gdmix_re_solve_scratch_bytes(const gdmix_re_packed* batch, cons
 GDMIX_API int gdmix_re_set_wave_lds_limit(gdmix_re_ctx* ctx, int bytes) {
   if (!ctx || bytes < 0) { set_error("bad argument"); return GDMIX_RE_EINVAL; }
   ctx->impl.wave_lds_limit = bytes > 65536 ? 65536 : bytes;
+  return GDMIX_RE_OK;
+}
+
+GDMIX_API int gdmix_re_set_tron_row_lds_limit(gdmix_re_ctx* ctx, int nbytes) {
+  if (!ctx) { set_error("ctx is NULL"); return GDMIX_RE_EINVAL; }
+  if (nbytes < 0 || nbytes > WAVE_SMALL_LDS) { set_error("gdmix_re_set_tron_row_lds_limit: %d is outside [0, 20480]", nbytes); return GDMIX_RE_EINVAL; }
+  ctx->impl.tron_row_lds_limit = nbytes;
   return GDMIX_RE_OK;
 }
 

@@ -338,6 +338,8 @@ struct gdmix_ctx_impl {
   int cap_small_set, cap_small_max;
   const void* cap_plan_ws;
   int64_t cap_plan_rows, cap_plan_entities, cap_plan_bound, cap_plan_kept, cap_plan_nnz;
+  // TRON (re_tron.hip): entities whose TRON footprint is within this go four to a wavefront (gdmix_re_set_tron_row_lds_limit; 0: none)
+  int tron_row_lds_limit;
 };
 
 // A few bytes from the device to the host WITHOUT a stream synchronise (round 5). The counts a pack or a solve decides its next

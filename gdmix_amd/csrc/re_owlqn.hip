@@ -34,16 +34,20 @@ static_assert(BOX_BAD_NAN == LDS_COUNT_WORDS && BOX_BAD_ID < LDS_READBACK_WORDS,
 // wave_lds_limit, else to the workgroup kernel. The wavefront kernel's large entities fill `order` from the front, the workgroup
 // kernel's from the back; the wavefront kernel's small entities (WAVE_SMALL_LDS) are a list of their own in `small` (the batch's
 // cls_tmp, solver-owned like `order`). Position inside a list is by ticket (per workgroup: LDS counters, then one global atomic per
-// list): no entity's result depends on it.
+// list): no entity's result depends on it. row_lds > 0 (TRON): the small entities within row_lds bytes are the row kernel's, a fourth
+// list at the back end of `small`; they count in words 0 and 4 as the other small entities do, and in the row words behind them
+// (re_entity_scaffold.hpp, ROWS_*), which the kernel leaves alone under row_lds == 0.
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void re_lds_route_kernel(const int64_t* __restrict__ ent_row_ptr, const int64_t* __restrict__ ent_nnz_ptr,
                                                            const int64_t* __restrict__ ent_feat_ptr, int64_t E, int ic, bool has_w, int p_vectors,
-                                                           int n_vectors, int m, int wave_lds_limit, int small_lds, int32_t* __restrict__ order,
-                                                           int32_t* __restrict__ small, int32_t* __restrict__ counts) {
-  __shared__ int32_t cnt[3], base[3], lds_max;   // lists: 0 wavefront kernel, small; 1 workgroup kernel; 2 wavefront kernel, large
+                                                           int n_vectors, int m, int wave_lds_limit, int small_lds, int row_lds,
+                                                           int32_t* __restrict__ order, int32_t* __restrict__ small, int32_t* __restrict__ counts) {
+  // lists: 0 wavefront kernel, small; 1 workgroup kernel; 2 wavefront kernel, large; 3 row kernel (small too)
+  __shared__ int32_t cnt[4], base[4], lds_max, row_max;
   for (int64_t start = (int64_t)blockIdx.x * blockDim.x; start < E; start += (int64_t)gridDim.x * blockDim.x) {
-    if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
-    if (threadIdx.x == 3) lds_max = 0;
+    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
+    if (threadIdx.x == 4) lds_max = 0;
+    if (threadIdx.x == 5) row_max = 0;
     __syncthreads();
     const int64_t e = start + threadIdx.x;
     int which = -1, pos = 0;
@@ -52,27 +56,37 @@ __global__ __launch_bounds__(256) void re_lds_route_kernel(const int64_t* __rest
       const int z = (int)(ent_nnz_ptr[e + 1] - ent_nnz_ptr[e]);
       const int d = (int)(ent_feat_ptr[e + 1] - ent_feat_ptr[e]);
       const size_t bytes = solver_lds_bytes(p_vectors, n_vectors, d + ic, n, z, d, m, has_w);
-      which = bytes > (size_t)wave_lds_limit ? 1 : (bytes <= (size_t)small_lds ? 0 : 2);
+      which = bytes > (size_t)wave_lds_limit ? 1 : (bytes <= (size_t)small_lds ? (bytes <= (size_t)row_lds ? 3 : 0) : 2);
       pos = atomicAdd(&cnt[which], 1);
       if (which == 2) atomicMax(&lds_max, (int32_t)bytes);
+      if (which == 3) atomicMax(&row_max, (int32_t)bytes);
     }
     __syncthreads();
-    if (threadIdx.x == 0) base[0] = cnt[0] ? atomicAdd(&counts[LDS_COUNT_WAVE_SMALL], cnt[0]) : 0;
+    if (row_lds <= 0) {
+      if (threadIdx.x == 0) base[0] = cnt[0] ? atomicAdd(&counts[LDS_COUNT_WAVE_SMALL], cnt[0]) : 0;
+    } else {   // word 4 counts the row kernel's entities too: the others' places come from a ticket word of their own
+      if (threadIdx.x == 0) base[0] = cnt[0] ? atomicAdd(&counts[ROWS_REST_TICKET], cnt[0]) : 0;
+      if (threadIdx.x == 5) base[3] = cnt[3] ? atomicAdd(&counts[ROWS_COUNT], cnt[3]) : 0;
+      if (threadIdx.x == 6 && cnt[0] + cnt[3] > 0) atomicAdd(&counts[LDS_COUNT_WAVE_SMALL], cnt[0] + cnt[3]);
+      if (threadIdx.x == 7 && row_max > 0) atomicMax(&counts[ROWS_MAX_LDS], row_max);
+    }
     if (threadIdx.x == 1) base[1] = cnt[1] ? atomicAdd(&counts[LDS_COUNT_BLOCK], cnt[1]) : 0;
     if (threadIdx.x == 2) base[2] = cnt[2] ? atomicAdd(&counts[LDS_COUNT_WAVE_LARGE], cnt[2]) : 0;
-    if (threadIdx.x == 3 && cnt[0] + cnt[2] > 0) atomicAdd(&counts[LDS_COUNT_WAVE], cnt[0] + cnt[2]);
+    if (threadIdx.x == 3 && cnt[0] + cnt[2] + cnt[3] > 0) atomicAdd(&counts[LDS_COUNT_WAVE], cnt[0] + cnt[2] + cnt[3]);
     if (threadIdx.x == 4 && lds_max > 0) atomicMax(&counts[LDS_MAX_WAVE_LDS], lds_max);
     __syncthreads();
     if (which == 0) small[base[0] + pos] = (int32_t)e;
+    else if (which == 3) small[E - 1 - (base[3] + pos)] = (int32_t)e;
     else if (which == 2) order[base[2] + pos] = (int32_t)e;
     else if (which == 1) order[E - 1 - (base[1] + pos)] = (int32_t)e;
     __syncthreads();
   }
 }
 
-hipError_t launch_lds_route(const gdmix_re_packed* b, int ic, int p_vectors, int n_vectors, int m, int wave_lds_limit, int small_lds, hipStream_t s) {
+hipError_t launch_lds_route(const gdmix_re_packed* b, int ic, int p_vectors, int n_vectors, int m, int wave_lds_limit, int small_lds, int row_lds,
+                            hipStream_t s) {
   hipLaunchKernelGGL(re_lds_route_kernel, dim3(grid_for(b->E, 256, 2048)), dim3(256), 0, s, b->ent_row_ptr, b->ent_nnz_ptr, b->ent_feat_ptr, b->E, ic,
-                     b->weight != nullptr, p_vectors, n_vectors, m, wave_lds_limit, small_lds, b->order, b->cls_tmp, b->class_count);
+                     b->weight != nullptr, p_vectors, n_vectors, m, wave_lds_limit, small_lds, row_lds, b->order, b->cls_tmp, b->class_count);
   return hipGetLastError();
 }
 

@@ -2,6 +2,8 @@
 //
 //   (re_owlqn.hip: re_lds_route_kernel, here with the TRON LDS footprint; re_entity_scaffold.hpp: the footprint, the count words and
 //    the host driver, solve_three_lists, shared with the elastic net and the box solve)
+//   (re_tron_rows.hip: re_tron_rows_kernel, FOUR ENTITIES PER WAVEFRONT, for the entities within the context's TRON row limit; a unit
+//    of its own because it is compiled with the packed fp32 instructions switched off, which would change the kernels here: build.UNIT_FLAGS)
 //   re_tron_wave_kernel        ONE WAVEFRONT PER ENTITY: the entity's block and all solver state live in LDS for the whole solve
 //   re_tron_block_kernel       one workgroup per entity, state in a global scratch slot per workgroup, X streamed, grid-stride
 //   gdmix_re_solve_tron, gdmix_re_solve_tron_scratch_bytes
@@ -14,6 +16,9 @@
 #include "re_tron.hpp"
 
 namespace gdmix {
+
+// re_tron_rows_kernel<a.P.loss> on list[0, count) (re_tron_rows.hip)
+hipError_t launch_tron_rows(const ListsArgs& a, int32_t* nhv, const int32_t* list, int count, int row_bytes, hipStream_t s);
 
 // doubles of global scratch one slot of the workgroup kernel needs: the coefficient vectors | the sample vectors | a few words
 inline size_t tron_slot_doubles(int64_t max_p, int64_t max_n) { return (size_t)TRON_P_VECTORS * max_p + (size_t)TRON_N_VECTORS * max_n + 8; }
@@ -169,6 +174,8 @@ struct TronLists {
       return hipGetLastError();
     });
   }
+  // the row kernel on list[0, count): four entities a wavefront, row_bytes of LDS each
+  hipError_t launch_rows(const int32_t* list, int count, int row_bytes, hipStream_t s) const { return launch_tron_rows(a, nhv, list, count, row_bytes, s); }
   hipError_t launch_block(int64_t last, int count, double* scratch, size_t slot_doubles, int slots, hipStream_t s) const {
     if (count <= 0) return hipSuccess;
     const int grid = count < slots ? count : slots;

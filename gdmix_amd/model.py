@@ -1110,8 +1110,10 @@ class RandomEffectLRLBFGSModel:
         if RandomEffectLRLBFGSModel._entity_tron(self):
             nhv, E = solved.nhv.cpu().numpy(), max(int(packed.E), 1)
             ended = ", ".join(f"status {int(c)}: {int(k)}" for c, k in zip(*np.unique(res["status"], return_counts=True)))
-            logger.info(f"entity_optimizer TRON: {packed.E} entities, {res['nfev'].sum() / E:.2f} evaluations and {nhv.sum() / E:.2f} Hessian-vector "
-                        f"products per entity on average; {ended}")
+            # (the host tests' solver stand-in, tests/helpers.OracleSolverDouble, has no count record: the clause is left out there, never a 0)
+            rows = f" ({solver.tron_row_count(packed)} four to a wavefront on the row kernel)" if hasattr(solver, "tron_row_count") else ""
+            logger.info(f"entity_optimizer TRON: {packed.E} entities{rows}, {res['nfev'].sum() / E:.2f} evaluations "
+                        f"and {nhv.sum() / E:.2f} Hessian-vector products per entity on average; {ended}")
         if (res["status"] == self.ST_ABORTED).any() and getattr(solver, "tall_team_n", 0) != 0:
             # a team of workgroups gave up waiting for a member (a device too busy, or too small, to keep four whole CUs per
             # team resident: csrc/re_solve_tall.hip). Not a reason to lose the job: the partition again with every tall

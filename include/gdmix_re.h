@@ -424,11 +424,29 @@ GDMIX_API size_t gdmix_re_solve_box_scratch_bytes(const gdmix_re_packed* batch, 
  *   kernel's entities within 20 KB are launched apart from the others, with that much LDS (eight one-wavefront workgroups per CU; their list
  *   is in the solver-owned cls_tmp). Limits: one workgroup per large entity (no size-class, tall, team or device-wide variants); no L1 term,
  *   no box, no prior, no normalisation, no l2 sweep and no re-balancing compose with it on the host (gdmix_amd/params.py).
+ * Small entities: four per wavefront. An entity whose footprint is within min(the TRON row limit, wave_lds_limit, 20 KB) is solved by
+ *   re_tron_rows_kernel: each DPP row of 16 lanes solves one entity in an LDS block of its own with the carve-up above, sample i and
+ *   coefficient j on lane i mod 16 and j mod 16 of the row, the rows of a wavefront advancing independently, one pass pair (an evaluation
+ *   or a product, whichever the row needs) per trip for all four. The launch's LDS is four times the largest such footprint of the batch.
+ *   These entities count in words 0 and 4 of class_count like every entity of the small launch; words 5 and 6 hold their number and their
+ *   largest footprint, word 7 a ticket counter (TRON's words: the route kernel writes none of the three under a row limit of 0). Their list
+ *   is the back end of cls_tmp. Order of the row kernel's sums: the wavefront kernel's. Lane l of a row keeps four partials, the k-th for the
+ *   elements l + 16 k, l + 16 k + 64, ... — what lane 16 k + l of the wavefront kernel adds —, each is summed over the row by a butterfly
+ *   that is the wavefront tree's row stage (pairs, quads, halves, the row), and the four sums are added as (k3 + k2) + (k1 + k0), that
+ *   tree's last two stages. An entity's results are therefore the same bits on either kernel, in whichever row and next to whichever
+ *   neighbours, and gdmix_re_set_tron_row_lds_limit changes the time of a solve and no bit of it.
+ * gdmix_re_set_tron_row_lds_limit: the TRON row limit in bytes, GDMIX_RE_TRON_ROW_LDS_DEFAULT by default (6 KB, the fastest of 6, 8 and 10 KB on the
+ *   C2-shaped batch, profiles/re_tron_rows.txt: four rows are 24 KB a wavefront, six wavefronts or 24 entities per CU of 160 KB, where the
+ *   small wavefront launch holds 8; on that batch no setting was faster than 0). 0 turns the row kernel off: the
+ *   routing, the launches and the lists of the library before it. Refused with GDMIX_RE_EINVAL: a NULL ctx, a negative value, a value above
+ *   20 KB (20480: no entity above the small launch's LDS is a row entity).
  * gdmix_re_solve_tron_scratch_bytes: device scratch the call needs beyond the pack workspace (gdmix_re_set_scratch), never less than
  *   gdmix_re_solve_scratch_bytes of the same arguments. With less, the workgroup kernel runs on as many slots as fit (at least one). */
 GDMIX_API int gdmix_re_solve_tron(gdmix_re_ctx* ctx, const gdmix_re_packed* batch, const gdmix_re_opts* opts, const double* theta0,
                                   const gdmix_re_result* out, int32_t* nhv, void* stream);
 GDMIX_API size_t gdmix_re_solve_tron_scratch_bytes(const gdmix_re_packed* batch, const gdmix_re_opts* opts);
+#define GDMIX_RE_TRON_ROW_LDS_DEFAULT 6144
+GDMIX_API int gdmix_re_set_tron_row_lds_limit(gdmix_re_ctx* ctx, int nbytes);
 
 /* Score: logit[i] = x_i . theta_e + offset[i] (fp64 accumulate, stored fp32 as the score Avro
  * does, io_utils.py:367-375), logit_per_coord[i] = logit[i] - offset[i] (job_consumers.py:145-150).

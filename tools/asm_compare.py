@@ -34,7 +34,8 @@ def compile_units(csrc, out):
 
     def one(f):
         dst = os.path.join(out, f + ".s")
-        subprocess.run([build.HIPCC] + flags + ["--cuda-device-only", "-S", os.path.join(csrc, f), "-o", dst], check=True, stderr=subprocess.DEVNULL)
+        unit_flags = flags + getattr(build, "UNIT_FLAGS", {}).get(f, [])      # (what build_library compiles the unit with)
+        subprocess.run([build.HIPCC] + unit_flags + ["--cuda-device-only", "-S", os.path.join(csrc, f), "-o", dst], check=True, stderr=subprocess.DEVNULL)
         return dst
     units = [f for f in build.SOURCES if os.path.exists(os.path.join(csrc, f))]
     with ThreadPoolExecutor(len(units)) as ex:

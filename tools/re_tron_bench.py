@@ -10,7 +10,16 @@ kernel's ms per evaluation in this same run, the parent's kernel: TRON's ms per 
 strict subset of an evaluation's work on the same staged block, and 1.05 is the margin the fixed effect's product was given against its
 evaluation. Total time against the group kernels is reported, not barred. Also reported: the LDS per workgroup of the TRON wavefront
 launches and of the plain wavefront kernel on this batch, and the wavefronts a CU of 160 KB holds of each. Without a device the output says
-"not measured". What the output file holds from its first line of dashes on is kept as it is."""
+"not measured". What the output file holds from its first line of dashes on is kept as it is.
+
+    python tools/re_tron_bench.py --rows [--parent DIR] [--out profiles/re_tron_rows.txt]
+
+The row kernel (re_tron_rows_kernel: four entities per wavefront) on the same batch: in one process and in alternation, the TRON solve under
+a row limit of 0 (the routing without that kernel), 6, 8 and 10 KB, and the plain solve under default routing for information. For each:
+the median of the timed solves with [min, max], the share of entities on the row kernel, evaluations and products per entity, ms per pass.
+--parent DIR names a tree that holds another build of the package (DIR/gdmix_amd with its library, e.g. the parent commit's): its TRON
+solve, as that build routes it by default, is timed on the same batch by a child process right behind the others, on the same device in the
+same session. --parent-label says in the output what that build is (the directory's name otherwise); both options may be given several times."""
 import argparse
 import os
 import sys
@@ -90,15 +99,115 @@ def measure(E, steps, warmup):
     return lines
 
 
+ROW_LIMITS = (0, 6144, 8192, 10240)
+
+
+def _c2(E):
+    import torch      # noqa: F401
+    from gdmix_amd import synthetic
+    from gdmix_amd.solver import REDeviceSolver, SolverOptions
+    b = synthetic.make_survey_batch(E, 16, 4, 1024, seed=synthetic.C2_SEED)
+    solver = REDeviceSolver(0)
+    return b, solver, solver.pack(b, has_intercept=True), SolverOptions(l2=1.0, ftol=1e-12)
+
+
+def _timed(call):
+    import torch
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    res = call()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1), res
+
+
+def _spread(ms):
+    return f"{np.median(ms):.3f} ms [{min(ms):.3f}, {max(ms):.3f}]"
+
+
+def time_package_tron(E, steps, warmup):
+    """The TRON solve of whichever package is first on sys.path, as that package routes it by default -> the timed runs in ms."""
+    b, solver, packed, opts = _c2(E)
+    ms = [_timed(lambda: solver.solve_tron(packed, opts))[0] for _ in range(warmup + steps)][warmup:]
+    solver.close()
+    return ms
+
+
+def measure_rows(E, steps, warmup, parents):
+    import json
+    import subprocess
+    b, solver, packed, opts = _c2(E)
+    lines = [f"C2-shaped synthetic batch (make_survey_batch({E}, 16, 4, 1024, seed=C2_SEED)): {packed.E} entities, {b.N} samples, {b.Z} non-zeros, {packed.P} coefficients",
+             f"logistic, l2 = 1, stage tolerances (pgtol 1e-5, ftol 1e-12, max_iter 100); median [min, max] of {steps} timed solves after {warmup} warm-up "
+             f"solves, the settings in alternation in one process", ""]
+    ms = {k: [] for k in ROW_LIMITS + ("plain",)}
+    last, rows = {}, {}
+    for step in range(warmup + steps):
+        for k in ms:
+            if k == "plain":
+                t, res = _timed(lambda: solver.solve(packed, opts))
+            else:
+                solver.set_tron_row_lds_limit(k)
+                t, res = _timed(lambda: solver.solve_tron(packed, opts))
+                rows[k] = solver.tron_row_count(packed)
+            if step >= warmup:
+                ms[k].append(t)
+            last[k] = res
+    solver.set_tron_row_lds_limit(solver.TRON_ROW_LDS_DEFAULT)
+    host = {k: last[k].to_host() for k in ROW_LIMITS}
+    tron, _ = footprints(b, packed, opts.m)
+    for k in ROW_LIMITS:
+        r = host[k]
+        nfev, nhv = float(r["nfev"].mean()), float(r["nhv"].mean())
+        same = all(np.array_equal(r[f], host[0][f]) for f in ("nfev", "nhv", "nit", "status")) and r["theta"].tobytes() == host[0]["theta"].tobytes()
+        fits = tron[tron <= k]
+        lds = f"LDS per workgroup 4 x {int(fits.max())} = {4 * int(fits.max())} B: {CU_LDS // (4 * int(fits.max()))} wavefronts, {4 * (CU_LDS // (4 * int(fits.max())))} entities per CU by arithmetic" if k and fits.size else "no row launch"
+        lines.append(f"TRON, row limit {k:5d} B: {_spread(ms[k])}; {rows[k]} of {packed.E} entities on the row kernel ({rows[k] / packed.E:.1%}); evaluations per entity "
+                     f"{nfev:.2f}, products per entity {nhv:.2f}, {np.median(ms[k]) / (nfev + nhv):.3f} ms per pass; counts and theta "
+                     f"{'equal to' if same else 'DIFFERENT from'} row limit 0's; {lds}")
+    lines.append(f"plain solve, default routing (for information): {_spread(ms['plain'])}")
+    d = solver.TRON_ROW_LDS_DEFAULT
+    faster = max(ms[d]) < min(ms[0])
+    lines.append(f"default row limit {d} B against row limit 0: {np.median(ms[0]) / np.median(ms[d]):.2f} x, [min, max] {'do not overlap: faster' if faster else 'OVERLAP or slower: bar missed'}; "
+                 f"against the plain solve under default routing: {np.median(ms[d]) / np.median(ms['plain']):.2f} x its time (reported only)")
+    solver.close()
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for parent, label in parents:
+        cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--rows-child", "--package-root", parent, "--entities", str(E), "--steps", str(steps),
+                             "--warmup", str(warmup)], capture_output=True, text=True, cwd=here)
+        if cp.returncode == 0:
+            pm = json.loads(cp.stdout.strip().splitlines()[-1])
+            def near(mine):      # do the two runs' [min, max] overlap?
+                return "[min, max] overlap" if min(pm) <= max(mine) and min(mine) <= max(pm) else "[min, max] APART"
+            lines.append(f"another build, {label}: its TRON solve under its default routing, a child process right behind: {_spread(pm)}; against row limit 0 "
+                         f"here ({_spread(ms[0])}): {near(ms[0])}; against row limit {d} here ({_spread(ms[d])}): {near(ms[d])}")
+        else:
+            lines.append(f"another build, {label}: not measured, the child process failed: {cp.stderr[-300:]}")
+    return lines
+
+
 def main():
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if "--package-root" in sys.argv:      # (before the package is imported: another build's tree in this one's place)
+        here = os.path.abspath(sys.argv[sys.argv.index("--package-root") + 1])
     sys.path.insert(0, here)
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", action="store_true", help="the row kernel's measurements (profiles/re_tron_rows.txt)")
+    ap.add_argument("--parent", action="append", default=[], help="with --rows: a tree with another build of the package, timed by a child process")
+    ap.add_argument("--parent-label", action="append", default=[], help="what the output calls that build (default: the directory's name)")
+    ap.add_argument("--rows-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--package-root", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--entities", type=int, default=1_000_000)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(here, "profiles", "re_tron.txt"))
     a = ap.parse_args()
+    if a.rows_child:
+        import json
+        print(json.dumps(time_package_tron(a.entities, a.steps, a.warmup)))
+        return
+    if a.rows and a.out.endswith("re_tron.txt"):
+        a.out = os.path.join(os.path.dirname(a.out), "re_tron_rows.txt")
     head = ["Random effect, trust-region Newton per entity (gdmix_re_solve_tron) next to the plain solve (gdmix_re_solve): 1 x MI355X, torch events around "
             "REDeviceSolver.solve_tron / solve, results left on the device."]
     try:
@@ -106,7 +215,14 @@ def main():
         have = torch.cuda.is_available()
     except Exception:
         have = False
-    lines = head + (measure(a.entities, a.steps, a.warmup) if have else ["not measured: no device"])
+    if a.rows:
+        labels = a.parent_label + [os.path.basename(os.path.normpath(d)) for d in a.parent[len(a.parent_label):]]
+        parents = list(zip(a.parent, labels))
+        head = ["Random effect, TRON with four entities per wavefront (re_tron_rows_kernel) next to the one-entity wavefront kernel: 1 x MI355X, torch events "
+                "around REDeviceSolver.solve_tron, results left on the device."]
+        lines = head + (measure_rows(a.entities, a.steps, a.warmup, parents) if have else ["not measured: no device"])
+    else:
+        lines = head + (measure(a.entities, a.steps, a.warmup) if have else ["not measured: no device"])
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     if os.path.exists(a.out):
