@@ -22,6 +22,13 @@
 //                         kernel's outputs from the same read when the caller wants them; topk_big_kernel: a workgroup per large entity on
 //                         its sorted segment (binary searches for the tie group of the cut). The sort path's steps up to the sorted keys
 //                         (sort_big_entities) and from them to the AUC outputs (rank_and_finish) are shared by the two entry points.
+//   AUPR                  gdmix_re_eval_aupr_entities, gdmix_re_eval_aupr_acc_finish (include/gdmix_re.h, "AUPR"): the trapezoid over every
+//                         distinct threshold as a sum of one fp64 term per tie group. aupr_small_kernel: the small geometry again, the
+//                         positives' and the negatives' keys through LDS, one lane per tie group forms the term. Sort path: the same radix
+//                         sort with scores DESCENDING inside a segment (sort_big_entities with the score bits complemented; the
+//                         accumulator's plain keys sorted descending, so they are only read), then pr_reduce_kernel / pr_scan_kernel, the
+//                         rank-sum pass's reduce-then-scan over a state of six counts, which write one term per sorted key, and the
+//                         fixed-shape sums of re_eval_sum.hpp over those terms. No atomics at all on this path.
 #include <stdint.h>
 #include <math.h>
 
@@ -146,9 +153,11 @@ __global__ void eval_big_list_kernel(const int64_t* __restrict__ mark, const int
   big_list[o >> 32] = (int32_t)e;
   big_off[o >> 32] = (int32_t)(o & 0xFFFFFFFFll);
 }
-// one thread per sample of a large entity, in the entities' order: segment = the entity's number among the large ones
+// one thread per sample of a large entity, in the entities' order: segment = the entity's number among the large ones. flip: 0, or all
+// ones to complement the 32 score bits of the key, so that the ascending sort leaves a segment's scores DESCENDING (AUPR)
 __global__ void eval_big_keys_kernel(const int64_t* __restrict__ ent_row_ptr, const int32_t* __restrict__ big_list, const int32_t* __restrict__ big_off,
-                                     int nbig, int64_t M, const float* __restrict__ score, const float* __restrict__ label, uint64_t* __restrict__ keys) {
+                                     int nbig, int64_t M, const float* __restrict__ score, const float* __restrict__ label, uint32_t flip,
+                                     uint64_t* __restrict__ keys) {
   const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= M) return;
   int lo = 0, hi = nbig - 1;   // the last b with big_off[b] <= m
@@ -157,7 +166,7 @@ __global__ void eval_big_keys_kernel(const int64_t* __restrict__ ent_row_ptr, co
     if ((int64_t)big_off[mid] <= m) lo = mid; else hi = mid - 1;
   }
   const int64_t i = ent_row_ptr[big_list[lo]] + (m - big_off[lo]);
-  keys[m] = ((uint64_t)lo << 33) | key33(score[i], label[i]);
+  keys[m] = ((uint64_t)lo << 33) | (key33(score[i], label[i]) ^ ((uint64_t)flip << 1));
 }
 
 // ---- rank-sum pass over sorted keys --------------------------------------------------------------------------------------------------
@@ -181,13 +190,15 @@ __device__ __forceinline__ RankState rank_element(uint64_t key, uint64_t prev, b
   r.f = ((first || (key >> 1) != (prev >> 1)) ? 1u : 0u) | ((first || (key >> 33) != (prev >> 33)) ? 2u : 0u);
   return r;
 }
-// inclusive scan of one state per thread in thread order (Hillis-Steele through LDS: 8 steps for 256 threads)
-__device__ __forceinline__ RankState rank_block_scan(RankState v, RankState* lds) {
+// inclusive scan of one state per thread in thread order (Hillis-Steele through LDS: 8 steps for 256 threads); S: RankState, or the
+// PrState of the AUPR pass below (rank_combine is overloaded)
+template <class S>
+__device__ __forceinline__ S rank_block_scan(S v, S* lds) {
   const int t = threadIdx.x;
   lds[t] = v;
   __syncthreads();
   for (int off = 1; off < RANK_THREADS; off <<= 1) {
-    RankState left = v;
+    S left = v;
     const bool take = t >= off;
     if (take) left = lds[t - off];
     __syncthreads();
@@ -484,6 +495,221 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_big_kernel(const int64_t* _
   }
 }
 
+// ---- AUPR: the area under the precision-recall curve (include/gdmix_re.h, "AUPR") ---------------------------------------------------------
+// One term per tie group that holds a positive. (Tp, Fp): the positives and negatives with a greater score, (T, F): those with a score not
+// smaller. Every path forms a term with these operations, so a term has the same bits wherever it is formed.
+__device__ __forceinline__ double pr_term(uint32_t Tp, uint32_t Fp, uint32_t T, uint32_t F) {
+  if (T == Tp) return 0.0;                                         // no positive in the group: no step in recall
+  const double P = (double)T / (double)(T + F);
+  const double Pp = (Tp + Fp) ? (double)Tp / (double)(Tp + Fp) : P;   // the first point of the curve is (0, P_1)
+  return (double)(T - Tp) * (0.5 * (Pp + P));
+}
+__device__ __forceinline__ double aupr_of(double pr_sum, int n_pos) {
+  return n_pos ? pr_sum / (double)n_pos : __longlong_as_double(0x7ff8000000000000ll);
+}
+struct AuprOutDev { double* pr_sum; int32_t* n_pos; int32_t* n_neg; int32_t* n_nan; double* aupr; };
+__device__ __forceinline__ void write_aupr(const AuprOutDev& O, int64_t e, double pr_sum, int n_pos, int n_neg, int n_nan) {
+  if (O.pr_sum) O.pr_sum[e] = pr_sum;
+  if (O.n_pos) O.n_pos[e] = n_pos;
+  if (O.n_neg) O.n_neg[e] = n_neg;
+  if (O.n_nan) O.n_nan[e] = n_nan;
+  if (O.aupr) O.aupr[e] = aupr_of(pr_sum, n_pos);
+}
+
+// Small entities: topk_small_kernel's geometry. A lane's key is the COMPLEMENT of its score's key, so a smaller key is a greater score and
+// the filler 0xFFFFFFFF of a lane without a valid sample (the complement of no score's key: those lie in [0x007FFFFF, 0xFF800000]) is below
+// every score. The 33-bit keys go through LDS as two arrays of 32-bit words, the positives' and the negatives' (the other array holds the
+// filler): a lane reads its group's 2 W words with W / 2 ds_read_b128 and counts, per class, the keys below its own (Tp, Fp) and not above
+// it (T, F), and the keys equal to its own on lower lanes. The lane of a tie group that finds none there speaks for the group: it forms
+// the term. One fp64 xor-butterfly adds the terms (the same tree on every lane), one integer butterfly the three counts. No sort, no atomics.
+__device__ __forceinline__ int small_width(int nmax) { return nmax <= 16 ? 16 : (nmax <= 32 ? 32 : 64); }   // lanes per entity, as the kernels above
+__global__ __launch_bounds__(64) void aupr_small_kernel(const int64_t* __restrict__ ent_row_ptr, int64_t E, const float* __restrict__ score,
+                                                        const float* __restrict__ label, AuprOutDev O, int small_max) {
+  __shared__ __attribute__((aligned(16))) uint32_t pos_keys[64];
+  __shared__ __attribute__((aligned(16))) uint32_t neg_keys[64];
+  const int lane = threadIdx.x;
+  const int64_t e0 = (int64_t)blockIdx.x * 4;
+  const int64_t last = e0 + 4 < E ? e0 + 4 : E;
+  const int64_t mine = ent_row_ptr[e0 + lane < last ? e0 + lane : last];   // lanes 0 .. 4 matter
+  int64_t rp[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) rp[k] = __shfl(mine, k);
+  int nmax = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t n = rp[k + 1] - rp[k];
+    if (n <= small_max && (int)n > nmax) nmax = (int)n;
+  }
+  const int W = small_width(nmax);
+  const int per_pass = 64 / W;
+  const int g = lane / W, li = lane & (W - 1), base = lane & ~(W - 1);
+  for (int pass = 0; pass < W / 16; ++pass) {
+    const int k = pass * per_pass + g;
+    const int64_t start = k == 0 ? rp[0] : (k == 1 ? rp[1] : (k == 2 ? rp[2] : rp[3]));
+    const int64_t end = k == 0 ? rp[1] : (k == 1 ? rp[2] : (k == 2 ? rp[3] : rp[4]));
+    const int64_t n = end - start;
+    const bool ent_ok = e0 + k < E && n <= small_max;
+    const bool have = ent_ok && li < n;
+    float s = 0.0f, y = 0.0f;
+    if (have) { s = score[start + li]; y = label[start + li]; }
+    const uint32_t key = have ? sortable_key(s) : KEY_NAN;
+    const bool nan = have && key == KEY_NAN;
+    const bool valid = have && !nan;
+    const bool pos = valid && y > 0.5f;
+    const uint32_t ck = valid ? ~key : KEY_NAN;     // KEY_NAN doubles as the filler: no valid complement equals it
+    pos_keys[lane] = pos ? ck : KEY_NAN;
+    neg_keys[lane] = (valid && !pos) ? ck : KEY_NAN;
+    __syncthreads();
+    uint32_t Tp = 0, T = 0, Fp = 0, F = 0, lower = 0;
+    for (int j = 0; j < W; j += 4) {
+      const uint4 p = *reinterpret_cast<const uint4*>(&pos_keys[base + j]);
+      const uint4 q = *reinterpret_cast<const uint4*>(&neg_keys[base + j]);
+      Tp += (uint32_t)(p.x < ck) + (uint32_t)(p.y < ck) + (uint32_t)(p.z < ck) + (uint32_t)(p.w < ck);
+      T += (uint32_t)(p.x <= ck) + (uint32_t)(p.y <= ck) + (uint32_t)(p.z <= ck) + (uint32_t)(p.w <= ck);
+      Fp += (uint32_t)(q.x < ck) + (uint32_t)(q.y < ck) + (uint32_t)(q.z < ck) + (uint32_t)(q.w < ck);
+      F += (uint32_t)(q.x <= ck) + (uint32_t)(q.y <= ck) + (uint32_t)(q.z <= ck) + (uint32_t)(q.w <= ck);
+      lower += (uint32_t)((p.x == ck || q.x == ck) && j + 0 < li) + (uint32_t)((p.y == ck || q.y == ck) && j + 1 < li) +
+               (uint32_t)((p.z == ck || q.z == ck) && j + 2 < li) + (uint32_t)((p.w == ck || q.w == ck) && j + 3 < li);
+    }
+    __syncthreads();   // the next pass overwrites the keys
+    double sum = (valid && lower == 0u) ? pr_term(Tp, Fp, T, F) : 0.0;
+    uint32_t c = (pos ? 1u : 0u) | (((valid && !pos) ? 1u : 0u) << 8) | ((nan ? 1u : 0u) << 16);   // three counts <= 64 in one word
+    for (int off = 1; off < W; off <<= 1) {
+      sum += __shfl_xor(sum, off);
+      c += __shfl_xor(c, off);
+    }
+    if (ent_ok && li == 0) write_aupr(O, e0 + k, sum, (int)(c & 0xFFu), (int)((c >> 8) & 0xFFu), (int)(c >> 16));
+  }
+}
+
+// Sort path: the keys of a segment sorted so that scores DESCEND, so every count a term needs is a prefix from the segment's head and no
+// segment total has to be known first. nan32: the 32 score bits of a NaN's key in that order (0 where the bits were complemented for an
+// ascending sort, KEY_NAN where the plain keys were sorted descending); such a key is neither a positive nor a negative. The scanned state
+// of a stretch of elements: (tp, fp) its positives and negatives, (gtp, gfp) / (stp, sfp) those in front of its last tie-group / segment
+// head (flags: it has one). Reduce-then-scan like the rank-sum pass: no workgroup waits for another.
+struct PrState { uint32_t tp, fp, gtp, gfp, stp, sfp, f; };
+__device__ __forceinline__ PrState rank_combine(const PrState& a, const PrState& b) {
+  PrState r;
+  r.tp = a.tp + b.tp;
+  r.fp = a.fp + b.fp;
+  r.gtp = (b.f & 1u) ? a.tp + b.gtp : a.gtp;
+  r.gfp = (b.f & 1u) ? a.fp + b.gfp : a.gfp;
+  r.stp = (b.f & 2u) ? a.tp + b.stp : a.stp;
+  r.sfp = (b.f & 2u) ? a.fp + b.sfp : a.sfp;
+  r.f = a.f | b.f;
+  return r;
+}
+__device__ __forceinline__ PrState pr_element(uint64_t key, uint64_t prev, bool first, uint32_t nan32) {
+  PrState r;
+  const bool valid = (uint32_t)(key >> 1) != nan32;
+  r.tp = (valid && (key & 1ull)) ? 1u : 0u;
+  r.fp = (valid && !(key & 1ull)) ? 1u : 0u;
+  r.gtp = 0u; r.gfp = 0u; r.stp = 0u; r.sfp = 0u;
+  r.f = ((first || (key >> 1) != (prev >> 1)) ? 1u : 0u) | ((first || (key >> 33) != (prev >> 33)) ? 2u : 0u);
+  return r;
+}
+__device__ __forceinline__ PrState pr_fold(const uint64_t* __restrict__ keys, int64_t first, int cnt, uint32_t nan32) {
+  PrState v = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  uint64_t p = (cnt > 0 && first > 0) ? keys[first - 1] : 0ull;
+  for (int j = 0; j < cnt; ++j) {
+    const uint64_t k = keys[first + j];
+    v = rank_combine(v, pr_element(k, p, first + j == 0, nan32));
+    p = k;
+  }
+  return v;
+}
+__global__ __launch_bounds__(RANK_THREADS) void pr_reduce_kernel(const uint64_t* __restrict__ keys, int64_t M, uint32_t nan32, PrState* __restrict__ partial) {
+  __shared__ PrState lds[RANK_THREADS];
+  const int64_t first = (int64_t)blockIdx.x * RANK_TILE + (int64_t)threadIdx.x * RANK_ITEMS;
+  const PrState v = rank_block_scan(pr_fold(keys, first, rank_count(M, first), nan32), lds);
+  if (threadIdx.x == RANK_THREADS - 1) partial[blockIdx.x] = v;
+}
+// A thread walks its keys with the state in front of them. The LAST element of a tie group — the next key differs above bit 0, which
+// covers the end of a segment, or the array ends — writes the group's term, every other position 0.0; the last element of a segment also
+// writes the segment's two counts. Every position of `terms` and every segment of `seg_cnt` is written by exactly one thread: no atomics.
+__global__ __launch_bounds__(RANK_THREADS) void pr_scan_kernel(const uint64_t* __restrict__ keys, int64_t M, uint32_t nan32, const PrState* __restrict__ partial,
+                                                               double* __restrict__ terms, uint2* __restrict__ seg_cnt) {
+  __shared__ PrState lds[RANK_THREADS];
+  __shared__ PrState block_prefix;
+  const int t = threadIdx.x;
+  {
+    const int nb = blockIdx.x;
+    const int c = (nb + RANK_THREADS - 1) / RANK_THREADS;
+    PrState v = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    for (int j = t * c; j < (t + 1) * c && j < nb; ++j) v = rank_combine(v, partial[j]);
+    v = rank_block_scan(v, lds);
+    if (t == RANK_THREADS - 1) block_prefix = v;
+    __syncthreads();
+  }
+  const int64_t first = (int64_t)blockIdx.x * RANK_TILE + (int64_t)t * RANK_ITEMS;
+  const int cnt = rank_count(M, first);
+  (void)rank_block_scan(pr_fold(keys, first, cnt, nan32), lds);
+  PrState run = block_prefix;
+  if (t > 0) run = rank_combine(run, lds[t - 1]);   // (lds holds the inclusive scan)
+  uint64_t p = (cnt > 0 && first > 0) ? keys[first - 1] : 0ull;
+  uint64_t k = cnt > 0 ? keys[first] : 0ull;
+  for (int j = 0; j < cnt; ++j) {
+    const int64_t i = first + j;
+    const bool at_end = i + 1 == M;
+    const uint64_t next = at_end ? 0ull : keys[i + 1];
+    run = rank_combine(run, pr_element(k, p, i == 0, nan32));
+    double term = 0.0;
+    if (at_end || (next >> 1) != (k >> 1)) {
+      term = pr_term(run.gtp - run.stp, run.gfp - run.sfp, run.tp - run.stp, run.fp - run.sfp);
+      if (at_end || (next >> 33) != (k >> 33)) seg_cnt[k >> 33] = make_uint2(run.tp - run.stp, run.fp - run.sfp);
+    }
+    terms[i] = term;
+    p = k; k = next;
+  }
+}
+
+// the lane sum of re_eval_sum.hpp over stored terms (sse_lane's shape)
+__device__ __forceinline__ double terms_lane(const double* __restrict__ terms, int64_t begin, int64_t end, int64_t stride) {
+  double top = 0.0, total = 0.0, run = 0.0;
+  int in_run = 0, runs = 0;
+  for (int64_t i = begin; i < end; i += stride) {
+    run += terms[i];
+    if (++in_run == EVAL_RUN) {
+      total += run; run = 0.0; in_run = 0;
+      if (++runs == EVAL_RUNS) { top += total; total = 0.0; runs = 0; }
+    }
+  }
+  return top + (total + run);
+}
+// one workgroup per large entity: the fixed-shape sum over its segment of `terms`, then its outputs
+__global__ __launch_bounds__(EVAL_THREADS) void aupr_big_finish_kernel(const int64_t* __restrict__ ent_row_ptr, const int32_t* __restrict__ big_list,
+                                                                       const int32_t* __restrict__ big_off, const double* __restrict__ terms,
+                                                                       const uint2* __restrict__ seg_cnt, AuprOutDev O) {
+  __shared__ double lds[EVAL_THREADS];
+  const int b = blockIdx.x;
+  const int64_t e = big_list[b];
+  const int64_t n = ent_row_ptr[e + 1] - ent_row_ptr[e], m0 = big_off[b];
+  const double sum = eval_block_tree(terms_lane(terms, m0 + threadIdx.x, m0 + n, EVAL_THREADS), lds);
+  if (threadIdx.x == 0) {
+    const uint2 c = seg_cnt[b];
+    write_aupr(O, e, sum, (int)c.x, (int)c.y, (int)(n - (int64_t)c.x - (int64_t)c.y));
+  }
+}
+// the accumulator: the two-level sum of eval_acc_add_kernel / eval_acc_sum_kernel over POSITIONS of the sorted array (workgroup sums in
+// position order, then one workgroup over those), so the bits depend on the multiset of keys alone
+__global__ __launch_bounds__(EVAL_THREADS) void aupr_acc_groups_kernel(const double* __restrict__ terms, int64_t M, double* __restrict__ group_sum) {
+  __shared__ double lds[EVAL_THREADS];
+  const int64_t stride = (int64_t)gridDim.x * EVAL_THREADS;
+  double total = 0.0, run = 0.0;
+  int in_run = 0;
+  for (int64_t i = (int64_t)blockIdx.x * EVAL_THREADS + threadIdx.x; i < M; i += stride) {
+    run += terms[i];
+    if (++in_run == EVAL_RUN) { total += run; run = 0.0; in_run = 0; }
+  }
+  const double v = eval_block_tree(total + run, lds);
+  if (threadIdx.x == 0) group_sum[blockIdx.x] = v;
+}
+__global__ __launch_bounds__(EVAL_THREADS) void aupr_acc_total_kernel(const double* __restrict__ group_sum, int groups, double* __restrict__ pr_sum) {
+  __shared__ double lds[EVAL_THREADS];
+  const double v = acc_group_tree(group_sum, groups, lds);
+  if (threadIdx.x == 0) *pr_sum = v;
+}
+
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int64_t rank_tiles(int64_t M) { return (M + RANK_TILE - 1) / RANK_TILE; }
 
@@ -513,14 +739,18 @@ static int rank_sum(const uint64_t* sorted, int64_t M, int64_t segments, RankSta
   return GDMIX_RE_OK;
 }
 
-static int sort_keys(gdmix_ctx_impl* ci, uint64_t* in, uint64_t* out, int64_t M, unsigned end_bit, hipStream_t s) {
+static int sort_keys(gdmix_ctx_impl* ci, uint64_t* in, uint64_t* out, int64_t M, unsigned end_bit, hipStream_t s, bool descending = false) {
+  unsigned long long* const none = nullptr;
   size_t bytes = 0;
-  HIP_TRY((rocprim::radix_sort_keys(nullptr, bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (size_t)M, 0u, end_bit, s)));
+  if (descending) HIP_TRY((rocprim::radix_sort_keys_desc(nullptr, bytes, none, none, (size_t)M, 0u, end_bit, s)));
+  else HIP_TRY((rocprim::radix_sort_keys(nullptr, bytes, none, none, (size_t)M, 0u, end_bit, s)));
   void* tmp = nullptr;
   const int rc = eval_tmp(ci, bytes ? bytes : 1, s, &tmp);
   if (rc != GDMIX_RE_OK) return rc;
-  HIP_TRY((rocprim::radix_sort_keys(tmp, bytes, reinterpret_cast<unsigned long long*>(in), reinterpret_cast<unsigned long long*>(out), (size_t)M, 0u,
-                                    end_bit, s)));
+  unsigned long long* const from = reinterpret_cast<unsigned long long*>(in);
+  unsigned long long* const to = reinterpret_cast<unsigned long long*>(out);
+  if (descending) HIP_TRY((rocprim::radix_sort_keys_desc(tmp, bytes, from, to, (size_t)M, 0u, end_bit, s)));
+  else HIP_TRY((rocprim::radix_sort_keys(tmp, bytes, from, to, (size_t)M, 0u, end_bit, s)));
   return GDMIX_RE_OK;
 }
 
@@ -554,12 +784,47 @@ static AccLayout acc_layout(int64_t N) {
   return L;
 }
 
+// AUPR per entity: the sort path's layout, then a term per sorted key and the scan's tile states. The two counts of a segment take the 8
+// bytes per entity of acc_two_u, which this call does not use otherwise.
+struct AuprLayout { EvalLayout ev; size_t terms, partial, total; };
+static AuprLayout aupr_layout(int64_t E, int64_t N) {
+  AuprLayout L;
+  L.ev = eval_layout(E, N);
+  L.terms = L.ev.total;
+  L.partial = L.terms + up256((size_t)N * 8);
+  L.total = L.partial + up256((size_t)(rank_tiles(N) + 1) * sizeof(PrState));
+  return L;
+}
+struct AuprAccLayout { size_t sorted, terms, partial, seg_cnt, group_sum, pr_sum, total; };
+static AuprAccLayout aupr_acc_layout(int64_t N) {
+  AuprAccLayout L;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = up256(off + bytes); return o; };
+  L.sorted = take((size_t)N * 8);
+  L.terms = take((size_t)N * 8);
+  L.partial = take((size_t)(rank_tiles(N) + 1) * sizeof(PrState));
+  L.seg_cnt = take(8);
+  L.group_sum = take((size_t)ACC_MAX_GROUPS * 8);
+  L.pr_sum = take(8);
+  L.total = off;
+  return L;
+}
+// sorted keys (scores descending inside a segment) -> terms[M] and the segments' counts
+static int pr_terms(const uint64_t* sorted, int64_t M, uint32_t nan32, PrState* partial, double* terms, uint2* seg_cnt, hipStream_t s) {
+  const int nb = (int)rank_tiles(M);
+  hipLaunchKernelGGL(pr_reduce_kernel, dim3(nb), dim3(RANK_THREADS), 0, s, sorted, M, nan32, partial);
+  hipLaunchKernelGGL(pr_scan_kernel, dim3(nb), dim3(RANK_THREADS), 0, s, sorted, M, nan32, (const PrState*)partial, terms, seg_cnt);
+  HIP_TRY(hipGetLastError());
+  return GDMIX_RE_OK;
+}
+
 // ---- the sort path's steps, shared by gdmix_re_eval_entities and gdmix_re_eval_topk_entities --------------------------------------------
 // mark -> one prefix sum -> (the one synchronisation: how many entities are large) -> list -> keys -> radix sort. `sorted` holds the
-// segments of the large entities in their order, segment b at big_off[b], a NaN score's key last in its segment.
+// segments of the large entities in their order, segment b at big_off[b], a NaN score's key last in its segment. With flip = all ones
+// (eval_big_keys_kernel) a segment's scores descend and its NaN keys (score bits 0) come first.
 struct SortedBig { int64_t nbig, M; int32_t* big_list; int32_t* big_off; uint64_t* sorted; RankState* partial; uint64_t* acc_two_u; uint32_t* acc_cnt; };
 static int sort_big_entities(gdmix_ctx_impl* ci, const char* who, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
-                             int small_max, const EvalLayout& L, char* base, hipStream_t s, SortedBig* B) {
+                             int small_max, const EvalLayout& L, char* base, hipStream_t s, SortedBig* B, uint32_t flip = 0u) {
   int64_t* mark = reinterpret_cast<int64_t*>(base + L.mark);
   int64_t* offs = reinterpret_cast<int64_t*>(base + L.offs);
   int32_t* big_list = reinterpret_cast<int32_t*>(base + L.big_list);
@@ -587,7 +852,7 @@ static int sort_big_entities(gdmix_ctx_impl* ci, const char* who, const int64_t*
   if (M > N) { set_error("%s: ent_row_ptr covers %lld samples, N is %lld", who, (long long)M, (long long)N); return GDMIX_RE_EINVAL; }
   hipLaunchKernelGGL(eval_big_list_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, (const int64_t*)mark, (const int64_t*)offs, E, big_list, big_off);
   if (M > 0) hipLaunchKernelGGL(eval_big_keys_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, ent_row_ptr, (const int32_t*)big_list,
-                                (const int32_t*)big_off, (int)nbig, M, score, label, keys_a);
+                                (const int32_t*)big_off, (int)nbig, M, score, label, flip, keys_a);
   HIP_TRY(hipGetLastError());
   unsigned sbits = 0;
   while (((int64_t)1 << sbits) < nbig) ++sbits;
@@ -770,6 +1035,93 @@ GDMIX_API int gdmix_re_eval_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_ac
   host_out->n_nan = cnt[2];
   host_out->n = M;
   host_out->sse = sse;
+  return GDMIX_RE_OK;
+}
+
+GDMIX_API size_t gdmix_re_eval_aupr_workspace_bytes(int64_t E, int64_t N) {
+  if (E < 0 || N < 0 || E >= EVAL_LIMIT || N >= EVAL_LIMIT) return 0;
+  return aupr_layout(E, N).total;
+}
+
+GDMIX_API int gdmix_re_eval_aupr_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                          const gdmix_re_eval_aupr_out* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ctx || !out || E < 0 || N < 0) { set_error("gdmix_re_eval_aupr_entities: bad argument"); return GDMIX_RE_EINVAL; }
+  if (N >= EVAL_LIMIT || E >= EVAL_LIMIT) {
+    set_error("gdmix_re_eval_aupr_entities: %lld samples / %lld entities; an evaluation takes fewer than 2^31 of each", (long long)N, (long long)E);
+    return GDMIX_RE_ERANGE;
+  }
+  if (E == 0) return GDMIX_RE_OK;
+  if (!ent_row_ptr || (N > 0 && (!score || !label))) { set_error("gdmix_re_eval_aupr_entities: NULL input"); return GDMIX_RE_EINVAL; }
+  const AuprLayout L = aupr_layout(E, N);
+  if (!workspace || workspace_bytes < L.total) {
+    set_error("gdmix_re_eval_aupr_entities: workspace of %zu bytes, %zu needed (gdmix_re_eval_aupr_workspace_bytes)", workspace_bytes, L.total);
+    return GDMIX_RE_ENOMEM;
+  }
+  gdmix_ctx_impl* ci = &ctx->impl;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(workspace);
+  const int small_max = ci->eval_small_set ? ci->eval_small_max : 64;
+  const AuprOutDev O = {out->pr_sum, out->n_pos, out->n_neg, out->n_nan, out->aupr};
+  // (with a limit of 0 this launch still writes the entities of no samples)
+  hipLaunchKernelGGL(aupr_small_kernel, dim3((unsigned)((E + 3) / 4)), dim3(64), 0, s, ent_row_ptr, E, score, label, O, small_max);
+  HIP_TRY(hipGetLastError());
+  SortedBig B;
+  int rc = sort_big_entities(ci, "gdmix_re_eval_aupr_entities", ent_row_ptr, E, N, score, label, small_max, L.ev, base, s, &B, 0xFFFFFFFFu);
+  if (rc != GDMIX_RE_OK || B.nbig == 0) return rc;
+  double* terms = reinterpret_cast<double*>(base + L.terms);
+  uint2* seg_cnt = reinterpret_cast<uint2*>(B.acc_two_u);
+  rc = pr_terms(B.sorted, B.M, 0u, reinterpret_cast<PrState*>(base + L.partial), terms, seg_cnt, s);
+  if (rc != GDMIX_RE_OK) return rc;
+  hipLaunchKernelGGL(aupr_big_finish_kernel, dim3((unsigned)B.nbig), dim3(EVAL_THREADS), 0, s, ent_row_ptr, (const int32_t*)B.big_list,
+                     (const int32_t*)B.big_off, (const double*)terms, (const uint2*)seg_cnt, O);
+  HIP_TRY(hipGetLastError());
+  return GDMIX_RE_OK;
+}
+
+GDMIX_API size_t gdmix_re_eval_aupr_acc_workspace_bytes(int64_t N) {
+  if (N < 0 || N >= EVAL_LIMIT) return 0;
+  return aupr_acc_layout(N).total;
+}
+
+GDMIX_API int gdmix_re_eval_aupr_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_acc* acc, void* workspace, size_t workspace_bytes,
+                                            gdmix_re_eval_aupr_totals* host_out, void* stream) {
+  if (!ctx || !acc || !host_out || acc->count < 0 || acc->count >= EVAL_LIMIT) { set_error("gdmix_re_eval_aupr_acc_finish: bad argument"); return GDMIX_RE_EINVAL; }
+  const int64_t M = acc->count;
+  host_out->pr_sum = 0.0;
+  host_out->n = M; host_out->n_pos = 0; host_out->n_neg = 0; host_out->n_nan = 0;
+  if (M == 0) return GDMIX_RE_OK;
+  const AuprAccLayout L = aupr_acc_layout(M);
+  if (!workspace || workspace_bytes < L.total || !acc->keys || acc->capacity < M) {
+    set_error("gdmix_re_eval_aupr_acc_finish: workspace of %zu bytes, %zu needed for %lld samples (gdmix_re_eval_aupr_acc_workspace_bytes)", workspace_bytes,
+              L.total, (long long)M);
+    return GDMIX_RE_ENOMEM;
+  }
+  gdmix_ctx_impl* ci = &ctx->impl;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(workspace);
+  uint64_t* sorted = reinterpret_cast<uint64_t*>(base + L.sorted);
+  double* terms = reinterpret_cast<double*>(base + L.terms);
+  uint2* seg_cnt = reinterpret_cast<uint2*>(base + L.seg_cnt);
+  double* group_sum = reinterpret_cast<double*>(base + L.group_sum);
+  double* pr_sum = reinterpret_cast<double*>(base + L.pr_sum);
+  // the accumulator's keys are read, not written: the plain keys sorted descending (a NaN's key first)
+  int rc = sort_keys(ci, acc->keys, sorted, M, 33u, s, true);
+  if (rc != GDMIX_RE_OK) return rc;
+  rc = pr_terms(sorted, M, KEY_NAN, reinterpret_cast<PrState*>(base + L.partial), terms, seg_cnt, s);
+  if (rc != GDMIX_RE_OK) return rc;
+  const int groups = (int)acc_groups(M);
+  hipLaunchKernelGGL(aupr_acc_groups_kernel, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, s, (const double*)terms, M, group_sum);
+  hipLaunchKernelGGL(aupr_acc_total_kernel, dim3(1), dim3(EVAL_THREADS), 0, s, (const double*)group_sum, groups, pr_sum);
+  HIP_TRY(hipGetLastError());
+  uint32_t cnt[2] = {0, 0};
+  double sum = 0.0;
+  HIP_TRY(hipMemcpyAsync(cnt, seg_cnt, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&sum, pr_sum, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  host_out->pr_sum = sum;
+  host_out->n_pos = cnt[0];
+  host_out->n_neg = cnt[1];
+  host_out->n_nan = M - (int64_t)cnt[0] - (int64_t)cnt[1];
   return GDMIX_RE_OK;
 }
 

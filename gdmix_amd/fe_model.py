@@ -111,7 +111,7 @@ class FixedLRParams(LRParams):
     # --action=inference accepts and ignores the flag.
     coefficient_constraints: Optional[str] = None
     # not in the reference; the random-effect stage's flag of the same name (params.REParams). A fixed effect has no entities: the list
-    # holds LOGISTIC_LOSS only, and the stage's evalSummary.json gains "logistic_loss" and "ll". Needs metric_output_dir and
+    # holds LOGISTIC_LOSS and AUPR only, and the stage's evalSummary.json gains "logistic_loss" and "ll", "aupr" and "pr_sum". Needs metric_output_dir and
     # --model_type=logistic_regression; does not run with l2_reg_weights.
     evaluators: Optional[str] = None
     # the random-effect stage's flag (params.REParams). This stage's parser ignores flags it does not know, so the field exists to refuse
@@ -263,7 +263,7 @@ class FixedEffectLRModelLBFGS:
         self.training_output_dir = base_training_params.training_score_dir
         self.validation_output_dir = base_training_params.validation_score_dir
         self.model_type = base_training_params.model_type
-        self.evaluator_spec = p.evaluator_spec()      # --evaluators (params.EvaluatorSpec: LOGISTIC_LOSS only here), or None
+        self.evaluator_spec = p.evaluator_spec()      # --evaluators (params.EvaluatorSpec: LOGISTIC_LOSS and AUPR here), or None
         check_evaluators_model_type(self.evaluator_spec, self.model_type)
         self.training_data_dir = p.training_data_dir
         self.validation_data_dir = p.validation_data_dir

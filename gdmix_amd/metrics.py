@@ -4,6 +4,9 @@ csrc/re_evaluate.hip). What gdmix-data's Evaluator.scala computes in a Spark job
 The device returns integers (twoU, n_pos, n_neg, n_nan) and the fp64 sum of squared errors; the divisions are done here, from exact
 integers. Unweighted, as the Evaluator is. There is no CPU fallback: the host functions below state the key and the division, they do
 not evaluate.
+
+AUPR (include/gdmix_re.h, "AUPR"): AuprEvaluator returns the device's fixed-shape fp64 sum of the trapezoid's terms and the counts, per entity
+and over the keys a DeviceEvaluator has accumulated; aupr_from_sum divides.
 """
 import ctypes as C
 import json
@@ -17,6 +20,7 @@ from . import solver as _solver
 
 AUC, MSE = "auc", "mse"
 POISSON_LOSS = "poisson_loss"        # mean of exp(s) - y s: the metric of a poisson_regression stage (include/gdmix_re.h, "poisson evaluation")
+AUPR = "aupr"                        # area under the precision-recall curve (include/gdmix_re.h, "AUPR"): --evaluators=AUPR,AUPR:<id>
 LOGISTIC_LOSS = "logistic_loss"      # mean of the logistic loss of a score (include/gdmix_re.h, "ranking evaluation"): --evaluators=LOGISTIC_LOSS
 
 
@@ -115,6 +119,22 @@ def ranking_entities_to_host(res, ks) -> dict:
     return h
 
 
+def aupr_from_sum(pr_sum, n_pos) -> float:
+    """AUPR = pr_sum / n_pos, one fp64 division of the device's sum by the exactly converted count; NaN without a positive."""
+    n_pos = int(n_pos)
+    return float("nan") if n_pos == 0 else float(pr_sum) / n_pos
+
+
+def aupr_entities_to_host(res) -> dict:
+    """The tensors of AuprEvaluator.entities -> numpy arrays, with `n` (every sample, NaN scores included) and `aupr` NaN for an entity
+    with a NaN score (the device wrote it NaN for an entity without a positive)."""
+    h = {k: _solver.host_array(v) for k, v in res.items()}
+    aupr = h["aupr"].copy()
+    aupr[h["n_nan"] > 0] = np.nan
+    h.update(n=h["n_pos"].astype(np.int64) + h["n_neg"] + h["n_nan"], aupr=aupr)
+    return h
+
+
 def poisson_entities_to_host(res) -> dict:
     """The tensors of PoissonEvaluator.entities -> numpy arrays, with `n` (every sample, NaN scores included) and `poisson_loss`
     (pl / n, NaN for an entity without samples or with a NaN score)."""
@@ -133,9 +153,11 @@ PER_ENTITY_SCHEMA = {"type": "record", "name": "EntityMetricAvro", "namespace": 
     {"name": "auc", "type": ["null", "double"]}, {"name": "mse", "type": "double"}]}
 PER_ENTITY_POISSON_SCHEMA = {"type": "record", "name": "EntityPoissonMetricAvro", "namespace": "gdmix_amd", "fields": [
     {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "poisson_loss", "type": "double"}]}
-def ranking_entity_schema(ks) -> dict:
-    """PER_ENTITY_SCHEMA with one nullable double per requested k behind it (null: a NaN score in the entity)."""
-    return dict(PER_ENTITY_SCHEMA, fields=PER_ENTITY_SCHEMA["fields"] + [{"name": precision_key(k), "type": ["null", "double"]} for k in ks])
+def ranking_entity_schema(ks, aupr=False) -> dict:
+    """PER_ENTITY_SCHEMA with one nullable double per requested k behind it (null: a NaN score in the entity), and with `aupr` one more
+    for AUPR (null: a NaN score, or no positive)."""
+    more = [precision_key(k) for k in ks] + ([AUPR] if aupr else [])
+    return dict(PER_ENTITY_SCHEMA, fields=PER_ENTITY_SCHEMA["fields"] + [{"name": name, "type": ["null", "double"]} for name in more])
 
 
 SUMMARY_KEYS = ("n", "n_pos", "n_neg", "n_nan", "two_u", "sse")
@@ -387,6 +409,39 @@ class RankingEvaluator(_Evaluator):
         return dict(res, **counts) if with_auc else counts
 
 
+class AuprEvaluator(_Evaluator):
+    """AUPR on one MI355X through the solver's context: `entities` per entity of a scored batch (gdmix_re_eval_aupr_entities), `finish`
+    over the keys a DeviceEvaluator has accumulated (gdmix_re_eval_aupr_acc_finish): a stage keeps one set of keys for AUC and AUPR."""
+    OUTPUTS = (("pr_sum", "float64"), ("n_pos", "int32"), ("n_neg", "int32"), ("n_nan", "int32"), ("aupr", "float64"))
+    OUT_STRUCT = _solver._EvalAuprOut
+    to_host = staticmethod(aupr_entities_to_host)
+
+    def entities(self, packed_or_ent_row_ptr, score, label=None, workspace_bytes=None) -> dict:
+        """-> {"pr_sum" float64, "n_pos", "n_neg", "n_nan" int32, "aupr" float64}: device tensors, one entry per entity."""
+        t, s = self.torch, self.solver
+        rp, score, label, E, N, res, c_out = self._entities_args(packed_or_ent_row_ptr, score, label)
+        nbytes = int(self.lib.gdmix_re_eval_aupr_workspace_bytes(E, N)) if workspace_bytes is None else int(workspace_bytes)
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=s.device)
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_aupr_entities(s._h, rp.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
+                                                                C.byref(c_out), ws.data_ptr(), nbytes, s._stream()), "gdmix_re_eval_aupr_entities")
+        return res
+
+    def finish(self, evaluator) -> dict:
+        """evaluator: a DeviceEvaluator of this solver -> {"aupr", "pr_sum", "n", "n_pos", "n_neg", "n_nan"} over everything added to it;
+        AUPR is NaN when a score was NaN or there is no positive. The accumulator stays as it is."""
+        t, s = self.torch, self.solver
+        nbytes = int(self.lib.gdmix_re_eval_aupr_acc_workspace_bytes(evaluator.count))
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=s.device)
+        tot = _solver._EvalAuprTotals()
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_aupr_acc_finish(s._h, C.byref(evaluator._acc), ws.data_ptr(), nbytes, C.byref(tot), s._stream()),
+                           "gdmix_re_eval_aupr_acc_finish")
+        n_pos, n_nan = int(tot.n_pos), int(tot.n_nan)
+        return {AUPR: float("nan") if n_nan > 0 else aupr_from_sum(tot.pr_sum, n_pos), "pr_sum": float(tot.pr_sum),
+                "n": int(tot.n), "n_pos": n_pos, "n_neg": int(tot.n_neg), "n_nan": n_nan}
+
+
 EVALUATOR_OF_METRIC = {AUC: DeviceEvaluator, MSE: DeviceEvaluator, POISSON_LOSS: PoissonEvaluator}
 
 
@@ -418,7 +473,9 @@ class StageMetrics:
                                                                that data: an entity with active and passive training data has two or more) that
                                                                have both classes, and how many those are
         "precision@K:<id>", "precision@K:<id>_records"         the mean of precision@K over the records with a sample, per requested K
-    and the records one nullable double precision_at_K per K. Each mean is math.fsum of the records' values over their number: the sum is
+        "aupr", "pr_sum"                                       AUPR over the block's samples and the device's sum (AuprEvaluator.finish)
+        "aupr:<id>", "aupr:<id>_records"                       the mean of aupr over the records with a positive
+    and the records one nullable double precision_at_K per K and, for AUPR:<id>, one nullable double aupr. Each mean is math.fsum of the records' values over their number: the sum is
     exact, so the value depends on no order or grouping of partitions. Any record with a NaN score makes it NaN (null), as the stage
     metric. Without `spec` every file is byte for byte what it was."""
 
@@ -432,9 +489,11 @@ class StageMetrics:
         self.ll = {}             # which -> LogLossEvaluator (spec.log_loss)
         self.ranking = None      # RankingEvaluator (spec.ranking): one device call gives the per-entity AUC outputs and precision@k
         self.records = {}        # which -> {"nan": records with a NaN score, "auc": [values], precision_key(k): [values]}
+        self.per_entity = spec is not None and (spec.ranking or spec.aupr_entity)      # the items whose values are means over records
         if spec is not None and spec.ranking:
             self.ks = spec.ks if spec.ks else (1,)      # AUC:<id> alone still takes the one call; its k is not reported
-            self.entity_schema = ranking_entity_schema(spec.ks)
+        if self.per_entity:
+            self.entity_schema = ranking_entity_schema(spec.ks, spec.aupr_entity)
 
     def add_log_loss(self, which, score, label):
         """--evaluators=LOGISTIC_LOSS: the scores of a batch (device) -> `which`'s log-loss accumulator. Nothing without it."""
@@ -462,12 +521,17 @@ class StageMetrics:
         if self.spec is not None and self.spec.ranking:
             if self.ranking is None:
                 self.ranking = RankingEvaluator(self.solver, self.ks)
-            return self.ranking.to_host(self.ranking.entities(packed, logit))
-        return ev.to_host(ev.entities(packed, logit))
+            host = self.ranking.to_host(self.ranking.entities(packed, logit))
+        else:
+            host = ev.to_host(ev.entities(packed, logit))
+        if self.spec is not None and self.spec.aupr_entity:
+            pr = AuprEvaluator(self.solver)
+            host[AUPR] = pr.to_host(pr.entities(packed, logit))[AUPR]
+        return host
 
     def _collect(self, which, host, e0, e1):
         """The records just written -> the values the aggregates of `which` are taken over."""
-        r = self.records.setdefault(which, dict({"nan": 0, "auc": []}, **{precision_key(k): [] for k in self.spec.ks}))
+        r = self.records.setdefault(which, dict({"nan": 0, "auc": [], AUPR: []}, **{precision_key(k): [] for k in self.spec.ks}))
         sl = slice(e0, e1)
         r["nan"] += int(np.count_nonzero(host["n_nan"][sl] > 0))
         both = (host["n_pos"][sl] > 0) & (host["n_neg"][sl] > 0) & (host["n_nan"][sl] == 0)
@@ -475,6 +539,8 @@ class StageMetrics:
         some = (host["n"][sl] >= 1) & (host["n_nan"][sl] == 0)
         for k in self.spec.ks:
             r[precision_key(k)].extend(host[precision_key(k)][sl][some].tolist())
+        if self.spec.aupr_entity:
+            r[AUPR].extend(host[AUPR][sl][(host["n_pos"][sl] > 0) & (host["n_nan"][sl] == 0)].tolist())
 
     def write_entities(self, which, output_file, entity_ids, host, e0=0, e1=None):
         from .io import avro
@@ -490,24 +556,31 @@ class StageMetrics:
         fields = [(f["name"], as_type[f["type"]] if isinstance(f["type"], str) else nullable) for f in self.entity_schema["fields"][1:]]
         recs = [dict({"entityId": str(entity_ids[i])}, **{k: conv(host[k][e0 + i]) for k, conv in fields}) for i in range(e1 - e0)]
         avro.write_file(os.path.join(d, name), self.entity_schema, recs)
-        if self.spec is not None and self.spec.ranking:
+        if self.per_entity:
             self._collect(which, host, e0, e1)
 
     def _aggregates(self, which) -> dict:
-        """The block's keys of --evaluators for `which` (in a fixed order: the log loss, the mean AUC, precision@k as listed)."""
+        """The block's keys of --evaluators for `which` (in a fixed order: the log loss, the mean AUC, precision@k as listed, AUPR, the
+        mean AUPR)."""
         import math
         out = {}
         if self.spec.log_loss and which in self.ll:
             r = self.ll[which].finish()
             out[LOGISTIC_LOSS], out["ll"] = _json_number(r[LOGISTIC_LOSS]), r["ll"]
+        r = self.records.get(which, {"nan": 0, "auc": [], AUPR: []})
+        mean = lambda v: None if r["nan"] > 0 or not v else math.fsum(v) / len(v)
         if self.spec.ranking:
-            r = self.records.get(which, {"nan": 0, "auc": []})
-            mean = lambda v: None if r["nan"] > 0 or not v else math.fsum(v) / len(v)
             if self.spec.auc:
                 out[f"auc:{self.spec.entity}"], out[f"auc:{self.spec.entity}_records"] = mean(r["auc"]), len(r["auc"])
             for k in self.spec.ks:
                 v = r.get(precision_key(k), [])
                 out[f"precision@{k}:{self.spec.entity}"], out[f"precision@{k}:{self.spec.entity}_records"] = mean(v), len(v)
+        if self.spec.aupr:
+            ev = self.ev[which]
+            tot = AuprEvaluator(ev.solver).finish(ev)
+            out[AUPR], out["pr_sum"] = _json_number(tot[AUPR]), tot["pr_sum"]
+        if self.spec.aupr_entity:
+            out[f"aupr:{self.spec.entity}"], out[f"aupr:{self.spec.entity}_records"] = mean(r[AUPR]), len(r[AUPR])
         return out
 
     def write_summary(self):

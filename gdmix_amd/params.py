@@ -199,11 +199,14 @@ def parse_l2_grid(text):
 
 @dataclass(frozen=True)
 class EvaluatorSpec:
-    """What --evaluators asks for: the logistic loss, the mean per-entity AUC, precision@k for these k (in the order given)."""
+    """What --evaluators asks for: the logistic loss, the mean per-entity AUC, precision@k for these k (in the order given), the stage-wide
+    AUPR and the mean per-entity AUPR."""
     log_loss: bool = False
     auc: bool = False
     ks: tuple = ()
     entity: Optional[str] = None
+    aupr: bool = False             # AUPR
+    aupr_entity: bool = False      # AUPR:<id>
 
     @property
     def ranking(self):
@@ -214,9 +217,9 @@ MAX_PRECISION_KS = 4      # values of K in one list: what one device call ranks 
 
 
 def parse_evaluators(text, entity, fixed_effect=False):
-    """--evaluators=LIST (Photon-ML's evaluator names, any case, comma-separated): LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, with <id>
-    the stage's --partition_entity (`entity`), K an integer >= 1, at most four distinct K, no item twice. A fixed-effect stage takes
-    LOGISTIC_LOSS only. -> EvaluatorSpec; ValueError for anything else."""
+    """--evaluators=LIST (Photon-ML's evaluator names, any case, comma-separated): LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, AUPR,
+    AUPR:<id>, with <id> the stage's --partition_entity (`entity`), K an integer >= 1, at most four distinct K, no item twice. A
+    fixed-effect stage takes the items that name no entity: LOGISTIC_LOSS and AUPR. -> EvaluatorSpec; ValueError for anything else."""
     log_loss, auc, ks, seen = False, False, [], set()
     for raw in str(text).split(","):
         item = raw.strip()
@@ -234,14 +237,18 @@ def parse_evaluators(text, entity, fixed_effect=False):
             key = ("PRECISION", k)
         elif kind in ("AUC", "LOGISTIC_LOSS"):
             key = (kind,)
+        elif kind == "AUPR":
+            key = ("AUPR:",) if colon else ("AUPR",)      # over the stage, or the mean over its entities: two items
         else:
-            raise ValueError(f"--evaluators={text!r}: {item!r} is none of LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>")
-        if key[0] == "LOGISTIC_LOSS":
+            raise ValueError(f"--evaluators={text!r}: {item!r} is none of LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, AUPR, AUPR:<id>")
+        if key[0] == "AUPR":
+            pass                                          # over all samples, of either kind of stage
+        elif key[0] == "LOGISTIC_LOSS":
             if colon:
                 raise ValueError(f"--evaluators={text!r}: {item!r}: LOGISTIC_LOSS is taken over all samples and names no entity")
         else:
             if fixed_effect:
-                raise ValueError(f"--evaluators={text!r}: {item!r}: a fixed effect has no entities (it takes LOGISTIC_LOSS only)")
+                raise ValueError(f"--evaluators={text!r}: {item!r}: a fixed effect has no entities (it takes LOGISTIC_LOSS and AUPR only)")
             if not colon or not ident.strip():
                 raise ValueError(f"--evaluators={text!r}: {item!r} names no entity: {name.strip()}:<id>, with <id> the stage's --partition_entity")
             if entity is None or ident.strip() != entity:
@@ -253,11 +260,11 @@ def parse_evaluators(text, entity, fixed_effect=False):
             log_loss = True
         elif key[0] == "AUC":
             auc = True
-        else:
+        elif key[0] == "PRECISION":
             ks.append(key[1])
             if len(ks) > MAX_PRECISION_KS:
                 raise ValueError(f"--evaluators={text!r}: more than {MAX_PRECISION_KS} distinct K")
-    return EvaluatorSpec(log_loss, auc, tuple(ks), None if fixed_effect else entity)
+    return EvaluatorSpec(log_loss, auc, tuple(ks), None if fixed_effect else entity, ("AUPR",) in seen, ("AUPR:",) in seen)
 
 
 def check_evaluators(p, entity, fixed_effect=False):
@@ -399,9 +406,10 @@ class REParams(LRParams):
     optimizer: str = "LBFGS"
     # ... and so is --coefficient_constraints: this stage's box constraints are --entity_coefficient_constraints (below).
     coefficient_constraints: Optional[str] = None
-    # not in the reference (Photon-ML's evaluator names): LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, comma-separated, any case, <id> this
-    # stage's partition_entity. The stage's evalSummary.json gains the logistic loss and the means of the per-entity AUC and precision@K,
-    # its perEntity records precision_at_K (include/gdmix_re.h, "ranking evaluation"; metrics.py). Needs metric_output_dir and
+    # not in the reference (Photon-ML's evaluator names): LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, AUPR, AUPR:<id>, comma-separated, any
+    # case, <id> this stage's partition_entity. The stage's evalSummary.json gains the logistic loss, the means of the per-entity AUC and
+    # precision@K, AUPR and the mean per-entity AUPR, its perEntity records precision_at_K and aupr (include/gdmix_re.h, "ranking
+    # evaluation", "AUPR"; metrics.py). Needs metric_output_dir and
     # --model_type=logistic_regression; does not run with l2_reg_weights. --action=inference honours it when the data has labels.
     evaluators: Optional[str] = None
     # not in the reference (Photon-ML's elastic net per random-effect coordinate): alpha in [0, 1], with l2_reg_weight as its lambda: every

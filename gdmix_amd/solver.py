@@ -100,6 +100,14 @@ class _EvalTopkOut(C.Structure):
     _fields_ = [("hits_sure", C.c_void_p), ("slots", C.c_void_p), ("tie_pos", C.c_void_p), ("tie_size", C.c_void_p)]
 
 
+class _EvalAuprOut(C.Structure):
+    _fields_ = [("pr_sum", C.c_void_p), ("n_pos", C.c_void_p), ("n_neg", C.c_void_p), ("n_nan", C.c_void_p), ("aupr", C.c_void_p)]
+
+
+class _EvalAuprTotals(C.Structure):
+    _fields_ = [("pr_sum", C.c_double), ("n", C.c_int64), ("n_pos", C.c_int64), ("n_neg", C.c_int64), ("n_nan", C.c_int64)]
+
+
 class _DownsampleOpts(C.Structure):
     _fields_ = [("rate", C.c_double), ("seed", C.c_uint64), ("negatives_only", C.c_int32), ("reserved", C.c_int32)]
 
@@ -162,6 +170,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_eval_pl_entities", "gdmix_re_eval_pl_acc_reset", "gdmix_re_eval_pl_acc_add", "gdmix_re_eval_pl_acc_finish",
     "gdmix_re_eval_topk_workspace_bytes", "gdmix_re_eval_topk_entities",
     "gdmix_re_eval_ll_entities", "gdmix_re_eval_ll_acc_reset", "gdmix_re_eval_ll_acc_add", "gdmix_re_eval_ll_acc_finish",
+    "gdmix_re_eval_aupr_workspace_bytes", "gdmix_re_eval_aupr_entities", "gdmix_re_eval_aupr_acc_workspace_bytes", "gdmix_re_eval_aupr_acc_finish",
     "gdmix_re_join_features", "gdmix_re_score_models_workspace_bytes", "gdmix_re_score_models",
     "gdmix_re_prior_workspace_bytes", "gdmix_re_prior_apply", "gdmix_re_prior_restore",
     "gdmix_re_feature_extent", "gdmix_re_feature_moments", "gdmix_re_feature_scale_expand",
@@ -310,6 +319,13 @@ def load_library():
     lib.gdmix_re_eval_topk_workspace_bytes.restype = C.c_size_t
     lib.gdmix_re_eval_topk_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int,
                                                 C.POINTER(_EvalTopkOut), C.POINTER(_EvalOut), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.gdmix_re_eval_aupr_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.gdmix_re_eval_aupr_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_eval_aupr_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(_EvalAuprOut), C.c_void_p,
+                                                C.c_size_t, C.c_void_p]
+    lib.gdmix_re_eval_aupr_acc_workspace_bytes.argtypes = [C.c_int64]
+    lib.gdmix_re_eval_aupr_acc_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_eval_aupr_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalAcc), C.c_void_p, C.c_size_t, C.POINTER(_EvalAuprTotals), C.c_void_p]
     lib.gdmix_re_join_features.argtypes = [C.c_void_p, C.POINTER(_Packed), C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gdmix_re_score_models_workspace_bytes.argtypes = [C.c_int64, C.c_int]
     lib.gdmix_re_score_models_workspace_bytes.restype = C.c_size_t

@@ -570,7 +570,7 @@ GDMIX_API const char* gdmix_re_class_kernel_name(int c);
  * The device returns the INTEGERS and the fp64 SSE; the global division is the caller's, from exact integers. Per entity the device also
  * writes auc[e] = (double)twoU / (2.0 * (double)n_pos * (double)n_neg), one division of exactly converted integers: exact (correctly
  * rounded) for entities below 2^26 samples — a caller redoes the division for larger ones.
- * Out of scope: sample weights in the metric; AUPR and RMSE (the Poisson loss, precision@k and the logistic loss have sections of their own
+ * Out of scope: sample weights in the metric; RMSE (the Poisson loss, precision@k, the logistic loss and AUPR have sections of their own
  * below); combining the accumulators of several workers (each worker
  * finishes its own; from the counts a caller can combine MSE exactly and AUC not at all). */
 typedef struct {          /* device pointers, [E] each; any may be NULL */
@@ -723,6 +723,51 @@ GDMIX_API int gdmix_re_eval_ll_entities(gdmix_re_ctx* ctx, const int64_t* ent_ro
 GDMIX_API int gdmix_re_eval_ll_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_ll_acc* acc, void* stream);
 GDMIX_API int gdmix_re_eval_ll_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_ll_acc* acc, const float* score, const float* label, int64_t N, void* stream);
 GDMIX_API int gdmix_re_eval_ll_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_ll_acc* acc, gdmix_re_eval_ll_totals* host_out, void* stream);
+
+/* ---- (ABI 27, additions) AUPR: the area under the precision-recall curve, per entity and over a whole stage ---------------------------------
+ * What Photon-ML's AUPR evaluator reports: Spark's BinaryClassificationMetrics.areaUnderPR without binning. The statement below is the one
+ * this library holds itself to; the match with Spark is by reading its definition, not by a run against it. csrc/re_evaluate.hip.
+ *
+ * Definitions, over the VALID samples (score not NaN; scores compare by the key of "evaluation": -0 equals +0, infinities order as usual;
+ * label positive <=> label > 0.5f)
+ *   thresholds  c_1 > c_2 > ... > c_G the distinct scores. For j = 1 .. G: T_j, F_j the positives and negatives with score >= c_j,
+ *               T_0 = F_0 = 0, t_j = T_j - T_(j-1), P_j = T_j / (T_j + F_j) for j >= 1 and P_0 := P_1.
+ *   pr_sum      sum_j t_j * (P_(j-1) + P_j) / 2: the trapezoid over every distinct threshold with the first point at (0, P_1). A whole tie
+ *               group is one threshold, as for AUC. AUPR = pr_sum / n_pos, NaN when n_pos == 0. One tie group: n_pos / n; n_neg == 0: 1.
+ *   terms       P = (double)T / (double)(T + F), one division; term_j = (double)t_j * (0.5 * (P_(j-1) + P_j)); only groups with t_j > 0
+ *               contribute, and every term is >= 0. Every path forms a term with these operations: the same bits per term.
+ *   sums        trees of fixed shape (csrc/re_eval_sum.hpp), never a floating-point atomic, the same bits from run to run.
+ *               |pr_sum - exact| <= 3e-13 * exact: fewer than 2 211 roundings in the longest chain of additions and four in a term (the
+ *               bound the Poisson sum states for the same trees). Entities of the register path and of the sort path add the same
+ *               terms in different trees: their pr_sum may differ in the last bits, and both lie inside the bound.
+ *   NaN         a NaN score is counted (n_nan) and left out of every count and sum; gdmix_amd/metrics.py reports NaN when n_nan > 0.
+ *   limits      those of gdmix_re_eval_entities: fewer than 2^31 samples and entities (GDMIX_RE_ERANGE), the workspace (GDMIX_RE_ENOMEM).
+ * Per entity: entities of at most 64 samples in registers, four per wavefront (aupr_small_kernel: a lane counts the positives and negatives
+ * above and at its key through LDS; one lane per tie group forms the term; no sort); larger ones by the (entity, key) radix sort with the
+ * score bits complemented, so a segment's scores descend and every count is a prefix from its head, then a reduce-then-scan pass that
+ * writes one term per sorted key and a workgroup per entity that adds its segment. gdmix_re_set_eval_small_max moves the limit for this
+ * call too. aupr[e] = pr_sum[e] / (double)n_pos[e], NaN when n_pos[e] is 0. Synchronises `stream` once, as gdmix_re_eval_entities does.
+ * Over a stage: gdmix_re_eval_aupr_acc_finish reads the key accumulator that gdmix_re_eval_acc_add fills (one set of keys serves AUC and
+ * AUPR) and leaves it as it found it. The sum runs over positions of the sorted array, so pr_sum is bit for bit independent of how the
+ * samples were split into batches and of the batches' order. Synchronises `stream`; an empty accumulator gives zeros and needs no workspace. */
+typedef struct {          /* device pointers, [E] each; any may be NULL */
+  double*  pr_sum;
+  int32_t* n_pos;
+  int32_t* n_neg;
+  int32_t* n_nan;
+  double*  aupr;
+} gdmix_re_eval_aupr_out;
+typedef struct {          /* host */
+  double  pr_sum;
+  int64_t n;              /* samples added, NaN scores included */
+  int64_t n_pos, n_neg, n_nan;
+} gdmix_re_eval_aupr_totals;
+GDMIX_API size_t gdmix_re_eval_aupr_workspace_bytes(int64_t E, int64_t N);
+GDMIX_API int gdmix_re_eval_aupr_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                          const gdmix_re_eval_aupr_out* out, void* workspace, size_t workspace_bytes, void* stream);
+GDMIX_API size_t gdmix_re_eval_aupr_acc_workspace_bytes(int64_t N);      /* N = acc->count */
+GDMIX_API int gdmix_re_eval_aupr_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_acc* acc, void* workspace, size_t workspace_bytes,
+                                            gdmix_re_eval_aupr_totals* host_out, void* stream);
 
 /* ---- (ABI 14) sweep: K models trained on one batch score another batch in one pass over its non-zeros ----------------------------
  * A stage that sweeps l2_reg_weight (gdmix_amd/sweep.py) solves a training partition K times and scores the validation partition under
