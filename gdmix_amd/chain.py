@@ -177,9 +177,10 @@ def read_scores(score_dir):
             np.array([np.nan if x is None else x for x in lab], np.float32))
 
 
-def partition_stage(root, data, stage, prev_train_scores, prev_valid_scores, num_partitions=4, upper_bound=None, model_type=LOGISTIC):
+def partition_stage(root, data, stage, prev_train_scores, prev_valid_scores, num_partitions=4, upper_bound=None, model_type=LOGISTIC, weights=None):
     """The Spark partition job ahead of a random-effect stage (DataPartitioner.scala:203-380), host side: offsets from the previous
-    stage's score files (update_offsets: inner join on uid, FLOAT), grouping by entity, Java-hash partition ids, active/ layout."""
+    stage's score files (update_offsets: inner join on uid, FLOAT), grouping by entity, Java-hash partition ids, active/ layout.
+    weights: one fp32 weight per sample of `data` — the partitions then carry a "weight" column (stage_argv(..., weighted=True) names it)."""
     ent_col = data["entity"][stage]
     ent = data["user"] if stage == "per_user" else data["movie"]
     out = os.path.join(root, stage, "partition")
@@ -194,16 +195,18 @@ def partition_stage(root, data, stage, prev_train_scores, prev_valid_scores, num
         ptr, cols, vals, dim = bag_rows(data, stage, rows)
         # training data: an entity with more than upper_bound samples keeps group 0 (uid mod (count / upper_bound + 1)) as ACTIVE data,
         # trained on; its other groups are PASSIVE data, only scored (DataPartitioner.scala:322-380)
-        batches = partitioner.build_batches(ent[rows], data["uid"][rows], label[rows].astype(np.float32), off, None, ptr, cols, vals,
+        batches = partitioner.build_batches(ent[rows], data["uid"][rows], label[rows].astype(np.float32), off,
+                                            None if weights is None else np.asarray(weights, np.float32)[rows], ptr, cols, vals,
                                             num_partitions, upper_bound=upper_bound if split else None, split=split, binary_labels=not linear)
-        partitioner.write_partitions(os.path.join(out, name), batches, ent_col, stage, int_entity_ids=True, weight_column_name=None)
+        partitioner.write_partitions(os.path.join(out, name), batches, ent_col, stage, int_entity_ids=True, weight_column_name=None if weights is None else "weight")
         if split:
             parts |= {p for (_, p) in batches}
     dim = data["bags"][stage][3]
     md = {"features": [{"name": stage, "dtype": "float", "shape": [dim], "isSparse": True},
                        {"name": "offset", "dtype": "float", "shape": [], "isSparse": False},
                        {"name": "uid", "dtype": "long", "shape": [], "isSparse": False},
-                       {"name": ent_col, "dtype": "long", "shape": [], "isSparse": False}],
+                       {"name": ent_col, "dtype": "long", "shape": [], "isSparse": False}] +
+                      ([] if weights is None else [{"name": "weight", "dtype": "float", "shape": [], "isSparse": False}]),
           "labels": [{"name": "response", "dtype": "float" if linear else "int", "shape": [], "isSparse": False}]}
     os.makedirs(os.path.join(out, "metadata"), exist_ok=True)
     with open(os.path.join(out, "metadata", "tensor_metadata.json"), "w") as f:
@@ -224,13 +227,14 @@ def metric_dir(root, stage):
     return os.path.join(root, stage, "metrics")
 
 
-def stage_argv(root, stage, model_type=LOGISTIC, device_metrics=False, l2_grids=None, optimizer=None, evaluators=None, entity_optimizer=None):
+def stage_argv(root, stage, model_type=LOGISTIC, device_metrics=False, l2_grids=None, optimizer=None, evaluators=None, entity_optimizer=None, weighted=False):
     """The flat argv gdmix-workflow would hand the trainer for this stage of lr-movieLens.yaml (output under <root>/<stage>/).
     device_metrics: a random-effect stage also reports its metric (--metric_output_dir, not a flag of the reference).
     l2_grids: {stage: "w0,w1,..."} — a stage listed there, the global one included, sweeps l2_reg_weight itself (--l2_reg_weights) and
     reports its metric (a sweep needs the directory). None: the argv of every stage is what it was before the argument existed.
     optimizer: the global stage's --optimizer (LBFGS | TRON). None: no such flag in the argv.
     entity_optimizer: the random-effect stages' --entity_optimizer (LBFGS | TRON). None: no such flag in the argv.
+    weighted: the stage's data carries a "weight" column (partition_stage(..., weights=...)): --weight_column_name=weight.
     evaluators: {stage: "LIST"} — a stage listed there gets --evaluators=LIST and reports its metric (the flag needs the directory)."""
     out = os.path.join(root, stage)
     common = [f"--model_type={model_type}"] + COMMON
@@ -238,6 +242,8 @@ def stage_argv(root, stage, model_type=LOGISTIC, device_metrics=False, l2_grids=
         common = common + [f"--optimizer={optimizer}"]
     if entity_optimizer is not None and stage != "global":
         common = common + [f"--entity_optimizer={entity_optimizer}"]
+    if weighted:
+        common = common + ["--weight_column_name=weight"]
     grid = (l2_grids or {}).get(stage)
     listed = (evaluators or {}).get(stage)
     if (device_metrics and stage != "global") or grid is not None or listed is not None:

@@ -15,6 +15,8 @@
 //                 Device state: a head of ACC_HEAD_BYTES for the metric's totals, then the batch's workgroup sums (acc_group_sums).
 //   Longest chain of roundings: 2 048 + 64 + 64 + 8 + 16 + 8 + 3 < 4 096. The shape depends on the sample count alone: two runs give the
 //   same bits. Never a floating-point atomic.
+// Also here, for the units that rank (re_evaluate.hip, re_evaluate_weighted.hip): the sortable key of a score, the lane width of the
+// four-per-wavefront kernels, the in-order workgroup scan of the reduce-then-scan passes and the lane sum over stored terms.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,6 +63,66 @@ __device__ __forceinline__ double acc_group_tree(const double* __restrict__ grou
     if (i < groups) v += group_sum[i];
   }
   return eval_block_tree(v, lds);
+}
+
+// ---- what the ranking units share ------------------------------------------------------------------------------------------------------
+constexpr uint32_t KEY_NAN = 0xFFFFFFFFu;   // the key of no score (it is the image of a NaN): sorts behind +inf, counted apart
+
+// fp32 score -> uint32 that orders as the floats do; -0 and +0 get one key
+__device__ __forceinline__ uint32_t sortable_key(float s) {
+  if (s != s) return KEY_NAN;
+  uint32_t b = __float_as_uint(s);
+  if (s == 0.0f) b = 0u;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ uint64_t key33(float s, float y) {
+  const uint32_t k = sortable_key(s);
+  return ((uint64_t)k << 1) | (uint64_t)((k != KEY_NAN && y > 0.5f) ? 1u : 0u);
+}
+__device__ __forceinline__ int small_width(int nmax) { return nmax <= 16 ? 16 : (nmax <= 32 ? 32 : 64); }   // lanes per entity of the four-per-wavefront kernels
+
+// inclusive scan of one state per thread in thread order (Hillis-Steele through LDS: 8 steps for 256 threads); S: a state with an
+// associative rank_combine(a, b) (found by its argument type)
+template <int THREADS, class S>
+__device__ __forceinline__ S eval_block_scan(S v, S* lds) {
+  const int t = threadIdx.x;
+  lds[t] = v;
+  __syncthreads();
+  for (int off = 1; off < THREADS; off <<= 1) {
+    S left = v;
+    const bool take = t >= off;
+    if (take) left = lds[t - off];
+    __syncthreads();
+    if (take) v = rank_combine(left, v);
+    lds[t] = v;
+    __syncthreads();
+  }
+  return v;
+}
+
+// the lane sum over stored terms (sse_lane's shape)
+__device__ __forceinline__ double terms_lane(const double* __restrict__ terms, int64_t begin, int64_t end, int64_t stride) {
+  double top = 0.0, total = 0.0, run = 0.0;
+  int in_run = 0, runs = 0;
+  for (int64_t i = begin; i < end; i += stride) {
+    run += terms[i];
+    if (++in_run == EVAL_RUN) {
+      total += run; run = 0.0; in_run = 0;
+      if (++runs == EVAL_RUNS) { top += total; total = 0.0; runs = 0; }
+    }
+  }
+  return top + (total + run);
+}
+
+// a sum v added to an accumulator's (hi, lo) pair without losing the rounding error of the addition
+__device__ __forceinline__ void acc_two_sum(double* pair, double v) {
+  const double hi = pair[0], lo = pair[1];
+  const double s = hi + v, bb = s - hi;
+  const double err = (hi - (s - bb)) + (v - bb);   // TwoSum: hi + v = s + err exactly
+  const double l2 = lo + err;
+  const double h2 = s + l2;                        // FastTwoSum: |s| >= |l2|
+  pair[0] = h2;
+  pair[1] = l2 - (h2 - s);
 }
 
 }  // namespace gdmix

@@ -40,20 +40,9 @@
 
 namespace gdmix {
 
-constexpr uint32_t KEY_NAN = 0xFFFFFFFFu;   // the key of no score (it is the image of a NaN): sorts behind +inf, counted apart
 constexpr int RANK_THREADS = 256, RANK_ITEMS = 16, RANK_TILE = RANK_THREADS * RANK_ITEMS;
 
-// fp32 score -> uint32 that orders as the floats do; -0 and +0 get one key
-__device__ __forceinline__ uint32_t sortable_key(float s) {
-  if (s != s) return KEY_NAN;
-  uint32_t b = __float_as_uint(s);
-  if (s == 0.0f) b = 0u;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ uint64_t key33(float s, float y) {
-  const uint32_t k = sortable_key(s);
-  return ((uint64_t)k << 1) | (uint64_t)((k != KEY_NAN && y > 0.5f) ? 1u : 0u);
-}
+// (KEY_NAN, sortable_key, key33: re_eval_sum.hpp)
 __device__ __forceinline__ double sq_err(float s, float y) {
   const double d = (double)y - (double)s;
   return d * d;
@@ -190,24 +179,10 @@ __device__ __forceinline__ RankState rank_element(uint64_t key, uint64_t prev, b
   r.f = ((first || (key >> 1) != (prev >> 1)) ? 1u : 0u) | ((first || (key >> 33) != (prev >> 33)) ? 2u : 0u);
   return r;
 }
-// inclusive scan of one state per thread in thread order (Hillis-Steele through LDS: 8 steps for 256 threads); S: RankState, or the
-// PrState of the AUPR pass below (rank_combine is overloaded)
+// inclusive scan of one state per thread in thread order (eval_block_scan of re_eval_sum.hpp); S: RankState, or the PrState of the AUPR
+// pass below (rank_combine is overloaded)
 template <class S>
-__device__ __forceinline__ S rank_block_scan(S v, S* lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int off = 1; off < RANK_THREADS; off <<= 1) {
-    S left = v;
-    const bool take = t >= off;
-    if (take) left = lds[t - off];
-    __syncthreads();
-    if (take) v = rank_combine(left, v);
-    lds[t] = v;
-    __syncthreads();
-  }
-  return v;
-}
+__device__ __forceinline__ S rank_block_scan(S v, S* lds) { return eval_block_scan<RANK_THREADS>(v, lds); }
 // a thread's RANK_ITEMS consecutive keys, folded in order (read from memory here and once more by the walk of rank_scan_kernel: the
 // second read hits the cache, and no key array is held in registers across the workgroup scans)
 __device__ __forceinline__ int rank_count(int64_t M, int64_t first) {
@@ -522,7 +497,6 @@ __device__ __forceinline__ void write_aupr(const AuprOutDev& O, int64_t e, doubl
 // filler): a lane reads its group's 2 W words with W / 2 ds_read_b128 and counts, per class, the keys below its own (Tp, Fp) and not above
 // it (T, F), and the keys equal to its own on lower lanes. The lane of a tie group that finds none there speaks for the group: it forms
 // the term. One fp64 xor-butterfly adds the terms (the same tree on every lane), one integer butterfly the three counts. No sort, no atomics.
-__device__ __forceinline__ int small_width(int nmax) { return nmax <= 16 ? 16 : (nmax <= 32 ? 32 : 64); }   // lanes per entity, as the kernels above
 __global__ __launch_bounds__(64) void aupr_small_kernel(const int64_t* __restrict__ ent_row_ptr, int64_t E, const float* __restrict__ score,
                                                         const float* __restrict__ label, AuprOutDev O, int small_max) {
   __shared__ __attribute__((aligned(16))) uint32_t pos_keys[64];
@@ -663,19 +637,6 @@ __global__ __launch_bounds__(RANK_THREADS) void pr_scan_kernel(const uint64_t* _
   }
 }
 
-// the lane sum of re_eval_sum.hpp over stored terms (sse_lane's shape)
-__device__ __forceinline__ double terms_lane(const double* __restrict__ terms, int64_t begin, int64_t end, int64_t stride) {
-  double top = 0.0, total = 0.0, run = 0.0;
-  int in_run = 0, runs = 0;
-  for (int64_t i = begin; i < end; i += stride) {
-    run += terms[i];
-    if (++in_run == EVAL_RUN) {
-      total += run; run = 0.0; in_run = 0;
-      if (++runs == EVAL_RUNS) { top += total; total = 0.0; runs = 0; }
-    }
-  }
-  return top + (total + run);
-}
 // one workgroup per large entity: the fixed-shape sum over its segment of `terms`, then its outputs
 __global__ __launch_bounds__(EVAL_THREADS) void aupr_big_finish_kernel(const int64_t* __restrict__ ent_row_ptr, const int32_t* __restrict__ big_list,
                                                                        const int32_t* __restrict__ big_off, const double* __restrict__ terms,
@@ -710,6 +671,15 @@ __global__ __launch_bounds__(EVAL_THREADS) void aupr_acc_total_kernel(const doub
   if (threadIdx.x == 0) *pr_sum = v;
 }
 
+// terms[M] -> *sum by the accumulator's two-level sum over positions; group_sum: ACC_MAX_GROUPS doubles (also re_evaluate_weighted.hip's)
+int eval_sum_positions(const double* terms, int64_t M, double* group_sum, double* sum, hipStream_t s) {
+  const int groups = (int)acc_groups(M);
+  hipLaunchKernelGGL(aupr_acc_groups_kernel, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, s, terms, M, group_sum);
+  hipLaunchKernelGGL(aupr_acc_total_kernel, dim3(1), dim3(EVAL_THREADS), 0, s, (const double*)group_sum, groups, sum);
+  HIP_TRY(hipGetLastError());
+  return GDMIX_RE_OK;
+}
+
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int64_t rank_tiles(int64_t M) { return (M + RANK_TILE - 1) / RANK_TILE; }
 
@@ -739,7 +709,7 @@ static int rank_sum(const uint64_t* sorted, int64_t M, int64_t segments, RankSta
   return GDMIX_RE_OK;
 }
 
-static int sort_keys(gdmix_ctx_impl* ci, uint64_t* in, uint64_t* out, int64_t M, unsigned end_bit, hipStream_t s, bool descending = false) {
+int sort_keys(gdmix_ctx_impl* ci, uint64_t* in, uint64_t* out, int64_t M, unsigned end_bit, hipStream_t s, bool descending) {
   unsigned long long* const none = nullptr;
   size_t bytes = 0;
   if (descending) HIP_TRY((rocprim::radix_sort_keys_desc(nullptr, bytes, none, none, (size_t)M, 0u, end_bit, s)));
@@ -823,20 +793,11 @@ static int pr_terms(const uint64_t* sorted, int64_t M, uint32_t nan32, PrState* 
 // segments of the large entities in their order, segment b at big_off[b], a NaN score's key last in its segment. With flip = all ones
 // (eval_big_keys_kernel) a segment's scores descend and its NaN keys (score bits 0) come first.
 struct SortedBig { int64_t nbig, M; int32_t* big_list; int32_t* big_off; uint64_t* sorted; RankState* partial; uint64_t* acc_two_u; uint32_t* acc_cnt; };
-static int sort_big_entities(gdmix_ctx_impl* ci, const char* who, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
-                             int small_max, const EvalLayout& L, char* base, hipStream_t s, SortedBig* B, uint32_t flip = 0u) {
-  int64_t* mark = reinterpret_cast<int64_t*>(base + L.mark);
-  int64_t* offs = reinterpret_cast<int64_t*>(base + L.offs);
-  int32_t* big_list = reinterpret_cast<int32_t*>(base + L.big_list);
-  int32_t* big_off = reinterpret_cast<int32_t*>(base + L.big_off);
-  uint64_t* keys_a = reinterpret_cast<uint64_t*>(base + L.keys_a);
-  uint64_t* keys_b = reinterpret_cast<uint64_t*>(base + L.keys_b);
-  B->nbig = 0; B->M = 0;
-  B->big_list = big_list; B->big_off = big_off; B->sorted = keys_b;
-  B->partial = reinterpret_cast<RankState*>(base + L.partial);
-  B->acc_two_u = reinterpret_cast<uint64_t*>(base + L.acc_two_u);
-  B->acc_cnt = reinterpret_cast<uint32_t*>(base + L.acc_cnt);
-  // the entities of the sort path: numbered and laid out by one prefix sum
+// the entities of the sort path, numbered and laid out by one prefix sum (the call's one synchronisation): mark, offs [E + 1] int64,
+// big_list, big_off [E + 1] int32 of the caller's workspace; *nbig of them with *M samples (re_evaluate_weighted.hip numbers its own so)
+int eval_number_big(gdmix_ctx_impl* ci, const char* who, const int64_t* ent_row_ptr, int64_t E, int64_t N, int small_max, int64_t* mark, int64_t* offs,
+                    int32_t* big_list, int32_t* big_off, hipStream_t s, int64_t* nbig_out, int64_t* M_out) {
+  *nbig_out = 0; *M_out = 0;
   hipLaunchKernelGGL(eval_mark_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, s, ent_row_ptr, E, small_max, mark);
   HIP_TRY(hipGetLastError());
   size_t scan_bytes = 0;
@@ -851,6 +812,25 @@ static int sort_big_entities(gdmix_ctx_impl* ci, const char* who, const int64_t*
   if (nbig == 0) return GDMIX_RE_OK;
   if (M > N) { set_error("%s: ent_row_ptr covers %lld samples, N is %lld", who, (long long)M, (long long)N); return GDMIX_RE_EINVAL; }
   hipLaunchKernelGGL(eval_big_list_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, (const int64_t*)mark, (const int64_t*)offs, E, big_list, big_off);
+  HIP_TRY(hipGetLastError());
+  *nbig_out = nbig; *M_out = M;
+  return GDMIX_RE_OK;
+}
+static int sort_big_entities(gdmix_ctx_impl* ci, const char* who, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                             int small_max, const EvalLayout& L, char* base, hipStream_t s, SortedBig* B, uint32_t flip = 0u) {
+  int32_t* big_list = reinterpret_cast<int32_t*>(base + L.big_list);
+  int32_t* big_off = reinterpret_cast<int32_t*>(base + L.big_off);
+  uint64_t* keys_a = reinterpret_cast<uint64_t*>(base + L.keys_a);
+  uint64_t* keys_b = reinterpret_cast<uint64_t*>(base + L.keys_b);
+  B->nbig = 0; B->M = 0;
+  B->big_list = big_list; B->big_off = big_off; B->sorted = keys_b;
+  B->partial = reinterpret_cast<RankState*>(base + L.partial);
+  B->acc_two_u = reinterpret_cast<uint64_t*>(base + L.acc_two_u);
+  B->acc_cnt = reinterpret_cast<uint32_t*>(base + L.acc_cnt);
+  int64_t nbig = 0, M = 0;
+  int rc = eval_number_big(ci, who, ent_row_ptr, E, N, small_max, reinterpret_cast<int64_t*>(base + L.mark), reinterpret_cast<int64_t*>(base + L.offs), big_list,
+                           big_off, s, &nbig, &M);
+  if (rc != GDMIX_RE_OK || nbig == 0) return rc;
   if (M > 0) hipLaunchKernelGGL(eval_big_keys_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, ent_row_ptr, (const int32_t*)big_list,
                                 (const int32_t*)big_off, (int)nbig, M, score, label, flip, keys_a);
   HIP_TRY(hipGetLastError());
@@ -1109,10 +1089,8 @@ GDMIX_API int gdmix_re_eval_aupr_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_ev
   if (rc != GDMIX_RE_OK) return rc;
   rc = pr_terms(sorted, M, KEY_NAN, reinterpret_cast<PrState*>(base + L.partial), terms, seg_cnt, s);
   if (rc != GDMIX_RE_OK) return rc;
-  const int groups = (int)acc_groups(M);
-  hipLaunchKernelGGL(aupr_acc_groups_kernel, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, s, (const double*)terms, M, group_sum);
-  hipLaunchKernelGGL(aupr_acc_total_kernel, dim3(1), dim3(EVAL_THREADS), 0, s, (const double*)group_sum, groups, pr_sum);
-  HIP_TRY(hipGetLastError());
+  rc = eval_sum_positions(terms, M, group_sum, pr_sum, s);
+  if (rc != GDMIX_RE_OK) return rc;
   uint32_t cnt[2] = {0, 0};
   double sum = 0.0;
   HIP_TRY(hipMemcpyAsync(cnt, seg_cnt, 8, hipMemcpyDeviceToHost, s));

@@ -140,15 +140,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pl_acc_add_kernel(const flo
 __global__ __launch_bounds__(EVAL_THREADS) void eval_pl_acc_sum_kernel(const double* __restrict__ group_sum, int groups, double* __restrict__ state) {
   __shared__ double lds[EVAL_THREADS];
   const double v = acc_group_tree(group_sum, groups, lds);
-  if (threadIdx.x == 0) {
-    const double hi = state[0], lo = state[1];
-    const double s = hi + v, bb = s - hi;
-    const double err = (hi - (s - bb)) + (v - bb);   // TwoSum: hi + v = s + err exactly
-    const double l2 = lo + err;
-    const double h2 = s + l2;                        // FastTwoSum: |s| >= |l2|
-    state[0] = h2;
-    state[1] = l2 - (h2 - s);
-  }
+  if (threadIdx.x == 0) acc_two_sum(state, v);   // TwoSum, then FastTwoSum (re_eval_sum.hpp)
 }
 
 // ---- the entry points' bodies: one per call, instantiated for the two terms ("gdmix_re_eval_pl" / "gdmix_re_eval_ll" in the messages) ------
@@ -219,11 +211,202 @@ static int term_acc_finish(const char* who, gdmix_re_ctx* ctx, const gdmix_re_ev
   return GDMIX_RE_OK;
 }
 
+// ---- the weighted log loss (include/gdmix_re.h, "weighted evaluation"): LL_w = sum w ce and W = sum w -----------------------------------------
+// The kernels above with a weight factor and a second sum, in the same trees. A bad weight (NaN, infinite, negative) is counted and the sample
+// left out; a NaN score under a good weight is counted as above. The accumulator's state: (hi, lo) of LL_w, (hi, lo) of W, the two counts
+// (u64) in its head; then a batch's workgroup sums of w ce and, ACC_MAX_GROUPS doubles further, of w.
+struct WllOutDev { double* ll_w; double* w; int32_t* n_nan; int32_t* n_bad; };
+constexpr size_t WLL_STATE_BYTES = ACC_HEAD_BYTES + 2 * (size_t)ACC_MAX_GROUPS * 8;
+
+// sample i of a weighted set -> its two terms (0 when it is left out) and its two flags
+struct WllSample { double t, w; unsigned nan, bad; };
+__device__ __forceinline__ WllSample wll_sample(const float* __restrict__ score, const float* __restrict__ label, const float* __restrict__ weight, int64_t i) {
+#pragma clang fp contract(off)
+  WllSample r = {0.0, 0.0, 0u, 0u};
+  const float wf = weight ? weight[i] : 1.0f;
+  const float s = score[i];
+  if (!(wf >= 0.0f) || wf == INFINITY) r.bad = 1u;
+  else if (s != s) r.nan = 1u;
+  else {
+    r.w = (double)wf + 0.0;                    // (-0 counts as 0)
+    r.t = r.w > 0.0 ? r.w * ll_term(s, label[i]) : 0.0;   // one rounding of the product, never fused into a sum; a weight of 0 adds 0 whatever the score
+  }
+  return r;
+}
+
+__global__ __launch_bounds__(64) void eval_wll_small_kernel(const int64_t* __restrict__ ent_row_ptr, int64_t E, const float* __restrict__ score,
+                                                            const float* __restrict__ label, const float* __restrict__ weight, WllOutDev O, int small_max) {
+  const int lane = threadIdx.x;
+  const int64_t e0 = (int64_t)blockIdx.x * 4;
+  const int64_t last = e0 + 4 < E ? e0 + 4 : E;
+  const int64_t mine = ent_row_ptr[e0 + lane < last ? e0 + lane : last];   // lanes 0 .. 4 matter
+  int64_t rp[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) rp[k] = __shfl(mine, k);
+  int nmax = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t n = rp[k + 1] - rp[k];
+    if (n <= small_max && (int)n > nmax) nmax = (int)n;
+  }
+  const int W = small_width(nmax);   // lanes per entity, as eval_pl_small_kernel
+  const int per_pass = 64 / W;
+  const int g = lane / W, li = lane & (W - 1);
+  for (int pass = 0; pass < W / 16; ++pass) {
+    const int k = pass * per_pass + g;
+    const int64_t start = k == 0 ? rp[0] : (k == 1 ? rp[1] : (k == 2 ? rp[2] : rp[3]));
+    const int64_t end = k == 0 ? rp[1] : (k == 1 ? rp[2] : (k == 2 ? rp[3] : rp[4]));
+    const int64_t n = end - start;
+    const bool ent_ok = e0 + k < E && n <= small_max;
+    WllSample v = {0.0, 0.0, 0u, 0u};
+    if (ent_ok && li < n) v = wll_sample(score, label, weight, start + li);
+    double t = v.t, w = v.w;
+    uint32_t c = v.nan | (v.bad << 16);   // two counts <= 64 in one word
+    for (int off = 1; off < W; off <<= 1) {
+      t += __shfl_xor(t, off);
+      w += __shfl_xor(w, off);
+      c += __shfl_xor(c, off);
+    }
+    if (ent_ok && li == 0) {
+      if (O.ll_w) O.ll_w[e0 + k] = t;
+      if (O.w) O.w[e0 + k] = w;
+      if (O.n_nan) O.n_nan[e0 + k] = (int)(c & 0xFFFFu);
+      if (O.n_bad) O.n_bad[e0 + k] = (int)(c >> 16);
+    }
+  }
+}
+
+// one workgroup per entity of the batch; those of the small path leave at once. Two lane sums of re_eval_sum.hpp's shape, two block trees.
+__global__ __launch_bounds__(EVAL_THREADS) void eval_wll_big_kernel(const int64_t* __restrict__ ent_row_ptr, const float* __restrict__ score,
+                                                                    const float* __restrict__ label, const float* __restrict__ weight, WllOutDev O,
+                                                                    int small_max) {
+  __shared__ double lds[EVAL_THREADS];
+  __shared__ unsigned counts[2];
+  const int64_t e = blockIdx.x;
+  const int64_t r0 = ent_row_ptr[e], r1 = ent_row_ptr[e + 1];
+  if (r1 - r0 <= small_max) return;
+  if (threadIdx.x < 2) counts[threadIdx.x] = 0u;
+  __syncthreads();
+  double top_t = 0.0, total_t = 0.0, run_t = 0.0, top_w = 0.0, total_w = 0.0, run_w = 0.0;
+  int in_run = 0, runs = 0;
+  unsigned nans = 0u, bads = 0u;
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += EVAL_THREADS) {
+    const WllSample v = wll_sample(score, label, weight, i);
+    run_t += v.t; run_w += v.w; nans += v.nan; bads += v.bad;
+    if (++in_run == EVAL_RUN) {
+      total_t += run_t; run_t = 0.0; total_w += run_w; run_w = 0.0; in_run = 0;
+      if (++runs == EVAL_RUNS) { top_t += total_t; total_t = 0.0; top_w += total_w; total_w = 0.0; runs = 0; }
+    }
+  }
+  if (nans) atomicAdd(&counts[0], nans);
+  if (bads) atomicAdd(&counts[1], bads);
+  const double t = eval_block_tree(top_t + (total_t + run_t), lds);   // (its barriers order the counts too)
+  const double w = eval_block_tree(top_w + (total_w + run_w), lds);
+  if (threadIdx.x == 0) {
+    if (O.ll_w) O.ll_w[e] = t;
+    if (O.w) O.w[e] = w;
+    if (O.n_nan) O.n_nan[e] = (int)counts[0];
+    if (O.n_bad) O.n_bad[e] = (int)counts[1];
+  }
+}
+
+__global__ __launch_bounds__(EVAL_THREADS) void eval_wll_acc_add_kernel(const float* __restrict__ score, const float* __restrict__ label,
+                                                                        const float* __restrict__ weight, int64_t N, double* __restrict__ group_sum,
+                                                                        unsigned long long* __restrict__ counts) {
+  __shared__ double lds[EVAL_THREADS];
+  const int64_t stride = (int64_t)gridDim.x * EVAL_THREADS;
+  double total_t = 0.0, run_t = 0.0, total_w = 0.0, run_w = 0.0;
+  int in_run = 0;
+  unsigned nans = 0u, bads = 0u;
+  for (int64_t i = (int64_t)blockIdx.x * EVAL_THREADS + threadIdx.x; i < N; i += stride) {
+    const WllSample v = wll_sample(score, label, weight, i);
+    run_t += v.t; run_w += v.w; nans += v.nan; bads += v.bad;
+    if (++in_run == EVAL_RUN) { total_t += run_t; run_t = 0.0; total_w += run_w; run_w = 0.0; in_run = 0; }
+  }
+  if (nans) atomicAdd(counts, (unsigned long long)nans);
+  if (bads) atomicAdd(counts + 1, (unsigned long long)bads);
+  const double t = eval_block_tree(total_t + run_t, lds);
+  const double w = eval_block_tree(total_w + run_w, lds);
+  if (threadIdx.x == 0) { group_sum[blockIdx.x] = t; group_sum[ACC_MAX_GROUPS + blockIdx.x] = w; }
+}
+// the workgroup sums of a batch -> two sums, each added to its (hi, lo) pair
+__global__ __launch_bounds__(EVAL_THREADS) void eval_wll_acc_sum_kernel(const double* __restrict__ group_sum, int groups, double* __restrict__ state) {
+  __shared__ double lds[EVAL_THREADS];
+  const double t = acc_group_tree(group_sum, groups, lds);
+  const double w = acc_group_tree(group_sum + ACC_MAX_GROUPS, groups, lds);
+  if (threadIdx.x == 0) { acc_two_sum(state, t); acc_two_sum(state + 2, w); }
+}
+
 }  // namespace gdmix
 
 using namespace gdmix;
 
 extern "C" {
+
+GDMIX_API int gdmix_re_eval_wll_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                         const float* weight, const gdmix_re_eval_wll_out* out, void* stream) {
+  if (!ctx || !out || E < 0 || N < 0) { set_error("gdmix_re_eval_wll_entities: bad argument"); return GDMIX_RE_EINVAL; }
+  if (N >= EVAL_LIMIT || E >= EVAL_LIMIT) {
+    set_error("gdmix_re_eval_wll_entities: %lld samples / %lld entities; an evaluation takes fewer than 2^31 of each", (long long)N, (long long)E);
+    return GDMIX_RE_ERANGE;
+  }
+  if (E == 0) return GDMIX_RE_OK;
+  if (!ent_row_ptr || (N > 0 && (!score || !label))) { set_error("gdmix_re_eval_wll_entities: NULL input"); return GDMIX_RE_EINVAL; }
+  gdmix_ctx_impl* ci = &ctx->impl;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(ci->device));
+  int small_max = 64;      // (the limit of term_entities above)
+  if (ci->eval_small_set) small_max = ci->eval_small_max;
+  const WllOutDev O = {out->ll_w, out->w, out->n_nan, out->n_bad_weight};
+  hipLaunchKernelGGL(eval_wll_small_kernel, dim3((unsigned)((E + 3) / 4)), dim3(64), 0, s, ent_row_ptr, E, score, label, weight, O, small_max);
+  hipLaunchKernelGGL(eval_wll_big_kernel, dim3((unsigned)E), dim3(EVAL_THREADS), 0, s, ent_row_ptr, score, label, weight, O, small_max);
+  HIP_TRY(hipGetLastError());
+  return GDMIX_RE_OK;
+}
+
+GDMIX_API int gdmix_re_eval_wll_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_wll_acc* acc, void* stream) {
+  static_assert(GDMIX_RE_EVAL_WLL_STATE_BYTES >= WLL_STATE_BYTES, "the weighted accumulator's device state");
+  return term_acc_reset("gdmix_re_eval_wll", ctx, acc, stream);
+}
+
+GDMIX_API int gdmix_re_eval_wll_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_wll_acc* acc, const float* score, const float* label, const float* weight,
+                                        int64_t N, void* stream) {
+  if (!ctx || !acc || !acc->state || N < 0 || acc->count < 0) { set_error("gdmix_re_eval_wll_acc_add: bad argument"); return GDMIX_RE_EINVAL; }
+  if (N == 0) return GDMIX_RE_OK;
+  if (acc->count + N >= EVAL_LIMIT) {
+    set_error("gdmix_re_eval_wll_acc_add: %lld + %lld samples; an evaluation takes fewer than 2^31", (long long)acc->count, (long long)N);
+    return GDMIX_RE_ERANGE;
+  }
+  if (!score || !label) { set_error("gdmix_re_eval_wll_acc_add: NULL input"); return GDMIX_RE_EINVAL; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(ctx->impl.device));
+  const int64_t groups = acc_groups(N);
+  double* state = static_cast<double*>(acc->state);
+  double* group_sum = acc_group_sums(acc->state);
+  hipLaunchKernelGGL(eval_wll_acc_add_kernel, dim3((unsigned)groups), dim3(EVAL_THREADS), 0, s, score, label, weight, N, group_sum,
+                     reinterpret_cast<unsigned long long*>(state + 4));
+  hipLaunchKernelGGL(eval_wll_acc_sum_kernel, dim3(1), dim3(EVAL_THREADS), 0, s, (const double*)group_sum, (int)groups, state);
+  HIP_TRY(hipGetLastError());
+  acc->count += N;
+  return GDMIX_RE_OK;
+}
+
+GDMIX_API int gdmix_re_eval_wll_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_wll_acc* acc, gdmix_re_eval_wll_totals* host_out, void* stream) {
+  if (!ctx || !acc || !acc->state || !host_out || acc->count < 0) { set_error("gdmix_re_eval_wll_acc_finish: bad argument"); return GDMIX_RE_EINVAL; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(ctx->impl.device));
+  double st[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  HIP_TRY(hipMemcpyAsync(st, acc->state, sizeof(st), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  uint64_t counts[2] = {0, 0};
+  memcpy(counts, &st[4], 16);
+  host_out->ll_w = st[0] + st[1];
+  host_out->w = st[2] + st[3];
+  host_out->n = acc->count;
+  host_out->n_nan = (int64_t)counts[0];
+  host_out->n_bad_weight = (int64_t)counts[1];
+  return GDMIX_RE_OK;
+}
 
 #define GDMIX_TERM_FAMILY(prefix, Term)                                                                                                               \
   GDMIX_API int prefix##_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,        \

@@ -580,6 +580,12 @@ hipError_t launch_partition_ids(const int64_t* ids, int64_t count, int32_t num_p
 void set_error(const char* fmt, ...);
 // device temporary of the context (grow-only; re_evaluate.hip): rocPRIM's temporary storage, whose size only the library can tell
 int eval_tmp(gdmix_ctx_impl* ci, size_t bytes, hipStream_t s, void** out);
+// steps of re_evaluate.hip that re_evaluate_weighted.hip takes too: the radix sort of 8-byte keys over bits [0, end_bit); the numbering
+// of a batch's sort-path entities (one prefix sum, the call's one synchronisation); the accumulator's sum over positions of stored terms
+int sort_keys(gdmix_ctx_impl* ci, uint64_t* in, uint64_t* out, int64_t M, unsigned end_bit, hipStream_t s, bool descending = false);
+int eval_number_big(gdmix_ctx_impl* ci, const char* who, const int64_t* ent_row_ptr, int64_t E, int64_t N, int small_max, int64_t* mark, int64_t* offs,
+                    int32_t* big_list, int32_t* big_off, hipStream_t s, int64_t* nbig_out, int64_t* M_out);
+int eval_sum_positions(const double* terms, int64_t M, double* group_sum, double* sum, hipStream_t s);
 
 // a HIP call inside a function of the C ABI: on failure the error text is set and the function returns GDMIX_RE_EHIP
 #define HIP_TRY(expr)                                                                        \

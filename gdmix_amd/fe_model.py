@@ -111,7 +111,8 @@ class FixedLRParams(LRParams):
     # --action=inference accepts and ignores the flag.
     coefficient_constraints: Optional[str] = None
     # not in the reference; the random-effect stage's flag of the same name (params.REParams). A fixed effect has no entities: the list
-    # holds LOGISTIC_LOSS and AUPR only, and the stage's evalSummary.json gains "logistic_loss" and "ll", "aupr" and "pr_sum". Needs metric_output_dir and
+    # holds LOGISTIC_LOSS, AUPR, WEIGHTED_AUC and WEIGHTED_LOGISTIC_LOSS only, and the stage's evalSummary.json gains "logistic_loss" and "ll", "aupr" and
+    # "pr_sum", "weighted_auc" with "two_u_w", "w_pos", "w_neg", "weighted_logistic_loss" with "ll_w", "w" (weights: the data's weight column, or ones). Needs metric_output_dir and
     # --model_type=logistic_regression; does not run with l2_reg_weights.
     evaluators: Optional[str] = None
     # the random-effect stage's flag (params.REParams). This stage's parser ignores flags it does not know, so the field exists to refuse
@@ -566,6 +567,7 @@ class FixedEffectLRModelLBFGS:
                 file_scores = fe.file_scores(shard, per_dev)
                 self._metrics.ev[which].add(file_scores, shard.y)
                 self._metrics.add_log_loss(which, file_scores, shard.y)      # (--evaluators=LOGISTIC_LOSS; nothing without it)
+                self._metrics.add_weighted(which, file_scores, shard.y, data["weight"] if data["has_weight"] else None)      # (WEIGHTED_AUC, WEIGHTED_LOGISTIC_LOSS)
             per_coord = fe.to_host(per_dev)
         else:
             fe = self._solver()

@@ -7,6 +7,9 @@ not evaluate.
 
 AUPR (include/gdmix_re.h, "AUPR"): AuprEvaluator returns the device's fixed-shape fp64 sum of the trapezoid's terms and the counts, per entity
 and over the keys a DeviceEvaluator has accumulated; aupr_from_sum divides.
+
+Sample weights (include/gdmix_re.h, "weighted evaluation"): WeightedEvaluator and WeightedLogLossEvaluator take (score, label, weight) and
+return the device's fp64 sums twoU_w, W_pos, W_neg and LL_w, W; weighted_auc_from_sums divides.
 """
 import ctypes as C
 import json
@@ -21,6 +24,8 @@ from . import solver as _solver
 AUC, MSE = "auc", "mse"
 POISSON_LOSS = "poisson_loss"        # mean of exp(s) - y s: the metric of a poisson_regression stage (include/gdmix_re.h, "poisson evaluation")
 AUPR = "aupr"                        # area under the precision-recall curve (include/gdmix_re.h, "AUPR"): --evaluators=AUPR,AUPR:<id>
+WEIGHTED_AUC = "weighted_auc"                        # --evaluators=WEIGHTED_AUC,WEIGHTED_AUC:<id> (include/gdmix_re.h, "weighted evaluation")
+WEIGHTED_LOGISTIC_LOSS = "weighted_logistic_loss"    # --evaluators=WEIGHTED_LOGISTIC_LOSS
 LOGISTIC_LOSS = "logistic_loss"      # mean of the logistic loss of a score (include/gdmix_re.h, "ranking evaluation"): --evaluators=LOGISTIC_LOSS
 
 
@@ -135,6 +140,35 @@ def aupr_entities_to_host(res) -> dict:
     return h
 
 
+def weighted_auc_from_sums(two_u_w, w_pos, w_neg) -> float:
+    """weighted AUC = twoU_w / (2 W_pos W_neg), the device's operations on its fp64 sums; NaN when a weight sum is 0."""
+    two_u_w, w_pos, w_neg = float(two_u_w), float(w_pos), float(w_neg)
+    if not w_pos > 0.0 or not w_neg > 0.0:
+        return float("nan")
+    return two_u_w / (2.0 * w_pos * w_neg)
+
+
+def weighted_entities_to_host(res) -> dict:
+    """The tensors of WeightedEvaluator.entities -> numpy arrays, with `weighted_auc`: the device's auc, NaN for an entity with a NaN
+    score or a bad weight (the device wrote it NaN for an entity with a weight sum of 0)."""
+    h = {k: _solver.host_array(v) for k, v in res.items()}
+    auc = h["auc"].copy()
+    auc[(h["n_nan"] > 0) | (h["n_bad_weight"] > 0)] = np.nan
+    h[WEIGHTED_AUC] = auc
+    return h
+
+
+def weighted_logloss_entities_to_host(res) -> dict:
+    """The tensors of WeightedLogLossEvaluator.entities -> numpy arrays, with `weighted_logistic_loss` = ll_w / w (NaN for a weight sum
+    of 0, a NaN score or a bad weight)."""
+    h = {k: _solver.host_array(v) for k, v in res.items()}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = h["ll_w"] / h["w"]
+    mean[~(h["w"] > 0.0) | (h["n_nan"] > 0) | (h["n_bad_weight"] > 0)] = np.nan
+    h[WEIGHTED_LOGISTIC_LOSS] = mean
+    return h
+
+
 def poisson_entities_to_host(res) -> dict:
     """The tensors of PoissonEvaluator.entities -> numpy arrays, with `n` (every sample, NaN scores included) and `poisson_loss`
     (pl / n, NaN for an entity without samples or with a NaN score)."""
@@ -153,10 +187,11 @@ PER_ENTITY_SCHEMA = {"type": "record", "name": "EntityMetricAvro", "namespace": 
     {"name": "auc", "type": ["null", "double"]}, {"name": "mse", "type": "double"}]}
 PER_ENTITY_POISSON_SCHEMA = {"type": "record", "name": "EntityPoissonMetricAvro", "namespace": "gdmix_amd", "fields": [
     {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "poisson_loss", "type": "double"}]}
-def ranking_entity_schema(ks, aupr=False) -> dict:
-    """PER_ENTITY_SCHEMA with one nullable double per requested k behind it (null: a NaN score in the entity), and with `aupr` one more
-    for AUPR (null: a NaN score, or no positive)."""
-    more = [precision_key(k) for k in ks] + ([AUPR] if aupr else [])
+def ranking_entity_schema(ks, aupr=False, weighted_auc=False) -> dict:
+    """PER_ENTITY_SCHEMA with one nullable double per requested k behind it (null: a NaN score in the entity), with `aupr` one more
+    for AUPR (null: a NaN score, or no positive), and with `weighted_auc` one more for the weighted AUC (null: a NaN score, a bad
+    weight, or a class without weight)."""
+    more = [precision_key(k) for k in ks] + ([AUPR] if aupr else []) + ([WEIGHTED_AUC] if weighted_auc else [])
     return dict(PER_ENTITY_SCHEMA, fields=PER_ENTITY_SCHEMA["fields"] + [{"name": name, "type": ["null", "double"]} for name in more])
 
 
@@ -180,6 +215,15 @@ class _Evaluator:
         if not x.is_cuda or x.dtype != t.float32 or not x.is_contiguous():
             raise _solver.GdmixReError(f"{what} must be a contiguous float32 array on the solver's device")
         return x
+
+    def _weight(self, weight, N):
+        """-> the weights' device tensor, checked, or None (ones)"""
+        if weight is None:
+            return None
+        weight = self._f32(weight, "weight")
+        if weight.numel() != N:
+            raise _solver.GdmixReError("score and weight differ in length")
+        return weight
 
     def _pair(self, score, label):
         """-> (score, label, N), checked"""
@@ -442,6 +486,115 @@ class AuprEvaluator(_Evaluator):
                 "n": int(tot.n), "n_pos": n_pos, "n_neg": int(tot.n_neg), "n_nan": n_nan}
 
 
+class WeightedEvaluator(DeviceEvaluator):
+    """The sample-weighted rank sum on one MI355X (include/gdmix_re.h, "weighted evaluation"): `entities` per entity of a scored batch,
+    `add` ... `finish` over everything a stage scores. DeviceEvaluator's accumulator (reset, reserve, count) holding weighted words: an
+    object of this class never takes an unweighted `add`. weight None: ones."""
+    OUTPUTS = (("two_u_w", "float64"), ("w_pos", "float64"), ("w_neg", "float64"), ("n_nan", "int32"), ("n_bad_weight", "int32"), ("auc", "float64"))
+    OUT_STRUCT = _solver._EvalWOut
+    SUMMARY_KEYS = ("two_u_w", "w_pos", "w_neg")
+    ENTITY_SCHEMA = None
+    to_host = staticmethod(weighted_entities_to_host)
+
+    def entities(self, packed_or_ent_row_ptr, score, label=None, weight=None, workspace_bytes=None) -> dict:
+        """-> {"two_u_w", "w_pos", "w_neg" float64, "n_nan", "n_bad_weight" int32, "auc" float64}: device tensors, one entry per entity.
+        With a PackedBatch its labels and weights are the defaults."""
+        t, s = self.torch, self.solver
+        if weight is None and isinstance(packed_or_ent_row_ptr, _solver.PackedBatch):
+            weight = packed_or_ent_row_ptr._raw_dev.get("weight")
+        rp, score, label, E, N, res, c_out = self._entities_args(packed_or_ent_row_ptr, score, label)
+        weight = self._weight(weight, N)
+        nbytes = int(self.lib.gdmix_re_eval_w_workspace_bytes(E, N)) if workspace_bytes is None else int(workspace_bytes)
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=s.device)
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_w_entities(s._h, rp.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
+                                                             weight.data_ptr() if N and weight is not None else None, C.byref(c_out), ws.data_ptr(), nbytes,
+                                                             s._stream()), "gdmix_re_eval_w_entities")
+        return res
+
+    def add(self, score, label, weight=None):
+        score, label, N = self._pair(score, label)
+        weight = self._weight(weight, N)
+        if N == 0:
+            return
+        if self._keys is None or self._keys.numel() < self.count + N:
+            self.reserve(max(self.count + N, 2 * (self._keys.numel() if self._keys is not None else 0)))
+        s = self.solver
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_w_acc_add(s._h, C.byref(self._acc), score.data_ptr(), label.data_ptr(),
+                                                            None if weight is None else weight.data_ptr(), N, s._stream()), "gdmix_re_eval_w_acc_add")
+
+    def finish(self) -> dict:
+        """-> {"weighted_auc", "two_u_w", "w_pos", "w_neg", "n", "n_nan", "n_bad_weight"}; the weighted AUC is NaN when a score was NaN,
+        a weight bad or a class without weight. The accumulator stays as it is: more batches may follow."""
+        t, s = self.torch, self.solver
+        nbytes = int(self.lib.gdmix_re_eval_w_acc_workspace_bytes(self.count))
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=s.device)
+        tot = _solver._EvalWTotals()
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_w_acc_finish(s._h, C.byref(self._acc), ws.data_ptr(), nbytes, C.byref(tot), s._stream()),
+                           "gdmix_re_eval_w_acc_finish")
+        n_nan, n_bad = int(tot.n_nan), int(tot.n_bad_weight)
+        auc = float("nan") if n_nan > 0 or n_bad > 0 else weighted_auc_from_sums(tot.two_u_w, tot.w_pos, tot.w_neg)
+        return {WEIGHTED_AUC: auc, "two_u_w": float(tot.two_u_w), "w_pos": float(tot.w_pos), "w_neg": float(tot.w_neg), "n": int(tot.n),
+                "n_nan": n_nan, "n_bad_weight": n_bad}
+
+
+class WeightedLogLossEvaluator(_Evaluator):
+    """The sample-weighted logistic loss (include/gdmix_re.h, "weighted evaluation"; the gdmix_re_eval_wll_ entry points) with
+    PoissonEvaluator's interface and a weight: `entities`, `add` ... `finish`. weight None: ones."""
+    OUTPUTS = (("ll_w", "float64"), ("w", "float64"), ("n_nan", "int32"), ("n_bad_weight", "int32"))
+    OUT_STRUCT = _solver._EvalWllOut
+    SUMMARY_KEYS = ("ll_w", "w")
+    ENTITY_SCHEMA = None
+    to_host = staticmethod(weighted_logloss_entities_to_host)
+
+    def __init__(self, solver):
+        super().__init__(solver)
+        self._state = self.torch.empty(_solver.EVAL_WLL_STATE_BYTES, dtype=self.torch.uint8, device=solver.device)
+        self._acc = _solver._EvalPlAcc(self._state.data_ptr(), 0)
+        self.reset()
+
+    def entities(self, packed_or_ent_row_ptr, score, label=None, weight=None) -> dict:
+        """-> {"ll_w", "w" float64, "n_nan", "n_bad_weight" int32}: device tensors, one entry per entity."""
+        s = self.solver
+        if weight is None and isinstance(packed_or_ent_row_ptr, _solver.PackedBatch):
+            weight = packed_or_ent_row_ptr._raw_dev.get("weight")
+        rp, score, label, E, N, res, c_out = self._entities_args(packed_or_ent_row_ptr, score, label)
+        weight = self._weight(weight, N)
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_wll_entities(s._h, rp.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
+                                                               weight.data_ptr() if N and weight is not None else None, C.byref(c_out), s._stream()),
+                           "gdmix_re_eval_wll_entities")
+        return res
+
+    def reset(self):
+        s = self.solver
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_wll_acc_reset(s._h, C.byref(self._acc), s._stream()), "gdmix_re_eval_wll_acc_reset")
+
+    def add(self, score, label, weight=None):
+        score, label, N = self._pair(score, label)
+        weight = self._weight(weight, N)
+        if N == 0:
+            return
+        s = self.solver
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_wll_acc_add(s._h, C.byref(self._acc), score.data_ptr(), label.data_ptr(),
+                                                              None if weight is None else weight.data_ptr(), N, s._stream()), "gdmix_re_eval_wll_acc_add")
+
+    def finish(self) -> dict:
+        """-> {"weighted_logistic_loss", "ll_w", "w", "n", "n_nan", "n_bad_weight"}: LL_w / W (NaN when a score was NaN, a weight bad or
+        W is 0), the two sums, every sample added, the two counts. The accumulator stays as it is."""
+        s = self.solver
+        tot = _solver._EvalWllTotals()
+        with s._ctx_lock:
+            _solver._check(self.lib.gdmix_re_eval_wll_acc_finish(s._h, C.byref(self._acc), C.byref(tot), s._stream()), "gdmix_re_eval_wll_acc_finish")
+        n_nan, n_bad, w = int(tot.n_nan), int(tot.n_bad_weight), float(tot.w)
+        mean = float("nan") if n_nan > 0 or n_bad > 0 or not w > 0.0 else float(tot.ll_w) / w
+        return {WEIGHTED_LOGISTIC_LOSS: mean, "ll_w": float(tot.ll_w), "w": w, "n": int(tot.n), "n_nan": n_nan, "n_bad_weight": n_bad}
+
+
 EVALUATOR_OF_METRIC = {AUC: DeviceEvaluator, MSE: DeviceEvaluator, POISSON_LOSS: PoissonEvaluator}
 
 
@@ -475,7 +628,11 @@ class StageMetrics:
         "precision@K:<id>", "precision@K:<id>_records"         the mean of precision@K over the records with a sample, per requested K
         "aupr", "pr_sum"                                       AUPR over the block's samples and the device's sum (AuprEvaluator.finish)
         "aupr:<id>", "aupr:<id>_records"                       the mean of aupr over the records with a positive
-    and the records one nullable double precision_at_K per K and, for AUPR:<id>, one nullable double aupr. Each mean is math.fsum of the records' values over their number: the sum is
+        "weighted_auc", "two_u_w", "w_pos", "w_neg"            the sample-weighted AUC over the block's samples and its three sums (WeightedEvaluator.finish)
+        "weighted_logistic_loss", "ll_w", "w"                  the sample-weighted logistic loss and its two sums (WeightedLogLossEvaluator.finish)
+        "weighted_auc:<id>", "weighted_auc:<id>_records"       the mean of weighted_auc over the records with weight in both classes
+    (the weights are the batch's weight column; a stage without one takes ones)
+    and the records one nullable double precision_at_K per K, for AUPR:<id> one nullable double aupr and for WEIGHTED_AUC:<id> one nullable double weighted_auc. Each mean is math.fsum of the records' values over their number: the sum is
     exact, so the value depends on no order or grouping of partitions. Any record with a NaN score makes it NaN (null), as the stage
     metric. Without `spec` every file is byte for byte what it was."""
 
@@ -489,11 +646,26 @@ class StageMetrics:
         self.ll = {}             # which -> LogLossEvaluator (spec.log_loss)
         self.ranking = None      # RankingEvaluator (spec.ranking): one device call gives the per-entity AUC outputs and precision@k
         self.records = {}        # which -> {"nan": records with a NaN score, "auc": [values], precision_key(k): [values]}
-        self.per_entity = spec is not None and (spec.ranking or spec.aupr_entity)      # the items whose values are means over records
+        self.wev, self.wll = {}, {}      # which -> WeightedEvaluator (spec.weighted_auc), WeightedLogLossEvaluator (spec.weighted_log_loss)
+        self.per_entity = spec is not None and (spec.ranking or spec.aupr_entity or spec.weighted_auc_entity)      # the items whose values are means over records
         if spec is not None and spec.ranking:
             self.ks = spec.ks if spec.ks else (1,)      # AUC:<id> alone still takes the one call; its k is not reported
         if self.per_entity:
-            self.entity_schema = ranking_entity_schema(spec.ks, spec.aupr_entity)
+            self.entity_schema = ranking_entity_schema(spec.ks, spec.aupr_entity, spec.weighted_auc_entity)
+
+    def add_weighted(self, which, score, label, weight):
+        """--evaluators=WEIGHTED_AUC,WEIGHTED_LOGISTIC_LOSS: the scores of a batch (device) -> `which`'s weighted accumulators; weight
+        None: ones. Nothing without the items."""
+        if self.spec is None:
+            return
+        if self.spec.weighted_auc:
+            if which not in self.wev:
+                self.wev[which] = WeightedEvaluator(self.solver)
+            self.wev[which].add(score, label, weight)
+        if self.spec.weighted_log_loss:
+            if which not in self.wll:
+                self.wll[which] = WeightedLogLossEvaluator(self.solver)
+            self.wll[which].add(score, label, weight)
 
     def add_log_loss(self, which, score, label):
         """--evaluators=LOGISTIC_LOSS: the scores of a batch (device) -> `which`'s log-loss accumulator. Nothing without it."""
@@ -518,6 +690,7 @@ class StageMetrics:
         ev = self._evaluator(which)
         ev.add(logit, packed._raw_dev["y"])
         self.add_log_loss(which, logit, packed._raw_dev["y"])
+        self.add_weighted(which, logit, packed._raw_dev["y"], packed._raw_dev.get("weight"))
         if self.spec is not None and self.spec.ranking:
             if self.ranking is None:
                 self.ranking = RankingEvaluator(self.solver, self.ks)
@@ -527,11 +700,15 @@ class StageMetrics:
         if self.spec is not None and self.spec.aupr_entity:
             pr = AuprEvaluator(self.solver)
             host[AUPR] = pr.to_host(pr.entities(packed, logit))[AUPR]
+        if self.spec is not None and self.spec.weighted_auc_entity:
+            wv = WeightedEvaluator(self.solver)
+            wh = wv.to_host(wv.entities(packed, logit, weight=packed._raw_dev.get("weight")))
+            host[WEIGHTED_AUC], host["w_left_out"] = wh[WEIGHTED_AUC], (wh["n_nan"] > 0) | (wh["n_bad_weight"] > 0)
         return host
 
     def _collect(self, which, host, e0, e1):
         """The records just written -> the values the aggregates of `which` are taken over."""
-        r = self.records.setdefault(which, dict({"nan": 0, "auc": [], AUPR: []}, **{precision_key(k): [] for k in self.spec.ks}))
+        r = self.records.setdefault(which, dict({"nan": 0, "auc": [], AUPR: [], WEIGHTED_AUC: [], "w_left_out": 0}, **{precision_key(k): [] for k in self.spec.ks}))
         sl = slice(e0, e1)
         r["nan"] += int(np.count_nonzero(host["n_nan"][sl] > 0))
         both = (host["n_pos"][sl] > 0) & (host["n_neg"][sl] > 0) & (host["n_nan"][sl] == 0)
@@ -541,6 +718,10 @@ class StageMetrics:
             r[precision_key(k)].extend(host[precision_key(k)][sl][some].tolist())
         if self.spec.aupr_entity:
             r[AUPR].extend(host[AUPR][sl][(host["n_pos"][sl] > 0) & (host["n_nan"][sl] == 0)].tolist())
+        if self.spec.weighted_auc_entity:      # (weighted_auc is NaN exactly where a class has no weight or a sample was left out)
+            r["w_left_out"] += int(np.count_nonzero(host["w_left_out"][sl]))
+            v = host[WEIGHTED_AUC][sl]
+            r[WEIGHTED_AUC].extend(v[v == v].tolist())
 
     def write_entities(self, which, output_file, entity_ids, host, e0=0, e1=None):
         from .io import avro
@@ -567,7 +748,7 @@ class StageMetrics:
         if self.spec.log_loss and which in self.ll:
             r = self.ll[which].finish()
             out[LOGISTIC_LOSS], out["ll"] = _json_number(r[LOGISTIC_LOSS]), r["ll"]
-        r = self.records.get(which, {"nan": 0, "auc": [], AUPR: []})
+        r = self.records.get(which, {"nan": 0, "auc": [], AUPR: [], WEIGHTED_AUC: [], "w_left_out": 0})
         mean = lambda v: None if r["nan"] > 0 or not v else math.fsum(v) / len(v)
         if self.spec.ranking:
             if self.spec.auc:
@@ -581,6 +762,16 @@ class StageMetrics:
             out[AUPR], out["pr_sum"] = _json_number(tot[AUPR]), tot["pr_sum"]
         if self.spec.aupr_entity:
             out[f"aupr:{self.spec.entity}"], out[f"aupr:{self.spec.entity}_records"] = mean(r[AUPR]), len(r[AUPR])
+        if self.spec.weighted_auc and which in self.wev:
+            tot = self.wev[which].finish()
+            out.update({WEIGHTED_AUC: _json_number(tot[WEIGHTED_AUC]), "two_u_w": tot["two_u_w"], "w_pos": tot["w_pos"], "w_neg": tot["w_neg"]})
+        if self.spec.weighted_log_loss and which in self.wll:
+            tot = self.wll[which].finish()
+            out.update({WEIGHTED_LOGISTIC_LOSS: _json_number(tot[WEIGHTED_LOGISTIC_LOSS]), "ll_w": tot["ll_w"], "w": tot["w"]})
+        if self.spec.weighted_auc_entity:
+            v = r[WEIGHTED_AUC]
+            out[f"weighted_auc:{self.spec.entity}"] = None if r["w_left_out"] > 0 or not v else math.fsum(v) / len(v)
+            out[f"weighted_auc:{self.spec.entity}_records"] = len(v)
         return out
 
     def write_summary(self):

@@ -200,13 +200,16 @@ def parse_l2_grid(text):
 @dataclass(frozen=True)
 class EvaluatorSpec:
     """What --evaluators asks for: the logistic loss, the mean per-entity AUC, precision@k for these k (in the order given), the stage-wide
-    AUPR and the mean per-entity AUPR."""
+    AUPR and the mean per-entity AUPR, and the sample-weighted AUC (stage-wide, mean per entity) and logistic loss."""
     log_loss: bool = False
     auc: bool = False
     ks: tuple = ()
     entity: Optional[str] = None
     aupr: bool = False             # AUPR
     aupr_entity: bool = False      # AUPR:<id>
+    weighted_auc: bool = False             # WEIGHTED_AUC
+    weighted_auc_entity: bool = False      # WEIGHTED_AUC:<id>
+    weighted_log_loss: bool = False        # WEIGHTED_LOGISTIC_LOSS
 
     @property
     def ranking(self):
@@ -218,8 +221,9 @@ MAX_PRECISION_KS = 4      # values of K in one list: what one device call ranks 
 
 def parse_evaluators(text, entity, fixed_effect=False):
     """--evaluators=LIST (Photon-ML's evaluator names, any case, comma-separated): LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, AUPR,
-    AUPR:<id>, with <id> the stage's --partition_entity (`entity`), K an integer >= 1, at most four distinct K, no item twice. A
-    fixed-effect stage takes the items that name no entity: LOGISTIC_LOSS and AUPR. -> EvaluatorSpec; ValueError for anything else."""
+    AUPR:<id>, WEIGHTED_AUC, WEIGHTED_AUC:<id>, WEIGHTED_LOGISTIC_LOSS, with <id> the stage's --partition_entity (`entity`), K an integer
+    >= 1, at most four distinct K, no item twice. A fixed-effect stage takes the items that name no entity: LOGISTIC_LOSS, AUPR,
+    WEIGHTED_AUC and WEIGHTED_LOGISTIC_LOSS. -> EvaluatorSpec; ValueError for anything else."""
     log_loss, auc, ks, seen = False, False, [], set()
     for raw in str(text).split(","):
         item = raw.strip()
@@ -235,20 +239,22 @@ def parse_evaluators(text, entity, fixed_effect=False):
             if k >= 1 << 31:
                 raise ValueError(f"--evaluators={text!r}: {item!r}: K is below 2^31")
             key = ("PRECISION", k)
-        elif kind in ("AUC", "LOGISTIC_LOSS"):
+        elif kind in ("AUC", "LOGISTIC_LOSS", "WEIGHTED_LOGISTIC_LOSS"):
             key = (kind,)
-        elif kind == "AUPR":
-            key = ("AUPR:",) if colon else ("AUPR",)      # over the stage, or the mean over its entities: two items
+        elif kind in ("AUPR", "WEIGHTED_AUC"):
+            key = (kind + ":",) if colon else (kind,)     # over the stage, or the mean over its entities: two items
         else:
-            raise ValueError(f"--evaluators={text!r}: {item!r} is none of LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, AUPR, AUPR:<id>")
-        if key[0] == "AUPR":
+            raise ValueError(f"--evaluators={text!r}: {item!r} is none of LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, AUPR, AUPR:<id>, WEIGHTED_AUC, "
+                             "WEIGHTED_AUC:<id>, WEIGHTED_LOGISTIC_LOSS")
+        if key[0] in ("AUPR", "WEIGHTED_AUC"):
             pass                                          # over all samples, of either kind of stage
-        elif key[0] == "LOGISTIC_LOSS":
+        elif key[0] in ("LOGISTIC_LOSS", "WEIGHTED_LOGISTIC_LOSS"):
             if colon:
-                raise ValueError(f"--evaluators={text!r}: {item!r}: LOGISTIC_LOSS is taken over all samples and names no entity")
+                raise ValueError(f"--evaluators={text!r}: {item!r}: {key[0]} is taken over all samples and names no entity")
         else:
             if fixed_effect:
-                raise ValueError(f"--evaluators={text!r}: {item!r}: a fixed effect has no entities (it takes LOGISTIC_LOSS and AUPR only)")
+                raise ValueError(f"--evaluators={text!r}: {item!r}: a fixed effect has no entities (it takes LOGISTIC_LOSS, AUPR, WEIGHTED_AUC and "
+                                 "WEIGHTED_LOGISTIC_LOSS only)")
             if not colon or not ident.strip():
                 raise ValueError(f"--evaluators={text!r}: {item!r} names no entity: {name.strip()}:<id>, with <id> the stage's --partition_entity")
             if entity is None or ident.strip() != entity:
@@ -264,7 +270,8 @@ def parse_evaluators(text, entity, fixed_effect=False):
             ks.append(key[1])
             if len(ks) > MAX_PRECISION_KS:
                 raise ValueError(f"--evaluators={text!r}: more than {MAX_PRECISION_KS} distinct K")
-    return EvaluatorSpec(log_loss, auc, tuple(ks), None if fixed_effect else entity, ("AUPR",) in seen, ("AUPR:",) in seen)
+    return EvaluatorSpec(log_loss, auc, tuple(ks), None if fixed_effect else entity, ("AUPR",) in seen, ("AUPR:",) in seen,
+                         ("WEIGHTED_AUC",) in seen, ("WEIGHTED_AUC:",) in seen, ("WEIGHTED_LOGISTIC_LOSS",) in seen)
 
 
 def check_evaluators(p, entity, fixed_effect=False):

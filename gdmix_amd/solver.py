@@ -108,6 +108,28 @@ class _EvalAuprTotals(C.Structure):
     _fields_ = [("pr_sum", C.c_double), ("n", C.c_int64), ("n_pos", C.c_int64), ("n_neg", C.c_int64), ("n_nan", C.c_int64)]
 
 
+# include/gdmix_re.h, "weighted evaluation"
+EVAL_W_SCAN_TILE = 4096                        # GDMIX_RE_EVAL_W_SCAN_TILE: sorted keys per workgroup of the weighted scan
+EVAL_W_BOUND = 7.5e-13                         # GDMIX_RE_EVAL_W_BOUND: the relative bound of twoU_w, W_pos, W_neg
+EVAL_WLL_STATE_BYTES = 65792                   # GDMIX_RE_EVAL_WLL_STATE_BYTES
+
+
+class _EvalWOut(C.Structure):
+    _fields_ = [("two_u_w", C.c_void_p), ("w_pos", C.c_void_p), ("w_neg", C.c_void_p), ("n_nan", C.c_void_p), ("n_bad_weight", C.c_void_p), ("auc", C.c_void_p)]
+
+
+class _EvalWTotals(C.Structure):
+    _fields_ = [("two_u_w", C.c_double), ("w_pos", C.c_double), ("w_neg", C.c_double), ("n", C.c_int64), ("n_nan", C.c_int64), ("n_bad_weight", C.c_int64)]
+
+
+class _EvalWllOut(C.Structure):
+    _fields_ = [("ll_w", C.c_void_p), ("w", C.c_void_p), ("n_nan", C.c_void_p), ("n_bad_weight", C.c_void_p)]
+
+
+class _EvalWllTotals(C.Structure):
+    _fields_ = [("ll_w", C.c_double), ("w", C.c_double), ("n", C.c_int64), ("n_nan", C.c_int64), ("n_bad_weight", C.c_int64)]
+
+
 class _DownsampleOpts(C.Structure):
     _fields_ = [("rate", C.c_double), ("seed", C.c_uint64), ("negatives_only", C.c_int32), ("reserved", C.c_int32)]
 
@@ -171,6 +193,8 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_eval_topk_workspace_bytes", "gdmix_re_eval_topk_entities",
     "gdmix_re_eval_ll_entities", "gdmix_re_eval_ll_acc_reset", "gdmix_re_eval_ll_acc_add", "gdmix_re_eval_ll_acc_finish",
     "gdmix_re_eval_aupr_workspace_bytes", "gdmix_re_eval_aupr_entities", "gdmix_re_eval_aupr_acc_workspace_bytes", "gdmix_re_eval_aupr_acc_finish",
+    "gdmix_re_eval_w_workspace_bytes", "gdmix_re_eval_w_entities", "gdmix_re_eval_w_acc_add", "gdmix_re_eval_w_acc_workspace_bytes", "gdmix_re_eval_w_acc_finish",
+    "gdmix_re_eval_wll_entities", "gdmix_re_eval_wll_acc_reset", "gdmix_re_eval_wll_acc_add", "gdmix_re_eval_wll_acc_finish",
     "gdmix_re_join_features", "gdmix_re_score_models_workspace_bytes", "gdmix_re_score_models",
     "gdmix_re_prior_workspace_bytes", "gdmix_re_prior_apply", "gdmix_re_prior_restore",
     "gdmix_re_feature_extent", "gdmix_re_feature_moments", "gdmix_re_feature_scale_expand",
@@ -326,6 +350,18 @@ def load_library():
     lib.gdmix_re_eval_aupr_acc_workspace_bytes.argtypes = [C.c_int64]
     lib.gdmix_re_eval_aupr_acc_workspace_bytes.restype = C.c_size_t
     lib.gdmix_re_eval_aupr_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalAcc), C.c_void_p, C.c_size_t, C.POINTER(_EvalAuprTotals), C.c_void_p]
+    lib.gdmix_re_eval_w_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.gdmix_re_eval_w_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_eval_w_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_EvalWOut), C.c_void_p,
+                                             C.c_size_t, C.c_void_p]
+    lib.gdmix_re_eval_w_acc_add.argtypes = [C.c_void_p, C.POINTER(_EvalAcc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.gdmix_re_eval_w_acc_workspace_bytes.argtypes = [C.c_int64]
+    lib.gdmix_re_eval_w_acc_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_eval_w_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalAcc), C.c_void_p, C.c_size_t, C.POINTER(_EvalWTotals), C.c_void_p]
+    lib.gdmix_re_eval_wll_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_EvalWllOut), C.c_void_p]
+    lib.gdmix_re_eval_wll_acc_reset.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.c_void_p]
+    lib.gdmix_re_eval_wll_acc_add.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.gdmix_re_eval_wll_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.POINTER(_EvalWllTotals), C.c_void_p]
     lib.gdmix_re_join_features.argtypes = [C.c_void_p, C.POINTER(_Packed), C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gdmix_re_score_models_workspace_bytes.argtypes = [C.c_int64, C.c_int]
     lib.gdmix_re_score_models_workspace_bytes.restype = C.c_size_t

@@ -570,7 +570,8 @@ GDMIX_API const char* gdmix_re_class_kernel_name(int c);
  * The device returns the INTEGERS and the fp64 SSE; the global division is the caller's, from exact integers. Per entity the device also
  * writes auc[e] = (double)twoU / (2.0 * (double)n_pos * (double)n_neg), one division of exactly converted integers: exact (correctly
  * rounded) for entities below 2^26 samples — a caller redoes the division for larger ones.
- * Out of scope: sample weights in the metric; RMSE (the Poisson loss, precision@k, the logistic loss and AUPR have sections of their own
+ * Out of scope: sample weights in THIS section's metrics (the weighted AUC and the weighted logistic loss have a section of their own below,
+ * "weighted evaluation"); RMSE (the Poisson loss, precision@k, the logistic loss and AUPR have sections of their own
  * below); combining the accumulators of several workers (each worker
  * finishes its own; from the counts a caller can combine MSE exactly and AUC not at all). */
 typedef struct {          /* device pointers, [E] each; any may be NULL */
@@ -768,6 +769,93 @@ GDMIX_API int gdmix_re_eval_aupr_entities(gdmix_re_ctx* ctx, const int64_t* ent_
 GDMIX_API size_t gdmix_re_eval_aupr_acc_workspace_bytes(int64_t N);      /* N = acc->count */
 GDMIX_API int gdmix_re_eval_aupr_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_acc* acc, void* workspace, size_t workspace_bytes,
                                             gdmix_re_eval_aupr_totals* host_out, void* stream);
+
+/* ---- (ABI 27, additions) weighted evaluation: sample-weighted AUC and logistic loss, per entity and over a whole stage ------------------------
+ * What Photon-ML's evaluators report on data with a weight column: they are taken over (score, label, weight). The sections above stay
+ * unweighted. csrc/re_evaluate_weighted.hip (the rank sum), csrc/re_evaluate_poisson.hip (the weighted log loss, next to its term).
+ *
+ * Definitions, over the VALID samples, with the rules of "evaluation" for scores, keys, the label's sign and NaN scores
+ *   weight      w, the fp32 weight widened to fp64. A `weight` pointer of NULL means ones. -0.0f counts as 0.
+ *   bad weight  a weight that is NaN, infinite or negative: the sample is counted in n_bad_weight and in nothing else (its score is not looked
+ *               at: n_nan counts the NaN scores among the samples with a good weight). gdmix_amd/metrics.py reports NaN when the count is not 0.
+ *   W_pos, W_neg  the weight sums of the valid positives and negatives.
+ *   twoU_w      sum over positives i of w_i (2 sum{w_j: j negative, s_j < s_i} + sum{w_j: j negative, s_j == s_i}). Per tie group g this is
+ *               P_g (2 Nbefore_g + N_g): P_g, N_g the group's positive and negative weight, Nbefore_g the negative weight below the group.
+ *               weighted_auc = twoU_w / (2 W_pos W_neg), NaN when W_pos == 0 or W_neg == 0.
+ *   terms       x = 2 Nbefore + N (the doubling is exact: one rounding), then P x (one rounding): the sort path forms one such term per tie
+ *               group, the register path one per positive sample, w_i (2 below_i + at_i), with the same two operations. Never fused.
+ *   LL_w, W     LL_w = sum_i w_i ce(s_i, y_i), ce as "ranking evaluation" forms it, then one rounding of the product (a sample of weight 0
+ *               adds 0 whatever its score, an infinite one included); W = sum_i w_i.
+ *               weighted_logistic_loss = LL_w / W, NaN when W == 0.
+ *   integers    with every weight a small integer all sums are exact integers in fp64: twoU_w, W_pos, W_neg then EQUAL two_u, n_pos, n_neg of the
+ *               unweighted call on the batch with every sample repeated w times, as numbers, on every path.
+ *   sums        every term is >= 0; fixed trees, never a floating-point atomic, the same bits from run to run. The sort path's scan
+ *               (GDMIX_RE_EVAL_W_SCAN_TILE keys per workgroup) is a SEGMENTED scan of non-negative numbers: no prefix is ever formed by a
+ *               subtraction. A weight passes at most 16 + 8 additions inside its tile, 2 048 + 8 over the tiles in front (2^19 tiles below 2^31
+ *               samples, 2 048 per lane), 1 + 16 to the element that reads the prefix: fewer than 2 100 roundings in P_g, N_g, Nbefore_g, W_pos
+ *               and W_neg. A term: 2 100 + 1 (x), + 2 100 + 1 (P x) = 4 202; the tree over the terms (csrc/re_eval_sum.hpp) fewer than 2 211:
+ *               6 413 roundings of 2^-53 each,
+ *                 |twoU_w - exact| <= GDMIX_RE_EVAL_W_BOUND * exact,   and the same bound (with room) for W_pos, W_neg and W.
+ *               The register path is far inside it (at most 64 + 2 + 6 roundings). The two paths add in different trees: they may differ
+ *               in the last bits, by at most twice the bound. LL_w: |LL_w - exact| <= 3e-13 * sum_i w_i ce_i + GDMIX_RE_EVAL_LL_TERM_EPS * W
+ *               (the log loss's bound with one more rounding per term; the trees of csrc/re_eval_sum.hpp).
+ *   limits      those of gdmix_re_eval_entities; error codes, the single stream synchronisation and the argument checks on an empty batch too.
+ * Per entity: entities of at most 64 samples in registers, four per wavefront (w_small_kernel: a lane holds its sample's key and weight and
+ * walks its entity's negative (key, weight) pairs through LDS in sample order, adding the weight below and at its key in fp64; xor
+ * butterflies over the entity's lanes add the terms and the weights; no sort). Larger ones: one radix sort of (entity, 33-bit key) with the
+ * weight as the value, a reduce-then-scan pass that writes one fp64 term per sorted key (0 where no tie group ends) and the segment's
+ * totals, and a workgroup per entity that adds its segment in the fixed tree. gdmix_re_set_eval_small_max moves the limit for this call too.
+ * Over a stage: the accumulator is gdmix_re_eval_acc. gdmix_re_eval_w_acc_add appends one 64-bit word per sample, the 33-bit key in the high
+ * bits and the 31 bits of the weight below its (clear) sign bit under it; a bad weight appends the word of all ones. An accumulator is
+ * weighted or unweighted for its whole life: mixing gdmix_re_eval_acc_add and gdmix_re_eval_w_acc_add on one accumulator is the caller's
+ * error and is not detected. gdmix_re_eval_acc_reset serves both. gdmix_re_eval_w_acc_finish sorts the words once (the accumulator stays as
+ * it is); the sorted array is a function of the multiset of (score, label, weight) alone, and the scan runs over it as one segment, so
+ * twoU_w, W_pos and W_neg are bit for bit independent of how the samples were split into batches and of the batches' order.
+ * The weighted log loss mirrors the gdmix_re_eval_ll_ family (four entities per wavefront up to the small limit, a workgroup above; the
+ * accumulator keeps a TwoSum (hi, lo) pair for LL_w and one for W) with a state of GDMIX_RE_EVAL_WLL_STATE_BYTES. */
+#define GDMIX_RE_EVAL_W_SCAN_TILE 4096
+#define GDMIX_RE_EVAL_W_BOUND 7.5e-13
+#define GDMIX_RE_EVAL_WLL_STATE_BYTES 65792
+typedef struct {          /* device pointers, [E] each; any may be NULL */
+  double*  two_u_w;
+  double*  w_pos;
+  double*  w_neg;
+  int32_t* n_nan;
+  int32_t* n_bad_weight;
+  double*  auc;           /* two_u_w / (2.0 * w_pos * w_neg), NaN when a weight sum is 0 */
+} gdmix_re_eval_w_out;
+typedef struct {          /* host */
+  double  two_u_w, w_pos, w_neg;
+  int64_t n;              /* samples added */
+  int64_t n_nan, n_bad_weight;
+} gdmix_re_eval_w_totals;
+typedef struct {          /* device pointers, [E] each; any may be NULL */
+  double*  ll_w;
+  double*  w;
+  int32_t* n_nan;
+  int32_t* n_bad_weight;
+} gdmix_re_eval_wll_out;
+typedef struct {          /* host */
+  double  ll_w, w;
+  int64_t n;              /* samples added */
+  int64_t n_nan, n_bad_weight;
+} gdmix_re_eval_wll_totals;
+typedef gdmix_re_eval_pl_acc gdmix_re_eval_wll_acc;      /* state: GDMIX_RE_EVAL_WLL_STATE_BYTES on the device */
+GDMIX_API size_t gdmix_re_eval_w_workspace_bytes(int64_t E, int64_t N);
+GDMIX_API int gdmix_re_eval_w_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                       const float* weight /* device, may be NULL */, const gdmix_re_eval_w_out* out, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+GDMIX_API int gdmix_re_eval_w_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_acc* acc, const float* score, const float* label, const float* weight, int64_t N,
+                                      void* stream);
+GDMIX_API size_t gdmix_re_eval_w_acc_workspace_bytes(int64_t N);      /* N = acc->count */
+GDMIX_API int gdmix_re_eval_w_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_acc* acc, void* workspace, size_t workspace_bytes,
+                                         gdmix_re_eval_w_totals* host_out, void* stream);
+GDMIX_API int gdmix_re_eval_wll_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                         const float* weight, const gdmix_re_eval_wll_out* out, void* stream);
+GDMIX_API int gdmix_re_eval_wll_acc_reset(gdmix_re_ctx* ctx, gdmix_re_eval_wll_acc* acc, void* stream);
+GDMIX_API int gdmix_re_eval_wll_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_wll_acc* acc, const float* score, const float* label, const float* weight,
+                                        int64_t N, void* stream);
+GDMIX_API int gdmix_re_eval_wll_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_wll_acc* acc, gdmix_re_eval_wll_totals* host_out, void* stream);
 
 /* ---- (ABI 14) sweep: K models trained on one batch score another batch in one pass over its non-zeros ----------------------------
  * A stage that sweeps l2_reg_weight (gdmix_amd/sweep.py) solves a training partition K times and scores the validation partition under
