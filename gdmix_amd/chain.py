@@ -334,7 +334,8 @@ def run_chain(root, data, num_partitions=4, child_process=False, log=None, upper
     "l2_reg_weight" (the winner, from <root>/<stage>/metrics/sweep/evals.json) and the device metrics, the global stage's too.
     optimizer: passed to the global stage as --optimizer (stage_argv).
     entity_optimizer: passed to the two random-effect stages as --entity_optimizer (stage_argv).
-    evaluators: {stage: "LIST"}, passed to the stages listed as --evaluators (stage_argv)."""
+    evaluators: {stage: "LIST"}, passed to the stages listed as --evaluators (stage_argv). Under linear_regression and poisson_regression
+    a random-effect stage takes NDCG@K:<id> items only (the ratings are the graded labels) and still reports its mse or poisson_loss."""
     if model_type not in (LOGISTIC, LINEAR, POISSON):
         raise ValueError(f"model type {model_type!r}: the chain runs logistic_regression and linear_regression, and poisson_regression on count labels")
     if model_type == POISSON and l2_grids:

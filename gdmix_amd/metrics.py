@@ -10,6 +10,9 @@ and over the keys a DeviceEvaluator has accumulated; aupr_from_sum divides.
 
 Sample weights (include/gdmix_re.h, "weighted evaluation"): WeightedEvaluator and WeightedLogLossEvaluator take (score, label, weight) and
 return the device's fp64 sums twoU_w, W_pos, W_neg and LL_w, W; weighted_auc_from_sums divides.
+
+NDCG@K on graded labels (include/gdmix_re.h, "NDCG"): NdcgEvaluator returns the device's two discounted sums per entity and K and the three
+counts; ndcg_from_sums divides and states the null cases. The one ranking metric of a linear or Poisson stage.
 """
 import ctypes as C
 import json
@@ -26,6 +29,7 @@ POISSON_LOSS = "poisson_loss"        # mean of exp(s) - y s: the metric of a poi
 AUPR = "aupr"                        # area under the precision-recall curve (include/gdmix_re.h, "AUPR"): --evaluators=AUPR,AUPR:<id>
 WEIGHTED_AUC = "weighted_auc"                        # --evaluators=WEIGHTED_AUC,WEIGHTED_AUC:<id> (include/gdmix_re.h, "weighted evaluation")
 WEIGHTED_LOGISTIC_LOSS = "weighted_logistic_loss"    # --evaluators=WEIGHTED_LOGISTIC_LOSS
+NDCG = "ndcg"                        # --evaluators=NDCG@K:<id> (include/gdmix_re.h, "NDCG"): summary keys ndcg@K:<id>, record fields ndcg_at_K
 LOGISTIC_LOSS = "logistic_loss"      # mean of the logistic loss of a score (include/gdmix_re.h, "ranking evaluation"): --evaluators=LOGISTIC_LOSS
 
 
@@ -140,6 +144,30 @@ def aupr_entities_to_host(res) -> dict:
     return h
 
 
+def ndcg_key(k) -> str:
+    """The per-entity field of NDCG@k (an Avro name)."""
+    return f"ndcg_at_{int(k)}"
+
+
+def ndcg_from_sums(dcg, idcg, n_nan=0, n_bad_label=0) -> float:
+    """NDCG = dcg / idcg, one fp64 division of the device's two sums; NaN (null) when idcg is 0 (every gain 0, or no sample), when a label
+    was outside [0, 64] or when a score was NaN."""
+    dcg, idcg = float(dcg), float(idcg)
+    if not idcg > 0.0 or int(n_nan) > 0 or int(n_bad_label) > 0:
+        return float("nan")
+    return dcg / idcg
+
+
+def ndcg_entities_to_host(res, ks) -> dict:
+    """The tensors of NdcgEvaluator.entities -> numpy arrays, and per k `ndcg_at_<k>` [E] float64: ndcg_from_sums, entity by entity."""
+    h = {k: _solver.host_array(v) for k, v in res.items()}
+    null = ~(h["idcg"] > 0.0) | (h["n_nan"] > 0)[None, :] | (h["n_bad_label"] > 0)[None, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ndcg = np.where(null, np.nan, h["dcg"] / h["idcg"])
+    h.update({ndcg_key(k): ndcg[j] for j, k in enumerate(ks)})
+    return h
+
+
 def weighted_auc_from_sums(two_u_w, w_pos, w_neg) -> float:
     """weighted AUC = twoU_w / (2 W_pos W_neg), the device's operations on its fp64 sums; NaN when a weight sum is 0."""
     two_u_w, w_pos, w_neg = float(two_u_w), float(w_pos), float(w_neg)
@@ -187,12 +215,13 @@ PER_ENTITY_SCHEMA = {"type": "record", "name": "EntityMetricAvro", "namespace": 
     {"name": "auc", "type": ["null", "double"]}, {"name": "mse", "type": "double"}]}
 PER_ENTITY_POISSON_SCHEMA = {"type": "record", "name": "EntityPoissonMetricAvro", "namespace": "gdmix_amd", "fields": [
     {"name": "entityId", "type": "string"}, {"name": "n", "type": "long"}, {"name": "poisson_loss", "type": "double"}]}
-def ranking_entity_schema(ks, aupr=False, weighted_auc=False) -> dict:
+def ranking_entity_schema(ks, aupr=False, weighted_auc=False, ndcg_ks=(), base=PER_ENTITY_SCHEMA) -> dict:
     """PER_ENTITY_SCHEMA with one nullable double per requested k behind it (null: a NaN score in the entity), with `aupr` one more
-    for AUPR (null: a NaN score, or no positive), and with `weighted_auc` one more for the weighted AUC (null: a NaN score, a bad
-    weight, or a class without weight)."""
-    more = [precision_key(k) for k in ks] + ([AUPR] if aupr else []) + ([WEIGHTED_AUC] if weighted_auc else [])
-    return dict(PER_ENTITY_SCHEMA, fields=PER_ENTITY_SCHEMA["fields"] + [{"name": name, "type": ["null", "double"]} for name in more])
+    for AUPR (null: a NaN score, or no positive), with `weighted_auc` one more for the weighted AUC (null: a NaN score, a bad
+    weight, or a class without weight), and one ndcg_at_K per K of `ndcg_ks` (null: a NaN score, a label outside [0, 64], or no gain).
+    base: the stage metric's own schema (a Poisson stage's records are PER_ENTITY_POISSON_SCHEMA's)."""
+    more = [precision_key(k) for k in ks] + ([AUPR] if aupr else []) + ([WEIGHTED_AUC] if weighted_auc else []) + [ndcg_key(k) for k in ndcg_ks]
+    return dict(base, fields=base["fields"] + [{"name": name, "type": ["null", "double"]} for name in more])
 
 
 SUMMARY_KEYS = ("n", "n_pos", "n_neg", "n_nan", "two_u", "sse")
@@ -486,6 +515,28 @@ class AuprEvaluator(_Evaluator):
                 "n": int(tot.n), "n_pos": n_pos, "n_neg": int(tot.n_neg), "n_nan": n_nan}
 
 
+class NdcgEvaluator(_Evaluator):
+    """NDCG@K on graded labels per entity for up to four K from one device call (gdmix_re_eval_ndcg_entities through
+    REDeviceSolver.eval_ndcg_entities). ks: distinct integers in [1, 2^31). There is no stage-wide NDCG: the metric is per entity."""
+    OUTPUTS = ()
+    OUT_STRUCT = _solver._EvalNdcgOut
+
+    def __init__(self, solver, ks):
+        super().__init__(solver)
+        self.ks = tuple(int(k) for k in ks)
+        if not 1 <= len(self.ks) <= _solver.EVAL_NDCG_MAX or len(set(self.ks)) != len(self.ks) or min(self.ks) < 1 or max(self.ks) >= 1 << 31:
+            raise _solver.GdmixReError(f"NdcgEvaluator: ks = {list(ks)}; 1 .. {_solver.EVAL_NDCG_MAX} distinct integers, each in [1, 2^31)")
+
+    def to_host(self, res):
+        return ndcg_entities_to_host(res, self.ks)
+
+    def entities(self, packed_or_ent_row_ptr, score, label=None, workspace_bytes=None) -> dict:
+        """-> {"dcg", "idcg": float64 [nk, E], "n", "n_nan", "n_bad_label": int32 [E]}: device tensors. With a PackedBatch its labels are
+        the default."""
+        rp, score, label, _, _, _, _ = self._entities_args(packed_or_ent_row_ptr, score, label)
+        return self.solver.eval_ndcg_entities(rp, score, label, self.ks, workspace_bytes=workspace_bytes)
+
+
 class WeightedEvaluator(DeviceEvaluator):
     """The sample-weighted rank sum on one MI355X (include/gdmix_re.h, "weighted evaluation"): `entities` per entity of a scored batch,
     `add` ... `finish` over everything a stage scores. DeviceEvaluator's accumulator (reset, reserve, count) holding weighted words: an
@@ -631,8 +682,10 @@ class StageMetrics:
         "weighted_auc", "two_u_w", "w_pos", "w_neg"            the sample-weighted AUC over the block's samples and its three sums (WeightedEvaluator.finish)
         "weighted_logistic_loss", "ll_w", "w"                  the sample-weighted logistic loss and its two sums (WeightedLogLossEvaluator.finish)
         "weighted_auc:<id>", "weighted_auc:<id>_records"       the mean of weighted_auc over the records with weight in both classes
+        "ndcg@K:<id>", "ndcg@K:<id>_records"                   the mean of NDCG@K over the records where it is defined (a gain above 0, every label
+                                                               in [0, 64]), per requested K; the one item a linear or Poisson stage takes
     (the weights are the batch's weight column; a stage without one takes ones)
-    and the records one nullable double precision_at_K per K, for AUPR:<id> one nullable double aupr and for WEIGHTED_AUC:<id> one nullable double weighted_auc. Each mean is math.fsum of the records' values over their number: the sum is
+    and the records one nullable double precision_at_K per K, for AUPR:<id> one nullable double aupr for WEIGHTED_AUC:<id> one nullable double weighted_auc and for NDCG@K:<id> one nullable double ndcg_at_K per K. Each mean is math.fsum of the records' values over their number: the sum is
     exact, so the value depends on no order or grouping of partitions. Any record with a NaN score makes it NaN (null), as the stage
     metric. Without `spec` every file is byte for byte what it was."""
 
@@ -647,11 +700,11 @@ class StageMetrics:
         self.ranking = None      # RankingEvaluator (spec.ranking): one device call gives the per-entity AUC outputs and precision@k
         self.records = {}        # which -> {"nan": records with a NaN score, "auc": [values], precision_key(k): [values]}
         self.wev, self.wll = {}, {}      # which -> WeightedEvaluator (spec.weighted_auc), WeightedLogLossEvaluator (spec.weighted_log_loss)
-        self.per_entity = spec is not None and (spec.ranking or spec.aupr_entity or spec.weighted_auc_entity)      # the items whose values are means over records
+        self.per_entity = spec is not None and bool(spec.ranking or spec.aupr_entity or spec.weighted_auc_entity or spec.ndcg_ks)      # the items whose values are means over records
         if spec is not None and spec.ranking:
             self.ks = spec.ks if spec.ks else (1,)      # AUC:<id> alone still takes the one call; its k is not reported
         if self.per_entity:
-            self.entity_schema = ranking_entity_schema(spec.ks, spec.aupr_entity, spec.weighted_auc_entity)
+            self.entity_schema = ranking_entity_schema(spec.ks, spec.aupr_entity, spec.weighted_auc_entity, spec.ndcg_ks, base=self.evaluator.ENTITY_SCHEMA)
 
     def add_weighted(self, which, score, label, weight):
         """--evaluators=WEIGHTED_AUC,WEIGHTED_LOGISTIC_LOSS: the scores of a batch (device) -> `which`'s weighted accumulators; weight
@@ -704,13 +757,23 @@ class StageMetrics:
             wv = WeightedEvaluator(self.solver)
             wh = wv.to_host(wv.entities(packed, logit, weight=packed._raw_dev.get("weight")))
             host[WEIGHTED_AUC], host["w_left_out"] = wh[WEIGHTED_AUC], (wh["n_nan"] > 0) | (wh["n_bad_weight"] > 0)
+        if self.spec is not None and self.spec.ndcg_ks:
+            nd = NdcgEvaluator(self.solver, self.spec.ndcg_ks)
+            nh = nd.to_host(nd.entities(packed, logit))
+            host.update({ndcg_key(k): nh[ndcg_key(k)] for k in self.spec.ndcg_ks})
         return host
 
     def _collect(self, which, host, e0, e1):
         """The records just written -> the values the aggregates of `which` are taken over."""
-        r = self.records.setdefault(which, dict({"nan": 0, "auc": [], AUPR: [], WEIGHTED_AUC: [], "w_left_out": 0}, **{precision_key(k): [] for k in self.spec.ks}))
+        r = self.records.setdefault(which, dict({"nan": 0, "auc": [], AUPR: [], WEIGHTED_AUC: [], "w_left_out": 0}, **{precision_key(k): [] for k in self.spec.ks},
+                                                **{ndcg_key(k): [] for k in self.spec.ndcg_ks}))
         sl = slice(e0, e1)
         r["nan"] += int(np.count_nonzero(host["n_nan"][sl] > 0))
+        for k in self.spec.ndcg_ks:      # (ndcg_at_K is NaN exactly where it is not defined)
+            v = host[ndcg_key(k)][sl]
+            r[ndcg_key(k)].extend(v[v == v].tolist())
+        if "n_pos" not in host:          # a Poisson stage's records: the items above are all it takes
+            return
         both = (host["n_pos"][sl] > 0) & (host["n_neg"][sl] > 0) & (host["n_nan"][sl] == 0)
         r["auc"].extend(host["auc"][sl][both].tolist())
         some = (host["n"][sl] >= 1) & (host["n_nan"][sl] == 0)
@@ -742,7 +805,7 @@ class StageMetrics:
 
     def _aggregates(self, which) -> dict:
         """The block's keys of --evaluators for `which` (in a fixed order: the log loss, the mean AUC, precision@k as listed, AUPR, the
-        mean AUPR)."""
+        mean AUPR, the weighted items, NDCG@K as listed)."""
         import math
         out = {}
         if self.spec.log_loss and which in self.ll:
@@ -772,6 +835,9 @@ class StageMetrics:
             v = r[WEIGHTED_AUC]
             out[f"weighted_auc:{self.spec.entity}"] = None if r["w_left_out"] > 0 or not v else math.fsum(v) / len(v)
             out[f"weighted_auc:{self.spec.entity}_records"] = len(v)
+        for k in self.spec.ndcg_ks:
+            v = r.get(ndcg_key(k), [])
+            out[f"ndcg@{k}:{self.spec.entity}"], out[f"ndcg@{k}:{self.spec.entity}_records"] = mean(v), len(v)
         return out
 
     def write_summary(self):

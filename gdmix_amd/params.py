@@ -200,7 +200,8 @@ def parse_l2_grid(text):
 @dataclass(frozen=True)
 class EvaluatorSpec:
     """What --evaluators asks for: the logistic loss, the mean per-entity AUC, precision@k for these k (in the order given), the stage-wide
-    AUPR and the mean per-entity AUPR, and the sample-weighted AUC (stage-wide, mean per entity) and logistic loss."""
+    AUPR and the mean per-entity AUPR, the sample-weighted AUC (stage-wide, mean per entity) and logistic loss, and the mean per-entity
+    NDCG@K on graded labels for these K (in the order given)."""
     log_loss: bool = False
     auc: bool = False
     ks: tuple = ()
@@ -210,42 +211,50 @@ class EvaluatorSpec:
     weighted_auc: bool = False             # WEIGHTED_AUC
     weighted_auc_entity: bool = False      # WEIGHTED_AUC:<id>
     weighted_log_loss: bool = False        # WEIGHTED_LOGISTIC_LOSS
+    ndcg_ks: tuple = ()                    # NDCG@K:<id>
 
     @property
     def ranking(self):
         return self.auc or len(self.ks) > 0
 
+    @property
+    def ndcg_only(self):
+        """Nothing but NDCG@K:<id> items: the one metric that takes graded labels, so the spec runs with every --model_type."""
+        return len(self.ndcg_ks) > 0 and self == EvaluatorSpec(entity=self.entity, ndcg_ks=self.ndcg_ks)
+
 
 MAX_PRECISION_KS = 4      # values of K in one list: what one device call ranks (include/gdmix_re.h, "ranking evaluation")
+MAX_NDCG_KS = 4           # values of K of NDCG@K in one list, counted apart (include/gdmix_re.h, "NDCG")
 
 
 def parse_evaluators(text, entity, fixed_effect=False):
     """--evaluators=LIST (Photon-ML's evaluator names, any case, comma-separated): LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, AUPR,
-    AUPR:<id>, WEIGHTED_AUC, WEIGHTED_AUC:<id>, WEIGHTED_LOGISTIC_LOSS, with <id> the stage's --partition_entity (`entity`), K an integer
-    >= 1, at most four distinct K, no item twice. A fixed-effect stage takes the items that name no entity: LOGISTIC_LOSS, AUPR,
+    AUPR:<id>, WEIGHTED_AUC, WEIGHTED_AUC:<id>, WEIGHTED_LOGISTIC_LOSS, NDCG@K:<id>, with <id> the stage's --partition_entity (`entity`), K an
+    integer >= 1, at most four distinct K of each of PRECISION@K and NDCG@K, no item twice. A fixed-effect stage takes the items that name no entity: LOGISTIC_LOSS, AUPR,
     WEIGHTED_AUC and WEIGHTED_LOGISTIC_LOSS. -> EvaluatorSpec; ValueError for anything else."""
-    log_loss, auc, ks, seen = False, False, [], set()
+    log_loss, auc, ks, ndcg_ks, seen = False, False, [], [], set()
     for raw in str(text).split(","):
         item = raw.strip()
         if not item:
             raise ValueError(f"--evaluators={text!r}: an empty item")
         name, colon, ident = item.partition(":")
         kind = name.strip().upper()
-        if kind.startswith("PRECISION@"):
-            k_text = kind[len("PRECISION@"):]
+        at_k = next((head for head in ("PRECISION@", "NDCG@") if kind.startswith(head)), None)
+        if at_k:
+            k_text = kind[len(at_k):]
             if not k_text.isdigit() or int(k_text) < 1:      # (a sign, a point or nothing: not an integer >= 1)
                 raise ValueError(f"--evaluators={text!r}: {item!r}: K is an integer >= 1")
             k = int(k_text)
             if k >= 1 << 31:
                 raise ValueError(f"--evaluators={text!r}: {item!r}: K is below 2^31")
-            key = ("PRECISION", k)
+            key = (at_k[:-1], k)
         elif kind in ("AUC", "LOGISTIC_LOSS", "WEIGHTED_LOGISTIC_LOSS"):
             key = (kind,)
         elif kind in ("AUPR", "WEIGHTED_AUC"):
             key = (kind + ":",) if colon else (kind,)     # over the stage, or the mean over its entities: two items
         else:
             raise ValueError(f"--evaluators={text!r}: {item!r} is none of LOGISTIC_LOSS, AUC:<id>, PRECISION@K:<id>, AUPR, AUPR:<id>, WEIGHTED_AUC, "
-                             "WEIGHTED_AUC:<id>, WEIGHTED_LOGISTIC_LOSS")
+                             "WEIGHTED_AUC:<id>, WEIGHTED_LOGISTIC_LOSS, NDCG@K:<id>")
         if key[0] in ("AUPR", "WEIGHTED_AUC"):
             pass                                          # over all samples, of either kind of stage
         elif key[0] in ("LOGISTIC_LOSS", "WEIGHTED_LOGISTIC_LOSS"):
@@ -270,8 +279,12 @@ def parse_evaluators(text, entity, fixed_effect=False):
             ks.append(key[1])
             if len(ks) > MAX_PRECISION_KS:
                 raise ValueError(f"--evaluators={text!r}: more than {MAX_PRECISION_KS} distinct K")
+        elif key[0] == "NDCG":
+            ndcg_ks.append(key[1])
+            if len(ndcg_ks) > MAX_NDCG_KS:
+                raise ValueError(f"--evaluators={text!r}: more than {MAX_NDCG_KS} distinct K of NDCG@K")
     return EvaluatorSpec(log_loss, auc, tuple(ks), None if fixed_effect else entity, ("AUPR",) in seen, ("AUPR:",) in seen,
-                         ("WEIGHTED_AUC",) in seen, ("WEIGHTED_AUC:",) in seen, ("WEIGHTED_LOGISTIC_LOSS",) in seen)
+                         ("WEIGHTED_AUC",) in seen, ("WEIGHTED_AUC:",) in seen, ("WEIGHTED_LOGISTIC_LOSS",) in seen, tuple(ndcg_ks))
 
 
 def check_evaluators(p, entity, fixed_effect=False):
@@ -288,8 +301,9 @@ def check_evaluators(p, entity, fixed_effect=False):
 
 
 def check_evaluators_model_type(spec, model_type):
-    """--evaluators rank and weigh a probability: the stage is a logistic regression."""
-    if spec is not None and model_type != constants.LOGISTIC_REGRESSION:
+    """--evaluators rank and weigh a probability: the stage is a logistic regression. NDCG@K:<id> alone ranks graded labels and runs with
+    every model type."""
+    if spec is not None and model_type != constants.LOGISTIC_REGRESSION and not spec.ndcg_only:
         raise ValueError(f"--evaluators needs --model_type={constants.LOGISTIC_REGRESSION}: this stage is a {model_type}")
 
 

@@ -130,6 +130,16 @@ class _EvalWllTotals(C.Structure):
     _fields_ = [("ll_w", C.c_double), ("w", C.c_double), ("n", C.c_int64), ("n_nan", C.c_int64), ("n_bad_weight", C.c_int64)]
 
 
+# include/gdmix_re.h, "NDCG"
+EVAL_NDCG_MAX = 4                              # values of K in one gdmix_re_eval_ndcg_entities call
+EVAL_NDCG_SCAN_TILE = 4096                     # GDMIX_RE_EVAL_NDCG_SCAN_TILE: sorted elements per workgroup of the sort path's scan
+EVAL_NDCG_BOUND = 7.5e-13                      # GDMIX_RE_EVAL_NDCG_BOUND: the relative bound of dcg and idcg
+
+
+class _EvalNdcgOut(C.Structure):
+    _fields_ = [("dcg", C.c_void_p), ("idcg", C.c_void_p), ("n", C.c_void_p), ("n_nan", C.c_void_p), ("n_bad_label", C.c_void_p)]
+
+
 class _DownsampleOpts(C.Structure):
     _fields_ = [("rate", C.c_double), ("seed", C.c_uint64), ("negatives_only", C.c_int32), ("reserved", C.c_int32)]
 
@@ -195,6 +205,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_eval_aupr_workspace_bytes", "gdmix_re_eval_aupr_entities", "gdmix_re_eval_aupr_acc_workspace_bytes", "gdmix_re_eval_aupr_acc_finish",
     "gdmix_re_eval_w_workspace_bytes", "gdmix_re_eval_w_entities", "gdmix_re_eval_w_acc_add", "gdmix_re_eval_w_acc_workspace_bytes", "gdmix_re_eval_w_acc_finish",
     "gdmix_re_eval_wll_entities", "gdmix_re_eval_wll_acc_reset", "gdmix_re_eval_wll_acc_add", "gdmix_re_eval_wll_acc_finish",
+    "gdmix_re_eval_ndcg_workspace_bytes", "gdmix_re_eval_ndcg_entities",
     "gdmix_re_join_features", "gdmix_re_score_models_workspace_bytes", "gdmix_re_score_models",
     "gdmix_re_prior_workspace_bytes", "gdmix_re_prior_apply", "gdmix_re_prior_restore",
     "gdmix_re_feature_extent", "gdmix_re_feature_moments", "gdmix_re_feature_scale_expand",
@@ -362,6 +373,10 @@ def load_library():
     lib.gdmix_re_eval_wll_acc_reset.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.c_void_p]
     lib.gdmix_re_eval_wll_acc_add.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.gdmix_re_eval_wll_acc_finish.argtypes = [C.c_void_p, C.POINTER(_EvalPlAcc), C.POINTER(_EvalWllTotals), C.c_void_p]
+    lib.gdmix_re_eval_ndcg_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.gdmix_re_eval_ndcg_workspace_bytes.restype = C.c_size_t
+    lib.gdmix_re_eval_ndcg_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int,
+                                                C.POINTER(_EvalNdcgOut), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.gdmix_re_join_features.argtypes = [C.c_void_p, C.POINTER(_Packed), C.POINTER(_Packed), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gdmix_re_score_models_workspace_bytes.argtypes = [C.c_int64, C.c_int]
     lib.gdmix_re_score_models_workspace_bytes.restype = C.c_size_t
@@ -1279,6 +1294,25 @@ class REDeviceSolver:
                                        None if has_model is None else has_model.data_ptr(), logit.data_ptr(),
                                        per.data_ptr(), self._stream()), "gdmix_re_score")
         return logit, per
+
+    # ---- NDCG@K on graded labels (include/gdmix_re.h, "NDCG") ----------------------------------------------------------------------
+    @_serialised
+    def eval_ndcg_entities(self, ent_row_ptr, score, label, ks, workspace_bytes=None, outputs=("dcg", "idcg", "n", "n_nan", "n_bad_label")):
+        """gdmix_re_eval_ndcg_entities: ent_row_ptr [E + 1] int64, score and label [N] float32, all contiguous on this device; ks: the values
+        of K as the library takes them (it refuses what the header refuses). -> {"dcg", "idcg": float64 [nk, E], "n", "n_nan",
+        "n_bad_label": int32 [E]}, device tensors; the division is metrics.ndcg_from_sums'. `outputs`: the ones wanted (the others are
+        passed as NULL and come back as None)."""
+        t = self.torch
+        E, N, nk = int(ent_row_ptr.numel()) - 1, int(score.numel()), len(ks)
+        shape = {"dcg": ((nk, E), t.float64), "idcg": ((nk, E), t.float64), "n": ((E,), t.int32), "n_nan": ((E,), t.int32), "n_bad_label": ((E,), t.int32)}
+        res = {k: t.zeros(sh, dtype=dt, device=self.device) if k in outputs else None for k, (sh, dt) in shape.items()}
+        c_out = _EvalNdcgOut(*(res[k].data_ptr() if res[k] is not None and res[k].numel() else None for k in shape))
+        c_ks = (C.c_int32 * max(nk, 1))(*(int(k) for k in ks))
+        nbytes = int(self.lib.gdmix_re_eval_ndcg_workspace_bytes(E, N)) if workspace_bytes is None else int(workspace_bytes)
+        ws = t.empty(max(nbytes, 1), dtype=t.uint8, device=self.device)
+        _check(self.lib.gdmix_re_eval_ndcg_entities(self._h, ent_row_ptr.data_ptr(), E, N, score.data_ptr() if N else None, label.data_ptr() if N else None,
+                                                    c_ks, nk, C.byref(c_out), ws.data_ptr(), nbytes, self._stream()), "gdmix_re_eval_ndcg_entities")
+        return res
 
     # ---- incremental training: L2 centred on a prior model (include/gdmix_re.h, "incremental training") ----------------------------
     def _coef_array(self, a, P, what):

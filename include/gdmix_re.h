@@ -857,6 +857,77 @@ GDMIX_API int gdmix_re_eval_wll_acc_add(gdmix_re_ctx* ctx, gdmix_re_eval_wll_acc
                                         int64_t N, void* stream);
 GDMIX_API int gdmix_re_eval_wll_acc_finish(gdmix_re_ctx* ctx, const gdmix_re_eval_wll_acc* acc, gdmix_re_eval_wll_totals* host_out, void* stream);
 
+/* ---- (ABI 27, additions) NDCG: normalised discounted cumulative gain at K on graded labels, per entity --------------------------------------
+ * The ranking metric of a stage whose labels are grades or counts (ratings under linear_regression, counts under poisson_regression): are
+ * the items an entity rated highest ranked highest. The reference's LR path has no such metric (its DeText side names one ndcg@k); the
+ * statement below is the one this library holds itself to. csrc/re_evaluate_ndcg.hip. No ABI bump: two new symbols, nothing else moves.
+ *
+ * Definitions, per entity, for each requested K, over the entity's VALID samples
+ *   valid        a sample whose score is not NaN; a NaN score is counted in n_nan and left out. Scores compare by the key of "evaluation":
+ *                -0 equals +0, infinities order as usual.
+ *   label        y, the fp32 label widened to fp64; its domain is finite and in [0, 64] (-0 is 0). A valid sample whose label is NaN,
+ *                infinite, negative or above 64 is counted in n_bad_label, adds a gain of 0, and makes every NDCG of its entity null, as a
+ *                bad weight does for the weighted AUC. (64: the gain is exponential, and 2^64 keeps a sum of 2^31 gains far from overflow.)
+ *   gain         g(y) = 2^y - 1. y = i + f with i = floor(y): 2^i is built by the exponent. An integral label gives (2^i) - 1: exact up to
+ *                53, correctly rounded beyond. A fraction goes through the library's own exp and log (csrc/re_device.hpp: exp_any, log_1_2):
+ *                x = f ln 2, u = exp(x), m = (u - 1) x / log(u) (= 2^f - 1, with a relative error also for a tiny f; m = x when u == 1),
+ *                g = fma(2^i, m, 2^i - 1).
+ *   discount     d(r) = 1 / log2(r + 2) for the 0-based rank r, formed as ln 2 / (e ln 2 + log(m)) with r + 2 = m 2^e, m in [1, 2), the
+ *                library's own log. d(0) = 1 exactly.
+ *   DCG@K        sort the valid samples by score, descending. A tie group occupying the ranks [a, b) contributes
+ *                  (sum of g over the group / (b - a)) * sum_{r = a}^{min(b, K) - 1} d(r),
+ *                nothing when a >= K: the expectation under a uniformly random order inside tie groups — what "ties count in expectation"
+ *                is for precision@k and "ties at half weight" for AUC.
+ *   IDCG@K       sum_{r < min(K, n)} g(y_(r)) d(r) with the labels sorted descending (ties between labels do not matter).
+ *   NDCG@K       DCG@K / IDCG@K; null when IDCG@K == 0 (every gain 0, or n = 0), when n_bad_label > 0, or when n_nan > 0 (the rule
+ *                gdmix_amd/metrics.py applies to the other metrics). The device returns dcg and idcg (fp64) and the three counts; the
+ *                division and the null cases are the host's (gdmix_amd/metrics.py: ndcg_from_sums). The stage value ndcg@K:<id> is the mean
+ *                over the entities whose NDCG@K is defined, an exact sum over the per-entity records as for auc:<id>.
+ *   terms, sums  every term is >= 0 and no sum is ever formed by a subtraction (no prefix sum of discounts is differenced), so a relative
+ *                bound holds; fixed trees (csrc/re_eval_sum.hpp), never a floating-point atomic, the same bits from run to run.
+ *                Register path: the lane of rank r < K adds (G / t) d(r), G and t its tie group's gain sum and size — summed over a
+ *                group's ranks that is the group's term above. G: at most 63 additions; the term: G, one division, d, one product; the
+ *                butterfly: 6.
+ *                Sort path: one term (G / t) D per tie group, G and D = the sum of the group's discounts below K from a SEGMENTED scan
+ *                (GDMIX_RE_EVAL_NDCG_SCAN_TILE elements per workgroup) restarted at every group head. A number passes at most 16 + 8
+ *                additions inside its tile, 2 048 + 8 over the tiles in front (2^19 tiles below 2^31 samples, 2 048 per lane) and 1 + 16 to
+ *                the element that reads the sum: fewer than 2 100 roundings each in G and D. A term: 2 100 (G) + 1 (/ t) + 2 100 (D) + 1
+ *                (the product) = 4 202 roundings of 2^-53, plus the errors of one gain and one discount; the tree over the terms fewer
+ *                than 2 211: 6 413 roundings, 7.12e-13, and GDMIX_RE_EVAL_NDCG_GAIN_EPS + GDMIX_RE_EVAL_NDCG_DISC_EPS on top:
+ *                  |dcg - exact| <= GDMIX_RE_EVAL_NDCG_BOUND * exact,   and the same for idcg
+ *                (idcg: one gain, one discount, one product and the tree; far inside). The two paths add different terms in different
+ *                trees: they may differ in the last bits and both lie within the bound.
+ *   ks           host, nk of them, 1 <= nk <= 4 (counted apart from the four k of gdmix_re_eval_topk_entities), distinct, each >= 1 (and, an
+ *                int32, below 2^31): anything else is GDMIX_RE_EINVAL, checked before anything is launched, also for an empty batch.
+ *   out          device; dcg and idcg [nk][E] k-major (the values of ks[j] at [j * E, (j + 1) * E)), the counts [E]; any may be NULL.
+ *   limits       those of gdmix_re_eval_topk_entities: fewer than 2^31 samples and entities (GDMIX_RE_ERANGE), the workspace (GDMIX_RE_ENOMEM).
+ * Entities of at most 64 samples are ranked in registers, four, two or one per wavefront as in gdmix_re_eval_entities: the complemented
+ * score keys, the label keys and the fp64 gains go through LDS, a lane counts the keys above and equal to its own, the equal ones on lower
+ * lanes (a distinct rank) and adds its tie group's gains, and counts the labels above and the equal ones on lower lanes (a distinct ideal
+ * rank); the discounts of ranks 0 .. 63 are a table built once per wavefront in LDS; all K are served from the one ranking; no sort. Larger
+ * ones: one radix sort of (entity, complemented score key) with the label's bits as the value, a second radix sort of (entity, label
+ * descending) on keys only, a reduce-then-scan pass over the first array that writes one DCG term per tie group and K, a pass over the
+ * second that writes g d(r) per position, and a workgroup per entity that adds its segments in the fixed tree (idcg@K over the first
+ * min(K, n) positions). gdmix_re_set_eval_small_max moves the limit for this call too. Synchronises `stream` once, to learn how many
+ * entities take the sort path; rocPRIM's temporary storage is the context's own; gdmix_re_eval_ndcg_workspace_bytes runs on the host only.
+ * Out of scope: sample weights; a stage-wide NDCG (the metric is per entity by nature); python -m gdmix_amd.evaluate (its score files carry
+ * no entity); --l2_reg_weights (still refused with --evaluators); MRR; linear gains. */
+#define GDMIX_RE_EVAL_NDCG_SCAN_TILE 4096
+#define GDMIX_RE_EVAL_NDCG_GAIN_EPS 1.0e-15   /* max |g - exact| / exact: measured 5.635e-16 (at y = 1.64322793e-13) over 2^25 fp32 labels in (0, 64] against long double, tools/ndcg_gain_check.c on the CPU */
+#define GDMIX_RE_EVAL_NDCG_DISC_EPS 5.0e-16   /* max |d - exact| / exact: measured 2.308e-16 (at r = 6878) over 2^23 ranks below 2^31, the same program */
+#define GDMIX_RE_EVAL_NDCG_BOUND 7.5e-13
+typedef struct {           /* device; dcg / idcg [nk][E] k-major, the counts [E]; any may be NULL */
+  double*  dcg;
+  double*  idcg;
+  int32_t* n;              /* valid samples */
+  int32_t* n_nan;
+  int32_t* n_bad_label;
+} gdmix_re_eval_ndcg_out;
+GDMIX_API size_t gdmix_re_eval_ndcg_workspace_bytes(int64_t E, int64_t N);
+GDMIX_API int gdmix_re_eval_ndcg_entities(gdmix_re_ctx* ctx, const int64_t* ent_row_ptr, int64_t E, int64_t N, const float* score, const float* label,
+                                          const int32_t* ks /* host */, int nk, const gdmix_re_eval_ndcg_out* out,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- (ABI 14) sweep: K models trained on one batch score another batch in one pass over its non-zeros ----------------------------
  * A stage that sweeps l2_reg_weight (gdmix_amd/sweep.py) solves a training partition K times and scores the validation partition under
  * all K models. The models live in the TRAINING batch's coefficient index space (gdmix_re_result.theta_thr of K solves of one packed
