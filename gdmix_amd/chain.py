@@ -233,7 +233,7 @@ def stage_argv(root, stage, model_type=LOGISTIC, device_metrics=False, l2_grids=
     l2_grids: {stage: "w0,w1,..."} — a stage listed there, the global one included, sweeps l2_reg_weight itself (--l2_reg_weights) and
     reports its metric (a sweep needs the directory). None: the argv of every stage is what it was before the argument existed.
     optimizer: the global stage's --optimizer (LBFGS | TRON). None: no such flag in the argv.
-    entity_optimizer: the random-effect stages' --entity_optimizer (LBFGS | TRON). None: no such flag in the argv.
+    entity_optimizer: the random-effect stages' --entity_optimizer (LBFGS | TRON | TRON_PCG). None: no such flag in the argv.
     weighted: the stage's data carries a "weight" column (partition_stage(..., weights=...)): --weight_column_name=weight.
     evaluators: {stage: "LIST"} — a stage listed there gets --evaluators=LIST and reports its metric (the flag needs the directory)."""
     out = os.path.join(root, stage)

@@ -92,6 +92,8 @@ hipError_t wait_small(gdmix_ctx_impl* ctx, const SmallFetch& f) {
   return hipSuccess;
 }
 
+std::atomic<int> tron_pcg_contexts{0};
+
 }  // namespace gdmix
 
 using namespace gdmix;
@@ -374,6 +376,7 @@ GDMIX_API int gdmix_re_create(int hip_device, gdmix_re_ctx** out) {
   c->impl.host_pinned = nullptr;
   c->impl.wave_lds_limit = 65536;
   c->impl.tron_row_lds_limit = GDMIX_RE_TRON_ROW_LDS_DEFAULT;
+  c->impl.tron_pcg_a = 0.0;
   c->impl.kernel_mask = 7;
   c->impl.timing = 0;
   c->impl.giant_nnz = 16777216;
@@ -456,6 +459,7 @@ GDMIX_API int gdmix_re_create(int hip_device, gdmix_re_ctx** out) {
 
 GDMIX_API void gdmix_re_destroy(gdmix_re_ctx* ctx) {
   if (!ctx) return;
+  if (ctx->impl.tron_pcg_a > 0.0) tron_pcg_contexts.fetch_sub(1, std::memory_order_relaxed);
   if (ctx->impl.unique_pending && ctx->impl.unique_ev) (void)hipEventSynchronize(ctx->impl.unique_ev);   // a deferred kernel nobody waited for
   if (ctx->impl.unique_ev) (void)hipEventDestroy(ctx->impl.unique_ev);
   if (ctx->impl.grid_sync) (void)hipFree(ctx->impl.grid_sync);
@@ -548,6 +552,15 @@ GDMIX_API int gdmix_re_set_tron_row_lds_limit(gdmix_re_ctx* ctx, int nbytes) {
   if (!ctx) { set_error("ctx is NULL"); return GDMIX_RE_EINVAL; }
   if (nbytes < 0 || nbytes > WAVE_SMALL_LDS) { set_error("gdmix_re_set_tron_row_lds_limit: %d is outside [0, 20480]", nbytes); return GDMIX_RE_EINVAL; }
   ctx->impl.tron_row_lds_limit = nbytes;
+  return GDMIX_RE_OK;
+}
+
+// The value is checked before the context: a bad one is refused with its own message whatever the context is.
+GDMIX_API int gdmix_re_set_tron_preconditioner(gdmix_re_ctx* ctx, double a) {
+  if (!(a >= 0.0 && a <= 1.0)) { set_error("gdmix_re_set_tron_preconditioner: a = %g is outside [0, 1] (0: off)", a); return GDMIX_RE_EINVAL; }
+  if (!ctx) { set_error("ctx is NULL"); return GDMIX_RE_EINVAL; }
+  tron_pcg_contexts.fetch_add((a > 0.0) - (ctx->impl.tron_pcg_a > 0.0), std::memory_order_relaxed);
+  ctx->impl.tron_pcg_a = a;
   return GDMIX_RE_OK;
 }
 

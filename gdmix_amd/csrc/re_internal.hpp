@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "../../include/gdmix_re.h"
@@ -340,7 +341,12 @@ struct gdmix_ctx_impl {
   int64_t cap_plan_rows, cap_plan_entities, cap_plan_bound, cap_plan_kept, cap_plan_nnz;
   // TRON (re_tron.hip): entities whose TRON footprint is within this go four to a wavefront (gdmix_re_set_tron_row_lds_limit; 0: none)
   int tron_row_lds_limit;
+  // TRON_PCG: the preconditioner's weight a of M = (1 - a) + a diag(H) (gdmix_re_set_tron_preconditioner; 0: off, the plain TRON kernels)
+  double tron_pcg_a;
 };
+
+// contexts of this process whose preconditioner is on: gdmix_re_solve_tron_scratch_bytes takes no context (defined in re_api.hip)
+extern std::atomic<int> tron_pcg_contexts;
 
 // A few bytes from the device to the host WITHOUT a stream synchronise (round 5). The counts a pack or a solve decides its next
 // launches on used to come back by hipMemcpyAsync + hipStreamSynchronize: 40 - 140 us each between the producing kernel's end and

@@ -7,6 +7,8 @@
 //   re_tron_wave_kernel        ONE WAVEFRONT PER ENTITY: the entity's block and all solver state live in LDS for the whole solve
 //   re_tron_block_kernel       one workgroup per entity, state in a global scratch slot per workgroup, X streamed, grid-stride
 //   gdmix_re_solve_tron, gdmix_re_solve_tron_scratch_bytes
+//   Both kernels have a second instantiation per loss, <LOSS, true>: the diagonally preconditioned solve ("TRON_PCG"), nine coefficient
+//   vectors instead of seven, taken when the context's preconditioner is on (gdmix_re_set_tron_preconditioner). It has no row kernel.
 //
 // The solve itself is tron_solve<LOSS> of re_tron.hpp. No kernel of the plain solve, the elastic net or the box solve is touched, and
 // the size-class table is not involved.
@@ -21,7 +23,11 @@ namespace gdmix {
 hipError_t launch_tron_rows(const ListsArgs& a, int32_t* nhv, const int32_t* list, int count, int row_bytes, hipStream_t s);
 
 // doubles of global scratch one slot of the workgroup kernel needs: the coefficient vectors | the sample vectors | a few words
-inline size_t tron_slot_doubles(int64_t max_p, int64_t max_n) { return (size_t)TRON_P_VECTORS * max_p + (size_t)TRON_N_VECTORS * max_n + 8; }
+inline size_t tron_slot_doubles(int p_vectors, int64_t max_p, int64_t max_n) { return (size_t)p_vectors * max_p + (size_t)TRON_N_VECTORS * max_n + 8; }
+
+// what a kernel takes as its options: SolveParams, or under PCG the same with the preconditioner's weight behind it
+template <bool PCG>
+using TronParams = std::conditional_t<PCG, TronPcgParams, SolveParams>;
 
 // theta, thresholded theta, stats (what write_results of re_solve.hip writes for the plain solve), and the products
 template <class G>
@@ -45,8 +51,8 @@ __device__ __forceinline__ void tron_write_results(G& grp, const OutDev& O, int3
 // ---------------------------------------------------------------------------------------------------
 // one wavefront per entity, everything LDS-resident: one batch of coalesced staging loads, then no HBM traffic until the results
 // ---------------------------------------------------------------------------------------------------
-template <int LOSS>
-__global__ __launch_bounds__(WAVE) void re_tron_wave_kernel(BatchDev B, OutDev O, int32_t* __restrict__ nhv, SolveParams o, const double* __restrict__ theta0,
+template <int LOSS, bool PCG>
+__global__ __launch_bounds__(WAVE) void re_tron_wave_kernel(BatchDev B, OutDev O, int32_t* __restrict__ nhv, TronParams<PCG> o, const double* __restrict__ theta0,
                                                             const int32_t* __restrict__ list, int count) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = threadIdx.x;
@@ -60,7 +66,8 @@ __global__ __launch_bounds__(WAVE) void re_tron_wave_kernel(BatchDev B, OutDev O
   const int p = d + ic;
   const int64_t c0 = f0 + e * ic;
 
-  // carve-up: doubles first (8-byte aligned), then 4-byte arrays; must match solver_lds_bytes() at m = 0 with TRON_P_VECTORS and TRON_N_VECTORS
+  // carve-up: doubles first (8-byte aligned), then 4-byte arrays; must match solver_lds_bytes() at m = 0 with TRON_P_VECTORS (PCG:
+  // TRON_PCG_P_VECTORS) and TRON_N_VECTORS
   TronWork W;
   double* dp = reinterpret_cast<double*>(smem);
   W.x = dp; dp += p;
@@ -70,6 +77,7 @@ __global__ __launch_bounds__(WAVE) void re_tron_wave_kernel(BatchDev B, OutDev O
   W.s = dp; dp += p;
   W.r = dp; dp += p;
   W.d = dp; dp += p;
+  if constexpr (PCG) { W.m = dp; dp += p; W.im = dp; dp += p; }
   W.rs = dp; dp += n;
   W.dc = dp; dp += n;
   W.dt = dp; dp += n;
@@ -106,7 +114,7 @@ __global__ __launch_bounds__(WAVE) void re_tron_wave_kernel(BatchDev B, OutDev O
   grp.sync();
   EntityView P{n, d, p, ic, s_row_ptr, s_csr_col, s_csr_val, s_col_ptr, s_csc_row, s_csc_val, s_y, s_o, s_w};
   TronStats st;
-  tron_solve<LOSS>(grp, P, o, W, st);
+  tron_solve<LOSS, PCG>(grp, P, o, W, st);
   tron_write_results(grp, O, nhv, o, e, c0, p, W, st);
   if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) tron_variance_simple(grp, P, o, W.dc, O.variance + c0);
 }
@@ -115,8 +123,8 @@ __global__ __launch_bounds__(WAVE) void re_tron_wave_kernel(BatchDev B, OutDev O
 // one workgroup per entity, state in a global scratch slot, X streamed from HBM/L2. No workgroup waits for another.
 // The list is read from its end: order[last - idx] (re_lds_route_kernel fills it from the back of `order`).
 // ---------------------------------------------------------------------------------------------------
-template <int LOSS>
-__global__ __launch_bounds__(WAVE* BLOCK_NW) void re_tron_block_kernel(BatchDev B, OutDev O, int32_t* __restrict__ nhv, SolveParams o,
+template <int LOSS, bool PCG>
+__global__ __launch_bounds__(WAVE* BLOCK_NW) void re_tron_block_kernel(BatchDev B, OutDev O, int32_t* __restrict__ nhv, TronParams<PCG> o,
                                                                         const double* __restrict__ theta0, int64_t last, int count, double* scratch,
                                                                         size_t slot_doubles, int64_t max_p, int64_t max_n) {
   __shared__ double red[2 * BLOCK_NW];
@@ -139,6 +147,7 @@ __global__ __launch_bounds__(WAVE* BLOCK_NW) void re_tron_block_kernel(BatchDev 
     W.s = dp; dp += max_p;
     W.r = dp; dp += max_p;
     W.d = dp; dp += max_p;
+    if constexpr (PCG) { W.m = dp; dp += max_p; W.im = dp; dp += max_p; }
     W.rs = dp; dp += max_n;
     W.dc = dp; dp += max_n;
     W.dt = dp;
@@ -148,44 +157,61 @@ __global__ __launch_bounds__(WAVE* BLOCK_NW) void re_tron_block_kernel(BatchDev 
     EntityView P{n, d, p, ic, B.row_ptr + r0 + e, B.csr_col + z0, B.csr_val + z0, B.col_ptr + z0 + e,
                  B.csc_row + z0, B.csc_val + z0, B.y + r0, B.offset + r0, B.weight ? B.weight + r0 : nullptr};
     TronStats st;
-    tron_solve<LOSS>(grp, P, o, W, st);
+    tron_solve<LOSS, PCG>(grp, P, o, W, st);
     tron_write_results(grp, O, nhv, o, e, c0, p, W, st);
     if (o.variance_mode == GDMIX_RE_VAR_SIMPLE && O.variance) tron_variance_simple(grp, P, o, W.dc, O.variance + c0);
     grp.sync();   // the slot is reused by the next entity
   }
 }
 
-// the solve as solve_three_lists takes it
-struct TronLists {
+// the solve as solve_three_lists takes it: the wavefront and the workgroup kernel of either variant
+template <bool PCG>
+struct TronKernels {
   ListsArgs a;
   int32_t* nhv;
   int64_t max_p, max_n;
+  double pcg_a;   // PCG: the preconditioner's weight
   static constexpr const char* family = "re_tron";
-  static constexpr int p_vectors = TRON_P_VECTORS, n_vectors = TRON_N_VECTORS, m = 0;   // (no history: gdmix_re_opts.m is ignored)
-  static size_t slot_doubles(const gdmix_re_packed* b, const gdmix_re_opts*) { return tron_slot_doubles(b->max_p, b->max_n); }
+  static constexpr int p_vectors = PCG ? TRON_PCG_P_VECTORS : TRON_P_VECTORS, n_vectors = TRON_N_VECTORS, m = 0;   // (no history: gdmix_re_opts.m is ignored)
+  static size_t slot_doubles(const gdmix_re_packed* b, const gdmix_re_opts*) { return tron_slot_doubles(p_vectors, b->max_p, b->max_n); }
   static int verdict(const int32_t*) { return GDMIX_RE_OK; }
+  TronParams<PCG> params() const {
+    if constexpr (PCG) {
+      TronPcgParams q;
+      static_cast<SolveParams&>(q) = a.P;
+      q.a = pcg_a;
+      return q;
+    } else {
+      return a.P;
+    }
+  }
   hipError_t launch_wave(const int32_t* list, int count, int lds_bytes, hipStream_t s) const {
     if (count <= 0) return hipSuccess;
     return with_loss(a.P.loss, [&](auto L) {
       constexpr int LOSS = decltype(L)::value;
       static DynLdsOnce lds_attr;   // one per instantiation of this lambda, i.e. per kernel
-      if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_tron_wave_kernel<LOSS>)); rc != hipSuccess) return rc;
-      hipLaunchKernelGGL((re_tron_wave_kernel<LOSS>), dim3(count), dim3(WAVE), (size_t)lds_bytes, s, a.B, a.O, nhv, a.P, a.theta0, list, count);
+      if (hipError_t rc = lds_attr.set(reinterpret_cast<const void*>(re_tron_wave_kernel<LOSS, PCG>)); rc != hipSuccess) return rc;
+      hipLaunchKernelGGL((re_tron_wave_kernel<LOSS, PCG>), dim3(count), dim3(WAVE), (size_t)lds_bytes, s, a.B, a.O, nhv, params(), a.theta0, list, count);
       return hipGetLastError();
     });
   }
-  // the row kernel on list[0, count): four entities a wavefront, row_bytes of LDS each
-  hipError_t launch_rows(const int32_t* list, int count, int row_bytes, hipStream_t s) const { return launch_tron_rows(a, nhv, list, count, row_bytes, s); }
   hipError_t launch_block(int64_t last, int count, double* scratch, size_t slot_doubles, int slots, hipStream_t s) const {
     if (count <= 0) return hipSuccess;
     const int grid = count < slots ? count : slots;
     return with_loss(a.P.loss, [&](auto L) {
-      hipLaunchKernelGGL((re_tron_block_kernel<decltype(L)::value>), dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, a.B, a.O, nhv, a.P, a.theta0, last, count,
-                         scratch, slot_doubles, max_p, max_n);
+      hipLaunchKernelGGL((re_tron_block_kernel<decltype(L)::value, PCG>), dim3(grid), dim3(WAVE * BLOCK_NW), 0, s, a.B, a.O, nhv, params(), a.theta0, last,
+                         count, scratch, slot_doubles, max_p, max_n);
       return hipGetLastError();
     });
   }
 };
+
+// TRON: with the row kernel on list[0, count), four entities a wavefront, row_bytes of LDS each
+struct TronLists : TronKernels<false> {
+  hipError_t launch_rows(const int32_t* list, int count, int row_bytes, hipStream_t s) const { return launch_tron_rows(a, nhv, list, count, row_bytes, s); }
+};
+// TRON_PCG: no row kernel, so solve_three_lists routes with a row limit of 0
+using TronPcgLists = TronKernels<true>;
 
 }  // namespace gdmix
 
@@ -194,6 +220,8 @@ using namespace gdmix;
 extern "C" {
 
 GDMIX_API size_t gdmix_re_solve_tron_scratch_bytes(const gdmix_re_packed* batch, const gdmix_re_opts* opts) {
+  // (no context here: the two vectors count while any context of the process has the preconditioner on)
+  if (tron_pcg_contexts.load(std::memory_order_relaxed) > 0) return lists_scratch_bytes<TronPcgLists>(batch, opts);
   return lists_scratch_bytes<TronLists>(batch, opts);
 }
 
@@ -207,7 +235,9 @@ GDMIX_API int gdmix_re_solve_tron(gdmix_re_ctx* ctx, const gdmix_re_packed* b, c
   if (opts->variance_mode != GDMIX_RE_VAR_NONE && !out->variance) { set_error("variance requested but out->variance is NULL"); return GDMIX_RE_EINVAL; }
   bool empty;
   if (const int rc = begin_lists_solve(ctx, b, stream, "gdmix_re_solve_tron", &empty); rc != GDMIX_RE_OK || empty) return rc;
-  return solve_three_lists(ctx, b, opts, TronLists{lists_args(b, opts, theta0, out), nhv, b->max_p, b->max_n}, out, stream, "gdmix_re_solve_tron");
+  const double pcg_a = ctx->impl.tron_pcg_a;
+  if (pcg_a > 0.0) return solve_three_lists(ctx, b, opts, TronPcgLists{lists_args(b, opts, theta0, out), nhv, b->max_p, b->max_n, pcg_a}, out, stream, "gdmix_re_solve_tron");
+  return solve_three_lists(ctx, b, opts, TronLists{{lists_args(b, opts, theta0, out), nhv, b->max_p, b->max_n, 0.0}}, out, stream, "gdmix_re_solve_tron");
 }
 
 }  // extern "C"

@@ -584,7 +584,20 @@ class RandomEffectLRLBFGSModel:
 
     def _entity_tron(self):
         """Does the stage solve its entities by trust-region Newton (REParams.entity_optimizer)? False without the flag: the plain solve."""
-        return getattr(getattr(self, "model_params", None), "entity_optimizer", None) == "TRON"
+        return getattr(getattr(self, "model_params", None), "entity_optimizer", None) in ("TRON", "TRON_PCG")
+
+    def _entity_tron_pcg(self):
+        """... with its conjugate gradients diagonally preconditioned (--entity_optimizer=TRON_PCG)?"""
+        return getattr(getattr(self, "model_params", None), "entity_optimizer", None) == "TRON_PCG"
+
+    @staticmethod
+    def _solve_tron_pcg(solver, packed, opts, theta0=None):
+        """solve_tron with the context's preconditioner on for the length of the call (include/gdmix_re.h, "TRON_PCG")."""
+        solver.set_tron_preconditioner(getattr(solver, "TRON_PCG_A", 0.01))
+        try:
+            return solver.solve_tron(packed, opts, theta0=theta0)
+        finally:
+            solver.set_tron_preconditioner(0.0)
 
     def _read_entity_bounds(self, num_features):
         """--entity_coefficient_constraints: the file, read once per stage -> (lower, upper) [num_features] by global feature id (the order
@@ -1101,7 +1114,8 @@ class RandomEffectLRLBFGSModel:
             bounds = RandomEffectLRLBFGSModel._entity_bounds(self, solver)
             solve = lambda packed, opts, theta0=None: solver.solve(packed, opts, theta0=theta0, bounds=bounds)
         elif RandomEffectLRLBFGSModel._entity_tron(self):      # (REParams refuses it with every branch above)
-            solve = solver.solve_tron
+            pcg = RandomEffectLRLBFGSModel._entity_tron_pcg(self)
+            solve = (lambda packed, opts, theta0=None: RandomEffectLRLBFGSModel._solve_tron_pcg(solver, packed, opts, theta0)) if pcg else solver.solve_tron
         else:
             solve = solver.solve
         packed = pack()
@@ -1112,8 +1126,13 @@ class RandomEffectLRLBFGSModel:
             ended = ", ".join(f"status {int(c)}: {int(k)}" for c, k in zip(*np.unique(res["status"], return_counts=True)))
             # (the host tests' solver stand-in, tests/helpers.OracleSolverDouble, has no count record: the clause is left out there, never a 0)
             rows = f" ({solver.tron_row_count(packed)} four to a wavefront on the row kernel)" if hasattr(solver, "tron_row_count") else ""
-            logger.info(f"entity_optimizer TRON: {packed.E} entities{rows}, {res['nfev'].sum() / E:.2f} evaluations "
-                        f"and {nhv.sum() / E:.2f} Hessian-vector products per entity on average; {ended}")
+            name = "TRON"
+            if RandomEffectLRLBFGSModel._entity_tron_pcg(self):      # (no row kernel under the preconditioner: the row limit is taken as 0)
+                name, rows = "TRON_PCG", " (row limit taken as 0: none on the row kernel)"
+            # a CG step takes one product, so the mean CG steps per entity is the mean product count; per trust-region subproblem beside it
+            logger.info(f"entity_optimizer {name}: {packed.E} entities{rows}, {res['nfev'].sum() / E:.2f} evaluations "
+                        f"and {nhv.sum() / E:.2f} Hessian-vector products per entity on average "
+                        f"({nhv.sum() / E:.2f} CG steps per entity, {nhv.sum() / max(int(res['nfev'].sum()) - int(packed.E), 1):.2f} per trust-region subproblem); {ended}")
         if (res["status"] == self.ST_ABORTED).any() and getattr(solver, "tall_team_n", 0) != 0:
             # a team of workgroups gave up waiting for a member (a device too busy, or too small, to keep four whole CUs per
             # team resident: csrc/re_solve_tall.hip). Not a reason to lose the job: the partition again with every tall

@@ -87,21 +87,22 @@ def check_elastic_net_alpha(p, stage_flags):
     return alpha
 
 
-ENTITY_OPTIMIZERS = ("LBFGS", "TRON")
+ENTITY_OPTIMIZERS = ("LBFGS", "TRON", "TRON_PCG")
 
 
 def check_entity_optimizer(p, stage_flags):
-    """--entity_optimizer of a random-effect stage's parameters: LBFGS or TRON in any case, and (for TRON) none of the stage's flags the
-    trust-region Newton solve does not run with, given as (set?, flag, why). -> "LBFGS" / "TRON", or None without the flag."""
+    """--entity_optimizer of a random-effect stage's parameters: LBFGS, TRON or TRON_PCG in any case, and (for the two TRONs) none of the
+    stage's flags the trust-region Newton solve does not run with, given as (set?, flag, why). -> the name in upper case, or None
+    without the flag."""
     if p.entity_optimizer is None:
         return None
     value = str(p.entity_optimizer).strip().upper()
     if value not in ENTITY_OPTIMIZERS:
         raise ValueError(f"--entity_optimizer={p.entity_optimizer!r}: one of {', '.join(ENTITY_OPTIMIZERS)}")
-    if value == "TRON":
+    if value != "LBFGS":
         for is_set, flag, why in stage_flags:
             if is_set:
-                raise ValueError(f"--entity_optimizer=TRON does not run with {flag}: {why}")
+                raise ValueError(f"--entity_optimizer={value} does not run with {flag}: {why}")
     return value
 
 
@@ -459,6 +460,8 @@ class REParams(LRParams):
     # Does not run with elastic_net_alpha > 0 or entity_coefficient_constraints (the objective must be smooth and unconstrained),
     # incremental_training or a feature_normalization (both are changes of variables on the packed batch and compose in principle: a
     # follow-up), l2_reg_weights or rebalance_entities. --action=inference accepts and ignores the flag.
+    # TRON_PCG: the same solve with its conjugate gradients preconditioned by M = 0.99 + 0.01 diag(H) (include/gdmix_re.h, "TRON_PCG";
+    # LIBLINEAR's tron since 2.20), for bags whose columns differ in scale by orders of magnitude. It is TRON for everything above.
     entity_optimizer: Optional[str] = None
 
     def l2_grid(self):
@@ -474,8 +477,12 @@ class REParams(LRParams):
         return check_evaluators(self, self.partition_entity)
 
     def entity_tron(self):
-        """Does --entity_optimizer ask for the trust-region Newton solve?"""
-        return self.entity_optimizer == "TRON"
+        """Does --entity_optimizer ask for the trust-region Newton solve (plain or preconditioned)?"""
+        return self.entity_optimizer in ("TRON", "TRON_PCG")
+
+    def entity_tron_pcg(self):
+        """Does --entity_optimizer ask for the diagonally preconditioned one?"""
+        return self.entity_optimizer == "TRON_PCG"
 
     def elastic_net(self):
         """(l1, l2) of the stage's solves: Photon-ML's (alpha, lambda) = (elastic_net_alpha, l2_reg_weight); (0, l2_reg_weight) without the flag."""

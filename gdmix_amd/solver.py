@@ -191,7 +191,7 @@ EXPORTED_SYMBOLS = (
     "gdmix_re_abi_version", "gdmix_re_build_id", "gdmix_re_device_shared", "gdmix_re_grid_lock_acquire", "gdmix_re_grid_lock_release", "gdmix_re_grid_lock_stats", "gdmix_re_last_error", "gdmix_re_default_opts", "gdmix_re_create",
     "gdmix_re_destroy", "gdmix_re_pack_workspace_bytes", "gdmix_re_pack", "gdmix_re_set_defer_unique", "gdmix_re_pack_join", "gdmix_re_solve",
     "gdmix_re_solve_l1", "gdmix_re_solve_l1_scratch_bytes", "gdmix_re_solve_box", "gdmix_re_solve_box_scratch_bytes",
-    "gdmix_re_solve_tron", "gdmix_re_solve_tron_scratch_bytes", "gdmix_re_set_tron_row_lds_limit",
+    "gdmix_re_solve_tron", "gdmix_re_solve_tron_scratch_bytes", "gdmix_re_set_tron_row_lds_limit", "gdmix_re_set_tron_preconditioner",
     "gdmix_re_solve_scratch_bytes", "gdmix_re_set_scratch", "gdmix_re_variance_full", "gdmix_re_set_wave_lds_limit", "gdmix_re_score",
     "gdmix_re_widen_workspace_bytes", "gdmix_re_widen", "gdmix_re_set_timing", "gdmix_re_last_solve_ms", "gdmix_re_set_kernel_mask", "gdmix_re_set_giant_nnz", "gdmix_re_set_team_nnz", "gdmix_re_set_tall_min_n", "gdmix_re_set_tall_split_n", "gdmix_re_set_tall_team_n", "gdmix_re_set_tall_mid_n", "gdmix_re_set_spread", "gdmix_re_set_narrow",
     "gdmix_fe_create", "gdmix_fe_destroy", "gdmix_fe_eval", "gdmix_fe_reduce_buffer", "gdmix_fe_step", "gdmix_fe_step_async", "gdmix_fe_step_status", "gdmix_fe_solve", "gdmix_fe_result",
@@ -277,6 +277,7 @@ def load_library():
     lib.gdmix_re_set_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.gdmix_re_set_wave_lds_limit.argtypes = [C.c_void_p, C.c_int]
     lib.gdmix_re_set_tron_row_lds_limit.argtypes = [C.c_void_p, C.c_int]
+    lib.gdmix_re_set_tron_preconditioner.argtypes = [C.c_void_p, C.c_double]
     lib.gdmix_re_set_kernel_mask.argtypes = [C.c_void_p, C.c_int]
     lib.gdmix_re_set_giant_nnz.argtypes = [C.c_void_p, C.c_int64]
     lib.gdmix_fe_create.argtypes = [C.c_void_p, C.POINTER(_Packed), C.c_int64, C.POINTER(_Opts), C.c_void_p,
@@ -1208,6 +1209,13 @@ class REDeviceSolver:
         """gdmix_re_set_tron_row_lds_limit: entities whose TRON footprint is within nbytes (and within the small wavefront launch's LDS) are
         solved four per wavefront by re_tron_rows_kernel. 0: none, the routing without that kernel. Refused: negative, above 20 KB."""
         _check(self.lib.gdmix_re_set_tron_row_lds_limit(self._h, int(nbytes)), "set_tron_row_lds_limit")
+
+    TRON_PCG_A = 0.01                # LIBLINEAR's weight of diag(H) in M = (1 - a) + a diag(H): what --entity_optimizer=TRON_PCG sets
+
+    def set_tron_preconditioner(self, a: float):
+        """gdmix_re_set_tron_preconditioner: 0 < a <= 1 sends solve_tron through the diagonally preconditioned kernels (include/gdmix_re.h,
+        "TRON_PCG": M = (1 - a) + a diag(H), nine coefficient vectors, no row kernel); 0, the default: plain TRON. Refused: a < 0, a > 1, NaN."""
+        _check(self.lib.gdmix_re_set_tron_preconditioner(self._h, float(a)), "set_tron_preconditioner")
 
     def tron_row_count(self, packed: PackedBatch):
         """Entities the row kernel took in the last TRON solve on this batch, from the count record as tron_counts (they are in tron_counts'

@@ -448,6 +448,42 @@ GDMIX_API size_t gdmix_re_solve_tron_scratch_bytes(const gdmix_re_packed* batch,
 #define GDMIX_RE_TRON_ROW_LDS_DEFAULT 6144
 GDMIX_API int gdmix_re_set_tron_row_lds_limit(gdmix_re_ctx* ctx, int nbytes);
 
+/* ---- TRON_PCG: TRON with diagonally preconditioned conjugate gradients (no ABI bump: one new symbol, gdmix_re_opts does not grow) ----
+ * --entity_optimizer=TRON_PCG. LIBLINEAR's tron with trpcg (Hsia, Chiang and Lin, 2018; LIBLINEAR from 2.20) on the F of "TRON" above,
+ * for entities whose columns differ in scale by orders of magnitude. gdmix_re_set_tron_preconditioner(ctx, a) with 0 < a <= 1 turns it on
+ * for the gdmix_re_solve_tron calls of that context, a = 0 (the default) turns it off; LIBLINEAR's a is 0.01.
+ * Preconditioner. At every accepted point (the start point included), with D of that point:
+ *     H_jj = (1/n) ( sum_k D_row(k) x_k^2 + l2 [j in R] ),   M_j = max( (1 - a) + a H_jj, 1e-12 )
+ *   the sum over column j's CSC entries in storage order (two entries of one matrix cell are two terms); the intercept's column is all
+ *   ones, H_00 = (1/n) ( sum_i D_i + l2 [0 in R] ), R as for the gradient. A rejected trial leaves M as it leaves D.
+ * Outer loop: TRON's, word for word (eta, sigma, the clamp of Delta before the first accepted step, acceptance, the stops and their
+ *   order, the status codes, nit / nfev / nhv), with two norms replaced: Delta_0 = sqrt(g' M^-1 g), and the step norm of the radius
+ *   updates is |s|_M = sqrt(sum_j M_j s_j^2). prered = -(g's - s'r) / 2 with r the CG residual, as in TRON.
+ * Preconditioned CG on the model at (x, g, D, M): s = 0, r = -g, z = r / M, d = z, rho = r'z (= g' M^-1 g). Per step, after h = H d
+ *   (one product, counted in nhv), six sums in one reduction:
+ *     d'h,  z'h = sum r_j h_j / M_j,  h' M^-1 h,  s'Md,  s'Ms,  d'Md
+ *   alpha = rho / d'h. If not d'h > 0, or s'Ms + 2 alpha s'Md + alpha^2 d'Md > Delta^2: to the boundary |s + tau d|_M = Delta,
+ *     gap = max(Delta^2 - s'Ms, 0), rad = sqrt((s'Md)^2 + d'Md gap), tau = gap / (s'Md + rad) if s'Md >= 0 else (rad - s'Md) / d'Md,
+ *     s += tau d, r -= tau h, and CG ends. Otherwise rho+ = max(rho - 2 alpha z'h + alpha^2 h'M^-1 h, 0) — the new r'z, known before the
+ *     update —, s += alpha d, r -= alpha h; CG ends if sqrt(rho+) <= 0.1 sqrt(g' M^-1 g) or after GDMIX_FE_TRON_MAX_CG steps; else
+ *     d = r / M + (rho+ / rho) d, rho = rho+.
+ *   Nothing is divided in a step: 1 / M_j is taken once per accepted point and stored beside M_j; z is never stored (z_j = r_j (1 / M_j)
+ *   where a pass needs it).
+ * Kernels: re_tron_wave_kernel<LOSS, true> and re_tron_block_kernel<LOSS, true>, TRON's two with nine coefficient vectors instead of
+ *   seven (M and 1 / M): the LDS footprint is 8 (9 p + 3 n) + 4 (4 nnz + (n + 1) + (d + 1) + (2 | 3) n) bytes rounded up to 16 — routing, the
+ *   20 KB list and the launches' LDS take that figure —, a scratch slot 9 max_p + 3 max_n + 8 doubles. There is no four-per-wavefront
+ *   kernel under the preconditioner: the TRON row limit is taken as 0 whatever it is set to. Order of the sums: rows and columns as in
+ *   TRON; across threads ONE order for both kernels, the workgroup kernel's — element t + 256 k belongs to partial sum t (0 <= t < 256),
+ *   added in the order of k; the partials 64 w .. 64 w + 63 are added by the wavefront tree, the four results as ((0 + 1) + 2) + 3. The
+ *   workgroup kernel's thread t keeps partial t; a lane of the wavefront kernel keeps the four partials lane + 64 w. So an entity's result
+ *   is the same bits on either kernel and wherever it sits, and gdmix_re_set_wave_lds_limit changes no bit of a TRON_PCG solve.
+ *   The sum of D for H_00 rides as a fourth value in the evaluation's reduction; M, 1 / M, |g|_inf and g' M^-1 g come from one column
+ *   pass per accepted point, which costs no exp, log or reciprocal per sample and one division per coefficient.
+ * gdmix_re_set_tron_preconditioner refuses with GDMIX_RE_EINVAL, the value first: a < 0, a > 1 or NaN (the message names the value), then
+ *   a NULL ctx. gdmix_re_solve_tron_scratch_bytes takes no context: it counts nine vectors while any context of the process has the
+ *   preconditioner on, seven otherwise (and with less scratch the workgroup kernel runs on as many slots as fit, as above). */
+GDMIX_API int gdmix_re_set_tron_preconditioner(gdmix_re_ctx* ctx, double a);
+
 /* Score: logit[i] = x_i . theta_e + offset[i] (fp64 accumulate, stored fp32 as the score Avro
  * does, io_utils.py:367-375), logit_per_coord[i] = logit[i] - offset[i] (job_consumers.py:145-150).
  * has_model: [E] uint8, 0 => entity has no model and logit = offset (job_consumers.py:145-146);

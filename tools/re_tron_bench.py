@@ -19,7 +19,14 @@ a row limit of 0 (the routing without that kernel), 6, 8 and 10 KB, and the plai
 the median of the timed solves with [min, max], the share of entities on the row kernel, evaluations and products per entity, ms per pass.
 --parent DIR names a tree that holds another build of the package (DIR/gdmix_amd with its library, e.g. the parent commit's): its TRON
 solve, as that build routes it by default, is timed on the same batch by a child process right behind the others, on the same device in the
-same session. --parent-label says in the output what that build is (the directory's name otherwise); both options may be given several times."""
+same session. --parent-label says in the output what that build is (the directory's name otherwise); both options may be given several times.
+
+    python tools/re_tron_bench.py --pcg [--steps 7] [--out profiles/re_tron_pcg.txt]
+
+The preconditioned solve (set_tron_preconditioner(0.01): "TRON_PCG") next to TRON on two batches in one process, the legs in alternation: the
+C2-shaped batch, and the same batch with every global column's values multiplied by 10^u, u uniform in [-3, 3]. Legs: TRON as shipped
+(default row limit), TRON under a row limit of 0 (the routing TRON_PCG has: it has no row kernel), TRON_PCG. For each: median [min, max] ms
+per solve, evaluations, products (= CG steps: a step takes one product) per entity, CG steps per trust-region subproblem, ms per pass."""
 import argparse
 import os
 import sys
@@ -186,6 +193,49 @@ def measure_rows(E, steps, warmup, parents):
     return lines
 
 
+def measure_pcg(E, steps, warmup):
+    import dataclasses
+    b, solver, packed, opts = _c2(E)
+    scale = (10.0 ** np.random.default_rng(5).uniform(-3.0, 3.0, 1024)).astype(np.float32)
+    b2 = dataclasses.replace(b, val=(b.val * scale[b.col_global]).astype(np.float32))
+    lines = [f"C2-shaped synthetic batch (make_survey_batch({E}, 16, 4, 1024, seed=C2_SEED)): {packed.E} entities, {b.N} samples, {b.Z} non-zeros, {packed.P} coefficients",
+             f"logistic, l2 = 1, stage tolerances (pgtol 1e-5, ftol 1e-12, max_iter 100); median [min, max] of {steps} timed solves after {warmup} warm-up "
+             f"solves, the legs in alternation in one process; a = {solver.TRON_PCG_A}", ""]
+    legs = {"TRON, default row limit": (solver.TRON_ROW_LDS_DEFAULT, 0.0), "TRON, row limit 0": (0, 0.0), "TRON_PCG": (solver.TRON_ROW_LDS_DEFAULT, solver.TRON_PCG_A)}
+    for what, batch in (("plain C2", b), ("C2 with its columns rescaled over 1e-3 .. 1e3 (10^u per global column, u uniform, seed 5)", b2)):
+        pk = packed if batch is b else solver.pack(batch, has_intercept=True)
+        ms, last = {k: [] for k in legs}, {}
+        for step in range(warmup + steps):
+            for k, (limit, a) in legs.items():
+                solver.set_tron_row_lds_limit(limit)
+                solver.set_tron_preconditioner(a)
+                t, last[k] = _timed(lambda: solver.solve_tron(pk, opts))
+                if step >= warmup:
+                    ms[k].append(t)
+        solver.set_tron_preconditioner(0.0)
+        solver.set_tron_row_lds_limit(solver.TRON_ROW_LDS_DEFAULT)
+        lines.append(f"{what}:")
+        for k in legs:
+            r = last[k].to_host()
+            nfev, nhv = float(r["nfev"].mean()), float(r["nhv"].mean())
+            lines.append(f"  {k}: {_spread(ms[k])}; evaluations per entity {nfev:.2f}, products (CG steps) per entity {nhv:.2f}, CG steps per subproblem "
+                         f"{r['nhv'].sum() / max(r['nfev'].sum() - packed.E, 1):.2f}, {np.median(ms[k]) / (nfev + nhv):.3f} ms per pass; status counts "
+                         f"{np.bincount(r['status'], minlength=5).tolist()}")
+        m = {k: float(np.median(v)) for k, v in ms.items()}
+        pp = lambda k: m[k] / float(last[k].to_host()["nfev"].mean() + last[k].to_host()["nhv"].mean())
+        lines.append(f"  TRON_PCG ms per solve / TRON's: {m['TRON_PCG'] / m['TRON, default row limit']:.3f} (default row limit), {m['TRON_PCG'] / m['TRON, row limit 0']:.3f} (row limit 0); "
+                     f"ms per pass / TRON's under row limit 0: {pp('TRON_PCG') / pp('TRON, row limit 0'):.3f}")
+        if batch is b:
+            tron, _ = footprints(b, packed, opts.m)
+            n9 = tron + 16 * (np.diff(packed.ent_feat_ptr().cpu().numpy()) + 1)
+            lines.append(f"  LDS footprint per entity at nine vectors, bytes: mean {n9.mean():.0f}, median {np.median(n9):.0f}, max {n9.max()} (seven: mean {tron.mean():.0f}, max "
+                         f"{tron.max()}); {int((n9 <= SMALL_LDS).sum())} of {packed.E} within the {SMALL_LDS} B launch: {CU_LDS // SMALL_LDS} resident wavefronts per CU of "
+                         f"160 KB there — arithmetic on the launch's LDS size, not a measurement")
+        lines.append("")
+    solver.close()
+    return lines
+
+
 def main():
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     if "--package-root" in sys.argv:      # (before the package is imported: another build's tree in this one's place)
@@ -195,6 +245,7 @@ def main():
     ap.add_argument("--rows", action="store_true", help="the row kernel's measurements (profiles/re_tron_rows.txt)")
     ap.add_argument("--parent", action="append", default=[], help="with --rows: a tree with another build of the package, timed by a child process")
     ap.add_argument("--parent-label", action="append", default=[], help="what the output calls that build (default: the directory's name)")
+    ap.add_argument("--pcg", action="store_true", help="TRON_PCG next to TRON on C2 and on C2 with rescaled columns (profiles/re_tron_pcg.txt)")
     ap.add_argument("--rows-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--package-root", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--entities", type=int, default=1_000_000)
@@ -215,7 +266,13 @@ def main():
         have = torch.cuda.is_available()
     except Exception:
         have = False
-    if a.rows:
+    if a.pcg:
+        if a.out.endswith("re_tron.txt"):
+            a.out = os.path.join(os.path.dirname(a.out), "re_tron_pcg.txt")
+        head = ["Random effect, TRON with diagonally preconditioned CG (TRON_PCG: gdmix_re_set_tron_preconditioner) next to TRON: 1 x MI355X, torch events around "
+                "REDeviceSolver.solve_tron, results left on the device."]
+        lines = head + (measure_pcg(a.entities, a.steps, a.warmup) if have else ["not measured: no device"])
+    elif a.rows:
         labels = a.parent_label + [os.path.basename(os.path.normpath(d)) for d in a.parent[len(a.parent_label):]]
         parents = list(zip(a.parent, labels))
         head = ["Random effect, TRON with four entities per wavefront (re_tron_rows_kernel) next to the one-entity wavefront kernel: 1 x MI355X, torch events "
