@@ -313,6 +313,15 @@ enum { SC_FOLD = 0, SC_GDOLD = 1, SC_THETA = 2, SC_MOVED = 3 };
 // 17 registers worse without the masked regions; they are the code they were. Every other kernel runs the trip without the tests.
 constexpr bool grp_slot_tests(int g, int epl) { return g > WAVE && epl >= 4; }
 
+// Which of the other kernels keep the test on ONE site, the restore of x and g from xo / go when a line search restarts (quad_solve): the
+// EPL = 3 kernels of at most a wavefront per entity. The site runs once in thousands of trips; what it decides is the register allocation
+// of the direction loop it stands in. Restored without the test, x and g of all three slots are redefined in one block at the head of
+// that loop, and the allocator then gives d one set of registers going into a masked two-loop step and another coming out of it: three
+// 64-bit copies per step of the first loop and six per step of the second, 90 in the kernel and about 35 executed per trip at C2's
+// history of 4.5 pairs (profiles/grp_epl3_slots.txt). With the test the steps are the code they were before the dead slots. The EPL = 2,
+// 4 and 5 kernels and the wider EPL = 3 ones compile to the same vector code either way and go without it.
+constexpr bool grp_restore_test(int g, int epl) { return g <= WAVE && epl == 3; }
+
 // (The per-entity rho, alpha and scalars in the lanes of a register pair instead of LDS: slower, rejected in round 6: profiles/r06_c2_ab.txt.)
 
 // Is `v` true in any lane of the entity's group? G <= 64: from the wavefront's ballot (all lanes of a group are active
@@ -533,7 +542,7 @@ struct QuadState {
 // columns mostly hold one entry (C2's <16,4>: n <= 16) the four short loops are as fast and spill less (+ 0.5 % with the fused loop)
 // KR: how many of the M_REG pairs live in the register shift register. KR < M_REG (the EPL = 5 kernel: ten pairs of five slots would
 // be 200 VGPRs) splits the history by age: the newest KR pairs in registers as ever, and a pair that ages out of them is written ONCE
-// into a per-lane ring of M_REG - KR pairs (a private array indexed by a per-row slot, i.e. scratch memory). A push moves no old pair;
+// into a per-lane ring of M_REG - KR pairs (a private array indexed by per-row offsets, i.e. scratch memory). A push moves no old pair;
 // the ring is read only by the two-loop steps of rows whose history is longer than KR. Same pairs, same order of the steps, same
 // arithmetic: where a pair lives changes no bit. KR == M_REG is the code as it was (no ring, every `if constexpr` below folds away).
 template <int G, int EPL, bool LONG_COLS = true, int LOSS = LOSS_LOGISTIC, int KR = M_REG, bool EMPTY = true>
@@ -544,8 +553,19 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
   static_assert(KR >= 1 && KR <= M_REG, "register-resident pairs");
   constexpr int RN = M_REG - KR;
   double S[KR][EPL], Y[KR][EPL];
-  double RS[RN > 0 ? RN : 1][EPL], RY[RN > 0 ? RN : 1][EPL];   // the ring; `head`: the slot the next aged pair goes to (per row)
-  int head = 0;
+  // the ring: slot k holds s at R[k * 2 EPL + 0 .. EPL) and y behind it. Where things are is kept as BYTE offsets into R, per row, and
+  // they change only when a pair is stored: `hoff` is the slot the next aged pair goes to, roff[a] the slot of pair a < RN (the pair that
+  // aged last is a = RN - 1). A push that stores rotates them — RN register moves under the push's own mask — and the two loops below index
+  // R with them as they stand. (Derived from a slot counter where they are used, `head - (RN - a)` with a wrap and the scaling, they were
+  // loop-invariant arithmetic that the compiler computed for all RN pairs in front of the direction loop of EVERY trip: 33 vector
+  // instructions, five of them quarter-rate multiplies, for wavefronts that never read the ring, and ten address registers.)
+  constexpr int RSTRIDE = 8 * 2 * EPL;   // bytes per slot
+  double R[(RN > 0 ? RN : 1) * 2 * EPL];
+  const auto ring = [&](int off, int k) -> double& { return *reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(R) + off + 8 * k); };
+  (void)ring;
+  int roff[RN > 0 ? RN : 1], hoff = 0;
+#pragma unroll
+  for (int a = 0; a < RN; ++a) roff[a] = 0;   // (not read before a store has set them; any value here is a slot of R)
 #pragma unroll
   for (int a = 0; a < KR; ++a) {
 #pragma unroll
@@ -656,12 +676,18 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
               for (int a = 0; a < M_REG - 1; ++a) rho[a] = rho[a + 1];
               if constexpr (RN > 0) {
                 // the oldest register pair ages into the ring; one that no direction can use again (cnt < KR: it has never been
-                // within the row's last cnt pairs and every later push moves it further away; m <= KR) is not worth the stores
+                // within the row's last cnt pairs and every later push moves it further away; m <= KR) is not worth the stores, and
+                // does not move the ring either: the pairs a direction reads, the last cnt - KR that aged, were stored by cnt - KR pushes
+                // one after the other (cnt falls only to 0, and the next KR pushes store nothing), so their slots are in order
                 if (cnt >= KR && m > KR) {
+                  __builtin_assume(hoff >= 0 && hoff < RN * RSTRIDE);
 #pragma unroll
-                  for (int s = 0; s < EPL; ++s) { RS[head][s] = S[0][s]; RY[head][s] = Y[0][s]; }
+                  for (int s = 0; s < EPL; ++s) { ring(hoff, s) = S[0][s]; ring(hoff, EPL + s) = Y[0][s]; }
+#pragma unroll
+                  for (int a = 0; a < RN - 1; ++a) roff[a] = roff[a + 1];
+                  roff[RN - 1] = hoff;
+                  hoff = (hoff + RSTRIDE == RN * RSTRIDE) ? 0 : hoff + RSTRIDE;
                 }
-                head = (head + 1 == RN) ? 0 : head + 1;
               }
 #pragma unroll
               for (int a = 0; a < KR - 1; ++a) {
@@ -688,7 +714,7 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
 #pragma unroll
         for (int s = 0; s < EPL; ++s) {
           const int j = gl + G * s;
-          if (live(j)) { V.x[s] = xo[j]; V.g[s] = go[j]; }
+          if (!(TESTS || grp_restore_test(G, EPL)) || j < p) { V.x[s] = xo[j]; V.g[s] = go[j]; }   // (a dead slot: zeros either way)
         }
         f = scal[SC_FOLD];
         restart = false;
@@ -709,9 +735,8 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
       // (Zero-multiplier steps for the rows that do not use a pair, instead of masked ones: slower, rejected in round 6: profiles/r06_c2_ab.txt.)
       const int cmax = wave_max_nonneg_i32(need_dir ? cnt : 0);
       const int a0 = M_REG - cmax;
-      // ring slot of pair a < RN: the pair that aged last (a = RN - 1) sits at head - 1, the one before it at head - 2, ...
-      const auto ring_slot = [&](int a) { const int sl = head - (RN - a); return sl < 0 ? sl + RN : sl; };
-      (void)ring_slot;
+      // (the ring steps are a < RN: they lie below a0 unless a row of the wavefront that needs a direction has more than KR pairs, so
+      // the uniform bounds keep a wavefront whose rows all have cnt <= KR out of every one of them, in both loops)
 #define QUAD_FIRST_LOOP_STEP(a)                                                   \
       {                                                                           \
         if ((a) < a0) goto first_loop_done;                                       \
@@ -724,12 +749,13 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
             alpha[a] = al;                                                        \
             _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] -= al * Y[(a) - RN][s]; \
           } else {                                                                \
-            const int sl = ring_slot(a);                                          \
+            const int ro = roff[(a) < RN ? (a) : 0];                              \
+            __builtin_assume(ro >= 0 && ro < RN * RSTRIDE);                       \
             double t = 0.0;                                                       \
-            _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += RS[sl][s] * V.d[s];       \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += ring(ro, s) * V.d[s];       \
             const double al = rho[a] * grp_sum<G>(t, X);                          \
             alpha[a] = al;                                                        \
-            _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] -= al * RY[sl][s];      \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] -= al * ring(ro, EPL + s); \
           }                                                                       \
         }                                                                         \
       }
@@ -753,11 +779,12 @@ __device__ __forceinline__ void quad_solve(const QuadLds& L, const SolveParams& 
             const double c = alpha[a] - rho[a] * grp_sum<G>(t, X);                \
             _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] += c * S[(a) - RN][s];  \
           } else {                                                                \
-            const int sl = ring_slot(a);                                          \
+            const int ro = roff[(a) < RN ? (a) : 0];                              \
+            __builtin_assume(ro >= 0 && ro < RN * RSTRIDE);                       \
             double t = 0.0;                                                       \
-            _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += RY[sl][s] * V.d[s];       \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) t += ring(ro, EPL + s) * V.d[s]; \
             const double c = alpha[a] - rho[a] * grp_sum<G>(t, X);                \
-            _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] += c * RS[sl][s];       \
+            _Pragma("unroll") for (int s = 0; s < EPL; ++s) V.d[s] += c * ring(ro, s);       \
           }                                                                       \
         }                                                                         \
       }
